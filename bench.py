@@ -12,9 +12,17 @@ BASELINE.json configs[1] per GPU (BMCNet x4, 180x240 -> 720x960, bs=4/GPU, fp32,
 configs[2] (bs=32 over 8 GPUs) is exactly the N=8 point.  Inputs (events) are resident in HBM before the timed
 region.  Rank 0 prints ONE JSON line.
 
-At N = 1 the same line also carries `extra` blocks measured after the headline run (`--also config3,config4,infer,dist1`,
-the default; `--also none` skips them): BASELINE configs[3] (EventZoom 31x56, its own bf16 arithmetic, and fp32 beside it),
-the reference's literal NFS LR shape (45x80, bs 2: config/train_nfs.yml:71), configs[4]'s per-GPU shape (RGB 180x190, T = 16
+A plain run sets up, warms up, times exactly K steps and prints the line: `value` (frames/s), `ms_per_step` (one timed
+step), `metric`, `unit`, `higher_is_better`, `dtype` and the run's configuration.  `--dump-outputs DIR` writes what the
+timed step computed in its last step -- the loss and last window's MSE it returns, the model's parameters after the optimizer
+step and their gradients -- as DIR/<name>.npy (float32; over 64 MB in all, a fixed seeded sample of each array).  With the
+same arguments the inputs (seeded events, seeded initial weights) are the same on every run.
+
+Everything else the benchmark measures runs only with `--full`, after the headline run (which then starts with RCCL
+initialised, for the `dist1` block): the dominant kernel's roofline (an instrumented extra step, the step on one stream, the
+isolated launch), the same step in the bf16x6 arithmetic (`--no-bf16x6` skips it), the CPU baseline (`--no-cpu-baseline`
+skips it), and at N = 1 `extra` blocks (`--also config3,config4,infer,dist1`, the default; `--also none` skips them):
+BASELINE configs[3] (EventZoom 31x56, its own bf16 arithmetic, and fp32 beside it), the reference's literal NFS LR shape (45x80, bs 2: config/train_nfs.yml:71), configs[4]'s per-GPU shape (RGB 180x190, T = 16
 windows, 8 sequences, per-window recompute) and the streaming-inference latency per window (infer_BMCNet.py:44-68)
 with and without HIP-graph replay, and (`dist1`) the C2 step once more with the multi-GPU path's gradient reducer and an RCCL
 all-reduce over a world of one rank in the timed region.  They are short (a few steps each), labelled with their own workload strings, and
@@ -462,8 +470,9 @@ def pin_rank_to_cores(local_rank, world):
 
 
 def timed(fn, warmup, steps, use_dist, dev):
-    """W untimed + exactly K timed steps between barrier + synchronize pairs; max over ranks."""
-    loss = None
+    """W untimed + exactly K timed steps between barrier + synchronize pairs; max over ranks.  Returns the time and what the
+    last step returned."""
+    last = None
     for _ in range(warmup):
         fn()
     torch.cuda.synchronize()
@@ -472,7 +481,7 @@ def timed(fn, warmup, steps, use_dist, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(steps):
-        loss, _ = fn()
+        last = fn()
     torch.cuda.synchronize()
     if use_dist:
         dist.barrier()
@@ -482,7 +491,7 @@ def timed(fn, warmup, steps, use_dist, dev):
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = t.item()
-    return dt, loss
+    return dt, last
 
 
 def extra_train(dev, tag, B, H, W, L, math, steps, warmup, recompute=False, graph=False, use_dist=False):
@@ -492,7 +501,7 @@ def extra_train(dev, tag, B, H, W, L, math, steps, warmup, recompute=False, grap
     torch.cuda.empty_cache()
     torch.cuda.reset_peak_memory_stats(dev)
     wl = Workload(dev, B, H, W, L, 128, 5, math, recompute=recompute, graph=graph, use_dist=use_dist)
-    dt, loss = timed(wl.step, warmup, steps, use_dist, dev)
+    dt, (loss, _) = timed(wl.step, warmup, steps, use_dist, dev)
     out = {"workload": workload_string(128, 5, H, W, B, L, math, recompute=recompute, graph=graph), "dtype": DTYPE[math],
            "steps": steps, "warmup": warmup, "ms_per_step": round(dt / steps * 1e3, 2),
            "value": round(B * (L - 1) * steps / dt, 2), "unit": "LR-voxel-frames/s",
@@ -539,6 +548,36 @@ def extra_infer(dev, windows=24):
     return out
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def step_outputs(model, last):
+    """What a caller of the timed step holds after its last step: the summed loss and the last window's MSE the step returns,
+    the model's parameters after the optimizer step and the gradients that step used, as float32 arrays (timed() has
+    synchronised the device)."""
+    loss, mse = last
+    out = {"loss": loss, "mse_last_window": mse}
+    for name, p in model.named_parameters():
+        out["param." + name] = p
+        if p.grad is not None:
+            out["grad." + name] = p.grad
+    return {k: v.detach().float().cpu().numpy() for k, v in out.items()}
+
+
+def dump_outputs(arrays, d, budget=DUMP_BUDGET_BYTES):
+    """Each array as d/<name>.npy.  Over the byte budget, every array keeps the same fraction of its elements, a fixed seeded
+    sample (the same indices on every run for the same shapes), flattened."""
+    import numpy as np
+    os.makedirs(d, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    frac = budget / total if total > budget else 1.0
+    for name, a in arrays.items():
+        k = max(1, int(a.size * frac))
+        if k < a.size:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(3407).choice(a.size, k, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -550,6 +589,10 @@ def main():
     ap.add_argument("--seql", type=int, default=9)
     ap.add_argument("--n_c", type=int, default=128)
     ap.add_argument("--n_b", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (roofline, bf16x6 mode, CPU baseline, --also blocks) after the headline run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed step computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--graph", action="store_true", help="capture the whole step in a HIP graph and replay it (single GPU; pays off when the step is launch-bound, i.e. small frames)")
     ap.add_argument("--recompute", action="store_true", help="per-window activation recompute (long sequences / big batches)")
@@ -557,8 +600,10 @@ def main():
                     help="arithmetic of the MFMA kernels for the headline measurement (default fp32 = native fp32 MFMA)")
     ap.add_argument("--no-bf16x6", action="store_true", help="skip the additional bf16x6-mode measurement")
     ap.add_argument("--also", default="config3,config4,infer,dist1",
-                    help="comma list of extra blocks appended to the JSON line at --gpus 1 (config3, config4, infer, dist1; 'none' = skip)")
+                    help="with --full: comma list of extra blocks appended to the JSON line at --gpus 1 (config3, config4, infer, dist1; 'none' = skip)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N`: become the launcher.  Nothing in this process has touched the GPU yet (importing
@@ -613,7 +658,7 @@ def main():
     # initialised AFTER a 120 GiB workload has run in the process costs the steps that follow it 50-80 ms each for a while
     # (tools/second_workload.py), so the group of one is created here, before anything else; the headline run does not use it
     dist1_group = False
-    if (world == 1 and not use_dist and "dist1" in args.also.split(",") and not args.graph
+    if (args.full and world == 1 and not use_dist and "dist1" in args.also.split(",") and not args.graph
             and (args.batch, args.height, args.width, args.seql, args.n_c, args.n_b) == (4, 180, 240, 9, 128, 5)):
         import socket
         with socket.socket() as sk:              # (a free port: two bench runs on one box must not meet on a fixed one)
@@ -633,8 +678,11 @@ def main():
     B, H, W, L = args.batch, args.height, args.width, args.seql
     wl = Workload(dev, B, H, W, L, n_c, n_b, args.math, recompute=args.recompute, graph=args.graph, use_dist=use_dist, rank=rank)
 
-    dt, loss = timed(wl.step, args.warmup, args.steps, use_dist, dev)
+    dt, last = timed(wl.step, args.warmup, args.steps, use_dist, dev)
+    loss = last[0]
     peak_mem = torch.cuda.max_memory_allocated(dev) / 2**30
+    if args.dump_outputs and rank == 0:
+        dump_outputs(step_outputs(wl.model, last), args.dump_outputs)
     lockstep = None
     if use_dist:
         # the ranks must be in lock step: identical parameters on every rank after the timed steps (a rank that missed an
@@ -650,15 +698,16 @@ def main():
         if not lockstep:
             raise SystemExit("bench.py: parameters differ between ranks after %d steps: %s" % (args.steps + args.warmup, [c.tolist() for c in allck]))
 
-    # the instrumented extra step contains the gradient all-reduce: every rank has to take part in it
-    iso = isolated_conv(dev, B, H, W, n_c) if rank == 0 else None
-    roof = dominant_kernel_roofline(wl.eager_step, iso, args.math, wl.shape_key(), step_ms=dt / args.steps * 1e3)
+    roof, split = None, None
+    if args.full:
+        # the instrumented extra step contains the gradient all-reduce: every rank has to take part in it
+        iso = isolated_conv(dev, B, H, W, n_c) if rank == 0 else None
+        roof = dominant_kernel_roofline(wl.eager_step, iso, args.math, wl.shape_key(), step_ms=dt / args.steps * 1e3)
     # second arithmetic mode of the same step (every rank takes part): the fp32-equivalent bf16x6 split -- reported
     # beside the headline number, never as it
-    split = None
-    if args.math == "fp32" and not args.no_bf16x6 and not args.graph:
+    if args.full and args.math == "fp32" and not args.no_bf16x6 and not args.graph:
         ops.set_math("bf16x6")
-        dt6, loss6 = timed(wl.eager_step, 1, args.steps, use_dist, dev)
+        dt6, (loss6, _) = timed(wl.eager_step, 1, args.steps, use_dist, dev)
         roof6 = dominant_kernel_roofline(wl.eager_step, None, "bf16x6", wl.shape_key(), step_ms=dt6 / args.steps * 1e3)
         ops.set_math("fp32")
         split = (dt6, float(loss6), roof6)
@@ -669,7 +718,7 @@ def main():
         windows = L - 1
         frames_per_step = world * B * windows
         value = frames_per_step * args.steps / dt
-        if step_flops:
+        if step_flops and roof is not None:
             roof["step_algorithmic_tflops_per_gpu"] = round(step_flops * args.steps / dt / 1e12, 2)
             roof["step_frac_algorithmic"] = round(step_flops * args.steps / dt / 1e12 / KERNEL_PEAK[args.math], 4)
         out = {
@@ -685,8 +734,9 @@ def main():
                        "rccl_initialised_before_headline_run": bool(dist1_group) or (use_dist and backend == "nccl"),
                        "peak_mem_GiB": round(peak_mem, 1),
                        "final_loss": round(float(loss), 6)},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if split is not None:
             dt6, loss6, roof6 = split
             roof6.pop("isolated_2B_128to128", None)
@@ -701,7 +751,7 @@ def main():
                               "workload, same step, `--math bf16x6` makes it the headline run"}
             if step_flops:
                 out["bf16x6_mode"]["step_fp32_equivalent_tflops_per_gpu"] = round(step_flops * args.steps / dt6 / 1e12, 2)
-        also = [] if args.also in ("", "none") or world != 1 or use_dist else [a.strip() for a in args.also.split(",") if a.strip()]
+        also = [] if not args.full or args.also in ("", "none") or world != 1 or use_dist else [a.strip() for a in args.also.split(",") if a.strip()]
         if also and (H, W, B, L, n_c, n_b) == (180, 240, 4, 9, 128, 5) and not args.graph:
             extra = {}
             if "config3" in also:
@@ -735,7 +785,7 @@ def main():
                     if dist.is_initialized():
                         dist.destroy_process_group()
             out["extra"] = extra
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(dev)
         sys.stdout.flush()
         os.write(json_fd, (json.dumps(out) + "\n").encode())

@@ -4,8 +4,8 @@
   models.*        -> this repo (HIP-backed modules),
   dataloader.*    -> the reference (its CPU workers keep calling its own events_to_channels),
 and the reference's SequenceDataset -> HDF5DataLoaderSequence chain (with worker processes) must feed window lists of
-the layout the trainer loop consumes.  Run in its own interpreter by tests/test_dropin_imports.py; needs
-/root/reference, so it only runs where the reference exists.  Prints one JSON line."""
+the layout the trainer loop consumes.  Needs the reference's source tree (BMC_REFERENCE), so it is run by hand where that
+tree exists: BMC_REFERENCE=<reference tree> python tests/dropin_check.py.  Exits non-zero on a failed check; prints one JSON line."""
 import json
 import os
 import sys
@@ -81,4 +81,5 @@ except RuntimeError as e:
     res["cpu_forward"] = "raises: " + str(e)[:60]
 if not torch.cuda.is_available():
     assert res["cpu_forward"].startswith("raises"), res
+assert res["bmcnet_keys"] == 318 and res["plain_load"] == "<All keys matched successfully>", res
 print(json.dumps(res))

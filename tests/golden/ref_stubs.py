@@ -1,5 +1,5 @@
 """Stand-ins for the reference's absent third-party imports, for the scripts that IMPORT THE REFERENCE in the build
-container (tests/golden/make_golden*.py, tests/test_dropin_imports.py).  Test infrastructure only.
+container (tests/golden/make_golden*.py, tests/dropin_check.py).  Test infrastructure only.
 
 * torchvision, cv2, open3d: empty modules (imported by models/submodules.py:4, dataloader/h5dataset.py:7,
   myutils/vis_events/*.py but untouched on the path exercised here);

@@ -62,10 +62,9 @@ def test_state_dict_keys_equal_golden_reference_keys():
         assert sorted(cls(scale, n_c, n_b).state_dict().keys()) == ref_keys
 
 
-def test_pretrained_plain_checkpoint_loads_strictly():
-    ck = "/root/reference/pretrain/BMCNet_plain_nfs_x4.pth"
-    if not os.path.exists(ck):
-        pytest.skip("reference checkpoint not present")
+def test_pretrained_plain_checkpoint_loads_strictly(tmp_path):
+    from pretrained_checkpoint import write_reference_checkpoint
+    ck = write_reference_checkpoint(str(tmp_path / "BMCNet_plain_nfs_x4.pth"))
     from models.BMCNet_plain import BMCNet_plain
     m = BMCNet_plain(4, 128, 5)
     assert not any(m.load_state_dict(torch.load(ck, map_location="cpu"), strict=True))

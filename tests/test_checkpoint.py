@@ -58,9 +58,8 @@ def test_bare_file_is_reference_format_and_keeps_alias_keys(tmp_path):
 
 
 def test_reference_pretrained_checkpoint_roundtrip(tmp_path):
-    ck = "/root/reference/pretrain/BMCNet_plain_nfs_x4.pth"
-    if not os.path.exists(ck):
-        pytest.skip("reference checkpoint not present")
+    from pretrained_checkpoint import write_reference_checkpoint
+    ck = write_reference_checkpoint(str(tmp_path / "BMCNet_plain_nfs_x4.pth"))
     from checkpoint import load_model_state, save_checkpoint
     from models.BMCNet_plain import BMCNet_plain
     m = BMCNet_plain(4, 128, 5)

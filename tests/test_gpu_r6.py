@@ -202,7 +202,7 @@ def test_bench_launcher_two_ranks_on_one_gpu():
     _gpu()
     env = dict(os.environ, BMC_BENCH_BACKEND="gloo", BMC_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "31", "--width", "56",
-           "--batch", "2", "--seql", "3", "--no-cpu-baseline", "--no-bf16x6", "--also", "none"]
+           "--batch", "2", "--seql", "3", "--full", "--no-cpu-baseline", "--no-bf16x6", "--also", "none"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     if r.returncode != 0:
         try:

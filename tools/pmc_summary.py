@@ -7,7 +7,7 @@ Collect on the GPU box (separate --pmc passes, the program directly after `--`, 
       for p in "sq:SQ_VALU_MFMA_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE GRBM_GUI_ACTIVE" \
                "fetch:FETCH_SIZE" "write:WRITE_SIZE"; do
         rocprofv3 --kernel-trace --pmc ${p#*:} -d gpurun_out/pmc_$m_${p%%:*} -o pmc -- \
-            python3 bench.py --steps 1 --warmup 1 --math $m --no-cpu-baseline --no-bf16x6
+            python3 bench.py --full --steps 1 --warmup 1 --math $m --no-cpu-baseline --no-bf16x6
       done
     done
     python tools/pmc_summary.py gpurun_out r02        # -> gpurun_out/r02_pmc_summary.json, then copied to profiles/
@@ -48,7 +48,7 @@ def short(name):
 
 
 def main(root, tag, steps=None):
-    # bench.py --steps 1 --warmup 1 runs warm-up, timed and instrumented (roofline block) steps: 3, and in the fp32 mode a fourth
+    # bench.py --full --steps 1 --warmup 1 runs warm-up, timed and instrumented (roofline block) steps: 3, and in the fp32 mode a fourth
     # (the instrumented step once more on one stream: roofline.alone)
     steps_of = {"fp32": steps or 4, "bf16x6": steps or 3}
     out = {"_comment": __doc__.split("\n\n")[0] + " Counters: rocprofv3 --pmc, one pass per counter group; "
