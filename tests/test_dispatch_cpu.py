@@ -118,3 +118,17 @@ def test_bench_ranks_pin_to_disjoint_runs_of_physical_cores():
     assert a["after"] == list(range(a["info"]["first"], a["info"]["last"] + 1)) or len(a["after"]) == a["info"]["logical_cpus"]
     off = run(1, 2, pin="0")
     assert off["info"] is None and off["after"] == off["before"]
+
+
+def test_bf16_kernel_cases_cover_every_tile_and_both_tap_row_sides():
+    """tests/test_gpu_bf16_kernels.py picks its convolution batches from the device's CU count with a copy of bmc_conv's tile rule
+    (csrc/conv.hip): at 256 CUs (and other counts) its forward launches reach all 8 (taps, BN, TH) of bmc_conv_bf_launch, and its
+    weight-gradient cases sit on both sides of ops.pgemm_raw's tap-row rule."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    import test_gpu_bf16_kernels as T
+    for cus in (256, 304, 228, 80):
+        assert T.conv_cases_tiles(cus) == T.ALL_BF_TILES, cus
+    assert T.conv_tile(4, 180, 240, 128, 256) == (128, 8) and T.conv_tile(1, 31, 56, 128, 256) == (64, 4)
+    assert T.conv_tile(4, 90, 120, 128, 256) == (128, 4) and T.conv_tile(8, 90, 120, 32, 256) == (32, 8)
+    assert {c[-1] for c in T.WGRAD_CASES} == {1, 3} and {c[4] for c in T.WGRAD_CASES} >= {16, 48, 160}
+    assert any(c[5] == 2 for c in T.WGRAD_CASES) and any(len(c[3]) > 1 for c in T.WGRAD_CASES)
