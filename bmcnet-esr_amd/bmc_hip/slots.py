@@ -1,0 +1,128 @@
+"""Recording slots of multi-stream inference (csrc/slots.hip; include/bmc_hip.h "multi-stream inference"): the per-window
+stage / commit / metrics launches of infer.MultiStreamSR, ONE launch each for all S slots.
+
+A slot table is S bmc_slot_t entries (SLOT_DTYPE) in a device uint8 tensor; the host fills a numpy view of a pinned copy
+(SlotTable) and uploads it with one small copy per window.  Feature states are laid out [nfeat][S][H][W][n_c]: the model's
+channels-last [S,n_c,H,W] views of state k are `to_nchw(buf[k])`, adjacent in one buffer (ops.stack_states reads them
+without a copy).  LAUNCHES counts the launches of each wrapper (the tests check that a window costs one of each)."""
+import numpy as np
+import torch
+
+from . import lib
+from .ops import _stream
+
+ACTIVE, RESET = 1, 2
+MAX_SLOTS = 256
+MAX_PARTS = 64
+SLOT_DTYPE = np.dtype([("frames", "<u8"), ("gt", "<u8"), ("keep", "<u8"), ("result", "<u8"), ("flags", "<i4"),
+                       ("pad", "<i4")])
+assert SLOT_DTYPE.itemsize == 40
+LAUNCHES = {"stage": 0, "commit": 0, "metrics": 0}
+
+
+class SlotTable:
+    """A device slot table and a small ring of pinned host copies: `host()` returns the numpy entries to fill for the next
+    window (cleared), `upload()` copies them to the device on the current stream.  A ring buffer is rewritten only after the
+    copy that last read it has completed, so the host never waits for the GPU to finish the window before."""
+
+    RING = 4
+
+    def __init__(self, S, device):
+        if not 1 <= S <= MAX_SLOTS:
+            raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
+        self.S = S
+        nbytes = S * SLOT_DTYPE.itemsize
+        self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
+        self._events = [None] * self.RING
+        self._k = 0
+
+    def host(self):
+        k = self._k
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        entries = self._pinned[k].numpy().view(SLOT_DTYPE)
+        entries[:] = 0
+        return entries
+
+    def upload(self):
+        k = self._k
+        self.dev.copy_(self._pinned[k], non_blocking=True)
+        ev = self._events[k] = self._events[k] or torch.cuda.Event()
+        ev.record()
+        self._k = (k + 1) % self.RING
+
+    def ptr(self):
+        return self.dev.data_ptr()
+
+
+def _check(cond, what):
+    if not cond:
+        raise ValueError("slots: " + what)
+
+
+def _feat_layout(pool):
+    """pool [nfeat, S, H, W, n_c] contiguous -> (nfeat, feat_n)."""
+    _check(pool.dim() == 5 and pool.is_contiguous() and pool.dtype in (torch.float32, torch.bfloat16),
+           "feature pool must be a contiguous [nfeat,S,H,W,n_c] fp32 / bf16 tensor")
+    return pool.shape[0], pool.shape[2] * pool.shape[3] * pool.shape[4]
+
+
+def stage(table, x, pool, feat, pred):
+    """x [S,2,seqn,H,W] <- the slots' windows; feat [nfeat,S,H,W,n_c] fp32 <- the pool's state (zeros for reset / empty
+    slots; feat may BE an fp32 pool); pred [S,2,sH,sW] (the previous predictions, in place) zeroed for reset / empty slots."""
+    S, two, seqn, H, W = x.shape
+    nfeat, feat_n = _feat_layout(pool)
+    _check(two == 2 and x.is_contiguous() and x.dtype == torch.float32, "x must be a contiguous fp32 [S,2,seqn,H,W]")
+    _check(tuple(feat.shape) == tuple(pool.shape) and feat.dtype == torch.float32 and feat.is_contiguous(),
+           "feat must be a contiguous fp32 tensor of the pool's shape")
+    _check(tuple(pool.shape[1:4]) == (S, H, W) and table.S == S, "pool / table do not match x")
+    _check(pred.shape[0] == S and pred.is_contiguous() and pred.dtype == torch.float32, "pred must be contiguous fp32 [S,...]")
+    lib.call(lib._slot_stage, "bmc_slot_stage", table.ptr(), S, seqn, H, W, x.data_ptr(), pool.data_ptr(),
+             int(pool.dtype == torch.bfloat16), feat.data_ptr(), nfeat, feat_n, pred.data_ptr(), pred[0].numel(), _stream())
+    LAUNCHES["stage"] += 1
+
+
+def commit(table, srcs, pool, pred_src, pred_pool):
+    """Active slots: pool[k] <- srcs[k] (the model's new [S,n_c,H,W] channels-last states; bf16 pool: nearest-even),
+    pred_pool <- pred_src, and the prediction to each slot's `keep` address."""
+    nfeat, feat_n = _feat_layout(pool)
+    S = pool.shape[1]
+    _check(len(srcs) == nfeat, "%d state tensors for a pool of %d" % (len(srcs), nfeat))
+    ptrs = (lib.C.c_void_p * 3)()
+    for k, t in enumerate(srcs):
+        _check(t.dtype == torch.float32 and t.shape[0] == S and t[0].numel() == feat_n and t.permute(0, 2, 3, 1).is_contiguous(),
+               "state %d must be a channels-last fp32 [S,n_c,H,W] tensor" % k)
+        ptrs[k] = t.data_ptr()
+    for t in (pred_src, pred_pool):
+        _check(t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(pred_pool.shape),
+               "predictions must be contiguous fp32 tensors of one shape")
+    lib.call(lib._slot_commit, "bmc_slot_commit", table.ptr(), S, ptrs, nfeat, feat_n, pool.data_ptr(),
+             int(pool.dtype == torch.bfloat16), pred_src.data_ptr(), pred_pool.data_ptr(), pred_pool[0].numel(), _stream())
+    LAUNCHES["commit"] += 1
+
+
+def metric_parts(gh, gw):
+    """Workgroups per slot of bmc_slot_metrics for a gh x gw ground truth (about 16 elements per lane, at most 64)."""
+    return max(1, min(MAX_PARTS, -(-2 * gh * gw // (1024 * 16))))
+
+
+def sum_parts(sse):
+    """[..., nparts, 2] partial sums (float64, any device) -> [..., 2] on the CPU, added in part order."""
+    sse = sse.cpu()
+    out = sse[..., 0, :].clone()
+    for p in range(1, sse.shape[-2]):
+        out += sse[..., p, :]
+    return out
+
+
+def metrics(table, pred, H, W, gh, gw, nparts):
+    """Per active slot with a result address: nparts x {esr_sse, bicubic_sse} partial sums (float64) of
+    sum (bicubic(pred -> gh x gw) - gt)^2 and sum (bicubic(frame 1 -> gh x gw) - gt)^2 -- the sums of infer_BMCNet.py:76-85
+    (sum_parts adds them; divide by 2*gh*gw for the MSE)."""
+    S, two, sH, sW = pred.shape
+    _check(two == 2 and pred.is_contiguous() and pred.dtype == torch.float32 and table.S == S,
+           "pred must be a contiguous fp32 [S,2,sH,sW]")
+    _check(1 <= nparts <= MAX_PARTS, "1 <= nparts <= %d" % MAX_PARTS)
+    lib.call(lib._slot_metrics, "bmc_slot_metrics", table.ptr(), S, pred.data_ptr(), sH, sW, H, W, gh, gw, nparts, _stream())
+    LAUNCHES["metrics"] += 1

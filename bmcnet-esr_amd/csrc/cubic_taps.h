@@ -1,0 +1,23 @@
+// ATen's bicubic taps (F.interpolate(..., mode='bicubic', align_corners=False)), shared by the loss-side resize (resize.hip)
+// and the per-slot inference metrics (slots.hip).  Per axis: scale = in / out (float), src = fma(scale, dst + 0.5, -0.5) (not
+// clamped), i0 = floor(src), t = src - i0, taps i0-1 .. i0+2 with the cubic-convolution weights for A = -0.75; the caller clamps
+// the tap indices to [0, in-1].
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace {
+
+constexpr float CUBIC_A = -0.75f;
+
+__device__ __forceinline__ void cubic_taps(int dst, float scale, int& i0, float (&w)[4]) {
+    const float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
+    const float fl = floorf(src);
+    const float t = src - fl;
+    i0 = (int)fl;
+    auto c1 = [](float v) { return ((CUBIC_A + 2.f) * v - (CUBIC_A + 3.f)) * v * v + 1.f; };                     // |v| <= 1
+    auto c2 = [](float v) { return ((CUBIC_A * v - 5.f * CUBIC_A) * v + 8.f * CUBIC_A) * v - 4.f * CUBIC_A; };   // 1 < |v| < 2
+    w[0] = c2(t + 1.f); w[1] = c1(t); w[2] = c1(1.f - t); w[3] = c2(2.f - t);
+}
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+}  // namespace

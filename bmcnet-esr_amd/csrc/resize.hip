@@ -8,21 +8,9 @@
 // The backward is the transposed operator written as a GATHER (each input element sums the output elements whose
 // taps touch it, clamped taps included), so it is deterministic -- no float atomics.
 #include "bmc_common.h"
+#include "cubic_taps.h"
 
 namespace {
-
-constexpr float CUBIC_A = -0.75f;
-
-__device__ __forceinline__ void cubic_taps(int dst, float scale, int& i0, float (&w)[4]) {
-    const float src = fmaf(scale, (float)dst + 0.5f, -0.5f);
-    const float fl = floorf(src);
-    const float t = src - fl;
-    i0 = (int)fl;
-    auto c1 = [](float v) { return ((CUBIC_A + 2.f) * v - (CUBIC_A + 3.f)) * v * v + 1.f; };                     // |v| <= 1
-    auto c2 = [](float v) { return ((CUBIC_A * v - 5.f * CUBIC_A) * v + 8.f * CUBIC_A) * v - 4.f * CUBIC_A; };   // 1 < |v| < 2
-    w[0] = c2(t + 1.f); w[1] = c1(t); w[2] = c1(1.f - t); w[3] = c2(2.f - t);
-}
-__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __global__ void bicubic_fwd_kernel(const float* __restrict__ x, long long planes, int H, int W, int Ho, int Wo,
                                    float sy, float sx, float* __restrict__ y) {

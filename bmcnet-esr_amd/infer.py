@@ -1,7 +1,13 @@
 """Streaming single-GPU inference with the reference's semantics (infer_BMCNet.py:20-103):
 the recurrent state (h, h_p, h_n, previous HR prediction) is created once and carried across calls, every call
 runs one window under no_grad, and the per-window latency is measured with events on the launch stream exactly
-where the reference puts its `starter/ender` pair (infer_BMCNet.py:54,66-68)."""
+where the reference puts its `starter/ender` pair (infer_BMCNet.py:54,66-68).
+
+MultiStreamSR runs many recordings through one model at once (slots of one batched window); evaluate_recordings is the
+reference's evaluation mode 1 on top of it."""
+import collections
+import statistics
+
 import torch
 
 
@@ -147,3 +153,264 @@ class StreamingSR:
         """Mean per-window latency (the reference's `time` metric), ignoring the first `skip` windows."""
         t = self.times_ms[skip:] or self.times_ms
         return sum(t) / max(len(t), 1)
+
+
+class SlotScheduler:
+    """Which recording each of S slots carries in each window -- the host-side part of MultiStreamSR, pure Python.
+
+    Recordings are queued with their window counts and served first come, first served.  plan() advances one window:
+    a recording whose windows are all done frees its slot, free slots take the next queued recordings in slot order (their
+    first window is a *reset*), and every occupied slot runs its next window."""
+
+    def __init__(self, slots):
+        if not 1 <= int(slots) <= 256:
+            raise ValueError("SlotScheduler: 1 <= slots <= 256 (got %r)" % (slots,))
+        self.slots = [None] * int(slots)         # per slot: [handle, next window] or None
+        self.n_windows = {}
+        self._queue = collections.deque()
+        self._next = 0
+
+    def add(self, n_windows):
+        """Queue a recording of n_windows >= 1 windows -> its handle."""
+        if int(n_windows) < 1:
+            raise ValueError("SlotScheduler: a recording needs at least one window (got %r)" % (n_windows,))
+        h = self._next
+        self._next += 1
+        self.n_windows[h] = int(n_windows)
+        self._queue.append(h)
+        return h
+
+    def pending(self):
+        """True while a window is left to run."""
+        return bool(self._queue) or any(s is not None and s[1] < self.n_windows[s[0]] for s in self.slots)
+
+    def plan(self):
+        """Advance one window -> per slot (handle, window index, reset) or None for an empty slot; None when no window is
+        left."""
+        for i, s in enumerate(self.slots):
+            if s is not None and s[1] >= self.n_windows[s[0]]:
+                self.slots[i] = None
+        fresh = set()
+        for i in range(len(self.slots)):
+            if self.slots[i] is None and self._queue:
+                self.slots[i] = [self._queue.popleft(), 0]
+                fresh.add(i)
+        if all(s is None for s in self.slots):
+            return None
+        out = []
+        for i, s in enumerate(self.slots):
+            if s is None:
+                out.append(None)
+            else:
+                out.append((s[0], s[1], i in fresh))
+                s[1] += 1
+        return out
+
+
+class MultiStreamSR:
+    """Many recordings through one model at once: S slots of one batched forward pass, each carrying its own recording's
+    recurrent state; a recording that ends frees its slot for the next queued one (infer_BMCNet.py mode 1, :248-295, runs
+    them one after another at batch 1).  Per window: bmc_slot_stage (inputs + state, exact zeros where a recording starts),
+    the model under no_grad with init=False (a zero state and a zero previous prediction give what init=True gives), then
+    bmc_slot_commit (state back to the pool) and bmc_slot_metrics (esr_mse / bicubic_mse sums per slot, read only when
+    results() asks) -- one launch each for all slots (bmc_hip/slots.py).
+
+    open(frames [L,2,H,W], gts [L,2,gh,gw]) queues a recording (fp32, on the GPU; windows as oracle.infer_windows: `seqn`
+    frames each, the ground truth of window i is frame i+1); step() runs one window for every active slot; run() steps to the
+    end; results(handle) gives per-window esr_mse, bicubic_mse, time (ms, events on the launch stream around the whole
+    window, shared by the slots of that window) and, with keep_predictions, the predictions [n_windows,2,sH,sW].
+
+    graph=True: from the third window on a window is ONE graph replay (stage, forward, commit, metrics captured; the slot
+    table is refreshed by one small copy before it).  Parameter updates invalidate the graph as in StreamingSR.
+    state_dtype=torch.bfloat16: the feature states rest in bf16 between windows, as StreamingSR(state_dtype=bf16)."""
+
+    def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
+                 seqn=3):
+        if state_dtype not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
+        if seqn < 2:
+            raise ValueError("MultiStreamSR: seqn >= 2 (the model reads frames 0 and 1 of a window)")
+        self.model = model.eval()
+        self.S, self.n_c, self.scale, self.plain, self.seqn = int(slots), n_c, scale, plain, int(seqn)
+        self.use_graph = graph
+        self.state_dtype = None if state_dtype is torch.float32 else state_dtype
+        self.keep_predictions = keep_predictions
+        self.sched = SlotScheduler(self.S)
+        self.replays = 0
+        self._recs = {}
+        self._size = None          # (H, W, gh, gw) of the first recording
+        self._bufs = None
+        self._steps = []           # (start, end) events per window
+        self._calls = 0
+        self._graph = self._stamp = None
+
+    # ---------------------------------------------------------------- recordings
+    def open(self, frames, gts, gt_size=None):
+        """Queue one recording -> handle.  frames [L,2,H,W], gts [L,2,gh,gw] (fp32, on the GPU); gt_size (the reference's
+        gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size."""
+        if frames.dim() != 4 or frames.shape[1] != 2 or gts.dim() != 4 or tuple(gts.shape[:2]) != (frames.shape[0], 2):
+            raise ValueError("MultiStreamSR.open: frames [L,2,H,W] and gts [L,2,gh,gw] (got %s, %s)"
+                             % (tuple(frames.shape), tuple(gts.shape)))
+        if not (frames.is_cuda and gts.is_cuda and frames.dtype == torch.float32 and gts.dtype == torch.float32):
+            raise ValueError("MultiStreamSR.open: frames and gts must be fp32 GPU tensors")
+        L = frames.shape[0]
+        if L < self.seqn:
+            raise ValueError("MultiStreamSR.open: %d frames, fewer than one window of seqn = %d" % (L, self.seqn))
+        H, W, gh, gw = frames.shape[2], frames.shape[3], gts.shape[2], gts.shape[3]
+        if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
+            raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
+        if self._size is None:
+            self._size = (H, W, gh, gw)
+        elif self._size != (H, W, gh, gw):
+            raise ValueError("MultiStreamSR.open: sizes %s differ from the first recording's %s (group recordings by sensor "
+                             "size)" % ((H, W, gh, gw), self._size))
+        nwin = L - self.seqn + 1
+        sH, sW = self.scale * H, self.scale * W
+        from bmc_hip import slots
+        rec = {"frames": frames.contiguous(), "gts": gts.contiguous(), "n": nwin, "steps": [],
+               "sse": torch.zeros(nwin, slots.metric_parts(gh, gw), 2, dtype=torch.float64, device=frames.device),
+               "keep": torch.empty(nwin, 2, sH, sW, device=frames.device) if self.keep_predictions else None}
+        h = self.sched.add(nwin)
+        self._recs[h] = rec
+        return h
+
+    def results(self, handle):
+        """-> dict(esr_mse=[...], bicubic_mse=[...], time=[...] per window done so far[, predictions=[n,2,sH,sW]])."""
+        r = self._recs[handle]
+        done = len(r["steps"])
+        if done:
+            self._steps[r["steps"][-1]][1].synchronize()
+        from bmc_hip import slots
+        n = 2 * self._size[2] * self._size[3]
+        sse = slots.sum_parts(r["sse"][:done]) / n
+        out = {"esr_mse": sse[:, 0].tolist(), "bicubic_mse": sse[:, 1].tolist(),
+               "time": [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]}
+        if self.keep_predictions:
+            out["predictions"] = r["keep"][:done]
+        return out
+
+    # ---------------------------------------------------------------- windows
+    def _buffers(self, device):
+        if self._bufs is None:
+            H, W, _, _ = self._size
+            S, nfeat = self.S, 1 if self.plain else 3
+            from bmc_hip import slots
+            b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
+                 "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
+                 "table": slots.SlotTable(S, device)}
+            if self.state_dtype is None:
+                b["pool"] = b["feat"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device)       # the model reads the pool
+            else:
+                b["pool"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device, dtype=self.state_dtype)
+                b["feat"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device)
+            self._bufs = b
+        return self._bufs
+
+    def _forward(self):
+        b = self._bufs
+        states = [t.permute(0, 3, 1, 2) for t in b["feat"]]             # channels-last [S,n_c,H,W] views, adjacent
+        return self.model(b["x"], *states, b["pred"], False)
+
+    def _window(self):
+        """stage -> model -> commit -> metrics (what a graph replay runs)."""
+        from bmc_hip import slots
+        b = self._bufs
+        H, W, gh, gw = self._size
+        slots.stage(b["table"], b["x"], b["pool"], b["feat"], b["pred"])
+        out = self._forward()
+        cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.contiguous(memory_format=torch.channels_last)
+        slots.commit(b["table"], [cl(t) for t in out[:-1]], b["pool"], out[-1].contiguous(), b["pred"])
+        slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
+
+    def _weights_stamp(self):
+        return tuple((id(p), p._version) for p in self.model.parameters())
+
+    def invalidate(self):
+        """Drop the captured graph (the next graph-mode step() captures again); the slots' states are kept."""
+        self._graph = self._stamp = None
+
+    def _capture(self):
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):                      # warm-up on a side stream: the forward alone (no state change)
+            self._forward()
+        torch.cuda.current_stream().wait_stream(side)
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            self._window()
+        self._graph = g
+        self._stamp = self._weights_stamp()
+
+    @torch.no_grad()
+    def step(self):
+        """Run one window for every active slot -> False when no recording had a window left."""
+        plan = self.sched.plan()
+        if plan is None:
+            return False
+        from bmc_hip import slots
+        H, W, gh, gw = self._size
+        first = next(self._recs[p[0]] for p in plan if p is not None)
+        b = self._buffers(first["frames"].device)
+        e = b["table"].host()
+        for s, p in enumerate(plan):
+            if p is None:
+                continue
+            h, i, reset = p
+            r = self._recs[h]
+            e[s]["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
+            e[s]["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * gh * gw
+            e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
+            e[s]["result"] = r["sse"][i].data_ptr()
+            e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
+            r["steps"].append(len(self._steps))
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        start.record()
+        b["table"].upload()
+        self._calls += 1
+        if self.use_graph and self._calls >= 3:
+            if self._graph is not None and self._stamp != self._weights_stamp():
+                self.invalidate()                          # the graph replays the OLD packed weights
+            if self._graph is None:
+                self._capture()
+            self._graph.replay()
+            self.replays += 1
+        else:
+            self._window()
+        end.record()
+        self._steps.append((start, end))
+        return True
+
+    def run(self):
+        """Step until every queued recording has finished."""
+        while self.step():
+            pass
+
+
+def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
+                        gt_size=None, keep_predictions=False):
+    """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
+    (or a sequence of such pairs, named "0", "1", ...) of one sensor size.  -> dict(
+      results = {metric: {name: value}}  per recording the mean over its windows of esr_mse, bicubic_mse, time (ms), and
+                                         params (millions) -- infer_body's MetricTracker result (:34,:70-86),
+      mean    = {metric: mean over recordings}  (results_mean, :284-291)[,
+      predictions = {name: [n_windows,2,sH,sW]}  with keep_predictions])."""
+    items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
+    ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
+                       keep_predictions=keep_predictions, seqn=seqn)
+    handles = [(name, ms.open(frames, gts, gt_size)) for name, (frames, gts) in items]
+    ms.run()
+    params = sum(p.numel() for p in model.parameters()) / 1e6
+    breakdown = collections.defaultdict(dict)
+    preds = {}
+    for name, h in handles:
+        r = ms.results(h)
+        for k in ("esr_mse", "bicubic_mse", "time"):
+            breakdown[k][name] = float(statistics.mean(r[k]))
+        breakdown["params"][name] = params
+        if keep_predictions:
+            preds[name] = r["predictions"]
+    out = {"results": dict(breakdown), "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items()}}
+    if keep_predictions:
+        out["predictions"] = preds
+    return out

@@ -442,6 +442,46 @@ int bmc_small_mm(const bmc_small_mm_args_t* host_args, bmc_stream_t s);
 int bmc_bicubic_resize_fwd(const float* x, long long planes, int H, int W, int Ho, int Wo, float* y, bmc_stream_t s);
 int bmc_bicubic_resize_bwd(const float* gy, long long planes, int H, int W, int Ho, int Wo, float* gx, bmc_stream_t s);
 
+/* ---- multi-stream inference: recording slots (bmcnet-esr_amd/infer.py::MultiStreamSR) ------------------------------
+ * S <= BMC_MAX_SLOTS independent recordings run through one batched forward pass, recording r in slot s of the batch.  The
+ * reference runs one recording at a time at batch 1 (infer_BMCNet.py:248-295 around the loop body :44-86).  Each call below is
+ * ONE launch for all S slots; `table` is a DEVICE array of S bmc_slot_t that the host refreshes before each window.
+ * Feature states: nfeat tensors (h, h_p, h_n for BMCNet; h for BMCNet_plain) of feat_n = n_c*H*W values per slot, NHWC per
+ * slot, laid out [nfeat][S][feat_n] (the model's channels-last [S,n_c,H,W] views, adjacent in one buffer).  The pool holds them
+ * in fp32 or bf16 (pool_bf16); the previous prediction [S][pred_n] (pred_n = 2*sH*sW) is always fp32. */
+#define BMC_MAX_SLOTS 256
+#define BMC_SLOT_ACTIVE 1   /* the slot carries a recording this window */
+#define BMC_SLOT_RESET 2    /* ... whose first window this is: its state is read as exact zeros (infer_BMCNet.py:55-60) */
+typedef struct bmc_slot {
+    const float* frames;    /* first frame of the window: [seqn][2][H][W] contiguous (frames[i:i+seqn] of a [L,2,H,W] recording) */
+    const float* gt;        /* the window's ground truth [2][gh][gw] (gt of window i = frame i+1, infer_BMCNet.py:49) */
+    float* keep;            /* NULL, or where bmc_slot_commit copies the slot's prediction [2][sH][sW] */
+    double* result;         /* NULL, or where bmc_slot_metrics writes nparts x {esr_sse, bicubic_sse} partial sums */
+    int flags;              /* BMC_SLOT_ACTIVE | BMC_SLOT_RESET; 0 (or frames NULL): an empty slot */
+    int pad_;
+} bmc_slot_t;
+
+/* Before the forward pass (replaces the per-recording input_stack / init_h / init_o tensors of infer_BMCNet.py:51,55-60):
+ * x[s] [2][seqn][H][W] = the window of slot s transposed (zeros for an empty slot); feat [nfeat][S][feat_n] fp32 = the pool's
+ * state (a bf16 pool widened exactly), exact zeros for a RESET or empty slot -- feat == feat_pool (fp32 pool) loads in place;
+ * pred [S][pred_n], read by the model in place, is zeroed for RESET / empty slots. */
+int bmc_slot_stage(const bmc_slot_t* table, int S, int seqn, int H, int W, float* x, const void* feat_pool, int pool_bf16,
+                   float* feat, int nfeat, long long feat_n, float* pred, long long pred_n, bmc_stream_t s);
+/* After the forward pass (the carried h, hp, hn, prediction of infer_BMCNet.py:62-63), active slots only: feat_src = HOST
+ * array of nfeat device pointers, each [S][feat_n] fp32 (the model's new states) -> the pool (bf16: round to nearest-even,
+ * bit-identical to tensor.to(torch.bfloat16)); pred_src [S][pred_n] -> pred_pool and, where the slot's `keep` is set, there. */
+int bmc_slot_commit(const bmc_slot_t* table, int S, const float* const* feat_src, int nfeat, long long feat_n, void* feat_pool,
+                    int pool_bf16, const float* pred_src, float* pred_pool, long long pred_n, bmc_stream_t s);
+/* The metrics of infer_BMCNet.py:76-85 as sums of squares, per active slot with a `result`, split into nparts
+ * (1 .. BMC_SLOT_MAX_PARTS) partial sums over fixed element sets (element i of [2][gh][gw] in part (i / 1024) % nparts):
+ * result[2p] = part p of sum (bicubic(pred[s] -> gh x gw) - gt)^2 (no resize when sH x sW == gh x gw), result[2p+1] = part p
+ * of sum (bicubic(frame 1 of the window -> gh x gw) - gt)^2.  ATen's bicubic taps (as bmc_bicubic_resize_fwd); no HR
+ * temporary; fixed-order reductions in double, no atomics: the caller adds the parts in a fixed order -- bit-reproducible,
+ * independent of the other slots. */
+#define BMC_SLOT_MAX_PARTS 64
+int bmc_slot_metrics(const bmc_slot_t* table, int S, const float* pred, int sH, int sW, int H, int W, int gh, int gw,
+                     int nparts, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif
