@@ -20,15 +20,20 @@
 // (3 xi) x (nu in {3 pg .. 3 pg + 2}) of the 32 x 32 block (co block cb, ci block kb): 9 x 16 accumulator registers, two waves
 // per SIMD.  Per stage and wave: 18 MFMAs of 64 cycles, 18 ds_read2_b32 of operand fragments (lane -> channel l & 31, tile
 // l >> 5 of the k-step: conflict-free).
-// Raw pixels reach LDS by LDS-DMA, 39 pieces of 1 KB per stage spread over the eight waves (5 each): no staging registers.  Inside
-// the image a piece is "scalar base of the stage + a per-lane offset that never changes"; stages that touch the image border take
-// a slower path (clamped per-lane addresses; the quads of out-of-image pixels are overwritten with zeros once landed) so that
-// the transforms never see the border.  Two raw buffers and two transformed images: 150 KB of LDS, one barrier per stage.
-// Work that is not MFMAs is split by WAVE so that it never stands in front of MFMAs the matrix pipe is waiting for (SIMD partners
-// are waves w and w + 4): waves 0-3 multiply and THEN transform the next stage on channel pairs, two items per lane -- wave 0 the
-// lone xi row of x (xi = 0 / 5), waves 1 / 2 sum / difference of the two xi rows that share their sub-sums (1, 2 / 3, 4), wave 3
-// all three xi of dY; waves 4-7 request the raw strips of the stage after next (all 39 DMA pieces) and THEN multiply.  While one
-// partner's MFMAs run, the other one transforms or requests.
+// Raw pixels reach LDS by LDS-DMA, 39 pieces of 1 KB per stage, piece w + 8 j on wave w (five each, wave 7 four): no staging
+// registers.  Inside the image a piece is "scalar base of the stage + a per-lane offset that never changes"; stages that touch the
+// image border take a slower path (clamped per-lane addresses computed once per stage; the quads of out-of-image pixels are
+// overwritten with zeros once landed) so that the transforms never see the border.
+// LDS budget (160 KB): two raw buffers of 39 KB + two transformed images of 36 KB = 150 KB; one barrier per stage.
+// Stage pipeline (round 7).  In stage s every wave multiplies stage s, transforms its share of stage s + 1 and requests its
+// pieces of stage s + 2, all of it placed BETWEEN its own MFMAs by a compile-time timetable (sched_barrier fences): its DMA pieces
+// behind MFMAs 0, 2, 4, 6, 8; the LDS reads of patch column c behind MFMA c, the column's combination three MFMAs later, the
+// along-the-row combinations and the LDS writes behind MFMAs 10, 12, 14.  The transform is shared by all eight waves, one item
+// (tile, channel pair) per lane: wave w takes tiles {0, 1} (w < 4) or {2, 3} of role w & 3 -- 0 the lone xi row of x (xi = 0 / 5),
+// 1 / 2 sum / difference of the two xi rows that share their sub-sums (1, 2 / 3, 4), 3 all three xi of dY -- and the six (four)
+// column chains of a lane are independent, so no gap holds more than a few dependent instructions.  Waves are specialised by
+// role at compile time (no branches in the MFMA stream); the loop has three forms (request + transform, transform only, last).
+// The end-of-stage vmcnt(0) follows the stage's last MFMA: the pieces have had ten MFMA gaps to land.
 // Partial sums leave in REGISTER order (one 1 KB store per accumulator quad: [split][type][wave][position][quad][lane][4]);
 // the reduction kernel knows the MFMA's D layout and reads them back as 16-byte quads of four consecutive output channels.
 #include "bmc_common.h"
@@ -37,10 +42,13 @@
 
 #ifndef BMC_W4G_ABL
 #define BMC_W4G_ABL 0     // ablation builds (tools/): 1 no MFMA, 2 no DMA, 4 no transforms, 8 no fragment reads, 16 every DMA from the
-                          // first stage's pixels (cache hits), 32 no wait for the DMA at the end of a stage
+                          // first stage's pixels (cache hits), 32 no wait for the DMA at the end of a stage.  libbmc_hip_w4gablNmM.so:
+                          // BMC_W4G_ABL = N, BMC_W4G_MODE = M (the DMA timetable, below)
 #endif
 
-#ifdef BMC_W4G_STAMP      // diagnostic build (tools/ only): per-wave cycle stamps of workgroup 8, iterations 40..103
+#ifdef BMC_W4G_STAMP      // diagnostic build (tools/ only): per-wave cycle stamps of workgroup 8, iterations 40..103; phases of a stage:
+                          // 0 top, 1 after rq_begin, 2 after position 4's MFMAs, 3 after the last MFMA, 4 after the DMA wait, 5 after
+                          // the barrier
 __device__ unsigned long long g_w4g_stamp[8][64][8];
 #define W4G_STAMP(it, k) do { if (blockIdx.x == 8 && (threadIdx.x & 63) == 0 && (it) >= 40 && (it) < 104) g_w4g_stamp[threadIdx.x >> 6][(it) - 40][(k)] = __builtin_amdgcn_s_memtime(); } while (0)
 #else
@@ -79,10 +87,38 @@ constexpr int XPC = 23, YPC = 16;           // DMA pieces (4 pixels x 64 channel
 constexpr int RAWX = XPC * 256;             // floats
 constexpr int RAWF = (XPC + YPC) * 256;     // floats per raw buffer (39 KB)
 constexpr int NPC = XPC + YPC;
-constexpr int PPW = 10;                     // pieces per requesting wave: waves 4-7 carry 10 each (pieces w - 4 + 4 j; slot 39 = piece 38 once more)
-constexpr int LDSF = 2 * RAWF + 2 * SIMG;   // 153 600 bytes
+constexpr int PPW = 5;                      // pieces per wave: piece w + 8 j (wave 7: four -- there is no piece 39)
+constexpr int LDSF = 2 * RAWF + 2 * SIMG;   // 153 600 bytes: 2 x 39 KB raw + 2 x 36 KB transformed (of 160 KB)
+static_assert(LDSF * 4 <= 160 * 1024, "LDS budget");
 
-template <int TG>
+// The stage's timetable, in gaps: gap g follows the wave's MFMA g of the stage (position g >> 1, k-step g & 1).
+//   DMA piece j:                 gap dma_gap(j) (BMC_W4G_MODE picks the variant; NOTEBOOK.md R7.1 has the measurements)
+//   transform, patch column c:   LDS reads at gap c, the column's combination at gap c + 3 (the reads have had ~3 MFMA gaps),
+//   transform, output step k:    gap 10 + 2 k (the along-the-row combinations and the LDS writes)
+#ifndef BMC_W4G_MODE
+#define BMC_W4G_MODE 0
+#endif
+constexpr int dma_gap(const int j) {       // 0: gaps 0, 2, 4, 6, 8; 1: 1, 4, 7, 10, 13; 2: 0 .. 4; 3: 1, 5, 9, 13, 17
+    return BMC_W4G_MODE == 1 ? 1 + 3 * j : (BMC_W4G_MODE == 2 ? j : (BMC_W4G_MODE == 3 ? 1 + 4 * j : 2 * j));
+}
+constexpr int TR_READ = 0, TR_COMB = 3, TR_OUT = 10;
+
+template <int I, int N>
+struct W4gFor {     // compile-time loop: f(integral_constant<int, I>) for I = 0 .. N - 1 (the accumulators must stay in registers)
+    template <class F>
+    static __device__ __forceinline__ void run(F&& f) {
+        f(std::integral_constant<int, I>{});
+        W4gFor<I + 1, N>::run(f);
+    }
+};
+template <int N>
+struct W4gFor<N, N> {
+    template <class F>
+    static __device__ __forceinline__ void run(F&&) {}
+};
+
+// ROLE = wave & 3: which part of the next stage's transform this wave computes (see the file header)
+template <int TG, int ROLE>
 __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, const int split, const int chh, const int kh) {
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -101,19 +137,15 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[i][r] = 0.f;
 
-    // ---- roles.  The CU's vector-memory path takes one 1 KB piece per ~40-60 cycles (PMC + ablations) and an in-order wave
-    // that issues a piece while requests queue there is blocked with everything behind it, its MFMAs included; a wave's
-    // transform is a chain of dependent packed operations behind LDS round trips.  Neither must stand in front of MFMAs the
-    // matrix pipe is waiting for, so the two kinds of work sit on DIFFERENT waves of every SIMD (partners are w and w + 4):
-    //   waves 0-3: multiply, THEN transform the next stage (wave 0 the lone xi row of x, wave 1 / 2 sum / difference of the xi pair,
-    //              wave 3 dY; two items per lane: tiles {0, 1} then {2, 3});
-    //   waves 4-7: request the raw strips of the stage after next (all 39 pieces, 10 slots each), THEN multiply.
-    // While one partner's MFMAs run, the other one transforms or requests.
-    const bool requester = wave >= 4;
+    // ---- requests: every wave issues its pieces w + 8 j of the stage after next, one per timetable slot.  Inside the image a piece
+    // is "scalar base of the stage + a per-lane offset that never changes" (poff); a border stage's clamped per-lane offsets are
+    // computed once per stage in rq_begin, outside the MFMA stream (pof: the offsets of the stage being requested)
     unsigned poff[PPW];       // byte offset from the stage's base pixel (interior stages)
+    unsigned pof[PPW];        // the offsets of the stage in flight
     unsigned pla[PPW];        // LDS byte address of the piece in raw buffer 0
     unsigned pxm = 0;         // bit j: piece j is an x piece
-    auto piece_of = [&](const int j) { return min((wave & 3) + 4 * j, NPC - 1); };
+    auto piece_of = [&](const int j) { return min(wave + 8 * j, NPC - 1); };
+    const bool has_last = wave + 8 * (PPW - 1) < NPC;
     // pixel slot (row r, column c) of this lane's quad of piece p; false: not a pixel (the last two slots of the x strip)
     auto slot_of = [&](const int p, int& r, int& c) __attribute__((always_inline)) {
         if (p < XPC) { const int q = 4 * p + (lane >> 4); r = q / 18; c = q - 18 * r; return q < 90; }
@@ -126,6 +158,7 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
         int r, c;
         const bool real = slot_of(p, r, c);
         poff[j] = real ? (unsigned)(((r * a.W + c) * 128 + (lane & 15) * 4) * 4) : 0u;
+        pof[j] = poff[j];
         pla[j] = lds_raw + (unsigned)(p * 1024);
         pxm |= p < XPC ? 1u << j : 0u;
     }
@@ -157,21 +190,37 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
     };
     row_setup();
 
-    // requests of the raw strips of the next stage: rq_begin fixes the stage (scalar state) and advances the cursor, rq_piece(j)
-    // issues this wave's piece j into the raw buffer rq_begin named
+    // rq_begin fixes the stage to request (scalar state, border offsets) and advances the cursor; rq_piece(j) issues piece j into
+    // the raw buffer rq_begin named
     const float* rq_xs = nullptr;
     const float* rq_ys = nullptr;
-    int rq_y0 = 0, rq_x0 = 0;
     unsigned rq_lo = 0;
-    bool rq_border = false;
     auto rq_begin = [&](const int rb) __attribute__((always_inline)) {
         rq_lo = (unsigned)(rb * RAWF * 4);
-        rq_y0 = 4 * nty - 1 + TG; rq_x0 = 16 * nsx - 1;
-        rq_border = rowborder || nsx == 0 || rq_x0 + 17 >= a.W;
+        const int y0 = 4 * nty - 1 + TG, x0 = 16 * nsx - 1;
+        const bool border = rowborder || nsx == 0 || x0 + 17 >= a.W;
         // interior: base = the strip's first pixel; border: base = the image (per-lane offsets are absolute then)
-        rq_xs = rq_border ? xbat : xrow + rq_x0 * 128;
-        rq_ys = rq_border ? ybat : yrow + (rq_x0 + 1) * 128;
+        rq_xs = border ? xbat : xrow + x0 * 128;
+        rq_ys = border ? ybat : yrow + (x0 + 1) * 128;
         zm = 0;
+        if (border) {
+            asm volatile("; image border" ::: "memory");
+#pragma unroll
+            for (int j = 0; j < PPW; ++j) {
+                const bool isx = (pxm >> j) & 1;
+                int r, c;
+                const bool real = slot_of(piece_of(j), r, c);
+                const int y = (isx ? y0 : y0 + 1 - TG) + r, x = (isx ? x0 : x0 + 1) + c;
+                const bool inside = y >= 0 && y < a.H && x >= 0 && x < a.W;
+                const int yc = min(max(y, 0), a.H - 1), xc = min(max(x, 0), a.W - 1);
+                pof[j] = real ? (unsigned)(((yc * a.W + xc) * 128 + (lane & 15) * 4) * 4) : 0u;
+                zm |= (real && !inside) ? (1u << j) : 0u;
+            }
+        } else {
+#pragma unroll
+            for (int j = 0; j < PPW; ++j) pof[j] = poff[j];
+        }
+        if (!has_last) zm &= ~(1u << (PPW - 1));
         if (BMC_W4G_ABL & 16) return;
         if (++nsx == a.SX) {
             nsx = 0;
@@ -181,19 +230,8 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
     };
     auto rq_piece = [&](const int j) __attribute__((always_inline)) {
         if (BMC_W4G_ABL & 2) return;
-        unsigned o = poff[j];
-        if (rq_border) {
-            asm volatile("; image border" ::: "memory");
-            const bool isx = (pxm >> j) & 1;
-            int r, c;
-            const bool real = slot_of(piece_of(j), r, c);
-            const int y = (isx ? rq_y0 : rq_y0 + 1 - TG) + r, x = (isx ? rq_x0 : rq_x0 + 1) + c;
-            const bool inside = y >= 0 && y < a.H && x >= 0 && x < a.W;
-            const int yc = min(max(y, 0), a.H - 1), xc = min(max(x, 0), a.W - 1);
-            o = real ? (unsigned)(((yc * a.W + xc) * 128 + (lane & 15) * 4) * 4) : 0u;
-            zm |= (real && !inside) ? (1u << j) : 0u;
-        }
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(o), "s"(((pxm >> j) & 1) ? rq_xs : rq_ys),
+        if (j == PPW - 1 && !has_last) return;
+        asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(pof[j]), "s"(((pxm >> j) & 1) ? rq_xs : rq_ys),
                      "s"(pla[j] + rq_lo) : "memory");
     };
     // after the requests have landed, before the barrier that publishes them: pixels outside the image become zeros
@@ -204,91 +242,96 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
             if ((zm >> j) & 1) *reinterpret_cast<f32x4*>(rawb + (pla[j] - lds_raw) / 4 + rb * RAWF + lane * 4) = f32x4{0.f, 0.f, 0.f, 0.f};
     };
 
-    // ---- producer role (waves 0-3): item = (tile, channel pair cp) of the stage; instance i of a wave: tiles 2 i + (lane >> 5)
-    const int cp = lane & 31;
+    // ---- transform of the next stage: item = (tile pt, channel pair cp), one per lane; wave w and w + 4 take tiles {0, 1} / {2, 3}.
+    //   ROLE 0: the lone xi row of x: xi = 0 = (4 0 -5 0 1 0) on patch rows 0, 2, 4; xi = 5 = (0 4 0 -5 0 1) on patch rows 1, 3, 5 --
+    //           staged rows 0, 2, 4 either way;
+    //   ROLE 1 / 2: sum / difference of the two xi rows on patch rows 1..4 (staged rows 1 - TG ..): xi = 1, 2 = (r4 - 4 r2) +- (r3 - 4 r1);
+    //           xi = 3, 4 = (r4 - r2) +- 2 (r3 - r1);
+    //   ROLE 3: all three xi of dY: (y0, (y0 + y2) +- (y1 + y3)) or ((y0 + 4 y2) +- 2 (y1 + 4 y3), y3).
+    // Then along the row: B^T (x) or A (dY) on the six / four column values.  The pieces are placed in the MFMA stream by the
+    // timetable above; every lane's column chains are independent of each other.
+    const int pt = 2 * (wave >> 2) + (lane >> 5), cp = lane & 31;
+    constexpr int NK = ROLE == 0 ? 3 : 4;                                   // rows read per patch column
+    constexpr int NC = ROLE == 3 ? 4 : 6;                                   // patch columns
+    constexpr int KS = ROLE == 0 ? 2 * 18 * CH : (ROLE == 3 ? 16 * CH : 18 * CH);
+    const int tsrc = (ROLE == 0 ? 4 * pt * CH : (ROLE == 3 ? RAWX + 4 * pt * CH : ((1 - TG) * 18 + 4 * pt) * CH)) + 2 * cp;
+    const int tdst = (ROLE == 3 ? 0 : IMG + (ROLE == 0 ? (TG == 0 ? 0 : 2) : (TG == 0 ? 1 : 0) + (ROLE == 2 ? 1 : 0)) * 6 * PIMG) + pt * CH + 2 * cp;
+    f32x2 td[NC][NK];          // the column's reads
+    f32x2 tw[3][NC];           // combined columns (x roles: tw[0]; dY: the three xi rows)
     f32x2 bsum = {0.f, 0.f};
-    // B^T along a row of six: (4 0 -5 0 1 0) (0 -4 -4 1 1 0) (0 4 -4 -1 1 0) (0 -2 -1 2 1 0) (0 2 -1 -2 1 0) (0 4 0 -5 0 1)
-    auto xcols = [&](const f32x2 (&w)[6], float* const dst) __attribute__((always_inline)) {
-        const f32x2 ta = w[4] - 4.f * w[2], tb = w[3] - 4.f * w[1], tc = w[4] - w[2], te = w[3] - w[1];
-        *reinterpret_cast<f32x2*>(dst) = 4.f * w[0] - 5.f * w[2] + w[4];
-        *reinterpret_cast<f32x2*>(dst + PIMG) = ta + tb;
-        *reinterpret_cast<f32x2*>(dst + 2 * PIMG) = ta - tb;
-        *reinterpret_cast<f32x2*>(dst + 3 * PIMG) = tc + 2.f * te;
-        *reinterpret_cast<f32x2*>(dst + 4 * PIMG) = tc - 2.f * te;
-        *reinterpret_cast<f32x2*>(dst + 5 * PIMG) = 4.f * w[1] - 5.f * w[3] + w[5];
-    };
-    // A along a row of four: (1 0 0 0) (1 1 1 1) (1 -1 1 -1) (1 2 4 8) (1 -2 4 -8) (0 0 0 1); returns the nu = 1 entry
-    auto ycols = [&](const f32x2 (&w)[4], float* const dst) __attribute__((always_inline)) -> f32x2 {
-        const f32x2 s = w[0] + w[2], t = w[1] + w[3], p = w[0] + 4.f * w[2], q = w[1] + 4.f * w[3];
-        const f32x2 m1 = s + t;
-        *reinterpret_cast<f32x2*>(dst) = w[0];
-        *reinterpret_cast<f32x2*>(dst + PIMG) = m1;
-        *reinterpret_cast<f32x2*>(dst + 2 * PIMG) = s - t;
-        *reinterpret_cast<f32x2*>(dst + 3 * PIMG) = p + 2.f * q;
-        *reinterpret_cast<f32x2*>(dst + 4 * PIMG) = p - 2.f * q;
-        *reinterpret_cast<f32x2*>(dst + 5 * PIMG) = w[3];
-        return m1;
-    };
-    auto transform = [&](const float* const raw, float* const img) __attribute__((always_inline)) {
+    auto ld2 = [](const float* p) __attribute__((always_inline)) { return *reinterpret_cast<const f32x2*>(p); };
+    auto st2 = [](float* p, const f32x2 v) __attribute__((always_inline)) { *reinterpret_cast<f32x2*>(p) = v; };
+    // the transform's share of gap G (compile time)
+    auto tgap = [&](auto gc, const float* const raw, float* const img) __attribute__((always_inline)) {
+        constexpr int G = decltype(gc)::value;
         if (BMC_W4G_ABL & 4) return;
-        auto ld2 = [](const float* p) __attribute__((always_inline)) { return *reinterpret_cast<const f32x2*>(p); };
+        constexpr int cr = G - TR_READ, cc = G - TR_COMB;
+        if constexpr (cr >= 0 && cr < NC) {
 #pragma unroll
-        for (int inst = 0; inst < 2; ++inst) {
-            const int pt = 2 * inst + (lane >> 5);
-            if (wave == 0) {
-                // the lone xi row of x: xi = 0 = (4 0 -5 0 1 0) on patch rows 0, 2, 4; xi = 5 = (0 4 0 -5 0 1) on patch rows 1, 3, 5 --
-                // staged rows 0, 2, 4 either way.  All 18 reads first
-                const float* const s = raw + (4 * pt) * CH + 2 * cp;
-                f32x2 d[3][6], w[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c)
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) d[k][c] = ld2(s + (2 * k * 18 + c) * CH);
-#pragma unroll
-                for (int c = 0; c < 6; ++c) w[c] = 4.f * d[0][c] - 5.f * d[1][c] + d[2][c];
-                xcols(w, img + IMG + ((TG == 0 ? 0 : 2) * 6) * PIMG + pt * CH + 2 * cp);
-            } else if (wave < 3) {
-                // the two xi rows on patch rows 1..4 (staged rows 1 - TG ..): xi = 1, 2 = (r4 - 4 r2) +- (r3 - 4 r1); xi = 3, 4 = (r4 - r2) +- 2 (r3 - r1);
-                // wave 1 the sum, wave 2 the difference
-                const float* const s = raw + ((1 - TG) * 18 + 4 * pt) * CH + 2 * cp;
+            for (int k = 0; k < NK; ++k) td[cr][k] = ld2(raw + tsrc + k * KS + cr * CH);
+        }
+        if constexpr (cc >= 0 && cc < NC) {
+            const f32x2* const d = td[cc];
+            if constexpr (ROLE == 0) {
+                tw[0][cc] = 4.f * d[0] - 5.f * d[1] + d[2];
+            } else if constexpr (ROLE < 3) {
                 constexpr float al = TG == 0 ? -4.f : -1.f;
-                const float ga = (TG == 0 ? 1.f : 2.f) * (wave == 2 ? -1.f : 1.f);
-                f32x2 d[4][6], w[6];
-#pragma unroll
-                for (int c = 0; c < 6; ++c)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) d[k][c] = ld2(s + (k * 18 + c) * CH);
-#pragma unroll
-                for (int c = 0; c < 6; ++c) w[c] = (d[3][c] + al * d[1][c]) + ga * (d[2][c] + al * d[0][c]);
-                xcols(w, img + IMG + (((TG == 0 ? 1 : 0) + (wave == 2 ? 1 : 0)) * 6) * PIMG + pt * CH + 2 * cp);
+                constexpr float ga = (TG == 0 ? 1.f : 2.f) * (ROLE == 2 ? -1.f : 1.f);
+                tw[0][cc] = (d[3] + al * d[1]) + ga * (d[2] + al * d[0]);
             } else {
-                // dY (wave 3), all three xi of the group: (y0, (y0 + y2) +- (y1 + y3)) or ((y0 + 4 y2) +- 2 (y1 + 4 y3), y3)
-                const float* const s = raw + RAWX + (4 * pt) * CH + 2 * cp;
                 constexpr float ka = TG == 0 ? 1.f : 4.f, la = TG == 0 ? 1.f : 2.f;
-                f32x2 y[4][4], u0[4], u1[4], u2[4];
-#pragma unroll
-                for (int c = 0; c < 4; ++c)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) y[k][c] = ld2(s + (16 * k + c) * CH);
-#pragma unroll
-                for (int c = 0; c < 4; ++c) {
-                    const f32x2 p = y[0][c] + ka * y[2][c], q = y[1][c] + ka * y[3][c];
-                    if (TG == 0) { u0[c] = y[0][c]; u1[c] = p + la * q; u2[c] = p - la * q; }
-                    else { u0[c] = p + la * q; u1[c] = p - la * q; u2[c] = y[3][c]; }
-                }
-                float* const dd = img + pt * CH + 2 * cp;
-                ycols(u0, dd);
-                const f32x2 m11 = ycols(u1, dd + 6 * PIMG);
-                ycols(u2, dd + 12 * PIMG);
-                if (TG == 0) bsum += m11;         // xi = 1, nu = 1: the sum of the tile's 16 dY pixels
+                const f32x2 p = d[0] + ka * d[2], q = d[1] + ka * d[3];
+                if (TG == 0) { tw[0][cc] = d[0]; tw[1][cc] = p + la * q; tw[2][cc] = p - la * q; }
+                else { tw[0][cc] = p + la * q; tw[1][cc] = p - la * q; tw[2][cc] = d[3]; }
             }
-            __builtin_amdgcn_sched_barrier(0);
+        }
+        constexpr int ko = G - TR_OUT;
+        if constexpr (ko >= 0 && ko < 6 && (ko & 1) == 0) {
+            constexpr int k = ko >> 1;
+            if constexpr (ROLE < 3) {
+                // B^T along a row of six: (4 0 -5 0 1 0) (0 -4 -4 1 1 0) (0 4 -4 -1 1 0) (0 -2 -1 2 1 0) (0 2 -1 -2 1 0) (0 4 0 -5 0 1)
+                const f32x2* const w = tw[0];
+                float* const dst = img + tdst;
+                if (k == 0) {
+                    st2(dst, 4.f * w[0] - 5.f * w[2] + w[4]);
+                    st2(dst + 5 * PIMG, 4.f * w[1] - 5.f * w[3] + w[5]);
+                } else if (k == 1) {
+                    const f32x2 ta = w[4] - 4.f * w[2], tb = w[3] - 4.f * w[1];
+                    st2(dst + PIMG, ta + tb);
+                    st2(dst + 2 * PIMG, ta - tb);
+                } else {
+                    const f32x2 tc = w[4] - w[2], te = w[3] - w[1];
+                    st2(dst + 3 * PIMG, tc + 2.f * te);
+                    st2(dst + 4 * PIMG, tc - 2.f * te);
+                }
+            } else {
+                // A along a row of four: (1 0 0 0) (1 1 1 1) (1 -1 1 -1) (1 2 4 8) (1 -2 4 -8) (0 0 0 1), on xi row k of the group
+                const f32x2* const w = tw[k];
+                float* const dst = img + tdst + 6 * k * PIMG;
+                const f32x2 s = w[0] + w[2], t = w[1] + w[3], p = w[0] + 4.f * w[2], q = w[1] + 4.f * w[3];
+                const f32x2 m1 = s + t;
+                st2(dst, w[0]);
+                st2(dst + PIMG, m1);
+                st2(dst + 2 * PIMG, s - t);
+                st2(dst + 3 * PIMG, p + 2.f * q);
+                st2(dst + 4 * PIMG, p - 2.f * q);
+                st2(dst + 5 * PIMG, w[3]);
+                if (TG == 0 && k == 1) bsum += m1;         // xi = 1, nu = 1: the sum of the tile's 16 dY pixels
+            }
         }
     };
 
-    // ---- matrix role: 9 positions x 2 k-steps on the stage's images.  The operand fragments of position i + 2 are requested
-    // before the MFMAs of position i are issued (a ring of three register sets): no MFMA waits for an LDS round trip
-    auto multiply = [&](const float* const img) __attribute__((always_inline)) {
+    // ---- one stage: 9 positions x 2 k-steps of v_mfma_f32_32x32x2_f32 on the stage's images, the timetable's pieces in the gaps.
+    // The operand fragments of position i + 2 are requested before the MFMAs of position i are issued (a ring of three register
+    // sets): no MFMA waits for an LDS round trip.  REQ: there is a stage after next to request; MORE: a next stage to transform
+    auto stage = [&](const int it, auto reqc, auto morec) __attribute__((always_inline)) {
+        constexpr bool REQ = decltype(reqc)::value, MORE = decltype(morec)::value;
+        const float* const img = imgb + (it & 1) * SIMG;
+        const float* const traw = rawb + ((it + 1) & 1) * RAWF;
+        float* const timg = imgb + ((it + 1) & 1) * SIMG;
+        W4G_STAMP(it, 0);
+        if (REQ) rq_begin(it & 1);
+        W4G_STAMP(it, 1);
         float af[3][2], bf[3][2];
         auto frag = [&](const int i) __attribute__((always_inline)) {
             const int u = i / 3, j = i - 3 * u, sl = i % 3;
@@ -299,68 +342,61 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
                 bf[sl][ks] = img[boff + (6 * u + j) * PIMG + 2 * ks * CH];
             }
         };
+        __builtin_amdgcn_sched_barrier(0);
         frag(0);
         frag(1);
-#pragma unroll
-        for (int i = 0; i < 9; ++i) {
+        W4gFor<0, 9>::run([&](auto ic) __attribute__((always_inline)) {
+            constexpr int i = decltype(ic)::value;
             __builtin_amdgcn_sched_barrier(0);
             if (i + 2 < 9) frag(i + 2);
             __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int ks = 0; ks < 2; ++ks) {
+            W4gFor<0, 2>::run([&](auto kc) __attribute__((always_inline)) {
+                constexpr int ks = decltype(kc)::value, g = 2 * i + ks;
                 if (BMC_W4G_ABL & 1) acc[i][0] += af[i % 3][ks] * bf[i % 3][ks];
                 else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i % 3][ks], bf[i % 3][ks], acc[i], 0, 0, 0);
-            }
-        }
-        __builtin_amdgcn_sched_barrier(0);
+                if (REQ) {
+#pragma unroll
+                    for (int j = 0; j < PPW; ++j)
+                        if (dma_gap(j) == g) rq_piece(j);
+                }
+                if (MORE) tgap(std::integral_constant<int, g>{}, traw, timg);
+                __builtin_amdgcn_sched_barrier(0);
+            });
+            if (i == 4) W4G_STAMP(it, 2);
+        });
+        W4G_STAMP(it, 3);
+        if (!(BMC_W4G_ABL & 32)) dma_wait<0>();
+        W4G_STAMP(it, 4);
+        if (REQ) patch(it & 1);
+        ring_publish();
+        W4G_STAMP(it, 5);
     };
 
     // ---- prologue: stage st0 raw -> image 0, stage st0 + 1 requested
     const int n = st1 - st0;
-    if (n > 0) {
-        rq_begin(0);
-        if (requester) {
+    if (n <= 0) return;
+    rq_begin(0);
 #pragma unroll
-            for (int j = 0; j < PPW; ++j) rq_piece(j);
-            dma_wait<0>();
-            patch(0);
-        }
-        ring_publish();
-        if (n > 1) {
-            rq_begin(1);
-            if (requester) {
+    for (int j = 0; j < PPW; ++j) rq_piece(j);
+    dma_wait<0>();
+    patch(0);
+    ring_publish();
+    if (n > 1) {
+        rq_begin(1);
 #pragma unroll
-                for (int j = 0; j < PPW; ++j) rq_piece(j);
-            }
-        }
-        if (!requester) transform(rawb, imgb);
-        dma_wait<0>();
-        if (n > 1 && requester) patch(1);
-        ring_publish();
+        for (int j = 0; j < PPW; ++j) rq_piece(j);
     }
-    for (int it = 0; it < n; ++it) {
-        const float* const img = imgb + (it & 1) * SIMG;
-        const bool req = it + 2 < n, more = it + 1 < n;                      // stage it + 2 -> the raw buffer stage it was made from
-        W4G_STAMP(it, 0);
-        if (req) rq_begin(it & 1);
-        W4G_STAMP(it, 1);
-        if (requester && req) {
-#pragma unroll
-            for (int j = 0; j < PPW; ++j) rq_piece(j);
-        }
-        W4G_STAMP(it, 2);
-        __builtin_amdgcn_sched_barrier(0);
-        multiply(img);
-        __builtin_amdgcn_sched_barrier(0);
-        W4G_STAMP(it, 3);
-        if (!requester && more) transform(rawb + ((it + 1) & 1) * RAWF, imgb + ((it + 1) & 1) * SIMG);
-        W4G_STAMP(it, 4);
-        if (!(BMC_W4G_ABL & 32)) dma_wait<0>();
-        W4G_STAMP(it, 5);
-        if (requester && req) patch(it & 1);
-        ring_publish();
-        W4G_STAMP(it, 6);
-    }
+    W4gFor<0, 18>::run([&](auto gc) __attribute__((always_inline)) { tgap(gc, rawb, imgb); });
+    dma_wait<0>();
+    if (n > 1) patch(1);
+    ring_publish();
+    // ---- stage it: multiply stage it, transform stage it + 1, request stage it + 2 (into the raw buffer stage it was made from)
+    using T_ = std::true_type;
+    using F_ = std::false_type;
+    int it = 0;
+    for (; it + 2 < n; ++it) stage(it, T_{}, T_{});
+    if (it + 1 < n) stage(it++, F_{}, T_{});
+    stage(it, F_{}, F_{});
 
     // ---- partial sums in register order: part[split][type][wave][position 3 u + j][quad m][lane][4] -- D row 8 m + 4 (l >> 5) + e
     // (co), column l & 31 (ci), e = 0..3: one coalesced 1 KB store per accumulator quad
@@ -373,9 +409,19 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
                 stg16(P + (i * 4 + m) * 256, f32x4{acc[i][4 * m], acc[i][4 * m + 1], acc[i][4 * m + 2], acc[i][4 * m + 3]});
     }
     if (TG == 0 && kh == 0 && a.bias_part) {      // bias partial: the 4 tile slots added through LDS (the loop ended on a barrier)
-        if (wave == 3) *reinterpret_cast<f32x2*>(lds + (lane >> 5) * CH + 2 * cp) = bsum;      // (the dY wave: tiles t and t + 2 per lane)
+        if (ROLE == 3) *reinterpret_cast<f32x2*>(lds + pt * CH + 2 * cp) = bsum;      // (the dY waves 3 / 7: tiles {0, 1} / {2, 3})
         __syncthreads();
-        if (tid < CH) a.bias_part[(long long)split * 128 + 64 * chh + tid] = lds[tid] + lds[CH + tid];
+        if (tid < CH) a.bias_part[(long long)split * 128 + 64 * chh + tid] = (lds[tid] + lds[CH + tid]) + (lds[2 * CH + tid] + lds[3 * CH + tid]);
+    }
+}
+
+template <int TG>
+__device__ __forceinline__ void wgrad4_role(const Wgrad4K& a, float* const lds, const int split, const int chh, const int kh) {
+    switch (__builtin_amdgcn_readfirstlane(threadIdx.x >> 6) & 3) {
+        case 0: wgrad4_body<TG, 0>(a, lds, split, chh, kh); break;
+        case 1: wgrad4_body<TG, 1>(a, lds, split, chh, kh); break;
+        case 2: wgrad4_body<TG, 2>(a, lds, split, chh, kh); break;
+        default: wgrad4_body<TG, 3>(a, lds, split, chh, kh); break;
     }
 }
 
@@ -391,67 +437,80 @@ __global__ __launch_bounds__(512, 2) void wino4_wgrad_kernel(const Wgrad4K a) {
         type = blockIdx.x & 7; split = blockIdx.x >> 3;
     }
     const int chh = (type >> 1) & 1, kh = type & 1;
-    if (type & 4) wgrad4_body<1>(a, lds, split, chh, kh);
-    else wgrad4_body<0>(a, lds, split, chh, kh);
+    if (type & 4) wgrad4_role<1>(a, lds, split, chh, kh);
+    else wgrad4_role<0>(a, lds, split, chh, kh);
 }
 
 // dW[co][k0 + ci][3][3] (+)= G^T (sum over splits of dU) G, db[co] (+)= sum of the bias partials.
-// Block = four consecutive co (one accumulator quad of the main kernel) x 32 consecutive ci (one MFMA column block) x 8 position
-// groups: thread (ci, pp) adds the positions p = pp, pp + 8, ... over ALL splits (fixed order), 16 bytes per load, applies
-// G^T . G to what it holds, and the eight partial tap sets are added through LDS in a fixed order.
-__global__ __launch_bounds__(256) void wino4_wgrad_reduce_kernel(const float* __restrict__ part, int nsplit, float* __restrict__ dw,
-                                                                int ldw, int k0, int accumulate, const float* __restrict__ bias_part,
-                                                                float* __restrict__ db) {
-    __shared__ float red[8][36][32];
-    const int ol = threadIdx.x & 31, pp = threadIdx.x >> 5;
-    if ((int)blockIdx.y == 32) {         // bias: one block, 128 channels x 2 halves of the splits
-        if (blockIdx.x != 0) return;
-        __shared__ float bs[2][128];
-        const int cc = threadIdx.x & 127, hf = threadIdx.x >> 7;
+// 512 workgroups of 288 threads (+ one for the bias).  Workgroup (c, r): c = (chh, kh, cb, kb) names a 32 x 32 accumulator block of
+// every position, r eight consecutive quads of it (quad m = r >> 3, lanes 8 (r & 7) .. + 7: four co x eight ci).  Phase 1: thread
+// (position p, quad) adds the 16-byte quads of all splits in split order, eight loads in flight.  Phase 2: thread (co, ci, tap)
+// applies G^T . G over the 36 positions held in LDS, in the order the summation always had.  Deterministic.
+constexpr int RED_THREADS = 288, RED_GROUPS = 512;
+__global__ __launch_bounds__(RED_THREADS) void wino4_wgrad_reduce_kernel(const float* __restrict__ part, int nsplit, float* __restrict__ dw,
+                                                                        int ldw, int k0, int accumulate, const float* __restrict__ bias_part,
+                                                                        float* __restrict__ db) {
+    constexpr long long SSTRIDE = 36ll * 16384;     // floats per split
+    const int t = threadIdx.x;
+    if ((int)blockIdx.x == RED_GROUPS) {            // bias: 128 channels, splits in order, eight loads in flight
+        if (t >= 128) return;
         float s = 0.f;
-        for (int i = hf; i < nsplit; i += 2) s += bias_part[(long long)i * 128 + cc];
-        bs[hf][cc] = s;
-        __syncthreads();
-        if (hf == 0) {
-            const float v = bs[0][cc] + bs[1][cc];
-            db[cc] = accumulate ? db[cc] + v : v;
+        int i = 0;
+        for (; i + 8 <= nsplit; i += 8) {
+            float q[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) q[k] = bias_part[(long long)(i + k) * 128 + t];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) s += q[k];
         }
+        for (; i < nsplit; ++i) s += bias_part[(long long)i * 128 + t];
+        db[t] = accumulate ? db[t] + s : s;
         return;
     }
-    const int co0 = 4 * blockIdx.y, ci = blockIdx.x * 32 + ol;
-    const int chh = co0 >> 6, cb = (co0 >> 5) & 1, m = (co0 >> 3) & 3, lh = (co0 >> 2) & 1;
-    const int kh = ci >> 6, kb = (ci >> 5) & 1;
+    __shared__ f32x4 U[36][8];
+    const int c = blockIdx.x >> 5, r = blockIdx.x & 31;
+    const int chh = c >> 3, kh = (c >> 2) & 1, cb = (c >> 1) & 1, kb = c & 1;
+    const int m = r >> 3, lane0 = 8 * (r & 7);
+    {
+        const int p = t >> 3, qi = t & 7;
+        const int xi = p / 6, nu = p - 6 * xi;
+        const int type = (xi / 3) * 4 + chh * 2 + kh, wv = (nu / 3) * 4 + cb * 2 + kb, a9 = 3 * (xi % 3) + nu % 3;
+        const float* const ps = part + (((long long)type * 8 + wv) * 9 + a9) * 1024 + m * 256 + (lane0 + qi) * 4;
+        f32x4 u = {0.f, 0.f, 0.f, 0.f};
+        int s = 0;
+        for (; s + 8 <= nsplit; s += 8) {
+            f32x4 q[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) q[k] = ldg16(ps + (s + k) * SSTRIDE);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) u += q[k];
+        }
+        for (; s < nsplit; ++s) u += ldg16(ps + s * SSTRIDE);
+        U[p][qi] = u;
+    }
+    __syncthreads();
     // rows of G: (1/4 0 0) (-1/6 -1/6 -1/6) (-1/6 1/6 -1/6) (1/24 1/12 1/6) (1/24 -1/12 1/6) (0 0 1);
     // dW[i][j] = sum_xi,nu G[xi][i] G[nu][j] dU[xi][nu]
     const float G[6][3] = {{0.25f, 0.f, 0.f}, {-1.f / 6, -1.f / 6, -1.f / 6}, {-1.f / 6, 1.f / 6, -1.f / 6},
                            {1.f / 24, 1.f / 12, 1.f / 6}, {1.f / 24, -1.f / 12, 1.f / 6}, {0.f, 0.f, 1.f}};
-    f32x4 tap[9];
+    const int e = t / 72, r2 = t - 72 * e, qi = r2 / 9, tap = r2 - 9 * qi, ti = tap / 3, tj = tap - 3 * ti;
+    float o = 0.f;
 #pragma unroll
-    for (int t = 0; t < 9; ++t) tap[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int p = pp; p < 36; p += 8) {
-        const int xi = p / 6, nu = p - 6 * xi;
-        const int type = (xi / 3) * 4 + chh * 2 + kh, wv = (nu / 3) * 4 + cb * 2 + kb, a9 = 3 * (xi % 3) + nu % 3;
-        const float* ps = part + ((((long long)type * 8 + wv) * 9 + a9) * 4 + m) * 256 + (lh * 32 + ol) * 4;
-        f32x4 u = {0.f, 0.f, 0.f, 0.f};
-        for (int s = 0; s < nsplit; ++s) u += ldg16(ps + (long long)s * 36 * 16384);
+    for (int k = 0; k < 8; ++k) {          // eight interleaved partial sums over the positions, then added in order
+        float tk = 0.f;
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+        for (int p = k; p < 36; p += 8) {
+            const int xi = p / 6, nu = p - 6 * xi;
+            float gi = 0.f, gj = 0.f;
 #pragma unroll
-            for (int jj = 0; jj < 3; ++jj) tap[3 * i + jj] += (G[xi][i] * G[nu][jj]) * u;
+            for (int q = 0; q < 3; ++q) { gi = q == ti ? G[xi][q] : gi; gj = q == tj ? G[nu][q] : gj; }
+            tk += (gi * gj) * U[p][qi][e];
+        }
+        o += tk;
     }
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int e = 0; e < 4; ++e) red[pp][e * 9 + t][ol] = tap[t][e];
-    __syncthreads();
-    for (int q = pp; q < 36; q += 8) {       // q = e * 9 + tap: output channel co0 + e
-        float o = 0.f;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o += red[k][q][ol];
-        const int e = q / 9, t = q - 9 * e;
-        float* const d = dw + ((long long)(co0 + e) * ldw + k0 + ci) * 9 + t;
-        *d = accumulate ? *d + o : o;
-    }
+    const int co = 64 * chh + 32 * cb + 8 * m + 4 * (lane0 >> 5) + e, ci = 64 * kh + 32 * kb + (lane0 & 31) + qi;
+    float* const d = dw + ((long long)co * ldw + k0 + ci) * 9 + tap;
+    *d = accumulate ? *d + o : o;
 }
 
 }  // namespace
@@ -499,7 +558,7 @@ extern "C" int bmc_wgrad_wino4_reduce(const float* part, int nsplit, float* dw, 
     BMC_CHECK_ARG(ldw >= 128 && k0 >= 0 && k0 + 128 <= ldw, "bmc_wgrad_wino4_reduce: columns [k0, k0 + 128) must lie inside the %d input "
                   "channels of the weight tensor", ldw);
     BMC_CHECK_ARG((bias_part == nullptr) == (db == nullptr), "bmc_wgrad_wino4_reduce: bias_part and db go together");
-    hipLaunchKernelGGL(wino4_wgrad_reduce_kernel, dim3(4, bias_part ? 33 : 32), dim3(256), 0, (hipStream_t)s, part, nsplit, dw, ldw, k0,
+    hipLaunchKernelGGL(wino4_wgrad_reduce_kernel, dim3(RED_GROUPS + (bias_part ? 1 : 0)), dim3(RED_THREADS), 0, (hipStream_t)s, part, nsplit, dw, ldw, k0,
                        accumulate, bias_part, db);
     BMC_CHECK_LAUNCH("bmc_wgrad_wino4_reduce");
     return 0;

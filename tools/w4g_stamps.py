@@ -26,12 +26,9 @@ f = lib._lib.bmc_w4g_read_stamps
 f.argtypes = [C.c_void_p]
 assert f(buf) == 0
 t = np.frombuffer(buf, dtype=np.uint64).reshape(8, 64, 8).astype(np.int64)
-names = ["rq_begin", "early: T+pieces", "multiply", "late: pieces+T", "vmcnt wait", "patch+barrier", "(next top)"]
-print("median cycles per phase (wave: " + ", ".join(names[:6]) + ", whole stage)")
+names = ["rq_begin", "MFMAs 0-9 + their gaps", "MFMAs 10-17 + their gaps", "vmcnt wait", "patch+barrier"]
+print("median cycles per phase (wave: " + ", ".join(names) + ", whole stage)")
 for wv in range(8):
-    d = np.diff(t[wv, :, :7], axis=1)
+    d = np.diff(t[wv, :, :6], axis=1)
     stage = np.diff(t[wv, :, 0])
-    print("wave %d: %s   stage %d" % (wv, " ".join("%6d" % int(np.median(d[:, k])) for k in range(6)), int(np.median(stage))))
-# relative start of multiply between partners
-for wv in range(4):
-    print("wave %d vs %d: M starts %+d / ends %+d cycles apart" % (wv, wv + 4, int(np.median(t[wv, :, 2] - t[wv + 4, :, 2])), int(np.median(t[wv, :, 3] - t[wv + 4, :, 3]))))
+    print("wave %d: %s   stage %d" % (wv, " ".join("%6d" % int(np.median(d[:, k])) for k in range(5)), int(np.median(stage))))
