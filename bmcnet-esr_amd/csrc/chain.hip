@@ -29,11 +29,6 @@
 #include "bmc_common.h"
 #include "dma_ring.h"
 
-#ifndef BMC_CHAIN_ABL
-#define BMC_CHAIN_ABL 0     // ablation bits for tools/ builds only: 1 no MFMAs, 2 no DMA issue, 4 no global stores,
-                            // 8 no LayerNorm math, 16 no barriers, 32 no fragment reads, 64 no DMA waits
-#endif
-
 namespace {
 
 constexpr int CK = BMC_CK;
@@ -66,7 +61,6 @@ struct ChainK {
 // SWZ[(row >> 2) & 3] on the DMA's SOURCE address and on the fragment reads (conflict-free ds_read_b128 for the
 // 16-row x 4-quad fragment shape), the LDS destination of a DMA stays lane-linear.
 __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
-    if (BMC_CHAIN_ABL & 1) { c[0] += a * b; return c; }      // ablation: one VALU fma instead, operands stay live
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
@@ -153,8 +147,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         const float* base = sbase + c_in;
         const unsigned dst = xb_lds + (unsigned)(((xl_cnt % NXR) * XSLOT + (wave & 1) * NDX * 256) * 4);
 #pragma unroll
-        for (int i = 0; i < NDX; ++i)
-            if (!(BMC_CHAIN_ABL & 2)) dma16(base, xvoff[i], dst + i * 1024);
+        for (int i = 0; i < NDX; ++i) dma16(base, xvoff[i], dst + i * 1024);
         ++xl_cnt;
         c_in += CK;
         if (c_in >= C) {
@@ -182,7 +175,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         const unsigned dst = wb_lds + (unsigned)(((wl_cnt % NWR) * WSLOT + (wave & 1) * NDW * 256) * 4);
 #pragma unroll
         for (int i = 0; i < NDW; ++i)
-            if (wact[i] && !(BMC_CHAIN_ABL & 2)) dma16(p, wvoff[i], dst + i * 1024);
+            if (wact[i]) dma16(p, wvoff[i], dst + i * 1024);
         ++wl_cnt;
         if (++wl_step == NS) wl_step = 0;
     };
@@ -192,16 +185,10 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     const int arow = (16 * wave + lp) * CK + qoff;
     const int brow = lp * CK + qoff;              // + 16*t rows
     f32x4 afA, afB, bfA[NT], bfB[NT];             // two fragment sets: the next step's reads fly under this step's MFMAs
-    auto read_a = [&](const float* xb, f32x4& af) {
-        if (BMC_CHAIN_ABL & 32) { af = f32x4{1.f, 2.f, 3.f, 4.f}; asm volatile("" : "+v"(af)); return; }
-        af = *reinterpret_cast<const f32x4*>(xb + arow);
-    };
+    auto read_a = [&](const float* xb, f32x4& af) { af = *reinterpret_cast<const f32x4*>(xb + arow); };
     auto read_b = [&](const float* wb, f32x4 (&bf)[NT]) {
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            if (BMC_CHAIN_ABL & 32) { bf[t] = f32x4{1.f, 2.f, 3.f, 4.f}; asm volatile("" : "+v"(bf[t])); continue; }
-            bf[t] = *reinterpret_cast<const f32x4*>(wb + brow + 16 * t * CK);
-        }
+        for (int t = 0; t < NT; ++t) bf[t] = *reinterpret_cast<const f32x4*>(wb + brow + 16 * t * CK);
     };
 
     f32x4 Ra[NT], Rt[NT], Rz[BWD ? NT : 1];
@@ -219,17 +206,15 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     auto loader = [&](bool x_step) {
         if (xrole) {
             if (x_step && xl_cnt < total_xchunks) issue_x();
-            if (BMC_CHAIN_ABL & 64) {}
-            else if (xl_cnt - (xc + (x_step ? 1 : 0)) >= DX) dma_wait<NDX * (DX - 1)>(); else dma_wait<0>();
+            if (xl_cnt - (xc + (x_step ? 1 : 0)) >= DX) dma_wait<NDX * (DX - 1)>(); else dma_wait<0>();
         } else {
             if (wl_cnt < total_steps) issue_w();
-            if (BMC_CHAIN_ABL & 64) {}
-            else if (wl_cnt - (gs + 1) >= DW) dma_wait<NDW * (DW - 1)>(); else dma_wait<0>();
+            if (wl_cnt - (gs + 1) >= DW) dma_wait<NDW * (DW - 1)>(); else dma_wait<0>();
         }
     };
     auto publish = [&]() {      // raw barrier: no vmcnt(0) drain of the rings' prefetch (a __syncthreads() would)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        if (!(BMC_CHAIN_ABL & 16)) __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
     };
 
@@ -301,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     };
     const long long img_elems = (long long)a.H * a.W;
     auto store_tile = [&](const f32x4 (&R)[NT], float* base) {     // base: batch plane [H][W][C]
-        if (!pok || ((BMC_CHAIN_ABL & 4) && R[0][0] != 12345.678f)) return;
+        if (!pok) return;
         float* p = base + (long long)pix * C + 4 * lg;
 #pragma unroll
         for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4*>(p + 16 * t) = R[t];
@@ -335,8 +320,8 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
             // ---- z = convf(cat[s0, s1]) + b_f
             for (int i = 0; i < NXC; i += 2) lds_pair(Ra, i + 2 < NXC);
             // ---- LayerNorm over the C channels of each pixel: 4 NT registers in each of the pixel's four lanes
-            float rstd = 1.f;
-            if (!(BMC_CHAIN_ABL & 8)) {
+            float rstd;
+            {
                 float s = 0.f;
 #pragma unroll
                 for (int t = 0; t < NT; ++t) s += (Ra[t][0] + Ra[t][1]) + (Ra[t][2] + Ra[t][3]);

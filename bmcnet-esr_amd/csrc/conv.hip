@@ -17,21 +17,6 @@
 #include "conv_k.h"
 #include <stdlib.h>
 
-#ifndef BMC_LX
-#define BMC_LX 1   // measured: deeper rings (2, 3) do not help the 1x1 kernel (it is power/clock limited)
-#endif
-#ifndef BMC_DIAG_MODE
-#define BMC_DIAG_MODE 0   // ablation bits for diagnostic builds (tools/): 1 no epilogue stores, 2 no global loads, 4 no MFMAs,
-                          // 8 no weight loads, 16 no activation loads
-#endif
-#ifdef BMC_DIAG
-// diagnostic build only (libbmc_hip_diag.so, tools/): per-block cycle / wall stamps; never in the product library
-__device__ unsigned long long* g_diag_buf = nullptr;
-extern "C" int bmc_diag_set_buffer(unsigned long long* p) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_diag_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#endif
-
 namespace {
 
 constexpr int CK = BMC_CK;  // channels per chunk
@@ -76,9 +61,6 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
         if (tid == i) tab[i] = a.src[i];
     if (tid < BN) init_lds[tid] = (bias_pre && tid < a.Cout) ? a.bias[tid] : 0.f;
     __syncthreads();
-#ifdef BMC_DIAG
-    const unsigned long long diag_c0 = __builtin_amdgcn_s_memtime(), diag_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     // Persistent workgroup: tiles blockIdx.x, blockIdx.x + gridDim.x, ... ; the load pipeline runs ahead of the
     // MFMA pipeline across tile boundaries, so only the very first tile of a workgroup pays load latency.
     // XCD-aware tile walk: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 shares an L2), so give each
@@ -155,7 +137,9 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
         s_idx = 0; c_in = 0; xl_chunk = 0;
         src_select();
     };
-    constexpr int LX = TAPS == 1 ? BMC_LX : 1;   // X register ring depth = how many steps a 1x1 tile load runs ahead
+    // X register ring depth = how many steps a 1x1 tile load runs ahead (deeper rings, 2 and 3, measured no gain: the 1x1
+    // kernel is power / clock limited)
+    constexpr int LX = 1;
     f32x4 xr[LX][NXLD], wr[NWLD];
     int xlds[NXLD];              // LDS offset of this thread's halo piece (tile-independent)
 #pragma unroll
@@ -166,11 +150,7 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
     auto load_x = [&](int slot) {
         const float* base = sbase + c_in + q4;
 #pragma unroll
-        for (int n = 0; n < NXLD; ++n) {
-            const float* src = xok[n] ? base + (long long)xpix[n] * spix : g_zero4;
-            if (BMC_DIAG_MODE & (2 | 16)) src = g_zero4;
-            xr[slot][n] = ldg16(src);
-        }
+        for (int n = 0; n < NXLD; ++n) xr[slot][n] = ldg16(xok[n] ? base + (long long)xpix[n] * spix : g_zero4);
         c_in += CK;
         if (++xl_chunk == a.nchunks) {
             xl_tile += t_stride;
@@ -200,7 +180,6 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
 #pragma unroll
         for (int n = 0; n < NWLD; ++n) {
             const int e = tid + 256 * n;
-            if (BMC_DIAG_MODE & (2 | 8)) { wr[n] = f32x4{1.f, 1.f, 1.f, 1.f}; continue; }
             // no branch around the load (a divergent branch makes the compiler serialise the loads with vmcnt(0)):
             // lanes past the slice re-read its last piece and never store it
             const int ec = (n + 1) * 256 <= BN * 4 ? e : (e < BN * 4 ? e : BN * 4 - 1);
@@ -257,13 +236,6 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
         for (int u = 0; u < NT; ++u) bf[u] = *reinterpret_cast<const f32x4*>(wb + boff[u] + 8 * kg);
     };
     auto mfma16 = [&](const f32x4 (&af)[MT], const f32x4 (&bf)[NT]) {
-        if (BMC_DIAG_MODE & 4) {   // ablation: keep the fragments live, skip the matrix pipe
-#pragma unroll
-            for (int t = 0; t < MT; ++t)
-#pragma unroll
-                for (int u = 0; u < NT; ++u) acc[t][u][0] += af[t][0] * bf[u][0] + af[t][3] * bf[u][3];
-            return;
-        }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -364,7 +336,6 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const int co = co0 + 32 * u + 8 * rq;
-                    if ((BMC_DIAG_MODE & 1) && acc[t][u][4 * rq] != 12345.678f) continue;
                     if (pok[t] && co < a.Cout) {
                         f32x4 v;
 #pragma unroll
@@ -458,12 +429,6 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
             epilogue(tile);
         }
     }
-#ifdef BMC_DIAG
-    if (g_diag_buf && tid == 0) {
-        unsigned long long* d = g_diag_buf + (unsigned long long)blockIdx.x * 4;
-        d[0] = diag_c0; d[1] = __builtin_amdgcn_s_memtime(); d[2] = diag_r0; d[3] = __builtin_amdgcn_s_memrealtime();
-    }
-#endif
 }
 
 }  // namespace

@@ -19,16 +19,6 @@
 #include "dma_ring.h"
 #include <stdlib.h>
 
-#ifndef BMC_C1P_EPF
-#define BMC_C1P_EPF 1     // K = 256 instantiation: epilogue operands requested in front of the tile's MFMAs (round 6); 0: behind them
-#endif
-#ifndef BMC_C1P_SPREAD
-#define BMC_C1P_SPREAD 1  // the next tile's DMA pieces dealt out over the MFMA groups of the tile's first half (round 6); 0: one burst behind the first group
-#endif
-#ifndef BMC_C1P_ABL
-#define BMC_C1P_ABL 0     // ablation builds (tools/): 1 no MFMA, 2 no stores, 4 no pixel DMA, 8 no fragment reads
-#endif
-
 namespace {
 
 constexpr int CK = BMC_CK;
@@ -106,7 +96,6 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
     };
     // pieces j0 .. j1 - 1 of this wave's NCH / 2 DMA instructions for one tile
     auto issue_x_part = [&](const TileIt& it, int slot, int j0, int j1) __attribute__((always_inline)) {
-        if (BMC_C1P_ABL & 4) return;
         if (it.b != xl_b) loader_image(it.b);
         int p = it.pt * PX + lpx;
         p = p < HW ? p : HW - 1;
@@ -151,10 +140,7 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
     const int xoff = li * CK + wq;                               // + chunk * CHF + pixel block * 16 * CK
     auto read_x = [&](const float* xb, int c, f32x4 (&xf)[4]) __attribute__((always_inline)) {
 #pragma unroll
-        for (int pb = 0; pb < 4; ++pb) {
-            if (BMC_C1P_ABL & 8) { xf[pb] = f32x4{1.f, 2.f, 3.f, 4.f}; asm volatile("" : "+v"(xf[pb])); continue; }
-            xf[pb] = *reinterpret_cast<const f32x4*>(xb + c * CHF + pb * 16 * CK + xoff);
-        }
+        for (int pb = 0; pb < 4; ++pb) xf[pb] = *reinterpret_cast<const f32x4*>(xb + c * CHF + pb * 16 * CK + xoff);
     };
 
     int tile = t_first;
@@ -199,7 +185,7 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
         //      sat through one memory round trip per tile with the matrix pipes idle (both SIMD partners reach their epilogues
         //      together: one barrier per tile keeps them in step).  K = 128 (four waves per SIMD, 128 registers): behind the MFMAs as
         //      before, one operand at a time -- the other workgroup's waves cover the round trip.
-        constexpr bool EPF = BMC_C1P_EPF && NCH == 16;
+        constexpr bool EPF = NCH == 16;
         f32x4 rv[4], mv[4], ov[4];
         auto ep_load = [&](const float* base, int stride, float fill, f32x4 (&v)[4]) __attribute__((always_inline)) {
 #pragma unroll
@@ -237,12 +223,8 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int pb = 0; pb < 4; ++pb) {
-                    if (BMC_C1P_ABL & 1) acc[pb][0] += wreg[c][j] * xfA[pb][j];
-                    else acc[pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][j], xfA[pb][j], acc[pb], 0, 0, 0);
-                }
+                for (int pb = 0; pb < 4; ++pb) acc[pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c][j], xfA[pb][j], acc[pb], 0, 0, 0);
             if (c + 2 < NCH) read_x(xb, c + 2, xfA);
-#if BMC_C1P_SPREAD
             // tile n + DEPTH into the buffer tile n - 1 was read from (before the previous barrier): requested between the MFMA
             // groups of the tile's FIRST HALF, NCH / 8 pieces per group -- as one burst behind the first group (rounds 3-5) the
             // eight pieces (~100 cycles each: two readfirstlanes, m0, the wait states) held every wave of the CU off the matrix pipe at
@@ -252,19 +234,10 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
                 issue_x_part(itl, nl % NS, (c / 2) * PER, (c / 2 + 1) * PER);
                 if (c == NCH / 2 - 2) { itl = advance(itl); tl += t_stride; ++nl; }
             }
-#else
-            if (c == 0 && more) {      // tile n + DEPTH into the buffer tile n - 1 was read from (before the previous barrier); requested
-                                       // here, between MFMA groups, not in front of the tile's first MFMA
-                issue_x(itl, nl % NS); itl = advance(itl); tl += t_stride; ++nl;
-            }
-#endif
 #pragma unroll
             for (int j = 0; j < 4; ++j)
 #pragma unroll
-                for (int pb = 0; pb < 4; ++pb) {
-                    if (BMC_C1P_ABL & 1) acc[pb][0] += wreg[c + 1][j] * xfB[pb][j];
-                    else acc[pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c + 1][j], xfB[pb][j], acc[pb], 0, 0, 0);
-                }
+                for (int pb = 0; pb < 4; ++pb) acc[pb] = __builtin_amdgcn_mfma_f32_16x16x4f32(wreg[c + 1][j], xfB[pb][j], acc[pb], 0, 0, 0);
         }
 
         // ---- epilogue
@@ -300,7 +273,7 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
         }
 #pragma unroll
         for (int pb = 0; pb < 4; ++pb)
-            if (ok[pb] && !((BMC_C1P_ABL & 2) && acc[pb][0] != 1.2345e30f)) stg16(outb + (long long)pix[pb] * a.out_pix_stride + co, acc[pb]);
+            if (ok[pb]) stg16(outb + (long long)pix[pb] * a.out_pix_stride + co, acc[pb]);
         // the next tile's pixels have landed: everything older than this tile's (at most 4) stores and the DEPTH - 1 younger
         // tiles' DMA (NCH / 2 instructions each; in the tail, where nothing was issued, the wait is merely stricter) is complete
         if (DEPTH > 1 && more) dma_wait<4 + (DEPTH - 1) * (NCH / 2)>(); else dma_wait<4>();

@@ -21,21 +21,6 @@
 #include "conv_k.h"
 #include "bf_split.h"
 
-#ifdef BMC_BF_STAMP
-// experiment builds only (tools/): cycle totals of the 1x1 kernel's step phases, wave 0 (halo role) and wave 2 (weight role)
-__device__ unsigned long long g_cstamp[16 * 1024];
-extern "C" int bmc_cstamp_read(unsigned long long* host, int n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_cstamp), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
-}
-#define ST(v) const unsigned long long v = __builtin_amdgcn_s_memtime()
-#else
-#define ST(v)
-#endif
-#ifndef BMC_BF_ABL
-#define BMC_BF_ABL 0   // ablation bits for experiment builds (tools/): 1 no epilogue stores, 4 no MFMAs, 8 no weight loads, 16 no activation loads (reads a zero constant: the
-                       // chip then clocks ~1.3x higher on the all-zero MFMA operands -- not a latency measurement), 32 no halo split + store
-#endif
-
 namespace {
 
 constexpr int CK = BMC_CK;
@@ -189,7 +174,7 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
     f32x4 xr[XD][NXLD];
     auto load_x = [&](int slot) {
         // (the byte offsets of one image of this source must fit the instruction's unsigned 32-bit lane offset)
-        if (TAPS == 1 && x_fast && (long long)a.H * a.W * spix < (1ll << 29) && !(BMC_BF_ABL & 16)) {
+        if (TAPS == 1 && x_fast && (long long)a.H * a.W * spix < (1ll << 29)) {
             // uniform, but it came through LDS (the source table): tell the compiler, so that it can live in SGPRs
             const unsigned long long sbv = reinterpret_cast<unsigned long long>(sbase + c_in);
             const unsigned sb_lo = __builtin_amdgcn_readfirstlane((unsigned)sbv), sb_hi = __builtin_amdgcn_readfirstlane((unsigned)(sbv >> 32));
@@ -206,7 +191,6 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
 #pragma unroll
             for (int n = 0; n < NXLD; ++n) {
                 const float* src = xok[n] ? base + (long long)xpix[n] * spix : g_zero4;
-                if (BMC_BF_ABL & 16) src = g_zero4;
                 if constexpr (ASMX) asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(xr[slot][n]) : "v"(src) : "memory");
                 else xr[slot][n] = ldg16(src);
             }
@@ -225,7 +209,6 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
         for (int n = 0; n < NXLD; ++n) asm volatile("" : "+v"(xr[slot][n]));
     };
     auto store_x_item = [&](int slot, int buf, int n) {
-        if (BMC_BF_ABL & 32) return;
         const int e = xt + 128 * n, hp = e >> 2;
         if ((n + 1) * 128 <= NHALO * 4 || hp < NHALO) {
             u32x2 pl[NP];
@@ -265,7 +248,7 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
 #pragma unroll
         for (int i = 0; i < PWMAX; ++i) {
             const int j = 2 * i + w2;
-            if (j < NDMA && !(BMC_BF_ABL & 8) && !(NDMA == 1 && w2))
+            if (j < NDMA && !(NDMA == 1 && w2))
                 dma16(p, dma_off[i], wb_lds + (unsigned)((wl_stage * WBUF + j * 256) * 4));
         }
         wl_stage = wl_stage == NSTG - 1 ? 0 : wl_stage + 1;
@@ -316,7 +299,6 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
         }
     };
     auto mma = [&](int pw, int px) {
-        if (BMC_BF_ABL & 4) return;
 #pragma unroll
         for (int t = 0; t < MT; ++t)
 #pragma unroll
@@ -420,7 +402,6 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
 #pragma unroll
                 for (int rq = 0; rq < 4; ++rq) {
                     const int co = co0 + 32 * u + 8 * rq;
-                    if ((BMC_BF_ABL & 1) && acc[t][u][4 * rq] != 12345.678f) continue;
                     if (pok[t] && co < a.Cout) {
                         f32x4 v;
 #pragma unroll
@@ -461,15 +442,11 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
     int stage = 0;
     if constexpr (TAPS == 1) {
         int tile = t_first, cc = 0, landed = 0;   // landed: upcoming steps whose ring slot is known to be complete
-#ifdef BMC_BF_STAMP
-        unsigned long long st_stage = 0, st_mma = 0, st_wait = 0, st_bar = 0, st_epi = 0;
-#endif
         for (int base = 0; base < total_steps; base += XD) {
 #pragma unroll
             for (int d = 0; d < XD; ++d) {
                 const int s = base + d;     // chunk s: LDS buffer s & 1; chunk c >= 1 travels through ring slot c % XD
                 if (s < total_steps) {
-                    ST(c0);
                     if (xrole) {
                         if (s + 1 < total_steps) {
                             // chunk s+1 sits in slot (d+1) % XD; younger loads in flight: chunks s+2 .. s+XD.  After a
@@ -485,10 +462,8 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
                     } else {
                         if (s + 2 < total_steps) dma_w();
                     }
-                    ST(c1);
                     read_frags(Xb + (s & 1) * XBUF, Wb + stage * WBUF, 0, 0);
                     mma_all();
-                    ST(c2);
                     const bool tile_end = cc + 1 == a.nchunks;
                     if (!xrole) {
                         // vmcnt completes in order and counts the epilogue's global stores: a wait for a slice issued
@@ -498,9 +473,7 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
                         else if (cc != 0 || s == 0) wait_older_slices();
                     }
                     stage = stage == NSTG - 1 ? 0 : stage + 1;
-                    ST(c3);
                     __syncthreads();
-                    ST(c4);
                     if (++cc == a.nchunks) {
                         // same for the halo waves: their ring loads are older than the stores about to be issued, but
                         // the compiler's static vmcnt for the next ds_write must also hold on the no-epilogue path and
@@ -510,19 +483,9 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
                         tile += t_stride;
                         cc = 0;
                     }
-#ifdef BMC_BF_STAMP
-                    { const unsigned long long c5 = __builtin_amdgcn_s_memtime();
-                      st_stage += c1 - c0; st_mma += c2 - c1; st_wait += c3 - c2; st_bar += c4 - c3; st_epi += c5 - c4; }
-#endif
                 }
             }
         }
-#ifdef BMC_BF_STAMP
-        if ((tid == 0 || tid == 128) && blockIdx.x < 1024) {
-            unsigned long long* o = g_cstamp + (blockIdx.x * 2 + (tid >> 7)) * 8;
-            o[0] = st_stage; o[1] = st_mma; o[2] = st_wait; o[3] = st_bar; o[4] = st_epi; o[5] = total_steps; o[6] = my_tiles;
-        }
-#endif
     } else {
         int gs = 0, gc = 0;
         for (int tile = t_first; tile < t_hi; tile += t_stride) {

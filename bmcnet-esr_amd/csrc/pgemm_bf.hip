@@ -21,14 +21,6 @@
 #include "bf_split.h"
 #include <type_traits>
 
-#ifdef BMC_BF_STAMP
-// experiment builds only (tools/): per-workgroup cycle totals of the producer / consumer phases
-__device__ unsigned long long g_stamp[8 * 1024];
-extern "C" int bmc_stamp_read(unsigned long long* host, int n) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_stamp), sizeof(unsigned long long) * n) == hipSuccess ? 0 : -1;
-}
-#endif
-
 namespace {
 
 typedef short s16x4 __attribute__((ext_vector_type(4)));
@@ -473,13 +465,7 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
             for (int it = 0; it < NIT; ++it) load_item(t1, it);
         }
         __syncthreads();
-#ifdef BMC_BF_STAMP
-        unsigned long long p_work = 0, p_wait = 0, p_store = 0, p_load = 0, p_t0 = __builtin_amdgcn_s_memtime();
-#endif
         for (int i = 0; i < nmine; ++i) {
-#ifdef BMC_BF_STAMP
-            const unsigned long long w0 = __builtin_amdgcn_s_memtime();
-#endif
             if (i + 1 < nmine) {
                 const TileP t2 = tile_setup(i + 2);
 #pragma unroll
@@ -489,14 +475,8 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
                     load_item(t2, it);
                 }
             }
-#ifdef BMC_BF_STAMP
-            p_work += __builtin_amdgcn_s_memtime() - w0;
-#endif
             __syncthreads();
         }
-#ifdef BMC_BF_STAMP
-        if (pt == 0 && blockIdx.x < 1024) { g_stamp[blockIdx.x * 8 + 0] = p_work; g_stamp[blockIdx.x * 8 + 1] = __builtin_amdgcn_s_memtime() - p_t0; g_stamp[blockIdx.x * 8 + 2] = nmine; g_stamp[blockIdx.x * 8 + 3] = p_wait; g_stamp[1024 * 8 - 2048 + blockIdx.x * 2] = p_store; g_stamp[1024 * 8 - 2048 + blockIdx.x * 2 + 1] = p_load; }
-#endif
         // bias: a producer thread always holds channel quad pt & 31; 8 threads per quad are folded to the 4 partial rows
         float* const red = reinterpret_cast<float*>(lds);
         if (do_bias) *reinterpret_cast<f32x4*>(red + (pt >> 5) * 128 + (pt & 31) * 4) = bsum;
@@ -539,13 +519,7 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
         return __builtin_bit_cast(bf16x8, f);
     };
     __syncthreads();
-#ifdef BMC_BF_STAMP
-    unsigned long long c_work = 0, c_t0 = __builtin_amdgcn_s_memtime();
-#endif
     for (int i = 0; i < nmine; ++i) {
-#ifdef BMC_BF_STAMP
-        const unsigned long long w0 = __builtin_amdgcn_s_memtime();
-#endif
         if (wave_active) {
             const unsigned char* const img = lds + (i & 1) * STAGE;
 #pragma unroll 1
@@ -570,14 +544,8 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
                 }
             }
         }
-#ifdef BMC_BF_STAMP
-        c_work += __builtin_amdgcn_s_memtime() - w0;
-#endif
         __syncthreads();
     }
-#ifdef BMC_BF_STAMP
-    if ((tid == 0 || tid == 256) && blockIdx.x < 1024) { g_stamp[blockIdx.x * 8 + 4 + (tid >> 8) * 2] = c_work; g_stamp[blockIdx.x * 8 + 5 + (tid >> 8) * 2] = __builtin_amdgcn_s_memtime() - c_t0; }
-#endif
     __syncthreads();                // the producers' bias fold
     if (wave_active) {
         float* const sl = a.slabs + (((long long)split * a.G + g) * 9) * a.Mpad * a.Npad;

@@ -17,14 +17,6 @@
 #include "dma_ring.h"
 #include <stdlib.h>
 
-#ifndef BMC_WINO_DMA_TAIL
-#define BMC_WINO_DMA_TAIL 1      // 1: a stage's DMA requests sit between its last two MFMA groups; 0: in front of its first
-#endif
-#ifndef BMC_WINO_ABL
-#define BMC_WINO_ABL 0     // ablation bits for tools/ builds only: 1 no MFMAs, 2 no weight DMA, 4 no halo loads, 8 no epilogue stores,
-                           // 16 no patch reads / input transform, 32 no weight fragment reads, 64 no barriers, 128 no output transform
-#endif
-
 namespace {
 
 constexpr int CK = BMC_CK;
@@ -36,7 +28,7 @@ constexpr int XROW = (HWD * RS + 63) / 64 * 64;      // halo row stride (as conv
 constexpr int XBUFA = 4096;              // floats per X buffer as allocated: 16 DMA instructions x 64 lanes x 4 floats >= 10 rows x XROW
 constexpr int BN = 128;                 // output channels per workgroup tile
 constexpr int WSTAGE = 4 * BN * CK;     // floats per weight stage: 4 positions (nu) x 128 rows x 16 channels
-constexpr int NWR = 3, DW = 2;          // weight ring: stages, stages ahead
+constexpr int NWR = 3;                  // weight ring stages
 constexpr int VSTAGE = 4 * 32 * CK;     // floats of transformed input per stage: 4 positions (nu) x 32 tiles x 16 channels
 
 // quad swizzle of 16-float LDS rows: dma_ring.h's table {0,2,3,1}[(row >> 2) & 3] -- conflict-free for the 16-row x 4-quad
@@ -192,8 +184,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
         const float* const base = sbase + c_in;
         xzm_landed = xzm;
 #pragma unroll
-        for (int k = 0; k < NXD; ++k)
-            if (!(BMC_WINO_ABL & 4)) dma16(base, xoff[k], xb_lds + (unsigned)((buf * XBUFA + (wave * NXD + k) * 256) * 4));
+        for (int k = 0; k < NXD; ++k) dma16(base, xoff[k], xb_lds + (unsigned)((buf * XBUFA + (wave * NXD + k) * 256) * 4));
         c_in += CK;
         if (++xl_chunk == nchunks) {
             xl_tile += t_stride;
@@ -233,7 +224,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
     };
     const unsigned wdst0 = wb_lds + (unsigned)(((wave >> 1) * BN * CK + (wave & 1) * 1024) * 4);
     auto issue_w = [&]() {
-        if (!(BMC_WINO_ABL & 2)) dma4k(wp, (unsigned)(lane * 16), wdst0 + (unsigned)(wslot * WSTAGE * 4));
+        dma4k(wp, (unsigned)(lane * 16), wdst0 + (unsigned)(wslot * WSTAGE * 4));
         wslot = wslot == NWR - 1 ? 0 : wslot + 1;
         wp += 4 * wrow;
         if (++wl_sub == 4 * nchunks) {
@@ -307,13 +298,6 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
     auto load_first = [&](const float* vb, const float* wb) __attribute__((always_inline)) {
 #pragma unroll
         for (int nu = 0; nu < 2; ++nu) {
-            if (BMC_WINO_ABL & 32) {
-                ufA[nu] = f32x4{1.f, 2.f, 3.f, 4.f};
-#pragma unroll
-                for (int tb = 0; tb < NTB; ++tb) { vfA[nu][tb] = f32x4{4.f, 3.f, 2.f, 1.f}; asm volatile("" : "+v"(vfA[nu][tb])); }
-                asm volatile("" : "+v"(ufA[nu]));
-                continue;
-            }
             ufA[nu] = *reinterpret_cast<const f32x4*>(wb + nu * BN * CK + woff);
 #pragma unroll
             for (int tb = 0; tb < NTB; ++tb) vfA[nu][tb] = *reinterpret_cast<const f32x4*>(vb + nu * 32 * CK + tb * 16 * CK + voff);
@@ -323,31 +307,21 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
-            for (int tb = 0; tb < NTB; ++tb) {
-                if (BMC_WINO_ABL & 1) c[tb][m] += u[m] * v[tb][m];
-                else c[tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[m], v[tb][m], c[tb], 0, 0, 0);
-            }
+            for (int tb = 0; tb < NTB; ++tb) c[tb] = __builtin_amdgcn_mfma_f32_16x16x4f32(u[m], v[tb][m], c[tb], 0, 0, 0);
     };
     // first half: everything before this stage's barrier
     auto stage_head = [&](const float* vb, const float* wb, int xi, const float* xb_n, float* vb_n, int xi_n, f32x4 (&ufB)[2],
                           f32x4 (&vfB)[2][NTB]) __attribute__((always_inline)) {
         f32x4 d[4];
-        if (!(BMC_WINO_ABL & 16)) produce_load(xb_n, xi_n, d);
+        produce_load(xb_n, xi_n, d);
         __builtin_amdgcn_sched_barrier(0);
         mfma8(acc[4 * xi + 0], ufA[0], vfA[0]);
-        if (!(BMC_WINO_ABL & 16)) produce_store(vb_n, xi_n, d);
+        produce_store(vb_n, xi_n, d);
         __builtin_amdgcn_sched_barrier(0);
         // the second half's fragments: read HERE -- 8 MFMAs (256 cycles) before the barrier's lgkmcnt(0) -- and consumed
         // behind the barrier
 #pragma unroll
         for (int nu = 0; nu < 2; ++nu) {
-            if (BMC_WINO_ABL & 32) {
-                ufB[nu] = f32x4{1.f, 2.f, 3.f, 4.f};
-#pragma unroll
-                for (int tb = 0; tb < NTB; ++tb) { vfB[nu][tb] = f32x4{4.f, 3.f, 2.f, 1.f}; asm volatile("" : "+v"(vfB[nu][tb])); }
-                asm volatile("" : "+v"(ufB[nu]));
-                continue;
-            }
             ufB[nu] = *reinterpret_cast<const f32x4*>(wb + (2 + nu) * BN * CK + woff);
 #pragma unroll
             for (int tb = 0; tb < NTB; ++tb) vfB[nu][tb] = *reinterpret_cast<const f32x4*>(vb + (2 + nu) * 32 * CK + tb * 16 * CK + voff);
@@ -365,10 +339,8 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
         __builtin_amdgcn_sched_barrier(0);
         mfma8(acc[4 * xi + 2], ufB[0], vfB[0]);
         __builtin_amdgcn_sched_barrier(0);
-        if (BMC_WINO_DMA_TAIL) {
-            issue_w();
-            if (xi == 3) load_x(xbuf);
-        }
+        issue_w();
+        if (xi == 3) load_x(xbuf);
         __builtin_amdgcn_sched_barrier(0);
         mfma8(acc[4 * xi + 3], ufB[1], vfB[1]);
         __builtin_amdgcn_sched_barrier(0);
@@ -381,20 +353,18 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
         pin_acc();
 #pragma unroll
         for (int tb = 0; tb < NTB; ++tb) {
-            if (!(BMC_WINO_ABL & 128)) {
-                // Y = A^T M A on whole accumulator quads (the four output channels of a lane at once): packed adds
-                f32x4 ta[4], y[4];
+            // Y = A^T M A on whole accumulator quads (the four output channels of a lane at once): packed adds
+            f32x4 ta[4], y[4];
 #pragma unroll
-                for (int nu = 0; nu < 4; ++nu) ta[nu] = (acc[nu][tb] + acc[4 + nu][tb]) + acc[8 + nu][tb];
-                y[0] = (ta[0] + ta[1]) + ta[2];
-                y[1] = sub4w(sub4w(ta[1], ta[2]), ta[3]);
+            for (int nu = 0; nu < 4; ++nu) ta[nu] = (acc[nu][tb] + acc[4 + nu][tb]) + acc[8 + nu][tb];
+            y[0] = (ta[0] + ta[1]) + ta[2];
+            y[1] = sub4w(sub4w(ta[1], ta[2]), ta[3]);
 #pragma unroll
-                for (int nu = 0; nu < 4; ++nu) ta[nu] = sub4w(sub4w(acc[4 + nu][tb], acc[8 + nu][tb]), acc[12 + nu][tb]);
-                y[2] = (ta[0] + ta[1]) + ta[2];
-                y[3] = sub4w(sub4w(ta[1], ta[2]), ta[3]);
+            for (int nu = 0; nu < 4; ++nu) ta[nu] = sub4w(sub4w(acc[4 + nu][tb], acc[8 + nu][tb]), acc[12 + nu][tb]);
+            y[2] = (ta[0] + ta[1]) + ta[2];
+            y[3] = sub4w(sub4w(ta[1], ta[2]), ta[3]);
 #pragma unroll
-                for (int p = 0; p < 4; ++p) acc[p][tb] = y[p];
-            }
+            for (int p = 0; p < 4; ++p) acc[p][tb] = y[p];
             pin_acc();
         }
         const int g = a.batch_per_group >= a.B ? 0 : it.b / a.batch_per_group;
@@ -471,7 +441,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
             }
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                if (pok[p] && !((BMC_WINO_ABL & 8) && v[p][0] != 12345.678f)) *reinterpret_cast<f32x4*>(outb + pix[p] * a.out_pix_stride + co) = v[p];
+                if (pok[p]) *reinterpret_cast<f32x4*>(outb + pix[p] * a.out_pix_stride + co) = v[p];
         }
         init_acc();
     };
@@ -480,10 +450,10 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
     xl_setup();
     wl_setup();
     load_x(0);
-    for (int k = 0; k < (BMC_WINO_DMA_TAIL ? NWR : DW); ++k) issue_w();          // stage g's tail requests the weights of stage g + NWR
+    for (int k = 0; k < NWR; ++k) issue_w();          // stage g's tail requests the weights of stage g + NWR
     dma_wait<0>();
     zero_x(0);
-    if (BMC_WINO_DMA_TAIL) load_x(1);                 // the halo of the second chunk: in flight across the first stages
+    load_x(1);                                        // the halo of the second chunk: in flight across the first stages
     __syncthreads();
     {
         f32x4 d[4];
@@ -504,10 +474,6 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
             const float* const xbn = Xb + ((gc + 1) & 1) * XBUFA;
 #pragma unroll
             for (int xi = 0; xi < 4; ++xi, ++gs) {
-                if (!BMC_WINO_DMA_TAIL) {
-                    issue_w();
-                    if (xi == 0) load_x((gc + 1) & 1);
-                }
                 const int nslot = rslot == NWR - 1 ? 0 : rslot + 1;
                 f32x4 ufB[2], vfB[2][NTB];
                 stage_head(Vb + (gs & 1) * VSTAGE, Wb + rslot * WSTAGE, xi, xi == 3 ? xbn : xb, Vb + ((gs + 1) & 1) * VSTAGE, (xi + 1) & 3,
@@ -515,9 +481,9 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
                 // everything but the newest DMA is complete: stage gs + 1's weights have landed (younger than them: the 4
                 // instructions of stage gs + 2's weights, and at xi = 0 the NXD halo instructions issued right behind those in the
                 // previous stage's tail); the halo itself is complete by xi = 1, in time for the production at xi = 3
-                if (BMC_WINO_DMA_TAIL ? xi == 0 : xi <= 1) dma_wait<4 + NXD>(); else dma_wait<4>();
+                if (xi == 0) dma_wait<4 + NXD>(); else dma_wait<4>();
                 if (xi == 2) zero_x((gc + 1) & 1);       // the next chunk's halo has landed (it is older than stage gs + 1)
-                if (BMC_WINO_ABL & 64) asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); else ring_publish();
+                ring_publish();
                 stage_tail(xi, Vb + ((gs + 1) & 1) * VSTAGE, Wb + nslot * WSTAGE, ufB, vfB, gc & 1);
                 rslot = nslot;
             }

@@ -38,22 +38,6 @@
 // the reduction kernel knows the MFMA's D layout and reads them back as 16-byte quads of four consecutive output channels.
 #include "bmc_common.h"
 #include "dma_ring.h"
-#include <stdlib.h>
-
-#ifndef BMC_W4G_ABL
-#define BMC_W4G_ABL 0     // ablation builds (tools/): 1 no MFMA, 2 no DMA, 4 no transforms, 8 no fragment reads, 16 every DMA from the
-                          // first stage's pixels (cache hits), 32 no wait for the DMA at the end of a stage.  libbmc_hip_w4gablNmM.so:
-                          // BMC_W4G_ABL = N, BMC_W4G_MODE = M (the DMA timetable, below)
-#endif
-
-#ifdef BMC_W4G_STAMP      // diagnostic build (tools/ only): per-wave cycle stamps of workgroup 8, iterations 40..103; phases of a stage:
-                          // 0 top, 1 after rq_begin, 2 after position 4's MFMAs, 3 after the last MFMA, 4 after the DMA wait, 5 after
-                          // the barrier
-__device__ unsigned long long g_w4g_stamp[8][64][8];
-#define W4G_STAMP(it, k) do { if (blockIdx.x == 8 && (threadIdx.x & 63) == 0 && (it) >= 40 && (it) < 104) g_w4g_stamp[threadIdx.x >> 6][(it) - 40][(k)] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define W4G_STAMP(it, k) do { } while (0)
-#endif
 
 namespace {
 
@@ -92,15 +76,10 @@ constexpr int LDSF = 2 * RAWF + 2 * SIMG;   // 153 600 bytes: 2 x 39 KB raw + 2 
 static_assert(LDSF * 4 <= 160 * 1024, "LDS budget");
 
 // The stage's timetable, in gaps: gap g follows the wave's MFMA g of the stage (position g >> 1, k-step g & 1).
-//   DMA piece j:                 gap dma_gap(j) (BMC_W4G_MODE picks the variant; NOTEBOOK.md R7.1 has the measurements)
+//   DMA piece j:                 gap dma_gap(j) = 2 j (NOTEBOOK.md R7.1 has the other timetables measured)
 //   transform, patch column c:   LDS reads at gap c, the column's combination at gap c + 3 (the reads have had ~3 MFMA gaps),
 //   transform, output step k:    gap 10 + 2 k (the along-the-row combinations and the LDS writes)
-#ifndef BMC_W4G_MODE
-#define BMC_W4G_MODE 0
-#endif
-constexpr int dma_gap(const int j) {       // 0: gaps 0, 2, 4, 6, 8; 1: 1, 4, 7, 10, 13; 2: 0 .. 4; 3: 1, 5, 9, 13, 17
-    return BMC_W4G_MODE == 1 ? 1 + 3 * j : (BMC_W4G_MODE == 2 ? j : (BMC_W4G_MODE == 3 ? 1 + 4 * j : 2 * j));
-}
+constexpr int dma_gap(const int j) { return 2 * j; }
 constexpr int TR_READ = 0, TR_COMB = 3, TR_OUT = 10;
 
 template <int I, int N>
@@ -221,7 +200,6 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
             for (int j = 0; j < PPW; ++j) pof[j] = poff[j];
         }
         if (!has_last) zm &= ~(1u << (PPW - 1));
-        if (BMC_W4G_ABL & 16) return;
         if (++nsx == a.SX) {
             nsx = 0;
             if (++nty == a.TY) { nty = 0; ++nb; }
@@ -229,7 +207,6 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
         }
     };
     auto rq_piece = [&](const int j) __attribute__((always_inline)) {
-        if (BMC_W4G_ABL & 2) return;
         if (j == PPW - 1 && !has_last) return;
         asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(pof[j]), "s"(((pxm >> j) & 1) ? rq_xs : rq_ys),
                      "s"(pla[j] + rq_lo) : "memory");
@@ -264,7 +241,6 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
     // the transform's share of gap G (compile time)
     auto tgap = [&](auto gc, const float* const raw, float* const img) __attribute__((always_inline)) {
         constexpr int G = decltype(gc)::value;
-        if (BMC_W4G_ABL & 4) return;
         constexpr int cr = G - TR_READ, cc = G - TR_COMB;
         if constexpr (cr >= 0 && cr < NC) {
 #pragma unroll
@@ -329,15 +305,12 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
         const float* const img = imgb + (it & 1) * SIMG;
         const float* const traw = rawb + ((it + 1) & 1) * RAWF;
         float* const timg = imgb + ((it + 1) & 1) * SIMG;
-        W4G_STAMP(it, 0);
         if (REQ) rq_begin(it & 1);
-        W4G_STAMP(it, 1);
         float af[3][2], bf[3][2];
         auto frag = [&](const int i) __attribute__((always_inline)) {
             const int u = i / 3, j = i - 3 * u, sl = i % 3;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                if (BMC_W4G_ABL & 8) { af[sl][ks] = 1.f + ks; bf[sl][ks] = 2.f + j; asm volatile("" : "+v"(af[sl][ks]), "+v"(bf[sl][ks])); continue; }
                 af[sl][ks] = img[aoff + (6 * u + j) * PIMG + 2 * ks * CH];
                 bf[sl][ks] = img[boff + (6 * u + j) * PIMG + 2 * ks * CH];
             }
@@ -352,8 +325,7 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
             __builtin_amdgcn_sched_barrier(0);
             W4gFor<0, 2>::run([&](auto kc) __attribute__((always_inline)) {
                 constexpr int ks = decltype(kc)::value, g = 2 * i + ks;
-                if (BMC_W4G_ABL & 1) acc[i][0] += af[i % 3][ks] * bf[i % 3][ks];
-                else acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i % 3][ks], bf[i % 3][ks], acc[i], 0, 0, 0);
+                acc[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(af[i % 3][ks], bf[i % 3][ks], acc[i], 0, 0, 0);
                 if (REQ) {
 #pragma unroll
                     for (int j = 0; j < PPW; ++j)
@@ -362,14 +334,10 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
                 if (MORE) tgap(std::integral_constant<int, g>{}, traw, timg);
                 __builtin_amdgcn_sched_barrier(0);
             });
-            if (i == 4) W4G_STAMP(it, 2);
         });
-        W4G_STAMP(it, 3);
-        if (!(BMC_W4G_ABL & 32)) dma_wait<0>();
-        W4G_STAMP(it, 4);
+        dma_wait<0>();
         if (REQ) patch(it & 1);
         ring_publish();
-        W4G_STAMP(it, 5);
     };
 
     // ---- prologue: stage st0 raw -> image 0, stage st0 + 1 requested
@@ -514,12 +482,6 @@ __global__ __launch_bounds__(RED_THREADS) void wino4_wgrad_reduce_kernel(const f
 }
 
 }  // namespace
-
-#ifdef BMC_W4G_STAMP
-extern "C" int bmc_w4g_read_stamps(unsigned long long* host) {
-    return hipMemcpyFromSymbol(host, HIP_SYMBOL(g_w4g_stamp), sizeof(unsigned long long) * 8 * 64 * 8) == hipSuccess ? 0 : -1;
-}
-#endif
 
 static long long w4g_stages(int B, int H, int W) { return (long long)B * ((H + 3) / 4) * (((W + 3) / 4 + TS - 1) / TS); }
 

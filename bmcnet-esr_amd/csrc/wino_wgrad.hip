@@ -24,14 +24,6 @@
 #include "bmc_common.h"
 #include "dma_ring.h"
 #include "wgrad_k.h"
-#include <stdlib.h>
-
-#ifndef BMC_WW_PIPE
-#define BMC_WW_PIPE 1     // 1: rows of stage s + 2 requested in the middle of stage s; 0: rows of stage s + 1 at its top
-#endif
-#ifndef BMC_WW_ABL
-#define BMC_WW_ABL 0      // ablation builds (tools/): 1 no MFMA, 2 no global loads, 4 no transform / LDS stores, 8 no fragment reads
-#endif
 
 namespace {
 
@@ -129,36 +121,29 @@ __device__ __forceinline__ void wgrad_body(const WgradK& a, float* const lds, co
     // lies outside the image: bits 0 / 1 / 2 / 3 = patch row a, patch row b, dY row 0, dY row 1, bits 8.. = first patch column
     // of the wave + 1, bit 31 = some column of the wave is outside.  Applied in produce() (the loads stay one batch in flight).
     auto load = [&]() __attribute__((always_inline)) -> unsigned {
-        unsigned zm = 0;
-        if (BMC_WW_ABL & 2) {
+        const int ty = 2 * nsy + tr;
+        const int ixw = 2 * (8 * nsx + tcw) - 1;                       // first patch column of the wave's first tile
+        const int iya = 2 * ty - 1 + ra, iyb = 2 * ty - 1 + rb;        // the two patch rows of B^T's row xi
+        const int oy0 = 2 * ty + (xi == 3 ? 1 : 0), oy1 = 2 * ty + 1;  // dY rows
+        const char* const pa = uni(xbase + min(max(iya, 0), a.H - 1) * rowb);
+        const char* const pb = uni(xbase + min(iyb, a.H - 1) * rowb);
+        const char* const q0 = uni(abase + min(oy0, a.H - 1) * rowb);
+        const char* const q1 = uni(abase + min(oy1, a.H - 1) * rowb);
+        unsigned zm = (iya < 0 || iya >= a.H ? 1u : 0u) | (iyb >= a.H ? 2u : 0u) | (oy0 >= a.H ? 4u : 0u) | (oy1 >= a.H ? 8u : 0u) |
+                      (ixw < 0 || ixw + 5 >= a.W ? 1u << 31 : 0u);
+        if (zm) zm |= (unsigned)(ixw + 1) << 8;
+        unsigned vo[4];
 #pragma unroll
-            for (int q = 0; q < 4; ++q) xa[q] = xb[q] = f32x4{1.f, 2.f, 3.f, 4.f};
-            y0[0] = y0[1] = y1[0] = y1[1] = f32x4{1.f, 2.f, 3.f, 4.f};
-        } else {
-            const int ty = 2 * nsy + tr;
-            const int ixw = 2 * (8 * nsx + tcw) - 1;                       // first patch column of the wave's first tile
-            const int iya = 2 * ty - 1 + ra, iyb = 2 * ty - 1 + rb;        // the two patch rows of B^T's row xi
-            const int oy0 = 2 * ty + (xi == 3 ? 1 : 0), oy1 = 2 * ty + 1;  // dY rows
-            const char* const pa = uni(xbase + min(max(iya, 0), a.H - 1) * rowb);
-            const char* const pb = uni(xbase + min(iyb, a.H - 1) * rowb);
-            const char* const q0 = uni(abase + min(oy0, a.H - 1) * rowb);
-            const char* const q1 = uni(abase + min(oy1, a.H - 1) * rowb);
-            zm = (iya < 0 || iya >= a.H ? 1u : 0u) | (iyb >= a.H ? 2u : 0u) | (oy0 >= a.H ? 4u : 0u) | (oy1 >= a.H ? 8u : 0u) |
-                 (ixw < 0 || ixw + 5 >= a.W ? 1u << 31 : 0u);
-            if (zm) zm |= (unsigned)(ixw + 1) << 8;
-            unsigned vo[4];
+        for (int q = 0; q < 4; ++q) vo[q] = (unsigned)min(max(ixw + 2 * hl + q, 0), a.W - 1) * (PS * 4) + (unsigned)cq * 16;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) vo[q] = (unsigned)min(max(ixw + 2 * hl + q, 0), a.W - 1) * (PS * 4) + (unsigned)cq * 16;
+        for (int q = 0; q < 4; ++q) {
+            xa[q] = ldg16(pa + vo[q]);
+            xb[q] = ldg16(pb + vo[q]);
+        }
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                xa[q] = ldg16(pa + vo[q]);
-                xb[q] = ldg16(pb + vo[q]);
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                y0[q] = ldg16(q0 + vo[q + 1]);
-                if (xi == 1 || xi == 2) y1[q] = ldg16(q1 + vo[q + 1]);
-            }
+        for (int q = 0; q < 2; ++q) {
+            y0[q] = ldg16(q0 + vo[q + 1]);
+            if (xi == 1 || xi == 2) y1[q] = ldg16(q1 + vo[q + 1]);
         }
         if (++nsx == a.SX) {
             nsx = 0;
@@ -174,7 +159,6 @@ __device__ __forceinline__ void wgrad_body(const WgradK& a, float* const lds, co
     };
     f32x4 bsum = {0.f, 0.f, 0.f, 0.f};
     auto produce = [&](float* buf, const unsigned zm) __attribute__((always_inline)) {
-        if (BMC_WW_ABL & 4) return;
         if (zm) {
             asm volatile("; image border" ::: "memory");      // (keeps this a branch: if-converted it costs selects in EVERY stage)
             const int col0 = (int)((zm >> 8) & 0x3fffff) - 1 + 2 * hl;
@@ -218,7 +202,7 @@ __device__ __forceinline__ void wgrad_body(const WgradK& a, float* const lds, co
         const unsigned zm = load();
         produce(lds, zm);
     }
-    if (BMC_WW_PIPE && st0 + 1 < st1) zmn = load();
+    if (st0 + 1 < st1) zmn = load();
     ring_publish();
     int it = 0;
     for (int st = st0; st < st1; ++st, ++it) {
@@ -232,7 +216,6 @@ __device__ __forceinline__ void wgrad_body(const WgradK& a, float* const lds, co
             for (int ks = 0; ks < 4; ++ks)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    if (BMC_WW_ABL & 8) { af[i][ks] = 1.f + i; bf[i][ks] = 2.f + ks; asm volatile("" : "+v"(af[i][ks]), "+v"(bf[i][ks])); continue; }
                     af[i][ks] = cur[aoff + ks * 4 * TROW + i * 16];
                     bf[i][ks] = cur[boff + ks * 4 * TROW + (4 * h + i) * 16];
                 }
@@ -243,18 +226,15 @@ __device__ __forceinline__ void wgrad_body(const WgradK& a, float* const lds, co
 #pragma unroll
                 for (int i = 0; i < 4; ++i)
 #pragma unroll
-                    for (int n = 0; n < 4; ++n) {
-                        if (BMC_WW_ABL & 1) acc[i][4 * h + n][0] += af[i][ks] * bf[n][ks];
-                        else acc[i][4 * h + n] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][ks], bf[n][ks], acc[i][4 * h + n], 0, 0, 0);
-                    }
+                    for (int n = 0; n < 4; ++n)
+                        acc[i][4 * h + n] = __builtin_amdgcn_mfma_f32_16x16x4f32(af[i][ks], bf[n][ks], acc[i][4 * h + n], 0, 0, 0);
         };
-        if (!BMC_WW_PIPE && st + 1 < st1) zmn = load();
         read_ab(0);
         mfma64(0);
         pin_acc();
         __builtin_amdgcn_sched_barrier(0);
         if (st + 1 < st1) produce(nxt, zmn);
-        if (BMC_WW_PIPE && st + 2 < st1) zmn = load();
+        if (st + 2 < st1) zmn = load();
         __builtin_amdgcn_sched_barrier(0);
         read_ab(1);
         mfma64(1);

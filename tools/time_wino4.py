@@ -22,7 +22,7 @@ w = torch.randn(1, Cn, CIN, 9, device=dev) * 0.03
 bias = torch.randn(1, Cn, device=dev)
 flops = 2.0 * B * H * W * Cn * 9 * CIN
 ref = None
-ONLY4 = os.environ.get("W4_ONLY") == "1"          # ablation libraries (BMC_HIP_LIB=...libbmc_hip_w4ablN.so): results are wrong by design
+ONLY4 = os.environ.get("W4_ONLY") == "1"          # the F(4x4) launch alone, no comparison against the direct kernel
 KINDS = [int(v) for v in os.environ.get("KB_KINDS", "0,2,4").split(",")]      # KB_KINDS=0,2: small launches the F(4x4) kernel does not take
 for name, wino in ((("F(4x4)", 4),) if ONLY4 else tuple(kv for kv in (("direct", 0), ("F(2x2)", 2), ("F(4x4)", 4)) if kv[1] in KINDS)):
     wp = _packed_weight(w, spec, None, wino=wino)
