@@ -101,6 +101,54 @@ def raw_events_to_channels_batch(xs_i16, ys_i16, ps_f64, offsets, flips=None, se
     return ops.encode_raw_events(xs_i16, ys_i16, ps_f64, offsets, flips, int(sensor_size[0]), int(sensor_size[1]))
 
 
+def event_window_indices(lr_ts, gt_ts, window=2048, sliding_window=1024, scale=4, dataset_length=None, mode="events"):
+    """The event blocks H5Dataset cuts a recording into for mode == 'events' (dataloader/h5dataset.py: set_data_mode
+    :164-195, compute_k_indices :197-215, get_gt_event_indices_num :362-390), from the two timestamp columns alone (numpy, on
+    the CPU) -> (lr_index [L,2], gt_index [L,2]) int64: item j is LR events [lr_index[j,0], lr_index[j,1]) and HR events
+    [gt_index[j,0], gt_index[j,1]) (what get_events / get_gt_events slice, :407-424).  The reference's quirks are kept:
+      * L = int(num_events / (window - sliding_window)), capped by dataset_length; L == 0 raises as the reference does;
+      * idx1 = idx0 + window clamped to num_events - 1: the tail blocks are shorter and the last LR event is never used;
+      * every HR block has scale^2 * (idx1 - idx0) events OF BLOCK 0, also where the LR block itself is shorter;
+      * the HR block starts at the first HR event with ts >= the LR block's first ts, found by ONE forward scan that hands
+        out each HR event at most once (base_dataset.py:39-51): a block whose start the previous block already took starts
+        one event later;
+      * an HR block that would end after num_gt_events - 1 is moved back to end there (which can push its start below zero:
+        the reference then fails in get_gt_event_indices; MultiStreamSR.open_events refuses such a table);
+      * LR blocks that start after the last HR timestamp get no HR block in the reference (its item access fails there):
+        both tables end at the last block that has one.
+    Only 'events' mode: the reference's 'time' and 'frame' modes call get_gt_event_indices_num(start_idx, end_idx) with two
+    arguments where it takes one (:231, :245) and cannot run with ground-truth events -> ValueError."""
+    import numpy as np
+    if mode != "events":
+        raise ValueError("event_window_indices: only mode='events' (the reference's %r mode cannot run with ground-truth "
+                         "events)" % (mode,))
+    lr_ts, gt_ts = np.asarray(lr_ts), np.asarray(gt_ts)
+    if lr_ts.ndim != 1 or gt_ts.ndim != 1:
+        raise ValueError("event_window_indices: lr_ts and gt_ts are 1-D timestamp columns")
+    step = int(window) - int(sliding_window)
+    if step <= 0:
+        raise ValueError("event_window_indices: window must exceed sliding_window")
+    n, n_gt = len(lr_ts), len(gt_ts)
+    L = max(int(n / step), 0)
+    if dataset_length is not None:
+        L = min(int(dataset_length), L)
+    if L <= 0:
+        raise ValueError("event_window_indices: %d events give no block of %d advancing by %d" % (n, window, step))
+    idx0 = step * np.arange(L, dtype=np.int64)
+    idx1 = np.minimum(idx0 + int(window), n - 1)
+    num_gt = int(scale) ** 2 * int(idx1[0] - idx0[0])
+    first = np.searchsorted(gt_ts, lr_ts[idx0], side="left").astype(np.int64)
+    k = np.arange(L, dtype=np.int64)
+    g0 = np.maximum.accumulate(first - k) + k              # each HR event is handed out once: g0[j] >= g0[j-1] + 1
+    keep = int(np.count_nonzero(g0 < n_gt))
+    idx0, idx1, g0 = idx0[:keep], idx1[:keep], g0[:keep]
+    g1 = g0 + num_gt
+    over = g1 > n_gt - 1
+    g1 = np.where(over, n_gt - 1, g1)
+    g0 = np.where(over, g1 - num_gt, g0)
+    return np.stack([idx0, idx1], 1), np.stack([g0, g1], 1)
+
+
 def events_to_image_torch(xs, ys, ps, device=None, sensor_size=(180, 240), clip_out_of_range=True, interpolation=None, padding=True):
     """events_to_image_torch of the reference (dataloader/encodings.py:16-73) on the GPU: same signature, same side effects
     (out-of-range events are reset in place to (0, 0) with weight 0), same summation order as its CPU index_put_ -> bit-identical.

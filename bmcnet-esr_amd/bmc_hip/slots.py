@@ -4,7 +4,11 @@ stage / commit / metrics launches of infer.MultiStreamSR, ONE launch each for al
 A slot table is S bmc_slot_t entries (SLOT_DTYPE) in a device uint8 tensor; the host fills a numpy view of a pinned copy
 (SlotTable) and uploads it with one small copy per window.  Feature states are laid out [nfeat][S][H][W][n_c]: the model's
 channels-last [S,n_c,H,W] views of state k are `to_nchw(buf[k])`, adjacent in one buffer (ops.stack_states reads them
-without a copy).  LAUNCHES counts the launches of each wrapper (the tests check that a window costs one of each)."""
+without a copy).  LAUNCHES counts the launches of each wrapper (the tests check that a window costs one of each).
+
+Event-backed slots (csrc/slot_events.hip): a second table of S bmc_slot_events_t entries (SLOT_EVENTS_DTYPE) behind the slot
+table in the same device tensor and the same pinned upload (SlotTable(events=True)); encode() builds the count images of
+every slot with an event entry in one launch, counted in ENCODE_LAUNCHES."""
 import numpy as np
 import torch
 
@@ -18,20 +22,29 @@ SLOT_DTYPE = np.dtype([("frames", "<u8"), ("gt", "<u8"), ("keep", "<u8"), ("resu
                        ("pad", "<i4")])
 assert SLOT_DTYPE.itemsize == 40
 LAUNCHES = {"stage": 0, "commit": 0, "metrics": 0}
+MAX_SEQN = 8
+MAX_ENCODE_WIDTH = 7680
+SLOT_EVENTS_DTYPE = np.dtype([("lr_xs", "<u8"), ("lr_ys", "<u8"), ("lr_ps", "<u8"), ("gt_xs", "<u8"), ("gt_ys", "<u8"),
+                              ("gt_ps", "<u8"), ("gt_range", "<i8", (2,)), ("lr_range", "<i8", (MAX_SEQN, 2))])
+assert SLOT_EVENTS_DTYPE.itemsize == 192
+ENCODE_LAUNCHES = 0
 
 
 class SlotTable:
     """A device slot table and a small ring of pinned host copies: `host()` returns the numpy entries to fill for the next
     window (cleared), `upload()` copies them to the device on the current stream.  A ring buffer is rewritten only after the
-    copy that last read it has completed, so the host never waits for the GPU to finish the window before."""
+    copy that last read it has completed, so the host never waits for the GPU to finish the window before.
+    events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy."""
 
     RING = 4
 
-    def __init__(self, S, device):
+    def __init__(self, S, device, events=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
-        nbytes = S * SLOT_DTYPE.itemsize
+        self.events = bool(events)
+        self._nslot = S * SLOT_DTYPE.itemsize
+        nbytes = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
         self._events = [None] * self.RING
@@ -41,9 +54,13 @@ class SlotTable:
         k = self._k
         if self._events[k] is not None:
             self._events[k].synchronize()
-        entries = self._pinned[k].numpy().view(SLOT_DTYPE)
-        entries[:] = 0
-        return entries
+        buf = self._pinned[k].numpy()
+        buf[:] = 0
+        return buf[:self._nslot].view(SLOT_DTYPE)
+
+    def events_host(self):
+        """The event entries of the window being filled (after host(), which cleared them)."""
+        return self._pinned[self._k].numpy()[self._nslot:].view(SLOT_EVENTS_DTYPE)
 
     def upload(self):
         k = self._k
@@ -54,6 +71,9 @@ class SlotTable:
 
     def ptr(self):
         return self.dev.data_ptr()
+
+    def events_ptr(self):
+        return self.dev.data_ptr() + self._nslot
 
 
 def _check(cond, what):
@@ -126,3 +146,22 @@ def metrics(table, pred, H, W, gh, gw, nparts):
     _check(1 <= nparts <= MAX_PARTS, "1 <= nparts <= %d" % MAX_PARTS)
     lib.call(lib._slot_metrics, "bmc_slot_metrics", table.ptr(), S, pred.data_ptr(), sH, sW, H, W, gh, gw, nparts, _stream())
     LAUNCHES["metrics"] += 1
+
+
+def encode(table, lr_scratch, gt_scratch):
+    """Every slot with an event entry: lr_scratch[s] [seqn,2,H,W] and gt_scratch[s] [2,gh,gw] <- the count images of the
+    entry's event ranges (bmc_slot_encode: one launch, integer counts, deterministic); other slots' scratch is not touched."""
+    global ENCODE_LAUNCHES
+    _check(table.events, "the slot table has no event entries (SlotTable(events=True))")
+    for t in (lr_scratch, gt_scratch):
+        _check(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == table.S,
+               "scratch must be contiguous fp32 GPU tensors [S,...]")
+    _check(lr_scratch.dim() == 5 and lr_scratch.shape[2] == 2 and gt_scratch.dim() == 4 and gt_scratch.shape[1] == 2,
+           "lr_scratch [S,seqn,2,H,W] and gt_scratch [S,2,gh,gw]")
+    S, seqn, _, H, W = lr_scratch.shape
+    gh, gw = gt_scratch.shape[2:]
+    _check(2 <= seqn <= MAX_SEQN, "2 <= seqn <= %d" % MAX_SEQN)
+    _check(max(W, gw) <= MAX_ENCODE_WIDTH, "frames wider than %d pixels are not supported" % MAX_ENCODE_WIDTH)
+    lib.call(lib._slot_encode, "bmc_slot_encode", table.events_ptr(), S, seqn, H, W, gh, gw, lr_scratch.data_ptr(),
+             gt_scratch.data_ptr(), _stream())
+    ENCODE_LAUNCHES += 1

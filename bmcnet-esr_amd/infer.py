@@ -4,11 +4,18 @@ runs one window under no_grad, and the per-window latency is measured with event
 where the reference puts its `starter/ender` pair (infer_BMCNet.py:54,66-68).
 
 MultiStreamSR runs many recordings through one model at once (slots of one batched window); evaluate_recordings is the
-reference's evaluation mode 1 on top of it."""
+reference's evaluation mode 1 on top of it.  A recording is handed over as count images (open) or as the dataset's raw event
+columns with the index tables of its blocks (open_events, EventRecording), encoded window by window on the GPU."""
 import collections
 import statistics
 
+import numpy as np
 import torch
+
+EventRecording = collections.namedtuple("EventRecording", "lr gt lr_index gt_index lr_size gt_size")
+EventRecording.__doc__ = """An event-backed recording for MultiStreamSR.open_events / evaluate_recordings: lr, gt = (xs, ys, ps)
+raw dataset columns on the GPU (int16, int16, float64); lr_index, gt_index [L,2] = the event range [first, end) of every
+item's LR / ground-truth frame (bmc_hip.encodings.event_window_indices); lr_size = (H, W), gt_size = (gh, gw)."""
 
 
 class StreamingSR:
@@ -220,8 +227,15 @@ class MultiStreamSR:
     end; results(handle) gives per-window esr_mse, bicubic_mse, time (ms, events on the launch stream around the whole
     window, shared by the slots of that window) and, with keep_predictions, the predictions [n_windows,2,sH,sW].
 
-    graph=True: from the third window on a window is ONE graph replay (stage, forward, commit, metrics captured; the slot
-    table is refreshed by one small copy before it).  Parameter updates invalidate the graph as in StreamingSR.
+    open_events(lr, gt, lr_index, gt_index, lr_size, gt_size) queues an EVENT-BACKED recording: the raw dataset columns stay
+    on the GPU (12 bytes per event instead of 8 bytes per pixel of every frame) and the frames of a window are encoded on the
+    fly by bmc_slot_encode -- one more launch per window for all slots, into per-slot scratch that the slot's table entry
+    points at; the other kernels do not know the difference, and the results are bit-identical to open() on the frames the
+    raw-column encoder (ops.encode_raw_events, no flips) gives for the same ranges.  The encode launch is issued only once an
+    event-backed recording has been opened; both kinds may share a session.
+
+    graph=True: from the third window on a window is ONE graph replay ([encode,] stage, forward, commit, metrics captured; the
+    slot table is refreshed by one small copy before it); the first open_events after a capture invalidates the graph.  Parameter updates invalidate the graph as in StreamingSR.
     state_dtype=torch.bfloat16: the feature states rest in bf16 between windows, as StreamingSR(state_dtype=bf16)."""
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
@@ -243,6 +257,7 @@ class MultiStreamSR:
         self._steps = []           # (start, end) events per window
         self._calls = 0
         self._graph = self._stamp = None
+        self._has_events = False
 
     # ---------------------------------------------------------------- recordings
     def open(self, frames, gts, gt_size=None):
@@ -259,20 +274,99 @@ class MultiStreamSR:
         H, W, gh, gw = frames.shape[2], frames.shape[3], gts.shape[2], gts.shape[3]
         if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
             raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
+        self._set_size("open", H, W, gh, gw)
+        return self._add({"frames": frames.contiguous(), "gts": gts.contiguous()}, L, frames.device)
+
+    def _set_size(self, who, H, W, gh, gw):
         if self._size is None:
             self._size = (H, W, gh, gw)
         elif self._size != (H, W, gh, gw):
-            raise ValueError("MultiStreamSR.open: sizes %s differ from the first recording's %s (group recordings by sensor "
-                             "size)" % ((H, W, gh, gw), self._size))
-        nwin = L - self.seqn + 1
-        sH, sW = self.scale * H, self.scale * W
+            raise ValueError("MultiStreamSR.%s: sizes %s differ from the first recording's %s (group recordings by sensor "
+                             "size)" % (who, (H, W, gh, gw), self._size))
+
+    def _add(self, rec, L, device):
+        """Queue a recording of L items (frames or event blocks) -> handle."""
         from bmc_hip import slots
-        rec = {"frames": frames.contiguous(), "gts": gts.contiguous(), "n": nwin, "steps": [],
-               "sse": torch.zeros(nwin, slots.metric_parts(gh, gw), 2, dtype=torch.float64, device=frames.device),
-               "keep": torch.empty(nwin, 2, sH, sW, device=frames.device) if self.keep_predictions else None}
+        H, W, gh, gw = self._size
+        nwin = L - self.seqn + 1
+        rec.update(n=nwin, steps=[], device=device,
+                   sse=torch.zeros(nwin, slots.metric_parts(gh, gw), 2, dtype=torch.float64, device=device),
+                   keep=torch.empty(nwin, 2, self.scale * H, self.scale * W, device=device) if self.keep_predictions else None)
         h = self.sched.add(nwin)
         self._recs[h] = rec
         return h
+
+    MAX_SEQN_EVENTS = 8          # bmc_slot_events_t holds the ranges of at most 8 LR frames (BMC_SLOT_MAX_SEQN)
+    MAX_WIDTH_EVENTS = 7680      # bmc_slot_encode: one row of both channels must fit a workgroup's LDS band
+
+    def open_events(self, lr, gt, lr_index, gt_index, lr_size, gt_size):
+        """Queue one event-backed recording -> handle.  lr, gt = (xs, ys, ps): the raw dataset columns of the LR and the
+        ground-truth stream (1-D int16, int16, float64 GPU tensors; polarities -1 / 0 / +1); lr_index, gt_index [L,2]
+        (integers, on the host): item j is LR events [lr_index[j,0], lr_index[j,1]) and ground-truth events [gt_index[j,0],
+        gt_index[j,1]) -- bmc_hip.encodings.event_window_indices gives the reference's tables.  Window i reads the LR frames of
+        items i .. i+seqn-1 and the ground truth of item i+1, as open() on the encoded frames.  Every range is checked here
+        against the column lengths: the kernel trusts the table."""
+        who = "MultiStreamSR.open_events: "
+        for name, cols in (("lr", lr), ("gt", gt)):
+            if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
+                raise ValueError(who + "%s must be three tensors (xs, ys, ps)" % name)
+            if [t.dtype for t in cols] != [torch.int16, torch.int16, torch.float64]:
+                raise ValueError(who + "%s columns must be int16, int16, float64 (got %s)" % (name, [t.dtype for t in cols]))
+            if any(t.dim() != 1 or t.numel() != cols[0].numel() or not t.is_contiguous() for t in cols):
+                raise ValueError(who + "%s columns must be contiguous 1-D tensors of one length" % name)
+        tables = []
+        for name, idx, n in (("lr_index", lr_index, lr[0].numel()), ("gt_index", gt_index, gt[0].numel())):
+            a = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx)
+            if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
+                raise ValueError(who + "%s must be an integer [L,2] table (got %s %s)" % (name, a.dtype, a.shape))
+            a = a.astype(np.int64)
+            if (a[:, 0] > a[:, 1]).any():
+                raise ValueError(who + "%s has a range with first > end" % name)
+            if a.size and (a.min() < 0 or a.max() > n):
+                raise ValueError(who + "%s has a range outside the %d events of its columns" % (name, n))
+            tables.append(a)
+        lr_index, gt_index = tables
+        if len(lr_index) != len(gt_index):
+            raise ValueError(who + "lr_index has %d rows, gt_index %d" % (len(lr_index), len(gt_index)))
+        L = len(lr_index)
+        if L < self.seqn:
+            raise ValueError(who + "%d items, fewer than one window of seqn = %d" % (L, self.seqn))
+        if self.seqn > self.MAX_SEQN_EVENTS:
+            raise ValueError(who + "seqn <= %d for event-backed recordings" % self.MAX_SEQN_EVENTS)
+        try:
+            (H, W), (gh, gw) = (int(v) for v in lr_size), (int(v) for v in gt_size)
+        except (TypeError, ValueError):
+            raise ValueError(who + "lr_size = (H, W) and gt_size = (gh, gw)") from None
+        if min(H, W, gh, gw) < 1 or max(W, gw) > self.MAX_WIDTH_EVENTS:
+            raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)"
+                             % (self.MAX_WIDTH_EVENTS, (H, W), (gh, gw)))
+        cols = tuple(lr) + tuple(gt)
+        if not all(t.is_cuda and t.device == cols[0].device for t in cols):
+            raise ValueError(who + "the columns must be GPU tensors on one device")
+        for name, ps in (("lr", lr[2]), ("gt", gt[2])):
+            if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
+                raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
+        self._set_size("open_events", H, W, gh, gw)
+        h = self._add({"lr": tuple(lr), "gt": tuple(gt), "lr_index": lr_index, "gt_index": gt_index}, L, cols[0].device)
+        if not self._has_events:
+            self._has_events = True
+            if self._bufs is not None:                     # a running frames-only session: the table grows an event part
+                self._event_buffers(self._bufs, cols[0].device)
+                self.invalidate()
+        return h
+
+    def resident_bytes(self, handle):
+        """Bytes the recording keeps on the GPU: its columns (event-backed) or frames, its result sums and kept predictions."""
+        r = self._recs[handle]
+        data = r["lr"] + r["gt"] if "lr" in r else (r["frames"], r["gts"])
+        return sum(t.numel() * t.element_size() for t in data + (r["sse"],) + (() if r["keep"] is None else (r["keep"],)))
+
+    def scratch_bytes(self):
+        """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened)."""
+        if not self._has_events:
+            return 0
+        H, W, gh, gw = self._size
+        return 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
 
     def results(self, handle):
         """-> dict(esr_mse=[...], bicubic_mse=[...], time=[...] per window done so far[, predictions=[n,2,sH,sW]])."""
@@ -297,7 +391,9 @@ class MultiStreamSR:
             from bmc_hip import slots
             b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
                  "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
-                 "table": slots.SlotTable(S, device)}
+                 "table": slots.SlotTable(S, device, events=self._has_events)}
+            if self._has_events:
+                self._event_buffers(b, device)
             if self.state_dtype is None:
                 b["pool"] = b["feat"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device)       # the model reads the pool
             else:
@@ -306,16 +402,26 @@ class MultiStreamSR:
             self._bufs = b
         return self._bufs
 
+    def _event_buffers(self, b, device):
+        from bmc_hip import slots
+        H, W, gh, gw = self._size
+        if not b["table"].events:
+            b["table"] = slots.SlotTable(self.S, device, events=True)
+        b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
+        b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
+
     def _forward(self):
         b = self._bufs
         states = [t.permute(0, 3, 1, 2) for t in b["feat"]]             # channels-last [S,n_c,H,W] views, adjacent
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """stage -> model -> commit -> metrics (what a graph replay runs)."""
+        """[encode ->] stage -> model -> commit -> metrics (what a graph replay runs)."""
         from bmc_hip import slots
         b = self._bufs
         H, W, gh, gw = self._size
+        if "lr_scratch" in b:
+            slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
         slots.stage(b["table"], b["x"], b["pool"], b["feat"], b["pred"])
         out = self._forward()
         cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.contiguous(memory_format=torch.channels_last)
@@ -351,15 +457,24 @@ class MultiStreamSR:
         from bmc_hip import slots
         H, W, gh, gw = self._size
         first = next(self._recs[p[0]] for p in plan if p is not None)
-        b = self._buffers(first["frames"].device)
+        b = self._buffers(first["device"])
         e = b["table"].host()
+        ev = b["table"].events_host() if b["table"].events else None
         for s, p in enumerate(plan):
             if p is None:
                 continue
             h, i, reset = p
             r = self._recs[h]
-            e[s]["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
-            e[s]["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * gh * gw
+            if "lr" in r:                                  # event-backed: the entry points at the slot's scratch images
+                e[s]["frames"] = b["lr_scratch"][s].data_ptr()
+                e[s]["gt"] = b["gt_scratch"][s].data_ptr()
+                for k, t in zip(("lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps"), r["lr"] + r["gt"]):
+                    ev[k][s] = t.data_ptr()
+                ev["lr_range"][s, :self.seqn] = r["lr_index"][i:i + self.seqn]
+                ev["gt_range"][s] = r["gt_index"][i + 1]
+            else:
+                e[s]["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
+                e[s]["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * gh * gw
             e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
             e[s]["result"] = r["sse"][i].data_ptr()
             e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
@@ -390,7 +505,8 @@ class MultiStreamSR:
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
-    (or a sequence of such pairs, named "0", "1", ...) of one sensor size.  -> dict(
+    (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
+    columns + index tables, encoded window by window: MultiStreamSR.open_events).  -> dict(
       results = {metric: {name: value}}  per recording the mean over its windows of esr_mse, bicubic_mse, time (ms), and
                                          params (millions) -- infer_body's MetricTracker result (:34,:70-86),
       mean    = {metric: mean over recordings}  (results_mean, :284-291)[,
@@ -398,7 +514,15 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn)
-    handles = [(name, ms.open(frames, gts, gt_size)) for name, (frames, gts) in items]
+    handles = []
+    for name, r in items:
+        if isinstance(r, EventRecording):
+            if gt_size is not None and tuple(int(v) for v in gt_size) != tuple(int(v) for v in r.gt_size):
+                raise ValueError("evaluate_recordings: gt_size %s differs from recording %s's %s"
+                                 % (tuple(gt_size), name, tuple(r.gt_size)))
+            handles.append((name, ms.open_events(*r)))
+        else:
+            handles.append((name, ms.open(r[0], r[1], gt_size)))
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
     breakdown = collections.defaultdict(dict)

@@ -482,6 +482,33 @@ int bmc_slot_commit(const bmc_slot_t* table, int S, const float* const* feat_src
 int bmc_slot_metrics(const bmc_slot_t* table, int S, const float* pred, int sH, int sW, int H, int W, int gh, int gw,
                      int nparts, bmc_stream_t s);
 
+/* Event-backed slots (MultiStreamSR.open_events): the recording stays on the GPU as raw dataset columns (xs / ys int16, ps
+ * float64, generate_dataset/tools/event_packagers.py:128-156) and the window's count images are encoded on the fly into
+ * per-slot scratch that the slot's bmc_slot_t entry points at (frames = lr_scratch[s], gt = gt_scratch[s]) -- replaces
+ * H5Dataset.__getitem__ (dataloader/h5dataset.py:261-316) for the windows that compute_k_indices / get_gt_event_indices_num
+ * (:197-215, :362-390) cut.  A second DEVICE table of S entries, parallel to the slot table; lr_xs NULL: the slot has no event
+ * entry (empty, or frame-backed).  Every range [first, end) must lie inside its columns: the kernel trusts the table, the
+ * host validates the ranges when a recording is opened. */
+#define BMC_SLOT_MAX_SEQN 8
+typedef struct bmc_slot_events {
+    const short* lr_xs;     /* LR columns of the slot's recording */
+    const short* lr_ys;
+    const double* lr_ps;
+    const short* gt_xs;     /* HR (ground-truth) columns */
+    const short* gt_ys;
+    const double* gt_ps;
+    long long gt_range[2];                      /* events [first, end) of the window's ground-truth frame (frame 1 of the window) */
+    long long lr_range[BMC_SLOT_MAX_SEQN][2];   /* events [first, end) of the window's LR frames 0 .. seqn-1 (they may overlap) */
+} bmc_slot_events_t;
+/* ONE launch for all slots with an event entry, before bmc_slot_stage: lr_scratch [S][seqn][2][H][W] and gt_scratch
+ * [S][2][gh][gw] <- the count images of the ranges, bit-identical to bmc_encode_raw_events without flips (out-of-range quirk
+ * included) for integer-valued polarities (+-1 in the datasets; a weight p*p is counted as an integer).  Slots without an
+ * entry are not touched.  A workgroup owns a band of rows of one frame: zeroed in LDS, counted with integer LDS atomics,
+ * stored once (the store is the zero fill) -- no global float atomics, no memset, order independent and run-to-run identical.
+ * W, gw <= 7680; 2 <= seqn <= BMC_SLOT_MAX_SEQN. */
+int bmc_slot_encode(const bmc_slot_events_t* table, int S, int seqn, int H, int W, int gh, int gw, float* lr_scratch,
+                    float* gt_scratch, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

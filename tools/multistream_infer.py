@@ -3,8 +3,13 @@
 eager and graph replay, next to StreamingSR at batch 1 in the same process.  Per configuration: the per-window latency
 (median of the events around each window, the reference's `time` metric) and the aggregate windows/s (slot-windows over the
 wall time of the timed windows, ended by a device synchronise; every slot busy in every timed window).
+--events adds, per configuration, the same session on EVENT-BACKED recordings (open_events: synthetic raw columns, LR blocks of
+2 048 events advancing by 1 024, ground-truth blocks of 32 768): its latency and windows/s, the encode launch alone
+(bmc_slot_encode on the session's last table, events around 20 launches) with its share of the window, and the bytes one
+recording keeps on the GPU either way.
 
-python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--out FILE]"""
+python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
+                                  [--modes eager,graph] [--out FILE]"""
 import argparse
 import json
 import os
@@ -30,9 +35,42 @@ def streaming(m, frames, graph, warmup, windows):
     return statistics.median(t), 1e3 * len(t) / sum(t)
 
 
-def multistream(m, recs, S, graph, warmup, windows):
+def event_recording(L, H, W, seed):
+    """Synthetic raw columns of L items on the CPU -> the arguments of open_events."""
+    import numpy as np
+    from bmc_hip.encodings import event_window_indices
+    rng = np.random.default_rng(seed)
+    n_lr = 1024 * L + 1
+    n_gt = 16 * n_lr
+    cols = []
+    for n, h, w in ((n_lr, H, W), (n_gt, 4 * H, 4 * W)):
+        cols.append((torch.from_numpy(rng.integers(0, w, n).astype(np.int16)), torch.from_numpy(rng.integers(0, h, n).astype(np.int16)),
+                     torch.from_numpy(rng.choice([-1.0, 1.0], n))))
+    lr_index, gt_index = event_window_indices(np.sort(rng.uniform(0, 1, n_lr)), np.sort(rng.uniform(0, 1, n_gt)), 2048, 1024, 4)
+    return cols[0], cols[1], lr_index, gt_index, (H, W), (4 * H, 4 * W)
+
+
+def encode_alone(ms, reps=20):
+    """ms per bmc_slot_encode launch on the session's buffers (the table of its last window)."""
+    from bmc_hip import slots
+    b = ms._bufs
+    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
+    a.record()
+    for _ in range(reps):
+        slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
+    z.record()
+    z.synchronize()
+    return a.elapsed_time(z) / reps
+
+
+def multistream(m, recs, S, graph, warmup, windows, events=False):
     ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN)
-    hs = [ms.open(f, g) for f, g in recs[:S]]
+    if events:
+        dev = next(m.parameters()).device
+        hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
+    else:
+        hs = [ms.open(f, g) for f, g in recs[:S]]
     for _ in range(warmup):
         ms.step()
     torch.cuda.synchronize()
@@ -42,7 +80,9 @@ def multistream(m, recs, S, graph, warmup, windows):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     lat = statistics.median(ms.results(hs[0])["time"][warmup:])
-    return lat, S * windows / wall
+    if events:
+        return lat, S * windows / wall, encode_alone(ms), ms.resident_bytes(hs[0])
+    return lat, S * windows / wall, ms.resident_bytes(hs[0])
 
 
 def main():
@@ -51,6 +91,8 @@ def main():
     ap.add_argument("--slots", default="1,8,32")
     ap.add_argument("--windows", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=4)
+    ap.add_argument("--events", action="store_true")
+    ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -64,17 +106,24 @@ def main():
         slots = [int(s) for s in a.slots.split(",")]
         recs = [(torch.poisson(torch.full((L, 2, H, W), 0.284), generator=g).to(dev),
                  torch.poisson(torch.full((L, 2, 4 * H, 4 * W), 0.1), generator=g).to(dev)) for _ in range(max(slots))]
-        for graph in (False, True):
-            mode = "graph" if graph else "eager"
+        erecs = [event_recording(L, H, W, H * W + k) for k in range(max(slots))] if a.events else None
+        for mode in a.modes.split(","):
+            graph = mode == "graph"
             lat, wps = streaming(m, recs[0][0], graph, a.warmup, a.windows)
             rows.append(dict(size=size, mode=mode, runner="StreamingSR", slots=1, ms_per_window=round(lat, 3),
                              windows_per_s=round(wps, 1)))
             print(json.dumps(rows[-1]), flush=True)
             for S in slots:
-                lat, wps = multistream(m, recs, S, graph, a.warmup, a.windows)
+                lat, wps, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows)
                 rows.append(dict(size=size, mode=mode, runner="MultiStreamSR", slots=S, ms_per_window=round(lat, 3),
-                                 windows_per_s=round(wps, 1)))
+                                 windows_per_s=round(wps, 1), resident_bytes=nbytes))
                 print(json.dumps(rows[-1]), flush=True)
+                if a.events:
+                    lat, wps, enc, nbytes = multistream(m, erecs, S, graph, a.warmup, a.windows, events=True)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(events)", slots=S, ms_per_window=round(lat, 3),
+                                     windows_per_s=round(wps, 1), encode_ms=round(enc, 4), encode_share=round(enc / lat, 4),
+                                     resident_bytes=nbytes))
+                    print(json.dumps(rows[-1]), flush=True)
                 torch.cuda.empty_cache()
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
