@@ -188,3 +188,56 @@ def events_to_voxel_torch(xs, ys, ts, ps, B, device=None, sensor_size=(180, 240)
     lib.call(lib._ev_vox_torch, "bmc_events_to_voxel_torch", xs.data_ptr(), ys.data_ptr(), ts.data_ptr(), ps.data_ptr(), n, B, H, W,
              out.data_ptr(), ws.data_ptr(), ops._stream())
     return out
+
+
+def counts_to_events(pred, max_count=255):
+    """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
+    (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in
+    the flat order of [2,sH,sW]: q = min(rint(v), max_count) for v > 0, else 0 (round-half-to-even: the rounded count image the
+    reference renders, infer_BMCNet.py:94), q events xs = x, ys = sH-1-row, ps = +1 (channel 0) / -1 (channel 1) -- encoding
+    image b's events at (sH, sW) without flips gives q back.  bmc_slot_emit on a temporary slot table, twice: a pass that only
+    counts (capacity 0) sizes the columns and gives every image its start, the second pass writes."""
+    from . import slots
+    if not (torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.dtype == torch.float32):
+        raise ValueError("counts_to_events: pred must be an fp32 [B,2,sH,sW] tensor")
+    if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= slots.MAX_COUNT_LIMIT:
+        raise ValueError("counts_to_events: max_count must be an integer, 1 <= max_count <= %d (got %r)"
+                         % (slots.MAX_COUNT_LIMIT, max_count))
+    if not pred.is_cuda:
+        raise RuntimeError("counts_to_events: pred must live on the MI355X (no CPU fallback in this build)")
+    pred = pred.contiguous()
+    B, _, sH, sW = pred.shape
+    dev = pred.device
+    nparts = slots.emit_parts(sH, sW)
+    groups = [(a, min(a + slots.MAX_SLOTS, B)) for a in range(0, B, slots.MAX_SLOTS)]
+    tables = {b - a: slots.SlotTable(b - a, dev, emit=True) for a, b in groups}
+    parts = torch.zeros(min(B, slots.MAX_SLOTS) * nparts, dtype=torch.int32, device=dev)
+    start = torch.zeros(B, dtype=torch.int64, device=dev)
+    end = torch.zeros(B, dtype=torch.int64, device=dev)
+
+    def run(xs, ys, ps, capacity):
+        for a, b in groups:
+            t = tables[b - a]
+            e = t.host()
+            em = t.emit_host()
+            for s in range(b - a):
+                e[s]["frames"], e[s]["flags"] = pred.data_ptr(), slots.ACTIVE
+                em[s]["xs"], em[s]["ys"], em[s]["ps"] = xs.data_ptr(), ys.data_ptr(), ps.data_ptr()
+                em[s]["index_in"], em[s]["index_out"] = start.data_ptr() + 8 * (a + s), end.data_ptr() + 8 * (a + s)
+                em[s]["capacity"] = capacity
+            t.upload()
+            slots.emit(t, pred[a:b], max_count, nparts, parts)
+
+    none = (torch.empty(1, dtype=torch.int16, device=dev), torch.empty(1, dtype=torch.int16, device=dev),
+            torch.empty(1, dtype=torch.int8, device=dev))
+    run(*none, 0)                                          # start = 0: end[b] = the events of image b; nothing is stored
+    index = torch.zeros(B + 1, dtype=torch.int64)
+    index[1:] = end.cpu().cumsum(0)
+    total = int(index[B])
+    if total == 0:
+        return none[0][:0], none[1][:0], none[2][:0], index
+    xs, ys = torch.empty(total, dtype=torch.int16, device=dev), torch.empty(total, dtype=torch.int16, device=dev)
+    ps = torch.empty(total, dtype=torch.int8, device=dev)
+    start.copy_(index[:B])
+    run(xs, ys, ps, total)
+    return xs, ys, ps, index

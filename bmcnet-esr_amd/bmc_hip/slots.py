@@ -8,7 +8,11 @@ without a copy).  LAUNCHES counts the launches of each wrapper (the tests check 
 
 Event-backed slots (csrc/slot_events.hip): a second table of S bmc_slot_events_t entries (SLOT_EVENTS_DTYPE) behind the slot
 table in the same device tensor and the same pinned upload (SlotTable(events=True)); encode() builds the count images of
-every slot with an event entry in one launch, counted in ENCODE_LAUNCHES."""
+every slot with an event entry in one launch, counted in ENCODE_LAUNCHES.
+
+Event output (csrc/slot_emit.hip): a third table of S bmc_slot_emit_t entries (SLOT_EMIT_DTYPE) behind the other two, same
+upload (SlotTable(emit=True)); emit() turns the predictions of every slot with an emit entry into events appended to the
+entry's columns (one call = two launches for all slots, counted in EMIT_LAUNCHES)."""
 import numpy as np
 import torch
 
@@ -28,23 +32,32 @@ SLOT_EVENTS_DTYPE = np.dtype([("lr_xs", "<u8"), ("lr_ys", "<u8"), ("lr_ps", "<u8
                               ("gt_ps", "<u8"), ("gt_range", "<i8", (2,)), ("lr_range", "<i8", (MAX_SEQN, 2))])
 assert SLOT_EVENTS_DTYPE.itemsize == 192
 ENCODE_LAUNCHES = 0
+MAX_EMIT_PARTS = 1024
+MAX_COUNT_LIMIT = 32767            # counts and coordinates of emitted events fit int16
+SLOT_EMIT_DTYPE = np.dtype([("xs", "<u8"), ("ys", "<u8"), ("ps", "<u8"), ("index_in", "<u8"), ("index_out", "<u8"),
+                            ("capacity", "<i8")])
+assert SLOT_EMIT_DTYPE.itemsize == 48
+EMIT_LAUNCHES = 0
 
 
 class SlotTable:
     """A device slot table and a small ring of pinned host copies: `host()` returns the numpy entries to fill for the next
     window (cleared), `upload()` copies them to the device on the current stream.  A ring buffer is rewritten only after the
     copy that last read it has completed, so the host never waits for the GPU to finish the window before.
-    events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy."""
+    events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy.
+    emit=True: S bmc_slot_emit_t entries follow those (`emit_host()`, `emit_ptr()`), same copy."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False):
+    def __init__(self, S, device, events=False, emit=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
         self.events = bool(events)
+        self.emit = bool(emit)
         self._nslot = S * SLOT_DTYPE.itemsize
-        nbytes = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
+        self._nevents = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
+        nbytes = self._nevents + (S * SLOT_EMIT_DTYPE.itemsize if emit else 0)
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
         self._events = [None] * self.RING
@@ -60,7 +73,11 @@ class SlotTable:
 
     def events_host(self):
         """The event entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nslot:].view(SLOT_EVENTS_DTYPE)
+        return self._pinned[self._k].numpy()[self._nslot:self._nevents].view(SLOT_EVENTS_DTYPE)
+
+    def emit_host(self):
+        """The emit entries of the window being filled (after host(), which cleared them)."""
+        return self._pinned[self._k].numpy()[self._nevents:].view(SLOT_EMIT_DTYPE)
 
     def upload(self):
         k = self._k
@@ -74,6 +91,9 @@ class SlotTable:
 
     def events_ptr(self):
         return self.dev.data_ptr() + self._nslot
+
+    def emit_ptr(self):
+        return self.dev.data_ptr() + self._nevents
 
 
 def _check(cond, what):
@@ -165,3 +185,33 @@ def encode(table, lr_scratch, gt_scratch):
     lib.call(lib._slot_encode, "bmc_slot_encode", table.events_ptr(), S, seqn, H, W, gh, gw, lr_scratch.data_ptr(),
              gt_scratch.data_ptr(), _stream())
     ENCODE_LAUNCHES += 1
+
+
+def emit_parts(sH, sW):
+    """Workgroups per slot of bmc_slot_emit for a [2,sH,sW] prediction (chunks of about 4 096 elements -- four tiles of a
+    workgroup --, at most 1 024: 338 at 720x960, more than the chip has CUs, so one slot alone fills it)."""
+    return max(1, min(MAX_EMIT_PARTS, -(-2 * sH * sW // 4096)))
+
+
+def emit(table, pred, max_count, nparts, parts):
+    """Every active slot with an emit entry: the events of pred[s] ([2,sH,sW]; q = min(rint(v), max_count) for v > 0, else 0;
+    q events (x, sH-1-row, +1 / -1 by channel) per element in flat order) are appended to the entry's columns at *index_in,
+    *index_out <- *index_in + their number (bmc_slot_emit: a count and a write launch for all slots, deterministic).
+    parts: int32 scratch of at least S * nparts words."""
+    global EMIT_LAUNCHES
+    _check(table.emit, "the slot table has no emit entries (SlotTable(emit=True))")
+    _check(isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_LIMIT, "1 <= max_count <= %d (got %r)"
+           % (MAX_COUNT_LIMIT, max_count))
+    _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
+    _check(torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.is_cuda and pred.is_contiguous()
+           and pred.dtype == torch.float32 and pred.shape[0] == table.S, "pred must be a contiguous fp32 GPU tensor [S,2,sH,sW]")
+    S, _, sH, sW = pred.shape
+    _check(max(sH, sW) <= MAX_COUNT_LIMIT, "predictions larger than %d pixels a side cannot be emitted (int16 coordinates)"
+           % MAX_COUNT_LIMIT)
+    _check(torch.is_tensor(parts) and parts.is_cuda and parts.dtype == torch.int32 and parts.is_contiguous()
+           and parts.numel() >= S * nparts, "parts must be a contiguous int32 GPU tensor of at least S * nparts words")
+    _check((-(-2 * sH * sW // nparts) + 3) // 4 * 4 * max_count < 2 ** 32,
+           "a part's event total would overflow 32 bits: use more parts")
+    lib.call(lib._slot_emit, "bmc_slot_emit", table.ptr(), table.emit_ptr(), S, pred.data_ptr(), sH, sW, max_count, nparts,
+             parts.data_ptr(), _stream())
+    EMIT_LAUNCHES += 1

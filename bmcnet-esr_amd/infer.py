@@ -5,7 +5,8 @@ where the reference puts its `starter/ender` pair (infer_BMCNet.py:54,66-68).
 
 MultiStreamSR runs many recordings through one model at once (slots of one batched window); evaluate_recordings is the
 reference's evaluation mode 1 on top of it.  A recording is handed over as count images (open) or as the dataset's raw event
-columns with the index tables of its blocks (open_events, EventRecording), encoded window by window on the GPU."""
+columns with the index tables of its blocks (open_events, EventRecording), encoded window by window on the GPU.  With
+emit_events the result leaves the same way: the super-resolved event stream of every window, in the dataset's column format."""
 import collections
 import statistics
 
@@ -236,19 +237,35 @@ class MultiStreamSR:
 
     graph=True: from the third window on a window is ONE graph replay ([encode,] stage, forward, commit, metrics captured; the
     slot table is refreshed by one small copy before it); the first open_events after a capture invalidates the graph.  Parameter updates invalidate the graph as in StreamingSR.
-    state_dtype=torch.bfloat16: the feature states rest in bf16 between windows, as StreamingSR(state_dtype=bf16)."""
+    state_dtype=torch.bfloat16: the feature states rest in bf16 between windows, as StreamingSR(state_dtype=bf16).
+
+    emit_events=True: every window's prediction is also turned into an EVENT LIST on the GPU (bmc_slot_emit: two more launches
+    per window for all slots, inside the captured graph too) and appended to the recording's own output columns: per element v
+    of the prediction [2,sH,sW] in flat order, q = min(rint(v), max_count) for v > 0 (else 0; round-half-to-even -- the rounded
+    count image the reference renders, infer_BMCNet.py:94) events xs = x, ys = sH-1-row, ps = +1 (channel 0) / -1 (channel 1),
+    so that encoding a window's events at (sH, sW) gives q back exactly.  results() then carries sr_events = (xs int16, ys int16,
+    ps int8) and sr_index [done+1] (window i owns events [sr_index[i], sr_index[i+1])); no timestamps: a count image has no time
+    inside the window.  The columns hold `event_capacity` events (open / open_events; default 2 x scale^2 x the recording's LR
+    events); the index keeps counting past it, and results() then raises with the capacity that is needed.  About 5 bytes per
+    event instead of 8 x sH x sW bytes per window of keep_predictions; both may be on."""
+
+    MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
-                 seqn=3):
+                 seqn=3, emit_events=False, max_count=255):
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
         if seqn < 2:
             raise ValueError("MultiStreamSR: seqn >= 2 (the model reads frames 0 and 1 of a window)")
+        if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= self.MAX_COUNT_LIMIT:
+            raise ValueError("MultiStreamSR: max_count must be an integer, 1 <= max_count <= %d (got %r)"
+                             % (self.MAX_COUNT_LIMIT, max_count))
         self.model = model.eval()
         self.S, self.n_c, self.scale, self.plain, self.seqn = int(slots), n_c, scale, plain, int(seqn)
         self.use_graph = graph
         self.state_dtype = None if state_dtype is torch.float32 else state_dtype
         self.keep_predictions = keep_predictions
+        self.emit_events, self.max_count = bool(emit_events), max_count
         self.sched = SlotScheduler(self.S)
         self.replays = 0
         self._recs = {}
@@ -260,9 +277,19 @@ class MultiStreamSR:
         self._has_events = False
 
     # ---------------------------------------------------------------- recordings
-    def open(self, frames, gts, gt_size=None):
+    def _check_capacity(self, who, event_capacity):
+        if event_capacity is None:
+            return
+        if not self.emit_events:
+            raise ValueError("MultiStreamSR.%s: event_capacity needs a session with emit_events=True" % who)
+        if isinstance(event_capacity, bool) or not isinstance(event_capacity, (int, np.integer)) or event_capacity < 1:
+            raise ValueError("MultiStreamSR.%s: event_capacity must be a positive integer (got %r)" % (who, event_capacity))
+
+    def open(self, frames, gts, gt_size=None, event_capacity=None):
         """Queue one recording -> handle.  frames [L,2,H,W], gts [L,2,gh,gw] (fp32, on the GPU); gt_size (the reference's
-        gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size."""
+        gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size.  event_capacity (emit_events):
+        events the output columns hold; default 2 x scale^2 x the sum of `frames` (one device reduction here)."""
+        self._check_capacity("open", event_capacity)
         if frames.dim() != 4 or frames.shape[1] != 2 or gts.dim() != 4 or tuple(gts.shape[:2]) != (frames.shape[0], 2):
             raise ValueError("MultiStreamSR.open: frames [L,2,H,W] and gts [L,2,gh,gw] (got %s, %s)"
                              % (tuple(frames.shape), tuple(gts.shape)))
@@ -274,8 +301,13 @@ class MultiStreamSR:
         H, W, gh, gw = frames.shape[2], frames.shape[3], gts.shape[2], gts.shape[3]
         if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
             raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
+        if max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT and self.emit_events:
+            raise ValueError("MultiStreamSR.open: predictions of %d x %d cannot be emitted (int16 coordinates)"
+                             % (self.scale * H, self.scale * W))
         self._set_size("open", H, W, gh, gw)
-        return self._add({"frames": frames.contiguous(), "gts": gts.contiguous()}, L, frames.device)
+        if self.emit_events and event_capacity is None:
+            event_capacity = 2 * self.scale ** 2 * int(frames.sum(dtype=torch.float64).item())
+        return self._add({"frames": frames.contiguous(), "gts": gts.contiguous()}, L, frames.device, event_capacity)
 
     def _set_size(self, who, H, W, gh, gw):
         if self._size is None:
@@ -284,7 +316,7 @@ class MultiStreamSR:
             raise ValueError("MultiStreamSR.%s: sizes %s differ from the first recording's %s (group recordings by sensor "
                              "size)" % (who, (H, W, gh, gw), self._size))
 
-    def _add(self, rec, L, device):
+    def _add(self, rec, L, device, event_capacity=None):
         """Queue a recording of L items (frames or event blocks) -> handle."""
         from bmc_hip import slots
         H, W, gh, gw = self._size
@@ -292,6 +324,12 @@ class MultiStreamSR:
         rec.update(n=nwin, steps=[], device=device,
                    sse=torch.zeros(nwin, slots.metric_parts(gh, gw), 2, dtype=torch.float64, device=device),
                    keep=torch.empty(nwin, 2, self.scale * H, self.scale * W, device=device) if self.keep_predictions else None)
+        if self.emit_events:                               # the recording's output stream: three columns and the index table
+            cap = max(int(event_capacity), 1)
+            rec.update(ev_capacity=cap, ev_xs=torch.empty(cap, dtype=torch.int16, device=device),
+                       ev_ys=torch.empty(cap, dtype=torch.int16, device=device),
+                       ev_ps=torch.empty(cap, dtype=torch.int8, device=device),
+                       ev_index=torch.zeros(nwin + 1, dtype=torch.int64, device=device))
         h = self.sched.add(nwin)
         self._recs[h] = rec
         return h
@@ -299,14 +337,16 @@ class MultiStreamSR:
     MAX_SEQN_EVENTS = 8          # bmc_slot_events_t holds the ranges of at most 8 LR frames (BMC_SLOT_MAX_SEQN)
     MAX_WIDTH_EVENTS = 7680      # bmc_slot_encode: one row of both channels must fit a workgroup's LDS band
 
-    def open_events(self, lr, gt, lr_index, gt_index, lr_size, gt_size):
+    def open_events(self, lr, gt, lr_index, gt_index, lr_size, gt_size, event_capacity=None):
         """Queue one event-backed recording -> handle.  lr, gt = (xs, ys, ps): the raw dataset columns of the LR and the
         ground-truth stream (1-D int16, int16, float64 GPU tensors; polarities -1 / 0 / +1); lr_index, gt_index [L,2]
         (integers, on the host): item j is LR events [lr_index[j,0], lr_index[j,1]) and ground-truth events [gt_index[j,0],
         gt_index[j,1]) -- bmc_hip.encodings.event_window_indices gives the reference's tables.  Window i reads the LR frames of
         items i .. i+seqn-1 and the ground truth of item i+1, as open() on the encoded frames.  Every range is checked here
-        against the column lengths: the kernel trusts the table."""
+        against the column lengths: the kernel trusts the table.  event_capacity (emit_events): events the output columns
+        hold; default 2 x scale^2 x the sum of the lengths of the LR item ranges."""
         who = "MultiStreamSR.open_events: "
+        self._check_capacity("open_events", event_capacity)
         for name, cols in (("lr", lr), ("gt", gt)):
             if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
                 raise ValueError(who + "%s must be three tensors (xs, ys, ps)" % name)
@@ -340,6 +380,9 @@ class MultiStreamSR:
         if min(H, W, gh, gw) < 1 or max(W, gw) > self.MAX_WIDTH_EVENTS:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)"
                              % (self.MAX_WIDTH_EVENTS, (H, W), (gh, gw)))
+        if self.emit_events and max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
+            raise ValueError(who + "predictions of %d x %d cannot be emitted (int16 coordinates)"
+                             % (self.scale * H, self.scale * W))
         cols = tuple(lr) + tuple(gt)
         if not all(t.is_cuda and t.device == cols[0].device for t in cols):
             raise ValueError(who + "the columns must be GPU tensors on one device")
@@ -347,7 +390,10 @@ class MultiStreamSR:
             if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
                 raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
         self._set_size("open_events", H, W, gh, gw)
-        h = self._add({"lr": tuple(lr), "gt": tuple(gt), "lr_index": lr_index, "gt_index": gt_index}, L, cols[0].device)
+        if self.emit_events and event_capacity is None:
+            event_capacity = 2 * self.scale ** 2 * int((lr_index[:, 1] - lr_index[:, 0]).sum())
+        h = self._add({"lr": tuple(lr), "gt": tuple(gt), "lr_index": lr_index, "gt_index": gt_index}, L, cols[0].device,
+                      event_capacity)
         if not self._has_events:
             self._has_events = True
             if self._bufs is not None:                     # a running frames-only session: the table grows an event part
@@ -356,9 +402,12 @@ class MultiStreamSR:
         return h
 
     def resident_bytes(self, handle):
-        """Bytes the recording keeps on the GPU: its columns (event-backed) or frames, its result sums and kept predictions."""
+        """Bytes the recording keeps on the GPU: its columns (event-backed) or frames, its result sums, kept predictions and
+        (emit_events) its output columns with their index."""
         r = self._recs[handle]
         data = r["lr"] + r["gt"] if "lr" in r else (r["frames"], r["gts"])
+        if "ev_xs" in r:
+            data = tuple(data) + (r["ev_xs"], r["ev_ys"], r["ev_ps"], r["ev_index"])
         return sum(t.numel() * t.element_size() for t in data + (r["sse"],) + (() if r["keep"] is None else (r["keep"],)))
 
     def scratch_bytes(self):
@@ -369,7 +418,9 @@ class MultiStreamSR:
         return 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
 
     def results(self, handle):
-        """-> dict(esr_mse=[...], bicubic_mse=[...], time=[...] per window done so far[, predictions=[n,2,sH,sW]])."""
+        """-> dict(esr_mse=[...], bicubic_mse=[...], time=[...] per window done so far[, predictions=[n,2,sH,sW]][,
+        sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host]).  Raises RuntimeError when
+        the windows emitted more events than the recording's event_capacity (the message names the capacity needed)."""
         r = self._recs[handle]
         done = len(r["steps"])
         if done:
@@ -381,6 +432,15 @@ class MultiStreamSR:
                "time": [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]}
         if self.keep_predictions:
             out["predictions"] = r["keep"][:done]
+        if self.emit_events:
+            index = r["ev_index"][:done + 1].cpu()
+            total = int(index[done])
+            if total > r["ev_capacity"]:
+                raise RuntimeError("MultiStreamSR.results: recording %d emitted %d events in %d windows, more than its "
+                                   "event_capacity of %d: open it with event_capacity >= %d"
+                                   % (handle, total, done, r["ev_capacity"], total))
+            out["sr_events"] = (r["ev_xs"][:total], r["ev_ys"][:total], r["ev_ps"][:total])
+            out["sr_index"] = index
         return out
 
     # ---------------------------------------------------------------- windows
@@ -391,7 +451,10 @@ class MultiStreamSR:
             from bmc_hip import slots
             b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
                  "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
-                 "table": slots.SlotTable(S, device, events=self._has_events)}
+                 "table": slots.SlotTable(S, device, events=self._has_events, emit=self.emit_events)}
+            if self.emit_events:
+                b["emit_parts"] = torch.zeros(S * slots.emit_parts(self.scale * H, self.scale * W), dtype=torch.int32,
+                                              device=device)
             if self._has_events:
                 self._event_buffers(b, device)
             if self.state_dtype is None:
@@ -406,7 +469,7 @@ class MultiStreamSR:
         from bmc_hip import slots
         H, W, gh, gw = self._size
         if not b["table"].events:
-            b["table"] = slots.SlotTable(self.S, device, events=True)
+            b["table"] = slots.SlotTable(self.S, device, events=True, emit=self.emit_events)
         b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
         b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
 
@@ -416,7 +479,7 @@ class MultiStreamSR:
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """[encode ->] stage -> model -> commit -> metrics (what a graph replay runs)."""
+        """[encode ->] stage -> model -> commit -> metrics [-> emit] (what a graph replay runs)."""
         from bmc_hip import slots
         b = self._bufs
         H, W, gh, gw = self._size
@@ -427,6 +490,9 @@ class MultiStreamSR:
         cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.contiguous(memory_format=torch.channels_last)
         slots.commit(b["table"], [cl(t) for t in out[:-1]], b["pool"], out[-1].contiguous(), b["pred"])
         slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
+        if self.emit_events:
+            slots.emit(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
+                       b["emit_parts"])
 
     def _weights_stamp(self):
         return tuple((id(p), p._version) for p in self.model.parameters())
@@ -460,6 +526,7 @@ class MultiStreamSR:
         b = self._buffers(first["device"])
         e = b["table"].host()
         ev = b["table"].events_host() if b["table"].events else None
+        em = b["table"].emit_host() if self.emit_events else None
         for s, p in enumerate(plan):
             if p is None:
                 continue
@@ -478,6 +545,11 @@ class MultiStreamSR:
             e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
             e[s]["result"] = r["sse"][i].data_ptr()
             e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
+            if em is not None:                             # window i appends at index[i] and leaves index[i+1]
+                em[s]["xs"], em[s]["ys"], em[s]["ps"] = r["ev_xs"].data_ptr(), r["ev_ys"].data_ptr(), r["ev_ps"].data_ptr()
+                em[s]["index_in"] = r["ev_index"].data_ptr() + 8 * i
+                em[s]["index_out"] = r["ev_index"].data_ptr() + 8 * (i + 1)
+                em[s]["capacity"] = r["ev_capacity"]
             r["steps"].append(len(self._steps))
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
@@ -503,30 +575,33 @@ class MultiStreamSR:
 
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
-                        gt_size=None, keep_predictions=False):
+                        gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  -> dict(
       results = {metric: {name: value}}  per recording the mean over its windows of esr_mse, bicubic_mse, time (ms), and
                                          params (millions) -- infer_body's MetricTracker result (:34,:70-86),
       mean    = {metric: mean over recordings}  (results_mean, :284-291)[,
-      predictions = {name: [n_windows,2,sH,sW]}  with keep_predictions])."""
+      predictions = {name: [n_windows,2,sH,sW]}  with keep_predictions][,
+      sr_events   = {name: (xs, ys, ps, index [n_windows+1])}  with emit_events: the super-resolved event stream of every
+                                         recording (MultiStreamSR(emit_events=True); event_capacity: per recording, None =
+                                         the default)])."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
-                       keep_predictions=keep_predictions, seqn=seqn)
+                       keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
             if gt_size is not None and tuple(int(v) for v in gt_size) != tuple(int(v) for v in r.gt_size):
                 raise ValueError("evaluate_recordings: gt_size %s differs from recording %s's %s"
                                  % (tuple(gt_size), name, tuple(r.gt_size)))
-            handles.append((name, ms.open_events(*r)))
+            handles.append((name, ms.open_events(*r, event_capacity=event_capacity)))
         else:
-            handles.append((name, ms.open(r[0], r[1], gt_size)))
+            handles.append((name, ms.open(r[0], r[1], gt_size, event_capacity=event_capacity)))
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
     breakdown = collections.defaultdict(dict)
-    preds = {}
+    preds, streams = {}, {}
     for name, h in handles:
         r = ms.results(h)
         for k in ("esr_mse", "bicubic_mse", "time"):
@@ -534,7 +609,11 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
         breakdown["params"][name] = params
         if keep_predictions:
             preds[name] = r["predictions"]
+        if emit_events:
+            streams[name] = r["sr_events"] + (r["sr_index"],)
     out = {"results": dict(breakdown), "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items()}}
     if keep_predictions:
         out["predictions"] = preds
+    if emit_events:
+        out["sr_events"] = streams
     return out

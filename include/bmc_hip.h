@@ -509,6 +509,33 @@ typedef struct bmc_slot_events {
 int bmc_slot_encode(const bmc_slot_events_t* table, int S, int seqn, int H, int W, int gh, int gw, float* lr_scratch,
                     float* gt_scratch, bmc_stream_t s);
 
+/* Event OUTPUT of the slots (MultiStreamSR(emit_events=True)): the window's prediction leaves the session as an event list
+ * appended to the recording's own output columns -- the rounded count image the reference renders (infer_BMCNet.py:94:
+ * esr_cnt[0].cpu().round()), clamped, as the stream whose encoding gives that image back.  Per element v of pred[s]
+ * [2][sH][sW], visited in flat order:  q = v > 0 ? min(rint(v), max_count) : 0  (round-half-to-even on the fp32 value; NaN ->
+ * 0, +inf -> max_count); element (c, row, x) contributes q consecutive events xs = x, ys = sH-1-row, ps = c == 0 ? +1 : -1
+ * (the inverse of bmc_slot_encode / bmc_encode_raw_events without flips: encoding the emitted events at (sH, sW) gives q).
+ * A third DEVICE table of S entries, parallel to the slot table; xs NULL (or an inactive slot): the slot emits nothing.
+ * The event at global position g of the recording is stored at xs[g], ys[g], ps[g] when g < capacity and dropped otherwise;
+ * *index_out = *index_in + the window's event count ALWAYS (the true running count, also past the capacity).  index_in and
+ * index_out must be different words (entries i and i+1 of the recording's index table). */
+typedef struct bmc_slot_emit {
+    short* xs;                  /* output columns of the slot's recording, `capacity` entries each */
+    short* ys;
+    signed char* ps;
+    const long long* index_in;  /* events emitted before this window */
+    long long* index_out;       /* ... and after it */
+    long long capacity;
+} bmc_slot_emit_t;
+/* TWO launches for all slots, grid (nparts, S), after the forward pass: a count pass (part p sums q over elements [p*chunk,
+ * (p+1)*chunk) of the slot, chunk = ceil(2*sH*sW / nparts) rounded up to 4, into parts[s][p]) and a write pass (part p starts
+ * at *index_in + the parts before it, scans its chunk and stores the events at their final positions).  No workgroup waits for
+ * another, no atomics; integer counts, the same bytes run after run.  parts: S x nparts words of scratch.  sH, sW <= 32767
+ * (int16 coordinates); 1 <= max_count <= 32767; 1 <= nparts <= BMC_SLOT_EMIT_MAX_PARTS and chunk * max_count < 2^32. */
+#define BMC_SLOT_EMIT_MAX_PARTS 1024
+int bmc_slot_emit(const bmc_slot_t* table, const bmc_slot_emit_t* emit, int S, const float* pred, int sH, int sW, int max_count,
+                  int nparts, unsigned* parts, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -7,9 +7,14 @@ wall time of the timed windows, ended by a device synchronise; every slot busy i
 2 048 events advancing by 1 024, ground-truth blocks of 32 768): its latency and windows/s, the encode launch alone
 (bmc_slot_encode on the session's last table, events around 20 launches) with its share of the window, and the bytes one
 recording keeps on the GPU either way.
+--emit-events adds, per configuration, the frame-backed session with the event OUTPUT on (emit_events=True): its latency and
+windows/s, the bmc_slot_emit call alone (both kernels, events around 20 calls on the session's last table and prediction),
+the events of its last window, and the bytes the recording keeps resident with events against with dense predictions.
+--resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
+with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
-                                  [--modes eager,graph] [--out FILE]"""
+                                  [--emit-events] [--resident-windows N] [--modes eager,graph] [--out FILE]"""
 import argparse
 import json
 import os
@@ -64,8 +69,25 @@ def encode_alone(ms, reps=20):
     return a.elapsed_time(z) / reps
 
 
-def multistream(m, recs, S, graph, warmup, windows, events=False):
-    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN)
+def emit_alone(ms, reps=20):
+    """ms per bmc_slot_emit call (count + write kernel) on the session's buffers: the table and prediction of its last window.
+    The repeated calls append nothing new: the entries' index words are the last window's."""
+    from bmc_hip import slots
+    b = ms._bufs
+    H, W = ms._size[:2]
+    args = (b["table"], b["pred"], ms.max_count, slots.emit_parts(ms.scale * H, ms.scale * W), b["emit_parts"])
+    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    slots.emit(*args)
+    a.record()
+    for _ in range(reps):
+        slots.emit(*args)
+    z.record()
+    z.synchronize()
+    return a.elapsed_time(z) / reps
+
+
+def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False):
+    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
@@ -80,6 +102,11 @@ def multistream(m, recs, S, graph, warmup, windows, events=False):
     torch.cuda.synchronize()
     wall = time.perf_counter() - t0
     lat = statistics.median(ms.results(hs[0])["time"][warmup:])
+    if emit:
+        index = ms.results(hs[0])["sr_index"]
+        dense = MultiStreamSR(m, S, n_c=128, scale=4, seqn=SEQN, keep_predictions=True)
+        return (lat, S * windows / wall, emit_alone(ms), int(index[-1] - index[-2]), ms.resident_bytes(hs[0]),
+                dense.resident_bytes(dense.open(*recs[0])))
     if events:
         return lat, S * windows / wall, encode_alone(ms), ms.resident_bytes(hs[0])
     return lat, S * windows / wall, ms.resident_bytes(hs[0])
@@ -92,6 +119,8 @@ def main():
     ap.add_argument("--windows", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--events", action="store_true")
+    ap.add_argument("--emit-events", action="store_true")
+    ap.add_argument("--resident-windows", type=int, default=0)
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -107,6 +136,17 @@ def main():
         recs = [(torch.poisson(torch.full((L, 2, H, W), 0.284), generator=g).to(dev),
                  torch.poisson(torch.full((L, 2, 4 * H, 4 * W), 0.1), generator=g).to(dev)) for _ in range(max(slots))]
         erecs = [event_recording(L, H, W, H * W + k) for k in range(max(slots))] if a.events else None
+        if a.resident_windows:
+            r = event_recording(a.resident_windows + SEQN - 1, H, W, 1)
+            r = (tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1])) + r[2:]
+            row = dict(size=size, runner="resident", windows=a.resident_windows)
+            for key, kw in (("input_only", {}), ("dense_predictions", dict(keep_predictions=True)), ("event_output", dict(emit_events=True))):
+                ms = MultiStreamSR(m, 1, n_c=128, scale=4, seqn=SEQN, **kw)
+                row[key + "_bytes"] = ms.resident_bytes(ms.open_events(*r))
+                del ms
+                torch.cuda.empty_cache()
+            rows.append(row)
+            print(json.dumps(row), flush=True)
         for mode in a.modes.split(","):
             graph = mode == "graph"
             lat, wps = streaming(m, recs[0][0], graph, a.warmup, a.windows)
@@ -123,6 +163,12 @@ def main():
                     rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(events)", slots=S, ms_per_window=round(lat, 3),
                                      windows_per_s=round(wps, 1), encode_ms=round(enc, 4), encode_share=round(enc / lat, 4),
                                      resident_bytes=nbytes))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.emit_events:
+                    lat, wps, emi, nev, nbytes, dense = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(emit)", slots=S, ms_per_window=round(lat, 3),
+                                     windows_per_s=round(wps, 1), emit_ms=round(emi, 4), emit_share=round(emi / lat, 4),
+                                     events_last_window=nev, resident_bytes=nbytes, resident_bytes_dense=dense))
                     print(json.dumps(rows[-1]), flush=True)
                 torch.cuda.empty_cache()
     if a.out:
