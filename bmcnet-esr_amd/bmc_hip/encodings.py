@@ -190,19 +190,28 @@ def events_to_voxel_torch(xs, ys, ts, ps, B, device=None, sensor_size=(180, 240)
     return out
 
 
-def counts_to_events(pred, max_count=255):
+def counts_to_events(pred, max_count=255, times=None):
     """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
     (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in
     the flat order of [2,sH,sW]: q = min(rint(v), max_count) for v > 0, else 0 (round-half-to-even: the rounded count image the
     reference renders, infer_BMCNet.py:94), q events xs = x, ys = sH-1-row, ps = +1 (channel 0) / -1 (channel 1) -- encoding
     image b's events at (sH, sW) without flips gives q back.  bmc_slot_emit on a temporary slot table, twice: a pass that only
-    counts (capacity 0) sizes the columns and gives every image its start, the second pass writes."""
+    counts (capacity 0) sizes the columns and gives every image its start, the second pass writes.
+    times="linear" (max_count <= 255): -> (xs, ys, ps, ts float32, index); event j of an element's n events has the time
+    float32(0.01 + 0.99 * j / (n - 1)) (0.01 for n = 1) and every image's events are sorted by the exact j / (n - 1), ties in
+    the flat order above -- the reference's linear redistribution (dataloader/encodings.py:367-414) with one time bin, by
+    bmc_slot_emit_timed (include/bmc_hip.h states the contract)."""
     from . import slots
+    if times not in (None, "linear"):
+        raise ValueError("counts_to_events: times must be None or 'linear' (got %r)" % (times,))
+    timed = times is not None
     if not (torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.dtype == torch.float32):
         raise ValueError("counts_to_events: pred must be an fp32 [B,2,sH,sW] tensor")
     if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= slots.MAX_COUNT_LIMIT:
         raise ValueError("counts_to_events: max_count must be an integer, 1 <= max_count <= %d (got %r)"
                          % (slots.MAX_COUNT_LIMIT, max_count))
+    if timed and max_count > slots.MAX_COUNT_TIMED:
+        raise ValueError("counts_to_events: times='linear' needs max_count <= %d (got %d)" % (slots.MAX_COUNT_TIMED, max_count))
     if not pred.is_cuda:
         raise RuntimeError("counts_to_events: pred must live on the MI355X (no CPU fallback in this build)")
     pred = pred.contiguous()
@@ -210,12 +219,13 @@ def counts_to_events(pred, max_count=255):
     dev = pred.device
     nparts = slots.emit_parts(sH, sW)
     groups = [(a, min(a + slots.MAX_SLOTS, B)) for a in range(0, B, slots.MAX_SLOTS)]
-    tables = {b - a: slots.SlotTable(b - a, dev, emit=True) for a, b in groups}
+    tables = {b - a: slots.SlotTable(b - a, dev, emit=True, timed=timed) for a, b in groups}
     parts = torch.zeros(min(B, slots.MAX_SLOTS) * nparts, dtype=torch.int32, device=dev)
     start = torch.zeros(B, dtype=torch.int64, device=dev)
     end = torch.zeros(B, dtype=torch.int64, device=dev)
 
-    def run(xs, ys, ps, capacity):
+    def run(xs, ys, ps, capacity, ts=None, window=1):
+        scratch = None
         for a, b in groups:
             t = tables[b - a]
             e = t.host()
@@ -225,19 +235,33 @@ def counts_to_events(pred, max_count=255):
                 em[s]["xs"], em[s]["ys"], em[s]["ps"] = xs.data_ptr(), ys.data_ptr(), ps.data_ptr()
                 em[s]["index_in"], em[s]["index_out"] = start.data_ptr() + 8 * (a + s), end.data_ptr() + 8 * (a + s)
                 em[s]["capacity"] = capacity
+                if timed:
+                    em[s]["ts"] = ts.data_ptr()
             t.upload()
-            slots.emit(t, pred[a:b], max_count, nparts, parts)
+            if timed:                                      # (the counting pass sorts nothing: window = 1, capacity = 0)
+                if scratch is None:
+                    scratch = torch.empty(slots.emit_timed_scratch_bytes(min(B, slots.MAX_SLOTS), nparts, window),
+                                          dtype=torch.uint8, device=dev)
+                slots.emit_timed(t, pred[a:b], max_count, nparts, parts, scratch, window)
+            else:
+                slots.emit(t, pred[a:b], max_count, nparts, parts)
 
     none = (torch.empty(1, dtype=torch.int16, device=dev), torch.empty(1, dtype=torch.int16, device=dev),
             torch.empty(1, dtype=torch.int8, device=dev))
-    run(*none, 0)                                          # start = 0: end[b] = the events of image b; nothing is stored
+    no_ts = torch.empty(1, dtype=torch.float32, device=dev)
+    run(*none, 0, no_ts)                                   # start = 0: end[b] = the events of image b; nothing is stored
     index = torch.zeros(B + 1, dtype=torch.int64)
-    index[1:] = end.cpu().cumsum(0)
+    counts = end.cpu()
+    index[1:] = counts.cumsum(0)
     total = int(index[B])
     if total == 0:
-        return none[0][:0], none[1][:0], none[2][:0], index
+        return (none[0][:0], none[1][:0], none[2][:0]) + ((no_ts[:0],) if timed else ()) + (index,)
     xs, ys = torch.empty(total, dtype=torch.int16, device=dev), torch.empty(total, dtype=torch.int16, device=dev)
     ps = torch.empty(total, dtype=torch.int8, device=dev)
     start.copy_(index[:B])
+    if timed:
+        ts = torch.empty(total, dtype=torch.float32, device=dev)
+        run(xs, ys, ps, total, ts, int(counts.max()))
+        return xs, ys, ps, ts, index
     run(xs, ys, ps, total)
     return xs, ys, ps, index

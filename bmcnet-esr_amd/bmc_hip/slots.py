@@ -12,7 +12,11 @@ every slot with an event entry in one launch, counted in ENCODE_LAUNCHES.
 
 Event output (csrc/slot_emit.hip): a third table of S bmc_slot_emit_t entries (SLOT_EMIT_DTYPE) behind the other two, same
 upload (SlotTable(emit=True)); emit() turns the predictions of every slot with an emit entry into events appended to the
-entry's columns (one call = two launches for all slots, counted in EMIT_LAUNCHES)."""
+entry's columns (one call = two launches for all slots, counted in EMIT_LAUNCHES).
+
+Timed event output (csrc/slot_emit_timed.hip): SlotTable(emit=True, timed=True) holds bmc_slot_emit_timed_t entries
+(SLOT_EMIT_TIMED_DTYPE: the same fields and a `ts` column) instead; emit_timed() appends every window's events with their
+float32 times, in time order (one call = EMIT_TIMED_KERNELS launches for all slots, counted in EMIT_TIMED_LAUNCHES)."""
 import numpy as np
 import torch
 
@@ -38,6 +42,14 @@ SLOT_EMIT_DTYPE = np.dtype([("xs", "<u8"), ("ys", "<u8"), ("ps", "<u8"), ("index
                             ("capacity", "<i8")])
 assert SLOT_EMIT_DTYPE.itemsize == 48
 EMIT_LAUNCHES = 0
+SLOT_EMIT_TIMED_DTYPE = np.dtype(SLOT_EMIT_DTYPE.descr + [("ts", "<u8")])
+assert SLOT_EMIT_TIMED_DTYPE.itemsize == 56
+EMIT_TIMED_LAUNCHES = 0
+EMIT_TIMED_KERNELS = 6             # launches of one bmc_slot_emit_timed call: count, scan, expand, histogram, scan, scatter
+MAX_COUNT_TIMED = 255              # the rank table of the timed mode
+MAX_WINDOW_CAPACITY = 1 << 28
+EVENT_T0, EVENT_T1 = 0.01, 1.0     # BMC_EVENT_T0 / BMC_EVENT_T1: the window's time axis
+_RANK_TABLES = {}
 
 
 class SlotTable:
@@ -45,19 +57,24 @@ class SlotTable:
     window (cleared), `upload()` copies them to the device on the current stream.  A ring buffer is rewritten only after the
     copy that last read it has completed, so the host never waits for the GPU to finish the window before.
     events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy.
-    emit=True: S bmc_slot_emit_t entries follow those (`emit_host()`, `emit_ptr()`), same copy."""
+    emit=True: S bmc_slot_emit_t entries follow those (`emit_host()`, `emit_ptr()`), same copy; with timed=True they are
+    bmc_slot_emit_timed_t entries."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False, emit=False):
+    def __init__(self, S, device, events=False, emit=False, timed=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
         self.events = bool(events)
         self.emit = bool(emit)
+        self.timed = bool(timed)
+        if self.timed and not self.emit:
+            raise ValueError("slots: timed=True needs emit=True")
+        self._emit_dtype = SLOT_EMIT_TIMED_DTYPE if self.timed else SLOT_EMIT_DTYPE
         self._nslot = S * SLOT_DTYPE.itemsize
         self._nevents = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
-        nbytes = self._nevents + (S * SLOT_EMIT_DTYPE.itemsize if emit else 0)
+        nbytes = self._nevents + (S * self._emit_dtype.itemsize if emit else 0)
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
         self._events = [None] * self.RING
@@ -77,7 +94,7 @@ class SlotTable:
 
     def emit_host(self):
         """The emit entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nevents:].view(SLOT_EMIT_DTYPE)
+        return self._pinned[self._k].numpy()[self._nevents:].view(self._emit_dtype)
 
     def upload(self):
         k = self._k
@@ -200,6 +217,7 @@ def emit(table, pred, max_count, nparts, parts):
     parts: int32 scratch of at least S * nparts words."""
     global EMIT_LAUNCHES
     _check(table.emit, "the slot table has no emit entries (SlotTable(emit=True))")
+    _check(not getattr(table, "timed", False), "the slot table has timed emit entries: use emit_timed()")
     _check(isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_LIMIT, "1 <= max_count <= %d (got %r)"
            % (MAX_COUNT_LIMIT, max_count))
     _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
@@ -215,3 +233,72 @@ def emit(table, pred, max_count, nparts, parts):
     lib.call(lib._slot_emit, "bmc_slot_emit", table.ptr(), table.emit_ptr(), S, pred.data_ptr(), sH, sW, max_count, nparts,
              parts.data_ptr(), _stream())
     EMIT_LAUNCHES += 1
+
+
+def emit_rank_table_np():
+    """[256][256] uint16: table[n][j] (0 <= j < n) = the dense rank of the rational j / (n - 1) (0 for n = 1) among all
+    fractions p/d with 1 <= d <= 254, 0 <= p <= d -- the sort key of the timed event output (include/bmc_hip.h).  Integer
+    arithmetic only: floor(j * 2^40 / (n - 1)) is equal for equal rationals, and distinct ones (at least 1 / (254 * 253)
+    apart) differ by more than 10^7, so the ranks of the distinct floors are the ranks of the rationals."""
+    n, j = np.meshgrid(np.arange(256, dtype=np.int64), np.arange(256, dtype=np.int64), indexing="ij")
+    valid = (j < n) & (n >= 2)
+    key = np.where(valid, (j << 40) // np.maximum(n - 1, 1), 0)       # n = 1, j = 0: the rational 0
+    ranks = np.unique(key[valid], return_inverse=True)[1]
+    table = np.zeros((256, 256), np.int64)
+    table[valid] = ranks
+    assert table.max() < 1 << 16
+    return table.astype(np.uint16)
+
+
+def emit_rank_table(device):
+    """The rank table on `device` (uploaded once per device; int16 storage of the uint16 bits)."""
+    device = torch.device(device)
+    if device not in _RANK_TABLES:
+        _RANK_TABLES[device] = torch.from_numpy(emit_rank_table_np().view(np.int16)).to(device)
+    return _RANK_TABLES[device]
+
+
+def _check_window_capacity(window_capacity):
+    _check(not isinstance(window_capacity, bool) and isinstance(window_capacity, (int, np.integer))
+           and 1 <= window_capacity <= MAX_WINDOW_CAPACITY,
+           "window_capacity must be an integer, 1 <= window_capacity <= %d (got %r)" % (MAX_WINDOW_CAPACITY, window_capacity))
+
+
+def emit_timed_scratch_bytes(S, nparts, window_capacity):
+    """Bytes of sort scratch of emit_timed for S slots: 8 per event of window_capacity per slot, and the digit histograms."""
+    _check(1 <= S <= MAX_SLOTS, "1 <= S <= %d" % MAX_SLOTS)
+    _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
+    _check_window_capacity(window_capacity)
+    return int(lib._slot_emit_timed_ws(S, nparts, int(window_capacity)))
+
+
+def emit_timed(table, pred, max_count, nparts, parts, scratch, window_capacity):
+    """emit() with times, every window in time order (bmc_slot_emit_timed; include/bmc_hip.h states the contract): event j of
+    an element with n events has t = float32(T0 + (T1 - T0) * j / (n - 1)); the window is sorted by the exact rational
+    j / (n - 1), ties in flat emission order, and appended to the entry's xs / ys / ps / ts columns at *index_in;
+    *index_out <- *index_in + the window's event count.  A window of more than window_capacity events stores nothing.
+    parts: int32 scratch of at least S * nparts words; scratch: uint8, emit_timed_scratch_bytes(S, nparts, window_capacity)."""
+    global EMIT_TIMED_LAUNCHES
+    _check(table.emit and getattr(table, "timed", False),
+           "the slot table has no timed emit entries (SlotTable(emit=True, timed=True))")
+    _check(not isinstance(max_count, bool) and isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_TIMED,
+           "timed emission needs 1 <= max_count <= %d (got %r)" % (MAX_COUNT_TIMED, max_count))
+    _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
+    _check_window_capacity(window_capacity)
+    _check(torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.is_cuda and pred.is_contiguous()
+           and pred.dtype == torch.float32 and pred.shape[0] == table.S, "pred must be a contiguous fp32 GPU tensor [S,2,sH,sW]")
+    S, _, sH, sW = pred.shape
+    _check(max(sH, sW) <= MAX_COUNT_LIMIT, "predictions larger than %d pixels a side cannot be emitted (int16 coordinates)"
+           % MAX_COUNT_LIMIT)
+    _check(torch.is_tensor(parts) and parts.is_cuda and parts.dtype == torch.int32 and parts.is_contiguous()
+           and parts.numel() >= S * nparts, "parts must be a contiguous int32 GPU tensor of at least S * nparts words")
+    _check((-(-2 * sH * sW // nparts) + 3) // 4 * 4 * max_count < 2 ** 32,
+           "a part's event total would overflow 32 bits: use more parts")
+    need = emit_timed_scratch_bytes(S, nparts, window_capacity)
+    _check(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
+           and scratch.numel() >= need and scratch.data_ptr() % 8 == 0,
+           "scratch must be a contiguous 8-byte aligned uint8 GPU tensor of at least %d bytes" % need)
+    lib.call(lib._slot_emit_timed, "bmc_slot_emit_timed", table.ptr(), table.emit_ptr(), S, pred.data_ptr(), sH, sW, max_count,
+             nparts, parts.data_ptr(), emit_rank_table(pred.device).data_ptr(), scratch.data_ptr(), int(window_capacity),
+             _stream())
+    EMIT_TIMED_LAUNCHES += 1

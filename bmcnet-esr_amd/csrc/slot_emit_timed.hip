@@ -1,0 +1,383 @@
+// Timed event output of multi-stream inference (MultiStreamSR(emit_events=True, event_times="linear")): the events of
+// slot_emit.hip, each with a float32 time inside its window, every window stored in time order (include/bmc_hip.h,
+// bmc_slot_emit_timed).  Event j of an element with n = q events has the time t0 + (t1 - t0) * j / (n - 1) (t0 for n = 1) -- the
+// reference's linear redistribution (dataloader/encodings.py:367-414) -- and the window is sorted by the EXACT rational
+// j / (n - 1), equal rationals in flat emission order.  The sort key is the rational's dense rank among all fractions with
+// denominators <= 254 (a host-built [256][256] uint16 table, rank_table[n][j]): fewer than 2^16 values, so a stable
+// least-significant-digit radix sort in two 8-bit passes is exact.
+//
+// SIX launches per window for all slots; no workgroup waits for another, no atomics on global memory (histograms are
+// counted with integer LDS atomics: order independent), every grid is fixed by the arguments:
+//   count    (nparts, S)  part p of slot s sums q over its chunk -> parts[s][p], and counts the LOW digits of its events
+//                         -> hist[s][p][256];
+//   scan     (S)          the slot's total -> tot[s], *index_out = *index_in + total; the histograms become exclusive
+//                         offsets over (digit, part); a window of more than window_capacity events stops here;
+//   expand   (nparts, S)  part p walks its chunk tile by tile as slot_emit_write_kernel does and stores the record of every
+//                         event (flat element index; rank, j, n) at its position by low digit in the slot's record buffer;
+//   hist     (blocks, S)  block b counts the HIGH digits of records [b * T2, (b+1) * T2) of that buffer;
+//   scan     (S)          ... exclusive offsets over (digit, block);
+//   scatter  (blocks, S)  block b stores xs / ys / ps / ts of its records at *index_in + position by high digit; positions
+//                         >= capacity are dropped.
+// Stability: a workgroup handles its records 256 at a time in sequence order; the position of a record among those of its
+// digit is (the workgroup's running count of the digit) + (the digit's counts of the lower waves in this step) + (the lanes
+// below it in its wave with the same digit: eight ballots).
+// Pointers read from the tables go through address-space(1) casts (global_* instructions, never flat_*), as in slots.hip.
+#include "bmc_common.h"
+
+namespace {
+
+template <class T>
+__device__ __forceinline__ T gld(const void* p) {
+    return *(const __attribute__((address_space(1))) T*)(unsigned long long)p;
+}
+template <class T>
+__device__ __forceinline__ void gst(void* p, T v) {
+    *(__attribute__((address_space(1))) T*)(unsigned long long)p = v;
+}
+
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int EMT = 256;             // threads per workgroup (4 waves)
+constexpr int NW = EMT / 64;
+constexpr int TILE = 4 * EMT;        // elements per tile: 4 consecutive ones per lane
+constexpr int T2 = BMC_SLOT_EMIT_TIMED_BLOCK;   // records per workgroup of the high-digit pass
+
+__device__ __forceinline__ unsigned quant(float v, float mc) { return v > 0.f ? (unsigned)fminf(rintf(v), mc) : 0u; }
+
+// q of the 4 elements i .. i+3 of a slot's prediction, 0 beyond `hi`.  vec: i, hi and the slot's base are multiples of 4
+__device__ __forceinline__ void load_q4(const float* ps, int i, int hi, bool vec, float mc, unsigned (&q)[4]) {
+    q[0] = q[1] = q[2] = q[3] = 0u;
+    if (i >= hi) return;
+    if (vec) {
+        const f32x4 v = gld<f32x4>(ps + i);
+        q[0] = quant(v.x, mc); q[1] = quant(v.y, mc); q[2] = quant(v.z, mc); q[3] = quant(v.w, mc);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + k < hi) q[k] = quant(gld<float>(ps + i + k), mc);
+    }
+}
+
+// the slot emits this window: it is active and its emit entry has columns (uniform over the workgroup)
+__device__ __forceinline__ bool emits(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, int s) {
+    return (gld<int>(&table[s].flags) & BMC_SLOT_ACTIVE) && gld<const float*>(&table[s].frames) != nullptr &&
+           gld<short*>(&emit[s].xs) != nullptr;
+}
+
+// One step of the stable split: every lane brings at most one record (digit d; !valid: none), the records of a step are in
+// sequence order by (wave, lane) and the steps of a workgroup follow one another.  run[d] = the position of the next record
+// of digit d (it starts at the workgroup's offset for the digit); stepc[w][d] = 0 between steps.  Called by all 256 threads.
+__device__ __forceinline__ unsigned place(unsigned* run, unsigned (*stepc)[256], bool valid, unsigned d, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned long long peers = __ballot(valid);                       // -> the lanes of this wave with the same digit
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long m = __ballot(valid && bit);
+        peers &= bit ? m : ~m;
+    }
+    const unsigned below = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
+    if (valid && below == 0u) stepc[wave][d] = (unsigned)__popcll(peers);
+    __syncthreads();
+    unsigned r = 0u;
+    if (valid) {
+        r = run[d] + below;
+#pragma unroll
+        for (int w = 0; w < NW - 1; ++w)
+            if (w < wave) r += stepc[w][d];
+    }
+    __syncthreads();
+    run[tid] += stepc[0][tid] + stepc[1][tid] + stepc[2][tid] + stepc[3][tid];     // thread t owns digit t
+    stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
+    __syncthreads();
+    return r;
+}
+
+// grid (nparts, S): part p owns elements [p * chunk, min(n, (p+1) * chunk)) of the slot's n = 2*sH*sW
+__global__ __launch_bounds__(EMT) void emit_timed_count_kernel(const bmc_slot_t* __restrict__ table,
+                                                               const bmc_slot_emit_timed_t* __restrict__ emit,
+                                                               const float* __restrict__ pred, int n, int chunk, int vec,
+                                                               float mc, const unsigned short* __restrict__ rank,
+                                                               unsigned* __restrict__ parts, unsigned* __restrict__ hist,
+                                                               int hrows) {
+    __shared__ unsigned wsum[NW];
+    __shared__ unsigned lh[256];
+    const int part = blockIdx.x, nparts = gridDim.x, s = blockIdx.y, tid = threadIdx.x;
+    if (!emits(table, emit, s)) return;
+    lh[tid] = 0u;
+    __syncthreads();
+    const float* const ps = pred + (long long)s * n;
+    const long long lo64 = (long long)part * chunk;
+    const int lo = (int)(lo64 < n ? lo64 : n), hi = (int)(lo64 + chunk < n ? lo64 + chunk : n);
+    unsigned acc = 0u;
+    for (int i = lo + 4 * tid; i < hi; i += TILE) {
+        unsigned q[4];
+        load_q4(ps, i, hi, vec, mc, q);
+        acc += q[0] + q[1] + q[2] + q[3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            for (unsigned j = 0; j < q[k]; ++j) atomicAdd(&lh[gld<unsigned short>(rank + q[k] * 256u + j) & 255u], 1u);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
+    __syncthreads();
+    if (tid == 0) gst<unsigned>(parts + (long long)s * nparts + part, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    gst<unsigned>(hist + ((long long)s * hrows + part) * 256 + tid, lh[tid]);
+}
+
+// grid (S).  first: rows = nparts histograms of the count pass; the slot's total and *index_out are written here.
+// Otherwise rows = the blocks of the high-digit pass that hold records.  hist[s][row][d] -> the records of digit d in the rows
+// before `row`; dbase[s][d] -> the records of the digits below d.
+__global__ __launch_bounds__(EMT) void emit_timed_scan_kernel(const bmc_slot_t* __restrict__ table,
+                                                              const bmc_slot_emit_timed_t* __restrict__ emit, int first,
+                                                              int nparts, const unsigned* __restrict__ parts,
+                                                              unsigned* __restrict__ hist, int hrows,
+                                                              unsigned* __restrict__ dbase, unsigned long long* __restrict__ tot,
+                                                              long long wcap) {
+    __shared__ unsigned long long red[NW];
+    __shared__ unsigned wtot[NW];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!emits(table, emit, s)) return;
+    unsigned long long total;
+    if (first) {
+        const unsigned* const pp = parts + (long long)s * nparts;
+        total = 0ull;
+        for (int j = tid; j < nparts; j += EMT) total += gld<unsigned>(pp + j);
+        for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o);
+        if (lane == 0) red[wave] = total;
+        __syncthreads();
+        total = red[0] + red[1] + red[2] + red[3];
+        if (tid == 0) {
+            const bmc_slot_emit_timed_t* const ent = emit + s;
+            gst<unsigned long long>(tot + s, total);
+            gst<long long>(gld<long long*>(&ent->index_out),
+                           gld<long long>(gld<const long long*>(&ent->index_in)) + (long long)total);
+        }
+    } else {
+        total = gld<unsigned long long>(tot + s);
+    }
+    if (total > (unsigned long long)wcap) return;                     // (uniform) the window does not fit: nothing is sorted
+    const int rows = first ? nparts : (int)((total + T2 - 1) / T2);
+    unsigned* const h = hist + (long long)s * hrows * 256 + tid;      // thread t owns digit t
+    unsigned running = 0u;
+    for (int r0 = 0; r0 < rows; r0 += 8) {
+        unsigned v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = r0 + k < rows ? gld<unsigned>(h + (long long)(r0 + k) * 256) : 0u;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            if (r0 + k < rows) gst<unsigned>(h + (long long)(r0 + k) * 256, running);
+            running += v[k];
+        }
+    }
+    unsigned inc = running;                                           // exclusive scan of the digit totals over the workgroup
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(inc, o);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wtot[wave] = inc;
+    __syncthreads();
+    unsigned woff = 0u;
+#pragma unroll
+    for (int w = 0; w < NW - 1; ++w)
+        if (w < wave) woff += wtot[w];
+    gst<unsigned>(dbase + (long long)s * 256 + tid, woff + inc - running);
+}
+
+// grid (nparts, S): the events of part p, in flat order, to their positions by low digit in rec[s]
+__global__ __launch_bounds__(EMT) void emit_timed_expand_kernel(const bmc_slot_t* __restrict__ table,
+                                                                const bmc_slot_emit_timed_t* __restrict__ emit,
+                                                                const float* __restrict__ pred, int n, int chunk, int vec,
+                                                                float mc, const unsigned short* __restrict__ rank,
+                                                                const unsigned* __restrict__ hist, int hrows,
+                                                                const unsigned* __restrict__ dbase,
+                                                                const unsigned long long* __restrict__ tot, long long wcap,
+                                                                u32x2* __restrict__ rec) {
+    __shared__ unsigned excl[TILE];          // exclusive prefix of q inside the tile
+    __shared__ unsigned wtot[NW];
+    __shared__ unsigned run[256];
+    __shared__ unsigned stepc[NW][256];
+    const int part = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    if (!emits(table, emit, s)) return;
+    if (gld<unsigned long long>(tot + s) > (unsigned long long)wcap) return;
+    run[tid] = gld<unsigned>(dbase + (long long)s * 256 + tid) + gld<unsigned>(hist + ((long long)s * hrows + part) * 256 + tid);
+    stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
+    u32x2* const out = rec + (long long)s * wcap;
+    const float* const ps = pred + (long long)s * n;
+    const long long lo64 = (long long)part * chunk;
+    const int lo = (int)(lo64 < n ? lo64 : n), hi = (int)(lo64 + chunk < n ? lo64 + chunk : n);
+    for (int tb = lo; tb < hi; tb += TILE) {                          // (uniform over the workgroup)
+        unsigned q[4];
+        load_q4(ps, tb + 4 * tid, hi, vec, mc, q);
+        const unsigned t = q[0] + q[1] + q[2] + q[3];
+        unsigned inc = t;                                             // inclusive scan over the wave
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned v = __shfl_up(inc, o);
+            if (lane >= o) inc += v;
+        }
+        if (lane == 63) wtot[wave] = inc;
+        __syncthreads();
+        unsigned woff = 0u, ttot = 0u;
+#pragma unroll
+        for (int w = 0; w < NW; ++w) {
+            const unsigned v = wtot[w];
+            if (w < wave) woff += v;
+            ttot += v;
+        }
+        const unsigned e0 = woff + inc - t;
+        excl[4 * tid] = e0;
+        excl[4 * tid + 1] = e0 + q[0];
+        excl[4 * tid + 2] = e0 + q[0] + q[1];
+        excl[4 * tid + 3] = e0 + q[0] + q[1] + q[2];
+        __syncthreads();
+        for (unsigned p0 = 0u; p0 < ttot; p0 += EMT) {                // 256 consecutive events of the tile per step
+            const unsigned p = p0 + tid;
+            const bool valid = p < ttot;
+            unsigned key = 0u, idx = 0u;
+            if (valid) {
+                int e = 0;                                            // the largest e with excl[e] <= p: its q is > 0
+#pragma unroll
+                for (int step = TILE / 2; step > 0; step >>= 1)
+                    if (excl[e + step] <= p) e += step;
+                const unsigned first = excl[e], nq = (e + 1 < TILE ? excl[e + 1] : ttot) - first, j = p - first;
+                idx = (unsigned)(tb + e);
+                key = ((unsigned)gld<unsigned short>(rank + nq * 256u + j) << 16) | (j << 8) | nq;
+            }
+            const unsigned pos = place(run, stepc, valid, (key >> 16) & 255u, tid);
+            if (valid && (long long)pos < wcap) gst<u32x2>(out + pos, u32x2{idx, key});
+        }
+    }
+}
+
+// grid (blocks, S): the high digits of records [b * T2, min(total, (b+1) * T2)) of rec[s] -> hist[s][b][256]
+__global__ __launch_bounds__(EMT) void emit_timed_hist_kernel(const bmc_slot_t* __restrict__ table,
+                                                              const bmc_slot_emit_timed_t* __restrict__ emit,
+                                                              unsigned* __restrict__ hist, int hrows,
+                                                              const unsigned long long* __restrict__ tot, long long wcap,
+                                                              const u32x2* __restrict__ rec) {
+    __shared__ unsigned lh[256];
+    const int b = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    if (!emits(table, emit, s)) return;
+    const unsigned long long total = gld<unsigned long long>(tot + s);
+    const long long lo = (long long)b * T2;
+    if (total > (unsigned long long)wcap || lo >= (long long)total) return;
+    const long long hi = lo + T2 < (long long)total ? lo + T2 : (long long)total;
+    lh[tid] = 0u;
+    __syncthreads();
+    const u32x2* const in = rec + (long long)s * wcap;
+    for (long long i = lo + tid; i < hi; i += EMT) atomicAdd(&lh[gld<u32x2>(in + i).y >> 24], 1u);
+    __syncthreads();
+    gst<unsigned>(hist + ((long long)s * hrows + b) * 256 + tid, lh[tid]);
+}
+
+// grid (blocks, S): records [b * T2, ...) of rec[s], in their order, to the columns at *index_in + position by high digit
+__global__ __launch_bounds__(EMT) void emit_timed_scatter_kernel(const bmc_slot_t* __restrict__ table,
+                                                                 const bmc_slot_emit_timed_t* __restrict__ emit, int sH, int sW,
+                                                                 const unsigned* __restrict__ hist, int hrows,
+                                                                 const unsigned* __restrict__ dbase,
+                                                                 const unsigned long long* __restrict__ tot, long long wcap,
+                                                                 const u32x2* __restrict__ rec) {
+    __shared__ unsigned run[256];
+    __shared__ unsigned stepc[NW][256];
+    const int b = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
+    if (!emits(table, emit, s)) return;
+    const unsigned long long total = gld<unsigned long long>(tot + s);
+    const long long lo = (long long)b * T2;
+    if (total > (unsigned long long)wcap || lo >= (long long)total) return;
+    const long long hi = lo + T2 < (long long)total ? lo + T2 : (long long)total;
+    const bmc_slot_emit_timed_t* const ent = emit + s;
+    short* const xs = gld<short*>(&ent->xs);
+    short* const ys = gld<short*>(&ent->ys);
+    signed char* const pol = gld<signed char*>(&ent->ps);
+    float* const ts = gld<float*>(&ent->ts);
+    const long long cap = gld<long long>(&ent->capacity);
+    const long long base = gld<long long>(gld<const long long*>(&ent->index_in));
+    run[tid] = gld<unsigned>(dbase + (long long)s * 256 + tid) + gld<unsigned>(hist + ((long long)s * hrows + b) * 256 + tid);
+    stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
+    __syncthreads();
+    const u32x2* const in = rec + (long long)s * wcap;
+    const unsigned hw = (unsigned)sH * (unsigned)sW;
+    for (long long i0 = lo; i0 < hi; i0 += EMT) {                     // (uniform over the workgroup)
+        const long long i = i0 + tid;
+        const bool valid = i < hi;
+        u32x2 r = u32x2{0u, 0u};
+        if (valid) r = gld<u32x2>(in + i);
+        const long long pos = base + place(run, stepc, valid, r.y >> 24, tid);
+        if (valid && pos < cap) {
+            const unsigned idx = r.x, j = (r.y >> 8) & 255u, nq = r.y & 255u;
+            const unsigned c = idx >= hw ? 1u : 0u, rem = idx - c * hw, row = rem / (unsigned)sW, x = rem - row * (unsigned)sW;
+            // float64, rounded once: t0 + (t1 - t0) * j / (n - 1)
+            const double t = nq > 1u ? BMC_EVENT_T0 + (BMC_EVENT_T1 - BMC_EVENT_T0) * (double)j / (double)(nq - 1u) : BMC_EVENT_T0;
+            gst<short>(xs + pos, (short)x);
+            gst<short>(ys + pos, (short)(sH - 1 - (int)row));
+            gst<signed char>(pol + pos, (signed char)(c ? -1 : 1));
+            gst<float>(ts + pos, (float)t);
+        }
+    }
+}
+
+long long hist_rows(int nparts, long long wcap) {
+    const long long blocks = (wcap + T2 - 1) / T2;
+    return blocks > nparts ? blocks : nparts;
+}
+
+}  // namespace
+
+extern "C" long long bmc_slot_emit_timed_scratch_bytes(int S, int nparts, long long window_capacity) {
+    if (S < 1 || S > BMC_MAX_SLOTS || nparts < 1 || nparts > BMC_SLOT_EMIT_MAX_PARTS || window_capacity < 1 ||
+        window_capacity > BMC_SLOT_EMIT_TIMED_MAX_WINDOW)
+        return -1;
+    // records [S][window_capacity] x 8, totals [S] x 8, digit bases [S][256] x 4, histograms [S][rows][256] x 4
+    return (long long)S * (8 * window_capacity + 8 + 1024 + 1024 * hist_rows(nparts, window_capacity));
+}
+
+extern "C" int bmc_slot_emit_timed(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, int S, const float* pred, int sH,
+                                   int sW, int max_count, int nparts, unsigned* parts, const unsigned short* rank_table,
+                                   void* scratch, long long window_capacity, bmc_stream_t s) {
+    BMC_CHECK_ARG(table && emit && pred && parts && rank_table && scratch && S >= 1 && S <= BMC_MAX_SLOTS,
+                  "bmc_slot_emit_timed: bad arguments");
+    BMC_CHECK_ARG(sH >= 1 && sW >= 1 && sH <= 32767 && sW <= 32767,
+                  "bmc_slot_emit_timed: sH, sW must be 1 .. 32767 (coordinates are int16; got %d x %d)", sH, sW);
+    BMC_CHECK_ARG(max_count >= 1 && max_count <= BMC_SLOT_EMIT_TIMED_MAX_COUNT,
+                  "bmc_slot_emit_timed: 1 <= max_count <= %d (the rank table; got %d)", BMC_SLOT_EMIT_TIMED_MAX_COUNT, max_count);
+    BMC_CHECK_ARG(nparts >= 1 && nparts <= BMC_SLOT_EMIT_MAX_PARTS, "bmc_slot_emit_timed: 1 <= nparts <= %d (got %d)",
+                  BMC_SLOT_EMIT_MAX_PARTS, nparts);
+    BMC_CHECK_ARG(window_capacity >= 1 && window_capacity <= BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
+                  "bmc_slot_emit_timed: 1 <= window_capacity <= %lld (got %lld)", (long long)BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
+                  window_capacity);
+    BMC_CHECK_ARG(((unsigned long long)pred & 3ull) == 0 && ((unsigned long long)scratch & 7ull) == 0 &&
+                      ((unsigned long long)rank_table & 1ull) == 0,
+                  "bmc_slot_emit_timed: pred must be 4-byte, scratch 8-byte, rank_table 2-byte aligned");
+    const long long n = 2ll * sH * sW;                                // < 2^31 for sH, sW <= 32767
+    const long long chunk = ((n + nparts - 1) / nparts + 3) / 4 * 4;
+    BMC_CHECK_ARG(chunk * max_count < (1ll << 32),
+                  "bmc_slot_emit_timed: %lld elements per part x max_count %d overflow a part's 32-bit total: use more parts",
+                  chunk, max_count);
+    const int vec = n % 4 == 0 && ((unsigned long long)pred & 15ull) == 0;
+    const int blocks = (int)((window_capacity + T2 - 1) / T2), hrows = (int)hist_rows(nparts, window_capacity);
+    u32x2* const rec = (u32x2*)scratch;
+    unsigned long long* const tot = (unsigned long long*)(rec + (long long)S * window_capacity);
+    unsigned* const dbase = (unsigned*)(tot + S);
+    unsigned* const hist = dbase + (long long)S * 256;
+    const hipStream_t st = (hipStream_t)s;
+    hipLaunchKernelGGL(emit_timed_count_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, (int)n, (int)chunk, vec,
+                       (float)max_count, rank_table, parts, hist, hrows);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (count)");
+    hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(S), dim3(EMT), 0, st, table, emit, 1, nparts, (const unsigned*)parts, hist,
+                       hrows, dbase, tot, window_capacity);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scan 1)");
+    hipLaunchKernelGGL(emit_timed_expand_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, (int)n, (int)chunk, vec,
+                       (float)max_count, rank_table, (const unsigned*)hist, hrows, (const unsigned*)dbase,
+                       (const unsigned long long*)tot, window_capacity, rec);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (expand)");
+    hipLaunchKernelGGL(emit_timed_hist_kernel, dim3(blocks, S), dim3(EMT), 0, st, table, emit, hist, hrows,
+                       (const unsigned long long*)tot, window_capacity, (const u32x2*)rec);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (histogram)");
+    hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(S), dim3(EMT), 0, st, table, emit, 0, nparts, (const unsigned*)parts, hist,
+                       hrows, dbase, tot, window_capacity);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scan 2)");
+    hipLaunchKernelGGL(emit_timed_scatter_kernel, dim3(blocks, S), dim3(EMT), 0, st, table, emit, sH, sW, (const unsigned*)hist,
+                       hrows, (const unsigned*)dbase, (const unsigned long long*)tot, window_capacity, (const u32x2*)rec);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scatter)");
+    return 0;
+}

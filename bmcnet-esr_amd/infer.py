@@ -244,15 +244,27 @@ class MultiStreamSR:
     of the prediction [2,sH,sW] in flat order, q = min(rint(v), max_count) for v > 0 (else 0; round-half-to-even -- the rounded
     count image the reference renders, infer_BMCNet.py:94) events xs = x, ys = sH-1-row, ps = +1 (channel 0) / -1 (channel 1),
     so that encoding a window's events at (sH, sW) gives q back exactly.  results() then carries sr_events = (xs int16, ys int16,
-    ps int8) and sr_index [done+1] (window i owns events [sr_index[i], sr_index[i+1])); no timestamps: a count image has no time
-    inside the window.  The columns hold `event_capacity` events (open / open_events; default 2 x scale^2 x the recording's LR
+    ps int8) and sr_index [done+1] (window i owns events [sr_index[i], sr_index[i+1])); without event_times there are no
+    timestamps and a window's events are in pixel order.  The columns hold `event_capacity` events (open / open_events; default 2 x scale^2 x the recording's LR
     events); the index keeps counting past it, and results() then raises with the capacity that is needed.  About 5 bytes per
-    event instead of 8 x sH x sW bytes per window of keep_predictions; both may be on."""
+    event instead of 8 x sH x sW bytes per window of keep_predictions; both may be on.
+
+    event_times="linear" (with emit_events; needs max_count <= 255): the list becomes a STREAM.  Every event also carries a
+    float32 time inside its window and a window's events are stored in time order (bmc_slot_emit_timed: six launches per
+    window instead of the two, inside the captured graph too) -- the reference's linear redistribution of a count image
+    (dataloader/encodings.py:367-414, mode='linear', one time bin): event j of a pixel's n events has t = 0.01 + 0.99 * j /
+    (n - 1) (0.01 for n = 1; float64, rounded once), the window is sorted by the exact j / (n - 1), ties in the pixel order
+    above.  results() then also carries sr_ts (float32, on the GPU), parallel to sr_events.  Times are window-normalised: a
+    count image has no absolute clock.  The sort works in per-slot scratch of `window_event_capacity` events (open /
+    open_events; default 2 x scale^2 x the LR events of the recording's busiest frame, at most 2 x sH x sW x max_count); a
+    window that emits more stores nothing, the index keeps the true count and results() raises with the capacity needed."""
 
     MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
+    MAX_COUNT_TIMED = 255        # event_times: the sort key is a 16-bit rank of j / (n - 1), n <= 255
+    MAX_WINDOW_CAPACITY = 1 << 28
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
-                 seqn=3, emit_events=False, max_count=255):
+                 seqn=3, emit_events=False, max_count=255, event_times=None):
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
         if seqn < 2:
@@ -260,6 +272,14 @@ class MultiStreamSR:
         if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= self.MAX_COUNT_LIMIT:
             raise ValueError("MultiStreamSR: max_count must be an integer, 1 <= max_count <= %d (got %r)"
                              % (self.MAX_COUNT_LIMIT, max_count))
+        if event_times not in (None, "linear"):
+            raise ValueError("MultiStreamSR: event_times must be None or 'linear' (got %r)" % (event_times,))
+        if event_times is not None and not emit_events:
+            raise ValueError("MultiStreamSR: event_times needs emit_events=True")
+        if event_times is not None and max_count > self.MAX_COUNT_TIMED:
+            raise ValueError("MultiStreamSR: event_times needs max_count <= %d (got %d)" % (self.MAX_COUNT_TIMED, max_count))
+        self.event_times = event_times
+        self._wcap = 0             # events per window the sort scratch holds (the largest window_event_capacity so far)
         self.model = model.eval()
         self.S, self.n_c, self.scale, self.plain, self.seqn = int(slots), n_c, scale, plain, int(seqn)
         self.use_graph = graph
@@ -285,11 +305,28 @@ class MultiStreamSR:
         if isinstance(event_capacity, bool) or not isinstance(event_capacity, (int, np.integer)) or event_capacity < 1:
             raise ValueError("MultiStreamSR.%s: event_capacity must be a positive integer (got %r)" % (who, event_capacity))
 
-    def open(self, frames, gts, gt_size=None, event_capacity=None):
+    def _check_window_capacity(self, who, capacity):
+        if capacity is None:
+            return
+        if self.event_times is None:
+            raise ValueError("MultiStreamSR.%s: window_event_capacity needs a session with event_times='linear'" % who)
+        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= self.MAX_WINDOW_CAPACITY:
+            raise ValueError("MultiStreamSR.%s: window_event_capacity must be a positive integer, at most %d (got %r)"
+                             % (who, self.MAX_WINDOW_CAPACITY, capacity))
+
+    def _default_window_capacity(self, busiest, H, W):
+        """2 x scale^2 x the LR events of the busiest frame, at most what a window can emit."""
+        most = 2 * self.scale ** 2 * H * W * self.max_count
+        return max(1, min(2 * self.scale ** 2 * int(busiest), most, self.MAX_WINDOW_CAPACITY))
+
+    def open(self, frames, gts, gt_size=None, event_capacity=None, window_event_capacity=None):
         """Queue one recording -> handle.  frames [L,2,H,W], gts [L,2,gh,gw] (fp32, on the GPU); gt_size (the reference's
         gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size.  event_capacity (emit_events):
-        events the output columns hold; default 2 x scale^2 x the sum of `frames` (one device reduction here)."""
+        events the output columns hold; default 2 x scale^2 x the sum of `frames` (one device reduction here).
+        window_event_capacity (event_times): events of ONE window the sort scratch holds; default 2 x scale^2 x the largest
+        sum of one frame."""
         self._check_capacity("open", event_capacity)
+        self._check_window_capacity("open", window_event_capacity)
         if frames.dim() != 4 or frames.shape[1] != 2 or gts.dim() != 4 or tuple(gts.shape[:2]) != (frames.shape[0], 2):
             raise ValueError("MultiStreamSR.open: frames [L,2,H,W] and gts [L,2,gh,gw] (got %s, %s)"
                              % (tuple(frames.shape), tuple(gts.shape)))
@@ -307,7 +344,10 @@ class MultiStreamSR:
         self._set_size("open", H, W, gh, gw)
         if self.emit_events and event_capacity is None:
             event_capacity = 2 * self.scale ** 2 * int(frames.sum(dtype=torch.float64).item())
-        return self._add({"frames": frames.contiguous(), "gts": gts.contiguous()}, L, frames.device, event_capacity)
+        if self.event_times is not None and window_event_capacity is None:
+            window_event_capacity = self._default_window_capacity(frames.sum(dim=(1, 2, 3), dtype=torch.float64).max().item(), H, W)
+        return self._add({"frames": frames.contiguous(), "gts": gts.contiguous()}, L, frames.device, event_capacity,
+                         window_event_capacity)
 
     def _set_size(self, who, H, W, gh, gw):
         if self._size is None:
@@ -316,7 +356,7 @@ class MultiStreamSR:
             raise ValueError("MultiStreamSR.%s: sizes %s differ from the first recording's %s (group recordings by sensor "
                              "size)" % (who, (H, W, gh, gw), self._size))
 
-    def _add(self, rec, L, device, event_capacity=None):
+    def _add(self, rec, L, device, event_capacity=None, window_event_capacity=None):
         """Queue a recording of L items (frames or event blocks) -> handle."""
         from bmc_hip import slots
         H, W, gh, gw = self._size
@@ -330,6 +370,13 @@ class MultiStreamSR:
                        ev_ys=torch.empty(cap, dtype=torch.int16, device=device),
                        ev_ps=torch.empty(cap, dtype=torch.int8, device=device),
                        ev_index=torch.zeros(nwin + 1, dtype=torch.int64, device=device))
+        if self.event_times is not None:                   # ... a time column, and room for its largest window in the sort
+            rec.update(ev_ts=torch.empty(cap, dtype=torch.float32, device=device), win_capacity=int(window_event_capacity))
+            if rec["win_capacity"] > self._wcap:
+                self._wcap = rec["win_capacity"]
+                if self._bufs is not None:                 # a running session: the sort scratch grows
+                    self._sort_buffers(self._bufs, device)
+                    self.invalidate()
         h = self.sched.add(nwin)
         self._recs[h] = rec
         return h
@@ -337,16 +384,18 @@ class MultiStreamSR:
     MAX_SEQN_EVENTS = 8          # bmc_slot_events_t holds the ranges of at most 8 LR frames (BMC_SLOT_MAX_SEQN)
     MAX_WIDTH_EVENTS = 7680      # bmc_slot_encode: one row of both channels must fit a workgroup's LDS band
 
-    def open_events(self, lr, gt, lr_index, gt_index, lr_size, gt_size, event_capacity=None):
+    def open_events(self, lr, gt, lr_index, gt_index, lr_size, gt_size, event_capacity=None, window_event_capacity=None):
         """Queue one event-backed recording -> handle.  lr, gt = (xs, ys, ps): the raw dataset columns of the LR and the
         ground-truth stream (1-D int16, int16, float64 GPU tensors; polarities -1 / 0 / +1); lr_index, gt_index [L,2]
         (integers, on the host): item j is LR events [lr_index[j,0], lr_index[j,1]) and ground-truth events [gt_index[j,0],
         gt_index[j,1]) -- bmc_hip.encodings.event_window_indices gives the reference's tables.  Window i reads the LR frames of
         items i .. i+seqn-1 and the ground truth of item i+1, as open() on the encoded frames.  Every range is checked here
         against the column lengths: the kernel trusts the table.  event_capacity (emit_events): events the output columns
-        hold; default 2 x scale^2 x the sum of the lengths of the LR item ranges."""
+        hold; default 2 x scale^2 x the sum of the lengths of the LR item ranges.  window_event_capacity (event_times): events of
+        ONE window the sort scratch holds; default 2 x scale^2 x the longest LR item range."""
         who = "MultiStreamSR.open_events: "
         self._check_capacity("open_events", event_capacity)
+        self._check_window_capacity("open_events", window_event_capacity)
         for name, cols in (("lr", lr), ("gt", gt)):
             if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
                 raise ValueError(who + "%s must be three tensors (xs, ys, ps)" % name)
@@ -392,8 +441,10 @@ class MultiStreamSR:
         self._set_size("open_events", H, W, gh, gw)
         if self.emit_events and event_capacity is None:
             event_capacity = 2 * self.scale ** 2 * int((lr_index[:, 1] - lr_index[:, 0]).sum())
+        if self.event_times is not None and window_event_capacity is None:
+            window_event_capacity = self._default_window_capacity((lr_index[:, 1] - lr_index[:, 0]).max(), H, W)
         h = self._add({"lr": tuple(lr), "gt": tuple(gt), "lr_index": lr_index, "gt_index": gt_index}, L, cols[0].device,
-                      event_capacity)
+                      event_capacity, window_event_capacity)
         if not self._has_events:
             self._has_events = True
             if self._bufs is not None:                     # a running frames-only session: the table grows an event part
@@ -407,20 +458,28 @@ class MultiStreamSR:
         r = self._recs[handle]
         data = r["lr"] + r["gt"] if "lr" in r else (r["frames"], r["gts"])
         if "ev_xs" in r:
-            data = tuple(data) + (r["ev_xs"], r["ev_ys"], r["ev_ps"], r["ev_index"])
+            data = tuple(data) + (r["ev_xs"], r["ev_ys"], r["ev_ps"], r["ev_index"]) + ((r["ev_ts"],) if "ev_ts" in r else ())
         return sum(t.numel() * t.element_size() for t in data + (r["sse"],) + (() if r["keep"] is None else (r["keep"],)))
 
     def scratch_bytes(self):
-        """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened)."""
+        """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened) and,
+        with event_times, of the sort scratch (0 until a recording has been opened)."""
+        nbytes = 0
+        if self._wcap:
+            from bmc_hip import slots
+            H, W = self._size[:2]
+            nbytes = slots.emit_timed_scratch_bytes(self.S, slots.emit_parts(self.scale * H, self.scale * W), self._wcap)
         if not self._has_events:
-            return 0
+            return nbytes
         H, W, gh, gw = self._size
-        return 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
+        return nbytes + 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
 
     def results(self, handle):
         """-> dict(esr_mse=[...], bicubic_mse=[...], time=[...] per window done so far[, predictions=[n,2,sH,sW]][,
-        sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host]).  Raises RuntimeError when
-        the windows emitted more events than the recording's event_capacity (the message names the capacity needed)."""
+        sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][, sr_ts float32 on the GPU,
+        parallel to sr_events (event_times)]).  Raises RuntimeError when the windows emitted more events than the recording's
+        event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity
+        needed)."""
         r = self._recs[handle]
         done = len(r["steps"])
         if done:
@@ -439,6 +498,13 @@ class MultiStreamSR:
                 raise RuntimeError("MultiStreamSR.results: recording %d emitted %d events in %d windows, more than its "
                                    "event_capacity of %d: open it with event_capacity >= %d"
                                    % (handle, total, done, r["ev_capacity"], total))
+            if self.event_times is not None:
+                most = int((index[1:] - index[:-1]).max()) if done else 0
+                if most > r["win_capacity"]:
+                    raise RuntimeError("MultiStreamSR.results: a window of recording %d emitted %d events, more than its "
+                                       "window_event_capacity of %d: open it with window_event_capacity >= %d"
+                                       % (handle, most, r["win_capacity"], most))
+                out["sr_ts"] = r["ev_ts"][:total]
             out["sr_events"] = (r["ev_xs"][:total], r["ev_ys"][:total], r["ev_ps"][:total])
             out["sr_index"] = index
         return out
@@ -451,10 +517,13 @@ class MultiStreamSR:
             from bmc_hip import slots
             b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
                  "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
-                 "table": slots.SlotTable(S, device, events=self._has_events, emit=self.emit_events)}
+                 "table": slots.SlotTable(S, device, events=self._has_events, emit=self.emit_events,
+                                          timed=self.event_times is not None)}
             if self.emit_events:
                 b["emit_parts"] = torch.zeros(S * slots.emit_parts(self.scale * H, self.scale * W), dtype=torch.int32,
                                               device=device)
+            if self.event_times is not None:
+                self._sort_buffers(b, device)
             if self._has_events:
                 self._event_buffers(b, device)
             if self.state_dtype is None:
@@ -465,11 +534,18 @@ class MultiStreamSR:
             self._bufs = b
         return self._bufs
 
+    def _sort_buffers(self, b, device):
+        from bmc_hip import slots
+        H, W = self._size[:2]
+        slots.emit_rank_table(device)                      # uploaded here, once per device: never inside a graph capture
+        b["emit_scratch"] = torch.empty(slots.emit_timed_scratch_bytes(self.S, slots.emit_parts(self.scale * H, self.scale * W),
+                                                                       self._wcap), dtype=torch.uint8, device=device)
+
     def _event_buffers(self, b, device):
         from bmc_hip import slots
         H, W, gh, gw = self._size
         if not b["table"].events:
-            b["table"] = slots.SlotTable(self.S, device, events=True, emit=self.emit_events)
+            b["table"] = slots.SlotTable(self.S, device, events=True, emit=self.emit_events, timed=self.event_times is not None)
         b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
         b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
 
@@ -490,7 +566,10 @@ class MultiStreamSR:
         cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.contiguous(memory_format=torch.channels_last)
         slots.commit(b["table"], [cl(t) for t in out[:-1]], b["pool"], out[-1].contiguous(), b["pred"])
         slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
-        if self.emit_events:
+        if self.event_times is not None:
+            slots.emit_timed(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
+                             b["emit_parts"], b["emit_scratch"], self._wcap)
+        elif self.emit_events:
             slots.emit(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
                        b["emit_parts"])
 
@@ -550,6 +629,8 @@ class MultiStreamSR:
                 em[s]["index_in"] = r["ev_index"].data_ptr() + 8 * i
                 em[s]["index_out"] = r["ev_index"].data_ptr() + 8 * (i + 1)
                 em[s]["capacity"] = r["ev_capacity"]
+                if "ev_ts" in r:
+                    em[s]["ts"] = r["ev_ts"].data_ptr()
             r["steps"].append(len(self._steps))
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
@@ -575,7 +656,8 @@ class MultiStreamSR:
 
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
-                        gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None):
+                        gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
+                        window_event_capacity=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  -> dict(
@@ -585,23 +667,27 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
       predictions = {name: [n_windows,2,sH,sW]}  with keep_predictions][,
       sr_events   = {name: (xs, ys, ps, index [n_windows+1])}  with emit_events: the super-resolved event stream of every
                                          recording (MultiStreamSR(emit_events=True); event_capacity: per recording, None =
-                                         the default)])."""
+                                         the default)][,
+      sr_ts       = {name: ts float32}           with event_times="linear": the events' times inside their windows, every
+                                         window in time order (window_event_capacity: per recording, None = the default)])."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
-                       keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count)
+                       keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
             if gt_size is not None and tuple(int(v) for v in gt_size) != tuple(int(v) for v in r.gt_size):
                 raise ValueError("evaluate_recordings: gt_size %s differs from recording %s's %s"
                                  % (tuple(gt_size), name, tuple(r.gt_size)))
-            handles.append((name, ms.open_events(*r, event_capacity=event_capacity)))
+            handles.append((name, ms.open_events(*r, event_capacity=event_capacity,
+                                                 window_event_capacity=window_event_capacity)))
         else:
-            handles.append((name, ms.open(r[0], r[1], gt_size, event_capacity=event_capacity)))
+            handles.append((name, ms.open(r[0], r[1], gt_size, event_capacity=event_capacity,
+                                          window_event_capacity=window_event_capacity)))
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
     breakdown = collections.defaultdict(dict)
-    preds, streams = {}, {}
+    preds, streams, times = {}, {}, {}
     for name, h in handles:
         r = ms.results(h)
         for k in ("esr_mse", "bicubic_mse", "time"):
@@ -611,9 +697,13 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
             preds[name] = r["predictions"]
         if emit_events:
             streams[name] = r["sr_events"] + (r["sr_index"],)
+        if event_times is not None:
+            times[name] = r["sr_ts"]
     out = {"results": dict(breakdown), "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items()}}
     if keep_predictions:
         out["predictions"] = preds
     if emit_events:
         out["sr_events"] = streams
+    if event_times is not None:
+        out["sr_ts"] = times
     return out

@@ -536,6 +536,54 @@ typedef struct bmc_slot_emit {
 int bmc_slot_emit(const bmc_slot_t* table, const bmc_slot_emit_t* emit, int S, const float* pred, int sH, int sW, int max_count,
                   int nparts, unsigned* parts, bmc_stream_t s);
 
+/* TIMED event output (MultiStreamSR(emit_events=True, event_times="linear")): the same events, each with a float32 time
+ * inside its window, every window stored in time order -- the reference's linear redistribution of a count image
+ * (dataloader/encodings.py:367-414, python_event_redistribute_PolarityStack, mode='linear', one time bin) with the sort on
+ * the GPU.  Per slot and window, with q, the flat order (c, row, x) and xs / ys / ps exactly as bmc_slot_emit defines them:
+ *   Time.   Event j (0 <= j < n) of an element with n = q events has  t = (float)(T0 + (T1 - T0) * j / (n - 1)),  evaluated in
+ *           float64 (the product first, then the quotient, then the sum) and rounded ONCE to float32; n = 1 gives (float)T0.
+ *           T0 = BMC_EVENT_T0 = 0.01, T1 = BMC_EVENT_T1 = 1.0: linspace(c/bins + 1/(100*bins), (c+1)/bins, n) at bins = 1, c = 0.
+ *   Order.  The window's events are ordered by the EXACT rational j / (n - 1) (0 for n = 1), ascending; equal rationals (1/2 =
+ *           2/4, every j = 0, every j = n-1) keep the flat emission order of bmc_slot_emit: a stable sort.  (The rounded
+ *           float is NOT the key, though it is non-decreasing along the sorted window.)
+ *   Limit.  max_count <= BMC_SLOT_EMIT_TIMED_MAX_COUNT = 255: distinct rationals with denominators <= 254 differ by at least
+ *           1 / (254 * 253) and there are fewer than 2^16 of them, so their dense rank is an exact 16-bit sort key.
+ *           rank_table: DEVICE [256][256] uint16, rank_table[n][j] = the number of distinct fractions p/d (1 <= d <= 254,
+ *           0 <= p <= d) smaller than j / (n - 1) (0 for n = 1), for 0 <= j < n; built by the host in integer arithmetic.
+ *   Storage. The window occupies [*index_in, *index_out) of the recording's columns, *index_out = *index_in + its event count
+ *           ALWAYS; the event at global position g is stored at xs[g], ys[g], ps[g], ts[g] when g < capacity and dropped
+ *           otherwise (bmc_slot_emit's rule).  The sort works in `scratch`, which holds window_capacity events per slot: a
+ *           window of more events stores NOTHING (its columns keep their bytes) and still advances the index by its true
+ *           count -- the caller compares index differences with window_capacity.
+ *   Determinism. Integer keys and counts; no workgroup waits for another; no atomics on global memory; grids fixed by the
+ *           arguments, the live sizes are read from device memory: the same bytes run after run, capturable in a graph.
+ * The device table entry: the fields of bmc_slot_emit_t, then ts. */
+#define BMC_EVENT_T0 0.01
+#define BMC_EVENT_T1 1.0
+#define BMC_SLOT_EMIT_TIMED_MAX_COUNT 255
+#define BMC_SLOT_EMIT_TIMED_BLOCK 4096                  /* records per workgroup of the second digit pass */
+#define BMC_SLOT_EMIT_TIMED_MAX_WINDOW (1ll << 28)      /* window_capacity limit */
+typedef struct bmc_slot_emit_timed {
+    short* xs;                  /* output columns of the slot's recording, `capacity` entries each */
+    short* ys;
+    signed char* ps;
+    const long long* index_in;  /* events emitted before this window */
+    long long* index_out;       /* ... and after it */
+    long long capacity;
+    float* ts;                  /* the time column, parallel to xs / ys / ps */
+} bmc_slot_emit_timed_t;
+/* SIX launches for all slots (csrc/slot_emit_timed.hip): a stable least-significant-digit radix sort on the 16-bit rank in
+ * two 8-bit passes.  count (nparts, S): part totals and low-digit histograms; scan (S): the slot's total, *index_out, exclusive
+ * offsets over (digit, part); expand (nparts, S): every event's record (flat element index, rank, j, n) to its position by low
+ * digit in scratch; histogram (blocks, S): high digits of blocks of BMC_SLOT_EMIT_TIMED_BLOCK records; scan (S); scatter
+ * (blocks, S): xs / ys / ps / ts to *index_in + the position by high digit.  blocks = ceil(window_capacity / BLOCK).
+ * parts: S x nparts words; scratch: bmc_slot_emit_timed_scratch_bytes(S, nparts, window_capacity) bytes, 8-byte aligned (-1 for
+ * arguments out of range).  Limits of bmc_slot_emit, and max_count <= 255, 1 <= window_capacity <= 2^28. */
+long long bmc_slot_emit_timed_scratch_bytes(int S, int nparts, long long window_capacity);
+int bmc_slot_emit_timed(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, int S, const float* pred, int sH, int sW,
+                        int max_count, int nparts, unsigned* parts, const unsigned short* rank_table, void* scratch,
+                        long long window_capacity, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

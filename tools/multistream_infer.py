@@ -76,18 +76,21 @@ def emit_alone(ms, reps=20):
     b = ms._bufs
     H, W = ms._size[:2]
     args = (b["table"], b["pred"], ms.max_count, slots.emit_parts(ms.scale * H, ms.scale * W), b["emit_parts"])
+    call = slots.emit
+    if ms.event_times is not None:                         # bmc_slot_emit_timed: the six launches of the sorted stream
+        args, call = args + (b["emit_scratch"], ms._wcap), slots.emit_timed
     a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    slots.emit(*args)
+    call(*args)
     a.record()
     for _ in range(reps):
-        slots.emit(*args)
+        call(*args)
     z.record()
     z.synchronize()
     return a.elapsed_time(z) / reps
 
 
-def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False):
-    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit)
+def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None):
+    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
@@ -120,10 +123,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--events", action="store_true")
     ap.add_argument("--emit-events", action="store_true")
+    ap.add_argument("--event-times", action="store_true",
+                    help="with --emit-events: the timed, time-ordered stream (MultiStreamSR(event_times='linear'))")
     ap.add_argument("--resident-windows", type=int, default=0)
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.event_times and not a.emit_events:
+        ap.error("--event-times needs --emit-events")
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     m = BMCNet(4, 128, 5).to(dev)
@@ -165,8 +172,10 @@ def main():
                                      resident_bytes=nbytes))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.emit_events:
-                    lat, wps, emi, nev, nbytes, dense = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True)
-                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(emit)", slots=S, ms_per_window=round(lat, 3),
+                    lat, wps, emi, nev, nbytes, dense = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True,
+                                                                    event_times="linear" if a.event_times else None)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(emit, timed)" if a.event_times else
+                                     "MultiStreamSR(emit)", slots=S, ms_per_window=round(lat, 3),
                                      windows_per_s=round(wps, 1), emit_ms=round(emi, 4), emit_share=round(emi / lat, 4),
                                      events_last_window=nev, resident_bytes=nbytes, resident_bytes_dense=dense))
                     print(json.dumps(rows[-1]), flush=True)
