@@ -116,19 +116,23 @@ def event_window_indices(lr_ts, gt_ts, window=2048, sliding_window=1024, scale=4
         the reference then fails in get_gt_event_indices; MultiStreamSR.open_events refuses such a table);
       * LR blocks that start after the last HR timestamp get no HR block in the reference (its item access fails there):
         both tables end at the last block that has one.
+    gt_ts=None: a recording WITHOUT ground truth (need_gt_events=False, h5dataset.py:278-279) -> (lr_index, None): the blocks
+    compute_k_indices cuts (the first two rules above) with no truncation by HR coverage.  For a stream that has a ground
+    truth this is the table returned with it, possibly followed by further rows.
     Only 'events' mode: the reference's 'time' and 'frame' modes call get_gt_event_indices_num(start_idx, end_idx) with two
     arguments where it takes one (:231, :245) and cannot run with ground-truth events -> ValueError."""
     import numpy as np
     if mode != "events":
         raise ValueError("event_window_indices: only mode='events' (the reference's %r mode cannot run with ground-truth "
                          "events)" % (mode,))
-    lr_ts, gt_ts = np.asarray(lr_ts), np.asarray(gt_ts)
-    if lr_ts.ndim != 1 or gt_ts.ndim != 1:
+    lr_ts = np.asarray(lr_ts)
+    gt_ts = None if gt_ts is None else np.asarray(gt_ts)
+    if lr_ts.ndim != 1 or (gt_ts is not None and gt_ts.ndim != 1):
         raise ValueError("event_window_indices: lr_ts and gt_ts are 1-D timestamp columns")
     step = int(window) - int(sliding_window)
     if step <= 0:
         raise ValueError("event_window_indices: window must exceed sliding_window")
-    n, n_gt = len(lr_ts), len(gt_ts)
+    n = len(lr_ts)
     L = max(int(n / step), 0)
     if dataset_length is not None:
         L = min(int(dataset_length), L)
@@ -136,6 +140,9 @@ def event_window_indices(lr_ts, gt_ts, window=2048, sliding_window=1024, scale=4
         raise ValueError("event_window_indices: %d events give no block of %d advancing by %d" % (n, window, step))
     idx0 = step * np.arange(L, dtype=np.int64)
     idx1 = np.minimum(idx0 + int(window), n - 1)
+    if gt_ts is None:
+        return np.stack([idx0, idx1], 1), None
+    n_gt = len(gt_ts)
     num_gt = int(scale) ** 2 * int(idx1[0] - idx0[0])
     first = np.searchsorted(gt_ts, lr_ts[idx0], side="left").astype(np.int64)
     k = np.arange(L, dtype=np.int64)
@@ -147,6 +154,45 @@ def event_window_indices(lr_ts, gt_ts, window=2048, sliding_window=1024, scale=4
     g1 = np.where(over, n_gt - 1, g1)
     g0 = np.where(over, g1 - num_gt, g0)
     return np.stack([idx0, idx1], 1), np.stack([g0, g1], 1)
+
+
+def event_block_spans(lr_ts, lr_index):
+    """The time span of every item of a recording on its own clock -> [L,2] float64 on the host: for item j = events
+    [first, end) of lr_index, (t_first, t_last) = (lr_ts[first], lr_ts[end - 1]); an empty item gets lr_ts[min(first, n - 1)]
+    twice.  lr_ts: the recording's timestamp column (1-D, n >= 1 entries; a numpy array or a tensor on the host or the GPU --
+    there one gather and one copy); lr_index: an integer [L,2] table with 0 <= first <= end <= n.  What
+    MultiStreamSR.open_events(lr_ts=...) hands to the clocked event output."""
+    import numpy as np
+    idx = np.asarray(lr_index.cpu() if torch.is_tensor(lr_index) else lr_index)
+    if idx.ndim != 2 or idx.shape[1] != 2 or idx.dtype.kind not in "iu":
+        raise ValueError("event_block_spans: lr_index must be an integer [L,2] table (got %s %s)" % (idx.dtype, idx.shape))
+    idx = idx.astype(np.int64)
+    n = lr_ts.numel() if torch.is_tensor(lr_ts) else np.asarray(lr_ts).size
+    if (lr_ts.dim() if torch.is_tensor(lr_ts) else np.asarray(lr_ts).ndim) != 1 or n < 1:
+        raise ValueError("event_block_spans: lr_ts is a 1-D timestamp column of at least one event")
+    if (idx[:, 0] > idx[:, 1]).any() or (idx.size and (idx.min() < 0 or idx.max() > n)):
+        raise ValueError("event_block_spans: lr_index has a range outside the %d events of the column" % n)
+    empty = idx[:, 0] == idx[:, 1]
+    first = np.where(empty, np.minimum(idx[:, 0], n - 1), idx[:, 0])
+    last = np.where(empty, first, idx[:, 1] - 1)
+    take = np.stack([first, last], 1).reshape(-1)
+    if torch.is_tensor(lr_ts):
+        got = lr_ts.index_select(0, torch.from_numpy(take).to(lr_ts.device)).to("cpu", torch.float64).numpy()
+    else:
+        got = np.asarray(lr_ts)[take].astype(np.float64)
+    return got.reshape(-1, 2)
+
+
+def check_spans(who, spans, L):
+    """spans -> a [L,2] float64 numpy table of finite (t_first, t_last) with t_last >= t_first, or ValueError."""
+    import numpy as np
+    a = np.asarray(spans.cpu() if torch.is_tensor(spans) else spans)
+    if a.ndim != 2 or a.shape != (L, 2) or a.dtype.kind not in "fiu":
+        raise ValueError(who + "spans must be a [%d,2] table of (t_first, t_last) (got %s %s)" % (L, a.dtype, a.shape))
+    a = a.astype(np.float64)
+    if not np.isfinite(a).all() or (a[:, 1] < a[:, 0]).any():
+        raise ValueError(who + "every span must be finite with t_last >= t_first")
+    return a
 
 
 def events_to_image_torch(xs, ys, ps, device=None, sensor_size=(180, 240), clip_out_of_range=True, interpolation=None, padding=True):
@@ -190,7 +236,7 @@ def events_to_voxel_torch(xs, ys, ts, ps, B, device=None, sensor_size=(180, 240)
     return out
 
 
-def counts_to_events(pred, max_count=255, times=None):
+def counts_to_events(pred, max_count=255, times=None, spans=None):
     """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
     (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in
     the flat order of [2,sH,sW]: q = min(rint(v), max_count) for v > 0, else 0 (round-half-to-even: the rounded count image the
@@ -200,11 +246,16 @@ def counts_to_events(pred, max_count=255, times=None):
     times="linear" (max_count <= 255): -> (xs, ys, ps, ts float32, index); event j of an element's n events has the time
     float32(0.01 + 0.99 * j / (n - 1)) (0.01 for n = 1) and every image's events are sorted by the exact j / (n - 1), ties in
     the flat order above -- the reference's linear redistribution (dataloader/encodings.py:367-414) with one time bin, by
-    bmc_slot_emit_timed (include/bmc_hip.h states the contract)."""
+    bmc_slot_emit_timed (include/bmc_hip.h states the contract).
+    spans [B,2] (with times="linear"; float64 on the host): (t_first, t_last) of every image on the sensor's clock -> ts is
+    FLOAT64 on that clock, t = t_first + tau * (t_last - t_first) with tau the float64 time above from the reduced fraction
+    (bmc_slot_emit_clocked); events and order are the same."""
     from . import slots
     if times not in (None, "linear"):
         raise ValueError("counts_to_events: times must be None or 'linear' (got %r)" % (times,))
     timed = times is not None
+    if spans is not None and not timed:
+        raise ValueError("counts_to_events: spans needs times='linear'")
     if not (torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.dtype == torch.float32):
         raise ValueError("counts_to_events: pred must be an fp32 [B,2,sH,sW] tensor")
     if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= slots.MAX_COUNT_LIMIT:
@@ -212,14 +263,17 @@ def counts_to_events(pred, max_count=255, times=None):
                          % (slots.MAX_COUNT_LIMIT, max_count))
     if timed and max_count > slots.MAX_COUNT_TIMED:
         raise ValueError("counts_to_events: times='linear' needs max_count <= %d (got %d)" % (slots.MAX_COUNT_TIMED, max_count))
+    if spans is not None:
+        spans = check_spans("counts_to_events: ", spans, pred.shape[0])
     if not pred.is_cuda:
         raise RuntimeError("counts_to_events: pred must live on the MI355X (no CPU fallback in this build)")
     pred = pred.contiguous()
     B, _, sH, sW = pred.shape
     dev = pred.device
+    clocked = spans is not None
     nparts = slots.emit_parts(sH, sW)
     groups = [(a, min(a + slots.MAX_SLOTS, B)) for a in range(0, B, slots.MAX_SLOTS)]
-    tables = {b - a: slots.SlotTable(b - a, dev, emit=True, timed=timed) for a, b in groups}
+    tables = {b - a: slots.SlotTable(b - a, dev, emit=True, timed=timed, clock=clocked) for a, b in groups}
     parts = torch.zeros(min(B, slots.MAX_SLOTS) * nparts, dtype=torch.int32, device=dev)
     start = torch.zeros(B, dtype=torch.int64, device=dev)
     end = torch.zeros(B, dtype=torch.int64, device=dev)
@@ -235,20 +289,24 @@ def counts_to_events(pred, max_count=255, times=None):
                 em[s]["xs"], em[s]["ys"], em[s]["ps"] = xs.data_ptr(), ys.data_ptr(), ps.data_ptr()
                 em[s]["index_in"], em[s]["index_out"] = start.data_ptr() + 8 * (a + s), end.data_ptr() + 8 * (a + s)
                 em[s]["capacity"] = capacity
-                if timed:
+                if clocked:
+                    ck = t.clock_host()
+                    ck[s]["t_first"], ck[s]["t_last"], ck[s]["ts"] = spans[a + s, 0], spans[a + s, 1], ts.data_ptr()
+                elif timed:
                     em[s]["ts"] = ts.data_ptr()
             t.upload()
             if timed:                                      # (the counting pass sorts nothing: window = 1, capacity = 0)
                 if scratch is None:
                     scratch = torch.empty(slots.emit_timed_scratch_bytes(min(B, slots.MAX_SLOTS), nparts, window),
                                           dtype=torch.uint8, device=dev)
-                slots.emit_timed(t, pred[a:b], max_count, nparts, parts, scratch, window)
+                (slots.emit_clocked if clocked else slots.emit_timed)(t, pred[a:b], max_count, nparts, parts, scratch, window)
             else:
                 slots.emit(t, pred[a:b], max_count, nparts, parts)
 
     none = (torch.empty(1, dtype=torch.int16, device=dev), torch.empty(1, dtype=torch.int16, device=dev),
             torch.empty(1, dtype=torch.int8, device=dev))
-    no_ts = torch.empty(1, dtype=torch.float32, device=dev)
+    ts_dtype = torch.float64 if clocked else torch.float32
+    no_ts = torch.empty(1, dtype=ts_dtype, device=dev)
     run(*none, 0, no_ts)                                   # start = 0: end[b] = the events of image b; nothing is stored
     index = torch.zeros(B + 1, dtype=torch.int64)
     counts = end.cpu()
@@ -260,7 +318,7 @@ def counts_to_events(pred, max_count=255, times=None):
     ps = torch.empty(total, dtype=torch.int8, device=dev)
     start.copy_(index[:B])
     if timed:
-        ts = torch.empty(total, dtype=torch.float32, device=dev)
+        ts = torch.empty(total, dtype=ts_dtype, device=dev)
         run(xs, ys, ps, total, ts, int(counts.max()))
         return xs, ys, ps, ts, index
     run(xs, ys, ps, total)

@@ -141,6 +141,7 @@ _slot_metrics = _sig("bmc_slot_metrics", [_p, _i, _p, _i, _i, _i, _i, _i, _i, _i
 _slot_encode = _sig("bmc_slot_encode", [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
 _slot_emit = _sig("bmc_slot_emit", [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p])
 _slot_emit_timed = _sig("bmc_slot_emit_timed", [_p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _ll, _p])
+_slot_emit_clocked = _sig("bmc_slot_emit_clocked", [_p, _p, _p, _i, _p, _i, _i, _i, _i, _p, _p, _p, _ll, _p])
 _slot_emit_timed_ws = _sig("bmc_slot_emit_timed_scratch_bytes", [_i, _i, _ll], C.c_longlong)
 
 EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_events_to_voxel", "bmc_events_to_stack", "bmc_encode_raw_events", "bmc_pack_weight", "bmc_pack_weight_t", "bmc_split_weight", "bmc_conv",
@@ -155,7 +156,7 @@ EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_event
            "bmc_events_to_voxel_torch", "bmc_stream_create_low_priority", "bmc_small_mm",
            "bmc_wgrad_wino4_nsplit", "bmc_wgrad_wino4", "bmc_wgrad_wino4_reduce", "bmc_wgrad_wino_multi", "bmc_ptr_table",
            "bmc_conv_wino_rows", "bmc_slot_stage", "bmc_slot_commit", "bmc_slot_metrics", "bmc_slot_encode", "bmc_slot_emit",
-           "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes"]
+           "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes", "bmc_slot_emit_clocked"]
 
 
 def check(rc, what):

@@ -16,7 +16,11 @@ entry's columns (one call = two launches for all slots, counted in EMIT_LAUNCHES
 
 Timed event output (csrc/slot_emit_timed.hip): SlotTable(emit=True, timed=True) holds bmc_slot_emit_timed_t entries
 (SLOT_EMIT_TIMED_DTYPE: the same fields and a `ts` column) instead; emit_timed() appends every window's events with their
-float32 times, in time order (one call = EMIT_TIMED_KERNELS launches for all slots, counted in EMIT_TIMED_LAUNCHES)."""
+float32 times, in time order (one call = EMIT_TIMED_KERNELS launches for all slots, counted in EMIT_TIMED_LAUNCHES).
+
+Clocked event output: SlotTable(emit=True, timed=True, clock=True) adds a fourth table of bmc_slot_clock_t entries
+(SLOT_CLOCK_DTYPE: the window's time span on the recording's clock and a float64 `ts` column); emit_clocked() is emit_timed()
+whose slots with a clock entry store float64 times on that clock instead (the same launches, the same counter)."""
 import numpy as np
 import torch
 
@@ -49,6 +53,8 @@ EMIT_TIMED_KERNELS = 6             # launches of one bmc_slot_emit_timed call: c
 MAX_COUNT_TIMED = 255              # the rank table of the timed mode
 MAX_WINDOW_CAPACITY = 1 << 28
 EVENT_T0, EVENT_T1 = 0.01, 1.0     # BMC_EVENT_T0 / BMC_EVENT_T1: the window's time axis
+SLOT_CLOCK_DTYPE = np.dtype([("t_first", "<f8"), ("t_last", "<f8"), ("ts", "<u8")])      # bmc_slot_clock_t
+assert SLOT_CLOCK_DTYPE.itemsize == 24
 _RANK_TABLES = {}
 
 
@@ -58,11 +64,12 @@ class SlotTable:
     copy that last read it has completed, so the host never waits for the GPU to finish the window before.
     events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy.
     emit=True: S bmc_slot_emit_t entries follow those (`emit_host()`, `emit_ptr()`), same copy; with timed=True they are
-    bmc_slot_emit_timed_t entries."""
+    bmc_slot_emit_timed_t entries.  clock=True (needs timed): S bmc_slot_clock_t entries follow those (`clock_host()`,
+    `clock_ptr()`), same copy."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False, emit=False, timed=False):
+    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
@@ -71,10 +78,14 @@ class SlotTable:
         self.timed = bool(timed)
         if self.timed and not self.emit:
             raise ValueError("slots: timed=True needs emit=True")
+        self.clock = bool(clock)
+        if self.clock and not self.timed:
+            raise ValueError("slots: clock=True needs timed=True")
         self._emit_dtype = SLOT_EMIT_TIMED_DTYPE if self.timed else SLOT_EMIT_DTYPE
         self._nslot = S * SLOT_DTYPE.itemsize
         self._nevents = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
-        nbytes = self._nevents + (S * self._emit_dtype.itemsize if emit else 0)
+        self._nemit = self._nevents + (S * self._emit_dtype.itemsize if emit else 0)
+        nbytes = self._nemit + (S * SLOT_CLOCK_DTYPE.itemsize if self.clock else 0)
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
         self._events = [None] * self.RING
@@ -94,7 +105,11 @@ class SlotTable:
 
     def emit_host(self):
         """The emit entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nevents:].view(self._emit_dtype)
+        return self._pinned[self._k].numpy()[self._nevents:self._nemit].view(self._emit_dtype)
+
+    def clock_host(self):
+        """The clock entries of the window being filled (after host(), which cleared them)."""
+        return self._pinned[self._k].numpy()[self._nemit:].view(SLOT_CLOCK_DTYPE)
 
     def upload(self):
         k = self._k
@@ -111,6 +126,9 @@ class SlotTable:
 
     def emit_ptr(self):
         return self.dev.data_ptr() + self._nevents
+
+    def clock_ptr(self):
+        return self.dev.data_ptr() + self._nemit
 
 
 def _check(cond, what):
@@ -278,6 +296,19 @@ def emit_timed(table, pred, max_count, nparts, parts, scratch, window_capacity):
     j / (n - 1), ties in flat emission order, and appended to the entry's xs / ys / ps / ts columns at *index_in;
     *index_out <- *index_in + the window's event count.  A window of more than window_capacity events stores nothing.
     parts: int32 scratch of at least S * nparts words; scratch: uint8, emit_timed_scratch_bytes(S, nparts, window_capacity)."""
+    _emit_timed(False, table, pred, max_count, nparts, parts, scratch, window_capacity)
+
+
+def emit_clocked(table, pred, max_count, nparts, parts, scratch, window_capacity):
+    """emit_timed() on a table with clock entries (bmc_slot_emit_clocked; include/bmc_hip.h states the contract): a slot whose
+    clock entry has a `ts` column stores float64 times t = t_first + tau * (t_last - t_first) there, tau from the reduced
+    fraction of j / (n - 1); a slot without one gets emit_timed()'s float32 column.  Same events, order, capacity rules,
+    arguments and launches (counted in EMIT_TIMED_LAUNCHES)."""
+    _check(getattr(table, "clock", False), "the slot table has no clock entries (SlotTable(emit=True, timed=True, clock=True))")
+    _emit_timed(True, table, pred, max_count, nparts, parts, scratch, window_capacity)
+
+
+def _emit_timed(clocked, table, pred, max_count, nparts, parts, scratch, window_capacity):
     global EMIT_TIMED_LAUNCHES
     _check(table.emit and getattr(table, "timed", False),
            "the slot table has no timed emit entries (SlotTable(emit=True, timed=True))")
@@ -298,7 +329,10 @@ def emit_timed(table, pred, max_count, nparts, parts, scratch, window_capacity):
     _check(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
            and scratch.numel() >= need and scratch.data_ptr() % 8 == 0,
            "scratch must be a contiguous 8-byte aligned uint8 GPU tensor of at least %d bytes" % need)
-    lib.call(lib._slot_emit_timed, "bmc_slot_emit_timed", table.ptr(), table.emit_ptr(), S, pred.data_ptr(), sH, sW, max_count,
-             nparts, parts.data_ptr(), emit_rank_table(pred.device).data_ptr(), scratch.data_ptr(), int(window_capacity),
-             _stream())
+    tail = (S, pred.data_ptr(), sH, sW, max_count, nparts, parts.data_ptr(), emit_rank_table(pred.device).data_ptr(),
+            scratch.data_ptr(), int(window_capacity), _stream())
+    if clocked:
+        lib.call(lib._slot_emit_clocked, "bmc_slot_emit_clocked", table.ptr(), table.emit_ptr(), table.clock_ptr(), *tail)
+    else:
+        lib.call(lib._slot_emit_timed, "bmc_slot_emit_timed", table.ptr(), table.emit_ptr(), *tail)
     EMIT_TIMED_LAUNCHES += 1

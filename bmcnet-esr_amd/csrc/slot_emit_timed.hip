@@ -22,6 +22,12 @@
 // digit is (the workgroup's running count of the digit) + (the digit's counts of the lower waves in this step) + (the lanes
 // below it in its wave with the same digit: eight ballots).
 // Pointers read from the tables go through address-space(1) casts (global_* instructions, never flat_*), as in slots.hip.
+//
+// Clocked output (bmc_slot_emit_clocked): the same six launches with a fourth table of bmc_slot_clock_t.  A slot whose clock
+// entry has a `ts` column stores float64 times on the recording's own clock there instead of the float32 column:
+// t = t_first + tau * (t_last - t_first), tau = T0 + (T1 - T0) * (j / g) / ((n - 1) / g), g = gcd(j, n - 1) -- the reduced
+// fraction gives equal rationals ONE tau, so the float64 column cannot decrease inside a run of ties.  Only the scatter
+// kernel reads the clock table; a NULL table (bmc_slot_emit_timed) or a NULL `ts` keeps the float32 behaviour.
 #include "bmc_common.h"
 
 namespace {
@@ -270,9 +276,29 @@ __global__ __launch_bounds__(EMT) void emit_timed_hist_kernel(const bmc_slot_t* 
     gst<unsigned>(hist + ((long long)s * hrows + b) * 256 + tid, lh[tid]);
 }
 
-// grid (blocks, S): records [b * T2, ...) of rec[s], in their order, to the columns at *index_in + position by high digit
+// float64 time of event j of n on the clock [t_first, t_first + dt]: tau from the REDUCED fraction (Euclid on 8-bit values: at
+// most 12 steps for j <= n - 1 <= 254), then a multiply and an add that are rounded separately (no fma contraction).
+__device__ __forceinline__ double clock_time(double t_first, double dt, unsigned j, unsigned nq) {
+#pragma clang fp contract(off)
+    double tau = BMC_EVENT_T0;
+    if (nq > 1u) {
+        unsigned a = j, b = nq - 1u;
+        for (int it = 0; it < 16 && b != 0u; ++it) {
+            const unsigned r = a % b;
+            a = b;
+            b = r;
+        }
+        tau = BMC_EVENT_T0 + (BMC_EVENT_T1 - BMC_EVENT_T0) * (double)(j / a) / (double)((nq - 1u) / a);
+    }
+    const double span = tau * dt;
+    return t_first + span;
+}
+
+// grid (blocks, S): records [b * T2, ...) of rec[s], in their order, to the columns at *index_in + position by high digit.
+// clock: NULL, or the table of bmc_slot_emit_clocked; a slot with clock[s].ts stores float64 clock times there, not ts.
 __global__ __launch_bounds__(EMT) void emit_timed_scatter_kernel(const bmc_slot_t* __restrict__ table,
-                                                                 const bmc_slot_emit_timed_t* __restrict__ emit, int sH, int sW,
+                                                                 const bmc_slot_emit_timed_t* __restrict__ emit,
+                                                                 const bmc_slot_clock_t* __restrict__ clock, int sH, int sW,
                                                                  const unsigned* __restrict__ hist, int hrows,
                                                                  const unsigned* __restrict__ dbase,
                                                                  const unsigned long long* __restrict__ tot, long long wcap,
@@ -292,6 +318,9 @@ __global__ __launch_bounds__(EMT) void emit_timed_scatter_kernel(const bmc_slot_
     float* const ts = gld<float*>(&ent->ts);
     const long long cap = gld<long long>(&ent->capacity);
     const long long base = gld<long long>(gld<const long long*>(&ent->index_in));
+    double* const ts64 = clock ? gld<double*>(&clock[s].ts) : nullptr;                    // (uniform) the slot is clocked
+    const double t_first = ts64 ? gld<double>(&clock[s].t_first) : 0.0;
+    const double dt = ts64 ? gld<double>(&clock[s].t_last) - t_first : 0.0;
     run[tid] = gld<unsigned>(dbase + (long long)s * 256 + tid) + gld<unsigned>(hist + ((long long)s * hrows + b) * 256 + tid);
     stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
     __syncthreads();
@@ -306,12 +335,16 @@ __global__ __launch_bounds__(EMT) void emit_timed_scatter_kernel(const bmc_slot_
         if (valid && pos < cap) {
             const unsigned idx = r.x, j = (r.y >> 8) & 255u, nq = r.y & 255u;
             const unsigned c = idx >= hw ? 1u : 0u, rem = idx - c * hw, row = rem / (unsigned)sW, x = rem - row * (unsigned)sW;
-            // float64, rounded once: t0 + (t1 - t0) * j / (n - 1)
-            const double t = nq > 1u ? BMC_EVENT_T0 + (BMC_EVENT_T1 - BMC_EVENT_T0) * (double)j / (double)(nq - 1u) : BMC_EVENT_T0;
             gst<short>(xs + pos, (short)x);
             gst<short>(ys + pos, (short)(sH - 1 - (int)row));
             gst<signed char>(pol + pos, (signed char)(c ? -1 : 1));
-            gst<float>(ts + pos, (float)t);
+            if (ts64) {
+                gst<double>(ts64 + pos, clock_time(t_first, dt, j, nq));
+            } else {
+                // float64, rounded once: t0 + (t1 - t0) * j / (n - 1)
+                const double t = nq > 1u ? BMC_EVENT_T0 + (BMC_EVENT_T1 - BMC_EVENT_T0) * (double)j / (double)(nq - 1u) : BMC_EVENT_T0;
+                gst<float>(ts + pos, (float)t);
+            }
         }
     }
 }
@@ -331,27 +364,30 @@ extern "C" long long bmc_slot_emit_timed_scratch_bytes(int S, int nparts, long l
     return (long long)S * (8 * window_capacity + 8 + 1024 + 1024 * hist_rows(nparts, window_capacity));
 }
 
-extern "C" int bmc_slot_emit_timed(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, int S, const float* pred, int sH,
-                                   int sW, int max_count, int nparts, unsigned* parts, const unsigned short* rank_table,
-                                   void* scratch, long long window_capacity, bmc_stream_t s) {
+namespace {
+
+// the six launches of bmc_slot_emit_timed (clock == NULL) and bmc_slot_emit_clocked; `who` names the entry point in messages
+int emit_timed_launch(const char* who, const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock,
+                      int S, const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
+                      const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s) {
     BMC_CHECK_ARG(table && emit && pred && parts && rank_table && scratch && S >= 1 && S <= BMC_MAX_SLOTS,
-                  "bmc_slot_emit_timed: bad arguments");
+                  "%s: bad arguments", who);
     BMC_CHECK_ARG(sH >= 1 && sW >= 1 && sH <= 32767 && sW <= 32767,
-                  "bmc_slot_emit_timed: sH, sW must be 1 .. 32767 (coordinates are int16; got %d x %d)", sH, sW);
+                  "%s: sH, sW must be 1 .. 32767 (coordinates are int16; got %d x %d)", who, sH, sW);
     BMC_CHECK_ARG(max_count >= 1 && max_count <= BMC_SLOT_EMIT_TIMED_MAX_COUNT,
-                  "bmc_slot_emit_timed: 1 <= max_count <= %d (the rank table; got %d)", BMC_SLOT_EMIT_TIMED_MAX_COUNT, max_count);
-    BMC_CHECK_ARG(nparts >= 1 && nparts <= BMC_SLOT_EMIT_MAX_PARTS, "bmc_slot_emit_timed: 1 <= nparts <= %d (got %d)",
+                  "%s: 1 <= max_count <= %d (the rank table; got %d)", who, BMC_SLOT_EMIT_TIMED_MAX_COUNT, max_count);
+    BMC_CHECK_ARG(nparts >= 1 && nparts <= BMC_SLOT_EMIT_MAX_PARTS, "%s: 1 <= nparts <= %d (got %d)", who,
                   BMC_SLOT_EMIT_MAX_PARTS, nparts);
     BMC_CHECK_ARG(window_capacity >= 1 && window_capacity <= BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
-                  "bmc_slot_emit_timed: 1 <= window_capacity <= %lld (got %lld)", (long long)BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
+                  "%s: 1 <= window_capacity <= %lld (got %lld)", who, (long long)BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
                   window_capacity);
     BMC_CHECK_ARG(((unsigned long long)pred & 3ull) == 0 && ((unsigned long long)scratch & 7ull) == 0 &&
                       ((unsigned long long)rank_table & 1ull) == 0,
-                  "bmc_slot_emit_timed: pred must be 4-byte, scratch 8-byte, rank_table 2-byte aligned");
+                  "%s: pred must be 4-byte, scratch 8-byte, rank_table 2-byte aligned", who);
     const long long n = 2ll * sH * sW;                                // < 2^31 for sH, sW <= 32767
     const long long chunk = ((n + nparts - 1) / nparts + 3) / 4 * 4;
     BMC_CHECK_ARG(chunk * max_count < (1ll << 32),
-                  "bmc_slot_emit_timed: %lld elements per part x max_count %d overflow a part's 32-bit total: use more parts",
+                  "%s: %lld elements per part x max_count %d overflow a part's 32-bit total: use more parts", who,
                   chunk, max_count);
     const int vec = n % 4 == 0 && ((unsigned long long)pred & 15ull) == 0;
     const int blocks = (int)((window_capacity + T2 - 1) / T2), hrows = (int)hist_rows(nparts, window_capacity);
@@ -376,8 +412,26 @@ extern "C" int bmc_slot_emit_timed(const bmc_slot_t* table, const bmc_slot_emit_
     hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(S), dim3(EMT), 0, st, table, emit, 0, nparts, (const unsigned*)parts, hist,
                        hrows, dbase, tot, window_capacity);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scan 2)");
-    hipLaunchKernelGGL(emit_timed_scatter_kernel, dim3(blocks, S), dim3(EMT), 0, st, table, emit, sH, sW, (const unsigned*)hist,
+    hipLaunchKernelGGL(emit_timed_scatter_kernel, dim3(blocks, S), dim3(EMT), 0, st, table, emit, clock, sH, sW, (const unsigned*)hist,
                        hrows, (const unsigned*)dbase, (const unsigned long long*)tot, window_capacity, (const u32x2*)rec);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scatter)");
     return 0;
+}
+
+}  // namespace
+
+extern "C" int bmc_slot_emit_timed(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, int S, const float* pred, int sH,
+                                   int sW, int max_count, int nparts, unsigned* parts, const unsigned short* rank_table,
+                                   void* scratch, long long window_capacity, bmc_stream_t s) {
+    return emit_timed_launch("bmc_slot_emit_timed", table, emit, nullptr, S, pred, sH, sW, max_count, nparts, parts, rank_table,
+                             scratch, window_capacity, s);
+}
+
+extern "C" int bmc_slot_emit_clocked(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock,
+                                     int S, const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
+                                     const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s) {
+    BMC_CHECK_ARG(clock && ((unsigned long long)clock & 7ull) == 0,
+                  "bmc_slot_emit_clocked: the clock table must be an 8-byte aligned device array of S entries");
+    return emit_timed_launch("bmc_slot_emit_clocked", table, emit, clock, S, pred, sH, sW, max_count, nparts, parts, rank_table,
+                             scratch, window_capacity, s);
 }

@@ -13,10 +13,11 @@ import statistics
 import numpy as np
 import torch
 
-EventRecording = collections.namedtuple("EventRecording", "lr gt lr_index gt_index lr_size gt_size")
+EventRecording = collections.namedtuple("EventRecording", "lr gt lr_index gt_index lr_size gt_size", defaults=(None,) * 5)
 EventRecording.__doc__ = """An event-backed recording for MultiStreamSR.open_events / evaluate_recordings: lr, gt = (xs, ys, ps)
 raw dataset columns on the GPU (int16, int16, float64); lr_index, gt_index [L,2] = the event range [first, end) of every
-item's LR / ground-truth frame (bmc_hip.encodings.event_window_indices); lr_size = (H, W), gt_size = (gh, gw)."""
+item's LR / ground-truth frame (bmc_hip.encodings.event_window_indices); lr_size = (H, W), gt_size = (gh, gw).  A recording
+without ground truth: gt = gt_index = gt_size = None."""
 
 
 class StreamingSR:
@@ -257,7 +258,21 @@ class MultiStreamSR:
     above.  results() then also carries sr_ts (float32, on the GPU), parallel to sr_events.  Times are window-normalised: a
     count image has no absolute clock.  The sort works in per-slot scratch of `window_event_capacity` events (open /
     open_events; default 2 x scale^2 x the LR events of the recording's busiest frame, at most 2 x sH x sW x max_count); a
-    window that emits more stores nothing, the index keeps the true count and results() raises with the capacity needed."""
+    window that emits more stores nothing, the index keeps the true count and results() raises with the capacity needed.
+
+    Recordings WITHOUT ground truth (open(frames), open_events(lr, None, lr_index, None, lr_size)): what a deployed sensor
+    delivers.  Their results() carry no esr_mse / bicubic_mse; they only have to match the session's (H, W) and may share it
+    with recordings that have a ground truth.  bmc_slot_metrics is launched only once a recording with ground truth has been
+    opened (the first such open after a capture invalidates the graph, as the first open_events does).
+
+    Events on the SENSOR'S CLOCK (event_times="linear"; open(..., spans=) / open_events(..., lr_ts= or spans=)): spans [L,2]
+    float64 = (t_first, t_last) of every item on the recording's own time base (open_events derives them from the timestamp
+    column lr_ts: bmc_hip.encodings.event_block_spans).  Window i predicts item i+1 (infer_BMCNet.py:52) and uses its span:
+    sr_ts is then FLOAT64, t = t_first + tau * (t_last - t_first) with tau the window time above computed from the reduced
+    fraction of j / (n - 1) (bmc_slot_emit_clocked; include/bmc_hip.h states the contract) -- the inverse of
+    event_formatting's normalisation (dataloader/base_dataset.py:30) without its 1e-6.  Each window is in time order; with
+    sliding_window < window the spans of consecutive windows overlap, so the concatenation of a recording's windows is
+    globally sorted only for non-overlapping spans.  Clocked and unclocked recordings may share a session."""
 
     MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
     MAX_COUNT_TIMED = 255        # event_times: the sort key is a 16-bit rank of j / (n - 1), n <= 255
@@ -289,12 +304,13 @@ class MultiStreamSR:
         self.sched = SlotScheduler(self.S)
         self.replays = 0
         self._recs = {}
-        self._size = None          # (H, W, gh, gw) of the first recording
+        self._size = None          # (H, W) of the first recording, (H, W, gh, gw) once one with ground truth has been opened
         self._bufs = None
         self._steps = []           # (start, end) events per window
         self._calls = 0
         self._graph = self._stamp = None
         self._has_events = False
+        self._has_clock = False
 
     # ---------------------------------------------------------------- recordings
     def _check_capacity(self, who, event_capacity):
@@ -319,23 +335,44 @@ class MultiStreamSR:
         most = 2 * self.scale ** 2 * H * W * self.max_count
         return max(1, min(2 * self.scale ** 2 * int(busiest), most, self.MAX_WINDOW_CAPACITY))
 
-    def open(self, frames, gts, gt_size=None, event_capacity=None, window_event_capacity=None):
+    def _check_spans(self, who, spans, L):
+        """spans (or None) -> a validated [L,2] float64 table on the host (or None)."""
+        if spans is None:
+            return None
+        if self.event_times is None:
+            raise ValueError("MultiStreamSR.%s: spans / lr_ts need a session with event_times='linear'" % who)
+        from bmc_hip.encodings import check_spans
+        return check_spans("MultiStreamSR.%s: " % who, spans, L)
+
+    def open(self, frames, gts=None, gt_size=None, event_capacity=None, window_event_capacity=None, spans=None):
         """Queue one recording -> handle.  frames [L,2,H,W], gts [L,2,gh,gw] (fp32, on the GPU); gt_size (the reference's
-        gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size.  event_capacity (emit_events):
-        events the output columns hold; default 2 x scale^2 x the sum of `frames` (one device reduction here).
-        window_event_capacity (event_times): events of ONE window the sort scratch holds; default 2 x scale^2 x the largest
-        sum of one frame."""
+        gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size.  gts=None: a recording without
+        ground truth (no metrics).  event_capacity (emit_events): events the output columns hold; default 2 x scale^2 x the
+        sum of `frames` (one device reduction here).  window_event_capacity (event_times): events of ONE window the sort
+        scratch holds; default 2 x scale^2 x the largest sum of one frame.  spans (event_times) [L,2] float64 on the host:
+        (t_first, t_last) of every frame on the sensor's clock -> sr_ts is float64 on that clock."""
         self._check_capacity("open", event_capacity)
         self._check_window_capacity("open", window_event_capacity)
-        if frames.dim() != 4 or frames.shape[1] != 2 or gts.dim() != 4 or tuple(gts.shape[:2]) != (frames.shape[0], 2):
-            raise ValueError("MultiStreamSR.open: frames [L,2,H,W] and gts [L,2,gh,gw] (got %s, %s)"
-                             % (tuple(frames.shape), tuple(gts.shape)))
-        if not (frames.is_cuda and gts.is_cuda and frames.dtype == torch.float32 and gts.dtype == torch.float32):
-            raise ValueError("MultiStreamSR.open: frames and gts must be fp32 GPU tensors")
+        if gts is None:
+            if frames.dim() != 4 or frames.shape[1] != 2:
+                raise ValueError("MultiStreamSR.open: frames [L,2,H,W] (got %s)" % (tuple(frames.shape),))
+            if gt_size is not None:
+                raise ValueError("MultiStreamSR.open: gt_size without a ground truth")
+            spans = self._check_spans("open", spans, frames.shape[0])
+            if not (frames.is_cuda and frames.dtype == torch.float32):
+                raise ValueError("MultiStreamSR.open: frames must be an fp32 GPU tensor")
+        else:
+            if frames.dim() != 4 or frames.shape[1] != 2 or gts.dim() != 4 or tuple(gts.shape[:2]) != (frames.shape[0], 2):
+                raise ValueError("MultiStreamSR.open: frames [L,2,H,W] and gts [L,2,gh,gw] (got %s, %s)"
+                                 % (tuple(frames.shape), tuple(gts.shape)))
+            spans = self._check_spans("open", spans, frames.shape[0])
+            if not (frames.is_cuda and gts.is_cuda and frames.dtype == torch.float32 and gts.dtype == torch.float32):
+                raise ValueError("MultiStreamSR.open: frames and gts must be fp32 GPU tensors")
         L = frames.shape[0]
         if L < self.seqn:
             raise ValueError("MultiStreamSR.open: %d frames, fewer than one window of seqn = %d" % (L, self.seqn))
-        H, W, gh, gw = frames.shape[2], frames.shape[3], gts.shape[2], gts.shape[3]
+        H, W = frames.shape[2], frames.shape[3]
+        gh, gw = (None, None) if gts is None else (gts.shape[2], gts.shape[3])
         if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
             raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
         if max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT and self.emit_events:
@@ -346,23 +383,33 @@ class MultiStreamSR:
             event_capacity = 2 * self.scale ** 2 * int(frames.sum(dtype=torch.float64).item())
         if self.event_times is not None and window_event_capacity is None:
             window_event_capacity = self._default_window_capacity(frames.sum(dim=(1, 2, 3), dtype=torch.float64).max().item(), H, W)
-        return self._add({"frames": frames.contiguous(), "gts": gts.contiguous()}, L, frames.device, event_capacity,
-                         window_event_capacity)
+        rec = {"frames": frames.contiguous()}
+        if gts is not None:
+            rec["gts"] = gts.contiguous()
+        return self._add(rec, L, frames.device, event_capacity, window_event_capacity, spans)
 
-    def _set_size(self, who, H, W, gh, gw):
-        if self._size is None:
-            self._size = (H, W, gh, gw)
-        elif self._size != (H, W, gh, gw):
+    def _set_size(self, who, H, W, gh=None, gw=None):
+        """The session's size: (H, W) and, once a recording with ground truth has been opened, (gh, gw).  A recording without
+        ground truth (gh None) only has to match (H, W)."""
+        size = (H, W) if gh is None else (H, W, gh, gw)
+        if self._size is not None and self._size[:len(size)] != size[:len(self._size)]:
             raise ValueError("MultiStreamSR.%s: sizes %s differ from the first recording's %s (group recordings by sensor "
-                             "size)" % (who, (H, W, gh, gw), self._size))
+                             "size)" % (who, size, self._size))
+        if self._size is None or len(size) > len(self._size):
+            self._size = size
+            if len(size) == 4 and self._bufs is not None:  # a running session without ground truth: the metrics launch joins
+                if "gt_scratch" in self._bufs:
+                    self._bufs["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=self._bufs["gt_scratch"].device)
+                self.invalidate()
 
-    def _add(self, rec, L, device, event_capacity=None, window_event_capacity=None):
+    def _add(self, rec, L, device, event_capacity=None, window_event_capacity=None, spans=None):
         """Queue a recording of L items (frames or event blocks) -> handle."""
         from bmc_hip import slots
-        H, W, gh, gw = self._size
+        H, W = self._size[:2]
         nwin = L - self.seqn + 1
+        if "gts" in rec or "gt" in rec:                    # the result sums of a recording with ground truth
+            rec["sse"] = torch.zeros(nwin, slots.metric_parts(*self._size[2:]), 2, dtype=torch.float64, device=device)
         rec.update(n=nwin, steps=[], device=device,
-                   sse=torch.zeros(nwin, slots.metric_parts(gh, gw), 2, dtype=torch.float64, device=device),
                    keep=torch.empty(nwin, 2, self.scale * H, self.scale * W, device=device) if self.keep_predictions else None)
         if self.emit_events:                               # the recording's output stream: three columns and the index table
             cap = max(int(event_capacity), 1)
@@ -371,7 +418,15 @@ class MultiStreamSR:
                        ev_ps=torch.empty(cap, dtype=torch.int8, device=device),
                        ev_index=torch.zeros(nwin + 1, dtype=torch.int64, device=device))
         if self.event_times is not None:                   # ... a time column, and room for its largest window in the sort
-            rec.update(ev_ts=torch.empty(cap, dtype=torch.float32, device=device), win_capacity=int(window_event_capacity))
+            rec.update(ev_ts=torch.empty(cap, dtype=torch.float32 if spans is None else torch.float64, device=device),
+                       win_capacity=int(window_event_capacity))
+            if spans is not None:                          # a clocked recording: float64 times on its own clock
+                rec["spans"] = spans
+                if not self._has_clock:
+                    self._has_clock = True
+                    if self._bufs is not None:             # a running session: the table grows a clock part
+                        self._bufs["table"] = self._table(device)
+                        self.invalidate()
             if rec["win_capacity"] > self._wcap:
                 self._wcap = rec["win_capacity"]
                 if self._bufs is not None:                 # a running session: the sort scratch grows
@@ -384,7 +439,8 @@ class MultiStreamSR:
     MAX_SEQN_EVENTS = 8          # bmc_slot_events_t holds the ranges of at most 8 LR frames (BMC_SLOT_MAX_SEQN)
     MAX_WIDTH_EVENTS = 7680      # bmc_slot_encode: one row of both channels must fit a workgroup's LDS band
 
-    def open_events(self, lr, gt, lr_index, gt_index, lr_size, gt_size, event_capacity=None, window_event_capacity=None):
+    def open_events(self, lr, gt=None, lr_index=None, gt_index=None, lr_size=None, gt_size=None, event_capacity=None,
+                    window_event_capacity=None, lr_ts=None, spans=None):
         """Queue one event-backed recording -> handle.  lr, gt = (xs, ys, ps): the raw dataset columns of the LR and the
         ground-truth stream (1-D int16, int16, float64 GPU tensors; polarities -1 / 0 / +1); lr_index, gt_index [L,2]
         (integers, on the host): item j is LR events [lr_index[j,0], lr_index[j,1]) and ground-truth events [gt_index[j,0],
@@ -392,11 +448,24 @@ class MultiStreamSR:
         items i .. i+seqn-1 and the ground truth of item i+1, as open() on the encoded frames.  Every range is checked here
         against the column lengths: the kernel trusts the table.  event_capacity (emit_events): events the output columns
         hold; default 2 x scale^2 x the sum of the lengths of the LR item ranges.  window_event_capacity (event_times): events of
-        ONE window the sort scratch holds; default 2 x scale^2 x the longest LR item range."""
+        ONE window the sort scratch holds; default 2 x scale^2 x the longest LR item range.
+        gt = gt_index = gt_size = None (all three or none): a recording without ground truth (no metrics).
+        lr_ts (event_times): the recording's float64 timestamp column, parallel to lr[0], on the GPU or the host -> the span
+        of every item (bmc_hip.encodings.event_block_spans) and float64 sr_ts on the sensor's clock; or spans [L,2] directly
+        (not both)."""
         who = "MultiStreamSR.open_events: "
         self._check_capacity("open_events", event_capacity)
         self._check_window_capacity("open_events", window_event_capacity)
-        for name, cols in (("lr", lr), ("gt", gt)):
+        if lr_index is None or lr_size is None:
+            raise ValueError(who + "lr_index and lr_size are required")
+        has_gt = gt is not None
+        if (gt_index is not None) != has_gt or (gt_size is not None) != has_gt:
+            raise ValueError(who + "gt, gt_index and gt_size are all given or all None")
+        if lr_ts is not None and spans is not None:
+            raise ValueError(who + "give lr_ts or spans, not both")
+        if (lr_ts is not None or spans is not None) and self.event_times is None:
+            raise ValueError(who + "spans / lr_ts need a session with event_times='linear'")
+        for name, cols in (("lr", lr), ("gt", gt))[:1 + has_gt]:
             if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
                 raise ValueError(who + "%s must be three tensors (xs, ys, ps)" % name)
             if [t.dtype for t in cols] != [torch.int16, torch.int16, torch.float64]:
@@ -404,7 +473,7 @@ class MultiStreamSR:
             if any(t.dim() != 1 or t.numel() != cols[0].numel() or not t.is_contiguous() for t in cols):
                 raise ValueError(who + "%s columns must be contiguous 1-D tensors of one length" % name)
         tables = []
-        for name, idx, n in (("lr_index", lr_index, lr[0].numel()), ("gt_index", gt_index, gt[0].numel())):
+        for name, idx, n in (("lr_index", lr_index, lr[0].numel()), ("gt_index", gt_index, gt[0].numel() if has_gt else 0))[:1 + has_gt]:
             a = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx)
             if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
                 raise ValueError(who + "%s must be an integer [L,2] table (got %s %s)" % (name, a.dtype, a.shape))
@@ -414,28 +483,36 @@ class MultiStreamSR:
             if a.size and (a.min() < 0 or a.max() > n):
                 raise ValueError(who + "%s has a range outside the %d events of its columns" % (name, n))
             tables.append(a)
-        lr_index, gt_index = tables
-        if len(lr_index) != len(gt_index):
+        lr_index, gt_index = tables if has_gt else (tables[0], None)
+        if has_gt and len(lr_index) != len(gt_index):
             raise ValueError(who + "lr_index has %d rows, gt_index %d" % (len(lr_index), len(gt_index)))
         L = len(lr_index)
         if L < self.seqn:
             raise ValueError(who + "%d items, fewer than one window of seqn = %d" % (L, self.seqn))
         if self.seqn > self.MAX_SEQN_EVENTS:
             raise ValueError(who + "seqn <= %d for event-backed recordings" % self.MAX_SEQN_EVENTS)
+        if lr_ts is not None:
+            if not ((torch.is_tensor(lr_ts) and lr_ts.dtype == torch.float64 and lr_ts.dim() == 1) or
+                    (isinstance(lr_ts, np.ndarray) and lr_ts.dtype == np.float64 and lr_ts.ndim == 1)) \
+                    or len(lr_ts) != lr[0].numel() or len(lr_ts) < 1:
+                raise ValueError(who + "lr_ts must be a 1-D float64 column parallel to lr[0]")
+            from bmc_hip.encodings import event_block_spans
+            spans = event_block_spans(lr_ts, lr_index)
+        spans = self._check_spans("open_events", spans, L)
         try:
-            (H, W), (gh, gw) = (int(v) for v in lr_size), (int(v) for v in gt_size)
+            (H, W), (gh, gw) = (int(v) for v in lr_size), ((int(v) for v in gt_size) if has_gt else (None, None))
         except (TypeError, ValueError):
             raise ValueError(who + "lr_size = (H, W) and gt_size = (gh, gw)") from None
-        if min(H, W, gh, gw) < 1 or max(W, gw) > self.MAX_WIDTH_EVENTS:
+        if min(H, W, gh or 1, gw or 1) < 1 or max(W, gw or 1) > self.MAX_WIDTH_EVENTS:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)"
                              % (self.MAX_WIDTH_EVENTS, (H, W), (gh, gw)))
         if self.emit_events and max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
             raise ValueError(who + "predictions of %d x %d cannot be emitted (int16 coordinates)"
                              % (self.scale * H, self.scale * W))
-        cols = tuple(lr) + tuple(gt)
+        cols = tuple(lr) + (tuple(gt) if has_gt else ())
         if not all(t.is_cuda and t.device == cols[0].device for t in cols):
             raise ValueError(who + "the columns must be GPU tensors on one device")
-        for name, ps in (("lr", lr[2]), ("gt", gt[2])):
+        for name, ps in (("lr", lr[2]), ("gt", gt[2] if has_gt else None))[:1 + has_gt]:
             if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
                 raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
         self._set_size("open_events", H, W, gh, gw)
@@ -443,8 +520,10 @@ class MultiStreamSR:
             event_capacity = 2 * self.scale ** 2 * int((lr_index[:, 1] - lr_index[:, 0]).sum())
         if self.event_times is not None and window_event_capacity is None:
             window_event_capacity = self._default_window_capacity((lr_index[:, 1] - lr_index[:, 0]).max(), H, W)
-        h = self._add({"lr": tuple(lr), "gt": tuple(gt), "lr_index": lr_index, "gt_index": gt_index}, L, cols[0].device,
-                      event_capacity, window_event_capacity)
+        rec = {"lr": tuple(lr), "lr_index": lr_index}
+        if has_gt:
+            rec.update(gt=tuple(gt), gt_index=gt_index)
+        h = self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
         if not self._has_events:
             self._has_events = True
             if self._bufs is not None:                     # a running frames-only session: the table grows an event part
@@ -456,10 +535,11 @@ class MultiStreamSR:
         """Bytes the recording keeps on the GPU: its columns (event-backed) or frames, its result sums, kept predictions and
         (emit_events) its output columns with their index."""
         r = self._recs[handle]
-        data = r["lr"] + r["gt"] if "lr" in r else (r["frames"], r["gts"])
+        data = r["lr"] + r.get("gt", ()) if "lr" in r else (r["frames"],) + ((r["gts"],) if "gts" in r else ())
         if "ev_xs" in r:
             data = tuple(data) + (r["ev_xs"], r["ev_ys"], r["ev_ps"], r["ev_index"]) + ((r["ev_ts"],) if "ev_ts" in r else ())
-        return sum(t.numel() * t.element_size() for t in data + (r["sse"],) + (() if r["keep"] is None else (r["keep"],)))
+        data = tuple(data) + ((r["sse"],) if "sse" in r else ()) + (() if r["keep"] is None else (r["keep"],))
+        return sum(t.numel() * t.element_size() for t in data)
 
     def scratch_bytes(self):
         """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened) and,
@@ -471,13 +551,20 @@ class MultiStreamSR:
             nbytes = slots.emit_timed_scratch_bytes(self.S, slots.emit_parts(self.scale * H, self.scale * W), self._wcap)
         if not self._has_events:
             return nbytes
-        H, W, gh, gw = self._size
+        H, W = self._size[:2]
+        gh, gw = self._gt_scratch_size()
         return nbytes + 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
 
+    def _gt_scratch_size(self):
+        """(gh, gw) of the event-backed slots' ground-truth scratch: a 1 x 1 placeholder (bmc_slot_encode only zero-fills it)
+        while no recording of the session has a ground truth."""
+        return self._size[2:] if len(self._size) == 4 else (1, 1)
+
     def results(self, handle):
-        """-> dict(esr_mse=[...], bicubic_mse=[...], time=[...] per window done so far[, predictions=[n,2,sH,sW]][,
-        sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][, sr_ts float32 on the GPU,
-        parallel to sr_events (event_times)]).  Raises RuntimeError when the windows emitted more events than the recording's
+        """-> dict(esr_mse=[...], bicubic_mse=[...] (a recording with ground truth only), time=[...] per window done so far[,
+        predictions=[n,2,sH,sW]][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
+        sr_ts on the GPU, parallel to sr_events (event_times): float32 inside each window, or float64 on the sensor's clock for
+        a recording opened with spans / lr_ts]).  Raises RuntimeError when the windows emitted more events than the recording's
         event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity
         needed)."""
         r = self._recs[handle]
@@ -485,10 +572,11 @@ class MultiStreamSR:
         if done:
             self._steps[r["steps"][-1]][1].synchronize()
         from bmc_hip import slots
-        n = 2 * self._size[2] * self._size[3]
-        sse = slots.sum_parts(r["sse"][:done]) / n
-        out = {"esr_mse": sse[:, 0].tolist(), "bicubic_mse": sse[:, 1].tolist(),
-               "time": [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]}
+        out = {}
+        if "sse" in r:
+            sse = slots.sum_parts(r["sse"][:done]) / (2 * self._size[2] * self._size[3])
+            out.update(esr_mse=sse[:, 0].tolist(), bicubic_mse=sse[:, 1].tolist())
+        out["time"] = [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]
         if self.keep_predictions:
             out["predictions"] = r["keep"][:done]
         if self.emit_events:
@@ -512,13 +600,12 @@ class MultiStreamSR:
     # ---------------------------------------------------------------- windows
     def _buffers(self, device):
         if self._bufs is None:
-            H, W, _, _ = self._size
+            H, W = self._size[:2]
             S, nfeat = self.S, 1 if self.plain else 3
             from bmc_hip import slots
             b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
                  "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
-                 "table": slots.SlotTable(S, device, events=self._has_events, emit=self.emit_events,
-                                          timed=self.event_times is not None)}
+                 "table": self._table(device)}
             if self.emit_events:
                 b["emit_parts"] = torch.zeros(S * slots.emit_parts(self.scale * H, self.scale * W), dtype=torch.int32,
                                               device=device)
@@ -534,6 +621,12 @@ class MultiStreamSR:
             self._bufs = b
         return self._bufs
 
+    def _table(self, device):
+        """The slot table with the parts the session needs so far."""
+        from bmc_hip import slots
+        return slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
+                               timed=self.event_times is not None, clock=self._has_clock)
+
     def _sort_buffers(self, b, device):
         from bmc_hip import slots
         H, W = self._size[:2]
@@ -542,10 +635,10 @@ class MultiStreamSR:
                                                                        self._wcap), dtype=torch.uint8, device=device)
 
     def _event_buffers(self, b, device):
-        from bmc_hip import slots
-        H, W, gh, gw = self._size
+        H, W = self._size[:2]
+        gh, gw = self._gt_scratch_size()
         if not b["table"].events:
-            b["table"] = slots.SlotTable(self.S, device, events=True, emit=self.emit_events, timed=self.event_times is not None)
+            b["table"] = self._table(device)
         b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
         b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
 
@@ -555,20 +648,23 @@ class MultiStreamSR:
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """[encode ->] stage -> model -> commit -> metrics [-> emit] (what a graph replay runs)."""
+        """[encode ->] stage -> model -> commit [-> metrics] [-> emit] (what a graph replay runs)."""
         from bmc_hip import slots
         b = self._bufs
-        H, W, gh, gw = self._size
+        H, W = self._size[:2]
         if "lr_scratch" in b:
             slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
         slots.stage(b["table"], b["x"], b["pool"], b["feat"], b["pred"])
         out = self._forward()
         cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.contiguous(memory_format=torch.channels_last)
         slots.commit(b["table"], [cl(t) for t in out[:-1]], b["pool"], out[-1].contiguous(), b["pred"])
-        slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
+        if len(self._size) == 4:                           # a recording with ground truth has been opened
+            gh, gw = self._size[2:]
+            slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
         if self.event_times is not None:
-            slots.emit_timed(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
-                             b["emit_parts"], b["emit_scratch"], self._wcap)
+            emit = slots.emit_clocked if self._has_clock else slots.emit_timed
+            emit(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
+                 b["emit_parts"], b["emit_scratch"], self._wcap)
         elif self.emit_events:
             slots.emit(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
                        b["emit_parts"])
@@ -600,12 +696,13 @@ class MultiStreamSR:
         if plan is None:
             return False
         from bmc_hip import slots
-        H, W, gh, gw = self._size
+        H, W = self._size[:2]
         first = next(self._recs[p[0]] for p in plan if p is not None)
         b = self._buffers(first["device"])
         e = b["table"].host()
         ev = b["table"].events_host() if b["table"].events else None
         em = b["table"].emit_host() if self.emit_events else None
+        ck = b["table"].clock_host() if b["table"].clock else None
         for s, p in enumerate(plan):
             if p is None:
                 continue
@@ -613,23 +710,29 @@ class MultiStreamSR:
             r = self._recs[h]
             if "lr" in r:                                  # event-backed: the entry points at the slot's scratch images
                 e[s]["frames"] = b["lr_scratch"][s].data_ptr()
-                e[s]["gt"] = b["gt_scratch"][s].data_ptr()
-                for k, t in zip(("lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps"), r["lr"] + r["gt"]):
+                for k, t in zip(("lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps"), r["lr"] + r.get("gt", ())):
                     ev[k][s] = t.data_ptr()
                 ev["lr_range"][s, :self.seqn] = r["lr_index"][i:i + self.seqn]
-                ev["gt_range"][s] = r["gt_index"][i + 1]
+                if "gt" in r:                              # (without: NULL columns, range (0, 0): the scratch is only zero-filled)
+                    e[s]["gt"] = b["gt_scratch"][s].data_ptr()
+                    ev["gt_range"][s] = r["gt_index"][i + 1]
             else:
                 e[s]["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
-                e[s]["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * gh * gw
+                if "gts" in r:
+                    e[s]["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * self._size[2] * self._size[3]
             e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
-            e[s]["result"] = r["sse"][i].data_ptr()
+            if "sse" in r:                                 # (without ground truth: gt = 0, result = 0 -- no metrics for the slot)
+                e[s]["result"] = r["sse"][i].data_ptr()
             e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
             if em is not None:                             # window i appends at index[i] and leaves index[i+1]
                 em[s]["xs"], em[s]["ys"], em[s]["ps"] = r["ev_xs"].data_ptr(), r["ev_ys"].data_ptr(), r["ev_ps"].data_ptr()
                 em[s]["index_in"] = r["ev_index"].data_ptr() + 8 * i
                 em[s]["index_out"] = r["ev_index"].data_ptr() + 8 * (i + 1)
                 em[s]["capacity"] = r["ev_capacity"]
-                if "ev_ts" in r:
+                if "spans" in r:                           # window i predicts item i+1: its span, float64 times
+                    ck[s]["t_first"], ck[s]["t_last"] = r["spans"][i + 1]
+                    ck[s]["ts"] = r["ev_ts"].data_ptr()
+                elif "ev_ts" in r:
                     em[s]["ts"] = r["ev_ts"].data_ptr()
             r["steps"].append(len(self._steps))
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -660,10 +763,12 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                         window_event_capacity=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
-    columns + index tables, encoded window by window: MultiStreamSR.open_events).  -> dict(
-      results = {metric: {name: value}}  per recording the mean over its windows of esr_mse, bicubic_mse, time (ms), and
-                                         params (millions) -- infer_body's MetricTracker result (:34,:70-86),
-      mean    = {metric: mean over recordings}  (results_mean, :284-291)[,
+    columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
+    (frames, None) or an EventRecording with gt = None.  -> dict(
+      results = {metric: {name: value}}  per recording the mean over its windows of esr_mse, bicubic_mse (recordings with
+                                         ground truth only), time (ms), and params (millions) -- infer_body's MetricTracker
+                                         result (:34,:70-86),
+      mean    = {metric: mean over the recordings listed}  (results_mean, :284-291; a metric no recording has is absent)[,
       predictions = {name: [n_windows,2,sH,sW]}  with keep_predictions][,
       sr_events   = {name: (xs, ys, ps, index [n_windows+1])}  with emit_events: the super-resolved event stream of every
                                          recording (MultiStreamSR(emit_events=True); event_capacity: per recording, None =
@@ -676,22 +781,23 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
-            if gt_size is not None and tuple(int(v) for v in gt_size) != tuple(int(v) for v in r.gt_size):
+            if gt_size is not None and r.gt_size is not None and tuple(int(v) for v in gt_size) != tuple(int(v) for v in r.gt_size):
                 raise ValueError("evaluate_recordings: gt_size %s differs from recording %s's %s"
                                  % (tuple(gt_size), name, tuple(r.gt_size)))
             handles.append((name, ms.open_events(*r, event_capacity=event_capacity,
                                                  window_event_capacity=window_event_capacity)))
         else:
-            handles.append((name, ms.open(r[0], r[1], gt_size, event_capacity=event_capacity,
+            handles.append((name, ms.open(r[0], r[1], gt_size if r[1] is not None else None, event_capacity=event_capacity,
                                           window_event_capacity=window_event_capacity)))
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
-    breakdown = collections.defaultdict(dict)
+    breakdown = {k: {} for k in ("esr_mse", "bicubic_mse", "time", "params")}
     preds, streams, times = {}, {}, {}
     for name, h in handles:
         r = ms.results(h)
         for k in ("esr_mse", "bicubic_mse", "time"):
-            breakdown[k][name] = float(statistics.mean(r[k]))
+            if k in r:
+                breakdown[k][name] = float(statistics.mean(r[k]))
         breakdown["params"][name] = params
         if keep_predictions:
             preds[name] = r["predictions"]
@@ -699,7 +805,7 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
             streams[name] = r["sr_events"] + (r["sr_index"],)
         if event_times is not None:
             times[name] = r["sr_ts"]
-    out = {"results": dict(breakdown), "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items()}}
+    out = {"results": breakdown, "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}}
     if keep_predictions:
         out["predictions"] = preds
     if emit_events:

@@ -584,6 +584,37 @@ int bmc_slot_emit_timed(const bmc_slot_t* table, const bmc_slot_emit_timed_t* em
                         int max_count, int nparts, unsigned* parts, const unsigned short* rank_table, void* scratch,
                         long long window_capacity, bmc_stream_t s);
 
+/* CLOCKED event output (MultiStreamSR.open / open_events with spans= or lr_ts=): the timed stream with float64 times on the
+ * RECORDING'S OWN CLOCK.  The caller supplies, per slot and window, the time span [t_first, t_last] of the item the window
+ * predicts (sensor microseconds, epoch seconds, ...: float32 cannot hold such a time base).  Counts, the event set, xs / ys /
+ * ps, the order (the exact rational j / (n - 1), ties in flat emission order), the storage rule, both capacity rules and the
+ * determinism are EXACTLY those of the timed output above; only the time column differs:
+ *   Time.   For event j of an element's n events let g = gcd(j, n - 1).  In float64,
+ *             tau = T0 + (T1 - T0) * (j / g) / ((n - 1) / g)   (the product first, then the quotient, then the sum; tau = T0
+ *                                                               for n = 1; j / g and (n - 1) / g are exact integers),
+ *             t   = t_first + tau * (t_last - t_first)         (a float64 multiply and a float64 add, each rounded on its own:
+ *                                                               never a fused multiply-add),
+ *           and t is stored as float64.  The REDUCED fraction matters: the unreduced float64 expression gives values one ulp
+ *           apart for equal rationals (925 of the 19 693 distinct rationals with n <= 255), which float32 rounding hides but
+ *           a float64 column would show as a decrease inside a run of ties.  With it every rational has one tau, tau is
+ *           strictly increasing in the rational, (float)tau equals the timed output's float32 time for every (j, n), and t is
+ *           non-decreasing along every sorted window for any t_last >= t_first.
+ *           This inverts the normalisation of BaseDataset.event_formatting (dataloader/base_dataset.py:30), ts_norm =
+ *           (ts - ts[0]) / (ts[-1] - ts[0] + 1e-6), WITHOUT its 1e-6: tau = T1 = 1 lands on t_last exactly.
+ * A fourth DEVICE table of S entries, parallel to the other three, refreshed per window like them (so the call works inside a
+ * captured graph).  ts NULL: the slot is not clocked and gets the timed output's float32 column (its emit entry's ts) -- one
+ * launch sequence serves a session of both kinds.  ts non-NULL: the slot's emit entry's float32 ts is not written and may be
+ * NULL.  The same SIX launches: only the scatter kernel reads this table. */
+typedef struct bmc_slot_clock {
+    double t_first;             /* time of the first ... */
+    double t_last;              /* ... and of the last event of the item this window predicts; finite, t_last >= t_first */
+    double* ts;                 /* NULL, or the recording's float64 time column, `capacity` entries, parallel to xs / ys / ps */
+} bmc_slot_clock_t;
+/* Arguments, limits and scratch of the timed call, and `clock` (8-byte aligned). */
+int bmc_slot_emit_clocked(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock, int S,
+                          const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
+                          const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,11 +10,14 @@ recording keeps on the GPU either way.
 --emit-events adds, per configuration, the frame-backed session with the event OUTPUT on (emit_events=True): its latency and
 windows/s, the bmc_slot_emit call alone (both kernels, events around 20 calls on the session's last table and prediction),
 the events of its last window, and the bytes the recording keeps resident with events against with dense predictions.
+--no-gt adds, per configuration, the frame-backed session on recordings WITHOUT ground truth (open(frames)): no metrics launch.
+--sensor-clock (implies --emit-events --event-times) opens the emitting session's recordings with synthetic monotone float64
+stamps (microseconds around 1e9, one frame every 33 333 us): float64 times on the sensor's clock, bmc_slot_emit_clocked.
 --resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
-                                  [--emit-events] [--resident-windows N] [--modes eager,graph] [--out FILE]"""
+                                  [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]"""
 import argparse
 import json
 import os
@@ -77,8 +80,8 @@ def emit_alone(ms, reps=20):
     H, W = ms._size[:2]
     args = (b["table"], b["pred"], ms.max_count, slots.emit_parts(ms.scale * H, ms.scale * W), b["emit_parts"])
     call = slots.emit
-    if ms.event_times is not None:                         # bmc_slot_emit_timed: the six launches of the sorted stream
-        args, call = args + (b["emit_scratch"], ms._wcap), slots.emit_timed
+    if ms.event_times is not None:                         # bmc_slot_emit_timed / _clocked: the six launches of the sorted stream
+        args, call = args + (b["emit_scratch"], ms._wcap), slots.emit_clocked if ms._has_clock else slots.emit_timed
     a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     call(*args)
     a.record()
@@ -89,13 +92,21 @@ def emit_alone(ms, reps=20):
     return a.elapsed_time(z) / reps
 
 
-def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None):
+def sensor_spans(L, k):
+    """Synthetic monotone float64 stamps of recording k: microseconds around 1e9, frame j spans [33 333 j, 33 333 j + 33 332]."""
+    import numpy as np
+    t0 = 1e9 + 1e7 * k + 33333.0 * np.arange(L, dtype=np.float64)
+    return np.stack([t0, t0 + 33332.0], 1)
+
+
+def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False):
     ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
     else:
-        hs = [ms.open(f, g) for f, g in recs[:S]]
+        hs = [ms.open(f, None if no_gt else g, spans=sensor_spans(len(f), k) if clock else None)
+              for k, (f, g) in enumerate(recs[:S])]
     for _ in range(warmup):
         ms.step()
     torch.cuda.synchronize()
@@ -125,10 +136,15 @@ def main():
     ap.add_argument("--emit-events", action="store_true")
     ap.add_argument("--event-times", action="store_true",
                     help="with --emit-events: the timed, time-ordered stream (MultiStreamSR(event_times='linear'))")
+    ap.add_argument("--sensor-clock", action="store_true",
+                    help="implies --emit-events --event-times: float64 times on a synthetic sensor clock (spans= at open)")
+    ap.add_argument("--no-gt", action="store_true", help="adds the session on recordings without ground truth")
     ap.add_argument("--resident-windows", type=int, default=0)
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
+    if a.sensor_clock:
+        a.emit_events = a.event_times = True
     if a.event_times and not a.emit_events:
         ap.error("--event-times needs --emit-events")
     dev = torch.device("cuda:0")
@@ -171,11 +187,17 @@ def main():
                                      windows_per_s=round(wps, 1), encode_ms=round(enc, 4), encode_share=round(enc / lat, 4),
                                      resident_bytes=nbytes))
                     print(json.dumps(rows[-1]), flush=True)
+                if a.no_gt:
+                    lat, wps, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, no_gt=True)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(no gt)", slots=S, ms_per_window=round(lat, 3),
+                                     windows_per_s=round(wps, 1), resident_bytes=nbytes))
+                    print(json.dumps(rows[-1]), flush=True)
                 if a.emit_events:
                     lat, wps, emi, nev, nbytes, dense = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True,
-                                                                    event_times="linear" if a.event_times else None)
-                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(emit, timed)" if a.event_times else
-                                     "MultiStreamSR(emit)", slots=S, ms_per_window=round(lat, 3),
+                                                                    event_times="linear" if a.event_times else None,
+                                                                    clock=a.sensor_clock)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(emit, clocked)" if a.sensor_clock else
+                                     "MultiStreamSR(emit, timed)" if a.event_times else "MultiStreamSR(emit)", slots=S, ms_per_window=round(lat, 3),
                                      windows_per_s=round(wps, 1), emit_ms=round(emi, 4), emit_share=round(emi / lat, 4),
                                      events_last_window=nev, resident_bytes=nbytes, resident_bytes_dense=dense))
                     print(json.dumps(rows[-1]), flush=True)
