@@ -6,7 +6,7 @@ reference including its out-of-range quirk and its in-place reset of the caller'
 are rejected: there is no CPU fallback."""
 import torch
 
-from . import ops
+from . import lib, ops
 
 
 def events_to_channels(xs, ys, ps, sensor_size=(180, 240)):
@@ -65,6 +65,24 @@ def events_to_mask(xs, ys, ps, sensor_size=(180, 240)):
     if not (xs.is_contiguous() and ys.is_contiguous() and ps.is_contiguous()):
         raise RuntimeError("events_to_mask: xs/ys/ps must be contiguous (they are updated in place)")
     return ops.events_to_mask(xs, ys, ps, int(sensor_size[0]), int(sensor_size[1]))
+
+
+def get_hot_event_mask(event_rate, idx, max_px=100, min_obvs=5, max_rate=0.8):
+    """Binary mask [H,W] (1 = keep) that removes the events of hot pixels (reference: dataloader/encodings.py:349-364, same
+    signature) on a contiguous float32 GPU tensor: if idx > min_obvs, the entries > max_rate, at most max_px of them, the
+    largest first and equal ones in flat order; as in the reference the selected entries of event_rate are zeroed in place.
+    bmc_hot_pixel_mask (include/bmc_hip.h) states the special values: any NaN masks nothing, -0.0 orders as +0.0, and a
+    negative max_rate spends what max_px leaves on one more entry."""
+    if not (torch.is_tensor(event_rate) and event_rate.is_cuda):
+        raise RuntimeError("get_hot_event_mask: event_rate must live on the MI355X (no CPU fallback in this build)")
+    if not (event_rate.dim() == 2 and event_rate.dtype == torch.float32 and event_rate.is_contiguous() and event_rate.numel()):
+        raise RuntimeError("get_hot_event_mask: event_rate must be a contiguous float32 [H,W] tensor (it is updated in place)")
+    H, W = event_rate.shape
+    mask = torch.empty_like(event_rate)
+    ws = torch.empty(H * W, dtype=torch.int32, device=event_rate.device)
+    lib.call(lib._hot_pixel_mask, "bmc_hot_pixel_mask", event_rate.data_ptr(), H, W, int(idx > min_obvs),
+             max(0, min(int(max_px), H * W)), float(max_rate), mask.data_ptr(), ws.data_ptr(), ops._stream())
+    return mask
 
 
 def events_to_channels_batch(xs, ys, ps, offsets, sensor_size=(180, 240), mutate=True):

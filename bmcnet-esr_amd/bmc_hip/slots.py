@@ -20,7 +20,12 @@ float32 times, in time order (one call = EMIT_TIMED_KERNELS launches for all slo
 
 Clocked event output: SlotTable(emit=True, timed=True, clock=True) adds a fourth table of bmc_slot_clock_t entries
 (SLOT_CLOCK_DTYPE: the window's time span on the recording's clock and a float64 `ts` column); emit_clocked() is emit_timed()
-whose slots with a clock entry store float64 times on that clock instead (the same launches, the same counter)."""
+whose slots with a clock entry store float64 times on that clock instead (the same launches, the same counter).
+
+Hot-pixel filter (csrc/slot_hot.hip; include/bmc_hip.h "hot-pixel filter" states the contract): SlotTable(events=True, hot=True)
+adds a table of bmc_slot_hot_t entries (SLOT_HOT_DTYPE) behind the others; hot_update() folds the newly observed items of every
+filtered slot into its counts and writes their masks into the slot's ring (one call = HOT_KERNELS launch for all slots, counted in
+HOT_LAUNCHES), encode_filtered() is encode() storing the LR frames through those masks (counted in ENCODE_LAUNCHES)."""
 import numpy as np
 import torch
 
@@ -56,6 +61,12 @@ EVENT_T0, EVENT_T1 = 0.01, 1.0     # BMC_EVENT_T0 / BMC_EVENT_T1: the window's t
 SLOT_CLOCK_DTYPE = np.dtype([("t_first", "<f8"), ("t_last", "<f8"), ("ts", "<u8")])      # bmc_slot_clock_t
 assert SLOT_CLOCK_DTYPE.itemsize == 24
 _RANK_TABLES = {}
+SLOT_HOT_DTYPE = np.dtype([("hot_pixels", "<u8"), ("hot_mask", "<u8"), ("first_item", "<i4"), ("new_from", "<i4"),
+                           ("active", "<i4"), ("pad", "<i4"), ("cmin", "<i4", (MAX_SEQN,))])                # bmc_slot_hot_t
+assert SLOT_HOT_DTYPE.itemsize == 64
+HOT_LAUNCHES = 0
+HOT_KERNELS = 1                    # launches of one bmc_slot_hot_update call
+HOT_MAX_ITEMS = 1 << 23            # below it distinct counts give distinct float32 rates (the contract's rule 3)
 
 
 class SlotTable:
@@ -65,11 +76,12 @@ class SlotTable:
     events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy.
     emit=True: S bmc_slot_emit_t entries follow those (`emit_host()`, `emit_ptr()`), same copy; with timed=True they are
     bmc_slot_emit_timed_t entries.  clock=True (needs timed): S bmc_slot_clock_t entries follow those (`clock_host()`,
-    `clock_ptr()`), same copy."""
+    `clock_ptr()`), same copy.  hot=True (needs events): S bmc_slot_hot_t entries follow those (`hot_host()`, `hot_ptr()`),
+    same copy."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False):
+    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
@@ -85,7 +97,11 @@ class SlotTable:
         self._nslot = S * SLOT_DTYPE.itemsize
         self._nevents = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
         self._nemit = self._nevents + (S * self._emit_dtype.itemsize if emit else 0)
-        nbytes = self._nemit + (S * SLOT_CLOCK_DTYPE.itemsize if self.clock else 0)
+        self.hot = bool(hot)
+        if self.hot and not self.events:
+            raise ValueError("slots: hot=True needs events=True")
+        self._nclock = self._nemit + (S * SLOT_CLOCK_DTYPE.itemsize if self.clock else 0)
+        nbytes = self._nclock + (S * SLOT_HOT_DTYPE.itemsize if self.hot else 0)
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
         self._events = [None] * self.RING
@@ -109,7 +125,11 @@ class SlotTable:
 
     def clock_host(self):
         """The clock entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nemit:].view(SLOT_CLOCK_DTYPE)
+        return self._pinned[self._k].numpy()[self._nemit:self._nclock].view(SLOT_CLOCK_DTYPE)
+
+    def hot_host(self):
+        """The hot-filter entries of the window being filled (after host(), which cleared them: all inactive)."""
+        return self._pinned[self._k].numpy()[self._nclock:].view(SLOT_HOT_DTYPE)
 
     def upload(self):
         k = self._k
@@ -129,6 +149,9 @@ class SlotTable:
 
     def clock_ptr(self):
         return self.dev.data_ptr() + self._nemit
+
+    def hot_ptr(self):
+        return self.dev.data_ptr() + self._nclock
 
 
 def _check(cond, what):
@@ -219,6 +242,94 @@ def encode(table, lr_scratch, gt_scratch):
     _check(max(W, gw) <= MAX_ENCODE_WIDTH, "frames wider than %d pixels are not supported" % MAX_ENCODE_WIDTH)
     lib.call(lib._slot_encode, "bmc_slot_encode", table.events_ptr(), S, seqn, H, W, gh, gw, lr_scratch.data_ptr(),
              gt_scratch.data_ptr(), _stream())
+    ENCODE_LAUNCHES += 1
+
+
+def check_hot_filter(who, hot_filter):
+    """hot_filter (None, or a dict with exactly the keys max_px, min_obvs, max_rate) -> None or (max_px, min_obvs, max_rate);
+    ValueError naming the bad key."""
+    if hot_filter is None:
+        return None
+    keys = ("max_px", "min_obvs", "max_rate")
+    if not isinstance(hot_filter, dict):
+        raise ValueError(who + "hot_filter must be None or a dict with the keys %s (got %r)" % (", ".join(keys), hot_filter))
+    for k in hot_filter:
+        if k not in keys:
+            raise ValueError(who + "hot_filter has an unknown key %r (the keys are %s)" % (k, ", ".join(keys)))
+    for k in keys:
+        if k not in hot_filter:
+            raise ValueError(who + "hot_filter lacks the key %r" % k)
+    for k in keys[:2]:
+        v = hot_filter[k]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v < 2 ** 31:
+            raise ValueError(who + "hot_filter[%r] must be an integer, 0 <= %s < 2^31 (got %r)" % (k, k, v))
+    r = hot_filter["max_rate"]
+    if isinstance(r, bool) or not isinstance(r, (int, float, np.integer, np.floating)) or not np.isfinite(np.float32(r)):
+        raise ValueError(who + "hot_filter['max_rate'] must be a finite number (got %r)" % (r,))
+    return int(hot_filter["max_px"]), int(hot_filter["min_obvs"]), float(r)
+
+
+def hot_cmin(idx, min_obvs, max_rate):
+    """Rule 3 of the hot-pixel contract for an item with idx observations, as the integer the kernel compares counts with:
+    0 (the item masks nothing) for idx <= min_obvs; 1 for max_rate < 0 (the pixels with a count; bmc_slot_hot_update's
+    negative_rate adds the rule's one further pixel); else the smallest c in [0, idx] with float32(c) / float32(idx) >
+    float32(max_rate), idx + 1 if there is none.  The comparison is made in float32, as torch makes it."""
+    idx = int(idx)
+    _check(1 <= idx < HOT_MAX_ITEMS, "1 <= idx < 2^23 (got %d)" % idx)
+    if idx <= min_obvs:
+        return 0
+    rate = np.float32(max_rate)
+    if rate < 0:
+        return 1
+    above = lambda c: bool(np.float32(c) / np.float32(idx) > rate)
+    c = min(max(int(np.floor(float(rate) * idx)) - 2, 0), idx)        # the rounded quotient is monotone in c: search near rate * idx
+    while c > 0 and above(c):
+        c -= 1
+    while c <= idx and not above(c):
+        c += 1
+    return c
+
+
+def hot_update(table, counts, ring, ws, max_px, max_rate):
+    """Every slot with an active hot entry (SlotTable.hot_host), for each of its window's newly observed frames in order: the
+    last-writer observation of the frame's LR events, counts[s] [H,W] int32 += it (= it at a reset), the selection of the
+    contract's rule 3 with the entry's cmin (hot_cmin) and max_px, the item's mask (uint8, 1 = keep) into ring[s, item % seqn];
+    the last item's mask count / mask go to the entry's hot_pixels / hot_mask addresses.  ws: int32 [S,H,W] of workspace.
+    One launch for all slots (bmc_slot_hot_update); inactive slots are not touched."""
+    global HOT_LAUNCHES
+    _check(table.events and getattr(table, "hot", False), "the slot table has no hot entries (SlotTable(events=True, hot=True))")
+    _check(torch.is_tensor(ring) and ring.dim() == 4 and ring.is_cuda and ring.is_contiguous() and ring.dtype == torch.uint8
+           and ring.shape[0] == table.S, "ring must be a contiguous uint8 GPU tensor [S,seqn,H,W]")
+    S, seqn, H, W = ring.shape
+    for name, t in (("counts", counts), ("ws", ws)):
+        _check(torch.is_tensor(t) and t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == (S, H, W),
+               "%s must be a contiguous int32 GPU tensor [S,H,W]" % name)
+    _check(2 <= seqn <= MAX_SEQN, "2 <= seqn <= %d" % MAX_SEQN)
+    _check(not isinstance(max_px, bool) and isinstance(max_px, (int, np.integer)) and 0 <= max_px < 2 ** 31,
+           "max_px must be an integer, 0 <= max_px < 2^31 (got %r)" % (max_px,))
+    lib.call(lib._slot_hot_update, "bmc_slot_hot_update", table.hot_ptr(), table.events_ptr(), S, seqn, H, W, int(max_px),
+             int(np.float32(max_rate) < 0), counts.data_ptr(), ring.data_ptr(), ws.data_ptr(), _stream())
+    HOT_LAUNCHES += 1
+
+
+def encode_filtered(table, lr_scratch, gt_scratch, ring):
+    """encode() of a filtered session (bmc_slot_encode_filtered: one launch): the LR frames of a slot with an active hot entry
+    are stored through their items' masks in ring [S,seqn,H,W] (the contract's rule 4); everything else as encode()."""
+    global ENCODE_LAUNCHES
+    _check(table.events and getattr(table, "hot", False), "the slot table has no hot entries (SlotTable(events=True, hot=True))")
+    for t in (lr_scratch, gt_scratch):
+        _check(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == table.S,
+               "scratch must be contiguous fp32 GPU tensors [S,...]")
+    _check(lr_scratch.dim() == 5 and lr_scratch.shape[2] == 2 and gt_scratch.dim() == 4 and gt_scratch.shape[1] == 2,
+           "lr_scratch [S,seqn,2,H,W] and gt_scratch [S,2,gh,gw]")
+    S, seqn, _, H, W = lr_scratch.shape
+    gh, gw = gt_scratch.shape[2:]
+    _check(2 <= seqn <= MAX_SEQN, "2 <= seqn <= %d" % MAX_SEQN)
+    _check(max(W, gw) <= MAX_ENCODE_WIDTH, "frames wider than %d pixels are not supported" % MAX_ENCODE_WIDTH)
+    _check(torch.is_tensor(ring) and ring.is_cuda and ring.is_contiguous() and ring.dtype == torch.uint8
+           and tuple(ring.shape) == (S, seqn, H, W), "ring must be a contiguous uint8 GPU tensor [S,seqn,H,W]")
+    lib.call(lib._slot_encode_filtered, "bmc_slot_encode_filtered", table.events_ptr(), table.hot_ptr(), ring.data_ptr(), S, seqn,
+             H, W, gh, gw, lr_scratch.data_ptr(), gt_scratch.data_ptr(), _stream())
     ENCODE_LAUNCHES += 1
 
 

@@ -12,80 +12,16 @@
 // depend on the order of the atomics and is the same bits run after run.
 // Pointers read from the table go through address-space(1) casts (global_* instructions, never flat_*), as in slots.hip.
 #include "bmc_common.h"
+#include "slot_encode_k.h"
 
 namespace {
-
-template <class T>
-__device__ __forceinline__ T gld(const void* p) {
-    return *(const __attribute__((address_space(1))) T*)(unsigned long long)p;
-}
-template <class T>
-__device__ __forceinline__ void gst(void* p, T v) {
-    *(__attribute__((address_space(1))) T*)(unsigned long long)p = v;
-}
-
-constexpr int ET = 1024;            // threads per workgroup
-constexpr int ENC_LDS = 15360;      // counters per workgroup: 2 channels x R rows x W (60 KB: two workgroups per CU)
 
 // grid (seqn * nb_lr + nb_gt, S): blockIdx.y is the slot, blockIdx.x a (frame, band) of that slot's window
 __global__ __launch_bounds__(ET) void slot_encode_kernel(const bmc_slot_events_t* __restrict__ table, int seqn, int H, int W,
                                                          int gh, int gw, int r_lr, int nb_lr, int r_gt,
                                                          float* __restrict__ lr_scratch, float* __restrict__ gt_scratch) {
     __shared__ unsigned cnt[ENC_LDS];
-    const int s = blockIdx.y, tid = threadIdx.x;
-    const bmc_slot_events_t* const ent = table + s;
-    if (gld<const short*>(&ent->lr_xs) == nullptr) return;           // no event entry: the slot's scratch is not touched
-    const short *xs, *ys;
-    const double* ps;
-    long long e0, e1;
-    int fh, fw, r0, rows;
-    float* out;
-    const int b = blockIdx.x;
-    if (b < seqn * nb_lr) {
-        const int t = b / nb_lr;
-        xs = gld<const short*>(&ent->lr_xs);
-        ys = gld<const short*>(&ent->lr_ys);
-        ps = gld<const double*>(&ent->lr_ps);
-        e0 = gld<long long>(&ent->lr_range[t][0]);
-        e1 = gld<long long>(&ent->lr_range[t][1]);
-        fh = H; fw = W; r0 = (b - t * nb_lr) * r_lr; rows = r_lr;
-        out = lr_scratch + ((long long)s * seqn + t) * 2 * H * W;
-    } else {
-        xs = gld<const short*>(&ent->gt_xs);
-        ys = gld<const short*>(&ent->gt_ys);
-        ps = gld<const double*>(&ent->gt_ps);
-        e0 = gld<long long>(&ent->gt_range[0]);
-        e1 = gld<long long>(&ent->gt_range[1]);
-        fh = gh; fw = gw; r0 = (b - seqn * nb_lr) * r_gt; rows = r_gt;
-        out = gt_scratch + (long long)s * 2 * gh * gw;
-    }
-    if (r0 + rows > fh) rows = fh - r0;
-    const int n = rows * fw;                                         // counters per channel: 2 * n <= ENC_LDS
-    for (int i = tid; i < 2 * n; i += ET) cnt[i] = 0u;
-    __syncthreads();
-    const bool last = r0 + rows == fh;                               // row fh-1 is where out-of-range negatives land
-    for (long long e = e0 + tid; e < e1; e += ET) {
-        // event_formatting's float32 cast of the int16 column is exact, so the range tests run on the integers
-        const int y = (int)gld<short>(ys + e);
-        const bool yin = y >= 0 && y < fh;
-        const int row = fh - 1 - (yin ? y : 0);
-        if (!(last || (yin && row >= r0 && row < r0 + rows))) continue;
-        const int x = (int)gld<short>(xs + e);
-        const float p = (float)gld<double>(ps + e);
-        const bool oob = !yin || x < 0 || x >= fw;
-        const bool neg = p < 0.f;
-        if (!(neg || (!oob && p > 0.f))) continue;                   // an out-of-range positive (or p = 0) counts nowhere
-        const int rr = (oob ? fh - 1 : row) - r0;                    // reset coordinates (0, 0) -> [fh-1][0] of channel 1
-        if (rr < 0 || rr >= rows) continue;
-        atomicAdd(&cnt[(neg ? n : 0) + rr * fw + (oob ? 0 : x)], (unsigned)(p * p));
-    }
-    __syncthreads();
-    float* const o0 = out + (long long)r0 * fw;
-    float* const o1 = o0 + (long long)fh * fw;
-    for (int i = tid; i < n; i += ET) {
-        gst<float>(o0 + i, (float)cnt[i]);
-        gst<float>(o1 + i, (float)cnt[n + i]);
-    }
+    slot_encode_body<false>(cnt, table, seqn, H, W, gh, gw, r_lr, nb_lr, r_gt, lr_scratch, gt_scratch, nullptr, nullptr);
 }
 
 }  // namespace
@@ -97,10 +33,9 @@ extern "C" int bmc_slot_encode(const bmc_slot_events_t* table, int S, int seqn, 
                   "bmc_slot_encode: bad arguments");
     BMC_CHECK_ARG(2 * W <= ENC_LDS && 2 * gw <= ENC_LDS, "bmc_slot_encode: frames wider than %d pixels are not supported",
                   ENC_LDS / 2);
-    const int r_lr = ENC_LDS / (2 * W) < H ? ENC_LDS / (2 * W) : H, r_gt = ENC_LDS / (2 * gw) < gh ? ENC_LDS / (2 * gw) : gh;
-    const int nb_lr = (H + r_lr - 1) / r_lr, nb_gt = (gh + r_gt - 1) / r_gt;
-    hipLaunchKernelGGL(slot_encode_kernel, dim3(seqn * nb_lr + nb_gt, S), dim3(ET), 0, (hipStream_t)s, table, seqn, H, W, gh, gw,
-                       r_lr, nb_lr, r_gt, lr_scratch, gt_scratch);
+    const SlotEncodeGrid g = slot_encode_grid(H, W, gh, gw);
+    hipLaunchKernelGGL(slot_encode_kernel, dim3(seqn * g.nb_lr + g.nb_gt, S), dim3(ET), 0, (hipStream_t)s, table, seqn, H, W, gh, gw,
+                       g.r_lr, g.nb_lr, g.r_gt, lr_scratch, gt_scratch);
     BMC_CHECK_LAUNCH("bmc_slot_encode");
     return 0;
 }

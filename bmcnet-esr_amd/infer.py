@@ -272,14 +272,26 @@ class MultiStreamSR:
     fraction of j / (n - 1) (bmc_slot_emit_clocked; include/bmc_hip.h states the contract) -- the inverse of
     event_formatting's normalisation (dataloader/base_dataset.py:30) without its 1e-6.  Each window is in time order; with
     sliding_window < window the spans of consecutive windows overlap, so the concatenation of a recording's windows is
-    globally sorted only for non-overlapping spans.  Clocked and unclocked recordings may share a session."""
+    globally sorted only for non-overlapping spans.  Clocked and unclocked recordings may share a session.
+
+    hot_filter=dict(max_px=, min_obvs=, max_rate=): the reference's hot-pixel filter (dataset.hot_filter; create_hot_mask,
+    dataloader/h5dataset.py:528-548; get_hot_event_mask, dataloader/encodings.py:349-364) on the GPU, for recordings opened with
+    open_events: every LR item is observed once, in item order (a per-slot count of the items in which a pixel fired), its mask
+    follows the reference's rule bit for bit, and the item's count image has both channels zeroed where the mask says so --
+    include/bmc_hip.h states the contract.  bmc_slot_hot_update (one more launch per window for all slots, inside the captured
+    graph too) runs before the encode launch, which becomes bmc_slot_encode_filtered.  Recordings opened with open() in the same
+    session stay UNFILTERED, and so does every ground truth.  results() then carries hot_pixels (per window, the number of
+    pixels masked for the item that window newly observed) and hot_mask ([H,W] uint8 in sensor coordinates, 1 = kept, of the
+    last item observed).  The option needs nothing else switched on."""
 
     MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
     MAX_COUNT_TIMED = 255        # event_times: the sort key is a 16-bit rank of j / (n - 1), n <= 255
     MAX_WINDOW_CAPACITY = 1 << 28
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
-                 seqn=3, emit_events=False, max_count=255, event_times=None):
+                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None):
+        from bmc_hip.slots import check_hot_filter
+        self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
         if seqn < 2:
@@ -436,6 +448,7 @@ class MultiStreamSR:
         self._recs[h] = rec
         return h
 
+    MAX_ITEMS_FILTERED = 1 << 23 # hot_filter: below it distinct counts give distinct float32 rates (include/bmc_hip.h)
     MAX_SEQN_EVENTS = 8          # bmc_slot_events_t holds the ranges of at most 8 LR frames (BMC_SLOT_MAX_SEQN)
     MAX_WIDTH_EVENTS = 7680      # bmc_slot_encode: one row of both channels must fit a workgroup's LDS band
 
@@ -491,6 +504,11 @@ class MultiStreamSR:
             raise ValueError(who + "%d items, fewer than one window of seqn = %d" % (L, self.seqn))
         if self.seqn > self.MAX_SEQN_EVENTS:
             raise ValueError(who + "seqn <= %d for event-backed recordings" % self.MAX_SEQN_EVENTS)
+        if self.hot_filter is not None:
+            if L >= self.MAX_ITEMS_FILTERED:
+                raise ValueError(who + "a filtered session takes recordings of fewer than 2^23 items (got %d)" % L)
+            if int((lr_index[:, 1] - lr_index[:, 0]).max()) >= 2 ** 31:
+                raise ValueError(who + "a filtered session takes LR items of fewer than 2^31 events")
         if lr_ts is not None:
             if not ((torch.is_tensor(lr_ts) and lr_ts.dtype == torch.float64 and lr_ts.dim() == 1) or
                     (isinstance(lr_ts, np.ndarray) and lr_ts.dtype == np.float64 and lr_ts.ndim == 1)) \
@@ -523,6 +541,12 @@ class MultiStreamSR:
         rec = {"lr": tuple(lr), "lr_index": lr_index}
         if has_gt:
             rec.update(gt=tuple(gt), gt_index=gt_index)
+        if self.hot_filter is not None:                    # written by bmc_slot_hot_update: the slot is reused after the recording
+            from bmc_hip import slots
+            _, min_obvs, max_rate = self.hot_filter
+            rec.update(hot_pixels=torch.zeros(L - self.seqn + 1, dtype=torch.int32, device=cols[0].device),
+                       hot_mask=torch.ones(H, W, dtype=torch.uint8, device=cols[0].device),
+                       hot_cmin=[slots.hot_cmin(j + 1, min_obvs, max_rate) for j in range(L)])
         h = self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
         if not self._has_events:
             self._has_events = True
@@ -539,11 +563,14 @@ class MultiStreamSR:
         if "ev_xs" in r:
             data = tuple(data) + (r["ev_xs"], r["ev_ys"], r["ev_ps"], r["ev_index"]) + ((r["ev_ts"],) if "ev_ts" in r else ())
         data = tuple(data) + ((r["sse"],) if "sse" in r else ()) + (() if r["keep"] is None else (r["keep"],))
+        if "hot_pixels" in r:                              # (hot_filter) the per-window mask counts and the last mask
+            data = data + (r["hot_pixels"], r["hot_mask"])
         return sum(t.numel() * t.element_size() for t in data)
 
     def scratch_bytes(self):
-        """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened) and,
-        with event_times, of the sort scratch (0 until a recording has been opened)."""
+        """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened; with
+        hot_filter also the slots' counts, mask rings and workspace: 8 + seqn bytes per pixel) and, with event_times, of the
+        sort scratch (0 until a recording has been opened)."""
         nbytes = 0
         if self._wcap:
             from bmc_hip import slots
@@ -553,6 +580,8 @@ class MultiStreamSR:
             return nbytes
         H, W = self._size[:2]
         gh, gw = self._gt_scratch_size()
+        if self.hot_filter is not None:
+            nbytes += self.S * H * W * (4 + 4 + self.seqn)
         return nbytes + 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
 
     def _gt_scratch_size(self):
@@ -562,6 +591,7 @@ class MultiStreamSR:
 
     def results(self, handle):
         """-> dict(esr_mse=[...], bicubic_mse=[...] (a recording with ground truth only), time=[...] per window done so far[,
+        hot_pixels=[...] per window, hot_mask=[H,W] uint8 on the GPU (hot_filter, event-backed recordings)][,
         predictions=[n,2,sH,sW]][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
         sr_ts on the GPU, parallel to sr_events (event_times): float32 inside each window, or float64 on the sensor's clock for
         a recording opened with spans / lr_ts]).  Raises RuntimeError when the windows emitted more events than the recording's
@@ -579,6 +609,8 @@ class MultiStreamSR:
         out["time"] = [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]
         if self.keep_predictions:
             out["predictions"] = r["keep"][:done]
+        if "hot_pixels" in r:
+            out.update(hot_pixels=r["hot_pixels"][:done].tolist(), hot_mask=r["hot_mask"])
         if self.emit_events:
             index = r["ev_index"][:done + 1].cpu()
             total = int(index[done])
@@ -625,7 +657,8 @@ class MultiStreamSR:
         """The slot table with the parts the session needs so far."""
         from bmc_hip import slots
         return slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
-                               timed=self.event_times is not None, clock=self._has_clock)
+                               timed=self.event_times is not None, clock=self._has_clock,
+                               hot=self._has_events and self.hot_filter is not None)
 
     def _sort_buffers(self, b, device):
         from bmc_hip import slots
@@ -641,6 +674,10 @@ class MultiStreamSR:
             b["table"] = self._table(device)
         b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
         b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
+        if self.hot_filter is not None:                    # per slot: the running counts, a ring of seqn masks, the workspace
+            b["hot_counts"] = torch.zeros(self.S, H, W, dtype=torch.int32, device=device)
+            b["hot_ring"] = torch.ones(self.S, self.seqn, H, W, dtype=torch.uint8, device=device)
+            b["hot_ws"] = torch.zeros(self.S, H, W, dtype=torch.int32, device=device)
 
     def _forward(self):
         b = self._bufs
@@ -648,11 +685,14 @@ class MultiStreamSR:
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """[encode ->] stage -> model -> commit [-> metrics] [-> emit] (what a graph replay runs)."""
+        """[[hot_update ->] encode ->] stage -> model -> commit [-> metrics] [-> emit] (what a graph replay runs)."""
         from bmc_hip import slots
         b = self._bufs
         H, W = self._size[:2]
-        if "lr_scratch" in b:
+        if "hot_ring" in b:
+            slots.hot_update(b["table"], b["hot_counts"], b["hot_ring"], b["hot_ws"], self.hot_filter[0], self.hot_filter[2])
+            slots.encode_filtered(b["table"], b["lr_scratch"], b["gt_scratch"], b["hot_ring"])
+        elif "lr_scratch" in b:
             slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
         slots.stage(b["table"], b["x"], b["pool"], b["feat"], b["pred"])
         out = self._forward()
@@ -703,6 +743,7 @@ class MultiStreamSR:
         ev = b["table"].events_host() if b["table"].events else None
         em = b["table"].emit_host() if self.emit_events else None
         ck = b["table"].clock_host() if b["table"].clock else None
+        ht = b["table"].hot_host() if b["table"].hot else None
         for s, p in enumerate(plan):
             if p is None:
                 continue
@@ -716,6 +757,11 @@ class MultiStreamSR:
                 if "gt" in r:                              # (without: NULL columns, range (0, 0): the scratch is only zero-filled)
                     e[s]["gt"] = b["gt_scratch"][s].data_ptr()
                     ev["gt_range"][s] = r["gt_index"][i + 1]
+                if ht is not None:                         # the first window observes items 0 .. seqn-1, a later one item i+seqn-1
+                    ht[s]["active"], ht[s]["first_item"], ht[s]["new_from"] = 1, i, 0 if reset else self.seqn - 1
+                    ht[s]["cmin"][:self.seqn] = r["hot_cmin"][i:i + self.seqn]
+                    ht[s]["hot_pixels"] = r["hot_pixels"].data_ptr() + 4 * i
+                    ht[s]["hot_mask"] = r["hot_mask"].data_ptr()
             else:
                 e[s]["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
                 if "gts" in r:
@@ -760,7 +806,7 @@ class MultiStreamSR:
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
-                        window_event_capacity=None):
+                        window_event_capacity=None, hot_filter=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
@@ -774,10 +820,12 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                                          recording (MultiStreamSR(emit_events=True); event_capacity: per recording, None =
                                          the default)][,
       sr_ts       = {name: ts float32}           with event_times="linear": the events' times inside their windows, every
-                                         window in time order (window_event_capacity: per recording, None = the default)])."""
+                                         window in time order (window_event_capacity: per recording, None = the default)]).
+    hot_filter: MultiStreamSR's option (the EventRecording items are filtered, frame pairs are not)."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
-                       keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times)
+                       keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
+                       hot_filter=hot_filter)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):

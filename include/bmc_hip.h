@@ -615,6 +615,71 @@ int bmc_slot_emit_clocked(const bmc_slot_t* table, const bmc_slot_emit_timed_t* 
                           const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
                           const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s);
 
+/* ---- hot-pixel filter of event-backed slots (MultiStreamSR(hot_filter=dict(max_px, min_obvs, max_rate))) -----------------
+ * The reference carries the filter as dataset.hot_filter.{enabled,max_px,min_obvs,max_rate} (infer_BMCNet.py:178), the state
+ * hot_events / hot_idx (dataloader/h5dataset.py:155-156), create_hot_mask (:528-548) and get_hot_event_mask
+ * (dataloader/encodings.py:349-364); it computes the mask but never applies it (__getitem__ does not call create_hot_mask), so
+ * rules 1-3 restate the reference and rules 4-5 are this project's statement of how the mask meets the count image.
+ * THE CONTRACT.  One recording, LR items 0 .. L-1 (lr_index), sensor (H, W), parameters max_px >= 0, min_obvs >= 0 (integers)
+ * and a finite max_rate:
+ *   1. Observation.  obs_j[y][x] = events_to_mask of item j's LR events (bmc_events_to_mask, oracle.events_to_mask_np): row =
+ *      the event's y (no vertical flip), value = |p| of the LAST event in column order that maps to the pixel; an out-of-range
+ *      event maps to (0, 0) with weight 0 (it can clear [0][0]).  Polarities are -1 / 0 / +1, so obs_j is 0 or 1.
+ *   2. Running count.  count_j = obs_0 + ... + obs_j (integers), idx_j = j + 1: every item is seen once, in item order, however
+ *      many windows it appears in.
+ *   3. Mask.  mask_j = get_hot_event_mask(float32(count_j) / float32(idx_j), idx_j, max_px, min_obvs, max_rate), 1 = keep.
+ *      On the integers: cmin = the smallest c in [0, idx] with float32(c) / float32(idx) > float32(max_rate) (idx + 1 if there
+ *      is none; the host evaluates this in float32 and hands the kernel an integer).  If idx > min_obvs, the pixels with count
+ *      >= cmin are masked, at most max_px of them, the largest counts first and equal counts in flat row-major order (argmax
+ *      returns the first maximum).  For idx < 2^23 distinct counts give distinct float32 rates, so the order by count is the
+ *      order by rate; a filtered session refuses L >= 2^23.
+ *      max_rate < 0: the reference's loop zeroes the rate it masks, and 0 > max_rate, so it finds that entry again.  Its result:
+ *      the pixels with count >= 1 are masked by the rule above and, if fewer than max_px of them exist, ONE more pixel -- the
+ *      first maximum of the zeroed image, which is pixel (0, 0).  (Not "every pixel": the loop never leaves that entry.)
+ *   4. Filtered frame j = the count image of item j as bmc_slot_encode builds it, with BOTH channels set to exactly 0 at
+ *      [H-1-y][x] for every (y, x) with mask_j[y][x] == 0 (so the out-of-range negatives on [H-1][0] of channel 1 go when
+ *      sensor pixel (0, 0) is masked).
+ *   5. Window i reads filtered frames i .. i+seqn-1, each with its OWN mask_j: a ring of seqn masks per slot, item j at ring
+ *      position j % seqn.  The first window of a recording observes items 0 .. seqn-1 in order, every later window item
+ *      i+seqn-1.  The ground-truth frame is not filtered; the bicubic baseline of bmc_slot_metrics reads the filtered middle
+ *      frame (the scratch it already reads).
+ * Consequence: a filtered event-backed recording is bit-identical to open() on the frames rules 1-4 give.
+ *
+ * A fifth DEVICE table of S entries, parallel to the slot and event tables.  An all-zero entry is the inactive form: a slot that
+ * is empty, frame-backed or not filtered -- neither call below touches anything of it. */
+typedef struct bmc_slot_hot {
+    int* hot_pixels;            /* NULL, or where the number of pixels masked for the window's LAST item is written */
+    unsigned char* hot_mask;    /* NULL, or [H][W] (sensor coordinates, 1 = kept): the mask of the window's last item */
+    int first_item;             /* item index i of the window's frame 0: frame t is item i + t, ring position (i + t) % seqn */
+    int new_from;               /* the first newly observed frame: 0 at a reset (the counts restart from zero), else seqn - 1 */
+    int active;                 /* 0: the slot is not filtered */
+    int pad_;
+    int cmin[BMC_SLOT_MAX_SEQN];/* per frame t >= new_from: rule 3's cmin for its item (1 with negative_rate); <= 0: idx <= min_obvs,
+                                   the item masks nothing */
+} bmc_slot_hot_t;
+/* ONE launch for all slots, before the encode launch (csrc/slot_hot.hip): for each newly observed frame of each active slot, in
+ * order: the last-writer observation (integer atomicMax over event indices in ws), counts += obs, the selection of rule 3, the
+ * item's mask into ring[s][(first_item + t) % seqn].  `events` is the window's event table (columns and lr_range).
+ * counts [S][H][W] int32, ring [S][seqn][H][W] uint8 (1 = keep), ws [S][H][W] int32 of workspace.  negative_rate: max_rate < 0.
+ * One workgroup per slot, no workgroup waits for another, integers only, global accesses only; the grid is fixed by S and the
+ * live values are read from device memory: the same bytes run after run, capturable in a graph.  Every LR item range must be
+ * shorter than 2^31 events. */
+int bmc_slot_hot_update(const bmc_slot_hot_t* hot, const bmc_slot_events_t* events, int S, int seqn, int H, int W, int max_px,
+                        int negative_rate, int* counts, unsigned char* ring, int* ws, bmc_stream_t s);
+/* bmc_slot_encode for a filtered session: an LR band of a slot with an active hot entry is multiplied by its item's mask when it
+ * is stored (rule 4: both channels, flipped row); ground-truth bands and slots without an active entry are stored as
+ * bmc_slot_encode stores them.  ONE launch, the same grid. */
+int bmc_slot_encode_filtered(const bmc_slot_events_t* table, const bmc_slot_hot_t* hot, const unsigned char* ring, int S, int seqn,
+                             int H, int W, int gh, int gw, float* lr_scratch, float* gt_scratch, bmc_stream_t s);
+/* get_hot_event_mask (dataloader/encodings.py:349-364) on a float32 [H][W] image: the same selection code on a monotone
+ * unsigned image of the values (-0.0 orders as +0.0).  mask [H][W] float32 <- 1 / 0; the selected entries of event_rate are
+ * zeroed IN PLACE as the reference does.  active = (idx > min_obvs).  Any NaN: nothing is masked (argmax finds the NaN, which is
+ * not > max_rate, and the loop stops).  max_rate < 0: after the positive entries, what is left of max_px goes to ONE entry, the
+ * first in flat order that is >= 0 (it becomes +0.0), or, when every entry is negative, the first maximum if it is > max_rate.
+ * ws: H*W words.  One workgroup. */
+int bmc_hot_pixel_mask(float* event_rate, int H, int W, int active, int max_px, float max_rate, float* mask, unsigned* ws,
+                       bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

@@ -13,10 +13,15 @@ the events of its last window, and the bytes the recording keeps resident with e
 --no-gt adds, per configuration, the frame-backed session on recordings WITHOUT ground truth (open(frames)): no metrics launch.
 --sensor-clock (implies --emit-events --event-times) opens the emitting session's recordings with synthetic monotone float64
 stamps (microseconds around 1e9, one frame every 33 333 us): float64 times on the sensor's clock, bmc_slot_emit_clocked.
+--hot-filter (implies --events) adds, per configuration, the event-backed session with the hot-pixel filter on
+(hot_filter=dict(max_px=100, min_obvs=5, max_rate=0.8), the reference's defaults) and off, --runs alternating runs each in this
+process (windows/s: the median, and every run), and the bmc_slot_hot_update call alone (events around 20 calls on the session's
+last table).
 --resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
+                                  [--hot-filter] [--runs 3]
                                   [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]"""
 import argparse
 import json
@@ -72,6 +77,25 @@ def encode_alone(ms, reps=20):
     return a.elapsed_time(z) / reps
 
 
+def hot_update_alone(ms, reps=20):
+    """ms per bmc_slot_hot_update call on the session's buffers (the table of its last window: every slot observes one more
+    item; the repeated calls keep counting it, which costs what a new item costs)."""
+    from bmc_hip import slots
+    b = ms._bufs
+    args = (b["table"], b["hot_counts"], b["hot_ring"], b["hot_ws"], ms.hot_filter[0], ms.hot_filter[2])
+    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    slots.hot_update(*args)
+    a.record()
+    for _ in range(reps):
+        slots.hot_update(*args)
+    z.record()
+    z.synchronize()
+    return a.elapsed_time(z) / reps
+
+
+HOT_FILTER = dict(max_px=100, min_obvs=5, max_rate=0.8)
+
+
 def emit_alone(ms, reps=20):
     """ms per bmc_slot_emit call (count + write kernel) on the session's buffers: the table and prediction of its last window.
     The repeated calls append nothing new: the entries' index words are the last window's."""
@@ -99,8 +123,10 @@ def sensor_spans(L, k):
     return np.stack([t0, t0 + 33332.0], 1)
 
 
-def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False):
-    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times)
+def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False,
+                hot_filter=None):
+    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times,
+                       hot_filter=hot_filter)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
@@ -121,6 +147,8 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
         dense = MultiStreamSR(m, S, n_c=128, scale=4, seqn=SEQN, keep_predictions=True)
         return (lat, S * windows / wall, emit_alone(ms), int(index[-1] - index[-2]), ms.resident_bytes(hs[0]),
                 dense.resident_bytes(dense.open(*recs[0])))
+    if hot_filter is not None:
+        return lat, S * windows / wall, hot_update_alone(ms), ms.resident_bytes(hs[0])
     if events:
         return lat, S * windows / wall, encode_alone(ms), ms.resident_bytes(hs[0])
     return lat, S * windows / wall, ms.resident_bytes(hs[0])
@@ -133,6 +161,9 @@ def main():
     ap.add_argument("--windows", type=int, default=8)
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--events", action="store_true")
+    ap.add_argument("--hot-filter", action="store_true",
+                    help="implies --events: the event-backed session with the hot-pixel filter on and off, alternating runs")
+    ap.add_argument("--runs", type=int, default=3, help="with --hot-filter: alternating runs of each")
     ap.add_argument("--emit-events", action="store_true")
     ap.add_argument("--event-times", action="store_true",
                     help="with --emit-events: the timed, time-ordered stream (MultiStreamSR(event_times='linear'))")
@@ -145,6 +176,8 @@ def main():
     a = ap.parse_args()
     if a.sensor_clock:
         a.emit_events = a.event_times = True
+    if a.hot_filter:
+        a.events = True
     if a.event_times and not a.emit_events:
         ap.error("--event-times needs --emit-events")
     dev = torch.device("cuda:0")
@@ -186,6 +219,21 @@ def main():
                     rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(events)", slots=S, ms_per_window=round(lat, 3),
                                      windows_per_s=round(wps, 1), encode_ms=round(enc, 4), encode_share=round(enc / lat, 4),
                                      resident_bytes=nbytes))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.hot_filter:
+                    off, on = [], []
+                    for _ in range(a.runs):
+                        off.append(multistream(m, erecs, S, graph, a.warmup, a.windows, events=True))
+                        on.append(multistream(m, erecs, S, graph, a.warmup, a.windows, events=True, hot_filter=HOT_FILTER))
+                    lat, upd = statistics.median(r[0] for r in on), statistics.median(r[2] for r in on)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(events, hot filter)", slots=S, events=True,
+                                     hot_filter=HOT_FILTER, ms_per_window=round(lat, 3),
+                                     windows_per_s=round(statistics.median(r[1] for r in on), 1),
+                                     windows_per_s_filter_off=round(statistics.median(r[1] for r in off), 1),
+                                     windows_per_s_runs=[round(r[1], 1) for r in on],
+                                     windows_per_s_filter_off_runs=[round(r[1], 1) for r in off],
+                                     hot_update_alone_ms=round(upd, 4), hot_update_share=round(upd / lat, 4),
+                                     resident_bytes=on[-1][3]))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.no_gt:
                     lat, wps, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, no_gt=True)
