@@ -69,15 +69,34 @@ HOT_KERNELS = 1                    # launches of one bmc_slot_hot_update call
 HOT_MAX_ITEMS = 1 << 23            # below it distinct counts give distinct float32 rates (the contract's rule 3)
 
 
+def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False):
+    """The sections of a slot table of S slots -> ([(name, dtype, byte offset), ...] in their order in memory, total bytes):
+    "slot" (bmc_slot_t) always, then "events", "emit" (bmc_slot_emit_timed_t entries with timed=True), "clock" (needs timed) and
+    "hot" (needs events), each S entries behind the one before."""
+    if timed and not emit:
+        raise ValueError("slots: timed=True needs emit=True")
+    if clock and not timed:
+        raise ValueError("slots: clock=True needs timed=True")
+    if hot and not events:
+        raise ValueError("slots: hot=True needs events=True")
+    sections, nbytes = [], 0
+    for name, dtype, on in (("slot", SLOT_DTYPE, True), ("events", SLOT_EVENTS_DTYPE, events),
+                            ("emit", SLOT_EMIT_TIMED_DTYPE if timed else SLOT_EMIT_DTYPE, emit),
+                            ("clock", SLOT_CLOCK_DTYPE, clock), ("hot", SLOT_HOT_DTYPE, hot)):
+        if on:
+            sections.append((name, dtype, nbytes))
+            nbytes += S * dtype.itemsize
+    return sections, nbytes
+
+
 class SlotTable:
     """A device slot table and a small ring of pinned host copies: `host()` returns the numpy entries to fill for the next
     window (cleared), `upload()` copies them to the device on the current stream.  A ring buffer is rewritten only after the
     copy that last read it has completed, so the host never waits for the GPU to finish the window before.
-    events=True: S bmc_slot_events_t entries follow the slot entries (`events_host()`, `events_ptr()`), same copy.
-    emit=True: S bmc_slot_emit_t entries follow those (`emit_host()`, `emit_ptr()`), same copy; with timed=True they are
-    bmc_slot_emit_timed_t entries.  clock=True (needs timed): S bmc_slot_clock_t entries follow those (`clock_host()`,
-    `clock_ptr()`), same copy.  hot=True (needs events): S bmc_slot_hot_t entries follow those (`hot_host()`, `hot_ptr()`),
-    same copy."""
+    The other sections of table_layout() share the tensor and the copy: `events_host()` / `events_ptr()` (events=True),
+    `emit_host()` / `emit_ptr()` (emit=True; timed=True: bmc_slot_emit_timed_t entries), `clock_host()` / `clock_ptr()`
+    (clock=True, needs timed), `hot_host()` / `hot_ptr()` (hot=True, needs events).  The *_host() views are those of the window
+    being filled, after host(), which cleared them."""
 
     RING = 4
 
@@ -85,51 +104,39 @@ class SlotTable:
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
-        self.events = bool(events)
-        self.emit = bool(emit)
-        self.timed = bool(timed)
-        if self.timed and not self.emit:
-            raise ValueError("slots: timed=True needs emit=True")
-        self.clock = bool(clock)
-        if self.clock and not self.timed:
-            raise ValueError("slots: clock=True needs timed=True")
-        self._emit_dtype = SLOT_EMIT_TIMED_DTYPE if self.timed else SLOT_EMIT_DTYPE
-        self._nslot = S * SLOT_DTYPE.itemsize
-        self._nevents = self._nslot + (S * SLOT_EVENTS_DTYPE.itemsize if events else 0)
-        self._nemit = self._nevents + (S * self._emit_dtype.itemsize if emit else 0)
-        self.hot = bool(hot)
-        if self.hot and not self.events:
-            raise ValueError("slots: hot=True needs events=True")
-        self._nclock = self._nemit + (S * SLOT_CLOCK_DTYPE.itemsize if self.clock else 0)
-        nbytes = self._nclock + (S * SLOT_HOT_DTYPE.itemsize if self.hot else 0)
+        self.events, self.emit, self.timed, self.clock, self.hot = bool(events), bool(emit), bool(timed), bool(clock), bool(hot)
+        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot)
+        self._at = {name: (dtype, off) for name, dtype, off in sections}
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
         self._events = [None] * self.RING
         self._k = 0
 
+    def _host(self, name):
+        dtype, off = self._at[name]
+        return self._pinned[self._k].numpy()[off:off + self.S * dtype.itemsize].view(dtype)
+
+    def _ptr(self, name):
+        return self.dev.data_ptr() + self._at[name][1]
+
     def host(self):
         k = self._k
         if self._events[k] is not None:
             self._events[k].synchronize()
-        buf = self._pinned[k].numpy()
-        buf[:] = 0
-        return buf[:self._nslot].view(SLOT_DTYPE)
+        self._pinned[k].numpy()[:] = 0
+        return self._host("slot")
 
     def events_host(self):
-        """The event entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nslot:self._nevents].view(SLOT_EVENTS_DTYPE)
+        return self._host("events")
 
     def emit_host(self):
-        """The emit entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nevents:self._nemit].view(self._emit_dtype)
+        return self._host("emit")
 
     def clock_host(self):
-        """The clock entries of the window being filled (after host(), which cleared them)."""
-        return self._pinned[self._k].numpy()[self._nemit:self._nclock].view(SLOT_CLOCK_DTYPE)
+        return self._host("clock")
 
     def hot_host(self):
-        """The hot-filter entries of the window being filled (after host(), which cleared them: all inactive)."""
-        return self._pinned[self._k].numpy()[self._nclock:].view(SLOT_HOT_DTYPE)
+        return self._host("hot")
 
     def upload(self):
         k = self._k
@@ -139,19 +146,19 @@ class SlotTable:
         self._k = (k + 1) % self.RING
 
     def ptr(self):
-        return self.dev.data_ptr()
+        return self._ptr("slot")
 
     def events_ptr(self):
-        return self.dev.data_ptr() + self._nslot
+        return self._ptr("events")
 
     def emit_ptr(self):
-        return self.dev.data_ptr() + self._nevents
+        return self._ptr("emit")
 
     def clock_ptr(self):
-        return self.dev.data_ptr() + self._nemit
+        return self._ptr("clock")
 
     def hot_ptr(self):
-        return self.dev.data_ptr() + self._nclock
+        return self._ptr("hot")
 
 
 def _check(cond, what):
@@ -226,11 +233,8 @@ def metrics(table, pred, H, W, gh, gw, nparts):
     LAUNCHES["metrics"] += 1
 
 
-def encode(table, lr_scratch, gt_scratch):
-    """Every slot with an event entry: lr_scratch[s] [seqn,2,H,W] and gt_scratch[s] [2,gh,gw] <- the count images of the
-    entry's event ranges (bmc_slot_encode: one launch, integer counts, deterministic); other slots' scratch is not touched."""
-    global ENCODE_LAUNCHES
-    _check(table.events, "the slot table has no event entries (SlotTable(events=True))")
+def _check_encode_args(table, lr_scratch, gt_scratch):
+    """The scratch images of encode() / encode_filtered() -> (S, seqn, H, W, gh, gw)."""
     for t in (lr_scratch, gt_scratch):
         _check(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == table.S,
                "scratch must be contiguous fp32 GPU tensors [S,...]")
@@ -240,6 +244,15 @@ def encode(table, lr_scratch, gt_scratch):
     gh, gw = gt_scratch.shape[2:]
     _check(2 <= seqn <= MAX_SEQN, "2 <= seqn <= %d" % MAX_SEQN)
     _check(max(W, gw) <= MAX_ENCODE_WIDTH, "frames wider than %d pixels are not supported" % MAX_ENCODE_WIDTH)
+    return S, seqn, H, W, gh, gw
+
+
+def encode(table, lr_scratch, gt_scratch):
+    """Every slot with an event entry: lr_scratch[s] [seqn,2,H,W] and gt_scratch[s] [2,gh,gw] <- the count images of the
+    entry's event ranges (bmc_slot_encode: one launch, integer counts, deterministic); other slots' scratch is not touched."""
+    global ENCODE_LAUNCHES
+    _check(table.events, "the slot table has no event entries (SlotTable(events=True))")
+    S, seqn, H, W, gh, gw = _check_encode_args(table, lr_scratch, gt_scratch)
     lib.call(lib._slot_encode, "bmc_slot_encode", table.events_ptr(), S, seqn, H, W, gh, gw, lr_scratch.data_ptr(),
              gt_scratch.data_ptr(), _stream())
     ENCODE_LAUNCHES += 1
@@ -297,7 +310,7 @@ def hot_update(table, counts, ring, ws, max_px, max_rate):
     the last item's mask count / mask go to the entry's hot_pixels / hot_mask addresses.  ws: int32 [S,H,W] of workspace.
     One launch for all slots (bmc_slot_hot_update); inactive slots are not touched."""
     global HOT_LAUNCHES
-    _check(table.events and getattr(table, "hot", False), "the slot table has no hot entries (SlotTable(events=True, hot=True))")
+    _check(table.events and table.hot, "the slot table has no hot entries (SlotTable(events=True, hot=True))")
     _check(torch.is_tensor(ring) and ring.dim() == 4 and ring.is_cuda and ring.is_contiguous() and ring.dtype == torch.uint8
            and ring.shape[0] == table.S, "ring must be a contiguous uint8 GPU tensor [S,seqn,H,W]")
     S, seqn, H, W = ring.shape
@@ -316,16 +329,8 @@ def encode_filtered(table, lr_scratch, gt_scratch, ring):
     """encode() of a filtered session (bmc_slot_encode_filtered: one launch): the LR frames of a slot with an active hot entry
     are stored through their items' masks in ring [S,seqn,H,W] (the contract's rule 4); everything else as encode()."""
     global ENCODE_LAUNCHES
-    _check(table.events and getattr(table, "hot", False), "the slot table has no hot entries (SlotTable(events=True, hot=True))")
-    for t in (lr_scratch, gt_scratch):
-        _check(t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == table.S,
-               "scratch must be contiguous fp32 GPU tensors [S,...]")
-    _check(lr_scratch.dim() == 5 and lr_scratch.shape[2] == 2 and gt_scratch.dim() == 4 and gt_scratch.shape[1] == 2,
-           "lr_scratch [S,seqn,2,H,W] and gt_scratch [S,2,gh,gw]")
-    S, seqn, _, H, W = lr_scratch.shape
-    gh, gw = gt_scratch.shape[2:]
-    _check(2 <= seqn <= MAX_SEQN, "2 <= seqn <= %d" % MAX_SEQN)
-    _check(max(W, gw) <= MAX_ENCODE_WIDTH, "frames wider than %d pixels are not supported" % MAX_ENCODE_WIDTH)
+    _check(table.events and table.hot, "the slot table has no hot entries (SlotTable(events=True, hot=True))")
+    S, seqn, H, W, gh, gw = _check_encode_args(table, lr_scratch, gt_scratch)
     _check(torch.is_tensor(ring) and ring.is_cuda and ring.is_contiguous() and ring.dtype == torch.uint8
            and tuple(ring.shape) == (S, seqn, H, W), "ring must be a contiguous uint8 GPU tensor [S,seqn,H,W]")
     lib.call(lib._slot_encode_filtered, "bmc_slot_encode_filtered", table.events_ptr(), table.hot_ptr(), ring.data_ptr(), S, seqn,
@@ -339,17 +344,8 @@ def emit_parts(sH, sW):
     return max(1, min(MAX_EMIT_PARTS, -(-2 * sH * sW // 4096)))
 
 
-def emit(table, pred, max_count, nparts, parts):
-    """Every active slot with an emit entry: the events of pred[s] ([2,sH,sW]; q = min(rint(v), max_count) for v > 0, else 0;
-    q events (x, sH-1-row, +1 / -1 by channel) per element in flat order) are appended to the entry's columns at *index_in,
-    *index_out <- *index_in + their number (bmc_slot_emit: a count and a write launch for all slots, deterministic).
-    parts: int32 scratch of at least S * nparts words."""
-    global EMIT_LAUNCHES
-    _check(table.emit, "the slot table has no emit entries (SlotTable(emit=True))")
-    _check(not getattr(table, "timed", False), "the slot table has timed emit entries: use emit_timed()")
-    _check(isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_LIMIT, "1 <= max_count <= %d (got %r)"
-           % (MAX_COUNT_LIMIT, max_count))
-    _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
+def _check_emit_args(table, pred, max_count, nparts, parts):
+    """The prediction and the part totals of emit() / emit_timed() (max_count and nparts are in range) -> (S, sH, sW)."""
     _check(torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.is_cuda and pred.is_contiguous()
            and pred.dtype == torch.float32 and pred.shape[0] == table.S, "pred must be a contiguous fp32 GPU tensor [S,2,sH,sW]")
     S, _, sH, sW = pred.shape
@@ -359,6 +355,21 @@ def emit(table, pred, max_count, nparts, parts):
            and parts.numel() >= S * nparts, "parts must be a contiguous int32 GPU tensor of at least S * nparts words")
     _check((-(-2 * sH * sW // nparts) + 3) // 4 * 4 * max_count < 2 ** 32,
            "a part's event total would overflow 32 bits: use more parts")
+    return S, sH, sW
+
+
+def emit(table, pred, max_count, nparts, parts):
+    """Every active slot with an emit entry: the events of pred[s] ([2,sH,sW]; q = min(rint(v), max_count) for v > 0, else 0;
+    q events (x, sH-1-row, +1 / -1 by channel) per element in flat order) are appended to the entry's columns at *index_in,
+    *index_out <- *index_in + their number (bmc_slot_emit: a count and a write launch for all slots, deterministic).
+    parts: int32 scratch of at least S * nparts words."""
+    global EMIT_LAUNCHES
+    _check(table.emit, "the slot table has no emit entries (SlotTable(emit=True))")
+    _check(not table.timed, "the slot table has timed emit entries: use emit_timed()")
+    _check(isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_LIMIT, "1 <= max_count <= %d (got %r)"
+           % (MAX_COUNT_LIMIT, max_count))
+    _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
+    S, sH, sW = _check_emit_args(table, pred, max_count, nparts, parts)
     lib.call(lib._slot_emit, "bmc_slot_emit", table.ptr(), table.emit_ptr(), S, pred.data_ptr(), sH, sW, max_count, nparts,
              parts.data_ptr(), _stream())
     EMIT_LAUNCHES += 1
@@ -415,27 +426,19 @@ def emit_clocked(table, pred, max_count, nparts, parts, scratch, window_capacity
     clock entry has a `ts` column stores float64 times t = t_first + tau * (t_last - t_first) there, tau from the reduced
     fraction of j / (n - 1); a slot without one gets emit_timed()'s float32 column.  Same events, order, capacity rules,
     arguments and launches (counted in EMIT_TIMED_LAUNCHES)."""
-    _check(getattr(table, "clock", False), "the slot table has no clock entries (SlotTable(emit=True, timed=True, clock=True))")
+    _check(table.clock, "the slot table has no clock entries (SlotTable(emit=True, timed=True, clock=True))")
     _emit_timed(True, table, pred, max_count, nparts, parts, scratch, window_capacity)
 
 
 def _emit_timed(clocked, table, pred, max_count, nparts, parts, scratch, window_capacity):
     global EMIT_TIMED_LAUNCHES
-    _check(table.emit and getattr(table, "timed", False),
+    _check(table.emit and table.timed,
            "the slot table has no timed emit entries (SlotTable(emit=True, timed=True))")
     _check(not isinstance(max_count, bool) and isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_TIMED,
            "timed emission needs 1 <= max_count <= %d (got %r)" % (MAX_COUNT_TIMED, max_count))
     _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
     _check_window_capacity(window_capacity)
-    _check(torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.is_cuda and pred.is_contiguous()
-           and pred.dtype == torch.float32 and pred.shape[0] == table.S, "pred must be a contiguous fp32 GPU tensor [S,2,sH,sW]")
-    S, _, sH, sW = pred.shape
-    _check(max(sH, sW) <= MAX_COUNT_LIMIT, "predictions larger than %d pixels a side cannot be emitted (int16 coordinates)"
-           % MAX_COUNT_LIMIT)
-    _check(torch.is_tensor(parts) and parts.is_cuda and parts.dtype == torch.int32 and parts.is_contiguous()
-           and parts.numel() >= S * nparts, "parts must be a contiguous int32 GPU tensor of at least S * nparts words")
-    _check((-(-2 * sH * sW // nparts) + 3) // 4 * 4 * max_count < 2 ** 32,
-           "a part's event total would overflow 32 bits: use more parts")
+    S, sH, sW = _check_emit_args(table, pred, max_count, nparts, parts)
     need = emit_timed_scratch_bytes(S, nparts, window_capacity)
     _check(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
            and scratch.numel() >= need and scratch.data_ptr() % 8 == 0,

@@ -1,0 +1,131 @@
+// What the two event-output files share (internal): slot_emit.hip (bmc_slot_emit) and slot_emit_timed.hip (bmc_slot_emit_timed /
+// _clocked).  A timed stream is "the events of slot_emit.hip, with times", so the quantisation rule, the walk over a slot's
+// prediction and the decoding of an element into an event exist once, here.  slot_emit.hip describes the algorithm.
+#pragma once
+#include "slot_k.h"
+
+namespace {
+
+constexpr int EMT = 256;             // threads per workgroup (4 waves)
+constexpr int NW = EMT / 64;
+constexpr int TILE = 4 * EMT;        // elements per tile: 4 consecutive ones per lane
+
+__device__ __forceinline__ unsigned quant(float v, float mc) { return v > 0.f ? (unsigned)fminf(rintf(v), mc) : 0u; }
+
+// q of the 4 elements i .. i+3 of a slot's prediction, 0 beyond `hi`.  vec: i, hi and the slot's base are multiples of 4
+__device__ __forceinline__ void load_q4(const float* ps, int i, int hi, bool vec, float mc, unsigned (&q)[4]) {
+    q[0] = q[1] = q[2] = q[3] = 0u;
+    if (i >= hi) return;
+    if (vec) {
+        const f32x4 v = gld<f32x4>(ps + i);
+        q[0] = quant(v.x, mc); q[1] = quant(v.y, mc); q[2] = quant(v.z, mc); q[3] = quant(v.w, mc);
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (i + k < hi) q[k] = quant(gld<float>(ps + i + k), mc);
+    }
+}
+
+// the slot emits this window: it is active and its emit entry has columns (uniform over the workgroup).  E: bmc_slot_emit_t
+// or bmc_slot_emit_timed_t (the same leading fields)
+template <class E>
+__device__ __forceinline__ bool emits(const bmc_slot_t* table, const E* emit, int s) {
+    return (gld<int>(&table[s].flags) & BMC_SLOT_ACTIVE) && gld<const float*>(&table[s].frames) != nullptr &&
+           gld<short*>(&emit[s].xs) != nullptr;
+}
+
+// part p of a grid (nparts, S) owns elements [lo, hi) = [p * chunk, min(n, (p+1) * chunk)) of the slot's n = 2*sH*sW
+struct PartRange {
+    int lo, hi;
+};
+__device__ __forceinline__ PartRange part_range(int part, int chunk, int n) {
+    const long long lo64 = (long long)part * chunk;
+    return PartRange{(int)(lo64 < n ? lo64 : n), (int)(lo64 + chunk < n ? lo64 + chunk : n)};
+}
+
+// pp[0] + .. + pp[cnt - 1] (part totals of a slot) in every thread.  red: NW words of LDS.  Called by all 256 threads.
+__device__ __forceinline__ unsigned long long sum_parts(const unsigned* pp, int cnt, unsigned long long* red, int tid) {
+    unsigned long long acc = 0ull;
+    for (int j = tid; j < cnt; j += EMT) acc += gld<unsigned>(pp + j);
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
+    if ((tid & 63) == 0) red[tid >> 6] = acc;
+    __syncthreads();
+    return red[0] + red[1] + red[2] + red[3];
+}
+
+// One tile of a part: lane `tid` brings the q of elements tb + 4 * tid .. + 3 (wave scan with cross-lane moves, one LDS
+// exchange between the waves); excl[TILE] <- the exclusive prefix of q inside the tile, -> the tile's events.  wtot: NW words
+// of LDS.  Called by all 256 threads; excl is complete when it returns.
+__device__ __forceinline__ unsigned tile_scan(const float* ps, int tb, int hi, bool vec, float mc, unsigned* excl, unsigned* wtot,
+                                              int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned q[4];
+    load_q4(ps, tb + 4 * tid, hi, vec, mc, q);
+    const unsigned t = q[0] + q[1] + q[2] + q[3];
+    unsigned inc = t;                                                 // inclusive scan over the wave
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned v = __shfl_up(inc, o);
+        if (lane >= o) inc += v;
+    }
+    if (lane == 63) wtot[wave] = inc;
+    __syncthreads();
+    unsigned woff = 0u, ttot = 0u;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) {
+        const unsigned v = wtot[w];
+        if (w < wave) woff += v;
+        ttot += v;
+    }
+    const unsigned e0 = woff + inc - t;
+    excl[4 * tid] = e0;
+    excl[4 * tid + 1] = e0 + q[0];
+    excl[4 * tid + 2] = e0 + q[0] + q[1];
+    excl[4 * tid + 3] = e0 + q[0] + q[1] + q[2];
+    __syncthreads();
+    return ttot;
+}
+
+// the element of the tile that owns output position p < ttot: the largest e with excl[e] <= p (its q is > 0)
+__device__ __forceinline__ int tile_owner(const unsigned* excl, unsigned p) {
+    int e = 0;
+#pragma unroll
+    for (int step = TILE / 2; step > 0; step >>= 1)
+        if (excl[e + step] <= p) e += step;
+    return e;
+}
+
+// flat element idx of [2][sH][sW] (hw = sH * sW) -> its event (x, sH-1-row, +1 / -1 by channel) at position pos of the columns
+__device__ __forceinline__ void store_event(short* xs, short* ys, signed char* pol, long long pos, unsigned idx, int sH, int sW,
+                                            unsigned hw) {
+    const unsigned c = idx >= hw ? 1u : 0u, rem = idx - c * hw, row = rem / (unsigned)sW, x = rem - row * (unsigned)sW;
+    gst<short>(xs + pos, (short)x);
+    gst<short>(ys + pos, (short)(sH - 1 - (int)row));
+    gst<signed char>(pol + pos, (signed char)(c ? -1 : 1));
+}
+
+// elements per slot and per part of a launch, and whether a lane may load its 4 elements as one f32x4
+struct EmitGeom {
+    int n, chunk, vec;
+};
+// The argument checks that bmc_slot_emit and bmc_slot_emit_timed / _clocked share (`who` names the entry point; max_count has
+// been checked by the caller, whose bound it is) -> 0 and the geometry, or -1 with the error set.
+static inline int emit_geometry(const char* who, const void* table, const void* emit, const float* pred, const unsigned* parts,
+                                int S, int sH, int sW, int max_count, int nparts, EmitGeom* g) {
+    BMC_CHECK_ARG(table && emit && pred && parts && S >= 1 && S <= BMC_MAX_SLOTS, "%s: bad arguments", who);
+    BMC_CHECK_ARG(sH >= 1 && sW >= 1 && sH <= 32767 && sW <= 32767,
+                  "%s: sH, sW must be 1 .. 32767 (coordinates are int16; got %d x %d)", who, sH, sW);
+    BMC_CHECK_ARG(nparts >= 1 && nparts <= BMC_SLOT_EMIT_MAX_PARTS, "%s: 1 <= nparts <= %d (got %d)", who,
+                  BMC_SLOT_EMIT_MAX_PARTS, nparts);
+    BMC_CHECK_ARG(((unsigned long long)pred & 3ull) == 0, "%s: pred must be 4-byte aligned", who);
+    const long long n = 2ll * sH * sW;                                // < 2^31 for sH, sW <= 32767
+    const long long chunk = ((n + nparts - 1) / nparts + 3) / 4 * 4;
+    BMC_CHECK_ARG(chunk * max_count < (1ll << 32),
+                  "%s: %lld elements per part x max_count %d overflow a part's 32-bit total: use more parts", who, chunk,
+                  max_count);
+    g->n = (int)n;
+    g->chunk = (int)chunk;
+    g->vec = n % 4 == 0 && ((unsigned long long)pred & 15ull) == 0;
+    return 0;
+}
+
+}  // namespace

@@ -21,54 +21,19 @@
 // Stability: a workgroup handles its records 256 at a time in sequence order; the position of a record among those of its
 // digit is (the workgroup's running count of the digit) + (the digit's counts of the lower waves in this step) + (the lanes
 // below it in its wave with the same digit: eight ballots).
-// Pointers read from the tables go through address-space(1) casts (global_* instructions, never flat_*), as in slots.hip.
 //
 // Clocked output (bmc_slot_emit_clocked): the same six launches with a fourth table of bmc_slot_clock_t.  A slot whose clock
 // entry has a `ts` column stores float64 times on the recording's own clock there instead of the float32 column:
 // t = t_first + tau * (t_last - t_first), tau = T0 + (T1 - T0) * (j / g) / ((n - 1) / g), g = gcd(j, n - 1) -- the reduced
 // fraction gives equal rationals ONE tau, so the float64 column cannot decrease inside a run of ties.  Only the scatter
 // kernel reads the clock table; a NULL table (bmc_slot_emit_timed) or a NULL `ts` keeps the float32 behaviour.
-#include "bmc_common.h"
+#include "slot_emit_k.h"
 
 namespace {
 
-template <class T>
-__device__ __forceinline__ T gld(const void* p) {
-    return *(const __attribute__((address_space(1))) T*)(unsigned long long)p;
-}
-template <class T>
-__device__ __forceinline__ void gst(void* p, T v) {
-    *(__attribute__((address_space(1))) T*)(unsigned long long)p = v;
-}
-
 typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
-constexpr int EMT = 256;             // threads per workgroup (4 waves)
-constexpr int NW = EMT / 64;
-constexpr int TILE = 4 * EMT;        // elements per tile: 4 consecutive ones per lane
 constexpr int T2 = BMC_SLOT_EMIT_TIMED_BLOCK;   // records per workgroup of the high-digit pass
-
-__device__ __forceinline__ unsigned quant(float v, float mc) { return v > 0.f ? (unsigned)fminf(rintf(v), mc) : 0u; }
-
-// q of the 4 elements i .. i+3 of a slot's prediction, 0 beyond `hi`.  vec: i, hi and the slot's base are multiples of 4
-__device__ __forceinline__ void load_q4(const float* ps, int i, int hi, bool vec, float mc, unsigned (&q)[4]) {
-    q[0] = q[1] = q[2] = q[3] = 0u;
-    if (i >= hi) return;
-    if (vec) {
-        const f32x4 v = gld<f32x4>(ps + i);
-        q[0] = quant(v.x, mc); q[1] = quant(v.y, mc); q[2] = quant(v.z, mc); q[3] = quant(v.w, mc);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (i + k < hi) q[k] = quant(gld<float>(ps + i + k), mc);
-    }
-}
-
-// the slot emits this window: it is active and its emit entry has columns (uniform over the workgroup)
-__device__ __forceinline__ bool emits(const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, int s) {
-    return (gld<int>(&table[s].flags) & BMC_SLOT_ACTIVE) && gld<const float*>(&table[s].frames) != nullptr &&
-           gld<short*>(&emit[s].xs) != nullptr;
-}
 
 // One step of the stable split: every lane brings at most one record (digit d; !valid: none), the records of a step are in
 // sequence order by (wave, lane) and the steps of a workgroup follow one another.  run[d] = the position of the next record
@@ -113,12 +78,11 @@ __global__ __launch_bounds__(EMT) void emit_timed_count_kernel(const bmc_slot_t*
     lh[tid] = 0u;
     __syncthreads();
     const float* const ps = pred + (long long)s * n;
-    const long long lo64 = (long long)part * chunk;
-    const int lo = (int)(lo64 < n ? lo64 : n), hi = (int)(lo64 + chunk < n ? lo64 + chunk : n);
+    const PartRange r = part_range(part, chunk, n);
     unsigned acc = 0u;
-    for (int i = lo + 4 * tid; i < hi; i += TILE) {
+    for (int i = r.lo + 4 * tid; i < r.hi; i += TILE) {
         unsigned q[4];
-        load_q4(ps, i, hi, vec, mc, q);
+        load_q4(ps, i, r.hi, vec, mc, q);
         acc += q[0] + q[1] + q[2] + q[3];
 #pragma unroll
         for (int k = 0; k < 4; ++k)
@@ -146,13 +110,7 @@ __global__ __launch_bounds__(EMT) void emit_timed_scan_kernel(const bmc_slot_t* 
     if (!emits(table, emit, s)) return;
     unsigned long long total;
     if (first) {
-        const unsigned* const pp = parts + (long long)s * nparts;
-        total = 0ull;
-        for (int j = tid; j < nparts; j += EMT) total += gld<unsigned>(pp + j);
-        for (int o = 32; o > 0; o >>= 1) total += __shfl_down(total, o);
-        if (lane == 0) red[wave] = total;
-        __syncthreads();
-        total = red[0] + red[1] + red[2] + red[3];
+        total = sum_parts(parts + (long long)s * nparts, nparts, red, tid);
         if (tid == 0) {
             const bmc_slot_emit_timed_t* const ent = emit + s;
             gst<unsigned long long>(tot + s, total);
@@ -203,48 +161,22 @@ __global__ __launch_bounds__(EMT) void emit_timed_expand_kernel(const bmc_slot_t
     __shared__ unsigned wtot[NW];
     __shared__ unsigned run[256];
     __shared__ unsigned stepc[NW][256];
-    const int part = blockIdx.x, s = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int part = blockIdx.x, s = blockIdx.y, tid = threadIdx.x;
     if (!emits(table, emit, s)) return;
     if (gld<unsigned long long>(tot + s) > (unsigned long long)wcap) return;
     run[tid] = gld<unsigned>(dbase + (long long)s * 256 + tid) + gld<unsigned>(hist + ((long long)s * hrows + part) * 256 + tid);
     stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
     u32x2* const out = rec + (long long)s * wcap;
     const float* const ps = pred + (long long)s * n;
-    const long long lo64 = (long long)part * chunk;
-    const int lo = (int)(lo64 < n ? lo64 : n), hi = (int)(lo64 + chunk < n ? lo64 + chunk : n);
-    for (int tb = lo; tb < hi; tb += TILE) {                          // (uniform over the workgroup)
-        unsigned q[4];
-        load_q4(ps, tb + 4 * tid, hi, vec, mc, q);
-        const unsigned t = q[0] + q[1] + q[2] + q[3];
-        unsigned inc = t;                                             // inclusive scan over the wave
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned v = __shfl_up(inc, o);
-            if (lane >= o) inc += v;
-        }
-        if (lane == 63) wtot[wave] = inc;
-        __syncthreads();
-        unsigned woff = 0u, ttot = 0u;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const unsigned v = wtot[w];
-            if (w < wave) woff += v;
-            ttot += v;
-        }
-        const unsigned e0 = woff + inc - t;
-        excl[4 * tid] = e0;
-        excl[4 * tid + 1] = e0 + q[0];
-        excl[4 * tid + 2] = e0 + q[0] + q[1];
-        excl[4 * tid + 3] = e0 + q[0] + q[1] + q[2];
-        __syncthreads();
+    const PartRange r = part_range(part, chunk, n);
+    for (int tb = r.lo; tb < r.hi; tb += TILE) {                      // (uniform over the workgroup)
+        const unsigned ttot = tile_scan(ps, tb, r.hi, vec, mc, excl, wtot, tid);
         for (unsigned p0 = 0u; p0 < ttot; p0 += EMT) {                // 256 consecutive events of the tile per step
             const unsigned p = p0 + tid;
             const bool valid = p < ttot;
             unsigned key = 0u, idx = 0u;
             if (valid) {
-                int e = 0;                                            // the largest e with excl[e] <= p: its q is > 0
-#pragma unroll
-                for (int step = TILE / 2; step > 0; step >>= 1)
-                    if (excl[e + step] <= p) e += step;
+                const int e = tile_owner(excl, p);
                 const unsigned first = excl[e], nq = (e + 1 < TILE ? excl[e + 1] : ttot) - first, j = p - first;
                 idx = (unsigned)(tb + e);
                 key = ((unsigned)gld<unsigned short>(rank + nq * 256u + j) << 16) | (j << 8) | nq;
@@ -334,10 +266,7 @@ __global__ __launch_bounds__(EMT) void emit_timed_scatter_kernel(const bmc_slot_
         const long long pos = base + place(run, stepc, valid, r.y >> 24, tid);
         if (valid && pos < cap) {
             const unsigned idx = r.x, j = (r.y >> 8) & 255u, nq = r.y & 255u;
-            const unsigned c = idx >= hw ? 1u : 0u, rem = idx - c * hw, row = rem / (unsigned)sW, x = rem - row * (unsigned)sW;
-            gst<short>(xs + pos, (short)x);
-            gst<short>(ys + pos, (short)(sH - 1 - (int)row));
-            gst<signed char>(pol + pos, (signed char)(c ? -1 : 1));
+            store_event(xs, ys, pol, pos, idx, sH, sW, hw);
             if (ts64) {
                 gst<double>(ts64 + pos, clock_time(t_first, dt, j, nq));
             } else {
@@ -370,39 +299,30 @@ namespace {
 int emit_timed_launch(const char* who, const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock,
                       int S, const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
                       const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s) {
-    BMC_CHECK_ARG(table && emit && pred && parts && rank_table && scratch && S >= 1 && S <= BMC_MAX_SLOTS,
-                  "%s: bad arguments", who);
-    BMC_CHECK_ARG(sH >= 1 && sW >= 1 && sH <= 32767 && sW <= 32767,
-                  "%s: sH, sW must be 1 .. 32767 (coordinates are int16; got %d x %d)", who, sH, sW);
+    BMC_CHECK_ARG(rank_table && scratch, "%s: bad arguments", who);
     BMC_CHECK_ARG(max_count >= 1 && max_count <= BMC_SLOT_EMIT_TIMED_MAX_COUNT,
                   "%s: 1 <= max_count <= %d (the rank table; got %d)", who, BMC_SLOT_EMIT_TIMED_MAX_COUNT, max_count);
-    BMC_CHECK_ARG(nparts >= 1 && nparts <= BMC_SLOT_EMIT_MAX_PARTS, "%s: 1 <= nparts <= %d (got %d)", who,
-                  BMC_SLOT_EMIT_MAX_PARTS, nparts);
     BMC_CHECK_ARG(window_capacity >= 1 && window_capacity <= BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
                   "%s: 1 <= window_capacity <= %lld (got %lld)", who, (long long)BMC_SLOT_EMIT_TIMED_MAX_WINDOW,
                   window_capacity);
     BMC_CHECK_ARG(((unsigned long long)pred & 3ull) == 0 && ((unsigned long long)scratch & 7ull) == 0 &&
                       ((unsigned long long)rank_table & 1ull) == 0,
                   "%s: pred must be 4-byte, scratch 8-byte, rank_table 2-byte aligned", who);
-    const long long n = 2ll * sH * sW;                                // < 2^31 for sH, sW <= 32767
-    const long long chunk = ((n + nparts - 1) / nparts + 3) / 4 * 4;
-    BMC_CHECK_ARG(chunk * max_count < (1ll << 32),
-                  "%s: %lld elements per part x max_count %d overflow a part's 32-bit total: use more parts", who,
-                  chunk, max_count);
-    const int vec = n % 4 == 0 && ((unsigned long long)pred & 15ull) == 0;
+    EmitGeom g;
+    if (emit_geometry(who, table, emit, pred, parts, S, sH, sW, max_count, nparts, &g)) return -1;
     const int blocks = (int)((window_capacity + T2 - 1) / T2), hrows = (int)hist_rows(nparts, window_capacity);
     u32x2* const rec = (u32x2*)scratch;
     unsigned long long* const tot = (unsigned long long*)(rec + (long long)S * window_capacity);
     unsigned* const dbase = (unsigned*)(tot + S);
     unsigned* const hist = dbase + (long long)S * 256;
     const hipStream_t st = (hipStream_t)s;
-    hipLaunchKernelGGL(emit_timed_count_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, (int)n, (int)chunk, vec,
+    hipLaunchKernelGGL(emit_timed_count_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, g.n, g.chunk, g.vec,
                        (float)max_count, rank_table, parts, hist, hrows);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (count)");
     hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(S), dim3(EMT), 0, st, table, emit, 1, nparts, (const unsigned*)parts, hist,
                        hrows, dbase, tot, window_capacity);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scan 1)");
-    hipLaunchKernelGGL(emit_timed_expand_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, (int)n, (int)chunk, vec,
+    hipLaunchKernelGGL(emit_timed_expand_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, g.n, g.chunk, g.vec,
                        (float)max_count, rank_table, (const unsigned*)hist, hrows, (const unsigned*)dbase,
                        (const unsigned long long*)tot, window_capacity, rec);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (expand)");

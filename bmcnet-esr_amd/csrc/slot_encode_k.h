@@ -2,18 +2,9 @@
 // slot_encode_filtered_kernel (slot_hot.hip, bmc_slot_encode_filtered) are its two instantiations.  slot_events.hip describes
 // the algorithm.
 #pragma once
-#include "bmc_common.h"
+#include "slot_k.h"
 
 namespace {
-
-template <class T>
-__device__ __forceinline__ T gld(const void* p) {
-    return *(const __attribute__((address_space(1))) T*)(unsigned long long)p;
-}
-template <class T>
-__device__ __forceinline__ void gst(void* p, T v) {
-    *(__attribute__((address_space(1))) T*)(unsigned long long)p = v;
-}
 
 constexpr int ET = 1024;            // threads per workgroup
 constexpr int ENC_LDS = 15360;      // counters per workgroup: 2 channels x R rows x W (60 KB: two workgroups per CU)

@@ -11,21 +11,12 @@
 // The per-slot table (bmc_slot_t) lives in device memory, so a captured graph replays with whatever the host copied into it.
 // Pointers read from the table are generic to the compiler: every access goes through an address-space(1) cast (global_*
 // instructions, never flat_*).
-#include "bmc_common.h"
+#include "slot_k.h"
 #include "cubic_taps.h"
 
 namespace {
 
 typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
-
-template <class T>
-__device__ __forceinline__ T gld(const void* p) {
-    return *(const __attribute__((address_space(1))) T*)(unsigned long long)p;
-}
-template <class T>
-__device__ __forceinline__ void gst(void* p, T v) {
-    *(__attribute__((address_space(1))) T*)(unsigned long long)p = v;
-}
 
 __device__ __forceinline__ float bf2f(unsigned short b) { return __uint_as_float((unsigned)b << 16); }
 // c10::BFloat16's round_to_nearest_even: NaN -> 0x7fc0, otherwise add 0x7fff + lsb and truncate

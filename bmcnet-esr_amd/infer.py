@@ -325,27 +325,33 @@ class MultiStreamSR:
         self._has_clock = False
 
     # ---------------------------------------------------------------- recordings
-    def _check_capacity(self, who, event_capacity):
-        if event_capacity is None:
-            return
-        if not self.emit_events:
-            raise ValueError("MultiStreamSR.%s: event_capacity needs a session with emit_events=True" % who)
-        if isinstance(event_capacity, bool) or not isinstance(event_capacity, (int, np.integer)) or event_capacity < 1:
-            raise ValueError("MultiStreamSR.%s: event_capacity must be a positive integer (got %r)" % (who, event_capacity))
+    def _check_capacities(self, who, event_capacity, capacity):
+        """The two capacities a caller of open / open_events may give (None: the default)."""
+        if event_capacity is not None:
+            if not self.emit_events:
+                raise ValueError("MultiStreamSR.%s: event_capacity needs a session with emit_events=True" % who)
+            if isinstance(event_capacity, bool) or not isinstance(event_capacity, (int, np.integer)) or event_capacity < 1:
+                raise ValueError("MultiStreamSR.%s: event_capacity must be a positive integer (got %r)" % (who, event_capacity))
+        if capacity is not None:
+            if self.event_times is None:
+                raise ValueError("MultiStreamSR.%s: window_event_capacity needs a session with event_times='linear'" % who)
+            if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= self.MAX_WINDOW_CAPACITY:
+                raise ValueError("MultiStreamSR.%s: window_event_capacity must be a positive integer, at most %d (got %r)"
+                                 % (who, self.MAX_WINDOW_CAPACITY, capacity))
 
-    def _check_window_capacity(self, who, capacity):
-        if capacity is None:
-            return
-        if self.event_times is None:
-            raise ValueError("MultiStreamSR.%s: window_event_capacity needs a session with event_times='linear'" % who)
-        if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= self.MAX_WINDOW_CAPACITY:
-            raise ValueError("MultiStreamSR.%s: window_event_capacity must be a positive integer, at most %d (got %r)"
-                             % (who, self.MAX_WINDOW_CAPACITY, capacity))
-
-    def _default_window_capacity(self, busiest, H, W):
-        """2 x scale^2 x the LR events of the busiest frame, at most what a window can emit."""
-        most = 2 * self.scale ** 2 * H * W * self.max_count
-        return max(1, min(2 * self.scale ** 2 * int(busiest), most, self.MAX_WINDOW_CAPACITY))
+    def _emit_room(self, who, H, W, event_capacity, window_event_capacity, total, busiest):
+        """What an emitting session needs of a recording of H x W frames: coordinates in int16, and the two capacities, by
+        default 2 x scale^2 x the recording's LR events / 2 x scale^2 x the LR events of its busiest item (at most what a window
+        can emit).  total / busiest give those counts and are called only where a default is needed."""
+        if self.emit_events and max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
+            raise ValueError("MultiStreamSR.%s: predictions of %d x %d cannot be emitted (int16 coordinates)"
+                             % (who, self.scale * H, self.scale * W))
+        if self.emit_events and event_capacity is None:
+            event_capacity = 2 * self.scale ** 2 * int(total())
+        if self.event_times is not None and window_event_capacity is None:
+            most = 2 * self.scale ** 2 * H * W * self.max_count
+            window_event_capacity = max(1, min(2 * self.scale ** 2 * int(busiest()), most, self.MAX_WINDOW_CAPACITY))
+        return event_capacity, window_event_capacity
 
     def _check_spans(self, who, spans, L):
         """spans (or None) -> a validated [L,2] float64 table on the host (or None)."""
@@ -363,23 +369,18 @@ class MultiStreamSR:
         sum of `frames` (one device reduction here).  window_event_capacity (event_times): events of ONE window the sort
         scratch holds; default 2 x scale^2 x the largest sum of one frame.  spans (event_times) [L,2] float64 on the host:
         (t_first, t_last) of every frame on the sensor's clock -> sr_ts is float64 on that clock."""
-        self._check_capacity("open", event_capacity)
-        self._check_window_capacity("open", window_event_capacity)
-        if gts is None:
-            if frames.dim() != 4 or frames.shape[1] != 2:
-                raise ValueError("MultiStreamSR.open: frames [L,2,H,W] (got %s)" % (tuple(frames.shape),))
-            if gt_size is not None:
-                raise ValueError("MultiStreamSR.open: gt_size without a ground truth")
-            spans = self._check_spans("open", spans, frames.shape[0])
-            if not (frames.is_cuda and frames.dtype == torch.float32):
-                raise ValueError("MultiStreamSR.open: frames must be an fp32 GPU tensor")
-        else:
-            if frames.dim() != 4 or frames.shape[1] != 2 or gts.dim() != 4 or tuple(gts.shape[:2]) != (frames.shape[0], 2):
-                raise ValueError("MultiStreamSR.open: frames [L,2,H,W] and gts [L,2,gh,gw] (got %s, %s)"
-                                 % (tuple(frames.shape), tuple(gts.shape)))
-            spans = self._check_spans("open", spans, frames.shape[0])
-            if not (frames.is_cuda and gts.is_cuda and frames.dtype == torch.float32 and gts.dtype == torch.float32):
-                raise ValueError("MultiStreamSR.open: frames and gts must be fp32 GPU tensors")
+        self._check_capacities("open", event_capacity, window_event_capacity)
+        given = (frames,) if gts is None else (frames, gts)
+        if frames.dim() != 4 or frames.shape[1] != 2 or any(g.dim() != 4 or tuple(g.shape[:2]) != (frames.shape[0], 2)
+                                                            for g in given[1:]):
+            raise ValueError("MultiStreamSR.open: frames [L,2,H,W]%s (got %s)"
+                             % (" and gts [L,2,gh,gw]" * (gts is not None), ", ".join(str(tuple(g.shape)) for g in given)))
+        if gts is None and gt_size is not None:
+            raise ValueError("MultiStreamSR.open: gt_size without a ground truth")
+        spans = self._check_spans("open", spans, frames.shape[0])
+        if not all(g.is_cuda and g.dtype == torch.float32 for g in given):
+            raise ValueError("MultiStreamSR.open: %s" % ("frames must be an fp32 GPU tensor" if gts is None else
+                                                         "frames and gts must be fp32 GPU tensors"))
         L = frames.shape[0]
         if L < self.seqn:
             raise ValueError("MultiStreamSR.open: %d frames, fewer than one window of seqn = %d" % (L, self.seqn))
@@ -387,14 +388,10 @@ class MultiStreamSR:
         gh, gw = (None, None) if gts is None else (gts.shape[2], gts.shape[3])
         if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
             raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
-        if max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT and self.emit_events:
-            raise ValueError("MultiStreamSR.open: predictions of %d x %d cannot be emitted (int16 coordinates)"
-                             % (self.scale * H, self.scale * W))
+        event_capacity, window_event_capacity = self._emit_room(
+            "open", H, W, event_capacity, window_event_capacity, lambda: frames.sum(dtype=torch.float64).item(),
+            lambda: frames.sum(dim=(1, 2, 3), dtype=torch.float64).max().item())
         self._set_size("open", H, W, gh, gw)
-        if self.emit_events and event_capacity is None:
-            event_capacity = 2 * self.scale ** 2 * int(frames.sum(dtype=torch.float64).item())
-        if self.event_times is not None and window_event_capacity is None:
-            window_event_capacity = self._default_window_capacity(frames.sum(dim=(1, 2, 3), dtype=torch.float64).max().item(), H, W)
         rec = {"frames": frames.contiguous()}
         if gts is not None:
             rec["gts"] = gts.contiguous()
@@ -408,11 +405,21 @@ class MultiStreamSR:
             raise ValueError("MultiStreamSR.%s: sizes %s differ from the first recording's %s (group recordings by sensor "
                              "size)" % (who, size, self._size))
         if self._size is None or len(size) > len(self._size):
+            if self._size is None:                         # once per session: workgroups per slot of the emit launches
+                from bmc_hip import slots
+                self._nparts = slots.emit_parts(self.scale * H, self.scale * W)
             self._size = size
-            if len(size) == 4 and self._bufs is not None:  # a running session without ground truth: the metrics launch joins
-                if "gt_scratch" in self._bufs:
-                    self._bufs["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=self._bufs["gt_scratch"].device)
-                self.invalidate()
+            if len(size) == 4:                             # a running session without ground truth: the metrics launch joins
+                self._grow(self._gt_scratch)
+
+    def _grow(self, *rebuild):
+        """The session gains a part (a first event-backed, clocked or ground-truth recording, a larger window capacity).  One
+        that has run already rebuilds the buffers concerned -- rebuild: methods taking (buffers, device) -- and drops its
+        captured graph, which holds the old addresses and launches."""
+        if self._bufs is not None:
+            for make in rebuild:
+                make(self._bufs, self._bufs["x"].device)
+            self.invalidate()
 
     def _add(self, rec, L, device, event_capacity=None, window_event_capacity=None, spans=None):
         """Queue a recording of L items (frames or event blocks) -> handle."""
@@ -436,14 +443,10 @@ class MultiStreamSR:
                 rec["spans"] = spans
                 if not self._has_clock:
                     self._has_clock = True
-                    if self._bufs is not None:             # a running session: the table grows a clock part
-                        self._bufs["table"] = self._table(device)
-                        self.invalidate()
+                    self._grow(self._new_table)            # the table grows a clock part
             if rec["win_capacity"] > self._wcap:
                 self._wcap = rec["win_capacity"]
-                if self._bufs is not None:                 # a running session: the sort scratch grows
-                    self._sort_buffers(self._bufs, device)
-                    self.invalidate()
+                self._grow(self._sort_buffers)             # the sort scratch grows
         h = self.sched.add(nwin)
         self._recs[h] = rec
         return h
@@ -467,8 +470,7 @@ class MultiStreamSR:
         of every item (bmc_hip.encodings.event_block_spans) and float64 sr_ts on the sensor's clock; or spans [L,2] directly
         (not both)."""
         who = "MultiStreamSR.open_events: "
-        self._check_capacity("open_events", event_capacity)
-        self._check_window_capacity("open_events", window_event_capacity)
+        self._check_capacities("open_events", event_capacity, window_event_capacity)
         if lr_index is None or lr_size is None:
             raise ValueError(who + "lr_index and lr_size are required")
         has_gt = gt is not None
@@ -524,9 +526,9 @@ class MultiStreamSR:
         if min(H, W, gh or 1, gw or 1) < 1 or max(W, gw or 1) > self.MAX_WIDTH_EVENTS:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)"
                              % (self.MAX_WIDTH_EVENTS, (H, W), (gh, gw)))
-        if self.emit_events and max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
-            raise ValueError(who + "predictions of %d x %d cannot be emitted (int16 coordinates)"
-                             % (self.scale * H, self.scale * W))
+        lengths = lr_index[:, 1] - lr_index[:, 0]
+        event_capacity, window_event_capacity = self._emit_room("open_events", H, W, event_capacity, window_event_capacity,
+                                                                lengths.sum, lengths.max)
         cols = tuple(lr) + (tuple(gt) if has_gt else ())
         if not all(t.is_cuda and t.device == cols[0].device for t in cols):
             raise ValueError(who + "the columns must be GPU tensors on one device")
@@ -534,10 +536,6 @@ class MultiStreamSR:
             if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
                 raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
         self._set_size("open_events", H, W, gh, gw)
-        if self.emit_events and event_capacity is None:
-            event_capacity = 2 * self.scale ** 2 * int((lr_index[:, 1] - lr_index[:, 0]).sum())
-        if self.event_times is not None and window_event_capacity is None:
-            window_event_capacity = self._default_window_capacity((lr_index[:, 1] - lr_index[:, 0]).max(), H, W)
         rec = {"lr": tuple(lr), "lr_index": lr_index}
         if has_gt:
             rec.update(gt=tuple(gt), gt_index=gt_index)
@@ -550,9 +548,7 @@ class MultiStreamSR:
         h = self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
         if not self._has_events:
             self._has_events = True
-            if self._bufs is not None:                     # a running frames-only session: the table grows an event part
-                self._event_buffers(self._bufs, cols[0].device)
-                self.invalidate()
+            self._grow(self._event_buffers)                # a frames-only session: the table grows an event part
         return h
 
     def resident_bytes(self, handle):
@@ -574,8 +570,7 @@ class MultiStreamSR:
         nbytes = 0
         if self._wcap:
             from bmc_hip import slots
-            H, W = self._size[:2]
-            nbytes = slots.emit_timed_scratch_bytes(self.S, slots.emit_parts(self.scale * H, self.scale * W), self._wcap)
+            nbytes = slots.emit_timed_scratch_bytes(self.S, self._nparts, self._wcap)
         if not self._has_events:
             return nbytes
         H, W = self._size[:2]
@@ -634,13 +629,11 @@ class MultiStreamSR:
         if self._bufs is None:
             H, W = self._size[:2]
             S, nfeat = self.S, 1 if self.plain else 3
-            from bmc_hip import slots
             b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
-                 "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
-                 "table": self._table(device)}
+                 "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device)}
+            self._new_table(b, device)
             if self.emit_events:
-                b["emit_parts"] = torch.zeros(S * slots.emit_parts(self.scale * H, self.scale * W), dtype=torch.int32,
-                                              device=device)
+                b["emit_parts"] = torch.zeros(S * self._nparts, dtype=torch.int32, device=device)
             if self.event_times is not None:
                 self._sort_buffers(b, device)
             if self._has_events:
@@ -653,27 +646,30 @@ class MultiStreamSR:
             self._bufs = b
         return self._bufs
 
-    def _table(self, device):
+    def _new_table(self, b, device):
         """The slot table with the parts the session needs so far."""
         from bmc_hip import slots
-        return slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
-                               timed=self.event_times is not None, clock=self._has_clock,
-                               hot=self._has_events and self.hot_filter is not None)
+        b["table"] = slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
+                                     timed=self.event_times is not None, clock=self._has_clock,
+                                     hot=self._has_events and self.hot_filter is not None)
 
     def _sort_buffers(self, b, device):
         from bmc_hip import slots
-        H, W = self._size[:2]
         slots.emit_rank_table(device)                      # uploaded here, once per device: never inside a graph capture
-        b["emit_scratch"] = torch.empty(slots.emit_timed_scratch_bytes(self.S, slots.emit_parts(self.scale * H, self.scale * W),
-                                                                       self._wcap), dtype=torch.uint8, device=device)
+        b["emit_scratch"] = torch.empty(slots.emit_timed_scratch_bytes(self.S, self._nparts, self._wcap), dtype=torch.uint8,
+                                        device=device)
+
+    def _gt_scratch(self, b, device):
+        if "lr_scratch" in b:                              # (event-backed slots only)
+            gh, gw = self._gt_scratch_size()
+            b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
 
     def _event_buffers(self, b, device):
         H, W = self._size[:2]
-        gh, gw = self._gt_scratch_size()
         if not b["table"].events:
-            b["table"] = self._table(device)
+            self._new_table(b, device)
         b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
-        b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
+        self._gt_scratch(b, device)
         if self.hot_filter is not None:                    # per slot: the running counts, a ring of seqn masks, the workspace
             b["hot_counts"] = torch.zeros(self.S, H, W, dtype=torch.int32, device=device)
             b["hot_ring"] = torch.ones(self.S, self.seqn, H, W, dtype=torch.uint8, device=device)
@@ -703,11 +699,9 @@ class MultiStreamSR:
             slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
         if self.event_times is not None:
             emit = slots.emit_clocked if self._has_clock else slots.emit_timed
-            emit(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
-                 b["emit_parts"], b["emit_scratch"], self._wcap)
+            emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"], b["emit_scratch"], self._wcap)
         elif self.emit_events:
-            slots.emit(b["table"], out[-1].contiguous(), self.max_count, slots.emit_parts(self.scale * H, self.scale * W),
-                       b["emit_parts"])
+            slots.emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"])
 
     def _weights_stamp(self):
         return tuple((id(p), p._version) for p in self.model.parameters())
@@ -729,61 +723,82 @@ class MultiStreamSR:
         self._graph = g
         self._stamp = self._weights_stamp()
 
+    def _fill_frames(self, e, r, i):
+        """Slot entry e of window i of a frame-backed recording."""
+        H, W = self._size[:2]
+        e["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
+        if "gts" in r:
+            e["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * self._size[2] * self._size[3]
+
+    def _fill_events(self, e, ev, ht, s, r, i, reset):
+        """Slot entry e, and entry s of the event (ev) and hot (ht, or None) parts, of window i of an event-backed recording:
+        the slot entry points at the slot's scratch images."""
+        b = self._bufs
+        e["frames"] = b["lr_scratch"][s].data_ptr()
+        for k, t in zip(("lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps"), r["lr"] + r.get("gt", ())):
+            ev[k][s] = t.data_ptr()
+        ev["lr_range"][s, :self.seqn] = r["lr_index"][i:i + self.seqn]
+        if "gt" in r:                                      # (without: NULL columns, range (0, 0): the scratch is only zero-filled)
+            e["gt"] = b["gt_scratch"][s].data_ptr()
+            ev["gt_range"][s] = r["gt_index"][i + 1]
+        if ht is not None:                                 # the first window observes items 0 .. seqn-1, a later one item i+seqn-1
+            ht[s]["active"], ht[s]["first_item"], ht[s]["new_from"] = 1, i, 0 if reset else self.seqn - 1
+            ht[s]["cmin"][:self.seqn] = r["hot_cmin"][i:i + self.seqn]
+            ht[s]["hot_pixels"] = r["hot_pixels"].data_ptr() + 4 * i
+            ht[s]["hot_mask"] = r["hot_mask"].data_ptr()
+
+    @staticmethod
+    def _fill_emit(em, ck, r, i):
+        """Emit entry em and clock entry ck (of a table with a clock part) of window i: it appends at index[i] and leaves
+        index[i+1]."""
+        em["xs"], em["ys"], em["ps"] = r["ev_xs"].data_ptr(), r["ev_ys"].data_ptr(), r["ev_ps"].data_ptr()
+        em["index_in"] = r["ev_index"].data_ptr() + 8 * i
+        em["index_out"] = r["ev_index"].data_ptr() + 8 * (i + 1)
+        em["capacity"] = r["ev_capacity"]
+        if "spans" in r:                                   # window i predicts item i+1: its span, float64 times
+            ck["t_first"], ck["t_last"] = r["spans"][i + 1]
+            ck["ts"] = r["ev_ts"].data_ptr()
+        elif "ev_ts" in r:
+            em["ts"] = r["ev_ts"].data_ptr()
+
+    def _fill(self, plan):
+        """The table entries of the window `plan`, into the table's host copy."""
+        from bmc_hip import slots
+        t = self._bufs["table"]
+        e = t.host()
+        ev = t.events_host() if t.events else None
+        em = t.emit_host() if self.emit_events else None
+        ck = t.clock_host() if t.clock else None
+        ht = t.hot_host() if t.hot else None
+        for s, p in enumerate(plan):
+            if p is None:
+                continue
+            h, i, reset = p
+            r = self._recs[h]
+            if "lr" in r:
+                self._fill_events(e[s], ev, ht, s, r, i, reset)
+            else:
+                self._fill_frames(e[s], r, i)
+            e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
+            if "sse" in r:                                 # (without ground truth: gt = 0, result = 0 -- no metrics for the slot)
+                e[s]["result"] = r["sse"][i].data_ptr()
+            e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
+            if em is not None:
+                self._fill_emit(em[s], ck[s] if "spans" in r else None, r, i)
+            r["steps"].append(len(self._steps))
+
     @torch.no_grad()
     def step(self):
         """Run one window for every active slot -> False when no recording had a window left."""
         plan = self.sched.plan()
         if plan is None:
             return False
-        from bmc_hip import slots
-        H, W = self._size[:2]
         first = next(self._recs[p[0]] for p in plan if p is not None)
-        b = self._buffers(first["device"])
-        e = b["table"].host()
-        ev = b["table"].events_host() if b["table"].events else None
-        em = b["table"].emit_host() if self.emit_events else None
-        ck = b["table"].clock_host() if b["table"].clock else None
-        ht = b["table"].hot_host() if b["table"].hot else None
-        for s, p in enumerate(plan):
-            if p is None:
-                continue
-            h, i, reset = p
-            r = self._recs[h]
-            if "lr" in r:                                  # event-backed: the entry points at the slot's scratch images
-                e[s]["frames"] = b["lr_scratch"][s].data_ptr()
-                for k, t in zip(("lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps"), r["lr"] + r.get("gt", ())):
-                    ev[k][s] = t.data_ptr()
-                ev["lr_range"][s, :self.seqn] = r["lr_index"][i:i + self.seqn]
-                if "gt" in r:                              # (without: NULL columns, range (0, 0): the scratch is only zero-filled)
-                    e[s]["gt"] = b["gt_scratch"][s].data_ptr()
-                    ev["gt_range"][s] = r["gt_index"][i + 1]
-                if ht is not None:                         # the first window observes items 0 .. seqn-1, a later one item i+seqn-1
-                    ht[s]["active"], ht[s]["first_item"], ht[s]["new_from"] = 1, i, 0 if reset else self.seqn - 1
-                    ht[s]["cmin"][:self.seqn] = r["hot_cmin"][i:i + self.seqn]
-                    ht[s]["hot_pixels"] = r["hot_pixels"].data_ptr() + 4 * i
-                    ht[s]["hot_mask"] = r["hot_mask"].data_ptr()
-            else:
-                e[s]["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
-                if "gts" in r:
-                    e[s]["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * self._size[2] * self._size[3]
-            e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
-            if "sse" in r:                                 # (without ground truth: gt = 0, result = 0 -- no metrics for the slot)
-                e[s]["result"] = r["sse"][i].data_ptr()
-            e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
-            if em is not None:                             # window i appends at index[i] and leaves index[i+1]
-                em[s]["xs"], em[s]["ys"], em[s]["ps"] = r["ev_xs"].data_ptr(), r["ev_ys"].data_ptr(), r["ev_ps"].data_ptr()
-                em[s]["index_in"] = r["ev_index"].data_ptr() + 8 * i
-                em[s]["index_out"] = r["ev_index"].data_ptr() + 8 * (i + 1)
-                em[s]["capacity"] = r["ev_capacity"]
-                if "spans" in r:                           # window i predicts item i+1: its span, float64 times
-                    ck[s]["t_first"], ck[s]["t_last"] = r["spans"][i + 1]
-                    ck[s]["ts"] = r["ev_ts"].data_ptr()
-                elif "ev_ts" in r:
-                    em[s]["ts"] = r["ev_ts"].data_ptr()
-            r["steps"].append(len(self._steps))
+        self._buffers(first["device"])
+        self._fill(plan)
         start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         start.record()
-        b["table"].upload()
+        self._bufs["table"].upload()
         self._calls += 1
         if self.use_graph and self._calls >= 3:
             if self._graph is not None and self._stamp != self._weights_stamp():

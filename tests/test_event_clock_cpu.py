@@ -270,7 +270,7 @@ def test_slots_emit_clocked_refusals():
     from bmc_hip import slots
     pred, parts, scratch = torch.zeros(2, 2, 8, 8), torch.zeros(2, dtype=torch.int32), torch.zeros(8, dtype=torch.uint8)
     with pytest.raises(ValueError, match="no clock entries"):
-        slots.emit_clocked(types.SimpleNamespace(S=2, emit=True, timed=True), pred, 255, 1, parts, scratch, 10)
+        slots.emit_clocked(types.SimpleNamespace(S=2, emit=True, timed=True, clock=False), pred, 255, 1, parts, scratch, 10)
     table = types.SimpleNamespace(S=2, emit=True, timed=True, clock=True)
     with pytest.raises(ValueError, match="no timed emit entries"):
         slots.emit_clocked(types.SimpleNamespace(S=2, emit=True, timed=False, clock=True), pred, 255, 1, parts, scratch, 10)

@@ -124,7 +124,7 @@ def test_slots_emit_refusals():
     parts = torch.zeros(2, dtype=torch.int32)
     with pytest.raises(ValueError, match="no emit entries"):
         slots.emit(types.SimpleNamespace(S=2, emit=False), pred, 255, 1, parts)
-    table = types.SimpleNamespace(S=2, emit=True)
+    table = types.SimpleNamespace(S=2, emit=True, timed=False)
     for bad in (0, 32768, 1.0):
         with pytest.raises(ValueError, match="max_count"):
             slots.emit(table, pred, bad, 1, parts)
@@ -203,9 +203,10 @@ def test_emit_source_has_no_wait_on_global_memory():
     """The property 'no backward branch whose body only polls global memory' is awkward to state on the assembly (the compiler
     rotates and unrolls the loops), so it is stated on the source: the file has no `while` / `do` loop, no volatile or atomic
     access, no fence, and every `for` advances its own induction variable by a constant or a power of two -- every loop is
-    counted, none re-reads a flag that another workgroup would have to write."""
+    counted, none re-reads a flag that another workgroup would have to write.  The file is read with the headers that hold what
+    it shares with slot_emit_timed.hip (slot_k.h, slot_emit_k.h)."""
     from test_isa_hygiene import CSRC
-    src = open(os.path.join(CSRC, "slot_emit.hip")).read()
+    src = "".join(open(os.path.join(CSRC, f)).read() for f in ("slot_k.h", "slot_emit_k.h", "slot_emit.hip"))
     body = re.sub(r"//[^\n]*", "", src)
     assert not re.search(r"\b(while|do|goto|volatile)\b", body)
     assert not re.search(r"atomic|__threadfence|__builtin_amdgcn_fence|__builtin_amdgcn_s_sleep|asm", body)

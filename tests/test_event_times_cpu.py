@@ -271,10 +271,11 @@ def test_timed_emit_kernels_isa(tmp_path):
 def test_timed_emit_source_has_no_wait_and_six_launches():
     """As test_event_output_cpu states it for slot_emit.hip: no `while` / `do` loop, no volatile access, no fence, no inline
     assembly, every `for` advances its own induction variable -- every loop is counted, none polls a flag.  The only atomics are
-    the two LDS histogram increments.  One call launches six kernels (slots.EMIT_TIMED_KERNELS)."""
+    the two LDS histogram increments.  One call launches six kernels (slots.EMIT_TIMED_KERNELS).  The file is read with the
+    headers that hold what it shares with slot_emit.hip (slot_k.h, slot_emit_k.h)."""
     from bmc_hip import slots
     from test_isa_hygiene import CSRC
-    src = open(os.path.join(CSRC, "slot_emit_timed.hip")).read()
+    src = "".join(open(os.path.join(CSRC, f)).read() for f in ("slot_k.h", "slot_emit_k.h", "slot_emit_timed.hip"))
     body = re.sub(r"//[^\n]*", "", src)
     assert not re.search(r"\b(while|do|goto|volatile)\b", body)
     assert not re.search(r"__threadfence|__builtin_amdgcn_fence|__builtin_amdgcn_s_sleep|asm", body)

@@ -79,6 +79,28 @@ def test_recording_without_windows_is_refused():
         SlotScheduler(2).add(0)
 
 
+# ------------------------------------------------------------------ the layout of the slot table (bmc_hip/slots.py)
+def test_table_layout_offsets_and_refusals():
+    """The byte offsets of a table of S = 3 slots, as literals: every section is S entries of its struct behind the one before
+    (40, 192, 48 / 56 timed, 24 and 64 bytes an entry); a section that is off takes no room."""
+    from bmc_hip import slots
+    sections, total = slots.table_layout(3, events=True, emit=True, timed=True, clock=True, hot=True)
+    assert sections == [("slot", slots.SLOT_DTYPE, 0), ("events", slots.SLOT_EVENTS_DTYPE, 120),
+                        ("emit", slots.SLOT_EMIT_TIMED_DTYPE, 696), ("clock", slots.SLOT_CLOCK_DTYPE, 864),
+                        ("hot", slots.SLOT_HOT_DTYPE, 936)] and total == 1128
+    sections, total = slots.table_layout(3, events=True, emit=True)
+    assert sections[2] == ("emit", slots.SLOT_EMIT_DTYPE, 696) and total == 840 and len(sections) == 3
+    sections, total = slots.table_layout(3, events=False, emit=True)
+    assert sections == [("slot", slots.SLOT_DTYPE, 0), ("emit", slots.SLOT_EMIT_DTYPE, 120)] and total == 264
+    assert slots.table_layout(3) == ([("slot", slots.SLOT_DTYPE, 0)], 120)
+    with pytest.raises(ValueError, match="timed=True needs emit=True"):
+        slots.table_layout(3, timed=True)
+    with pytest.raises(ValueError, match="clock=True needs timed=True"):
+        slots.table_layout(3, emit=True, clock=True)
+    with pytest.raises(ValueError, match="hot=True needs events=True"):
+        slots.table_layout(3, hot=True)
+
+
 # ------------------------------------------------------------------ ISA of csrc/slots.hip
 HIPCC = "/opt/rocm/bin/hipcc"
 
