@@ -254,6 +254,38 @@ def events_to_voxel_torch(xs, ys, ts, ps, B, device=None, sensor_size=(180, 240)
     return out
 
 
+def render_event_counts(cnt, round=False):
+    """The pictures of count images: cnt [B,2,h,w] (fp32, on the GPU) -> uint8 [B,h,w,3] on the GPU, image b the array the
+    reference's event_visualisation.plot_event_cnt returns for cnt[b].transpose(1, 2, 0) with its defaults (blue_red on white,
+    normalised by the 1st / 99th percentiles; myutils/vis_events/matplotlib_plot_events.py:125-248), byte for byte -- what
+    infer_BMCNet.py:90-97 hands matplotlib for lr_event_img, hr_bicubic_event_img, hr_esr_event_img and hr_gt_event_img.
+    round=True rounds the counts half-to-even first, as :94 rounds the prediction.  bmc_slot_render on a temporary slot table
+    (include/bmc_hip.h "event-count images" states the contract; 1 <= h * w <= 2^24, finite values)."""
+    from . import slots
+    if not (torch.is_tensor(cnt) and cnt.dim() == 4 and cnt.shape[1] == 2 and cnt.dtype == torch.float32):
+        raise ValueError("render_event_counts: cnt must be an fp32 [B,2,h,w] tensor")
+    B, _, h, w = cnt.shape
+    if not 1 <= h * w <= slots.MAX_RENDER_PIXELS:
+        raise ValueError("render_event_counts: images of 1 .. 2^24 pixels can be rendered (got %d x %d)" % (h, w))
+    if not cnt.is_cuda:
+        raise RuntimeError("render_event_counts: cnt must live on the MI355X (no CPU fallback in this build)")
+    cnt = cnt.contiguous()
+    out = torch.empty(B, h, w, 3, dtype=torch.uint8, device=cnt.device)
+    scratch = torch.empty(4 * min(max(B, 1), slots.MAX_SLOTS), dtype=torch.float32, device=cnt.device)
+    tables = {}
+    for a in range(0, B, slots.MAX_SLOTS):
+        n = min(slots.MAX_SLOTS, B - a)
+        t = tables[n] = tables.get(n) or slots.SlotTable(n, cnt.device, render=1)
+        e = t.host()
+        rn = t.render_host()[0]
+        for s in range(n):
+            e[s]["frames"], e[s]["flags"] = cnt[a + s].data_ptr(), slots.ACTIVE
+            rn[s]["src"], rn[s]["dst"] = cnt[a + s].data_ptr(), out[a + s].data_ptr()
+        t.upload()
+        slots.render(t, 0, h, w, round, scratch)
+    return out
+
+
 def counts_to_events(pred, max_count=255, times=None, spans=None):
     """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
     (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in

@@ -25,7 +25,11 @@ whose slots with a clock entry store float64 times on that clock instead (the sa
 Hot-pixel filter (csrc/slot_hot.hip; include/bmc_hip.h "hot-pixel filter" states the contract): SlotTable(events=True, hot=True)
 adds a table of bmc_slot_hot_t entries (SLOT_HOT_DTYPE) behind the others; hot_update() folds the newly observed items of every
 filtered slot into its counts and writes their masks into the slot's ring (one call = HOT_KERNELS launch for all slots, counted in
-HOT_LAUNCHES), encode_filtered() is encode() storing the LR frames through those masks (counted in ENCODE_LAUNCHES)."""
+HOT_LAUNCHES), encode_filtered() is encode() storing the LR frames through those masks (counted in ENCODE_LAUNCHES).
+
+Event-count images (csrc/slot_render.hip; include/bmc_hip.h "event-count images" states the contract): SlotTable(render=K) adds K
+tables of bmc_slot_render_t entries (SLOT_RENDER_DTYPE: a count image and where its picture goes) behind the others, one per kind
+of image; render() draws table k's images for all slots (one call = RENDER_KERNELS launches, counted in RENDER_LAUNCHES)."""
 import numpy as np
 import torch
 
@@ -67,25 +71,35 @@ assert SLOT_HOT_DTYPE.itemsize == 64
 HOT_LAUNCHES = 0
 HOT_KERNELS = 1                    # launches of one bmc_slot_hot_update call
 HOT_MAX_ITEMS = 1 << 23            # below it distinct counts give distinct float32 rates (the contract's rule 3)
+SLOT_RENDER_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8")])                                                  # bmc_slot_render_t
+assert SLOT_RENDER_DTYPE.itemsize == 16
+RENDER_LAUNCHES = 0
+RENDER_KERNELS = 2                 # launches of one bmc_slot_render call: select, colour
+MAX_RENDER_PIXELS = 1 << 24        # BMC_SLOT_RENDER_MAX_PIXELS: h * w - 1 is exact in float32
+MAX_RENDER_PARTS = 1024
+MAX_RENDER_TABLES = 8
 
 
-def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False):
+def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0):
     """The sections of a slot table of S slots -> ([(name, dtype, byte offset), ...] in their order in memory, total bytes):
     "slot" (bmc_slot_t) always, then "events", "emit" (bmc_slot_emit_timed_t entries with timed=True), "clock" (needs timed) and
-    "hot" (needs events), each S entries behind the one before."""
+    "hot" (needs events), each S entries behind the one before, and "render" (render tables of S entries each)."""
     if timed and not emit:
         raise ValueError("slots: timed=True needs emit=True")
     if clock and not timed:
         raise ValueError("slots: clock=True needs timed=True")
     if hot and not events:
         raise ValueError("slots: hot=True needs events=True")
+    if isinstance(render, bool) or not isinstance(render, int) or not 0 <= render <= MAX_RENDER_TABLES:
+        raise ValueError("slots: render must be a number of tables, 0 .. %d (got %r)" % (MAX_RENDER_TABLES, render))
     sections, nbytes = [], 0
-    for name, dtype, on in (("slot", SLOT_DTYPE, True), ("events", SLOT_EVENTS_DTYPE, events),
-                            ("emit", SLOT_EMIT_TIMED_DTYPE if timed else SLOT_EMIT_DTYPE, emit),
-                            ("clock", SLOT_CLOCK_DTYPE, clock), ("hot", SLOT_HOT_DTYPE, hot)):
-        if on:
+    for name, dtype, count in (("slot", SLOT_DTYPE, 1), ("events", SLOT_EVENTS_DTYPE, int(bool(events))),
+                               ("emit", SLOT_EMIT_TIMED_DTYPE if timed else SLOT_EMIT_DTYPE, int(bool(emit))),
+                               ("clock", SLOT_CLOCK_DTYPE, int(bool(clock))), ("hot", SLOT_HOT_DTYPE, int(bool(hot))),
+                               ("render", SLOT_RENDER_DTYPE, render)):
+        if count:
             sections.append((name, dtype, nbytes))
-            nbytes += S * dtype.itemsize
+            nbytes += count * S * dtype.itemsize
     return sections, nbytes
 
 
@@ -95,17 +109,18 @@ class SlotTable:
     copy that last read it has completed, so the host never waits for the GPU to finish the window before.
     The other sections of table_layout() share the tensor and the copy: `events_host()` / `events_ptr()` (events=True),
     `emit_host()` / `emit_ptr()` (emit=True; timed=True: bmc_slot_emit_timed_t entries), `clock_host()` / `clock_ptr()`
-    (clock=True, needs timed), `hot_host()` / `hot_ptr()` (hot=True, needs events).  The *_host() views are those of the window
-    being filled, after host(), which cleared them."""
+    (clock=True, needs timed), `hot_host()` / `hot_ptr()` (hot=True, needs events), `render_host()` [K,S] / `render_ptr(k)`
+    (render=K tables).  The *_host() views are those of the window being filled, after host(), which cleared them."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False):
+    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False, render=0):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
         self.events, self.emit, self.timed, self.clock, self.hot = bool(events), bool(emit), bool(timed), bool(clock), bool(hot)
-        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot)
+        self.render = render
+        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render)
         self._at = {name: (dtype, off) for name, dtype, off in sections}
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
@@ -138,6 +153,10 @@ class SlotTable:
     def hot_host(self):
         return self._host("hot")
 
+    def render_host(self):
+        dtype, off = self._at["render"]
+        return self._pinned[self._k].numpy()[off:off + self.render * self.S * dtype.itemsize].view(dtype).reshape(self.render, self.S)
+
     def upload(self):
         k = self._k
         self.dev.copy_(self._pinned[k], non_blocking=True)
@@ -159,6 +178,11 @@ class SlotTable:
 
     def hot_ptr(self):
         return self._ptr("hot")
+
+    def render_ptr(self, k):
+        if not 0 <= k < self.render:
+            raise ValueError("slots: the table has %d render tables (got %r)" % (self.render, k))
+        return self._ptr("render") + k * self.S * SLOT_RENDER_DTYPE.itemsize
 
 
 def _check(cond, what):
@@ -336,6 +360,27 @@ def encode_filtered(table, lr_scratch, gt_scratch, ring):
     lib.call(lib._slot_encode_filtered, "bmc_slot_encode_filtered", table.events_ptr(), table.hot_ptr(), ring.data_ptr(), S, seqn,
              H, W, gh, gw, lr_scratch.data_ptr(), gt_scratch.data_ptr(), _stream())
     ENCODE_LAUNCHES += 1
+
+
+def render_parts(h, w):
+    """Workgroups per slot of bmc_slot_render's colour launch for an h x w image (about 4 096 pixels each, at most 1 024)."""
+    return max(1, min(MAX_RENDER_PARTS, -(-h * w // 4096)))
+
+
+def render(table, k, h, w, round, scratch):
+    """Every active slot whose entry in render table k has a src and a dst: dst (uint8 [h,w,3]) <- the picture the reference's
+    plot_event_cnt returns for the count image src (float32 [2,h,w]; round: rounded half-to-even first) -- include/bmc_hip.h
+    "event-count images" states the contract.  Two launches for all slots (bmc_slot_render), deterministic; other slots are not
+    touched.  scratch: float32 GPU tensor of at least 4 * S values (the percentiles)."""
+    global RENDER_LAUNCHES
+    _check(table.render > 0, "the slot table has no render tables (SlotTable(render=K))")
+    _check(all(not isinstance(v, bool) and isinstance(v, (int, np.integer)) and v >= 1 for v in (h, w))
+           and h * w <= MAX_RENDER_PIXELS, "images of 1 .. 2^24 pixels can be rendered (got %r x %r)" % (h, w))
+    _check(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.float32 and scratch.is_contiguous()
+           and scratch.numel() >= 4 * table.S, "scratch must be a contiguous fp32 GPU tensor of at least 4 * S values")
+    lib.call(lib._slot_render, "bmc_slot_render", table.ptr(), table.render_ptr(k), table.S, int(h), int(w), int(bool(round)),
+             render_parts(h, w), scratch.data_ptr(), _stream())
+    RENDER_LAUNCHES += 1
 
 
 def emit_parts(sH, sW):

@@ -282,16 +282,28 @@ class MultiStreamSR:
     graph too) runs before the encode launch, which becomes bmc_slot_encode_filtered.  Recordings opened with open() in the same
     session stay UNFILTERED, and so does every ground truth.  results() then carries hot_pixels (per window, the number of
     pixels masked for the item that window newly observed) and hot_mask ([H,W] uint8 in sensor coordinates, 1 = kept, of the
-    last item observed).  The option needs nothing else switched on."""
+    last item observed).  The option needs nothing else switched on.
 
+    render=(kinds...) from ("lr", "bicubic", "esr", "gt"): the four EVENT-COUNT IMAGES the reference's inference writes per
+    window (infer_BMCNet.py:90-97: lr_event_img, hr_bicubic_event_img, hr_esr_event_img, hr_gt_event_img), rendered on the GPU as
+    the uint8 [h,w,3] arrays its plot_event_cnt returns, byte for byte (bmc_slot_render: two launches per kind for all slots,
+    inside the captured graph too; include/bmc_hip.h "event-count images" states the contract).  lr: frame 1 of the window as
+    the model sees it (H x W; after the hot-pixel filter where one applies); esr: the prediction, resized to the ground truth's
+    size where that differs (bmc_bicubic_resize_fwd, as the metric does) and rounded half-to-even; bicubic: frame 1 resized to
+    the ground truth's size; gt: the window's ground truth.  A recording without ground truth gets lr and esr (at the
+    prediction's size) only.  results() then carries images = {kind: uint8 [done,h,w,3]} on the GPU: 3 bytes per pixel and
+    window instead of the 8 of keep_predictions.  None (the default): no image, no launch."""
+
+    RENDER_KINDS = ("lr", "bicubic", "esr", "gt")
     MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
     MAX_COUNT_TIMED = 255        # event_times: the sort key is a 16-bit rank of j / (n - 1), n <= 255
     MAX_WINDOW_CAPACITY = 1 << 28
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
-                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None):
+                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None):
         from bmc_hip.slots import check_hot_filter
         self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)
+        self.render = self.check_render("MultiStreamSR: ", render)
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
         if seqn < 2:
@@ -323,6 +335,31 @@ class MultiStreamSR:
         self._graph = self._stamp = None
         self._has_events = False
         self._has_clock = False
+
+    @classmethod
+    def check_render(cls, who, render):
+        """render (None, or a tuple / list of distinct kinds from RENDER_KINDS) -> the kinds in RENDER_KINDS' order (() for None);
+        ValueError naming what is wrong."""
+        if render is None:
+            return ()
+        if isinstance(render, str) or not isinstance(render, (tuple, list)) or not render:
+            raise ValueError(who + "render must be None or a non-empty tuple of kinds from %s (got %r)" % (cls.RENDER_KINDS, render))
+        for k in render:
+            if not isinstance(k, str) or k not in cls.RENDER_KINDS:
+                raise ValueError(who + "render has an unknown kind %r (the kinds are %s)" % (k, ", ".join(cls.RENDER_KINDS)))
+        if len(set(render)) != len(render):
+            raise ValueError(who + "render names a kind twice (got %r)" % (render,))
+        return tuple(k for k in cls.RENDER_KINDS if k in render)
+
+    # the render tables of the slot table: "esr" draws from the prediction, "esr_gt" from the prediction resized to the ground truth
+    RENDER_TABLES = ("lr", "esr", "esr_gt", "bicubic", "gt")
+
+    def _render_size(self, kind, has_gt):
+        """(h, w) of a recording's image of `kind`."""
+        H, W = self._size[:2]
+        if kind == "lr":
+            return H, W
+        return tuple(self._size[2:]) if has_gt else (self.scale * H, self.scale * W)
 
     # ---------------------------------------------------------------- recordings
     def _check_capacities(self, who, event_capacity, capacity):
@@ -410,7 +447,7 @@ class MultiStreamSR:
                 self._nparts = slots.emit_parts(self.scale * H, self.scale * W)
             self._size = size
             if len(size) == 4:                             # a running session without ground truth: the metrics launch joins
-                self._grow(self._gt_scratch)
+                self._grow(self._gt_scratch, self._render_buffers)
 
     def _grow(self, *rebuild):
         """The session gains a part (a first event-backed, clocked or ground-truth recording, a larger window capacity).  One
@@ -430,6 +467,12 @@ class MultiStreamSR:
             rec["sse"] = torch.zeros(nwin, slots.metric_parts(*self._size[2:]), 2, dtype=torch.float64, device=device)
         rec.update(n=nwin, steps=[], device=device,
                    keep=torch.empty(nwin, 2, self.scale * H, self.scale * W, device=device) if self.keep_predictions else None)
+        if self.render:                                    # the recording's pictures: without ground truth, lr and esr only
+            has_gt = "sse" in rec
+            if max(h * w for h, w in (self._render_size(k, has_gt) for k in self.render)) > slots.MAX_RENDER_PIXELS:
+                raise ValueError("MultiStreamSR: images of more than 2^24 pixels cannot be rendered (sizes %s)" % (self._size,))
+            rec["images"] = {k: torch.empty((nwin,) + self._render_size(k, has_gt) + (3,), dtype=torch.uint8, device=device)
+                             for k in self.render if has_gt or k in ("lr", "esr")}
         if self.emit_events:                               # the recording's output stream: three columns and the index table
             cap = max(int(event_capacity), 1)
             rec.update(ev_capacity=cap, ev_xs=torch.empty(cap, dtype=torch.int16, device=device),
@@ -561,13 +604,19 @@ class MultiStreamSR:
         data = tuple(data) + ((r["sse"],) if "sse" in r else ()) + (() if r["keep"] is None else (r["keep"],))
         if "hot_pixels" in r:                              # (hot_filter) the per-window mask counts and the last mask
             data = data + (r["hot_pixels"], r["hot_mask"])
+        data = data + tuple(r.get("images", {}).values())  # (render) the pictures
         return sum(t.numel() * t.element_size() for t in data)
 
     def scratch_bytes(self):
         """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened; with
         hot_filter also the slots' counts, mask rings and workspace: 8 + seqn bytes per pixel) and, with event_times, of the
-        sort scratch (0 until a recording has been opened)."""
+        sort scratch (0 until a recording has been opened); with render, the percentiles and, once a recording with ground truth
+        has been opened, the resize scratch [S,2,gh,gw] that bicubic and a resized esr share and the frames [S,2,H,W] it reads."""
         nbytes = 0
+        if self.render and self._size is not None:
+            nbytes += 4 * 4 * self.S
+            if len(self._size) == 4 and self._render_resizes():
+                nbytes += 4 * self.S * 2 * (self._size[2] * self._size[3] + ("bicubic" in self.render) * self._size[0] * self._size[1])
         if self._wcap:
             from bmc_hip import slots
             nbytes = slots.emit_timed_scratch_bytes(self.S, self._nparts, self._wcap)
@@ -587,7 +636,7 @@ class MultiStreamSR:
     def results(self, handle):
         """-> dict(esr_mse=[...], bicubic_mse=[...] (a recording with ground truth only), time=[...] per window done so far[,
         hot_pixels=[...] per window, hot_mask=[H,W] uint8 on the GPU (hot_filter, event-backed recordings)][,
-        predictions=[n,2,sH,sW]][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
+        predictions=[n,2,sH,sW]][, images={kind: uint8 [n,h,w,3] on the GPU} (render)][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
         sr_ts on the GPU, parallel to sr_events (event_times): float32 inside each window, or float64 on the sensor's clock for
         a recording opened with spans / lr_ts]).  Raises RuntimeError when the windows emitted more events than the recording's
         event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity
@@ -606,6 +655,8 @@ class MultiStreamSR:
             out["predictions"] = r["keep"][:done]
         if "hot_pixels" in r:
             out.update(hot_pixels=r["hot_pixels"][:done].tolist(), hot_mask=r["hot_mask"])
+        if self.render:
+            out["images"] = {k: t[:done] for k, t in r["images"].items()}
         if self.emit_events:
             index = r["ev_index"][:done + 1].cpu()
             total = int(index[done])
@@ -638,6 +689,7 @@ class MultiStreamSR:
                 self._sort_buffers(b, device)
             if self._has_events:
                 self._event_buffers(b, device)
+            self._render_buffers(b, device)
             if self.state_dtype is None:
                 b["pool"] = b["feat"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device)       # the model reads the pool
             else:
@@ -651,7 +703,23 @@ class MultiStreamSR:
         from bmc_hip import slots
         b["table"] = slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
                                      timed=self.event_times is not None, clock=self._has_clock,
-                                     hot=self._has_events and self.hot_filter is not None)
+                                     hot=self._has_events and self.hot_filter is not None,
+                                     render=len(self.RENDER_TABLES) if self.render else 0)
+
+    def _render_resizes(self):
+        """Does a session with ground truth resize for its pictures (bicubic always, esr when the sizes differ)?"""
+        H, W = self._size[:2]
+        return "bicubic" in self.render or ("esr" in self.render and tuple(self._size[2:]) != (self.scale * H, self.scale * W))
+
+    def _render_buffers(self, b, device):
+        if not self.render:
+            return
+        H, W = self._size[:2]
+        b["render_minmax"] = torch.zeros(4 * self.S, device=device)
+        if len(self._size) == 4 and self._render_resizes():
+            b["render_resize"] = torch.zeros(self.S, 2, *self._size[2:], device=device)
+            if "bicubic" in self.render:
+                b["render_mid"] = torch.zeros(self.S, 2, H, W, device=device)
 
     def _sort_buffers(self, b, device):
         from bmc_hip import slots
@@ -681,7 +749,7 @@ class MultiStreamSR:
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """[[hot_update ->] encode ->] stage -> model -> commit [-> metrics] [-> emit] (what a graph replay runs)."""
+        """[[hot_update ->] encode ->] stage -> model -> commit [-> metrics] [-> emit] [-> render] (what a graph replay runs)."""
         from bmc_hip import slots
         b = self._bufs
         H, W = self._size[:2]
@@ -702,6 +770,37 @@ class MultiStreamSR:
             emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"], b["emit_scratch"], self._wcap)
         elif self.emit_events:
             slots.emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"])
+        if self.render:
+            self._render_window(out[-1].contiguous())
+
+    def _render_window(self, pred):
+        """The render launches of a window, one pair per table in use: the slots' entries say which of them a slot takes part in.
+        The resize scratch serves the resized prediction first and the resized frame 1 after it."""
+        from bmc_hip import lib, slots
+        from bmc_hip.ops import _stream
+        b = self._bufs
+        t, mm, S = b["table"], b["render_minmax"], self.S
+        H, W = self._size[:2]
+        sH, sW = self.scale * H, self.scale * W
+        at = self.RENDER_TABLES.index
+        if "lr" in self.render:
+            slots.render(t, at("lr"), H, W, False, mm)
+        if "esr" in self.render:                           # b["pred"]: the window's predictions, where commit has put them
+            slots.render(t, at("esr"), sH, sW, True, mm)
+        if len(self._size) == 2:
+            return
+        gh, gw = self._size[2:]
+        if "esr" in self.render and (gh, gw) != (sH, sW):
+            lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", pred.data_ptr(), 2 * S, sH, sW, gh, gw,
+                     b["render_resize"].data_ptr(), _stream())
+            slots.render(t, at("esr_gt"), gh, gw, True, mm)
+        if "bicubic" in self.render:
+            b["render_mid"].copy_(b["x"][:, :, 1])         # frame 1 of every slot's window, as stage gathered it: [S,2,H,W]
+            lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", b["render_mid"].data_ptr(), 2 * S, H, W, gh, gw,
+                     b["render_resize"].data_ptr(), _stream())
+            slots.render(t, at("bicubic"), gh, gw, False, mm)
+        if "gt" in self.render:
+            slots.render(t, at("gt"), gh, gw, False, mm)
 
     def _weights_stamp(self):
         return tuple((id(p), p._version) for p in self.model.parameters())
@@ -761,6 +860,24 @@ class MultiStreamSR:
         elif "ev_ts" in r:
             em["ts"] = r["ev_ts"].data_ptr()
 
+    def _fill_render(self, rn, e, s, r, i):
+        """Entries s of the render tables rn [K,S] for window i of recording r, whose slot entry e has been filled: where each
+        of the recording's pictures reads its count image."""
+        b = self._bufs
+        H, W = self._size[:2]
+        resized = "sse" in r and tuple(self._size[2:]) != (self.scale * H, self.scale * W)
+        for kind, img in r["images"].items():
+            if kind == "lr":                               # frame 1 of the window
+                table, src = "lr", int(e["frames"]) + 4 * 2 * H * W
+            elif kind == "esr":
+                table, src = ("esr_gt", b["render_resize"][s].data_ptr()) if resized else ("esr", b["pred"][s].data_ptr())
+            elif kind == "bicubic":
+                table, src = "bicubic", b["render_resize"][s].data_ptr()
+            else:
+                table, src = "gt", int(e["gt"])
+            k = self.RENDER_TABLES.index(table)
+            rn[k, s]["src"], rn[k, s]["dst"] = src, img[i].data_ptr()
+
     def _fill(self, plan):
         """The table entries of the window `plan`, into the table's host copy."""
         from bmc_hip import slots
@@ -785,6 +902,8 @@ class MultiStreamSR:
             e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
             if em is not None:
                 self._fill_emit(em[s], ck[s] if "spans" in r else None, r, i)
+            if self.render:
+                self._fill_render(t.render_host(), e[s], s, r, i)
             r["steps"].append(len(self._steps))
 
     @torch.no_grad()
@@ -821,7 +940,7 @@ class MultiStreamSR:
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
-                        window_event_capacity=None, hot_filter=None):
+                        window_event_capacity=None, hot_filter=None, render=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
@@ -836,11 +955,13 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                                          the default)][,
       sr_ts       = {name: ts float32}           with event_times="linear": the events' times inside their windows, every
                                          window in time order (window_event_capacity: per recording, None = the default)]).
-    hot_filter: MultiStreamSR's option (the EventRecording items are filtered, frame pairs are not)."""
+      images      = {name: {kind: uint8 [n_windows,h,w,3]}}  with render: the event-count images of every recording]).
+    hot_filter: MultiStreamSR's option (the EventRecording items are filtered, frame pairs are not).  render: MultiStreamSR's
+    option (a tuple of kinds from "lr", "bicubic", "esr", "gt")."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
-                       hot_filter=hot_filter)
+                       hot_filter=hot_filter, render=render)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
@@ -855,7 +976,7 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
     breakdown = {k: {} for k in ("esr_mse", "bicubic_mse", "time", "params")}
-    preds, streams, times = {}, {}, {}
+    preds, streams, times, images = {}, {}, {}, {}
     for name, h in handles:
         r = ms.results(h)
         for k in ("esr_mse", "bicubic_mse", "time"):
@@ -868,6 +989,8 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
             streams[name] = r["sr_events"] + (r["sr_index"],)
         if event_times is not None:
             times[name] = r["sr_ts"]
+        if ms.render:
+            images[name] = r["images"]
     out = {"results": breakdown, "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}}
     if keep_predictions:
         out["predictions"] = preds
@@ -875,4 +998,6 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
         out["sr_events"] = streams
     if event_times is not None:
         out["sr_ts"] = times
+    if ms.render:
+        out["images"] = images
     return out

@@ -680,6 +680,44 @@ int bmc_slot_encode_filtered(const bmc_slot_events_t* table, const bmc_slot_hot_
 int bmc_hot_pixel_mask(float* event_rate, int H, int W, int active, int max_px, float max_rate, float* mask, unsigned* ws,
                        bmc_stream_t s);
 
+/* ---- event-count images of the slots (MultiStreamSR(render=...)) ---------------------------------------------------------
+ * The reference's inference writes four rendered images per window (infer_BMCNet.py:90-97) with
+ * event_visualisation.plot_event_cnt (myutils/vis_events/matplotlib_plot_events.py:125-248), called with its defaults
+ * (color_scheme="blue_red", use_opencv=False, is_black_background=False, is_norm=True).
+ * THE CONTRACT is the uint8 [h][w][3] array that function RETURNS for a float32 count image cnt [2][h][w] (channel 0 positive,
+ * 1 negative); the PNG matplotlib then draws from it at 300 dpi is not part of it.  N = h * w:
+ *   1. Percentiles.  Per channel c: min_c = np.percentile(cnt[c], 1), max_c = np.percentile(cnt[c], 99), as NumPy 2.x computes
+ *      them for a FLOAT32 array (method "linear"): q = float32(1) / float32(100) resp. float32(99) / float32(100); the virtual
+ *      index vi = float32(N - 1) * q, ONE float32 product (not float64: np.percentile divides by the array's own float32(100),
+ *      and a 0-d float32 array times a Python int stays float32); k = floor(vi), gamma = vi - k (exact), the neighbours are the
+ *      order statistics k and k + 1 (both N - 1 when vi >= N - 1, i.e. N = 1) of the sorted channel; the result is NumPy's lerp
+ *      in float32, every operation rounded on its own:  d = b - a;  gamma >= 0.5 ?  b - d * (1 - gamma)  :  a + d * gamma.
+ *      mx = max_0 > max_1 ? max_0 : max_1.
+ *   2. Normalisation.  Per channel: if min_c != mx then v = (v - min_c) / (mx - min_c) in float32 (the division correctly
+ *      rounded, no fused multiply-add); otherwise the channel is left AS IT IS (the reference's quirk).  Then clip to [0, 1].
+ *   3. Colour.  p, n = the two clipped channels.  p > 0 and (n == 0 or p >= n): (c0, c1, c2) = (1, 1 - p, 1 - p); else n > 0:
+ *      (1 - n, 1 - n, 1); else (1, 1, 1).  1 - p is a float32 difference; byte = trunc((double)c * 255.0).  The BGR -> RGB
+ *      conversion reverses the triple: out[y][x] = (byte(c2), byte(c1), byte(c0)) -- positive counts come out blue, negative red.
+ *   `round` != 0: every value is first rounded half-to-even (rintf), as infer_BMCNet.py:94 rounds the prediction.
+ *   A -0.0 is treated as +0.0 (it cannot change a byte).  Non-finite inputs are OUTSIDE the contract: the call is safe for them
+ *   and its bytes are unspecified.  Limits: 1 <= h * w <= BMC_SLOT_RENDER_MAX_PIXELS = 2^24 (N - 1 exact in float32).
+ * A DEVICE table of S entries, parallel to the slot table: src NULL, dst NULL or an inactive slot: nothing of the slot is read or
+ * written.  dst needs no alignment (a 4-byte aligned dst is stored in 32-bit words). */
+#define BMC_SLOT_RENDER_MAX_PIXELS (1 << 24)
+#define BMC_SLOT_RENDER_MAX_PARTS 1024
+typedef struct bmc_slot_render {
+    const float* src;           /* the count image [2][h][w] */
+    unsigned char* dst;         /* the rendered image [h][w][3] */
+} bmc_slot_render_t;
+/* TWO launches for all slots (csrc/slot_render.hip).  select, grid (2, S): one workgroup per (channel, slot) finds the four order
+ * statistics of rule 1 exactly, by an 8-bit radix select over order-preserving 32-bit keys of the values (four passes over the
+ * plane, one 256-bin LDS histogram per tracked rank, integer LDS atomics), and writes (min_c, max_c) to scratch.  colour, grid
+ * (nparts, S), 1 <= nparts <= BMC_SLOT_RENDER_MAX_PARTS: rules 2 and 3, four pixels per lane.  scratch: 4 * S floats.  No float
+ * atomics, no global atomics, no dependence on other slots, no workgroup waits for another: the same bytes run after run,
+ * capturable in a graph. */
+int bmc_slot_render(const bmc_slot_t* table, const bmc_slot_render_t* render, int S, int h, int w, int round, int nparts,
+                    float* scratch, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

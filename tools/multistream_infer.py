@@ -17,12 +17,18 @@ stamps (microseconds around 1e9, one frame every 33 333 us): float64 times on th
 (hot_filter=dict(max_px=100, min_obvs=5, max_rate=0.8), the reference's defaults) and off, --runs alternating runs each in this
 process (windows/s: the median, and every run), and the bmc_slot_hot_update call alone (events around 20 calls on the session's
 last table).
+--render DIR [--render-kinds lr,bicubic,esr,gt] adds, per configuration, the frame-backed session with the event-count images on
+(render=kinds): its latency and windows/s, one bmc_slot_render call alone per kind (both kernels, events around 20 calls on the
+session's last table), and writes the images of the first such session as DIR/<recording>/event_img/<kind dir>/%09d.png with the
+reference's directory names (lr_event_img, hr_bicubic_event_img, hr_esr_event_img, hr_gt_event_img).  A file holds the rendered
+array itself, one pixel per element; the reference's files are the same array resampled by matplotlib at 300 dpi.
 --resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
                                   [--hot-filter] [--runs 3]
-                                  [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]"""
+                                  [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
+                                  [--render DIR] [--render-kinds lr,bicubic,esr,gt]"""
 import argparse
 import json
 import os
@@ -116,6 +122,48 @@ def emit_alone(ms, reps=20):
     return a.elapsed_time(z) / reps
 
 
+RENDER_DIRS = {"lr": "lr_event_img", "bicubic": "hr_bicubic_event_img", "esr": "hr_esr_event_img", "gt": "hr_gt_event_img"}
+
+
+def render_alone(ms, reps=20):
+    """{table: ms per bmc_slot_render call (select + colour)} on the session's buffers, for every render table the session's
+    last window drew (the table and count images of that window; the repeated calls redraw the same pictures)."""
+    from bmc_hip import slots
+    b = ms._bufs
+    H, W = ms._size[:2]
+    sizes = {"lr": (H, W), "esr": (ms.scale * H, ms.scale * W)}
+    if len(ms._size) == 4:
+        sizes.update({k: tuple(ms._size[2:]) for k in ("esr_gt", "bicubic", "gt")})
+        if sizes["esr"] != sizes["gt"]:
+            del sizes["esr"]                               # (every recording of the benchmark has a ground truth)
+        else:
+            del sizes["esr_gt"]
+    out = {}
+    for k, name in enumerate(ms.RENDER_TABLES):
+        if name not in sizes or name.split("_")[0] not in ms.render:
+            continue
+        args = (b["table"], k) + sizes[name] + (name.startswith("esr"), b["render_minmax"])
+        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        slots.render(*args)
+        a.record()
+        for _ in range(reps):
+            slots.render(*args)
+        z.record()
+        z.synchronize()
+        out[name] = a.elapsed_time(z) / reps
+    return out
+
+
+def write_images(root, name, images):
+    """images {kind: uint8 [n,h,w,3]} of recording `name` -> root/name/event_img/<kind dir>/%09d.png (PIL): the arrays themselves."""
+    from PIL import Image
+    for kind, t in images.items():
+        d = os.path.join(root, name, "event_img", RENDER_DIRS[kind])
+        os.makedirs(d, exist_ok=True)
+        for i, img in enumerate(t.cpu().numpy()):
+            Image.fromarray(img, "RGB").save(os.path.join(d, "%09d.png" % i))
+
+
 def sensor_spans(L, k):
     """Synthetic monotone float64 stamps of recording k: microseconds around 1e9, frame j spans [33 333 j, 33 333 j + 33 332]."""
     import numpy as np
@@ -124,9 +172,9 @@ def sensor_spans(L, k):
 
 
 def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False,
-                hot_filter=None):
+                hot_filter=None, render=None, render_dir=None):
     ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times,
-                       hot_filter=hot_filter)
+                       hot_filter=hot_filter, render=render)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
@@ -147,6 +195,11 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
         dense = MultiStreamSR(m, S, n_c=128, scale=4, seqn=SEQN, keep_predictions=True)
         return (lat, S * windows / wall, emit_alone(ms), int(index[-1] - index[-2]), ms.resident_bytes(hs[0]),
                 dense.resident_bytes(dense.open(*recs[0])))
+    if render:
+        if render_dir:
+            for k, h in enumerate(hs):
+                write_images(render_dir, "rec%03d" % k, ms.results(h)["images"])
+        return lat, S * windows / wall, render_alone(ms), ms.resident_bytes(hs[0])
     if hot_filter is not None:
         return lat, S * windows / wall, hot_update_alone(ms), ms.resident_bytes(hs[0])
     if events:
@@ -154,7 +207,7 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
     return lat, S * windows / wall, ms.resident_bytes(hs[0])
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="31x56,45x80,180x240")
     ap.add_argument("--slots", default="1,8,32")
@@ -173,13 +226,32 @@ def main():
     ap.add_argument("--resident-windows", type=int, default=0)
     ap.add_argument("--modes", default="eager,graph")
     ap.add_argument("--out", default=None)
-    a = ap.parse_args()
+    ap.add_argument("--render", metavar="DIR", default=None,
+                    help="adds the session with the event-count images on and writes them as DIR/<recording>/event_img/<kind dir>/"
+                         "%%09d.png: the rendered arrays themselves (the reference's files are the same arrays resampled by "
+                         "matplotlib at 300 dpi)")
+    ap.add_argument("--render-kinds", default=None,
+                    help="with --render: the kinds, a comma-separated choice of lr,bicubic,esr,gt (default: all four)")
+    a = ap.parse_args(argv)
+    if a.render_kinds is not None and a.render is None:
+        ap.error("--render-kinds needs --render DIR")
+    if a.render is not None:
+        try:
+            a.render_kinds = MultiStreamSR.check_render("--render-kinds: ", tuple(("lr,bicubic,esr,gt" if a.render_kinds is None else a.render_kinds).split(",")))
+        except ValueError as e:
+            ap.error(str(e))
     if a.sensor_clock:
         a.emit_events = a.event_times = True
     if a.hot_filter:
         a.events = True
     if a.event_times and not a.emit_events:
         ap.error("--event-times needs --emit-events")
+    return a
+
+
+def main():
+    a = parse_args()
+    render_dir = a.render
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     m = BMCNet(4, 128, 5).to(dev)
@@ -234,6 +306,15 @@ def main():
                                      windows_per_s_filter_off_runs=[round(r[1], 1) for r in off],
                                      hot_update_alone_ms=round(upd, 4), hot_update_share=round(upd / lat, 4),
                                      resident_bytes=on[-1][3]))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.render is not None:
+                    lat, wps, alone, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, render=a.render_kinds,
+                                                          render_dir=render_dir)
+                    render_dir = None                      # (the first such session's images are the ones written)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(render)", slots=S, kinds=list(a.render_kinds),
+                                     ms_per_window=round(lat, 3), windows_per_s=round(wps, 1),
+                                     render_ms={k: round(v, 4) for k, v in alone.items()},
+                                     render_share=round(sum(alone.values()) / lat, 4), resident_bytes=nbytes))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.no_gt:
                     lat, wps, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, no_gt=True)
