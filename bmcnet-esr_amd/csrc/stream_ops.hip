@@ -92,7 +92,16 @@ __global__ void ln_fwd_kernel(const float* __restrict__ x, const float* __restri
         float s = v[0] + v[1] + v[2] + v[3];
 #pragma unroll
         for (int m = 1; m < LPP; m <<= 1) s += __shfl_xor(s, m);
-        const float mu = s * (1.f / C);
+        // mean in two steps: s * (1/C) is off by an ulp or two (1/C is inexact when C is no power of two), and on a row of
+        // (nearly) equal values rstd ~ 1/sqrt(eps) multiplies that error into y; the mean of the residuals takes it back
+        // (a constant row gets mean == its value and d == 0 exactly)
+        const float mu0 = s * (1.f / C);
+        float e = 0.f;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) e += act ? v[k] - mu0 : 0.f;
+#pragma unroll
+        for (int m = 1; m < LPP; m <<= 1) e += __shfl_xor(e, m);
+        const float mu = mu0 + e * (1.f / C);
         f32x4 d;
         float q = 0.f;
 #pragma unroll
@@ -160,12 +169,21 @@ __global__ void ln_bwd_kernel(const float* __restrict__ dy, const float* __restr
 #pragma unroll
     for (int k = 0; k < 4; ++k) { red[0][threadIdx.x * 4 + k] = dg[k]; red[1][threadIdx.x * 4 + k] = db[k]; }
     __syncthreads();
-    if (threadIdx.x < C) {
-        const int c = threadIdx.x, s = c >> 2, k = c & 3;
-        float a = 0.f, b = 0.f;
-        for (int t = s; t < (int)blockDim.x; t += LPP) { a += red[0][t * 4 + k]; b += red[1][t * 4 + k]; }
-        ws[((long long)blockIdx.x * 2 + 0) * C + c] = a;
-        ws[((long long)blockIdx.x * 2 + 1) * C + c] = b;
+    // pairwise tree over the 256 / LPP lanes that own the same float4 of the row (thread t and t + w own the same one for every
+    // w that is a multiple of LPP): fixed order, and log2 instead of 256 / LPP roundings on the way to a block's partial sum
+    for (int w = 128; w >= LPP; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                red[0][threadIdx.x * 4 + k] += red[0][(threadIdx.x + w) * 4 + k];
+                red[1][threadIdx.x * 4 + k] += red[1][(threadIdx.x + w) * 4 + k];
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < C) {      // thread t < LPP now holds channels 4t .. 4t+3 at red[.][4t + k]: channel c at red[.][c]
+        ws[((long long)blockIdx.x * 2 + 0) * C + threadIdx.x] = red[0][threadIdx.x];
+        ws[((long long)blockIdx.x * 2 + 1) * C + threadIdx.x] = red[1][threadIdx.x];
     }
 }
 // grid = 2*C blocks (dgamma channels then dbeta channels), same fixed-order reduction as colsum_stage2
@@ -462,6 +480,7 @@ static int ln_lpp(int C) {
 
 extern "C" int bmc_layernorm_fwd(const float* x, const float* gamma, const float* beta, long long npix, int C, float eps,
                                  float* y, float* stats, bmc_stream_t s) {
+    BMC_CHECK_ARG(x && gamma && beta && y && stats && npix >= 0, "bmc_layernorm_fwd: bad arguments");
     hipStream_t st = (hipStream_t)s;
     dim3 grid(nblocks(npix * ln_lpp(C), 256 * 4));
     LN_DISPATCH(ln_fwd_kernel, x, gamma, beta, npix, C, eps, y, stats);
@@ -471,6 +490,7 @@ extern "C" int bmc_layernorm_fwd(const float* x, const float* gamma, const float
 
 extern "C" int bmc_layernorm_bwd(const float* dy, const float* x, const float* stats, const float* gamma, long long npix,
                                  int C, float* dx, float* ws, float* dgamma, float* dbeta, int accumulate, bmc_stream_t s) {
+    BMC_CHECK_ARG(dy && x && stats && gamma && dx && ws && dgamma && dbeta && npix >= 0, "bmc_layernorm_bwd: bad arguments");
     hipStream_t st = (hipStream_t)s;
     int nb = nblocks(npix * ln_lpp(C), 256 * 4);
     if (nb > 1024) nb = 1024;
@@ -482,12 +502,14 @@ extern "C" int bmc_layernorm_bwd(const float* dy, const float* x, const float* s
 }
 
 extern "C" int bmc_softmax_fwd(const float* a, long long rows, int C, float* p, bmc_stream_t s) {
+    BMC_CHECK_ARG(a && p && rows >= 0 && C >= 1, "bmc_softmax_fwd: bad arguments");
     hipLaunchKernelGGL(softmax_fwd_kernel, dim3(nblocks(rows, 4)), dim3(256), 0, (hipStream_t)s, a, rows, C, p);
     BMC_CHECK_LAUNCH("bmc_softmax_fwd");
     return 0;
 }
 extern "C" int bmc_softmax_bwd(const float* p, const float* dp, long long rows, int C, float scale_out, float* da,
                                bmc_stream_t s) {
+    BMC_CHECK_ARG(p && dp && da && rows >= 0 && C >= 1, "bmc_softmax_bwd: bad arguments");
     hipLaunchKernelGGL(softmax_bwd_kernel, dim3(nblocks(rows, 4)), dim3(256), 0, (hipStream_t)s, p, dp, rows, C, scale_out, da);
     BMC_CHECK_LAUNCH("bmc_softmax_bwd");
     return 0;
