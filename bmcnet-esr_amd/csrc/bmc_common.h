@@ -21,6 +21,9 @@ __device__ __forceinline__ void stg16(void* p, f32x4 v) {
     *(__attribute__((address_space(1))) f32x4*)(unsigned long long)p = v;
 }
 
+// 16 zero bytes: what out-of-image lanes of a halo load read instead of a pixel (no branch, nothing to fix up afterwards)
+static __device__ __attribute__((aligned(16))) const float g_zero4[4] = {0.f, 0.f, 0.f, 0.f};
+
 void bmc_set_error(const char* fmt, ...);
 
 #define BMC_CHECK_ARG(cond, ...)          \
@@ -60,6 +63,14 @@ static inline SrcDev to_dev(const bmc_src_t& s) {
     d.batch_shift = s.batch_shift; d.batch_mod = s.batch_mod == BMC_SRC_TABLE ? BMC_SRC_TABLE : (s.batch_mod < 1 ? 1 : s.batch_mod);
     return d;
 }
+// Kernel prologue: the launch's source descriptors into the LDS table the loaders index at run time (indexing the by-value
+// kernel argument would make the compiler keep a copy of it in scratch memory).  The caller's barrier publishes it.
+// A macro on purpose: handed to a function by address, the argument block is loaded whole at the kernel's entry instead of
+// field by field where it is used, and the scalar registers that holds cost five of the seven kernels spills
+// (conv_kernel<9,128,8>: 50 -> 85 spilled SGPRs).
+#define BMC_LOAD_SRC_TABLE(tab, a, tid)                                  \
+    _Pragma("unroll") for (int i_ = 0; i_ < BMC_MAX_SRC; ++i_)           \
+        if ((tid) == i_) (tab)[i_] = (a).src[i_]
 __device__ __forceinline__ const float* src_batch_ptr(const SrcDev& s, int b) {
     int bs = b + s.batch_shift;
     if (s.batch_mod > 0) bs %= s.batch_mod;

@@ -28,6 +28,7 @@
 // LayerNorm affine gradients follow algebraically from its results (bmc_chain_affine_grads below).
 #include "bmc_common.h"
 #include "dma_ring.h"
+#include "tile_walk.h"
 
 namespace {
 
@@ -79,8 +80,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     float* const Wb = lds + NXR * XSLOT;
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + NXR * XSLOT + NWR * WSLOT);
     float* const img = lds + NXR * XSLOT + NWR * WSLOT + 2 * 8;     // [0] b_f | 0   [1] b_c | 0   [2] gamma   [3] beta   [4] zeros
-    const unsigned xb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Xb;
-    const unsigned wb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Wb;
+    const unsigned xb_lds = lds_addr(Xb), wb_lds = lds_addr(Wb);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lp = lane & 15, lg = lane >> 4;     // pixel of the wave's row / channel quad: D rows 4*lg .. 4*lg+3
@@ -91,27 +91,13 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     }
     __syncthreads();
 
-    // ---- persistent walk over units, XCD-contiguous ranges (as conv.hip)
-    const int nunits = a.nunits;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && nunits >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)nunits * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)nunits * (xcd + 1) / NX_) : nunits;
-    const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
-    const int t_stride = xcd_map ? per_x : (int)gridDim.x;
-    const int my_units = t_first < t_hi ? (t_hi - t_first + t_stride - 1) / t_stride : 0;
+    const TileWalk tw = tile_walk(a.nunits);      // persistent workgroups; a unit = one 8 x 16 pixel tile, all channels
+    const int t_first = tw.first, t_hi = tw.hi, t_stride = tw.stride, my_units = tw.count;
     if (my_units == 0) return;
     const int total_steps = my_units * NS, total_xchunks = my_units * NXC;
 
-    struct UnitIt { int tx, ty, b; };
-    auto decode = [&](int t) {
-        UnitIt it;
-        it.tx = t % a.tiles_x; t /= a.tiles_x;
-        it.ty = t % a.tiles_y;
-        it.b = t / a.tiles_y;
-        return it;
-    };
+    using UnitIt = Tile3;         // (no channel tiles: nt = 0)
+    auto decode = [&](int t) { return tile_decode(t, 1, a.tiles_x, a.tiles_y); };
 
     // ---- X ring loader (waves 0-1): chunks of 16 channels in consumption order; a unit has two segments of C channels
     //      (fwd: s0 then s1 at batch b; bwd: dcentre at batch b then at batch b + n).  Instruction i of X wave w covers the
@@ -212,11 +198,6 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
             if (wl_cnt - (gs + 1) >= DW) dma_wait<NDW * (DW - 1)>(); else dma_wait<0>();
         }
     };
-    auto publish = [&]() {      // raw barrier: no vmcnt(0) drain of the rings' prefetch (a __syncthreads() would)
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-    };
 
     // Two steps whose pixel operand comes from LDS (chunks xc, xc + 1), fragment sets A then B.  next_lds: the step after
     // the pair also reads an X chunk.  (LDS phases always have an even number of steps: NR is even for C >= 32.)
@@ -230,7 +211,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
             const bool has_next = gs + 1 < total_steps;
             const bool nl = h == 0 || next_lds;
             loader(true);
-            publish();                      // stage gs + 1 (and chunk xc + 1) is in LDS for everybody
+            ring_publish();                      // stage gs + 1 (and chunk xc + 1) is in LDS for everybody
             if (has_next) {
                 read_b(Wb + ((gs + 1) % NWR) * WSLOT, bfn);
                 if (nl) read_a(Xb + ((xc + 1) % NXR) * XSLOT, afn);
@@ -258,7 +239,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
             const bool has_next = gs + 1 < total_steps;
             const bool nl = (c == NR - 1) && next_lds;
             loader(false);
-            publish();
+            ring_publish();
             if (has_next) {
                 read_b(Wb + ((gs + 1) % NWR) * WSLOT, bfn);
                 if (nl) read_a(Xb + (xc % NXR) * XSLOT, afn);
@@ -305,7 +286,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         for (int k = 0; k < DW && wl_cnt < total_steps; ++k) issue_w();
     }
     dma_wait<0>();
-    publish();
+    ring_publish();
     read_a(Xb, afA);
     read_b(Wb, bfA);
     init_acc(Ra, BWD ? 4 : 0);

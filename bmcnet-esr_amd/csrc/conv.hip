@@ -15,6 +15,8 @@
 // product does not care about.
 #include "bmc_common.h"
 #include "conv_k.h"
+#include "dma_ring.h"
+#include "tile_walk.h"
 #include <stdlib.h>
 
 namespace {
@@ -22,8 +24,6 @@ namespace {
 constexpr int CK = BMC_CK;  // channels per chunk
 constexpr int RS = 20;      // LDS row stride in floats (16 + 4 pad: conflict-free ds_read_b128)
 constexpr int TW = 16;      // tile width; the tile height TH (8 or 4 rows) is a kernel template parameter
-__device__ __attribute__((aligned(16))) const float g_zero4[4] = {0.f, 0.f, 0.f, 0.f};   // source of out-of-image lanes
-
 
 // Tile shapes (4 waves): BN = 128: waves 2(px) x 2(ch), wave = (TH/2 rows x 16) px x 64 ch  [TH = 8: 2x2 MFMA tiles, TH = 4: 1x2]
 //                        BN =  64: waves 2 x 2,           wave = (TH/2 rows x 16) px x 32 ch  [small problems: 4x the workgroups]
@@ -47,31 +47,22 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
     float* const Xb = lds;
     float* const Wb = lds + 2 * XBUF;
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 2 * XBUF + 2 * WBUF);   // source table (runtime-indexed)
-    // Accumulator start values: the bias when it is the same for every tile of the launch (one weight group, one
-    // channel tile -- the usual case), zeros otherwise.  A tile's accumulators are (re)initialised with 16 LDS reads
-    // straight into the accumulator registers: that replaces 64 v_mov + 64 bias adds + the bias loads of the epilogue,
-    // and VALU instructions issued beside the other workgroups' MFMAs cost 20-30 cycles each (in-kernel stamps).
-    float* const init_lds = lds + 2 * XBUF + 2 * WBUF + BMC_MAX_SRC * 8;
-    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    float* const init_lds = lds + 2 * XBUF + 2 * WBUF + BMC_MAX_SRC * 8;     // accumulator start values (bias or zeros: bias_start_values, conv_k.h)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, lh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
+    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     if (tid < BN) init_lds[tid] = (bias_pre && tid < a.Cout) ? a.bias[tid] : 0.f;
     __syncthreads();
-    // Persistent workgroup: tiles blockIdx.x, blockIdx.x + gridDim.x, ... ; the load pipeline runs ahead of the
-    // MFMA pipeline across tile boundaries, so only the very first tile of a workgroup pays load latency.
-    // XCD-aware tile walk: workgroups are dealt round-robin over the 8 XCDs (blockIdx % 8 shares an L2), so give each
-    // XCD one contiguous eighth of the tile list and let its workgroups sweep it side by side -- neighbouring tiles
-    // (shared halo rows/columns) then meet in the same L2 while hot.  Speed only; any placement is correct.
+    // tile_walk() of tile_walk.h, written out, like bias_start_values() (conv_k.h) above: with the calls this kernel's
+    // scalar registers are allocated differently (up to 5 more of them spilled, other v_readlane / v_writelane counts),
+    // with the same code in place they are not.
     const int ntiles = a.ntiles;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && ntiles >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NX_) : ntiles;
+    const bool xcd_map = (gridDim.x % NUM_XCD) == 0 && ntiles >= (int)gridDim.x;
+    const int xcd = blockIdx.x % NUM_XCD, xj = blockIdx.x / NUM_XCD, per_x = gridDim.x / NUM_XCD;
+    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NUM_XCD) : 0;
+    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NUM_XCD) : ntiles;
     const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
     const int t_stride = xcd_map ? per_x : (int)gridDim.x;
     const int my_tiles = t_first < t_hi ? (t_hi - t_first + t_stride - 1) / t_stride : 0;
@@ -80,36 +71,10 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
     if (my_tiles == 0) return;   // block-uniform
     const long long wstep = (long long)a.Coutpad * CK;
 
-    // Tile index -> (channel tile, tile column, tile row, image) is a mixed-radix decode = three integer divisions, ~100
-    // VALU instructions that three users (X loader, W loader, epilogue) would pay per tile beside the MFMAs.  A
-    // workgroup visits t_first, t_first + t_stride, ...: decode once, then advance digit-wise with carries.
-    struct TileIt { int nt, tx, ty, b; };
-    TileIt it0;
-    {
-        int t = t_first;
-        it0.nt = t % a.ntn; t /= a.ntn;
-        it0.tx = t % a.tiles_x; t /= a.tiles_x;
-        it0.ty = t % a.tiles_y;
-        it0.b = t / a.tiles_y;
-    }
-    int d_nt, d_tx, d_ty, d_b;
-    {
-        int t = t_stride;
-        d_nt = t % a.ntn; t /= a.ntn;
-        d_tx = t % a.tiles_x; t /= a.tiles_x;
-        d_ty = t % a.tiles_y;
-        d_b = t / a.tiles_y;
-    }
-    auto it_next = [&](TileIt& it) {
-        it.nt += d_nt;
-        int c = 0;
-        if (it.nt >= a.ntn) { it.nt -= a.ntn; c = 1; }
-        it.tx += d_tx + c; c = 0;
-        if (it.tx >= a.tiles_x) { it.tx -= a.tiles_x; c = 1; }
-        it.ty += d_ty + c; c = 0;
-        if (it.ty >= a.tiles_y) { it.ty -= a.tiles_y; c = 1; }
-        it.b += d_b + c;
-    };
+    // the three users of a tile's coordinates (X loader, W loader, epilogue) each walk their own copy of the digits
+    using TileIt = Tile3;
+    const TileIt it0 = tile_decode(t_first, a.ntn, a.tiles_x, a.tiles_y), stp = tile_decode(t_stride, a.ntn, a.tiles_x, a.tiles_y);
+    auto it_next = [&](TileIt& it) { it = tile_advance(it, stp, a.ntn, a.tiles_x, a.tiles_y); };
     TileIt xl_it = it0, wl_it = it0, ep_it = it0;
     const int q4 = (tid & 3) * 4;
 
@@ -425,7 +390,7 @@ __global__ __launch_bounds__(256, (BN == 128 && TH == 8) ? 3 : 4) void conv_kern
             // every load in flight (the next slice, issued half a step ago; the next halo, eight steps ago) lands BEFORE the
             // stores go out: vmcnt counts stores too and completes in order, so the compiler's wait in front of the next
             // step's slice store would otherwise sit out the round trip of this tile's 16 stores (-0.9 %)
-            __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8));
+            dma_wait<0>();
             epilogue(tile);
         }
     }

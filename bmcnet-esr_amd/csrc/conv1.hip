@@ -13,6 +13,7 @@
 #include "bmc_common.h"
 #include "conv_k.h"
 #include "dma_ring.h"
+#include "tile_walk.h"
 #include <stdlib.h>
 
 namespace {
@@ -32,41 +33,22 @@ __global__ __launch_bounds__(256, 2) void conv1_kernel(const ConvK a) {
     float* const Wb = lds + NXR * XSLOT;
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + NXR * XSLOT + NWR * WSLOT);
     float* const init_lds = lds + NXR * XSLOT + NWR * WSLOT + BMC_MAX_SRC * 8;     // accumulator start values (bias or zeros)
-    const unsigned xb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Xb;
-    const unsigned wb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Wb;
-    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    const unsigned xb_lds = lds_addr(Xb), wb_lds = lds_addr(Wb);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lp = lane & 15, lg = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
-    if (tid < BN) init_lds[tid] = (bias_pre && tid < a.Cout) ? a.bias[tid] : 0.f;
+    const bool bias_pre = bias_start_values(init_lds, a, BN, tid);
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     __syncthreads();
 
-    // ---- persistent walk over tiles, XCD-contiguous ranges (as conv.hip)
-    const int ntiles = a.ntiles;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && ntiles >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NX_) : ntiles;
-    const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
-    const int t_stride = xcd_map ? per_x : (int)gridDim.x;
-    const int my_tiles = t_first < t_hi ? (t_hi - t_first + t_stride - 1) / t_stride : 0;
+    const TileWalk tw = tile_walk(a.ntiles);      // persistent workgroups
+    const int t_first = tw.first, t_hi = tw.hi, t_stride = tw.stride, my_tiles = tw.count;
     if (my_tiles == 0) return;
     const int nsteps = a.nchunks;                 // steps (= X chunks = weight slices) per tile
     const int total_steps = my_tiles * nsteps;
 
-    struct TileIt { int nt, tx, ty, b; };
-    auto decode = [&](int t) {
-        TileIt it;
-        it.nt = t % a.ntn; t /= a.ntn;
-        it.tx = t % a.tiles_x; t /= a.tiles_x;
-        it.ty = t % a.tiles_y;
-        it.b = t / a.tiles_y;
-        return it;
-    };
+    using TileIt = Tile3;
+    auto decode = [&](int t) { return tile_decode(t, a.ntn, a.tiles_x, a.tiles_y); };
 
     // ---- X ring loader (waves 0-1): the tile's 16-channel chunks, source after source.  Instruction i of X wave w covers
     //      tile row NDX w + i (16 pixels, 4 lanes per pixel row); lane (pixel p, position q') fetches quad q' ^ swz(p).

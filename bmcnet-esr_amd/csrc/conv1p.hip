@@ -17,6 +17,7 @@
 #include "bmc_common.h"
 #include "conv_k.h"
 #include "dma_ring.h"
+#include "tile_walk.h"
 #include <stdlib.h>
 
 namespace {
@@ -32,45 +33,23 @@ __global__ __launch_bounds__(512, (NCH == 8 && DEPTH == 1) ? 4 : 2) void conv1p_
     constexpr int NS = DEPTH + 1;
     __shared__ __attribute__((aligned(16))) float lds[NS * SLOT + BMC_MAX_SRC * 8];
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + NS * SLOT);
-    const unsigned x_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)lds;
+    const unsigned x_lds = lds_addr(lds);
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     __syncthreads();
 
-    // ---- persistent walk over tiles, XCD-contiguous ranges (as conv.hip); tile = (image b, 64-pixel run pt, channel tile nt)
+    // ---- persistent walk over tiles; tile = (image b, 64-pixel run pt, channel tile nt)
     const int HW = a.H * a.W;
     const int tpi = (HW + PX - 1) / PX;                          // pixel tiles per image
-    const int ntiles = a.ntiles;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && ntiles >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NX_) : ntiles;
-    const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
-    const int t_stride = xcd_map ? per_x : (int)gridDim.x;
+    const TileWalk tw = tile_walk(a.ntiles);
+    const int t_first = tw.first, t_hi = tw.hi, t_stride = tw.stride;
     if (t_first >= t_hi) return;
-    struct TileIt { int nt, pt, b; };
-    auto decode = [&](int t) {
-        TileIt it;
-        it.nt = t % a.ntn; t /= a.ntn;
-        it.pt = t % tpi;
-        it.b = t / tpi;
-        return it;
-    };
-    // tiles are visited t_first, t_first + t_stride, ...: (nt, pt, b) advance by the digits of t_stride with carries -- integer
-    // divisions (~40 VALU instructions each) stay out of the tile loop: they cost 1.6 us per tile when they were in it
+    // (the divisions of a decode cost 1.6 us per tile when they were in the tile loop)
+    using TileIt = Tile2;
+    auto decode = [&](int t) { return tile_decode(t, a.ntn, tpi); };
     const TileIt stp = decode(t_stride);
-    auto advance = [&](TileIt it) {
-        it.nt += stp.nt;
-        if (it.nt >= a.ntn) { it.nt -= a.ntn; ++it.pt; }
-        it.pt += stp.pt;
-        if (it.pt >= tpi) { it.pt -= tpi; ++it.b; }
-        it.b += stp.b;
-        return it;
-    };
+    auto advance = [&](TileIt it) { return tile_advance(it, stp, a.ntn, tpi); };
 
     // ---- pixel-tile loader.  DMA unit u (1 KB = 16 pixels x one 16-channel chunk): chunk u >> 2, pixel group u & 3; wave w
     //      issues units w, w + 8, ...: always ITS pixel group w & 3 (lane -> pixel (w & 3) * 16 + (lane >> 2), quad lane & 3

@@ -20,31 +20,17 @@
 // set; pixels: odd halo rows) makes all fragment reads conflict-free.
 #include "conv_k.h"
 #include "bf_split.h"
+#include "dma_ring.h"
+#include "tile_walk.h"
 
 namespace {
 
 constexpr int CK = BMC_CK;
 constexpr int TW = 16;
 constexpr int RD = 8;   // dwords per LDS row (16 bf16)
-__device__ __attribute__((aligned(16))) const float g_zero4[4] = {0.f, 0.f, 0.f, 0.f};   // source of out-of-image lanes
 
 __device__ __forceinline__ int swz_w(int row, int half) { return row * RD + 4 * (half ^ ((row >> 4) & 1)); }
 __device__ __forceinline__ int swz_x(int hp, int hy, int half) { return hp * RD + 4 * (half ^ (hy & 1)); }
-
-// 16 bytes per lane from global memory straight into LDS (lane-linear image at the wave-uniform LDS byte address).
-// Inline asm on purpose: the compiler must not track this as an LDS store, or it drains vmcnt(0) before every later
-// ds_read and the ring could never run ahead.  Completion is waited for explicitly (dma_wait) before the barrier
-// that publishes the stage.
-// Address = uniform base (SGPR pair) + this lane's 32-bit byte offset: no per-piece VALU.  (m0 is reserved and cannot be
-// named as a clobber; nothing else in this kernel uses it.  s_nop 4: wait states for a VALU-written SGPR base / m0.)
-__device__ __forceinline__ void dma16(const void* gbase, unsigned voff, unsigned lds_addr) {
-    asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(gbase), "s"(lds_addr) : "memory");
-}
-template <int N>
-__device__ __forceinline__ void dma_wait() {   // all but the newest N vector-memory operations of this wave are done
-    static_assert(N >= 0 && N < 64, "vmcnt range");
-    __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-}
 
 // Loader roles are split by wave, because a wave's vmcnt completes IN ORDER: a wave that issued the next chunk's halo
 // loads (HBM, needed 8 steps later) and then waits for a weight slice (L2, needed next step) waits for the halo too.
@@ -65,27 +51,25 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
     u32* const Xb = lds;
     u32* const Wb = lds + 2 * XBUF;
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 2 * XBUF + NSTG * WBUF);
-    // accumulator start values (bias when it is the same for every tile of the launch, else zeros): see conv.hip
-    float* const init_lds = reinterpret_cast<float*>(lds + 2 * XBUF + NSTG * WBUF + BMC_MAX_SRC * 8);
-    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    float* const init_lds = reinterpret_cast<float*>(lds + 2 * XBUF + NSTG * WBUF + BMC_MAX_SRC * 8);   // accumulator start values (bias or zeros: bias_start_values, conv_k.h)
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool xrole = wave < 2;
     const int li = lane & 31, lh = lane >> 5;
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
+    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     if (tid < BN) init_lds[tid] = (bias_pre && tid < a.Cout) ? a.bias[tid] : 0.f;
     __syncthreads();
 
-    // persistent workgroups with the XCD-aware tile walk of conv.hip
+    // tile_walk() of tile_walk.h, written out, like bias_start_values() (conv_k.h) above: with the calls this kernel's
+    // scalar registers are allocated differently (up to 5 more of them spilled, other v_readlane / v_writelane counts),
+    // with the same code in place they are not.
     const int ntiles = a.ntiles;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && ntiles >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NX_) : ntiles;
+    const bool xcd_map = (gridDim.x % NUM_XCD) == 0 && ntiles >= (int)gridDim.x;
+    const int xcd = blockIdx.x % NUM_XCD, xj = blockIdx.x / NUM_XCD, per_x = gridDim.x / NUM_XCD;
+    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NUM_XCD) : 0;
+    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NUM_XCD) : ntiles;
     const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
     const int t_stride = xcd_map ? per_x : (int)gridDim.x;
     const int my_tiles = t_first < t_hi ? (t_hi - t_first + t_stride - 1) / t_stride : 0;
@@ -94,36 +78,10 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
     if (my_tiles == 0) return;
     const long long wstep = (long long)NP * a.Coutpad * RD;   // dwords per step in the packed planes
 
-    // Tile index -> (channel tile, tile column, tile row, image) is a mixed-radix decode = three integer divisions, ~100
-    // VALU instructions that three users (halo loader, weight loader, epilogue) would pay per tile beside the MFMAs.
-    // A workgroup visits t_first, t_first + t_stride, ...: decode once, then advance digit-wise with carries.
-    struct TileIt { int nt, tx, ty, b; };
-    TileIt it0;
-    {
-        int t = t_first;
-        it0.nt = t % a.ntn; t /= a.ntn;
-        it0.tx = t % a.tiles_x; t /= a.tiles_x;
-        it0.ty = t % a.tiles_y;
-        it0.b = t / a.tiles_y;
-    }
-    int d_nt, d_tx, d_ty, d_b;
-    {
-        int t = t_stride;
-        d_nt = t % a.ntn; t /= a.ntn;
-        d_tx = t % a.tiles_x; t /= a.tiles_x;
-        d_ty = t % a.tiles_y;
-        d_b = t / a.tiles_y;
-    }
-    auto it_next = [&](TileIt& it) {
-        it.nt += d_nt;
-        int c = 0;
-        if (it.nt >= a.ntn) { it.nt -= a.ntn; c = 1; }
-        it.tx += d_tx + c; c = 0;
-        if (it.tx >= a.tiles_x) { it.tx -= a.tiles_x; c = 1; }
-        it.ty += d_ty + c; c = 0;
-        if (it.ty >= a.tiles_y) { it.ty -= a.tiles_y; c = 1; }
-        it.b += d_b + c;
-    };
+    // the three users of a tile's coordinates (halo loader, weight loader, epilogue) each walk their own copy of the digits
+    using TileIt = Tile3;
+    const TileIt it0 = tile_decode(t_first, a.ntn, a.tiles_x, a.tiles_y), stp = tile_decode(t_stride, a.ntn, a.tiles_x, a.tiles_y);
+    auto it_next = [&](TileIt& it) { it = tile_advance(it, stp, a.ntn, a.tiles_x, a.tiles_y); };
     TileIt xl_it = it0, wl_it = it0, ep_it = it0;
 
     // ---- X loader (waves 0-1): fp32 from HBM into registers; split into planes when written to LDS
@@ -231,7 +189,7 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
         wl_base = static_cast<const u32*>(a.w) + (long long)grp * a.w_group_stride + (long long)wl_it.nt * BN * RD;
         wl_step = 0;
     };
-    const unsigned wb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Wb;
+    const unsigned wb_lds = lds_addr(Wb);
     // this wave issues the pieces j = w2, w2 + 2, ... of a slice; a piece's offset inside the slice never changes
     constexpr int PWMAX = (NDMA + 1) / 2;
     unsigned dma_off[PWMAX];
@@ -249,7 +207,7 @@ __global__ __launch_bounds__(256, (BN == 128 && (TH == 8 || NP == 3)) ? 2 : 3) v
         for (int i = 0; i < PWMAX; ++i) {
             const int j = 2 * i + w2;
             if (j < NDMA && !(NDMA == 1 && w2))
-                dma16(p, dma_off[i], wb_lds + (unsigned)((wl_stage * WBUF + j * 256) * 4));
+                dma16_sgpr(p, dma_off[i], wb_lds + (unsigned)((wl_stage * WBUF + j * 256) * 4));
         }
         wl_stage = wl_stage == NSTG - 1 ? 0 : wl_stage + 1;
         if (++wl_step == nsteps) {

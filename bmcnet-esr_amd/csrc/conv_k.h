@@ -21,6 +21,17 @@ struct ConvK {
     int tiles_x, tiles_y, ntn, nchunks, ntiles;
 };
 
+// Kernel prologue: accumulator start values for the BN channels of a tile -- the bias when it is the same for every tile of
+// the launch (one weight group, one channel tile: the usual case; returns true then), zeros otherwise.  A tile's
+// accumulators are (re)initialised with LDS reads straight into the accumulator registers: that replaces the v_movs, the
+// bias adds and the bias loads of the epilogue, and VALU instructions issued beside the other workgroups' MFMAs cost
+// 20-30 cycles each (in-kernel stamps).  The caller's barrier publishes the values.
+__device__ __forceinline__ bool bias_start_values(float* init_lds, const ConvK& a, int BN, int tid) {
+    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    if (tid < BN) init_lds[tid] = (bias_pre && tid < a.Cout) ? a.bias[tid] : 0.f;
+    return bias_pre;
+}
+
 // conv_bf.hip: launch the bf16-plane kernel (planes = 1: bf16 operands; 3: fp32 operands split into three bf16 planes,
 // six plane products -- fp32-equivalent result) for an already validated argument block.
 int bmc_conv_bf_launch(const ConvK& k, int taps, int BN, int TH, int planes, int cus, hipStream_t st);

@@ -17,7 +17,7 @@ namespace {
 // LDS-DMA pixel-reduction GEMM: ONE 8-wave workgroup per CU.
 //   TAPS = 9: 128 rows x 64 columns x 9 taps per workgroup (wave = 32 x 32 x 9 taps, 144 accumulator registers);
 //   TAPS = 1: 128 rows x 128 columns              (wave = 32 x 64, 32 accumulator registers).
-// Both operand tiles are double-buffered in LDS and filled by global_load_lds_dwordx4 (no staging registers, no
+// Both operand tiles are double-buffered in LDS and filled by LDS-DMA (dma_ring.h: no staging registers, no
 // ds_write): the fill of pixel tile t+1 is in flight under the MFMAs of tile t, one barrier per tile.  The LDS images
 // are lane-linear ([px][128] for A, [halo px][64] or [px][128] for X); pixels outside the image and channels beyond
 // M / N are sourced from a small zero buffer.
@@ -38,9 +38,7 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
     // argument made the compiler keep a copy of it in scratch memory)
     __shared__ SrcDev tab[BMC_MAX_SRC];
     const int tid = threadIdx.x, lane = tid & 63;
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
@@ -98,15 +96,7 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
         const int tin = split - nx_bb * a.tiles_per_img;
         nx_ty = TAPS == 9 ? tin / a.tiles_x : 0; nx_tx = TAPS == 9 ? tin - nx_ty * a.tiles_x : tin;
     }
-    auto dma = [&](const void* sbase, unsigned voff, float* ldst) {
-        const unsigned long long pv = reinterpret_cast<unsigned long long>(sbase);
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pv), hi = __builtin_amdgcn_readfirstlane((unsigned)(pv >> 32));
-        const void* const sb = reinterpret_cast<const void*>(((unsigned long long)hi << 32) | lo);
-        const unsigned la = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)ldst);
-        // (s_nop 4: wait states between the VALU-written SGPRs / m0 and the VMEM instruction; inline asm is opaque to the
-        //  hazard recognizer.  m0 is reserved and cannot be named as a clobber; nothing else in this kernel uses it.)
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 4\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(voff), "s"(sb), "s"(la) : "memory");
-    };
+    auto dma = [&](const void* sbase, unsigned voff, float* ldst) { dma16(sbase, voff, lds_addr(ldst)); };
     auto issue = [&](int tile, int buf) {      // must be called for tiles split, split + nsplit, ... in order
         const int b = g * a.batch_per_group + nx_bb;
         int y0 = 0, x0 = 0, p0 = 0;
@@ -144,7 +134,7 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
             }
             const float* src = a.zeros;
             if (ok && m0 + c4 < a.M) src = ab + pix * a.a.pix_stride + m0 + c4;
-            dma16v(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(lds + buf * BUF + (i * 512 + wave * 64) * 4));
+            dma16v(src, lds_addr(lds + buf * BUF + (i * 512 + wave * 64) * 4));
         }
 #pragma unroll
         for (int i = 0; i < 4; ++i) {            // X tile: [108 halo px][64 ch] (+ padding lanes) or [64 px][128 ch]
@@ -170,12 +160,12 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
                 const SrcDev S = tab[s_i];
                 src = src_bp<TAB>(S, b) + pix * S.pix_stride + ch;
             }
-            dma16v(src, (unsigned)(size_t)(__attribute__((address_space(3))) void*)(lds + (2 + buf) * BUF + (i * 512 + wave * 64) * 4));
+            dma16v(src, lds_addr(lds + (2 + buf) * BUF + (i * 512 + wave * 64) * 4));
         }
     };
 
     if (split < ntiles) issue(split, 0);
-    __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8));   // vmcnt(0): the asm DMA is invisible to the compiler's own waits
+    dma_wait<0>();      // the asm DMA is invisible to the compiler's own waits
     __syncthreads();
     // bias gradient = column sums of A over pixels: the first n-block adds up its A tiles straight from LDS
     // (thread -> channel tid & 127, rows (tid >> 7) * 16 .. + 16); 4 partial rows per workgroup go to bias_slabs
@@ -236,7 +226,7 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
                     }
             }
         }
-        __builtin_amdgcn_s_waitcnt(0 | (7 << 4) | (15 << 8));   // vmcnt(0): the next tile's DMA has landed
+        dma_wait<0>();      // the next tile's DMA has landed
         __syncthreads();    // publishes it and fences this tile's LDS reads
     }
 

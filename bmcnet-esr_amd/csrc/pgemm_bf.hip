@@ -19,7 +19,7 @@
 //   1x1           : 128 x 128,    waves 4 x 2 (columns), 2 column tiles per wave.
 #include "pgemm_k.h"
 #include "bf_split.h"
-#include <type_traits>
+#include "dma_ring.h"
 
 namespace {
 
@@ -446,10 +446,6 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
                 }
             }
         };
-        auto wait_n = [&](auto n) {   // all but the newest n vector-memory operations of this wave are done
-            constexpr int N = decltype(n)::value;
-            __builtin_amdgcn_s_waitcnt((N & 15) | (7 << 4) | (15 << 8) | ((N >> 4) << 14));
-        };
         // Rotating pipeline, one item at a time: wait for the OLDEST outstanding load (item `it` of tile i+1, issued one
         // whole iteration ago), split + store it into image (i+1) & 1, and reissue the same registers for tile i+2: every
         // load has a full iteration to land, with one tile's worth of staging registers.
@@ -457,7 +453,7 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
             const TileP t0 = tile_setup(0);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) load_item(t0, it);
-            wait_n(std::integral_constant<int, 0>{});
+            dma_wait<0>();
 #pragma unroll
             for (int it = 0; it < NIT; ++it) store_item(it, 0);
             const TileP t1 = tile_setup(1);
@@ -470,7 +466,7 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
                 const TileP t2 = tile_setup(i + 2);
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
-                    wait_n(std::integral_constant<int, NIT - 1>{});
+                    dma_wait<NIT - 1>();
                     store_item(it, (i + 1) & 1);             // image (i+1)&1 was last read for tile i-1: barrier passed
                     load_item(t2, it);
                 }

@@ -15,6 +15,7 @@
 #include "bmc_common.h"
 #include "conv_k.h"
 #include "dma_ring.h"
+#include "tile_walk.h"
 #include <stdlib.h>
 
 namespace {
@@ -54,21 +55,6 @@ __device__ __forceinline__ f32x4 sub4w(f32x4 a, f32x4 b) {
     return __builtin_shufflevector(lo, hi, 0, 1, 2, 3);
 }
 
-// 4 KB linear copy global -> LDS by this wave (4 LDS-DMA instructions, one asm block: the base pointer reaches its SGPR pair once, the instruction's immediate offset advances the global AND the LDS address alike)
-__device__ __forceinline__ void dma4k(const void* gbase, unsigned lane_off, unsigned lds_addr) {
-    const unsigned long long pv = reinterpret_cast<unsigned long long>(gbase);
-    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pv), hi = __builtin_amdgcn_readfirstlane((unsigned)(pv >> 32));
-    const unsigned long long b0 = ((unsigned long long)hi << 32) | lo;
-    const unsigned la = __builtin_amdgcn_readfirstlane(lds_addr);
-    asm volatile(
-        "s_mov_b32 m0, %2\n\ts_nop 4\n\t"
-        "global_load_lds_dwordx4 %0, %1\n\t"
-        "global_load_lds_dwordx4 %0, %1 offset:1024\n\t"
-        "global_load_lds_dwordx4 %0, %1 offset:2048\n\t"
-        "global_load_lds_dwordx4 %0, %1 offset:3072"
-        ::"v"(lane_off), "s"(b0), "s"(la) : "memory");
-}
-
 // ---- machine mapping: TWO waves per SIMD.
 // Round 3's first kernel (removed in round 4) kept all 16 transform positions of 32 tiles x 32 channels in one wave (256 accumulator
 // registers): one wave per SIMD, and every instruction that is not an MFMA -- fragment reads, DMA issue, waits, barriers, the output
@@ -94,53 +80,26 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
     float* const Vb = lds + 2 * XBUFA + NWR * WSTAGE;
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 2 * XBUFA + NWR * WSTAGE + 2 * VSTAGE);
     float* const init_lds = lds + 2 * XBUFA + NWR * WSTAGE + 2 * VSTAGE + BMC_MAX_SRC * 8;
-    const unsigned wb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Wb;
-    const unsigned xb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Xb;
-    const bool bias_pre = a.bias != nullptr && a.batch_per_group >= a.B && a.ntn == 1;
+    const unsigned wb_lds = lds_addr(Wb), xb_lds = lds_addr(Xb);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lj = lane & 15, lk = lane >> 4;
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
-    if (tid < BN) init_lds[tid] = (bias_pre && tid < a.Cout) ? a.bias[tid] : 0.f;
+    const bool bias_pre = bias_start_values(init_lds, a, BN, tid);
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     __syncthreads();
 
-    const int ntiles = a.ntiles;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && ntiles >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NX_) : ntiles;
-    const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
-    const int t_stride = xcd_map ? per_x : (int)gridDim.x;
-    const int my_tiles = t_first < t_hi ? (t_hi - t_first + t_stride - 1) / t_stride : 0;
-    if (my_tiles == 0) return;
+    const TileWalk tw = tile_walk(a.ntiles);      // persistent workgroups
+    const int t_first = tw.first, t_hi = tw.hi, t_stride = tw.stride;
+    if (tw.count == 0) return;
     const int nchunks = a.nchunks;
 
-    struct TileIt { int nt, tx, ty, b; };
-    auto decode = [&](int t) {
-        TileIt it;
-        it.nt = t % a.ntn; t /= a.ntn;
-        it.tx = t % a.tiles_x; t /= a.tiles_x;
-        it.ty = t % a.tiles_y;
-        it.b = t / a.tiles_y;
-        return it;
-    };
+    using TileIt = Tile3;
+    auto decode = [&](int t) { return tile_decode(t, a.ntn, a.tiles_x, a.tiles_y); };
 
     // The halo and weight loaders visit t_first, t_first + t_stride, ...: they advance by the digits of t_stride with carries
     // (a decode() there is three runtime divisions of scalar code the compiler speculates into the per-stage path)
     const TileIt stp = decode(t_stride);
-    auto advance = [&](TileIt it) {
-        it.nt += stp.nt;
-        if (it.nt >= a.ntn) { it.nt -= a.ntn; ++it.tx; }
-        it.tx += stp.tx;
-        if (it.tx >= a.tiles_x) { it.tx -= a.tiles_x; ++it.ty; }
-        it.ty += stp.ty;
-        if (it.ty >= a.tiles_y) { it.ty -= a.tiles_y; ++it.b; }
-        it.b += stp.b;
-        return it;
-    };
+    auto advance = [&](TileIt it) { return tile_advance(it, stp, a.ntn, a.tiles_x, a.tiles_y); };
 
     // ---- X loader: 16 DMA instructions per halo tile, 2 per wave (layout and quad stream as in the kernel above), in the
     // cheap form "uniform base (SGPR pair) + per-lane 32-bit offset": EVERY lane fetches a valid address -- pixels outside
@@ -163,8 +122,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
         xzm = 0;
 #pragma unroll
         for (int k = 0; k < NXD; ++k) {
-            int ln;                           // (lane index re-derived here, once per tile and source: not a loop-invariant to keep
-            asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));    // in a register -- or to spill)
+            const int ln = lane_id_pinned();  // (once per tile and source)
             const int Q = (wave * NXD + k) * 64 + ln;
             const int hy = Q / 96, rq = Q - hy * 96, hx = rq / 5, q = rq - hx * 5;
             const bool real = hy < HHT && hx < HWD && q < 4;            // a quad some patch read will touch
@@ -203,8 +161,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
                 f32x4 z;
                 asm volatile("v_mov_b32 %0, 0\n\tv_mov_b32 %1, 0\n\tv_mov_b32 %2, 0\n\tv_mov_b32 %3, 0"
                              : "=v"(z[0]), "=v"(z[1]), "=v"(z[2]), "=v"(z[3]));      // (made here: a zero quad kept live would be spilled)
-                int zl;
-                asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(zl));
+                const int zl = lane_id_pinned();
                 *reinterpret_cast<f32x4*>(Xb + buf * XBUFA + ((wave * NXD + k) * 64 + zl) * 4) = z;
             }
     };
@@ -248,11 +205,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
 
     f32x4 acc[16][NTB];
     auto init_acc = [&]() {
-        // (the lane's quad index is re-derived here, once per tile, from v_mbcnt: kept live across the stage loop the address was
-        //  the one value the register allocator spilled, and its reload -- a scratch load -- waited, in order, for every DMA
-        //  in flight at the top of every tile)
-        int ln;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+        const int ln = lane_id_pinned();     // (the lane's quad index, once per tile: kept live across the stage loop it was spilled)
         const f32x4 bq = *reinterpret_cast<const f32x4*>(init_lds + 16 * wave + 4 * (ln >> 4));
 #pragma unroll
         for (int p = 0; p < 16; ++p)
@@ -377,8 +330,7 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
         }
         const float* const resb = ep_res;
         const float* const maskb = ep_mask;
-        int eln;      // (lane index re-derived: the epilogue's lane-dependent values are not kept -- or spilled -- across the stages)
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(eln));
+        const int eln = lane_id_pinned();      // (the epilogue's lane-dependent values are not kept -- or spilled -- across the stages)
         const int elk = eln >> 4, elj = eln & 15;
         const int co = it.nt * BN + 16 * wave + 4 * elk;
         const bool cok = co < a.Cout;

@@ -40,6 +40,7 @@
 #include "bmc_common.h"
 #include "conv_k.h"
 #include "dma_ring.h"
+#include "tile_walk.h"
 #include <type_traits>
 
 namespace {
@@ -97,7 +98,7 @@ struct W4For<N, N> {
     static __device__ __forceinline__ void run(F&&) {}
 };
 
-struct W4Tile { int nt, wt, b; };
+using W4Tile = Tile2;      // (channel tile nt, workgroup tile pt of the image, image b)
 
 // LOADER = false: waves 0-5 (producer of row xi = wave of the position grid); true: waves 6-7 (halo DMA)
 template <bool LOADER>
@@ -124,7 +125,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     float* const Vb = lds + 2 * XBUFA;
     int* const xtab = reinterpret_cast<int*>(lds + 2 * XBUFA + 2 * VBUF);          // [NLW][PPW][64]
     const SrcDev* const tab = reinterpret_cast<const SrcDev*>(lds + 2 * XBUFA + 2 * VBUF + NLW * PPW * 64);
-    const unsigned xb_lds = (unsigned)(size_t)(__attribute__((address_space(3))) void*)Xb;
+    const unsigned xb_lds = lds_addr(Xb);
 
     const int lane = threadIdx.x & 63;
     const int lj = lane & 15, lk = lane >> 4;
@@ -132,22 +133,11 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     const int tpi = a.tiles_x * a.tiles_y;            // Winograd tiles per image
     const int wpi = (tpi + NT - 1) / NT;              // workgroup tiles per image
 
-    // (lane-dependent addresses that are needed once or twice per chunk are re-derived from v_mbcnt where they are used: kept
-    //  live across 144 MFMAs they are what the register allocator spills, and a scratch reload waits, in order, for every
+    // (lane-dependent addresses that are needed once or twice per chunk are re-derived with lane_id_pinned() where they are used:
+    //  kept live across 144 MFMAs they are what the register allocator spills, and a scratch reload waits, in order, for every
     //  weight request in flight)
-    auto lane_now = [&]() __attribute__((always_inline)) {
-        int l;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
-        return l;
-    };
-    auto decode = [&](int t) {
-        W4Tile it;
-        it.nt = t % a.ntn; t /= a.ntn;
-        it.wt = t % wpi;
-        it.b = t / wpi;
-        return it;
-    };
-    // A workgroup visits the tiles t_first, t_first + t_stride, ...: (nt, wt, b) advance by the digits of t_stride with carries.  No
+    auto decode = [&](int t) { return tile_decode(t, a.ntn, wpi); };
+    // A workgroup visits the tiles t_first, t_first + t_stride, ...: (nt, pt, b) advance by the digits of t_stride with carries.  No
     // integer division stays in the tile loop (three decodes per tile and wave were ~120 vector instructions, and the two reciprocals
     // they keep in registers were what the allocator spilled once the epilogue prefetched its operand: round 6).
     // tiles_x as a divisor the compiler cannot hoist: the per-tile divisions below recompute their reciprocal (~25 instructions per
@@ -165,14 +155,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
         return sd.ptr + (long long)bs * sd.batch_stride;
     };
     const W4Tile stp = decode(t_stride);
-    auto advance = [&](W4Tile it) {
-        it.nt += stp.nt;
-        if (it.nt >= a.ntn) { it.nt -= a.ntn; ++it.wt; }
-        it.wt += stp.wt;
-        if (it.wt >= wpi) { it.wt -= wpi; ++it.b; }
-        it.b += stp.b;
-        return it;
-    };
+    auto advance = [&](W4Tile it) { return tile_advance(it, stp, a.ntn, wpi); };
 
     // ---------------------------------------------------------------- U stream (every wave: its own 16 rows)
     const unsigned uvoff = (unsigned)(lane * 16);
@@ -196,7 +179,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     int tb_ty0 = 0, tb_tx0 = 0, tb_st1 = 0, tb_st2 = 0, tb_st3 = 0, tb_st4 = 0;
     // once per tile: pixel index / channel quad / zero flag of every quad this wave copies
     auto table_setup = [&]() {
-        const int T0 = xl_it.wt * NT;
+        const int T0 = xl_it.pt * NT;
         tb_ty0 = T0 / tiles_x_now(); tb_tx0 = T0 - tb_ty0 * a.tiles_x;
         // segments g = 0..3: the tiles of tile row ty0 + g, n_g of them from tile column (g == 0 ? tx0 : 0), pixel slots
         // [st_g, st_g + 4 n_g + 2): neighbours in a row share two columns, every row break starts a fresh 6-column patch
@@ -212,7 +195,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
         xzm_next = 0;
     };
     auto table_piece = [&](int k) __attribute__((always_inline)) {
-        const int l = lane_now();
+        const int l = lane_id_pinned();
         const int Q = (wl * PPW + k) * 64 + l;
         const int r = Q / (XROWF / 4), rem = Q - r * (XROWF / 4);
         const int s = rem / 5, q = rem - 5 * s;
@@ -252,7 +235,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     unsigned xoff[KREG];
     bool xl_newoff = true;
     auto offsets_from_table = [&]() {
-        const int l = lane_now();
+        const int l = lane_id_pinned();
 #pragma unroll
         for (int k = 0; k < KREG; ++k) {
             const int e = xtab[(wl * PPW + k) * 64 + l];
@@ -262,7 +245,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     };
     int xoj_e[2] = {0, 0};                            // table entries of the two pieces the NEXT pair issues (k >= KREG)
     auto xoj_fetch = [&](int k, int slot) __attribute__((always_inline)) {
-        const int l = lane_now();
+        const int l = lane_id_pinned();
         xoj_e[slot] = xtab[(wl * PPW + k) * 64 + l];
     };
     auto load_x_piece = [&](int k) __attribute__((always_inline)) {
@@ -270,7 +253,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
         unsigned off;
         if (k < KREG) off = xoff[k < KREG ? k : 0];
         else { const int e = xoj_e[k & 1]; off = __umul24((unsigned)(e >> 2), (unsigned)x_stride4) + (unsigned)(e & 3) * 16u; }
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(off), "s"(sbase + c_in), "s"(la) : "memory");
+        dma16_sgpr<1>(sbase + c_in, off, la);
     };
     auto load_x_begin = [&]() {
         if (xl_rebuild) { xzm = xzm_next; xl_rebuild = false; }
@@ -309,7 +292,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     };
     auto zero_x = [&](int buf) {                      // after the burst has landed, before the barrier that publishes it
         if (__builtin_amdgcn_ballot_w64(xzm_landed != 0) == 0) return;
-        const int l = lane_now();
+        const int l = lane_id_pinned();
 #pragma unroll
         for (int k = 0; k < PPW; ++k)
             if ((xzm_landed >> k) & 1)
@@ -327,10 +310,9 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     const float pk3 = (xi == 0 || xi == 5) ? 0.f : 1.f;
     int prow[4];                                      // float offsets of (patch row k, this lane's tile, channel quad) in an X buffer
     auto prod_setup = [&](const W4Tile& it) {         // geometry of the tile whose chunks the producer is working on
-        int pln;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(pln));
+        const int pln = lane_id_pinned();
         const int ptile = pln >> 2, pq = pln & 3;
-        const int T0 = it.wt * NT;
+        const int T0 = it.pt * NT;
         const int txn = tiles_x_now();
         const int ty0 = T0 / txn;
         const int ty = (T0 + ptile) / txn;
@@ -413,7 +395,7 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
         for (int e = 0; e < 2; ++e) { pt[3][e] = __builtin_fmaf(2.f, te[e], tc[e]); pt[4][e] = __builtin_fmaf(-2.f, te[e], tc[e]); }
     };
     auto prod_addr = [&](int h) __attribute__((always_inline)) {          // (the half of its quad this lane writes in pass h included)
-        const int l = lane_now();
+        const int l = lane_id_pinned();
         int vst = xi * 6 * NT * CK + (l >> 2) * CK + (((l & 3) ^ swz(l >> 2)) * 4) + 2 * h;
         asm volatile("" : "+v"(vst));
         return vst;
@@ -588,14 +570,13 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
         const float* const maskb = ep_mask;
         // (lane index re-derived: the epilogue's lane-dependent values must not be kept -- or spilled -- across the chunks; a
         //  scratch reload inside the chunk loop waits, in order, for every weight request in flight)
-        int eln;
-        asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(eln));
+        const int eln = lane_id_pinned();
         const int elj = eln & 15, elk = eln >> 4;
         const int co = it.nt * BN + 16 * wave + 4 * elk;
         const bool cok = co < a.Cout;
         f32x4 bq = {0.f, 0.f, 0.f, 0.f};
         if (biasg && cok) bq = ldg16(biasg + co);
-        const int T = it.wt * NT + elj;
+        const int T = it.pt * NT + elj;
         const int ty = T / tiles_x_now(), tx = T - ty * a.tiles_x;
         const int y0 = 4 * ty, x0 = 4 * tx;
         const int pix0 = y0 * a.W + x0;
@@ -740,22 +721,13 @@ __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const ConvK a) {
     __shared__ __attribute__((aligned(16))) float lds[2 * XBUFA + 2 * VBUF + NLW * PPW * 64 + BMC_MAX_SRC * 8];
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 2 * XBUFA + 2 * VBUF + NLW * PPW * 64);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#pragma unroll
-    for (int i = 0; i < BMC_MAX_SRC; ++i)
-        if (tid == i) tab[i] = a.src[i];
+    BMC_LOAD_SRC_TABLE(tab, a, tid);
     __syncthreads();
 
-    const int ntiles = a.ntiles;
-    constexpr int NX_ = 8;
-    const bool xcd_map = (gridDim.x % NX_) == 0 && ntiles >= (int)gridDim.x;
-    const int xcd = blockIdx.x % NX_, xj = blockIdx.x / NX_, per_x = gridDim.x / NX_;
-    const int t_lo = xcd_map ? (int)((long long)ntiles * xcd / NX_) : 0;
-    const int t_hi = xcd_map ? (int)((long long)ntiles * (xcd + 1) / NX_) : ntiles;
-    const int t_first = xcd_map ? t_lo + xj : (int)blockIdx.x;
-    const int t_stride = xcd_map ? per_x : (int)gridDim.x;
-    if (t_first >= t_hi) return;
-    if (wave >= 8 - NLW) wino4_body<true>(a, lds, wave, t_first, t_hi, t_stride);
-    else wino4_body<false>(a, lds, wave, t_first, t_hi, t_stride);
+    const TileWalk tw = tile_walk(a.ntiles);
+    if (tw.first >= tw.hi) return;
+    if (wave >= 8 - NLW) wino4_body<true>(a, lds, wave, tw.first, tw.hi, tw.stride);
+    else wino4_body<false>(a, lds, wave, tw.first, tw.hi, tw.stride);
 }
 
 // U = G g G^T (6x6 from 3x3, G rows (1/4 0 0) (-1/6 -1/6 -1/6) (-1/6 1/6 -1/6) (1/24 1/12 1/6) (1/24 -1/12 1/6) (0 0 1)), made in

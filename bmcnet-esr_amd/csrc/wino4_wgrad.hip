@@ -103,7 +103,7 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     float* const rawb = lds;
     float* const imgb = lds + 2 * RAWF;
-    const unsigned lds_raw = (unsigned)(size_t)(__attribute__((address_space(3))) void*)rawb;
+    const unsigned lds_raw = lds_addr(rawb);
 
     // ---- consumer role: wave = (nu group pg, co block cb, ci block kb); lane -> channel l & 31 of the block, tile l >> 5 of a k-step
     const int pg = wave >> 2, cb = (wave >> 1) & 1, kb = wave & 1;
@@ -208,8 +208,7 @@ __device__ __forceinline__ void wgrad4_body(const Wgrad4K& a, float* const lds, 
     };
     auto rq_piece = [&](const int j) __attribute__((always_inline)) {
         if (j == PPW - 1 && !has_last) return;
-        asm volatile("s_mov_b32 m0, %2\n\ts_nop 1\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"(pof[j]), "s"(((pxm >> j) & 1) ? rq_xs : rq_ys),
-                     "s"(pla[j] + rq_lo) : "memory");
+        dma16_sgpr<1>(((pxm >> j) & 1) ? rq_xs : rq_ys, pof[j], pla[j] + rq_lo);
     };
     // after the requests have landed, before the barrier that publishes them: pixels outside the image become zeros
     auto patch = [&](const int rb) __attribute__((always_inline)) {

@@ -275,3 +275,104 @@ def test_epilogue_forms_with_operands_requested_ahead(kind, res, relu, mask, acc
     err = rel_l2(out, y)
     print("%s res=%d relu=%d mask=%d acc=%d: %.2e" % (kind, res, relu, mask, acc, err))
     assert err < (1e-5 if kind == "wino4" else 2e-6)
+
+
+# ------------------------------------------------------------------ the persistent tile walk, many tiles per workgroup
+_WALK_H, _WALK_W, _WALK_CN = 37, 53, 128      # ragged for the 8x16, 4x16 and 4x4 tilings and for 64-pixel runs
+# kernel -> (taps, input channels, Winograd form, math mode, PROFILE kind, bar or None = the bf16 kernel tests' bar)
+_WALK_CASES = {
+    "direct": (9, 32, 0, "fp32", "conv_kernel<9,128>", 2e-6),
+    "f2x2": (9, 32, 2, "fp32", "wino_conv<9,128>", 1e-5),
+    "f4x4": (9, 32, 4, "fp32", "wino4_conv<9,128>", 1e-5),
+    "conv1p_k128": (1, 128, 0, "fp32", "conv_kernel<1,128>", 2e-6),
+    "conv1p_k256": (1, 256, 0, "fp32", "conv_kernel<1,128>", 2e-6),
+    "conv1_k192": (1, 192, 0, "fp32", "conv_kernel<1,128>", 2e-6),       # a K conv1p does not take
+    "bf16": (9, 32, 0, "bf16", "conv_kernel<9,128>", None),
+    "bf16x6": (9, 32, 0, "bf16x6", "conv_kernel<9,128>", None),
+}
+_WALK_REF = {}
+
+
+def _walk_tiles_per_image(kernel):
+    """Tiles of one 37 x 53 x 128 image by each launcher's own formula (csrc/conv.hip, wino.hip, wino4.hip, conv1.hip, conv1p.hip)."""
+    H, W = _WALK_H, _WALK_W
+    if kernel == "f4x4":
+        return (((W + 3) // 4) * ((H + 3) // 4) + 15) // 16         # 16 Winograd tiles per workgroup tile
+    if kernel.startswith("conv1p"):
+        return (H * W + 63) // 64                                   # 64-pixel runs
+    return ((W + 15) // 16) * ((H + 7) // 8)                        # 8 x 16 pixels (every launch here has >= 2 tiles per CU)
+
+
+def _walk_problem(taps, cin, B, rounded):
+    """Operands and the float64 reference relu(conv + bias + residual), made once per shape and shared by the cases."""
+    key = (taps, cin, B)
+    if key not in _WALK_REF:
+        g = torch.Generator().manual_seed(977 + 16 * taps + cin)
+        k = 3 if taps == 9 else 1
+        x = torch.randn(B, _WALK_H, _WALK_W, cin, generator=g)
+        w = torch.randn(_WALK_CN, cin, k, k, generator=g) / (cin * taps) ** 0.5
+        b = torch.randn(_WALK_CN, generator=g)
+        r = torch.randn(B, _WALK_H, _WALK_W, _WALK_CN, generator=g)
+        _WALK_REF[key] = {"ops": (x, w, b, r)}
+    ent = _WALK_REF[key]
+    if rounded not in ent:
+        from test_gpu_bf16_kernels import O
+        x, w, b, r = ent["ops"]
+        rd = O.round_bf16 if rounded else (lambda t: t)
+        y = F.conv2d(rd(x.permute(0, 3, 1, 2).double()), rd(w.double()), b.double(), padding=taps // 9).permute(0, 2, 3, 1)
+        ent[rounded] = torch.relu(y + r.double())
+    return ent["ops"], ent[rounded]
+
+
+@pytest.mark.parametrize("kernel", list(_WALK_CASES))
+def test_persistent_tile_walk_many_tiles_per_workgroup(kernel):
+    """The XCD-aware persistent tile range and the digit-wise tile iterator (csrc/tile_walk.h) of every kernel that conv_raw
+    reaches, on ONE launch with more than 3 tiles per CU and a tile count that is no multiple of 8: the eighths of the tile list are
+    unequal, workgroups walk several tiles with the XCD stride, and the walk carries into the tile column, the tile row and the
+    image (37 x 53 images hang over every tiling).  The per-kernel tests elsewhere launch about one tile per workgroup; only the
+    full-model tests reached the multi-tile paths.  Against float64 relu(conv + bias + residual) per launch AND per image (a fault
+    confined to the last image is named): one misplaced tile out of ~800 moves rel-L2 to ~3e-2, one wrong element out of 1e7 to ~3e-4.
+    (Kernels with 2-3 resident workgroups per CU -- direct, bf16 planes, conv1, conv1p at K = 128 -- walk fewer tiles per workgroup
+    than the one-per-CU Winograd kernels at this size.)"""
+    dev = _gpu()
+    from bmc_hip import ops
+    from bmc_hip.ops import ConvSpec, _packed_weight, _src, conv_raw, coutpad
+    taps, cin, wino, math, kind, bar = _WALK_CASES[kernel]
+    H, W, Cn = _WALK_H, _WALK_W, _WALK_CN
+    cus = torch.cuda.get_device_properties(dev).multi_processor_count
+    per_img = _walk_tiles_per_image(kernel)
+    # conv1.hip takes a 1x1 launch from 4 tiles per CU on (below that it is conv.hip's): the launcher's threshold, not this test's
+    floor = 4 * cus - 1 if kernel.startswith("conv1_") else 3 * cus
+    B = floor // per_img + 1
+    while (B * per_img) % 8 == 0:
+        B += 1
+    ntiles = B * per_img
+    assert ntiles > 3 * cus and ntiles % 8 != 0, (B, per_img, ntiles, cus)
+    if bar is None:
+        from test_gpu_bf16_kernels import BAR, BAR_X6
+        bar = BAR if math == "bf16" else BAR_X6
+    (x, w, b, r), y = _walk_problem(taps, cin, B, rounded=(math == "bf16"))
+    spec = ConvSpec.dense(cin)
+    xg, bg, rg = x.to(dev), b.reshape(1, Cn).to(dev), r.to(dev)
+    out = torch.empty(B, H, W, Cn, device=dev)
+    ops.set_math(math)
+    ops.PROFILE = []
+    try:
+        wp = _packed_weight(w.reshape(1, Cn, cin, taps).to(dev), spec, None, wino=wino) if wino else \
+            _packed_weight(w.reshape(1, Cn, cin, taps).to(dev), spec, None)
+        conv_raw([_src(xg, 0, cin, 0, None, 0, B)], wp, spec.kpad * taps * coutpad(Cn), bg, Cn, out.data_ptr(), H * W * Cn, Cn,
+                 B, H, W, Cn, taps, relu=True, residual=_src(rg, 0, Cn, 0, None, 0, B), bpg=B, wino=wino)
+        torch.cuda.synchronize()
+        kinds = [p[0] for p in ops.PROFILE]
+    finally:
+        ops.PROFILE = None
+        ops.set_math("fp32")
+    assert kinds == [kind], kinds
+    out = out.cpu().double()
+    err = rel_l2(out, y)
+    per_image = [rel_l2(out[i], y[i]) for i in range(B)]
+    worst = max(range(B), key=lambda i: per_image[i])
+    print("%s: %d CUs, B=%d, %d tiles (%d per image): %.2e per launch, worst image %d: %.2e (bar %.0e)"
+          % (kernel, cus, B, ntiles, per_img, err, worst, per_image[worst], bar))
+    assert err < bar, (kernel, err, bar)
+    assert per_image[worst] < bar, (kernel, "image", worst, per_image[worst], bar)

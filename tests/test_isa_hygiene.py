@@ -4,7 +4,7 @@ assembly (hipcc cross-compiles here without a GPU; nothing is executed):
 * no flat_load / flat_store in the MFMA kernels: a flat access counts on vmcnt AND lgkmcnt and may complete out of order,
   so every wait for one is vmcnt(0) + lgkmcnt(0) -- it silently turns a prefetch ring into depth one (bmc_common.h: ldg16);
 * no scratch memory (spills, or a by-value kernel argument indexed per lane) beyond the one known 8-byte SGPR spill;
-* m0 is touched only inside the hand-written LDS-DMA asm (dma_ring.h, pgemm.hip, conv_bf.hip write it without being able
+* m0 is touched only inside the hand-written LDS-DMA asm (dma_ring.h, the one file that writes it, without being able
   to declare the clobber: VERDICT r1 item 12) -- if a compiler upgrade starts using m0 itself, this fails loudly;
 * register budgets: the occupancy each __launch_bounds__ was written for is what the compiler delivered.
 """
