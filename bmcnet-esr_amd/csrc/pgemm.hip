@@ -25,8 +25,16 @@ namespace {
 // are only reached by cutting the pixel axis into ~128 splits and every split writes a whole [taps][M][N] slab -- at
 // 31x56 the slab writes took as long as the MFMAs, and the reduction read 75 MB per weight gradient.  Three times the
 // workgroups per split = a third of the splits = a third of the slab bytes, for three times the (cheap) tile fills.
-template <int TAPS, int TG = TAPS, bool TAB = false>
+// KS = shares of a tile's k-steps (pixel pairs), for the 3x3 launches whose shape leaves waves of the fixed 4 x 2 map without
+// rows or columns of their own (pgemm_wave_map below).  The 8 waves are (32-row blocks) x (32-column blocks) x KS:
+//   KS = 1: wave = (mw, nw) = (wave & 3, wave >> 2), all 32 k-steps of a tile;
+//   KS = 2: Npad <= 32, one column block: wave = (mw, ks) = (wave & 3, wave >> 2), tile rows 2 ks, 2 ks + 1;
+//   KS = 4: Mpad = 32, one row block:     wave = (nw, ks) = (wave & 1, wave >> 1), tile row ks.
+// Fill, LDS images, barriers and accumulators are the same; after the last tile the partial sums of ks = 1 .. KS - 1 go
+// through the (then free) LDS buffers and the ks = 0 wave adds them in that order before it writes the slab.
+template <int TAPS, int TG = TAPS, bool TAB = false, int KS = 1>
 __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
+    static_assert(KS == 1 || ((KS == 2 || KS == 4) && TAPS == 9 && TG == 9), "k-step shares: the all-taps 3x3 kernel only");
     constexpr int HWD = PT_W + 2, HHT = PT_H + 2;
     constexpr int NHALO = TAPS == 9 ? HWD * HHT : PT;                   // 108 halo pixels or 64 pixels
     constexpr int XCH = TAPS == 9 ? 64 : 128;                           // columns per workgroup
@@ -42,7 +50,8 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
     __syncthreads();
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int li = lane & 31, lh = lane >> 5;
-    const int mw = wave & 3, nw = wave >> 2;
+    const int mw = KS == 4 ? 0 : wave & 3, nw = KS == 1 ? wave >> 2 : KS == 2 ? 0 : wave & 1;
+    const int ks = KS == 1 ? 0 : KS == 2 ? wave >> 2 : wave >> 1;
 
     int bid = blockIdx.x;
     const int split = bid % a.nsplit; bid /= a.nsplit;
@@ -52,7 +61,7 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
     const int mb = bid % a.n_mblk;
     const int g = bid / a.n_mblk;
     const int m0 = mb * 128, n0 = nb * XCH;
-    const bool wave_active = m0 + 32 * mw < a.Mpad;
+    const bool wave_active = KS == 4 ? n0 + 32 * nw < a.Npad : m0 + 32 * mw < a.Mpad;
     const int HWp = a.H * a.W;
 
     f32x16 acc[TG * NT];
@@ -182,8 +191,10 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
             for (int r = 0; r < 16; ++r) bsum += bp[r * 128];
         }
         if (wave_active) {
-            const float* const ap = lds + cur * BUF + lh * 128 + 32 * mw + li;
-            const float* const xp = lds + (2 + cur) * BUF + lh * XCH + 32 * NT * nw + li + (TG == TAPS ? 0 : tg * HWD * XCH);
+            // (KS > 1: this wave's share is k-steps [ks * 32 / KS, (ks + 1) * 32 / KS) = whole tile rows, folded into ap / xp)
+            const float* const ap = lds + cur * BUF + lh * 128 + 32 * mw + li + (KS == 1 ? 0 : ks * (PT / KS) * 128);
+            const float* const xp = lds + (2 + cur) * BUF + lh * XCH + 32 * NT * nw + li + (TG == TAPS ? 0 : tg * HWD * XCH) +
+                                    (KS == 1 ? 0 : ks * (PT_H / KS) * HWD * XCH);
             if constexpr (TAPS == 1) {
                 // 1x1: two MFMAs per pair of operand reads.  Left to itself the compiler issues each read right in front of its
                 // MFMAs and waits for it (lgkmcnt(0) before every pair: an LDS round trip per 128 matrix-pipe cycles, 0.71 of the
@@ -213,7 +224,7 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
                 }
             } else
 #pragma unroll
-            for (int q = 0; q < PT / 2; ++q) {
+            for (int q = 0; q < PT / 2 / KS; ++q) {
                 const float av = ap[2 * q * 128];
 #pragma unroll
                 for (int tap = 0; tap < TG; ++tap)       // (TG = 3: tap row tg is folded into xp)
@@ -232,7 +243,35 @@ __global__ __launch_bounds__(512, 2) void pgemm_dma_kernel(const PgemmK a) {
 
     if (do_bias && m0 + (tid & 127) < a.Mpad)
         a.bias_slabs[(((long long)split * a.G + g) * 4 + (tid >> 7)) * a.Mpad + m0 + (tid & 127)] = bsum;
-    if (wave_active) {
+    if constexpr (KS > 1) {
+        // the loop's last barrier left the LDS buffers free (no DMA in flight).  Three taps per pass: (KS - 1) * 8 / KS waves x
+        // 3 taps x 16 registers x 64 lanes = 48 or 72 KB.  ks = 0 adds the shares in the order 1, 2, 3: a fixed order.
+        constexpr int NG = 8 / KS, PASS = 3 * 16 * 64;
+        const int grp = KS == 2 ? mw : nw;
+#pragma unroll
+        for (int t0 = 0; t0 < TG; t0 += 3) {
+            if (ks > 0 && wave_active) {
+                float* const w = lds + ((ks - 1) * NG + grp) * PASS + lane;
+#pragma unroll
+                for (int t = 0; t < 3; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) w[(t * 16 + r) * 64] = acc[t0 + t][r];
+            }
+            __syncthreads();
+            if (ks == 0 && wave_active) {
+#pragma unroll 1       // (unrolled, the compiler hoists all 144 reads of a pass and spills)
+                for (int k = 1; k < KS; ++k) {
+                    const float* const rd = lds + ((k - 1) * NG + grp) * PASS + lane;
+#pragma unroll
+                    for (int t = 0; t < 3; ++t)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[t0 + t][r] += rd[(t * 16 + r) * 64];
+                }
+            }
+            __syncthreads();
+        }
+    }
+    if (wave_active && ks == 0) {
         float* const sl = a.slabs + (((long long)split * a.G + g) * TAPS + (TG == TAPS ? 0 : tg * TG)) * a.Mpad * a.Npad;
 #pragma unroll
         for (int tap = 0; tap < TG; ++tap)
@@ -433,6 +472,19 @@ __global__ void reduce_plain_kernel(const float* slabs, int nsplit, int G, int M
 
 }  // namespace
 
+// Wave map of a 3x3 all-taps fp32 launch = its number of k-step shares (pgemm_dma_kernel): 2 when all columns fit one 32-column
+// block (the second column block of the 4 x 2 map would multiply the zero buffer), 4 when all rows fit one 32-row block (three
+// of four row blocks would idle), else 1.
+static int pgemm_wave_map(int taps, int Mpad, int Npad) {
+    if (taps != 9) return 1;
+    if (Mpad <= 32) return 4;
+    return Npad <= 32 ? 2 : 1;
+}
+
+extern "C" int bmc_pgemm_wave_map(int taps, int M, int N) {
+    return pgemm_wave_map(taps, bmc_round_up(M, 32), bmc_round_up(N, 32));
+}
+
 extern "C" int bmc_pgemm(const bmc_pgemm_args_t* h, bmc_stream_t stream) {
     BMC_CHECK_ARG(h != nullptr, "bmc_pgemm: null args");
     BMC_CHECK_ARG(h->nsrc >= 1 && h->nsrc <= BMC_MAX_SRC, "bmc_pgemm: nsrc=%d out of range", h->nsrc);
@@ -487,7 +539,14 @@ extern "C" int bmc_pgemm(const bmc_pgemm_args_t* h, bmc_stream_t stream) {
             else hipLaunchKernelGGL((pgemm_dma_kernel<9, 3>), grid, dim3(512), 0, st, k);
         } else {
             dim3 grid((unsigned)((long long)k.G * k.n_mblk * k.n_nblk * k.nsplit));
-            if (tab) hipLaunchKernelGGL((pgemm_dma_kernel<9, 9, true>), grid, dim3(512), 0, st, k);
+            const int ksh = pgemm_wave_map(9, k.Mpad, k.Npad);
+            if (ksh == 2) {
+                if (tab) hipLaunchKernelGGL((pgemm_dma_kernel<9, 9, true, 2>), grid, dim3(512), 0, st, k);
+                else hipLaunchKernelGGL((pgemm_dma_kernel<9, 9, false, 2>), grid, dim3(512), 0, st, k);
+            } else if (ksh == 4) {
+                if (tab) hipLaunchKernelGGL((pgemm_dma_kernel<9, 9, true, 4>), grid, dim3(512), 0, st, k);
+                else hipLaunchKernelGGL((pgemm_dma_kernel<9, 9, false, 4>), grid, dim3(512), 0, st, k);
+            } else if (tab) hipLaunchKernelGGL((pgemm_dma_kernel<9, 9, true>), grid, dim3(512), 0, st, k);
             else hipLaunchKernelGGL(pgemm_dma_kernel<9>, grid, dim3(512), 0, st, k);
         }
     } else {

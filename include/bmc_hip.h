@@ -246,6 +246,10 @@ typedef struct bmc_pgemm_args {
                                    smaller slab writes); same slab layout */
 } bmc_pgemm_args_t;
 int bmc_pgemm(const bmc_pgemm_args_t* host_args, bmc_stream_t s);
+/* How bmc_pgemm deals the 8 waves of a workgroup for an fp32 launch with all taps per workgroup: the number of shares the
+ * k-steps (pixel pairs) of each pixel tile are cut into.  1: 4 row blocks x 2 column blocks; 2 (taps = 9, N <= 32): 4 row blocks
+ * x 2 shares; 4 (taps = 9, M <= 32): 2 column blocks x 4 shares.  The shares are summed in a fixed order inside the workgroup. */
+int bmc_pgemm_wave_map(int taps, int M, int N);
 /* slabs -> dW[Cout][Cin][taps] (nn.Conv2d layout) through kmap; beta 0/1 = overwrite/accumulate */
 int bmc_pgemm_reduce_weight(const float* slabs, int nsplit, int G, int taps, int M, int N, const int* kmap,
                             int Cin, float* dw, int accumulate, const float* bias_slabs /* or NULL */,
