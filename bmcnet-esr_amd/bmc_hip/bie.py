@@ -17,8 +17,7 @@ import weakref
 import torch
 
 from . import lib, ops
-from .ops import (CK, ConvSpec, _dense_spec, _need_gpu, _null_src, _packed_weight, _packed_weight_t, _src, _stream,
-                  conv_raw, coutpad, pgemm_raw, round_up)
+from .ops import ConvSpec, _dense_spec, _need_gpu, _null_src, _src, _stream, conv_launch, dgrad_launch, pgemm_raw, round_up
 
 _SPEC2 = {}
 
@@ -188,45 +187,6 @@ def _spec2(c):
     return s
 
 
-def _conv(srcs, w4, spec, owner, bias, out, B, relu=False, residual=None, mask=None, bpg=None, accumulate=False,
-          out_b0=0, rule=None):
-    """Forward-style launch: out[out_b0 : out_b0+B] = epi(conv(cat(srcs)) + bias)."""
-    G, Cout, Cin, taps = w4.shape
-    _, H, W, Co = out.shape
-    stride = max([x.pix_stride for x in srcs] + [Co] + [x.pix_stride for x in (residual, mask) if x is not None])
-    wn = ops.wino_ok(B, H, W, Cout, taps, fwd=not accumulate and mask is None, stride=stride, rule=rule)
-    wp = _packed_weight(w4, spec, owner, wino=wn)
-    conv_raw(srcs, wp, spec.kpad * taps * coutpad(Cout), bias, Cout if bias is not None else 0,
-             out.data_ptr() + 4 * out_b0 * H * W * Co, H * W * Co, Co, B, H, W, Cout, taps, relu=relu, residual=residual,
-             bpg=bpg, accumulate=accumulate, mask=mask, flops=2.0 * B * H * W * Cout * taps * spec.kreal, wino=wn)
-
-
-def _dgrad(g_src, w4, spec, src_index, owner, out, B, residual=None, mask=None, bpg=None, accumulate=False, out_b0=0):
-    """Data gradient w.r.t. source `src_index` of the conv with weights w4: out[out_b0:+B] (=|+=) conv^T(g)."""
-    G, Cout, Cin, taps = w4.shape
-    _, H, W, Co = out.shape
-    nch = spec.nch[src_index]
-    stride = max([g_src.pix_stride, Co] + [x.pix_stride for x in (residual, mask) if x is not None])
-    wn = ops.wino_ok(B, H, W, nch, taps, stride=stride)
-    wt = _packed_weight_t(w4, spec, src_index, owner, wino=wn)
-    conv_raw([g_src], wt, round_up(Cout, CK) * taps * coutpad(nch), None, 0, out.data_ptr() + 4 * out_b0 * H * W * Co,
-             H * W * Co, Co, B, H, W, nch, taps, residual=residual, mask=mask, bpg=bpg, accumulate=accumulate,
-             flops=2.0 * B * H * W * spec.real_nch[src_index] * taps * Cout, wino=wn)
-
-
-def _wgrad(a_src, x_srcs, spec, B, H, W, taps, Cout, dev, w_param, b_param, G=1, w_shape=None, keep=(), window=None):
-    # (w_param / b_param: a parameter, None, or for G > 1 a tuple of the G parameters of the weight groups)
-    """Weight gradient + bias gradient (column sums of the same A operand, taken from the tiles the pixel-reduction
-    GEMM stages anyway) -> (dW, db) for autograd; None where the sums went straight into the leaf parameters' .grad
-    (ops.reduce_wgrad).  G > 1 (stacked per-group weights): w_param None, result [G, ...]."""
-    # keep: the operand tensors behind a_src / x_srcs (ops.wgrad_side: small launches run on the side stream)
-    if ops.wino_wgrad_ok(a_src, x_srcs, spec, taps, Cout, G) and w_param is not None:
-        return ops.wgrad_wino(a_src, x_srcs[0], B, H, W, spec, dev, w_param, b_param, w_shape if w_shape is not None else w_param.shape,
-                              keep=keep, window=window)
-    return ops.wgrad_pgemm(a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param,
-                           w_shape if w_shape is not None else w_param.shape, G=G, keep=keep, window=window)
-
-
 class BIETwinFn(torch.autograd.Function):
     """inputs: x12 [2n,H,W,C] = [first; second], xs [n,H,W,C], then the 16 parameter tensors
     (res.conv1 w,b; res.conv2 w,b; convf w,b; norm w,b; clustering w,b; unclustering w,b; v1 w,b; v2 w,b).
@@ -245,8 +205,8 @@ class BIETwinFn(torch.autograd.Function):
         d = lambda t: t.detach()
         # residual block on both halves (shared weights)
         t12, r12 = new(B2), new(B2)
-        _conv([X(x12)], d(rw1).reshape(1, Cn, Cn, 9), s1, rw1, d(rb1), t12, B2, relu=True, rule=rb1)
-        _conv([X(t12)], d(rw2).reshape(1, Cn, Cn, 9), s1, rw2, d(rb2), r12, B2, residual=X(x12), rule=rb2)
+        conv_launch([X(x12)], d(rw1).reshape(1, Cn, Cn, 9), s1, rw1, d(rb1), t12, B2, relu=True, rule=rb1)
+        conv_launch([X(t12)], d(rw2).reshape(1, Cn, Cn, 9), s1, rw2, d(rb2), r12, B2, residual=X(x12), rule=rb2)
         # centres: clustering(LN(convf(cat[xs, other half])))
         fused = chain_supported(Cn)
         if fused:       # one launch; saved for backward: yhat (normalised, before the affine) and rstd
@@ -255,11 +215,11 @@ class BIETwinFn(torch.autograd.Function):
             y12 = z12
         else:
             z12, y12, c12 = new(B2), new(B2), new(B2)
-            _conv([X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], d(wf).reshape(1, Cn, 2 * Cn, 1), s2, wf, d(bf), z12, B2)
+            conv_launch([X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], d(wf).reshape(1, Cn, 2 * Cn, 1), s2, wf, d(bf), z12, B2)
             stats = torch.empty(B2 * H * W * 2, device=dev, dtype=torch.float32)
             lib.call(lib._ln_fwd, "bmc_layernorm_fwd", z12.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B2 * H * W, Cn, eps,
                      y12.data_ptr(), stats.data_ptr(), _stream())
-            _conv([X(y12)], d(wc).reshape(1, Cn, Cn, 1), s1, wc, d(bc), c12, B2)
+            conv_launch([X(y12)], d(wc).reshape(1, Cn, Cn, 1), s1, wc, d(bc), c12, B2)
         # values: v1 on the first half, v2 on the second (two weight groups)
         wv = ops.stacked((wv1, wv2), lambda: torch.stack([d(wv1).reshape(Cn, Cn, 1), d(wv2).reshape(Cn, Cn, 1)]), "v1x1")
         bv = ops.stacked((bv1, bv2), lambda: torch.stack([d(bv1), d(bv2)]), "stack")
@@ -273,21 +233,21 @@ class BIETwinFn(torch.autograd.Function):
             lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), B2 * Cn, Cn, p.data_ptr(), _stream())
             pw, pb = torch.empty_like(p), torch.empty_like(sc)                                 # P W_v [b, i, k],  P b_v [b, i]
             _times_w(p, wg, bv, n, pw, (Cn * Cn, Cn, 1), vec=pb)
-            _conv([X(x12)], pw.view(B2, Cn, Cn, 1), s1, None, pb, o12, B2, residual=X(r12, shift=n, mod=B2), bpg=1)
+            conv_launch([X(x12)], pw.view(B2, Cn, Cn, 1), s1, None, pb, o12, B2, residual=X(r12, shift=n, mod=B2), bpg=1)
         else:
             G0 = sc = None
             v12 = new(B2)
-            _conv([X(x12)], wv, s1, wv, bv, v12, B2, bpg=n)
+            conv_launch([X(x12)], wv, s1, wv, bv, v12, B2, bpg=n)
             # channel attention per sample
             slabs, nsplit, G = pgemm_raw(X(c12), [X(v12)], B2, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * B2 * H * W * Cn * Cn)
             att = torch.empty((B2, Cn, Cn), device=dev, dtype=torch.float32)
             lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, G, Cn, Cn, scale, att.data_ptr(), _stream())
             p = torch.empty_like(att)
             lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), B2 * Cn, Cn, p.data_ptr(), _stream())
-            _conv([X(v12)], p.view(B2, Cn, Cn, 1), s1, None, None, o12, B2, residual=X(r12, shift=n, mod=B2), bpg=1)
+            conv_launch([X(v12)], p.view(B2, Cn, Cn, 1), s1, None, None, o12, B2, residual=X(r12, shift=n, mod=B2), bpg=1)
         # shared stream: unclustering(cat[c1, c2]) + xs
         xs_new = new(n)
-        _conv([X(c12, b0=0, B=n), X(c12, b0=n, B=n)], d(wu).reshape(1, Cn, 2 * Cn, 1), s2, wu, d(bu), xs_new, n, residual=X(xs))
+        conv_launch([X(c12, b0=0, B=n), X(c12, b0=n, B=n)], d(wu).reshape(1, Cn, 2 * Cn, 1), s2, wu, d(bu), xs_new, n, residual=X(xs))
         ctx.save_for_backward(x12, xs, t12, z12, stats, y12, c12, v12 if not vfree else G0, p, rw1, rw2, wf, gamma, wc, wu, wv1, wv2, beta,
                               *((sc, bv1, bv2) if vfree else ()))
         ctx.vfree = vfree
@@ -357,26 +317,26 @@ class BIETwinFn(torch.autograd.Function):
             _times_w(da, wg, bg, n, w_dc, (cc2, 2 * Cn, 1), vec=ds)                            # [da W_v | .],  da b_v
             _times_w(da, wg, bg, n, w_dx[:, :, Cn:], (cc2, 1, 2 * Cn))                         # [. | (da W_v)^T]
             _times_w(p, wg, bg, n, w_dx, (cc2, 1, 2 * Cn))                                     # [(P W_v)^T | .]
-            _conv([X(x12), X(g_x, mod=n, B=B2)], w_dc, s2, None, ds, dc12, B2, bpg=1)
+            conv_launch([X(x12), X(g_x, mod=n, B=B2)], w_dc, s2, None, ds, dc12, B2, bpg=1)
         else:
             dv12 = new(B2)
             w_dv = torch.cat([p.transpose(1, 2), da.transpose(1, 2)], 2).view(B2, Cn, 2 * Cn, 1)
-            _conv([X(g_o), X(c12)], w_dv, s2, None, None, dv12, B2, bpg=1)
+            conv_launch([X(g_o), X(c12)], w_dv, s2, None, None, dv12, B2, bpg=1)
             w_dc = torch.cat([da, w_ut], 2).view(B2, Cn, 2 * Cn, 1)
-            _conv([X(v12), X(g_x, mod=n, B=B2)], w_dc, s2, None, None, dc12, B2, bpg=1)
+            conv_launch([X(v12), X(g_x, mod=n, B=B2)], w_dc, s2, None, None, dc12, B2, bpg=1)
         # ---- unclustering(cat[c1, c2]) + xs: weight gradient
-        dwu, dbu = _wgrad(X(g_x), [X(c12, b0=0, B=n), X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12), window=ctx.window)
+        dwu, dbu = ops.wgrad(X(g_x), [X(c12, b0=0, B=n), X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12), window=ctx.window, merge_pgemm=True)
         # ---- value convs (two weight groups)
         if not vfree:
-            dwv, dbv = _wgrad(X(dv12), [X(x12)], s1, B2, H, W, 1, Cn, dev, ctx.vparams[:2], ctx.vparams[2:], G=2,
-                              w_shape=(2, Cn, Cn, 1, 1), keep=(dv12, x12), window=ctx.window)
+            dwv, dbv = ops.wgrad(X(dv12), [X(x12)], s1, B2, H, W, 1, Cn, dev, ctx.vparams[:2], ctx.vparams[2:], G=2,
+                              w_shape=(2, Cn, Cn, 1, 1), keep=(dv12, x12), window=ctx.window, merge_pgemm=True)
         if ctx.fused:
             # ---- clustering, LayerNorm, convf: ONE data-gradient launch (csrc/chain.hip); y12 holds yhat, stats rstd.
             # dx12 = conv_f^T (second half of its inputs), dxs = skip + conv_f^T (first half) summed over both halves.
             dz12, dx12, dxs = chain_bwd(X(dc12), y12, stats, gamma.detach(), wf, wc, X(g_x), n, H, W, Cn, dev,
                                         ds1=ops.grad_slot(ctx.gslot, x12))
             # G = dc^T yhat and the clustering bias gradient (temporaries: dW_c, dgamma, dbeta follow from them)
-            Gm, dbc_t = _wgrad(X(dc12), [X(y12)], s1, B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn))
+            Gm, dbc_t = ops.wgrad(X(dc12), [X(y12)], s1, B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn), merge_pgemm=True)
             sg = ops.sink_group([p_wc, p_bc, p_gamma, p_beta])
             if sg is not None:
                 (o_w, o_b, o_g, o_bt), acc = sg
@@ -389,22 +349,22 @@ class BIETwinFn(torch.autograd.Function):
             lib.call(lib._chain_affine, "bmc_chain_affine_grads", Gm.data_ptr(), dbc_t.data_ptr(), wc.detach().data_ptr(),
                      gamma.detach().data_ptr(), beta.detach().data_ptr(), Cn, o_w.data_ptr(),
                      o_b.data_ptr() if o_b is not None else None, o_g.data_ptr(), o_bt.data_ptr(), acc, _stream())
-            dwf, dbf = _wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
-                              keep=(dz12, xs, x12), window=ctx.window)
+            dwf, dbf = ops.wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
+                              keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
             if vfree:
-                _conv([X(g_o), X(c12)], w_dx, s2, None, None, dx12, B2, bpg=1, accumulate=True)         # dx12 += attention
+                conv_launch([X(g_o), X(c12)], w_dx, s2, None, None, dx12, B2, bpg=1, accumulate=True)         # dx12 += attention
             else:
-                _dgrad(X(dv12), w_v, s1, 0, w_v, dx12, B2, bpg=n, accumulate=True)                      # dx12 += value convs
+                dgrad_launch(X(dv12), w_v, s1, 0, w_v, dx12, B2, bpg=n, accumulate=True)                      # dx12 += value convs
         else:
             dx12 = ops.grad_slot(ctx.gslot, x12)
             if vfree:
-                _conv([X(g_o), X(c12)], w_dx, s2, None, None, dx12, B2, bpg=1)
+                conv_launch([X(g_o), X(c12)], w_dx, s2, None, None, dx12, B2, bpg=1)
             else:
-                _dgrad(X(dv12), w_v, s1, 0, w_v, dx12, B2, bpg=n)                                       # dx12  =
+                dgrad_launch(X(dv12), w_v, s1, 0, w_v, dx12, B2, bpg=n)                                       # dx12  =
             # ---- clustering, LayerNorm, convf
-            dwc, dbc = _wgrad(X(dc12), [X(y12)], s1, B2, H, W, 1, Cn, dev, p_wc, p_bc, keep=(dc12, y12), window=ctx.window)
+            dwc, dbc = ops.wgrad(X(dc12), [X(y12)], s1, B2, H, W, 1, Cn, dev, p_wc, p_bc, keep=(dc12, y12), window=ctx.window, merge_pgemm=True)
             dy12 = new(B2)
-            _dgrad(X(dc12), w_c, s1, 0, o_wc, dy12, B2)
+            dgrad_launch(X(dc12), w_c, s1, 0, o_wc, dy12, B2)
             dz12 = new(B2)
             ws = torch.empty(2 * 1024 * Cn, device=dev, dtype=torch.float32)
             sg = ops.sink_group([p_gamma, p_beta])
@@ -417,19 +377,19 @@ class BIETwinFn(torch.autograd.Function):
                 ln_acc = 0
             lib.call(lib._ln_bwd, "bmc_layernorm_bwd", dy12.data_ptr(), z12.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
                      B2 * H * W, Cn, dz12.data_ptr(), ws.data_ptr(), o_g.data_ptr(), o_bt.data_ptr(), ln_acc, _stream())
-            dwf, dbf = _wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
-                              keep=(dz12, xs, x12), window=ctx.window)
+            dwf, dbf = ops.wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
+                              keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
             dxs = new(n)
-            _dgrad(X(dz12, b0=0, B=n), w_f, s2, 0, o_wf, dxs, n, residual=X(g_x))                        # dxs  = skip + half 0
-            _dgrad(X(dz12, b0=n, B=n), w_f, s2, 0, o_wf, dxs, n, accumulate=True)                        # dxs += half 1
-            _dgrad(X(dz12, shift=n, mod=B2), w_f, s2, 1, o_wf, dx12, B2, accumulate=True)                # dx12 += (rotated)
+            dgrad_launch(X(dz12, b0=0, B=n), w_f, s2, 0, o_wf, dxs, n, residual=X(g_x))                        # dxs  = skip + half 0
+            dgrad_launch(X(dz12, b0=n, B=n), w_f, s2, 0, o_wf, dxs, n, accumulate=True)                        # dxs += half 1
+            dgrad_launch(X(dz12, shift=n, mod=B2), w_f, s2, 1, o_wf, dx12, B2, accumulate=True)                # dx12 += (rotated)
         # ---- residual block, upstream gradient = batch-rotated g_o
         g_r = X(g_o, shift=n, mod=B2)
-        dw2, db2 = _wgrad(g_r, [X(t12)], s1, B2, H, W, 9, Cn, dev, p_rw2, p_rb2, keep=(g_o, t12), window=ctx.window)
+        dw2, db2 = ops.wgrad(g_r, [X(t12)], s1, B2, H, W, 9, Cn, dev, p_rw2, p_rb2, keep=(g_o, t12), window=ctx.window, merge_pgemm=True)
         dt = new(B2)
-        _dgrad(g_r, w_r2, s1, 0, o_rw2, dt, B2, mask=X(t12))
-        dw1, db1 = _wgrad(X(dt), [X(x12)], s1, B2, H, W, 9, Cn, dev, p_rw1, p_rb1, keep=(dt, x12), window=ctx.window)
-        _dgrad(X(dt), w_r1, s1, 0, o_rw1, dx12, B2, residual=g_r, accumulate=True)                       # dx12 += conv1^T + skip
+        dgrad_launch(g_r, w_r2, s1, 0, o_rw2, dt, B2, mask=X(t12))
+        dw1, db1 = ops.wgrad(X(dt), [X(x12)], s1, B2, H, W, 9, Cn, dev, p_rw1, p_rb1, keep=(dt, x12), window=ctx.window, merge_pgemm=True)
+        dgrad_launch(X(dt), w_r1, s1, 0, o_rw1, dx12, B2, residual=g_r, accumulate=True)                       # dx12 += conv1^T + skip
         v = lambda t, ref: None if t is None else t.view(ref.shape)
         gv = (None,) * 4 if dwv is None else (dwv[0].reshape(wv1.shape), dbv[0], dwv[1].reshape(wv2.shape), dbv[1])
         return (dx12, dxs, dw1, db1, dw2, db2, dwf, dbf, dgamma, dbeta, v(dwc, wc), dbc, dwu, dbu, *gv, None, None)
@@ -455,8 +415,8 @@ class BIEFirstFn(torch.autograd.Function):
         d = lambda t: t.detach()
         second = X(x12, b0=n, B=n)
         t2, r2 = new(n), new(n)
-        _conv([second], d(rw1).reshape(1, Cn, Cn, 9), s1, rw1, d(rb1), t2, n, relu=True, rule=rb1)
-        _conv([X(t2)], d(rw2).reshape(1, Cn, Cn, 9), s1, rw2, d(rb2), r2, n, residual=second, rule=rb2)
+        conv_launch([second], d(rw1).reshape(1, Cn, Cn, 9), s1, rw1, d(rb1), t2, n, relu=True, rule=rb1)
+        conv_launch([X(t2)], d(rw2).reshape(1, Cn, Cn, 9), s1, rw2, d(rb2), r2, n, residual=second, rule=rb2)
         yhat, rstd, c12 = chain_fwd(X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2), wf, d(bf), d(gamma), d(beta), wc, d(bc), eps,
                                     B2, H, W, Cn, dev)
         vfree = vfree_supported(B2 * H * W)
@@ -469,19 +429,19 @@ class BIEFirstFn(torch.autograd.Function):
             lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), n * Cn, Cn, p.data_ptr(), _stream())
             pw, pb = torch.empty_like(p), torch.empty_like(sc)
             _times_w(p, wg, bg, n, pw, (Cn * Cn, Cn, 1), vec=pb)
-            _conv([X(x12, b0=0, B=n)], pw.view(n, Cn, Cn, 1), s1, None, pb, o1, n, residual=X(r2), bpg=1)
+            conv_launch([X(x12, b0=0, B=n)], pw.view(n, Cn, Cn, 1), s1, None, pb, o1, n, residual=X(r2), bpg=1)
         else:
             G0 = sc = None
             v1 = new(n)
-            _conv([X(x12, b0=0, B=n)], d(wv1).reshape(1, Cn, Cn, 1), s1, wv1, d(bv1), v1, n)
+            conv_launch([X(x12, b0=0, B=n)], d(wv1).reshape(1, Cn, Cn, 1), s1, wv1, d(bv1), v1, n)
             slabs, nsplit, G = pgemm_raw(X(c12, b0=0, B=n), [X(v1)], n, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * n * H * W * Cn * Cn)
             att = torch.empty((n, Cn, Cn), device=dev, dtype=torch.float32)
             lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, G, Cn, Cn, scale, att.data_ptr(), _stream())
             p = torch.empty_like(att)
             lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), n * Cn, Cn, p.data_ptr(), _stream())
-            _conv([X(v1)], p.view(n, Cn, Cn, 1), s1, None, None, o1, n, residual=X(r2), bpg=1)
+            conv_launch([X(v1)], p.view(n, Cn, Cn, 1), s1, None, None, o1, n, residual=X(r2), bpg=1)
         xs_new = new(n)
-        _conv([X(c12, b0=0, B=n), X(c12, b0=n, B=n)], d(wu).reshape(1, Cn, 2 * Cn, 1), s2, wu, d(bu), xs_new, n, residual=X(xs))
+        conv_launch([X(c12, b0=0, B=n), X(c12, b0=n, B=n)], d(wu).reshape(1, Cn, 2 * Cn, 1), s2, wu, d(bu), xs_new, n, residual=X(xs))
         ctx.save_for_backward(x12, xs, t2, yhat, rstd, c12, v1 if not vfree else G0, p, rw1, rw2, wf, gamma, wc, wu, wv1, beta,
                               *((sc, bv1) if vfree else ()))
         ctx.vfree = vfree
@@ -539,19 +499,19 @@ class BIEFirstFn(torch.autograd.Function):
             _times_w(da, wg, bg, n, w_dc, (cc2, 2 * Cn, 1), vec=ds)                            # (first n samples; the rest stay zero)
             _times_w(da, wg, bg, n, w_dx[:, :, Cn:], (cc2, 1, 2 * Cn))
             _times_w(p, wg, bg, n, w_dx, (cc2, 1, 2 * Cn))
-            _conv([X(x12), X(g_x, mod=n, B=B2)], w_dc, s2, None, ds, dc12, B2, bpg=1)
+            conv_launch([X(x12), X(g_x, mod=n, B=B2)], w_dc, s2, None, ds, dc12, B2, bpg=1)
         else:
             dv1 = new(n)
             w_dv = torch.cat([p.transpose(1, 2), da.transpose(1, 2)], 2).view(n, Cn, 2 * Cn, 1)
-            _conv([X(g_o), X(c12, b0=0, B=n)], w_dv, s2, None, None, dv1, n, bpg=1)
+            conv_launch([X(g_o), X(c12, b0=0, B=n)], w_dv, s2, None, None, dv1, n, bpg=1)
             w_dc = torch.cat([torch.cat([da, torch.zeros_like(da)], 0), w_ut], 2).view(B2, Cn, 2 * Cn, 1)
-            _conv([X(v1, mod=n, B=B2), X(g_x, mod=n, B=B2)], w_dc, s2, None, None, dc12, B2, bpg=1)
-        dwu, dbu = _wgrad(X(g_x), [X(c12, b0=0, B=n), X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12), window=ctx.window)
+            conv_launch([X(v1, mod=n, B=B2), X(g_x, mod=n, B=B2)], w_dc, s2, None, None, dc12, B2, bpg=1)
+        dwu, dbu = ops.wgrad(X(g_x), [X(c12, b0=0, B=n), X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12), window=ctx.window, merge_pgemm=True)
         if not vfree:
-            dwv1, dbv1 = _wgrad(X(dv1), [X(x12, b0=0, B=n)], s1, n, H, W, 1, Cn, dev, p_wv1, p_bv1, keep=(dv1, x12), window=ctx.window)
+            dwv1, dbv1 = ops.wgrad(X(dv1), [X(x12, b0=0, B=n)], s1, n, H, W, 1, Cn, dev, p_wv1, p_bv1, keep=(dv1, x12), window=ctx.window, merge_pgemm=True)
         # ---- clustering, LayerNorm, convf (csrc/chain.hip), as in BIETwinFn
         dz12, dx12, dxs = chain_bwd(X(dc12), yhat, rstd, gamma.detach(), wf, wc, X(g_x), n, H, W, Cn, dev)
-        Gm, dbc_t = _wgrad(X(dc12), [X(yhat)], s1, B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn))
+        Gm, dbc_t = ops.wgrad(X(dc12), [X(yhat)], s1, B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn), merge_pgemm=True)
         sg = ops.sink_group([p_wc, p_bc, p_gamma, p_beta])
         if sg is not None:
             (o_w, o_b, o_g, o_bt), acc = sg
@@ -564,18 +524,18 @@ class BIEFirstFn(torch.autograd.Function):
         lib.call(lib._chain_affine, "bmc_chain_affine_grads", Gm.data_ptr(), dbc_t.data_ptr(), wc.detach().data_ptr(),
                  gamma.detach().data_ptr(), beta.detach().data_ptr(), Cn, o_w.data_ptr(),
                  o_b.data_ptr() if o_b is not None else None, o_g.data_ptr(), o_bt.data_ptr(), acc, _stream())
-        dwf, dbf = _wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
-                          keep=(dz12, xs, x12), window=ctx.window)
+        dwf, dbf = ops.wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
+                          keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
         if vfree:
-            _conv([X(g_o), X(c12, b0=0, B=n)], w_dx, s2, None, None, dx12, n, bpg=1, accumulate=True)    # dx12[first] += attention
+            conv_launch([X(g_o), X(c12, b0=0, B=n)], w_dx, s2, None, None, dx12, n, bpg=1, accumulate=True)    # dx12[first] += attention
         else:
-            _dgrad(X(dv1), w_v1, s1, 0, o_wv1, dx12, n, accumulate=True)                                 # dx12[first] += value conv
+            dgrad_launch(X(dv1), w_v1, s1, 0, o_wv1, dx12, n, accumulate=True)                                 # dx12[first] += value conv
         # ---- residual block (second half), upstream gradient = g_o
-        dw2, db2 = _wgrad(X(g_o), [X(t2)], s1, n, H, W, 9, Cn, dev, p_rw2, p_rb2, keep=(g_o, t2), window=ctx.window)
+        dw2, db2 = ops.wgrad(X(g_o), [X(t2)], s1, n, H, W, 9, Cn, dev, p_rw2, p_rb2, keep=(g_o, t2), window=ctx.window, merge_pgemm=True)
         dt = new(n)
-        _dgrad(X(g_o), w_r2, s1, 0, o_rw2, dt, n, mask=X(t2))
-        dw1, db1 = _wgrad(X(dt), [X(x12, b0=n, B=n)], s1, n, H, W, 9, Cn, dev, p_rw1, p_rb1, keep=(dt, x12), window=ctx.window)
-        _dgrad(X(dt), w_r1, s1, 0, o_rw1, dx12, n, residual=X(g_o), accumulate=True, out_b0=n)           # dx12[second] += conv1^T + skip
+        dgrad_launch(X(g_o), w_r2, s1, 0, o_rw2, dt, n, mask=X(t2))
+        dw1, db1 = ops.wgrad(X(dt), [X(x12, b0=n, B=n)], s1, n, H, W, 9, Cn, dev, p_rw1, p_rb1, keep=(dt, x12), window=ctx.window, merge_pgemm=True)
+        dgrad_launch(X(dt), w_r1, s1, 0, o_rw1, dx12, n, residual=X(g_o), accumulate=True, out_b0=n)           # dx12[second] += conv1^T + skip
         v = lambda t, ref: None if t is None else t.view(ref.shape)
         return (dx12, dxs, dw1, db1, dw2, db2, dwf, dbf, dgamma, dbeta, v(dwc, wc), dbc, dwu, dbu, v(dwv1, wv1), dbv1, None, None)
 

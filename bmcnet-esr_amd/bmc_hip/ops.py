@@ -11,6 +11,7 @@ import ctypes as C
 import os
 import threading
 import weakref
+from collections import namedtuple
 from typing import List, Optional, Sequence
 
 import torch
@@ -658,20 +659,25 @@ def current_window():
     return _WINDOW[0]
 
 
-class _MergeQueue:
-    __slots__ = ("items", "spec", "dev", "w_param", "b_param", "want_bias", "k0", "full", "H", "W", "window", "pg")
+_Use = namedtuple("_Use", "a_src x_srcs B keep")       # one queued use of a weight: operand descriptors, images, the tensors behind them
 
-    def __init__(self, spec, dev, w_param, b_param, want_bias, k0, full, H, W, window, pg=None):
-        self.items = []
-        self.spec, self.dev, self.w_param, self.b_param, self.want_bias, self.k0, self.full, self.H, self.W, self.window, self.pg = \
-            spec, dev, w_param, b_param, want_bias, k0, full, H, W, window, pg      # pg: (taps, Cout, w_shape) of a pixel-reduction queue
+
+class _MergeQueue:
+    """Uses of ONE sink weight within one window that leave as one launch.  wino: through bmc_wgrad_wino_multi (x_srcs of a use
+    holds one source; k0 / full: wgrad_wino's), else through the pixel-reduction GEMM over pointer tables."""
+    __slots__ = ("uses", "wino", "spec", "dev", "w_param", "b_param", "k0", "full", "H", "W", "taps", "Cout", "w_shape", "window")
+
+    def __init__(self, **fields):
+        self.uses = []
+        for k, v in fields.items():
+            setattr(self, k, v)
 
 
 # Queues belong to the autograd graph task (backward pass) that filled them: a nested pass -- torch.utils.checkpoint(use_reentrant=True),
 # a Function whose backward calls autograd.backward -- has its own task id, its own queues and its own end-of-pass flush, and neither
 # launches nor drops what the pass around it has queued.  Queues of a pass that RAISED (it never flushes) are dropped by wgrad_join()
 # once no backward pass is running.
-_MERGE = {}                  # graph task id -> {(id(w_param), k0, H, W, want_bias) -> _MergeQueue}
+_MERGE = {}                  # graph task id -> {(id(w_param), k0, taps, sources, H, W, want_bias) -> _MergeQueue}
 _FLUSH_QUEUED = set()        # graph tasks whose end-of-pass flush is queued
 PTR_TABLE_MAX = 256          # csrc/stream_ops.hip: bmc_ptr_table takes its pointers by value in the argument block
 
@@ -685,7 +691,7 @@ def flush_wgrads(task=None):
     if not qs:
         return
     for q in list(qs.values()):
-        if q.items:
+        if q.uses:
             _launch_merged(q)
 
 
@@ -726,125 +732,118 @@ def _table_src(srcs, batches, btot, dev):
 
 
 def _launch_merged(q):
-    items, q.items = q.items, []
-    keep = tuple(t for it in items for t in it[3])
-    npx = items[0][2] * q.H * q.W          # (the side-stream decision of a pass is made per launch size as before: first segment)
-    if q.pg is not None:
-        taps, Cout, w_shape = q.pg
-        batches = [it[2] for it in items]
+    uses, q.uses = q.uses, []
+    keep = tuple(t for u in uses for t in u.keep)
+    batches = [u.B for u in uses]
+    npx = batches[0] * q.H * q.W          # (the side-stream decision of a pass is made per launch size as before: first segment)
+    want_bias = q.b_param is not None      # (a queued use wants its bias gradient exactly when it names a bias: _queue_use)
+    with wgrad_side(npx, [q.w_param, q.b_param], keep):
+        if q.wino:
+            _wgrad_wino([u.a_src for u in uses], [u.x_srcs[0] for u in uses], batches, q.H, q.W, q.spec, q.dev, q.w_param, q.b_param,
+                        None, want_bias, q.k0, q.full)
+            return
         btot = sum(batches)
-        nx = len(items[0][1])
-        with wgrad_side(npx, [q.w_param, q.b_param] if q.want_bias else [q.w_param], keep):
-            a_t, tab_a = _table_src([it[0] for it in items], batches, btot, q.dev)
-            x_tt = [_table_src([it[1][k] for it in items], batches, btot, q.dev) for k in range(nx)]
-            x_t = [t for t, _ in x_tt]
-            _on_side(tab_a, *[tb for _, tb in x_tt])
-            r = pgemm_raw(a_t, x_t, btot, q.H, q.W, taps, btot, Cout, q.spec.kpad, q.dev,
-                          flops=2.0 * btot * q.H * q.W * Cout * taps * q.spec.kreal, want_bias=q.want_bias)
-            reduce_wgrad(r[0], r[1], 1, taps, Cout, q.spec, q.dev, r[3] if q.want_bias else None, q.w_param,
-                         q.b_param if q.want_bias else None, w_shape)
-        return
-    with wgrad_side(npx, [q.w_param, q.b_param] if q.want_bias else [q.w_param], keep):
-        _wgrad_wino([it[0] for it in items], [it[1] for it in items], [it[2] for it in items], q.H, q.W, q.spec, q.dev, q.w_param,
-                    q.b_param, None, q.want_bias, q.k0, q.full)
+        a_t, tab_a = _table_src([u.a_src for u in uses], batches, btot, q.dev)
+        x_tt = [_table_src([u.x_srcs[k] for u in uses], batches, btot, q.dev) for k in range(len(uses[0].x_srcs))]
+        _on_side(tab_a, *[tb for _, tb in x_tt])
+        _pgemm_wgrad(a_t, [t for t, _ in x_tt], btot, q.H, q.W, q.taps, q.Cout, q.spec, q.dev, q.w_param, q.b_param, q.w_shape, 1, want_bias)
 
 
-def _queue_use(key, make_queue, item, task, npx):
-    """Append one use to its merge queue (created by make_queue() if new / stale) and launch the queue when it is full."""
+def _queue_use(wino, a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param, w_shape, want_bias, k0, full, keep, window):
+    """Queue one use of a sink weight for a merged launch, if it may be merged (below) -> was it queued?  The queue is launched
+    when it is full; what is left when the backward pass ends leaves then (_queue_flush)."""
+    task = torch._C._current_graph_task_id()
+    if not (WGRAD_MERGE > 1 and window is not None and B * H * W <= WGRAD_MERGE_MAX_PIXELS and task >= 0 and w_param is not None
+            and not isinstance(w_param, (tuple, list)) and is_sink(w_param) and (not want_bias or is_sink(b_param)) and keep
+            and not torch.cuda.is_current_stream_capturing()):
+        return False
+    if wino:
+        if wgrad_wino4_ok(B, H, W):         # (merged launches stay on F(2x2): a use that F(4x4) takes leaves alone)
+            return False
+    elif not (B <= PTR_TABLE_MAX and a_src.batch_mod != -1 and all(x.batch_mod != -1 for x in x_srcs)):
+        return False
+    key = (id(w_param), k0, taps, len(x_srcs), H, W, want_bias)
     qs = _MERGE.setdefault(task, {})
     q = qs.get(key)
-    if q is None or q.w_param is not item[4] or q.window != item[5]:       # (another window's uses: the old queue leaves first)
-        if q is not None and q.items:
+    if q is None or q.w_param is not w_param or q.window != window:       # (another window's uses: the old queue leaves first)
+        if q is not None and q.uses:
             _launch_merged(q)
-        q = qs[key] = make_queue()
-    if q.pg is not None and q.items and sum(it[2] for it in q.items) + item[2] > PTR_TABLE_MAX:
+        q = qs[key] = _MergeQueue(wino=wino, spec=spec, dev=dev, w_param=w_param, b_param=b_param if want_bias else None, k0=k0,
+                                  full=full, H=H, W=W, taps=taps, Cout=Cout, w_shape=w_shape, window=window)
+    if not wino and q.uses and sum(u.B for u in q.uses) + B > PTR_TABLE_MAX:
         _launch_merged(q)            # (a pointer table holds PTR_TABLE_MAX images: what is queued leaves before this use joins)
     _queue_flush(task)               # the first queued use of this backward pass: flush what is left when the pass ends
-    _side_arm(npx)                   # (the pass's side-stream decision is made by its first USE, as without the queue)
-    q.items.append(item[:4])
-    if len(q.items) >= WGRAD_MERGE:
+    _side_arm(B * H * W)             # (the pass's side-stream decision is made by its first USE, as without the queue)
+    q.uses.append(_Use(a_src, list(x_srcs), B, tuple(keep)))
+    if len(q.uses) >= WGRAD_MERGE:
         _launch_merged(q)
+    return True
 
 
-def _mergeable(B, H, W, w_param, b_param, want_bias, keep, window):
-    task = torch._C._current_graph_task_id()
-    ok = (WGRAD_MERGE > 1 and window is not None and B * H * W <= WGRAD_MERGE_MAX_PIXELS and task >= 0 and w_param is not None
-          and not isinstance(w_param, (tuple, list)) and is_sink(w_param) and (not want_bias or is_sink(b_param)) and keep
-          and not torch.cuda.is_current_stream_capturing())
-    return ok, task
+def _pgemm_wgrad(a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param, w_shape, G, want_bias):
+    r = pgemm_raw(a_src, x_srcs, B, H, W, taps, B // G, Cout, spec.kpad, dev, flops=2.0 * B * H * W * Cout * taps * spec.kreal,
+                  want_bias=want_bias)
+    return reduce_wgrad(r[0], r[1], G, taps, Cout, spec, dev, r[3] if want_bias else None, w_param, b_param if want_bias else None,
+                        w_shape)
 
 
 def wgrad_pgemm(a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param, w_shape, G=1, want_bias=True, keep=(), window=None):
     """Weight (+ bias) gradient through the pixel-reduction GEMM + its slab reduction, with reduce_wgrad's conventions.  Uses of one
     sink parameter inside a window are queued and merged like wgrad_wino's: the merged launch reads its operands through
     per-image pointer tables (bmc_src_t BMC_SRC_TABLE; bmc_ptr_table)."""
-    if G == 1:
-        ok, task = _mergeable(B, H, W, w_param, b_param, want_bias, keep, window)
-        if ok and B <= PTR_TABLE_MAX and all(x.batch_mod != -1 for x in x_srcs) and a_src.batch_mod != -1:
-            key = (id(w_param), "pg", taps, len(x_srcs), H, W, bool(want_bias))
-            _queue_use(key, lambda: _MergeQueue(spec, dev, w_param, b_param, want_bias, None, spec.covers_all, H, W, window,
-                                                pg=(taps, Cout, w_shape)),
-                       (a_src, list(x_srcs), B, tuple(keep), w_param, window), task, B * H * W)
-            return None, None
+    want_bias = bool(want_bias)
+    if G == 1 and _queue_use(False, a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param, w_shape, want_bias, None,
+                             spec.covers_all, keep, window):
+        return None, None
     with wgrad_side(B * H * W, _flat_params(w_param, b_param if want_bias else None), keep):
-        r = pgemm_raw(a_src, x_srcs, B, H, W, taps, B // G, Cout, spec.kpad, dev, flops=2.0 * B * H * W * Cout * taps * spec.kreal,
-                      want_bias=want_bias)
-        return reduce_wgrad(r[0], r[1], G, taps, Cout, spec, dev, r[3] if want_bias else None, w_param,
-                            b_param if want_bias else None, w_shape)
+        return _pgemm_wgrad(a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param, w_shape, G, want_bias)
 
 
 def wgrad_wino(a_src, x_src, B, H, W, spec, dev, w_param, b_param, w_shape, want_bias=True, k0=None, full=None, keep=(), window=None):
     """(dW, db) of a convolution wino_wgrad_ok() accepted, with reduce_wgrad's conventions: None where the sums went straight
     into a leaf parameter's .grad.  k0 / full: the launch covers only the weight columns [k0, k0 + 128) of a wider convolution
-    (one 128-channel source of a multi-source launch: split_wgrad_ok).  window: the recurrent window the use belongs to
+    (one 128-channel source of a multi-source launch: split_wgrad).  window: the recurrent window the use belongs to
     (current_window() at its forward) -- uses are merged within one window; None: not merged."""
-    ok, task = _mergeable(B, H, W, w_param, b_param, want_bias, keep, window)
-    if ok and not wgrad_wino4_ok(B, H, W):
-        k0_ = spec.kmap_host[0] if k0 is None else k0
-        key = (id(w_param), k0_, H, W, bool(want_bias))
-        _queue_use(key, lambda: _MergeQueue(spec, dev, w_param, b_param, want_bias, k0_, spec.covers_all if full is None else full, H, W,
-                                            window),
-                   (a_src, x_src, B, tuple(keep), w_param, window), task, B * H * W)
+    want_bias = bool(want_bias)
+    k0 = spec.kmap_host[0] if k0 is None else k0
+    full = spec.covers_all if full is None else full
+    if _queue_use(True, a_src, [x_src], B, H, W, 9, 128, spec, dev, w_param, b_param, w_shape, want_bias, k0, full, keep, window):
         return None, None
     with (wgrad_side(B * H * W, [w_param, b_param] if want_bias else [w_param], keep) if w_param is not None else _NOCTX):
-        return _wgrad_wino(a_src, x_src, B, H, W, spec, dev, w_param, b_param, w_shape, want_bias, k0, full)
+        return _wgrad_wino([a_src], [x_src], [B], H, W, spec, dev, w_param, b_param, w_shape, want_bias, k0, full)
 
 
-def _wgrad_wino(a_src, x_src, B, H, W, spec, dev, w_param, b_param, w_shape, want_bias, k0, full):
-    # a_src / x_src / B: one operand pair, or lists of them (a merged launch: several uses of one weight)
-    multi = isinstance(a_src, (list, tuple))
-    Bt = sum(B) if multi else B
-    f4 = not multi and wgrad_wino4_ok(B, H, W)
-    if f4:
+def _wgrad_wino(a_srcs, x_srcs, Bs, H, W, spec, dev, w_param, b_param, w_shape, want_bias, k0, full):
+    """One launch + reduction over the (dY, x) pairs of `a_srcs` / `x_srcs` with Bs[i] images each: one pair takes the
+    single-use entry points (F(4x4) where wgrad_wino4_ok), several (a merged launch: uses of one sink weight) bmc_wgrad_wino_multi."""
+    n, Bt = len(a_srcs), sum(Bs)
+    if n == 1 and wgrad_wino4_ok(Bt, H, W):
         f_ns, f_main, f_red, nm, npos, kind = lib._ww4_nsplit, lib._ww4, lib._ww4_red, "bmc_wgrad_wino4", 36, "wgrad_wino4<9>"
     else:
         f_ns, f_main, f_red, nm, npos, kind = lib._ww_nsplit, lib._ww, lib._ww_red, "bmc_wgrad_wino", 16, "wgrad_wino<9>"
     nsplit = f_ns(Bt, H, W)
     part = torch.empty(nsplit * npos * 128 * 128, device=dev, dtype=torch.float32)
     bpart = torch.empty(nsplit * 128, device=dev, dtype=torch.float32) if want_bias else None
+    bpart_p = bpart.data_ptr() if want_bias else None
     _on_side(part, bpart)
     e0 = _prof_begin()
-    if multi:
-        n = len(a_src)
-        lib.call(lib._ww_multi, "bmc_wgrad_wino_multi", (lib.Src * n)(*a_src), (lib.Src * n)(*x_src), (C.c_int * n)(*B), n, H, W, nsplit,
-                 part.data_ptr(), bpart.data_ptr() if want_bias else None, _stream())
+    if n > 1:
+        lib.call(lib._ww_multi, "bmc_wgrad_wino_multi", (lib.Src * n)(*a_srcs), (lib.Src * n)(*x_srcs), (C.c_int * n)(*Bs), n, H, W, nsplit,
+                 part.data_ptr(), bpart_p, _stream())
     else:
-        lib.call(f_main, nm, C.byref(a_src), C.byref(x_src), B, H, W, nsplit, part.data_ptr(),
-                 bpart.data_ptr() if want_bias else None, _stream())
+        lib.call(f_main, nm, C.byref(a_srcs[0]), C.byref(x_srcs[0]), Bt, H, W, nsplit, part.data_ptr(), bpart_p, _stream())
     _prof_end(e0, kind, 2.0 * Bt * H * W * 128 * 9 * 128, 4.0 * Bt * H * W * 256 + 4.0 * part.numel())
-    k0 = spec.kmap_host[0] if k0 is None else k0
-    full = spec.covers_all if full is None else full
     sg = sink_group([w_param, b_param] if want_bias else [w_param], full) if w_param is not None else None
     if sg is not None:
         (gw, *rest), acc = sg
-        lib.call(f_red, nm + "_reduce", part.data_ptr(), nsplit, gw.data_ptr(), spec.cin, k0, acc,
-                 bpart.data_ptr() if want_bias else None, rest[0].data_ptr() if want_bias else None, _stream())
+        lib.call(f_red, nm + "_reduce", part.data_ptr(), nsplit, gw.data_ptr(), spec.cin, k0, acc, bpart_p,
+                 rest[0].data_ptr() if want_bias else None, _stream())
         return None, None
-    assert not multi
+    assert n == 1
     dw = (torch.empty if full else torch.zeros)(128 * spec.cin * 9, device=dev, dtype=torch.float32)
     db = torch.empty(128, device=dev, dtype=torch.float32) if want_bias else None
-    lib.call(f_red, nm + "_reduce", part.data_ptr(), nsplit, dw.data_ptr(), spec.cin, k0, 0,
-             bpart.data_ptr() if want_bias else None, db.data_ptr() if want_bias else None, _stream())
+    lib.call(f_red, nm + "_reduce", part.data_ptr(), nsplit, dw.data_ptr(), spec.cin, k0, 0, bpart_p,
+             db.data_ptr() if want_bias else None, _stream())
     return dw.view(w_shape), db
 
 
@@ -876,6 +875,109 @@ def split_wgrad(spec, metas):
         res = (big, rest, sub)
     cache[key] = res
     return res or None
+
+
+def wgrad_route(spec, a_src, x_srcs, metas, taps, Cout, G, w_param, b_param=None, want_bias=False):
+    """Which kernels compute this weight gradient?  -> (route, split_wgrad's result for "split" else None); decided here ONCE for
+    every autograd node, from the geometry, the parameters and the switches WINO / WINO_WGRAD / MATH alone (no launch, no
+    allocation, nothing that needs a GPU):
+      "split"        multi-source 3x3 -> 128 on sink parameters (metas: the sources' view metas; None: the caller has none, no
+                     split): its dense 128-channel sources each through the Winograd kernel, the narrow rest through ONE
+                     pixel-reduction launch, all adding into the same .grad (the first zero-fills it: none defines every column)
+      "wino"         what wino_wgrad_ok accepts, for ONE parameter (sink or not: the result may go back to autograd)
+      "wino_groups"  a grouped launch over 2 .. 4 separate parameters (conv_groups: conv_hp / conv_hn): one Winograd weight
+                     gradient per group, on the group's batch window of both operands
+      "pgemm"        everything else (1x1, narrow or grouped-weight launches, no parameter, the bf16 modes)."""
+    if not (WINO and WINO_WGRAD and MATH == 0 and taps == 9 and Cout == 128) or w_param is None:
+        return "pgemm", None
+    if isinstance(w_param, (tuple, list)):
+        if (1 < G <= 4 and len(w_param) == G and metas is not None and metas[0][2] == 0 and metas[0][3] is None
+                and wino_wgrad_ok(a_src, x_srcs, spec, taps, Cout, 1)):
+            return "wino_groups", None
+        return "pgemm", None
+    if (G == 1 and len(x_srcs) > 1 and metas is not None and is_sink(w_param) and (not want_bias or is_sink(b_param))
+            and a_src.pix_stride == 128 and all(x.pix_stride == 128 for x, n in zip(x_srcs, spec.nch) if n == 128)):
+        sp = split_wgrad(spec, metas)
+        if sp is not None:
+            return "split", sp
+    return ("wino" if wino_wgrad_ok(a_src, x_srcs, spec, taps, Cout, G) else "pgemm"), None
+
+
+def _batch_window(s: lib.Src, b0, nb) -> lib.Src:
+    """Launch batches [b0, b0 + nb) of an operand without a batch map, as an operand of its own."""
+    w = lib.Src()
+    w.ptr, w.batch_stride, w.pix_stride, w.nch = s.ptr + 4 * b0 * s.batch_stride, s.batch_stride, s.pix_stride, s.nch
+    w.batch_shift, w.batch_mod = 0, max(nb, 1)
+    return w
+
+
+def wgrad(a_src, x_srcs, spec, B, H, W, taps, Cout, dev, w_param, b_param, G=1, w_shape=None, keep=(), window=None, *, metas=None,
+          want_bias=True, merge_pgemm):
+    """Weight gradient + bias gradient (column sums of the same A operand) of one convolution use, by wgrad_route's kernels
+    -> (dW, db) for autograd; None where the sums went straight into the leaf parameters' .grad (reduce_wgrad).  For the
+    "wino_groups" route: two lists of the per-group results (the caller re-stacks them: conv_groups' convention).
+    w_param / b_param: a parameter, None, or for G > 1 a tuple of the G parameters of the weight groups (w_param None: result
+    [G, ...]).  keep: the tensors behind a_src and (with metas: one per source, in order) x_srcs (wgrad_side: the launches
+    may run on the side stream).  merge_pgemm: queue pixel-reduction uses for merging (wgrad_pgemm) -- the fused nodes
+    (ResBlockFn, the BIE) do, ConvFn does not: its pixel-reduction launches have never been merged, and changing that is a
+    change of behaviour (summation order) for a pull request of its own."""
+    if not want_bias:
+        b_param = None
+    if w_shape is None:
+        w_shape = w_param.shape
+    route, sp = wgrad_route(spec, a_src, x_srcs, metas, taps, Cout, G, w_param, b_param, want_bias)
+    if route == "wino":
+        return wgrad_wino(a_src, x_srcs[0], B, H, W, spec, dev, w_param, b_param, w_shape, want_bias=want_bias, keep=keep, window=window)
+    if route == "split":
+        big, rest, sub = sp
+        for n, (i, k0) in enumerate(big):
+            first = want_bias and n == 0            # (the bias gradient rides on the first launch)
+            wgrad_wino(a_src, x_srcs[i], B, H, W, spec, dev, w_param, b_param if first else None, w_shape, want_bias=first, k0=k0,
+                       full=False, keep=(keep[0], keep[1 + i]), window=window)
+        if rest:
+            wgrad_pgemm(a_src, [x_srcs[i] for i in rest], B, H, W, taps, Cout, sub, dev, w_param, None, w_shape, want_bias=False, keep=keep)
+        return None, None
+    if route == "wino_groups":
+        bpg = B // G
+        outs = [wgrad_wino(_batch_window(a_src, gi * bpg, bpg), _batch_window(x_srcs[0], gi * bpg, bpg), bpg, H, W, spec, dev,
+                           w_param[gi], b_param[gi] if want_bias else None, w_param[gi].shape, want_bias=want_bias, keep=keep,
+                           window=window) for gi in range(G)]
+        return [o[0] for o in outs], [o[1] for o in outs]
+    return wgrad_pgemm(a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_param, w_shape, G=G, want_bias=want_bias, keep=keep,
+                       window=window if merge_pgemm else None)
+
+
+# --------------------------------------------------------------------------
+# the two convolution launchers: every node's forward-style and data-gradient launches
+# --------------------------------------------------------------------------
+def _launch_stride(srcs, Co, residual, mask):
+    # the widest pixel stride the launch addresses (wino_ok: the Winograd launchers' 32-bit offsets)
+    return max([x.pix_stride for x in srcs] + [Co] + [x.pix_stride for x in (residual, mask) if x is not None])
+
+
+def conv_launch(srcs, w4, spec, owner, bias, out, B, relu=False, residual=None, mask=None, bpg=None, accumulate=False,
+                out_b0=0, rule=None):
+    """Forward-style launch: out[out_b0 : out_b0+B] = epi(conv(cat(srcs)) + bias), w4 [G,Cout,Cin,taps] (owner: the parameter
+    it was derived from, the pack-cache key, or None).  The kernel is decided ONCE here (wino_ok) for the pack and the launch."""
+    G, Cout, Cin, taps = w4.shape
+    _, H, W, Co = out.shape
+    wn = wino_ok(B, H, W, Cout, taps, fwd=not accumulate and mask is None, stride=_launch_stride(srcs, Co, residual, mask), rule=rule)
+    wp = _packed_weight(w4, spec, owner, wino=wn)
+    conv_raw(srcs, wp, spec.kpad * taps * coutpad(Cout), bias, Cout if bias is not None else 0,
+             out.data_ptr() + 4 * out_b0 * H * W * Co, H * W * Co, Co, B, H, W, Cout, taps, relu=relu, residual=residual,
+             bpg=bpg, accumulate=accumulate, mask=mask, flops=2.0 * B * H * W * Cout * taps * spec.kreal, wino=wn)
+
+
+def dgrad_launch(g_src, w4, spec, src_index, owner, out, B, residual=None, mask=None, bpg=None, accumulate=False, out_b0=0, out_c0=0):
+    """Data gradient w.r.t. source `src_index` of the conv with weights w4: out[out_b0:+B, :, :, out_c0:+nch] (=|+=) conv^T(g)."""
+    G, Cout, Cin, taps = w4.shape
+    _, H, W, Co = out.shape
+    nch = spec.nch[src_index]
+    wn = wino_ok(B, H, W, nch, taps, stride=_launch_stride([g_src], Co, residual, mask))
+    wt = _packed_weight_t(w4, spec, src_index, owner, wino=wn)
+    conv_raw([g_src], wt, round_up(Cout, CK) * taps * coutpad(nch), None, 0, out.data_ptr() + 4 * (out_b0 * H * W * Co + out_c0),
+             H * W * Co, Co, B, H, W, nch, taps, residual=residual, mask=mask, bpg=bpg, accumulate=accumulate,
+             flops=2.0 * B * H * W * spec.real_nch[src_index] * taps * Cout, wino=wn)
 
 
 def relu_bwd(dy, y):
@@ -1247,9 +1349,6 @@ class ConvFn(torch.autograd.Function):
         w4 = weight.detach().reshape(G, -1, meta.spec.cin, taps)
         Cout = w4.shape[1]
         ck = weight if meta.cache else None
-        wn = wino_ok(B, H, W, Cout, taps, fwd=True, stride=max([t.shape[3] for t in src_ts] + [res_t.shape[3] if res_t is not None else 0]),
-                     rule=meta.rule if meta.rule is not None else bias)
-        wp = _packed_weight(w4.contiguous(), meta.spec, ck, wino=wn)
         if meta.out is not None:       # write into a batch range of a preallocated buffer (see OutSlot)
             out = meta.out.t[meta.out.b0:meta.out.b0 + B]
             assert out.shape == (B, H, W, Cout) and out.is_contiguous()
@@ -1259,10 +1358,8 @@ class ConvFn(torch.autograd.Function):
         res = None
         if res_t is not None:
             res = _src(res_t.detach(), 0, Cout, meta.res[0], meta.res[1], 0, B)
-        cp = coutpad(Cout)
-        conv_raw(srcs, wp, meta.spec.kpad * taps * cp, bias.detach() if bias is not None else None, Cout,
-                 out.data_ptr(), H * W * Cout, Cout, B, H, W, Cout, taps, relu=meta.relu, residual=res,
-                 bpg=B // G, flops=2.0 * B * H * W * Cout * taps * meta.spec.kreal, wino=wn)
+        conv_launch(srcs, w4.contiguous(), meta.spec, ck, bias.detach() if bias is not None else None, out, B, relu=meta.relu,
+                    residual=res, bpg=B // G, rule=meta.rule if meta.rule is not None else bias)
         ctx.meta = meta
         ctx.params = (weight, bias)  # the objects the caller passed (leaf parameters take their gradients directly)
         if meta.ngp:
@@ -1294,57 +1391,18 @@ class ConvFn(torch.autograd.Function):
             need[2] = any(need[4 + nsrc + G:])
         dw = db = dres = None
         bias_done = False
-        # ---- weight gradient: pixel-reduction GEMM  dW[co][k][tap] = sum_px g[px][co] * x[px+tap][k]
+        a_src = _src(g, 0, Cout, 0, None, 0, B)
+        # ---- weight gradient  dW[co][k][tap] = sum_px g[px][co] * x[px+tap][k]  (+ the bias gradient from the same launch)
         if need[1]:
-            srcs = [_src(t, *v, B) for t, v in zip(src_ts, meta.views)]
-            a_src = _src(g, 0, Cout, 0, None, 0, B)
             wb = ctx.has_bias and need[2]
             wp_, bp_ = ctx.params
-            v0 = meta.views[0]
-            sp = None
-            if (WINO and WINO_WGRAD and MATH == 0 and taps == 9 and G == 1 and Cout == 128 and nsrc > 1 and not ngp
-                    and is_sink(wp_) and (not wb or is_sink(bp_)) and a_src.pix_stride == 128
-                    and all(t.shape[3] == 128 for t, n in zip(src_ts, spec.nch) if n == 128)):
-                sp = split_wgrad(spec, meta.views)
-            if sp is not None:
-                # multi-source convolution on leaf parameters: the 128-channel sources through the Winograd kernel (each its own
-                # column window of the weight gradient), the narrow ones through one pixel-reduction launch; all of them add
-                # into the same .grad (the first one zero-fills it: none defines every column)
-                big, rest, sub = sp
-                for n, (i, k0) in enumerate(big):
-                    wgrad_wino(a_src, srcs[i], B, H, W, spec, dev, wp_, bp_ if (wb and n == 0) else None, weight.shape,
-                               want_bias=wb and n == 0, k0=k0, full=False, keep=(g, src_ts[i]), window=ctx.window)
-                if rest:
-                    with wgrad_side(B * H * W, [wp_], (g, *src_ts)):
-                        r_pg = pgemm_raw(a_src, [srcs[i] for i in rest], B, H, W, taps, B, Cout, sub.kpad, dev,
-                                         flops=2.0 * B * H * W * Cout * taps * sub.kreal)
-                        reduce_wgrad(r_pg[0], r_pg[1], 1, taps, Cout, sub, dev, None, wp_, None, weight.shape)
-                dw = db = None
-            elif wino_wgrad_ok(a_src, srcs, spec, taps, Cout, G) and not isinstance(wp_, (tuple, list)):
-                dw, db = wgrad_wino(a_src, srcs[0], B, H, W, spec, dev, wp_, bp_ if wb else None, weight.shape, want_bias=wb,
-                                    keep=(g, src_ts[0]), window=ctx.window)
-            elif (ngp and 1 < G <= 4 and len(wp_) == G and wino_wgrad_ok(a_src, srcs, spec, taps, Cout, 1) and v0[2] == 0
-                  and v0[3] is None):
-                # grouped launch over separate parameters (conv_hp / conv_hn): one Winograd weight gradient per group, on the
-                # group's batch window of both operands
-                bpg = B // G
-                outs = []
-                for gi in range(G):
-                    a_g = _src(g, 0, Cout, 0, None, gi * bpg, bpg)
-                    x_g = _src(src_ts[0], v0[0], v0[1], 0, None, v0[4] + gi * bpg, bpg)
-                    outs.append(wgrad_wino(a_g, x_g, bpg, H, W, spec, dev, wp_[gi], bp_[gi] if wb else None, wp_[gi].shape, want_bias=wb,
-                                           keep=(g, src_ts[0]), window=ctx.window))
-                dw = None if all(o[0] is None for o in outs) else torch.stack([
-                    o[0] if o[0] is not None else torch.zeros_like(wp_[i]) for i, o in enumerate(outs)])
-                db = None if (not wb or all(o[1] is None for o in outs)) else torch.stack([
-                    o[1] if o[1] is not None else torch.zeros_like(bp_[i]) for i, o in enumerate(outs)])
-            else:
-                with wgrad_side(B * H * W, _flat_params(wp_, bp_ if wb else None), (g, *src_ts)):
-                    r_pg = pgemm_raw(a_src, srcs, B, H, W, taps, B // G, Cout, spec.kpad, dev,
-                                     flops=2.0 * B * H * W * Cout * taps * spec.kreal, want_bias=wb)
-                    slabs, nsplit = r_pg[0], r_pg[1]
-                    dw, db = reduce_wgrad(slabs, nsplit, G, taps, Cout, spec, dev, r_pg[3] if wb else None, wp_,
-                                          bp_ if wb else None, weight.shape)
+            dw, db = wgrad(a_src, [_src(t, *v, B) for t, v in zip(src_ts, meta.views)], spec, B, H, W, taps, Cout, dev, wp_, bp_, G=G,
+                           w_shape=weight.shape, keep=(g, *src_ts), window=ctx.window, metas=meta.views, want_bias=wb, merge_pgemm=False)
+            if isinstance(dw, list):        # one result per group (wgrad_route's "wino_groups"): the stacked weight's gradient
+                dw = None if all(o is None for o in dw) else torch.stack([
+                    o if o is not None else torch.zeros_like(wp_[i]) for i, o in enumerate(dw)])
+                db = None if (not wb or all(o is None for o in db)) else torch.stack([
+                    o if o is not None else torch.zeros_like(bp_[i]) for i, o in enumerate(db)])
             bias_done = wb
         if ctx.has_bias and need[2] and not bias_done:
             bpg = B // G
@@ -1382,30 +1440,16 @@ class ConvFn(torch.autograd.Function):
                 dsrcs.append(None)
                 continue
             grp = shared_dx.get(id(t)) if simple(v) else None
-            if grp is not None:
-                c0, nch, shift, mod, b0 = v
-                Bt, _, _, Ct = t.shape
-                dxs_ = grp[1]
-                wn = wino_ok(B, H, W, nch, taps, stride=Ct)
-                wt = _packed_weight_t(w4, spec, i, ck, wino=wn)
-                conv_raw([_src(g, 0, Cout, 0, None, 0, B)], wt, round_up(Cout, CK) * taps * coutpad(nch), None, 0,
-                         dxs_.data_ptr() + 4 * (b0 * H * W * Ct + c0), H * W * Ct, Ct, B, H, W, nch, taps, bpg=B,
-                         flops=2.0 * B * H * W * spec.real_nch[i] * taps * Cout, wino=wn)
-                dsrcs.append(dxs_ if i == grp[0][0] else None)
-                continue
             c0, nch, shift, mod, b0 = v
             Bt, _, _, Ct = t.shape
-            c16 = round_up(Cout, CK)
-            nkpad = coutpad(nch)
-            gs, nb, gshift, gmod = g, B, 0, None
-            post = None
+            if grp is not None:
+                dgrad_launch(a_src, w4, spec, i, ck, grp[1], B, out_b0=b0, out_c0=c0)
+                dsrcs.append(grp[1] if i == grp[0][0] else None)
+                continue
             if G > 1 and ((mod is not None and mod < B) or shift):
                 # grouped weights + remapped operand: launch over the full batch, fold the batch map afterwards
                 tmp = torch.empty((B, H, W, nch), device=dev, dtype=torch.float32)
-                wn = wino_ok(B, H, W, nch, taps)
-                wt = _packed_weight_t(w4, spec, i, ck, wino=wn)
-                conv_raw([_src(g, 0, Cout, 0, None, 0, B)], wt, c16 * taps * nkpad, None, 0, tmp.data_ptr(), H * W * nch,
-                         nch, B, H, W, nch, taps, bpg=B // G, flops=2.0 * B * H * W * spec.real_nch[i] * taps * Cout, wino=wn)
+                dgrad_launch(a_src, w4, spec, i, ck, tmp, B, bpg=B // G)
                 if mod is not None and mod < B:
                     tmp = tmp.view(B // mod, mod, H, W, nch).sum(0)
                     if shift:
@@ -1420,6 +1464,7 @@ class ConvFn(torch.autograd.Function):
                     dx[b0:b0 + nbt, :, :, c0:c0 + nch] = tmp
                 dsrcs.append(dx)
                 continue
+            gs, nb, gshift, gmod = g, B, 0, None
             if mod is not None and mod < B:          # operand shared by several launch batches: sum first (linearity)
                 assert shift == 0
                 gs, nb = group_sum(g, B // mod), mod
@@ -1428,13 +1473,9 @@ class ConvFn(torch.autograd.Function):
                 gshift, gmod = (mod - shift) % mod, mod
             full = (c0 == 0 and nch == Ct and b0 == 0 and nb == Bt)
             dx = torch.empty_like(t) if full else torch.zeros_like(t)
-            gsrc = _src(gs, 0, Cout, gshift, gmod, 0, nb)
             if Cout % CK:
                 raise RuntimeError("bmc_hip: conv output channels must be a multiple of 16 for the data gradient")
-            wn = wino_ok(nb, H, W, nch, taps, stride=Ct)
-            wt = _packed_weight_t(w4, spec, i, ck, wino=wn)
-            conv_raw([gsrc], wt, c16 * taps * nkpad, None, 0, dx.data_ptr() + 4 * (b0 * H * W * Ct + c0), H * W * Ct, Ct,
-                     nb, H, W, nch, taps, bpg=nb // G, flops=2.0 * nb * H * W * spec.real_nch[i] * taps * Cout, wino=wn)
+            dgrad_launch(_src(gs, 0, Cout, gshift, gmod, 0, nb), w4, spec, i, ck, dx, nb, bpg=nb // G, out_b0=b0, out_c0=c0)
             dsrcs.append(dx)
         if ngp:      # gradients of the stacked weights' owners: None when they went straight into .grad, else the stack's slices
             wps, bps = ctx.params
@@ -1484,14 +1525,11 @@ def conv_groups(views: Sequence[View], weights, biases, spec: ConvSpec, *, B=Non
 # convolution epilogues, so the backward is exactly 2 data-gradient + 2 weight-gradient launches (+ bias sums)
 # --------------------------------------------------------------------------
 def _wgrad_plain(g, x, spec, w_param, b_param, taps, window=None):
-    """-> (dW, db) for autograd (None where accumulated into the leaf parameter's .grad): weight gradient and bias
-    gradient (column sums of g) from one pgemm launch."""
+    """ops.wgrad on whole tensors, g [B,H,W,Cout] and x [B,H,W,Cin] (ResBlockFn's two uses; the kernel tests and tools/time_wgrad.py
+    call it too): descriptors only, the routing is wgrad's."""
     B, H, W, Cout = g.shape
-    dev = g.device
-    a_src, x_src = _src(g, 0, Cout, 0, None, 0, B), _src(x, 0, x.shape[3], 0, None, 0, B)
-    if wino_wgrad_ok(a_src, [x_src], spec, taps, Cout, 1):
-        return wgrad_wino(a_src, x_src, B, H, W, spec, dev, w_param, b_param, w_param.shape, keep=(g, x), window=window)
-    return wgrad_pgemm(a_src, [x_src], B, H, W, taps, Cout, spec, dev, w_param, b_param, w_param.shape, keep=(g, x), window=window)
+    return wgrad(_src(g, 0, Cout, 0, None, 0, B), [_src(x, 0, x.shape[3], 0, None, 0, B)], spec, B, H, W, taps, Cout, g.device, w_param,
+                 b_param, keep=(g, x), window=window, merge_pgemm=True)
 
 
 class GradPair:
@@ -1540,18 +1578,11 @@ class ResBlockFn(torch.autograd.Function):
         _need_gpu(x)
         B, H, W, Cn = x.shape
         taps = w1.shape[-1] * w1.shape[-2]
-        cp = coutpad(Cn)
         xs = _src(x.detach(), 0, Cn, 0, None, 0, B)
-        wn1, wn2 = wino_ok(B, H, W, Cn, taps, fwd=True, rule=b1), wino_ok(B, H, W, Cn, taps, fwd=True, rule=b2)
-        wp1 = _packed_weight(w1.detach().reshape(1, Cn, Cn, taps), spec, w1, wino=wn1)
-        wp2 = _packed_weight(w2.detach().reshape(1, Cn, Cn, taps), spec, w2, wino=wn2)
-        fl = 2.0 * B * H * W * Cn * taps * Cn
         t = torch.empty_like(x)
-        conv_raw([xs], wp1, spec.kpad * taps * cp, b1.detach(), Cn, t.data_ptr(), H * W * Cn, Cn, B, H, W, Cn, taps, relu=True,
-                 flops=fl, wino=wn1)
+        conv_launch([xs], w1.detach().reshape(1, Cn, Cn, taps), spec, w1, b1.detach(), t, B, relu=True, rule=b1)
         y = torch.empty_like(x) if out is None else out.t[out.b0:out.b0 + B]
-        conv_raw([_src(t, 0, Cn, 0, None, 0, B)], wp2, spec.kpad * taps * cp, b2.detach(), Cn, y.data_ptr(), H * W * Cn, Cn, B, H,
-                 W, Cn, taps, residual=xs, flops=fl, wino=wn2)
+        conv_launch([_src(t, 0, Cn, 0, None, 0, B)], w2.detach().reshape(1, Cn, Cn, taps), spec, w2, b2.detach(), y, B, residual=xs, rule=b2)
         ctx.save_for_backward(x, t, w1, w2)
         ctx.spec, ctx.taps = spec, taps
         ctx.owners = (w1, w2)
@@ -1566,26 +1597,19 @@ class ResBlockFn(torch.autograd.Function):
         spec, taps = ctx.spec, ctx.taps
         g = g.contiguous()
         B, H, W, Cn = g.shape
-        dev = g.device
         need = ctx.needs_input_grad
-        fl = 2.0 * B * H * W * Cn * taps * Cn
-        gs = _src(g, 0, Cn, 0, None, 0, B)
-        nkpad, c16 = coutpad(Cn), round_up(Cn, CK)
+        gs, ts = _src(g, 0, Cn, 0, None, 0, B), _src(t, 0, Cn, 0, None, 0, B)
         p_w1, p_b1, p_w2, p_b2 = ctx.params
         dw2, db2 = _wgrad_plain(g, t, spec, p_w2, p_b2, taps, ctx.window) if (need[3] or need[4]) else (None, None)
         # d(pre-activation of conv1) = ReLU'(t) * conv2^T(g): mask epilogue
-        wn = wino_ok(B, H, W, Cn, taps)
-        w2t = _packed_weight_t(w2.detach().reshape(1, Cn, Cn, taps), spec, 0, ctx.owners[1], wino=wn)
         dt = torch.empty_like(g)
-        conv_raw([gs], w2t, c16 * taps * nkpad, None, 0, dt.data_ptr(), H * W * Cn, Cn, B, H, W, Cn, taps,
-                 mask=_src(t, 0, Cn, 0, None, 0, B), flops=fl, wino=wn)
+        dgrad_launch(gs, w2.detach().reshape(1, Cn, Cn, taps), spec, 0, ctx.owners[1], dt, B, mask=ts)
+        dts = _src(dt, 0, Cn, 0, None, 0, B)
         dw1, db1 = _wgrad_plain(dt, x, spec, p_w1, p_b1, taps, ctx.window) if (need[1] or need[2]) else (None, None)
         dx = None
         if need[0]:   # dx = conv1^T(dt) + g (skip path): residual epilogue
-            w1t = _packed_weight_t(w1.detach().reshape(1, Cn, Cn, taps), spec, 0, ctx.owners[0], wino=wn)
             dx = grad_slot(ctx.gslot, g)
-            conv_raw([_src(dt, 0, Cn, 0, None, 0, B)], w1t, c16 * taps * nkpad, None, 0, dx.data_ptr(), H * W * Cn, Cn, B, H, W,
-                     Cn, taps, residual=gs, flops=fl, wino=wn)
+            dgrad_launch(dts, w1.detach().reshape(1, Cn, Cn, taps), spec, 0, ctx.owners[0], dx, B, residual=gs)
         return dx, dw1, db1, dw2, db2, None, None
 
 
@@ -1674,17 +1698,12 @@ class GramFn(torch.autograd.Function):
         spec = _dense_spec(Cn)
         ds = (datt * ctx.scale).contiguous()
         dc = dv = None
-        cp = coutpad(Cn)
         if ctx.needs_input_grad[0]:   # dc[px,i] = sum_j ds[i,j] v[px,j]
-            wp = _packed_weight(ds.view(B, Cn, Cn, 1), spec, None)
             dc = torch.empty_like(c)
-            conv_raw([_src(v, 0, Cn, 0, None, 0, B)], wp, spec.kpad * cp, None, 0, dc.data_ptr(), H * W * Cn, Cn, B, H, W,
-                     Cn, 1, bpg=1, flops=2.0 * B * H * W * Cn * Cn)
+            conv_launch([_src(v, 0, Cn, 0, None, 0, B)], ds.view(B, Cn, Cn, 1), spec, None, None, dc, B, bpg=1)
         if ctx.needs_input_grad[1]:   # dv[px,j] = sum_i ds[i,j] c[px,i]
-            wp = _packed_weight(ds.transpose(1, 2).contiguous().view(B, Cn, Cn, 1), spec, None)
             dv = torch.empty_like(v)
-            conv_raw([_src(c, 0, Cn, 0, None, 0, B)], wp, spec.kpad * cp, None, 0, dv.data_ptr(), H * W * Cn, Cn, B, H, W,
-                     Cn, 1, bpg=1, flops=2.0 * B * H * W * Cn * Cn)
+            conv_launch([_src(c, 0, Cn, 0, None, 0, B)], ds.transpose(1, 2).contiguous().view(B, Cn, Cn, 1), spec, None, None, dv, B, bpg=1)
         return dc, dv, None
 
 

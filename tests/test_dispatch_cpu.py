@@ -132,3 +132,57 @@ def test_bf16_kernel_cases_cover_every_tile_and_both_tap_row_sides():
     assert T.conv_tile(4, 90, 120, 128, 256) == (128, 4) and T.conv_tile(8, 90, 120, 32, 256) == (32, 8)
     assert {c[-1] for c in T.WGRAD_CASES} == {1, 3} and {c[4] for c in T.WGRAD_CASES} >= {16, 48, 160}
     assert any(c[5] == 2 for c in T.WGRAD_CASES) and any(len(c[3]) > 1 for c in T.WGRAD_CASES)
+
+
+def test_wgrad_route_table(monkeypatch):
+    """ops.wgrad_route: the one weight-gradient decision of every autograd node, as a table (read off the routing of ConvFn,
+    ResBlockFn and the BIE nodes; no launch, no GPU).  Every case goes to the pixel-reduction GEMM in a bf16 mode and with the
+    Winograd weight gradient switched off."""
+    from bmc_hip import ops
+    monkeypatch.setattr(ops, "WINO", True)
+    monkeypatch.setattr(ops, "WINO_WGRAD", True)
+    monkeypatch.setattr(ops, "MATH", 0)
+    monkeypatch.setattr(ops, "ACCUM_PARAM_GRADS", True)
+    B, H, W = 2, 8, 16
+    leaf = lambda *shape: torch.nn.Parameter(torch.zeros(*shape))
+    derived = lambda *shape: leaf(*shape) * 1.0                       # a non-leaf weight: its gradient goes back to autograd
+
+    def operands(widths, views=None, Cout=128):
+        """-> (a_src, x_srcs, metas) for dense source tensors of these channel widths (views: View keywords per source)."""
+        vs = [ops.View(torch.zeros(B, H, W, n), **(views[i] if views else {})) for i, n in enumerate(widths)]
+        metas = [v.meta() for v in vs]
+        return ops._src(torch.zeros(B, H, W, Cout), 0, Cout, 0, None, 0, B), [ops._src(v.t, *m, B) for v, m in zip(vs, metas)], metas
+
+    one = ops.ConvSpec.dense(128)
+    cases = []          # (name, expected route, expected (big sources, rest) of a split, arguments of wgrad_route)
+
+    def case(name, want, spec, widths, w, b=None, taps=9, Cout=128, G=1, views=None, split=None):
+        a, xs, metas = operands(widths, views, Cout)
+        cases.append((name, want, split, (spec, a, xs, metas, taps, Cout, G, w, b, b is not None)))
+
+    case("dense 128 -> 128", "wino", one, [128], leaf(128, 128, 3, 3), leaf(128))
+    case("128 + 128 + 16 + 16", "split", ops.ConvSpec.dense(128, 128, 16, 16), [128, 128, 16, 16], leaf(128, 288, 3, 3), leaf(128),
+         split=([0, 1], [2, 3]))
+    case("128 + 16", "split", ops.ConvSpec.dense(128, 16), [128, 16], leaf(128, 144, 3, 3), leaf(128), split=([0], [1]))
+    case("two stacked per-group parameters", "wino_groups", one, [128], (leaf(128, 128, 3, 3), leaf(128, 128, 3, 3)),
+         (leaf(128), leaf(128)), G=2)
+    case("1x1", "pgemm", one, [128], leaf(128, 128, 1, 1), leaf(128), taps=1)
+    case("Cout = 32", "pgemm", one, [128], leaf(32, 128, 3, 3), leaf(32), Cout=32)
+    # wino_wgrad_ok does not look at the batch map (the Winograd kernels read their operands through the same descriptors)
+    case("batch modulus", "wino", one, [128], leaf(128, 128, 3, 3), leaf(128), views=[dict(mod=1)])
+    case("multi-source, non-leaf weight", "pgemm", ops.ConvSpec.dense(128, 16), [128, 16], derived(128, 144, 3, 3))
+    case("single source, non-leaf weight", "wino", one, [128], derived(128, 128, 3, 3))
+    case("no parameter", "pgemm", one, [128], None)
+    for name, want, split, args in cases:
+        route, sp = ops.wgrad_route(*args)
+        assert route == want, name
+        assert (sp is None) == (want != "split"), name
+        if split is not None:
+            big, rest, sub = sp
+            assert ([i for i, _ in big], rest) == split and sub.nch == [args[0].nch[i] for i in rest], name
+    assert ops.wino_wgrad_ok(*cases[6][3][1:3], one, 9, 128, 1)          # the batch-modulus case: what is pinned above
+    for switch, value in (("MATH", 1), ("WINO_WGRAD", False)):
+        with monkeypatch.context() as mp:
+            mp.setattr(ops, switch, value)
+            for name, _, _, args in cases:
+                assert ops.wgrad_route(*args) == ("pgemm", None), (switch, name)

@@ -53,8 +53,8 @@ for n in (4, 8):
     st = torch.empty(B2 * H * W * 2, device=dev)
 
     def unfused():
-        bie._conv([X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], wf.detach().reshape(1, Cn, 2 * Cn, 1), s2, wf, bf, z, B2)
+        ops.conv_launch([X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], wf.detach().reshape(1, Cn, 2 * Cn, 1), s2, wf, bf, z, B2)
         lib.call(lib._ln_fwd, "ln", z.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B2 * H * W, Cn, 1e-6, y.data_ptr(), st.data_ptr(), _stream())
-        bie._conv([X(y)], wc.detach().reshape(1, Cn, Cn, 1), s1, wc, bc, cc, B2)
+        ops.conv_launch([X(y)], wc.detach().reshape(1, Cn, Cn, 1), s1, wc, bc, cc, B2)
     tu = timeit(unfused)
     print("       unfused fwd (conv, LN, conv) %.3f ms (%.1f TF)" % (tu, flop / tu / 1e9), flush=True)
