@@ -373,3 +373,29 @@ def counts_to_events(pred, max_count=255, times=None, spans=None):
         return xs, ys, ps, ts, index
     run(xs, ys, ps, total)
     return xs, ys, ps, index
+
+
+def encode_sequences(table, B, L, lr_size, gt_size, out=None):
+    """The training batch of a DEVICE table of B bmc_seq_sample_t entries (uint8 tensor; event_dataset.SEQ_SAMPLE_DTYPE) ->
+    (inp_cnt [B,L,2,H,W], gt_cnt [B,L,2,gh,gw]) float32: ONE bmc_seq_encode launch on the current stream (include/bmc_hip.h
+    "sequence encoder for training").  The ranges of the table are trusted: event_dataset.EventTrainSet checks them when a
+    recording is added.  out: (inp_cnt, gt_cnt) to write into instead of new tensors."""
+    B, L = int(B), int(L)
+    (H, W), (gh, gw) = (int(v) for v in lr_size), (int(v) for v in gt_size)
+    if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous()):
+        raise RuntimeError("encode_sequences: the table must be a contiguous uint8 tensor on the MI355X (no CPU fallback in this build)")
+    if B < 1 or table.numel() < B * SEQ_SAMPLE_BYTES or table.data_ptr() % 8:
+        raise ValueError("encode_sequences: the table holds fewer than %d entries of %d bytes (8-byte aligned)" % (B, SEQ_SAMPLE_BYTES))
+    shapes = ((B, L, 2, H, W), (B, L, 2, gh, gw))
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.float32, device=table.device) for s in shapes)
+    for t, s in zip(out, shapes):
+        if not (t.is_cuda and t.device == table.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == s):
+            raise ValueError("encode_sequences: out must be contiguous float32 tensors %s and %s on the table's device" % shapes)
+    with torch.cuda.device(table.device):
+        lib.call(lib._seq_encode, "bmc_seq_encode", table.data_ptr(), B, L, H, W, gh, gw, out[0].data_ptr(), out[1].data_ptr(),
+                 ops._stream())
+    return out[0], out[1]
+
+
+SEQ_SAMPLE_BYTES = 1112          # sizeof(bmc_seq_sample_t)

@@ -148,6 +148,7 @@ _slot_hot_update = _sig("bmc_slot_hot_update", [_p, _p, _i, _i, _i, _i, _i, _i, 
 _slot_encode_filtered = _sig("bmc_slot_encode_filtered", [_p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
 _hot_pixel_mask = _sig("bmc_hot_pixel_mask", [_p, _i, _i, _i, _i, _f, _p, _p, _p])
 _slot_render = _sig("bmc_slot_render", [_p, _p, _i, _i, _i, _i, _i, _p, _p])
+_seq_encode = _sig("bmc_seq_encode", [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
 
 EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_events_to_voxel", "bmc_events_to_stack", "bmc_encode_raw_events", "bmc_pack_weight", "bmc_pack_weight_t", "bmc_split_weight", "bmc_conv",
            "bmc_pgemm", "bmc_pgemm_wave_map", "bmc_pgemm_reduce_weight", "bmc_pgemm_reduce_plain", "bmc_colsum", "bmc_relu_bwd",
@@ -162,7 +163,7 @@ EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_event
            "bmc_wgrad_wino4_nsplit", "bmc_wgrad_wino4", "bmc_wgrad_wino4_reduce", "bmc_wgrad_wino_multi", "bmc_ptr_table",
            "bmc_conv_wino_rows", "bmc_slot_stage", "bmc_slot_commit", "bmc_slot_metrics", "bmc_slot_encode", "bmc_slot_emit",
            "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes", "bmc_slot_emit_clocked", "bmc_slot_hot_update",
-           "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render"]
+           "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_seq_encode"]
 
 
 def check(rc, what):

@@ -1,0 +1,120 @@
+// Sequence encoder for training (bmcnet-esr_amd/event_dataset.py::EventTrainSet.batch): recordings stay on the GPU as raw
+// dataset columns and bmc_seq_encode builds, in ONE launch per batch, every LR and HR count image of B sequences of L items in
+// the collate layout -- what SequenceDataset.__getitem__ (dataloader/h5dataset.py:666-700) has H5Dataset.__getitem__ (:261-316)
+// do per item in the loader's worker processes: flips shared by the sequence, paused items, noise events.  The contract:
+// include/bmc_hip.h "sequence encoder for training".
+//
+// The scheme is slot_events.hip's (slot_encode_k.h): a workgroup owns a band of R rows (both channels) of one output frame,
+// zeroes it in LDS, scans the frame's events -- ys first, xs / ps only for events that can land in the band -- counts with
+// integer LDS atomics and stores the band once; the store is the zero fill.  No global atomics, no memset, no workgroup waits
+// for another; counts are integers, so the result does not depend on the order of the atomics.  The differences: a frame per
+// item for the ground truth too, the flips applied to the int16 coordinates and the polarity before the range test, a
+// paused LR item that scans nothing, and the sample's noise events counted (unflipped) on top of every LR item that runs.
+#include "bmc_common.h"
+#include "slot_encode_k.h"
+
+namespace {
+
+// One event of a frame fh x fw whose row test has passed (or whose band holds row fh-1, `last`): the arithmetic of
+// slot_encode_body, on the flipped values.
+__device__ __forceinline__ void seq_count(unsigned* cnt, int x, bool yin, int row, float p, int fh, int fw, int r0, int rows, int n) {
+    const bool oob = !yin || x < 0 || x >= fw;
+    const bool neg = p < 0.f;
+    if (!(neg || (!oob && p > 0.f))) return;                         // an out-of-range positive (or p = 0) counts nowhere
+    const int rr = (oob ? fh - 1 : row) - r0;                        // reset coordinates (0, 0) -> [fh-1][0] of channel 1
+    if (rr < 0 || rr >= rows) return;
+    atomicAdd(&cnt[(neg ? n : 0) + rr * fw + (oob ? 0 : x)], (unsigned)(p * p));
+}
+
+// grid (L * (nb_lr + nb_gt), B): blockIdx.y is the sample, blockIdx.x a (frame, band): first the L * nb_lr LR bands, then the
+// L * nb_gt HR bands
+__global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* __restrict__ table, int L, int H, int W, int gh, int gw,
+                                                        int r_lr, int nb_lr, int r_gt, int nb_gt, float* __restrict__ inp_cnt,
+                                                        float* __restrict__ gt_cnt) {
+    __shared__ unsigned cnt[ENC_LDS];
+    const int s = blockIdx.y, tid = threadIdx.x;
+    const bmc_seq_sample_t* const ent = table + s;
+    const unsigned fl = gld<unsigned>(&ent->flips);
+    const short *xs, *ys;
+    const double* ps;
+    long long e0, e1;
+    int fh, fw, r0, rows, n_noise = 0;
+    float* out;
+    const int b = blockIdx.x;
+    if (b < L * nb_lr) {
+        const int t = b / nb_lr;
+        xs = gld<const short*>(&ent->lr_xs);
+        ys = gld<const short*>(&ent->lr_ys);
+        ps = gld<const double*>(&ent->lr_ps);
+        e0 = gld<long long>(&ent->lr_range[t][0]);
+        e1 = gld<long long>(&ent->lr_range[t][1]);
+        fh = H; fw = W; r0 = (b - t * nb_lr) * r_lr; rows = r_lr;
+        out = inp_cnt + ((long long)s * L + t) * 2 * H * W;
+        if ((gld<unsigned>(&ent->paused) >> t) & 1u) e1 = e0;        // a paused item: no events, no noise -> all +0.0
+        else n_noise = gld<int>(&ent->n_noise);
+    } else {
+        const int t = (b - L * nb_lr) / nb_gt;
+        xs = gld<const short*>(&ent->gt_xs);
+        ys = gld<const short*>(&ent->gt_ys);
+        ps = gld<const double*>(&ent->gt_ps);
+        e0 = gld<long long>(&ent->gt_range[t][0]);
+        e1 = gld<long long>(&ent->gt_range[t][1]);
+        fh = gh; fw = gw; r0 = (b - L * nb_lr - t * nb_gt) * r_gt; rows = r_gt;
+        out = gt_cnt + ((long long)s * L + t) * 2 * gh * gw;
+    }
+    if (r0 + rows > fh) rows = fh - r0;
+    const int n = rows * fw;                                         // counters per channel: 2 * n <= ENC_LDS
+    for (int i = tid; i < 2 * n; i += ET) cnt[i] = 0u;
+    __syncthreads();
+    const bool last = r0 + rows == fh;                               // row fh-1 is where out-of-range negatives land
+    const bool fx = fl & 1u, fy = fl & 2u, fp = fl & 4u;
+    for (long long e = e0 + tid; e < e1; e += ET) {
+        // augment_event's float64 flip and event_formatting's float32 cast are exact on int16 values: integers throughout
+        int y = (int)gld<short>(ys + e);
+        if (fy) y = fh - 1 - y;
+        const bool yin = y >= 0 && y < fh;
+        const int row = fh - 1 - (yin ? y : 0);
+        if (!(last || (yin && row >= r0 && row < r0 + rows))) continue;
+        int x = (int)gld<short>(xs + e);
+        if (fx) x = fw - 1 - x;
+        float p = (float)gld<double>(ps + e);
+        if (fp) p = -p;
+        seq_count(cnt, x, yin, row, p, fh, fw, r0, rows, n);
+    }
+    if (n_noise > 0) {                                               // concatenated AFTER augment_event: never flipped
+        const short* const nx = gld<const short*>(&ent->noise_xs);
+        const short* const ny = gld<const short*>(&ent->noise_ys);
+        const signed char* const np = gld<const signed char*>(&ent->noise_ps);
+        for (int e = tid; e < n_noise; e += ET) {
+            const int y = (int)gld<short>(ny + e);
+            const bool yin = y >= 0 && y < fh;
+            const int row = fh - 1 - (yin ? y : 0);
+            if (!(last || (yin && row >= r0 && row < r0 + rows))) continue;
+            seq_count(cnt, (int)gld<short>(nx + e), yin, row, (float)gld<signed char>(np + e), fh, fw, r0, rows, n);
+        }
+    }
+    __syncthreads();
+    float* const o0 = out + (long long)r0 * fw;
+    float* const o1 = o0 + (long long)fh * fw;
+    for (int i = tid; i < n; i += ET) {
+        gst<float>(o0 + i, (float)cnt[i]);
+        gst<float>(o1 + i, (float)cnt[n + i]);
+    }
+}
+
+}  // namespace
+
+extern "C" int bmc_seq_encode(const bmc_seq_sample_t* table, int B, int L, int H, int W, int gh, int gw, float* inp_cnt, float* gt_cnt,
+                              bmc_stream_t s) {
+    BMC_CHECK_ARG(table && inp_cnt && gt_cnt && B >= 1 && B <= 65535 && L >= 2 && L <= BMC_SEQ_MAX_ITEMS && H > 0 && W > 0 &&
+                      gh > 0 && gw > 0,
+                  "bmc_seq_encode: bad arguments");
+    BMC_CHECK_ARG(2 * W <= ENC_LDS && 2 * gw <= ENC_LDS, "bmc_seq_encode: frames wider than %d pixels are not supported", ENC_LDS / 2);
+    const SlotEncodeGrid g = slot_encode_grid(H, W, gh, gw);
+    const long long gx = (long long)L * (g.nb_lr + g.nb_gt);
+    BMC_CHECK_ARG(gx < (1ll << 31), "bmc_seq_encode: too many bands");
+    hipLaunchKernelGGL(seq_encode_kernel, dim3((unsigned)gx, B), dim3(ET), 0, (hipStream_t)s, table, L, H, W, gh, gw, g.r_lr, g.nb_lr,
+                       g.r_gt, g.nb_gt, inp_cnt, gt_cnt);
+    BMC_CHECK_LAUNCH("bmc_seq_encode");
+    return 0;
+}

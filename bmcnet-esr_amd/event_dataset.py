@@ -1,0 +1,291 @@
+"""Training from recordings kept on the GPU as raw event columns: the training counterpart of MultiStreamSR.open_events.
+
+The reference trains from SequenceDataset (dataloader/h5dataset.py:637-700): per sequence L items of H5Dataset.__getitem__
+(:261-316), each an HDF5 slice, flips and an index_put_ scatter in a loader worker.  Here the recordings stay on the GPU as the
+dataset's raw columns (xs / ys int16, ps float64) and EventTrainSet.batch encodes every LR and HR frame of B sequences in ONE
+launch (csrc/seq_encode.hip, bmc_seq_encode; include/bmc_hip.h "sequence encoder for training" states the contract) into the
+collate layout train_step.bptt_step takes.  The host part is the reference's sequence sampling, bit for bit: the step size,
+the seed and the flips one sequence shares, the pause chain, the noise events (sequence_plan, noise_events).
+
+Out of scope, as in event_window_indices: HDF5 reading, the reference's 'time' / 'frame' modes, the hot-pixel filter (the
+reference never applies it in training)."""
+import random
+
+import numpy as np
+import torch
+
+MAX_ITEMS = 32           # BMC_SEQ_MAX_ITEMS
+MAX_BATCH = 65535
+MAX_WIDTH = 7680         # one row of both channels must fit a workgroup's LDS band
+SEQ_SAMPLE_DTYPE = np.dtype({
+    "names": ["lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps", "noise_xs", "noise_ys", "noise_ps", "n_noise", "flips", "paused",
+              "lr_range", "gt_range"],
+    "formats": ["<u8"] * 9 + ["<i4", "<u4", "<u4", ("<i8", (MAX_ITEMS, 2)), ("<i8", (MAX_ITEMS, 2))],
+    "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 88, 88 + 16 * MAX_ITEMS],
+    "itemsize": 88 + 32 * MAX_ITEMS})          # bmc_seq_sample_t
+ENCODE_LAUNCHES = 0      # bmc_seq_encode launches of this process
+
+
+def _augment_args(augment):
+    """None (off) or (mechanisms, probs): config['data_augment']['augment'] / ['augment_prob'] of the reference."""
+    if augment is None:
+        return None
+    try:
+        mechanisms, probs = augment
+        mechanisms, probs = tuple(mechanisms), tuple(float(p) for p in probs)
+    except (TypeError, ValueError):
+        raise ValueError("augment must be None or (mechanisms, probs)") from None
+    if len(probs) < len(mechanisms):
+        raise ValueError("augment: %d mechanisms, %d probabilities" % (len(mechanisms), len(probs)))
+    return mechanisms, probs
+
+
+def _pause_args(pause):
+    """None (off) or (proba_pause_when_running, proba_pause_when_paused)."""
+    if pause is None:
+        return None
+    try:
+        running, paused = pause
+        return float(running), float(paused)
+    except (TypeError, ValueError):
+        raise ValueError("pause must be None or (proba_pause_when_running, proba_pause_when_paused)") from None
+
+
+def _flags_on(rng, seed, mechanisms, probs):
+    """bmc_hip.encodings.augment_flags' rule on `rng`: augment_event (dataloader/h5dataset.py:559-578) re-seeds with seed,
+    seed + 1, seed + 2 for Horizontal / Vertical / Polarity and draws once each; other names are skipped, as there."""
+    flags = 0
+    for i, mech in enumerate(mechanisms):
+        bit = {"Horizontal": 0, "Vertical": 1, "Polarity": 2}.get(mech)
+        if bit is None:
+            continue
+        rng.seed(seed + bit)
+        if rng.random() < probs[i]:
+            flags |= 1 << bit
+    return flags
+
+
+def sequence_plan(i, length, L, step_size=None, augment=None, pause=None, rng=random):
+    """Sequence i of a recording of `length` items -> (seed, items, paused, flips): the L dataset items SequenceDataset.__getitem__
+    (dataloader/h5dataset.py:666-700) reads, which of them it reads with Pause=True, the seed it hands to every item and the
+    flip flags (bit0 horizontal, bit1 vertical, bit2 polarity) that seed gives.  Call for call on `rng` (the `random` module, or
+    a random.Random): rng.randint(0, 2**32) for the seed; for every item, with augmentation on, the re-seeding draws of
+    augment_event (the reference runs them twice per item, for the LR and the HR events: the second run leaves the same state
+    and is not repeated here); between the items, with pause on, the chain's rng.random(), the item counter not advancing on a
+    paused item (which is paired with the last item's ground truth).
+    Kept, not fixed: with augmentation on every item re-seeds rng, so all pause draws of a sequence are the same number -- the
+    second draw after rng.seed(seed + 2) when Polarity is the last mechanism.  Item 0 is never paused.
+    step_size None: L, as the reference.  augment: None or (mechanisms, probs); pause: None or (proba_pause_when_running,
+    proba_pause_when_paused).  L > length raises: the reference shortens that one sequence and its collate then fails."""
+    L, length = int(L), int(length)
+    step = L if step_size is None else int(step_size)
+    if L < 1 or step < 1:
+        raise ValueError("sequence_plan: L and step_size must be positive")
+    if L > length:
+        raise ValueError("sequence_plan: a sequence of L = %d items does not fit a recording of %d" % (L, length))
+    n = (length - L) // step + 1
+    if not 0 <= i < n:
+        raise IndexError("sequence_plan: sequence %d of %d" % (i, n))
+    augment, pause = _augment_args(augment), _pause_args(pause)
+    seed = rng.randint(0, 2 ** 32)
+    flips = 0
+    j, k = int(i) * step, 0
+    if augment is not None:
+        flips = _flags_on(rng, seed, *augment)
+    items, paused = [j], [False]
+    now = False
+    for _ in range(L - 1):
+        if pause is not None:
+            now = rng.random() < (pause[1] if now else pause[0])
+        if not now:
+            k += 1
+        items.append(j + k)
+        paused.append(now)
+        if augment is not None:
+            _flags_on(rng, seed, *augment)
+    return seed, items, paused, flips
+
+
+def noise_events(window, lr_size, seed, noise_level):
+    """The noise events H5Dataset.add_noise_event (dataloader/h5dataset.py:623-634) appends to every LR item of a sequence with
+    this seed -> (xs int16, ys int16, ps int8) numpy columns of int(window * noise_level) events: x = int(u0 * W), y = int(u1 * H),
+    p = +-1 from u3, u = torch.rand([4, n]).  A local torch.Generator seeded with `seed` draws the same values as the reference's
+    torch.manual_seed(seed) and leaves the global generator alone.  The float32 product can round up to W (or H): such an event
+    is out of range and counts as one.  The columns are small integers and are made on the host."""
+    H, W = (int(v) for v in lr_size)
+    n = int(window * noise_level)
+    g = torch.Generator()
+    g.manual_seed(int(seed))
+    u = torch.rand([4, n], generator=g)
+    xs = (u[0] * W).int().to(torch.int16).numpy()
+    ys = (u[1] * H).int().to(torch.int16).numpy()
+    ps = ((u[3] * 2).int() * 2 - 1).to(torch.int8).numpy()
+    return xs, ys, ps
+
+
+def _index_table(who, name, idx, n):
+    a = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx)
+    if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
+        raise ValueError(who + "%s must be an integer [L,2] table (got %s %s)" % (name, a.dtype, a.shape))
+    a = a.astype(np.int64)
+    if (a[:, 0] > a[:, 1]).any():
+        raise ValueError(who + "%s has a range with first > end" % name)
+    if a.size and (a.min() < 0 or a.max() > n):
+        raise ValueError(who + "%s has a range outside the %d events of its columns" % (name, n))
+    return a
+
+
+class EventTrainSet:
+    """Recordings on the GPU as raw event columns -> training batches of count images, one launch per batch.
+
+    L, step_size, augment, pause as sequence_plan; add_noise: None or the reference's noise_level; window: the LR events per
+    item the noise count is taken from (config['window']).  Sequence indices run over the recordings in the order they were
+    added, (length - L) // step_size + 1 each, as ConcatDataset over SequenceDataset."""
+    RING = 2
+
+    def __init__(self, L=9, step_size=None, augment=None, pause=None, add_noise=None, window=2048):
+        self.L = int(L)
+        if not 2 <= self.L <= MAX_ITEMS:
+            raise ValueError("EventTrainSet: 2 <= L <= %d (got %d)" % (MAX_ITEMS, self.L))
+        self.step_size = self.L if step_size is None else int(step_size)
+        if self.step_size < 1:
+            raise ValueError("EventTrainSet: step_size must be positive")
+        self.augment, self.pause = _augment_args(augment), _pause_args(pause)
+        self.noise_level = None if add_noise is None else float(add_noise)
+        self.window = int(window)
+        self.n_noise = 0 if self.noise_level is None else int(self.window * self.noise_level)
+        self._recs, self._ends, self._size, self._device = [], [], None, None
+        self._pinned, self._events, self._table, self._k = None, [None] * self.RING, None, 0
+
+    # ------------------------------------------------------------------ recordings
+    def add_recording(self, lr, gt, lr_index, gt_index, lr_size, gt_size):
+        """One recording -> its number.  lr, gt = (xs, ys, ps): 1-D int16, int16, float64 GPU tensors, polarities -1 / 0 / +1;
+        lr_index, gt_index [length,2] integer tables on the host (bmc_hip.encodings.event_window_indices gives the reference's);
+        every range is checked here against the column lengths: the kernel trusts the table.  All recordings share one pair
+        of sizes."""
+        who = "EventTrainSet.add_recording: "
+        for name, cols in (("lr", lr), ("gt", gt)):
+            if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
+                raise ValueError(who + "%s must be three tensors (xs, ys, ps)" % name)
+            if [t.dtype for t in cols] != [torch.int16, torch.int16, torch.float64]:
+                raise ValueError(who + "%s columns must be int16, int16, float64 (got %s)" % (name, [t.dtype for t in cols]))
+            if any(t.dim() != 1 or t.numel() != cols[0].numel() or not t.is_contiguous() for t in cols):
+                raise ValueError(who + "%s columns must be contiguous 1-D tensors of one length" % name)
+        lr_index = _index_table(who, "lr_index", lr_index, lr[0].numel())
+        gt_index = _index_table(who, "gt_index", gt_index, gt[0].numel())
+        if len(lr_index) != len(gt_index):
+            raise ValueError(who + "lr_index has %d rows, gt_index %d" % (len(lr_index), len(gt_index)))
+        if len(lr_index) < self.L:
+            raise ValueError(who + "%d items, fewer than one sequence of L = %d" % (len(lr_index), self.L))
+        try:
+            (H, W), (gh, gw) = (int(v) for v in lr_size), (int(v) for v in gt_size)
+        except (TypeError, ValueError):
+            raise ValueError(who + "lr_size = (H, W) and gt_size = (gh, gw)") from None
+        if min(H, W, gh, gw) < 1 or max(W, gw) > MAX_WIDTH:
+            raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)" % (MAX_WIDTH, (H, W), (gh, gw)))
+        if self._size is not None and self._size != (H, W, gh, gw):
+            raise ValueError(who + "sizes differ: this set holds %s -> %s, the recording is %s -> %s"
+                             % (self._size[:2], self._size[2:], (H, W), (gh, gw)))
+        cols = tuple(lr) + tuple(gt)
+        if not all(t.is_cuda and t.device == cols[0].device for t in cols) or (self._device or cols[0].device) != cols[0].device:
+            raise ValueError(who + "the columns must be GPU tensors on one device")
+        for name, ps in (("lr", lr[2]), ("gt", gt[2])):
+            if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
+                raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
+        self._size, self._device = (H, W, gh, gw), cols[0].device
+        self._recs.append(dict(cols=cols, ptrs=[t.data_ptr() for t in cols], lr_index=lr_index, gt_index=gt_index))
+        self._ends.append(len(self) + (len(lr_index) - self.L) // self.step_size + 1)
+        return len(self._recs) - 1
+
+    def __len__(self):
+        return self._ends[-1] if self._ends else 0
+
+    def locate(self, index):
+        """Sequence index of the set -> (recording number, sequence number inside it)."""
+        index = int(index)
+        if not 0 <= index < len(self):
+            raise IndexError("EventTrainSet: sequence %d of %d" % (index, len(self)))
+        r = int(np.searchsorted(self._ends, index, side="right"))
+        return r, index - (self._ends[r - 1] if r else 0)
+
+    # ------------------------------------------------------------------ batches
+    def plan(self, index, rng=random):
+        """-> (recording number,) + sequence_plan(...) of sequence `index`."""
+        r, i = self.locate(index)
+        return (r,) + sequence_plan(i, len(self._recs[r]["lr_index"]), self.L, self.step_size, self.augment, self.pause, rng)
+
+    def _buffers(self, B):
+        """Pinned host copies (a ring: one is rewritten only after the copy that last read it has completed) and the device
+        buffer of B table entries followed by B noise column sets; grown when a larger batch comes."""
+        nbytes = B * (SEQ_SAMPLE_DTYPE.itemsize + 8 * ((5 * self.n_noise + 7) // 8))
+        if self._table is None or self._table.numel() < nbytes:
+            torch.cuda.synchronize(self._device)
+            self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
+            self._events = [None] * self.RING
+            self._table = torch.zeros(nbytes, dtype=torch.uint8, device=self._device)
+        return nbytes
+
+    def batch(self, indices, rng=random):
+        """Sequences `indices` of the set -> (inp_cnt [B,L,2,H,W], gt_cnt [B,L,2,gh,gw]) float32 on the GPU, the layout
+        train_step.bptt_step takes: one table copy (entries and noise columns in one pinned buffer) and ONE bmc_seq_encode launch
+        on the current stream.  The samples' plans draw from `rng` in the order of `indices`, as a loader worker would walk them.
+        The pinned table and its device copy are reused between calls; the two results are new tensors."""
+        global ENCODE_LAUNCHES
+        from bmc_hip.encodings import encode_sequences
+        indices = [int(v) for v in indices]
+        B = len(indices)
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError("EventTrainSet.batch: 1 <= B <= %d sequences (got %d)" % (MAX_BATCH, B))
+        plans = [self.plan(v, rng) for v in indices]
+        H, W, gh, gw = self._size
+        L, nn = self.L, self.n_noise
+        nbytes = self._buffers(B)
+        k = self._k
+        if self._events[k] is not None:
+            self._events[k].synchronize()
+        host = self._pinned[k].numpy()
+        tab = host[:B * SEQ_SAMPLE_DTYPE.itemsize].view(SEQ_SAMPLE_DTYPE)
+        tab[:] = np.zeros((), SEQ_SAMPLE_DTYPE)
+        stride = 8 * ((5 * nn + 7) // 8)
+        for b, (r, seed, items, paused, flips) in enumerate(plans):
+            rec = self._recs[r]
+            for name, p in zip(SEQ_SAMPLE_DTYPE.names[:6], rec["ptrs"]):
+                tab[name][b] = p
+            tab["lr_range"][b, :L] = rec["lr_index"][items]
+            tab["gt_range"][b, :L] = rec["gt_index"][items]
+            tab["flips"][b] = flips
+            tab["paused"][b] = sum(1 << t for t, p in enumerate(paused) if p)
+            if nn:
+                off = B * SEQ_SAMPLE_DTYPE.itemsize + b * stride
+                xs, ys, ps = noise_events(self.window, (H, W), seed, self.noise_level)
+                host[off:off + 2 * nn].view(np.int16)[:] = xs
+                host[off + 2 * nn:off + 4 * nn].view(np.int16)[:] = ys
+                host[off + 4 * nn:off + 5 * nn].view(np.int8)[:] = ps
+                base = self._table.data_ptr() + off
+                tab["noise_xs"][b], tab["noise_ys"][b], tab["noise_ps"][b], tab["n_noise"][b] = base, base + 2 * nn, base + 4 * nn, nn
+        with torch.cuda.device(self._device):
+            self._table[:nbytes].copy_(self._pinned[k][:nbytes], non_blocking=True)
+            ev = self._events[k] = self._events[k] or torch.cuda.Event()
+            ev.record()
+            self._k = (k + 1) % self.RING
+            out = encode_sequences(self._table, B, L, (H, W), (gh, gw))
+        ENCODE_LAUNCHES += 1
+        return out
+
+    def batches(self, batch_size, shuffle=True, drop_last=True, generator=None, rank=0, world=1):
+        """Index lists for one epoch -> list of lists for batch().  The order is torch.randperm(len, generator=generator) when
+        shuffle (else 0 .. len-1), padded by its own head to a multiple of `world`; rank r takes every world-th index from r --
+        DistributedSampler's rule (the reference's loader, dataloader/h5dataloader.py:191-201) -- and cuts its share into
+        batches of batch_size, the last short one dropped with drop_last."""
+        n, world, rank, batch_size = len(self), int(world), int(rank), int(batch_size)
+        if batch_size < 1 or world < 1 or not 0 <= rank < world:
+            raise ValueError("EventTrainSet.batches: batch_size >= 1 and 0 <= rank < world")
+        order = torch.randperm(n, generator=generator).tolist() if shuffle else list(range(n))
+        total = -(-n // world) * world
+        while n and len(order) < total:
+            order += order[:total - len(order)]
+        mine = order[rank:total:world]
+        out = [mine[a:a + batch_size] for a in range(0, len(mine), batch_size)]
+        if drop_last and out and len(out[-1]) < batch_size:
+            out.pop()
+        return out

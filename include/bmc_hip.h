@@ -513,6 +513,44 @@ typedef struct bmc_slot_events {
 int bmc_slot_encode(const bmc_slot_events_t* table, int S, int seqn, int H, int W, int gh, int gw, float* lr_scratch,
                     float* gt_scratch, bmc_stream_t s);
 
+/* ---- sequence encoder for training ----------------------------------------
+ * The training counterpart of the event-backed slots (event_dataset.EventTrainSet.batch): recordings stay on the GPU as raw
+ * dataset columns and ONE launch per batch encodes every LR and HR count image of B sequences of L items into the collate
+ * layout inp_cnt [B][L][2][H][W], gt_cnt [B][L][2][gh][gw] -- what SequenceDataset.__getitem__ (dataloader/h5dataset.py:666-700)
+ * has H5Dataset.__getitem__ (:261-316) do per item in the loader's workers.  A DEVICE table of B entries:
+ *   LR item t, not paused: the count image bmc_encode_raw_events gives for events [first, end) of lr_range[t] with `flips`
+ *     (augment_event :559-578: the flip is applied to the int16 coordinate and the polarity BEFORE the range test, so the
+ *     out-of-range quirk applies to the flipped values: an out-of-range negative adds 1 at [H-1][0] of channel 1, an
+ *     out-of-range positive counts nowhere), plus the sample's n_noise noise events, NOT flipped (:281-285: the noise is
+ *     concatenated after augment_event) and under the same range rule (add_noise_event :623-634 can give x == W or y == H:
+ *     out of range).
+ *   LR item t, paused (bit t of `paused`): all +0.0 -- no events, no noise (:304-306).
+ *   HR item t: gt_range[t] encoded with the same `flips` at (gh, gw), paused or not, never with noise.
+ * Polarities are -1 / 0 / +1 and counters are integers (a weight p*p is counted as an integer); below 2^24 events per pixel
+ * the result is the float32 sum of the reference.  The scheme is bmc_slot_encode's: a workgroup owns a band of rows of one
+ * frame, at most 60 KB of LDS counters, integer LDS atomics, stored once (the store is the zero fill) -- no global atomics, no
+ * memset, order independent and run-to-run identical.  Limits the CALLER checks and the kernel trusts: every range inside its
+ * columns, first <= end; checked here: 2 <= L <= BMC_SEQ_MAX_ITEMS, W, gw <= 7680, 1 <= B <= 65535. */
+#define BMC_SEQ_MAX_ITEMS 32
+typedef struct bmc_seq_sample {           /* one sequence of the batch */
+    const short* lr_xs;     /* its recording's LR columns */
+    const short* lr_ys;
+    const double* lr_ps;
+    const short* gt_xs;     /* HR (ground-truth) columns */
+    const short* gt_ys;
+    const double* gt_ps;
+    const short* noise_xs;  /* n_noise noise events; NULL / 0: none */
+    const short* noise_ys;
+    const signed char* noise_ps;
+    int n_noise;
+    unsigned flips;         /* bit0 horizontal, bit1 vertical, bit2 polarity (as bmc_encode_raw_events) */
+    unsigned paused;        /* bit t: item t is a paused frame */
+    long long lr_range[BMC_SEQ_MAX_ITEMS][2];   /* events [first, end) of LR item t; ranges may overlap */
+    long long gt_range[BMC_SEQ_MAX_ITEMS][2];
+} bmc_seq_sample_t;
+int bmc_seq_encode(const bmc_seq_sample_t* table, int B, int L, int H, int W, int gh, int gw, float* inp_cnt, float* gt_cnt,
+                   bmc_stream_t s);
+
 /* Event OUTPUT of the slots (MultiStreamSR(emit_events=True)): the window's prediction leaves the session as an event list
  * appended to the recording's own output columns -- the rounded count image the reference renders (infer_BMCNet.py:94:
  * esr_cnt[0].cpu().round()), clamped, as the stream whose encoding gives that image back.  Per element v of pred[s]

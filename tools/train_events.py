@@ -1,0 +1,119 @@
+#!/usr/bin/env python3
+"""Train from recordings kept on the GPU as raw event columns (event_dataset.EventTrainSet): N bptt_steps whose batches are
+encoded by ONE bmc_seq_encode launch each; prints the loss per step and the encode time per batch (HIP events around
+EventTrainSet.batch's launch: the table copy and the kernel).
+
+A recording is an .npz of raw columns, the ones tools/multistream_infer.py --events builds synthetically (event_recording):
+lr_xs / lr_ys (int16), lr_ps (float64), lr_ts (float64, sorted), the same four with gt_, and lr_size = (H, W), gt_size = (gh, gw).
+The index tables are cut here with bmc_hip.encodings.event_window_indices (the reference's blocks: --window / --sliding).
+--synthetic K makes K such recordings of --items items at --size instead (and --save DIR writes them out).
+
+python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x80] [--steps 10] [--batch 2] [--L 9] [--step-size S]
+                             [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
+"""
+import argparse
+import json
+import os
+import random
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
+import numpy as np
+import torch
+
+from bmc_hip.encodings import event_window_indices
+from event_dataset import EventTrainSet
+from models.BMCNet import BMCNet
+from train_step import bptt_step
+
+KEYS = ("xs", "ys", "ps", "ts")
+
+
+def synthetic_recording(items, H, W, scale, window, sliding, seed):
+    """Raw columns of about `items` items: uniform coordinates, +-1 polarities, sorted uniform timestamps."""
+    rng = np.random.default_rng(seed)
+    n_lr = (window - sliding) * items + 1
+    rec = {"lr_size": np.asarray([H, W]), "gt_size": np.asarray([scale * H, scale * W])}
+    for side, n, h, w in (("lr", n_lr, H, W), ("gt", scale * scale * n_lr, scale * H, scale * W)):
+        rec[side + "_xs"] = rng.integers(0, w, n).astype(np.int16)
+        rec[side + "_ys"] = rng.integers(0, h, n).astype(np.int16)
+        rec[side + "_ps"] = rng.choice([-1.0, 1.0], n)
+        rec[side + "_ts"] = np.sort(rng.uniform(0, 1, n))
+    return rec
+
+
+def add(ts, rec, dev, window, sliding, scale):
+    lr_index, gt_index = event_window_indices(rec["lr_ts"], rec["gt_ts"], window, sliding, scale)
+    cols = lambda side: tuple(torch.from_numpy(np.ascontiguousarray(rec["%s_%s" % (side, k)])).to(dev) for k in KEYS[:3])
+    return ts.add_recording(cols("lr"), cols("gt"), lr_index, gt_index, tuple(rec["lr_size"].tolist()), tuple(rec["gt_size"].tolist()))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("recordings", nargs="*")
+    ap.add_argument("--synthetic", type=int, default=0)
+    ap.add_argument("--items", type=int, default=24)
+    ap.add_argument("--size", default="45x80")
+    ap.add_argument("--save", default=None)
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--batch", type=int, default=2)
+    ap.add_argument("--L", type=int, default=9)
+    ap.add_argument("--step-size", type=int, default=None)
+    ap.add_argument("--window", type=int, default=2048)
+    ap.add_argument("--sliding", type=int, default=1024)
+    ap.add_argument("--scale", type=int, default=4)
+    ap.add_argument("--augment", action="store_true", help="Horizontal / Vertical / Polarity flips, 0.5 each")
+    ap.add_argument("--pause", default=None, help="proba_pause_when_running,proba_pause_when_paused")
+    ap.add_argument("--noise", type=float, default=None, help="noise_level")
+    ap.add_argument("--n-c", type=int, default=128)
+    ap.add_argument("--n-b", type=int, default=5)
+    ap.add_argument("--lr", type=float, default=1e-4)
+    ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if not a.recordings and not a.synthetic:
+        ap.error("give recordings or --synthetic K")
+    dev = torch.device("cuda:0")
+    H, W = (int(v) for v in a.size.split("x"))
+    recs = [dict(np.load(p)) for p in a.recordings]
+    recs += [synthetic_recording(a.items, H, W, a.scale, a.window, a.sliding, a.seed + k) for k in range(a.synthetic)]
+    if a.save:
+        os.makedirs(a.save, exist_ok=True)
+        for k, r in enumerate(recs[len(a.recordings):]):
+            np.savez(os.path.join(a.save, "synthetic%d.npz" % k), **r)
+    ts = EventTrainSet(L=a.L, step_size=a.step_size, augment=(("Horizontal", "Vertical", "Polarity"), (0.5, 0.5, 0.5)) if a.augment else None,
+                       pause=tuple(float(v) for v in a.pause.split(",")) if a.pause else None, add_noise=a.noise, window=a.window)
+    for r in recs:
+        add(ts, r, dev, a.window, a.sliding, a.scale)
+    print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L))
+    random.seed(a.seed)
+    torch.manual_seed(a.seed)
+    m = BMCNet(a.scale, a.n_c, a.n_b).to(dev)
+    opt = torch.optim.Adam(m.parameters(), lr=a.lr)
+    g = torch.Generator().manual_seed(a.seed)
+    rows, step, epoch = [], 0, 0
+    while step < a.steps:
+        batches = ts.batches(a.batch, generator=g)
+        if not batches:
+            raise SystemExit("the recordings give %d sequences, fewer than one batch of %d" % (len(ts), a.batch))
+        for idx in batches:
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            inp, gt = ts.batch(idx)
+            t1.record()
+            loss, mse = bptt_step(m, opt, inp, gt, a.n_c, a.scale)
+            loss = float(loss)
+            rows.append(dict(step=step, epoch=epoch, sequences=idx, loss=loss, encode_ms=round(t0.elapsed_time(t1), 4)))
+            print("step %d  loss %.6f  encode %.3f ms  sequences %s" % (step, loss, rows[-1]["encode_ms"], idx))
+            step += 1
+            if step >= a.steps:
+                break
+        epoch += 1
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(rows, f)
+
+
+if __name__ == "__main__":
+    main()
