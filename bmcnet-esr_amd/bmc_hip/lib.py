@@ -74,6 +74,13 @@ class SmallMmArgs(C.Structure):
                 ("vec_out", C.c_void_p), ("vo_sb", C.c_longlong), ("vo_sg", C.c_longlong), ("accumulate", C.c_int)]
 
 
+class AdamHyper(C.Structure):
+    _fields_ = [("lr", C.c_double), ("beta1_f64", C.c_double), ("beta2_f64", C.c_double),
+                ("beta1", C.c_float), ("one_minus_beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta2", C.c_float),
+                ("eps", C.c_float), ("weight_decay", C.c_float), ("step_size", C.c_float), ("bias_correction2_sqrt", C.c_float),
+                ("amsgrad", C.c_int)]
+
+
 def _sig(name, argtypes, restype=C.c_int):
     fn = getattr(_lib, name)
     fn.argtypes = argtypes
@@ -149,6 +156,8 @@ _slot_encode_filtered = _sig("bmc_slot_encode_filtered", [_p, _p, _p, _i, _i, _i
 _hot_pixel_mask = _sig("bmc_hot_pixel_mask", [_p, _i, _i, _i, _i, _f, _p, _p, _p])
 _slot_render = _sig("bmc_slot_render", [_p, _p, _i, _i, _i, _i, _i, _p, _p])
 _seq_encode = _sig("bmc_seq_encode", [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
+_adam_step = _sig("bmc_adam_step", [_p, _i, AdamHyper, _p, _p])
+_adam_step_cap = _sig("bmc_adam_step_capturable", [_p, _i, AdamHyper, _p, _p, _p])
 
 EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_events_to_voxel", "bmc_events_to_stack", "bmc_encode_raw_events", "bmc_pack_weight", "bmc_pack_weight_t", "bmc_split_weight", "bmc_conv",
            "bmc_pgemm", "bmc_pgemm_wave_map", "bmc_pgemm_reduce_weight", "bmc_pgemm_reduce_plain", "bmc_colsum", "bmc_relu_bwd",
@@ -163,7 +172,8 @@ EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_event
            "bmc_wgrad_wino4_nsplit", "bmc_wgrad_wino4", "bmc_wgrad_wino4_reduce", "bmc_wgrad_wino_multi", "bmc_ptr_table",
            "bmc_conv_wino_rows", "bmc_slot_stage", "bmc_slot_commit", "bmc_slot_metrics", "bmc_slot_encode", "bmc_slot_emit",
            "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes", "bmc_slot_emit_clocked", "bmc_slot_hot_update",
-           "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_seq_encode"]
+           "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_seq_encode", "bmc_adam_step",
+           "bmc_adam_step_capturable"]
 
 
 def check(rc, what):

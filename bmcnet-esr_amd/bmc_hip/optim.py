@@ -1,0 +1,289 @@
+"""The optimizer step of the training loop (train.py:237,653: Adam(amsgrad=True, weight_decay=1e-5)) in ONE HIP launch for all
+parameters of a group: csrc/optim.hip, bmc_adam_step; include/bmc_hip.h "optimizer step" states the arithmetic, rounding by rounding.
+
+`Adam` is a drop-in for the constructor calls this repository and the reference make.  It IS a torch.optim.Optimizer: the global
+pre-step hook of bmc_hip.ops (weight gradients on the side stream), GradAllReducer's pre-step hook and LR schedulers work on
+it as on torch's, and its state has torch's keys, dtypes and devices -- state_dict() of either optimizer loads into the other.
+The class keeps the name `Adam`: checkpoint.resume matches optimizers by type(optimizer).__name__.
+
+What happens per step and group: the parameters that have a gradient and share a step count are cut into chunks of at most 4096
+elements of one tensor (chunk_table); the table is built in a pinned buffer, copied to the device once and memoised by the tuple
+of all data pointers (the caching allocator repeats addresses: from the second step on usually nothing is copied); one launch
+updates p, exp_avg, exp_avg_sq and max_exp_avg_sq in place, 36 bytes per element; the parameters' version counters advance, so
+that every cache keyed on them (weight packs, chains, inference graphs) sees the new values.  There is no fallback: what the
+kernel does not do (CPU, non-fp32 or non-contiguous parameters, sparse gradients, maximize, ...) raises ValueError.
+"""
+from __future__ import annotations
+
+from collections import OrderedDict
+
+import numpy as np
+import torch
+
+from . import lib
+from . import ops  # noqa: F401  -- registers the global pre-step hook (ops._join_before_step) wherever this optimizer is used
+
+CHUNK = 4096                      # BMC_ADAM_CHUNK
+CHUNK_DTYPE = np.dtype({"names": ["p", "g", "m", "v", "vmax", "n", "aligned"], "formats": ["<u8"] * 5 + ["<i4", "<i4"],
+                        "offsets": [0, 8, 16, 24, 32, 40, 44], "itemsize": 48})       # bmc_adam_chunk_t
+STEP_LAUNCHES = 0                 # calls of bmc_adam_step / bmc_adam_step_capturable of this process
+TABLE_COPIES = 0                  # chunk tables copied to the device
+MEMO_TABLES = 8                   # chunk tables kept per optimizer
+_REFUSED = ("maximize", "foreach", "fused", "differentiable", "decoupled_weight_decay")
+
+
+def chunk_table(entries):
+    """The chunk table of one launch, a pure host function.  entries: per parameter (p, g, m, v, vmax, n) -- five addresses (vmax 0
+    or None without amsgrad; g None: the parameter has no gradient and is left out) and the element count.  -> CHUNK_DTYPE array:
+    a parameter of n elements gives ceil(n / 4096) consecutive chunks, none spans two parameters; `aligned` is set where all
+    five addresses are multiples of 16 (a chunk starts a multiple of 16 KiB after its tensor, so it shares the tensor's alignment)."""
+    rows = [(p, g, m, v, x or 0, n) for p, g, m, v, x, n in entries if g is not None]
+    if not rows:
+        return np.zeros(0, CHUNK_DTYPE)
+    a = np.asarray(rows, dtype=np.uint64)
+    if int(a[:, 5].min()) < 1:
+        raise ValueError("chunk_table: a parameter without elements")
+    n = a[:, 5].astype(np.int64)
+    per = (n + CHUNK - 1) // CHUNK
+    which = np.repeat(np.arange(len(rows)), per)
+    first = np.repeat(np.cumsum(per) - per, per)
+    off = (np.arange(int(per.sum())) - first) * CHUNK                      # element offset of the chunk inside its tensor
+    tab = np.zeros(len(which), CHUNK_DTYPE)
+    byte = (4 * off).astype(np.uint64)
+    for c, key in enumerate(("p", "g", "m", "v")):
+        tab[key] = a[which, c] + byte
+    tab["vmax"] = np.where(a[which, 4] != 0, a[which, 4] + byte, np.uint64(0))
+    tab["n"] = np.minimum(CHUNK, n[which] - off)
+    tab["aligned"] = ((a[:, 0] | a[:, 1] | a[:, 2] | a[:, 3] | a[:, 4]) & np.uint64(15))[which] == 0
+    return tab
+
+
+def step_hyper(lr, beta1, beta2, eps, weight_decay, amsgrad, step):
+    """bmc_adam_hyper_t of step `step` (1-based): float64 arithmetic exactly as torch's _single_tensor_adam, each value rounded
+    to float32 once (by the ctypes field)."""
+    h = lib.AdamHyper()
+    h.lr, h.beta1_f64, h.beta2_f64 = lr, beta1, beta2
+    h.beta1, h.one_minus_beta1, h.beta2, h.one_minus_beta2 = beta1, 1 - beta1, beta2, 1 - beta2
+    h.eps, h.weight_decay, h.amsgrad = eps, weight_decay, int(bool(amsgrad))
+    if step is not None:
+        h.step_size = lr / (1 - beta1 ** step)
+        h.bias_correction2_sqrt = (1 - beta2 ** step) ** 0.5
+    return h
+
+
+class Adam(torch.optim.Optimizer):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, capturable=False,
+                 track_grad_norm=False, foreach=None, maximize=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+        if isinstance(lr, torch.Tensor):
+            raise ValueError("bmc_hip.optim.Adam: a tensor lr is not supported (the step size is computed on the host)")
+        if not 0.0 <= lr:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if not 0.0 <= eps:
+            raise ValueError(f"Invalid epsilon value: {eps}")
+        if any(isinstance(b, torch.Tensor) for b in betas) or not (0.0 <= betas[0] < 1.0 and 0.0 <= betas[1] < 1.0):
+            raise ValueError(f"Invalid beta parameters: {betas}")
+        if not 0.0 <= weight_decay:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        # torch's group keys, all of them: a state_dict of this optimizer loads into torch.optim.Adam and back
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, amsgrad=amsgrad, maximize=maximize, foreach=foreach,
+                        capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
+        _check_group(defaults)
+        self.track_grad_norm = bool(track_grad_norm)
+        self._memo = OrderedDict()        # data pointers of a launch -> (device table, chunks, partials or None)
+        self._pinned = self._pinned_event = None
+        self._norm_parts = None           # the partials the last step() wrote
+        self._cohorts = {}                # capturable: ids of the parameters of a launch -> their device int32 step counter
+        self._cohort_of = {}
+        self._count = {}                  # capturable: parameter -> (its step tensor, the count the host believes it holds)
+        super().__init__(params, defaults)
+
+    def add_param_group(self, param_group):
+        super().add_param_group(param_group)
+        group = self.param_groups[-1]
+        _check_group(group)
+        for i, p in enumerate(group["params"]):
+            _check_param(p, _name(group, i, len(self.param_groups) - 1))
+
+    def load_state_dict(self, state_dict):
+        super().load_state_dict(state_dict)
+        self._cohorts.clear(); self._cohort_of.clear(); self._count.clear()       # the state tensors are other tensors now
+        self._memo.clear()
+
+    # ------------------------------------------------------------------ one step
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        parts = []
+        for gi, group in enumerate(self.param_groups):
+            self._step_group(gi, group, parts)
+        if self.track_grad_norm:
+            self._norm_parts = parts
+        return loss
+
+    def _step_group(self, gi, group, parts):
+        _check_group(group)
+        amsgrad, cap = bool(group["amsgrad"]), bool(group["capturable"])
+        launches = {}                     # (device index, step count) -> [(p, grad, state)]
+        for i, p in enumerate(group["params"]):
+            g = p.grad
+            if g is None:
+                continue
+            if g.is_sparse or g.dtype != p.dtype or g.device != p.device or g.shape != p.shape or not g.is_contiguous():
+                raise ValueError("bmc_hip.optim.Adam: the gradient of %s (%s, %s, %s, %s%s) does not match its parameter (%s, %s, %s): "
+                                 "a dense contiguous gradient of the parameter's shape, dtype and device is required" % (
+                                     _name(group, i, gi), tuple(g.shape), g.dtype, g.device, g.layout,
+                                     "" if g.is_sparse or g.is_contiguous() else ", not contiguous", tuple(p.shape), p.dtype, p.device))
+            st = self.state[p]
+            if len(st) == 0:
+                _check_param(p, _name(group, i, gi))
+                st["step"] = torch.zeros((), dtype=torch.float32, device=p.device) if cap else torch.tensor(0.0, dtype=torch.float32)
+                st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if amsgrad:
+                    st["max_exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                if cap:
+                    self._count[p] = (st["step"], 0)
+            elif amsgrad and "max_exp_avg_sq" not in st:
+                raise ValueError("bmc_hip.optim.Adam: the state of %s has no max_exp_avg_sq (amsgrad switched on after the first step)"
+                                 % _name(group, i, gi))
+            step_t = st["step"]
+            if cap:
+                if not step_t.is_cuda:
+                    step_t = st["step"] = step_t.to(device=p.device, dtype=torch.float32)
+                seen = self._count.get(p)
+                if seen is None or seen[0] is not step_t:
+                    seen = (step_t, int(step_t.item()))      # once after load_state_dict (not inside a capture: it reads the device)
+                count = seen[1]
+                self._count[p] = (step_t, count + 1)
+            else:
+                if step_t.is_cuda:
+                    step_t = st["step"] = step_t.cpu()
+                count = step_t.item()
+            launches.setdefault((p.device.index, count), []).append((p, g, st))
+        for (dev, count), rows in launches.items():
+            self._launch(group, dev, count, rows, amsgrad, cap, parts)
+
+    def _launch(self, group, dev, count, rows, amsgrad, cap, parts):
+        global STEP_LAUNCHES
+        key = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                     st["max_exp_avg_sq"].data_ptr() if amsgrad else 0, p.numel()) for p, g, st in rows)
+        other = torch.cuda.current_device() != dev
+        if other:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(dev)
+        try:
+            table, n_chunks, partial = self._table(key, dev)
+            beta1, beta2 = group["betas"]
+            steps = [st["step"] for _, _, st in rows]
+            stream = torch._C._cuda_getCurrentRawStream(dev)
+            part_ptr = partial.data_ptr() if partial is not None else None
+            if cap:
+                h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, None)
+                step_dev = self._cohort(rows, dev)
+                lib.call(lib._adam_step_cap, "bmc_adam_step_capturable", table.data_ptr(), n_chunks, h, step_dev.data_ptr(), part_ptr,
+                         stream)
+                torch._foreach_add_(steps, 1.0)              # torch's own state key, kept true on the device
+            else:
+                h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, count + 1)
+                lib.call(lib._adam_step, "bmc_adam_step", table.data_ptr(), n_chunks, h, part_ptr, stream)
+                torch._foreach_add_(steps, 1.0)              # host tensors: no launch
+        finally:
+            if other:
+                torch.cuda.set_device(prev)
+        STEP_LAUNCHES += 1
+        # the kernel wrote the parameters behind autograd's back: everything keyed on p._version must see a new version
+        torch.autograd.graph.increment_version([p for p, _, _ in rows])
+        if partial is not None:
+            parts.append(partial)
+
+    def _table(self, key, dev):
+        global TABLE_COPIES
+        hit = self._memo.get(key)
+        if hit is not None:
+            self._memo.move_to_end(key)
+            return hit
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bmc_hip.optim.Adam: this set of parameter, gradient and state buffers has no chunk table on the device "
+                               "yet and none can be copied during a graph capture; take one step() with the same buffers first")
+        tab = chunk_table([k for k in key])
+        nbytes = tab.nbytes
+        if self._pinned is None or self._pinned.numel() < nbytes:
+            if self._pinned_event is not None:
+                self._pinned_event.synchronize()
+            self._pinned = torch.empty(max(nbytes, 1 << 16), dtype=torch.uint8, pin_memory=True)
+            self._pinned_event = torch.cuda.Event()
+        else:
+            self._pinned_event.synchronize()                 # the copy of the previous table has read the buffer
+        self._pinned[:nbytes].copy_(torch.from_numpy(tab.view(np.uint8).reshape(-1)))
+        table = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", dev))
+        table.copy_(self._pinned[:nbytes], non_blocking=True)
+        self._pinned_event.record()
+        TABLE_COPIES += 1
+        partial = torch.empty(len(tab), dtype=torch.float64, device=table.device) if self.track_grad_norm else None
+        hit = self._memo[key] = (table, len(tab), partial)
+        while len(self._memo) > MEMO_TABLES:
+            self._memo.popitem(last=False)
+        return hit
+
+    def _cohort(self, rows, dev):
+        """capturable: the device int32 step counter of the parameters that leave in one launch.  It is made from the first
+        parameter's own `step` tensor (the device holds the truth: a replayed graph advances both without the host), and a
+        parameter belongs to one cohort at a time."""
+        ckey = tuple(id(p) for p, _, _ in rows)
+        c = self._cohorts.get(ckey)
+        if c is not None and all(self._cohort_of.get(p) == ckey for p, _, _ in rows):
+            return c
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bmc_hip.optim.Adam(capturable=True): take one step() before capturing one (the step counter of this "
+                               "set of parameters is made outside a capture)")
+        for p, _, _ in rows:
+            self._cohorts.pop(self._cohort_of.get(p), None)
+            self._cohort_of[p] = ckey
+        c = self._cohorts[ckey] = rows[0][2]["step"].to(torch.int32).reshape(1).clone()
+        return c
+
+    def step_counter(self, group=0):
+        """capturable: the device int32 counters (one per launch) of a group's parameters, for inspection."""
+        ids = {id(p) for p in self.param_groups[group]["params"]}
+        return [c for k, c in self._cohorts.items() if ids.issuperset(k)]
+
+    # ------------------------------------------------------------------ gradient norm
+    def grad_norm(self):
+        """L2 norm of the raw gradients the last step() consumed (before weight decay): a 0-d float64 device tensor, the square
+        root of the sum of the per-chunk float64 partials the kernel stored.  No host sync."""
+        if not self.track_grad_norm:
+            raise RuntimeError("bmc_hip.optim.Adam: grad_norm() needs track_grad_norm=True")
+        if not self._norm_parts:
+            raise RuntimeError("bmc_hip.optim.Adam: grad_norm() before the first step() that had gradients")
+        parts = self._norm_parts
+        flat = parts[0] if len(parts) == 1 else torch.cat([q.to(parts[0].device) for q in parts])
+        return flat.sum().sqrt()
+
+
+def _name(group, i, gi):
+    names = group.get("param_names")
+    p = group["params"][i]
+    return "parameter %s#%d of group %d (shape %s)" % (repr(names[i]) + " " if names else "", i, gi, tuple(p.shape))
+
+
+def _check_group(group):
+    given = [k for k in _REFUSED if group.get(k)]
+    if given:
+        raise ValueError("bmc_hip.optim.Adam does not implement %s (there is no fallback to torch's kernels)" % ", ".join(given))
+    if isinstance(group["lr"], torch.Tensor):
+        raise ValueError("bmc_hip.optim.Adam: a tensor lr is not supported (the step size is computed on the host)")
+    if any(isinstance(b, torch.Tensor) for b in group["betas"]):
+        raise ValueError("bmc_hip.optim.Adam: tensor betas are not supported")
+
+
+def _check_param(p, name):
+    if not p.is_cuda:
+        raise ValueError("bmc_hip.optim.Adam: %s is on %s; the step runs on the GPU only (move the model before building the optimizer)"
+                         % (name, p.device))
+    if p.dtype != torch.float32:
+        raise ValueError("bmc_hip.optim.Adam: %s is %s; only float32 parameters are supported" % (name, p.dtype))
+    if p.is_sparse or not p.is_contiguous():
+        raise ValueError("bmc_hip.optim.Adam: %s is not a dense contiguous tensor" % name)

@@ -760,6 +760,53 @@ typedef struct bmc_slot_render {
 int bmc_slot_render(const bmc_slot_t* table, const bmc_slot_render_t* render, int S, int h, int w, int round, int nparts,
                     float* scratch, bmc_stream_t s);
 
+/* ---- optimizer step (bmcnet-esr_amd/bmc_hip/optim.py::Adam) ----------------------------------------------------------------
+ * torch.optim.Adam(amsgrad, weight_decay) as train.py:653 builds it and train.py:237 steps it, for ALL parameters of a group in
+ * ONE launch over a DEVICE table of chunks.  A chunk is at most BMC_ADAM_CHUNK = 4096 consecutive elements of ONE tensor (a tensor
+ * of n elements gives ceil(n / 4096) chunks; a chunk never spans two tensors); the grid is n_chunks workgroups of 256 lanes.
+ * Per element, in float32, every line ONE correctly rounded operation (no fused multiply-add, IEEE square root and division):
+ *     g' = g + weight_decay * p        (skipped when weight_decay == 0; g itself is never written)
+ *     m  = m + one_minus_beta1 * (g' - m)
+ *     v  = v * beta2 + one_minus_beta2 * (g' * g')
+ *     vmax = max(vmax, v)              (amsgrad; otherwise vmax is not touched and the denominator uses v)
+ *     den = sqrt(vmax) / bias_correction2_sqrt + eps
+ *     p  = p - step_size * (m / den)
+ * NaN and Inf propagate as the formulas say; max gives NaN when either side is NaN (torch.maximum).  Subnormals are kept.
+ * `aligned` != 0 promises that all five pointers of the chunk (four without amsgrad) are 16-byte aligned: whole groups of four
+ * elements then move as 16-byte loads and stores and the last n % 4 elements one by one; `aligned` == 0 (a gradient that is a view
+ * into a flat reduction bucket at any element offset) moves every element on its own.  Both paths compute the same roundings.
+ * No workgroup waits for another, no atomics, no scratch memory; every access through a table pointer is a global access.
+ * partial_sq, NULL or a device float64 [n_chunks] array: chunk i also stores sum(double(g) * double(g)) over its elements (the
+ * RAW gradient, before weight decay; squares of floats are exact in float64) at partial_sq[i] -- each lane adds its elements in
+ * index order, then a fixed tree over the workgroup: the same bits run after run.
+ * The host rounds every float of bmc_adam_hyper_t ONCE from the float64 values torch's _single_tensor_adam computes for step t:
+ * step_size = lr / (1 - beta1^t), bias_correction2_sqrt = (1 - beta2^t)^0.5. */
+#define BMC_ADAM_CHUNK 4096
+typedef struct bmc_adam_chunk {
+    float* p;
+    const float* g;
+    float* m;               /* exp_avg */
+    float* v;               /* exp_avg_sq */
+    float* vmax;            /* max_exp_avg_sq; NULL without amsgrad */
+    int n;                  /* 1 .. BMC_ADAM_CHUNK elements */
+    int aligned;
+} bmc_adam_chunk_t;
+typedef struct bmc_adam_hyper {
+    double lr, beta1_f64, beta2_f64;    /* read by the capturable entry point only */
+    float beta1, one_minus_beta1, beta2, one_minus_beta2, eps, weight_decay;
+    float step_size, bias_correction2_sqrt;     /* ignored by the capturable entry point */
+    int amsgrad;
+} bmc_adam_hyper_t;
+/* Checked: n_chunks >= 0 (0: nothing is launched), a table when n_chunks > 0, every hyper-parameter the entry point reads
+ * finite.  Trusted: the table's pointers, counts and flags. */
+int bmc_adam_step(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, double* partial_sq, bmc_stream_t s);
+/* The same pass for a captured graph, TWO launches.  step_dev is a device int32.  The first launch reads t = *step_dev + 1; one
+ * lane per workgroup computes step_size = lr / (1 - beta1_f64^t) and bias_correction2_sqrt = sqrt(1 - beta2_f64^t) in float64 and
+ * rounds them to float32; the pass then runs as above.  The second launch (one lane) stores t to *step_dev.  lr, beta1_f64 and
+ * beta2_f64 are baked into the graph. */
+int bmc_adam_step_capturable(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, int* step_dev, double* partial_sq,
+                             bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

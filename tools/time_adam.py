@@ -1,0 +1,144 @@
+#!/usr/bin/env python3
+"""The optimizer step alone: torch.optim.Adam with its default (foreach), torch.optim.Adam(foreach=False) and
+bmc_hip.optim.Adam (csrc/optim.hip, ONE launch) on the BMCNet(4,128,5) and BMCNet_plain(4,128,5) parameter sets with random
+gradients, Adam(lr=1e-4, weight_decay=1e-5, amsgrad=True) as train.py:653 builds it.
+
+Timing: the three optimizers alternate in one process, HIP events around --steps steps after --warmup steps, --rounds rounds
+each; every round is printed (ms per step: the GPU-side span of the step's launches as the host issues them, so a host that
+cannot keep up shows here too) and the median.  Floors for comparison: 36 bytes per element over 6.3 TB/s of HBM.
+
+--trace: the kernel launches per step.  Each optimizer runs twice in a child process of its own under
+`rocprofv3 --kernel-trace --stats -- python tools/time_adam.py --only NAME --steps N` (N = 2 and N = 7, no timing) and the
+difference of the two traces' kernel counts over 5 steps is printed: set-up kernels cancel.  No counters are collected.
+
+python tools/time_adam.py [--steps 50 --warmup 10 --rounds 3] [--sets bmcnet,plain] [--only hip|foreach|single] [--trace [--trace-dir DIR]]
+"""
+import argparse
+import csv
+import glob
+import os
+import statistics
+import subprocess
+import sys
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
+
+CFG = dict(lr=1e-4, weight_decay=1e-5, amsgrad=True)
+NAMES = ("foreach", "single", "hip")
+
+
+def make(name, params):
+    import torch
+    from bmc_hip.optim import Adam
+    if name == "hip":
+        return Adam(params, **CFG)
+    return torch.optim.Adam(params, foreach=None if name == "foreach" else False, **CFG)
+
+
+def parameter_set(kind, dev):
+    import torch
+    from models.BMCNet import BMCNet
+    from models.BMCNet_plain import BMCNet_plain
+    torch.manual_seed(0)
+    model = (BMCNet if kind == "bmcnet" else BMCNet_plain)(4, 128, 5)
+    params = [torch.nn.Parameter(p.detach().to(dev)) for p in model.parameters()]
+    gen = torch.Generator().manual_seed(1)
+    for p in params:
+        p.grad = (torch.randn(p.shape, generator=gen) * 1e-3).to(dev)
+    return params
+
+
+def timed(opt, steps):
+    import torch
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(steps):
+        opt.step()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / steps
+
+
+def run(a):
+    import torch
+    dev = torch.device("cuda:0")
+    names = [a.only] if a.only else list(NAMES)
+    for kind in a.sets.split(","):
+        base = parameter_set(kind, dev)
+        n = sum(p.numel() for p in base)
+        opts = {}
+        for name in names:                      # every optimizer on its own copy of the parameters, the same gradients
+            params = [torch.nn.Parameter(p.detach().clone()) for p in base]
+            for p, q in zip(params, base):
+                p.grad = q.grad.clone()
+            opts[name] = make(name, params)
+        for _ in range(a.warmup):
+            for name in names:
+                opts[name].step()
+        torch.cuda.synchronize()
+        if a.rounds == 0:                       # the traced runs: the steps, no timing
+            for name in names:
+                for _ in range(a.steps):
+                    opts[name].step()
+            torch.cuda.synchronize()
+            continue
+        rounds = {name: [] for name in names}
+        for _ in range(a.rounds):
+            for name in names:                  # alternating: what shares the machine hits all three alike
+                rounds[name].append(timed(opts[name], a.steps))
+        print("%s: %d tensors, %d elements, %.1f MB per pass (36 B per element; %.1f us at 6.3 TB/s)" % (
+            kind, len(base), n, 36 * n / 1e6, 36 * n / 6.3e12 * 1e6))
+        for name in names:
+            print("  %-8s ms per step, %d steps per round: %s   median %.4f" % (
+                name, a.steps, "  ".join("%.4f" % v for v in rounds[name]), statistics.median(rounds[name])))
+
+
+def kernel_count(out_dir):
+    files = glob.glob(os.path.join(out_dir, "**", "*kernel_trace.csv"), recursive=True)
+    if not files:
+        raise SystemExit("no kernel trace under %s" % out_dir)
+    total = 0
+    for f in files:
+        with open(f, newline="") as fh:
+            total += sum(1 for _ in csv.DictReader(fh))
+    return total
+
+
+def trace(a):
+    base = a.trace_dir or tempfile.mkdtemp(prefix="time_adam_trace_")
+    for kind in a.sets.split(","):
+        for name in ([a.only] if a.only else NAMES):
+            counts = {}
+            for steps in (2, 7):
+                out = os.path.join(base, "%s_%s_%d" % (kind, name, steps))
+                cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "t", "--", sys.executable,
+                       os.path.abspath(__file__), "--only", name, "--sets", kind, "--steps", str(steps), "--warmup", "0", "--rounds", "0"]
+                r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=a.child_timeout)
+                if r.returncode != 0:
+                    raise SystemExit("traced run failed (rc %d):\n%s" % (r.returncode, r.stdout.decode()[-2000:]))
+                counts[steps] = kernel_count(out)
+            print("%s %-8s kernel launches per step: %.1f   (%d kernels in 7 steps, %d in 2)" % (
+                kind, name, (counts[7] - counts[2]) / 5.0, counts[7], counts[2]))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--sets", default="bmcnet,plain")
+    ap.add_argument("--only", choices=NAMES, default=None)
+    ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--trace-dir", default=None)
+    ap.add_argument("--child-timeout", type=float, default=240.0)
+    a = ap.parse_args()
+    if a.trace:
+        trace(a)           # this process never opens the GPU: each traced run is a fresh child
+    else:
+        run(a)
+
+
+if __name__ == "__main__":
+    main()

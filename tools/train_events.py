@@ -10,12 +10,16 @@ The index tables are cut here with bmc_hip.encodings.event_window_indices (the r
 
 python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x80] [--steps 10] [--batch 2] [--L 9] [--step-size S]
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
+                             [--optimizer hip|torch] [--wall]
+--optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
+--wall: also print the wall time per step at the end (host clock, device synchronised, the first step left out).
 """
 import argparse
 import json
 import os
 import random
 import sys
+import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
@@ -71,6 +75,8 @@ def main():
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--optimizer", choices=("hip", "torch"), default="hip")
+    ap.add_argument("--wall", action="store_true")
     a = ap.parse_args()
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
@@ -90,9 +96,13 @@ def main():
     random.seed(a.seed)
     torch.manual_seed(a.seed)
     m = BMCNet(a.scale, a.n_c, a.n_b).to(dev)
-    opt = torch.optim.Adam(m.parameters(), lr=a.lr)
+    if a.optimizer == "hip":
+        from bmc_hip.optim import Adam
+        opt = Adam(m.parameters(), lr=a.lr)
+    else:
+        opt = torch.optim.Adam(m.parameters(), lr=a.lr)
     g = torch.Generator().manual_seed(a.seed)
-    rows, step, epoch = [], 0, 0
+    rows, step, epoch, clock = [], 0, 0, None
     while step < a.steps:
         batches = ts.batches(a.batch, generator=g)
         if not batches:
@@ -107,9 +117,15 @@ def main():
             rows.append(dict(step=step, epoch=epoch, sequences=idx, loss=loss, encode_ms=round(t0.elapsed_time(t1), 4)))
             print("step %d  loss %.6f  encode %.3f ms  sequences %s" % (step, loss, rows[-1]["encode_ms"], idx))
             step += 1
+            if step == 1:
+                torch.cuda.synchronize()
+                clock = time.perf_counter()
             if step >= a.steps:
                 break
         epoch += 1
+    if a.wall and step > 1:
+        torch.cuda.synchronize()
+        print("optimizer %s: %.3f ms wall per step over steps 1..%d" % (a.optimizer, (time.perf_counter() - clock) * 1e3 / (step - 1), step - 1))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(rows, f)
