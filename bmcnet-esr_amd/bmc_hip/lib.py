@@ -81,6 +81,11 @@ class AdamHyper(C.Structure):
                 ("amsgrad", C.c_int)]
 
 
+class AdamClip(C.Structure):
+    _fields_ = [("partial_sq", C.c_void_p), ("info", C.c_void_p), ("skipped", C.c_void_p), ("n_partials", C.c_int),
+                ("max_norm", C.c_float), ("skip_nonfinite", C.c_int)]
+
+
 def _sig(name, argtypes, restype=C.c_int):
     fn = getattr(_lib, name)
     fn.argtypes = argtypes
@@ -158,6 +163,9 @@ _slot_render = _sig("bmc_slot_render", [_p, _p, _i, _i, _i, _i, _i, _p, _p])
 _seq_encode = _sig("bmc_seq_encode", [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
 _adam_step = _sig("bmc_adam_step", [_p, _i, AdamHyper, _p, _p])
 _adam_step_cap = _sig("bmc_adam_step_capturable", [_p, _i, AdamHyper, _p, _p, _p])
+_adam_grad_sq = _sig("bmc_adam_grad_sq", [_p, _i, _p, _p])
+_adam_step_clip = _sig("bmc_adam_step_clipped", [_p, _i, AdamHyper, AdamClip, _p])
+_adam_step_clip_cap = _sig("bmc_adam_step_clipped_capturable", [_p, _i, AdamHyper, _p, AdamClip, _p])
 
 EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_events_to_voxel", "bmc_events_to_stack", "bmc_encode_raw_events", "bmc_pack_weight", "bmc_pack_weight_t", "bmc_split_weight", "bmc_conv",
            "bmc_pgemm", "bmc_pgemm_wave_map", "bmc_pgemm_reduce_weight", "bmc_pgemm_reduce_plain", "bmc_colsum", "bmc_relu_bwd",
@@ -173,7 +181,7 @@ EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_event
            "bmc_conv_wino_rows", "bmc_slot_stage", "bmc_slot_commit", "bmc_slot_metrics", "bmc_slot_encode", "bmc_slot_emit",
            "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes", "bmc_slot_emit_clocked", "bmc_slot_hot_update",
            "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_seq_encode", "bmc_adam_step",
-           "bmc_adam_step_capturable"]
+           "bmc_adam_step_capturable", "bmc_adam_grad_sq", "bmc_adam_step_clipped", "bmc_adam_step_clipped_capturable"]
 
 
 def check(rc, what):

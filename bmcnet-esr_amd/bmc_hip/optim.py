@@ -12,9 +12,22 @@ of all data pointers (the caching allocator repeats addresses: from the second s
 updates p, exp_avg, exp_avg_sq and max_exp_avg_sq in place, 36 bytes per element; the parameters' version counters advance, so
 that every cache keyed on them (weight packs, chains, inference graphs) sees the new values.  There is no fallback: what the
 kernel does not do (CPU, non-fp32 or non-contiguous parameters, sparse gradients, maximize, ...) raises ValueError.
+
+Clipping (csrc/optim_clip.hip; include/bmc_hip.h "optimizer step: clipping").  Adam(..., max_grad_norm=X) clips by the global L2
+norm of ALL gradients of the step, as torch.nn.utils.clip_grad_norm_(model.parameters(), X) before step() does, and
+nonfinite="skip" leaves parameters and state untouched when any gradient element is Inf or NaN -- both without a host round
+trip: one norm launch per step launch writes float64 partials, and every workgroup of the step launches adds them up in one
+fixed order to the same coefficient c = min(1, X / (norm + 1e-6)).  Different from torch: `.grad` is NEVER written (the kernel
+multiplies while it reads), so gradients that are views of GradAllReducer's flat buckets stay as reduced; the pre-step hooks
+(the side-stream join of bmc_hip.ops, the reducer's all-reduce) run before the norm launch, so the norm is that of the
+reduced gradients.  A skipped step still counts as a step: `step` advances on the host and on the device (nothing on the host
+can know it was skipped without a sync), later bias corrections see t one higher, and the parameters' version counters advance
+after every step, a skipped one included.  The two options are attributes of the optimizer like track_grad_norm, not part of
+param_groups or state_dict(): state dicts keep interchanging with torch.optim.Adam.
 """
 from __future__ import annotations
 
+import numbers
 from collections import OrderedDict
 
 import numpy as np
@@ -27,6 +40,7 @@ CHUNK = 4096                      # BMC_ADAM_CHUNK
 CHUNK_DTYPE = np.dtype({"names": ["p", "g", "m", "v", "vmax", "n", "aligned"], "formats": ["<u8"] * 5 + ["<i4", "<i4"],
                         "offsets": [0, 8, 16, 24, 32, 40, 44], "itemsize": 48})       # bmc_adam_chunk_t
 STEP_LAUNCHES = 0                 # calls of bmc_adam_step / bmc_adam_step_capturable of this process
+NORM_LAUNCHES = 0                 # calls of bmc_adam_grad_sq of this process (a clipped step: one per step launch)
 TABLE_COPIES = 0                  # chunk tables copied to the device
 MEMO_TABLES = 8                   # chunk tables kept per optimizer
 _REFUSED = ("maximize", "foreach", "fused", "differentiable", "decoupled_weight_decay")
@@ -73,7 +87,9 @@ def step_hyper(lr, beta1, beta2, eps, weight_decay, amsgrad, step):
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, capturable=False,
-                 track_grad_norm=False, foreach=None, maximize=False, differentiable=False, fused=None, decoupled_weight_decay=False):
+                 track_grad_norm=False, foreach=None, maximize=False, differentiable=False, fused=None, decoupled_weight_decay=False,
+                 max_grad_norm=None, nonfinite="propagate"):
+        _check_clip(max_grad_norm, nonfinite)                # before the parameters are looked at
         if isinstance(lr, torch.Tensor):
             raise ValueError("bmc_hip.optim.Adam: a tensor lr is not supported (the step size is computed on the host)")
         if not 0.0 <= lr:
@@ -89,6 +105,11 @@ class Adam(torch.optim.Optimizer):
                         capturable=capturable, differentiable=differentiable, fused=fused, decoupled_weight_decay=decoupled_weight_decay)
         _check_group(defaults)
         self.track_grad_norm = bool(track_grad_norm)
+        self.max_grad_norm = max_grad_norm                   # None: never clip
+        self.nonfinite = nonfinite                           # "propagate" | "skip"
+        self._clip_memo = OrderedDict()   # the tables' keys of a clipped step -> its float64 partials (one array for all launches)
+        self._clip_info = self._skipped = None               # device float64[2] {norm, c}; device int32 count of skipped steps
+        self._clip_stepped = False
         self._memo = OrderedDict()        # data pointers of a launch -> (device table, chunks, partials or None)
         self._pinned = self._pinned_event = None
         self._norm_parts = None           # the partials the last step() wrote
@@ -107,7 +128,7 @@ class Adam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._cohorts.clear(); self._cohort_of.clear(); self._count.clear()       # the state tensors are other tensors now
-        self._memo.clear()
+        self._memo.clear(); self._clip_memo.clear()
 
     # ------------------------------------------------------------------ one step
     @torch.no_grad()
@@ -116,6 +137,10 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        _check_clip(self.max_grad_norm, self.nonfinite)
+        if self._clipping:
+            self._step_clipped()
+            return loss
         parts = []
         for gi, group in enumerate(self.param_groups):
             self._step_group(gi, group, parts)
@@ -123,10 +148,20 @@ class Adam(torch.optim.Optimizer):
             self._norm_parts = parts
         return loss
 
+    @property
+    def _clipping(self):
+        return self.max_grad_norm is not None or self.nonfinite == "skip"
+
     def _step_group(self, gi, group, parts):
+        amsgrad, cap = bool(group["amsgrad"]), bool(group["capturable"])
+        for (dev, count), rows in self._collect(gi, group).items():
+            self._launch(group, dev, count, rows, amsgrad, cap, parts)
+
+    def _collect(self, gi, group):
+        """The launches of one group: (device index, step count) -> [(p, grad, state)], state made where it is missing."""
         _check_group(group)
         amsgrad, cap = bool(group["amsgrad"]), bool(group["capturable"])
-        launches = {}                     # (device index, step count) -> [(p, grad, state)]
+        launches = {}
         for i, p in enumerate(group["params"]):
             g = p.grad
             if g is None:
@@ -163,13 +198,11 @@ class Adam(torch.optim.Optimizer):
                     step_t = st["step"] = step_t.cpu()
                 count = step_t.item()
             launches.setdefault((p.device.index, count), []).append((p, g, st))
-        for (dev, count), rows in launches.items():
-            self._launch(group, dev, count, rows, amsgrad, cap, parts)
+        return launches
 
     def _launch(self, group, dev, count, rows, amsgrad, cap, parts):
         global STEP_LAUNCHES
-        key = tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                     st["max_exp_avg_sq"].data_ptr() if amsgrad else 0, p.numel()) for p, g, st in rows)
+        key = _table_key(rows, amsgrad)
         other = torch.cuda.current_device() != dev
         if other:
             prev = torch.cuda.current_device()
@@ -222,11 +255,105 @@ class Adam(torch.optim.Optimizer):
         table.copy_(self._pinned[:nbytes], non_blocking=True)
         self._pinned_event.record()
         TABLE_COPIES += 1
-        partial = torch.empty(len(tab), dtype=torch.float64, device=table.device) if self.track_grad_norm else None
+        partial = torch.empty(len(tab), dtype=torch.float64, device=table.device) if self.track_grad_norm and not self._clipping else None
         hit = self._memo[key] = (table, len(tab), partial)
         while len(self._memo) > MEMO_TABLES:
             self._memo.popitem(last=False)
         return hit
+
+    # ------------------------------------------------------------------ one clipped step
+    def _step_clipped(self):
+        """k norm launches into ONE partials array, then k step launches that each read all of it (k: the launches of an
+        unclipped step).  The norm is global: over every parameter that has a gradient, across groups and cohorts."""
+        global STEP_LAUNCHES, NORM_LAUNCHES
+        devs = {p.grad.device for group in self.param_groups for p in group["params"] if p.grad is not None}
+        if len(devs) > 1:
+            raise ValueError("bmc_hip.optim.Adam: the gradients of a clipped step live on %s; one global norm needs them on one "
+                             "device" % ", ".join(sorted(str(d) for d in devs)))
+        plan = []
+        for gi, group in enumerate(self.param_groups):
+            amsgrad, cap = bool(group["amsgrad"]), bool(group["capturable"])
+            for (dev, count), rows in self._collect(gi, group).items():
+                plan.append((group, dev, count, rows, amsgrad, cap))
+        if not plan:
+            return
+        dev = plan[0][1]
+        other = torch.cuda.current_device() != dev
+        if other:
+            prev = torch.cuda.current_device()
+            torch.cuda.set_device(dev)
+        try:
+            keys = tuple(_table_key(rows, amsgrad) for _, _, _, rows, amsgrad, _ in plan)
+            tables = [self._table(key, dev) for key in keys]
+            partials = self._clip_buffers(keys, sum(n for _, n, _ in tables), dev)
+            stream = torch._C._cuda_getCurrentRawStream(dev)
+            at = 0
+            for table, n_chunks, _ in tables:                # all norm launches first ...
+                lib.call(lib._adam_grad_sq, "bmc_adam_grad_sq", table.data_ptr(), n_chunks, partials.data_ptr() + 8 * at, stream)
+                NORM_LAUNCHES += 1
+                at += n_chunks
+            for j, ((group, _, count, rows, amsgrad, cap), (table, n_chunks, _)) in enumerate(zip(plan, tables)):
+                clip = lib.AdamClip()                        # ... then the step launches, each reading the whole array
+                clip.partial_sq, clip.n_partials = partials.data_ptr(), partials.numel()
+                clip.max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
+                clip.skip_nonfinite = int(self.nonfinite == "skip")
+                if j == 0:                                   # the first step launch of the step reports
+                    clip.info, clip.skipped = self._clip_info.data_ptr(), self._skipped.data_ptr()
+                beta1, beta2 = group["betas"]
+                steps = [st["step"] for _, _, st in rows]
+                if cap:
+                    h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, None)
+                    step_dev = self._cohort(rows, dev)
+                    lib.call(lib._adam_step_clip_cap, "bmc_adam_step_clipped_capturable", table.data_ptr(), n_chunks, h,
+                             step_dev.data_ptr(), clip, stream)
+                else:
+                    h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, count + 1)
+                    lib.call(lib._adam_step_clip, "bmc_adam_step_clipped", table.data_ptr(), n_chunks, h, clip, stream)
+                torch._foreach_add_(steps, 1.0)              # a skipped step counts as a step
+                STEP_LAUNCHES += 1
+                torch.autograd.graph.increment_version([p for p, _, _ in rows])      # also after a skipped step
+        finally:
+            if other:
+                torch.cuda.set_device(prev)
+        self._norm_parts = [partials]
+        self._clip_stepped = True
+
+    def _clip_buffers(self, keys, n_partials, dev):
+        """The partials array of a clipped step, memoised like the chunk tables by the buffers of all its launches; the info and
+        skipped buffers live as long as the optimizer.  Nothing is allocated during a graph capture."""
+        partials = self._clip_memo.get(keys)
+        device = torch.device("cuda", dev)
+        if partials is not None and self._clip_info is not None and self._clip_info.device == device:
+            self._clip_memo.move_to_end(keys)
+            return partials
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bmc_hip.optim.Adam: this set of parameter, gradient and state buffers has no partials buffer on the "
+                               "device yet and none can be allocated during a graph capture; take one step() with the same buffers first")
+        if self._clip_info is None or self._clip_info.device != device:
+            self._clip_info = torch.zeros(2, dtype=torch.float64, device=device)
+            self._skipped = torch.zeros((), dtype=torch.int32, device=device)
+        if partials is None:
+            partials = self._clip_memo[keys] = torch.zeros(n_partials, dtype=torch.float64, device=device)
+            while len(self._clip_memo) > MEMO_TABLES:
+                self._clip_memo.popitem(last=False)
+        return partials
+
+    def last_clip(self):
+        """The device float64[2] tensor {norm, c} of the last clipped step(): the global L2 norm of its gradients and the
+        coefficient they were multiplied by (1.0: not clipped).  After a skipped step the norm is not finite.  No host sync."""
+        if not self._clipping:
+            raise RuntimeError("bmc_hip.optim.Adam: last_clip() needs max_grad_norm or nonfinite='skip'")
+        if not self._clip_stepped:
+            raise RuntimeError("bmc_hip.optim.Adam: last_clip() before the first step() that had gradients")
+        return self._clip_info
+
+    def skipped_steps(self):
+        """A 0-d device int32 tensor: the steps skipped so far under nonfinite='skip'.  No host sync."""
+        if not self._clipping:
+            raise RuntimeError("bmc_hip.optim.Adam: skipped_steps() needs max_grad_norm or nonfinite='skip'")
+        if not self._clip_stepped:
+            raise RuntimeError("bmc_hip.optim.Adam: skipped_steps() before the first step() that had gradients")
+        return self._skipped
 
     def _cohort(self, rows, dev):
         """capturable: the device int32 step counter of the parameters that leave in one launch.  It is made from the first
@@ -253,14 +380,30 @@ class Adam(torch.optim.Optimizer):
     # ------------------------------------------------------------------ gradient norm
     def grad_norm(self):
         """L2 norm of the raw gradients the last step() consumed (before weight decay): a 0-d float64 device tensor, the square
-        root of the sum of the per-chunk float64 partials the kernel stored.  No host sync."""
-        if not self.track_grad_norm:
+        root of the sum of the per-chunk float64 partials the kernel stored (with clipping on: the norm launches' partials, the
+        norm BEFORE clipping).  No host sync."""
+        if not (self.track_grad_norm or self._clipping):
             raise RuntimeError("bmc_hip.optim.Adam: grad_norm() needs track_grad_norm=True")
         if not self._norm_parts:
             raise RuntimeError("bmc_hip.optim.Adam: grad_norm() before the first step() that had gradients")
         parts = self._norm_parts
         flat = parts[0] if len(parts) == 1 else torch.cat([q.to(parts[0].device) for q in parts])
         return flat.sum().sqrt()
+
+
+def _table_key(rows, amsgrad):
+    return tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                  st["max_exp_avg_sq"].data_ptr() if amsgrad else 0, p.numel()) for p, g, st in rows)
+
+
+def _check_clip(max_grad_norm, nonfinite):
+    if max_grad_norm is not None:
+        if isinstance(max_grad_norm, (bool, torch.Tensor)) or not isinstance(max_grad_norm, numbers.Real):
+            raise ValueError("bmc_hip.optim.Adam: max_grad_norm must be None or a positive Python number, not %r" % (max_grad_norm,))
+        if not float(np.float32(max_grad_norm)) > 0:         # NaN fails too; the kernel takes it as float32
+            raise ValueError("bmc_hip.optim.Adam: max_grad_norm = %r is not a positive number (in float32)" % (max_grad_norm,))
+    if nonfinite not in ("propagate", "skip"):
+        raise ValueError("bmc_hip.optim.Adam: nonfinite must be 'propagate' or 'skip', not %r" % (nonfinite,))
 
 
 def _name(group, i, gi):

@@ -807,6 +807,54 @@ int bmc_adam_step(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t 
 int bmc_adam_step_capturable(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, int* step_dev, double* partial_sq,
                              bmc_stream_t s);
 
+/* ---- optimizer step: clipping (bmcnet-esr_amd/bmc_hip/optim.py::Adam(max_grad_norm=, nonfinite=); csrc/optim_clip.hip) ----------
+ * Clipping by the GLOBAL L2 norm of all gradients of a step (torch.nn.utils.clip_grad_norm_ followed by Adam.step()) and the skip
+ * of a step whose gradients are not finite, with no host round trip.  A clipped step of one optimizer is k NORM launches followed
+ * by k STEP launches over the same k chunk tables, k being the launches of an unclipped step (one per group and step-count cohort,
+ * normally 1).  The partials of all k norm launches share ONE float64 array of n_partials entries; launch j writes its n_chunks
+ * entries at its offset, and every step launch reads the whole array.
+ * Norm launch, bmc_adam_grad_sq: grid n_chunks workgroups of 256 lanes; chunk i stores sum(double(g) * double(g)) over its
+ * elements at partial_sq[i], with the lane-to-element assignment (aligned and element-wise path alike), the per-lane order and the
+ * fixed LDS tree of the step kernel above: for one table the values are BIT-IDENTICAL to what bmc_adam_step(..., partial_sq, ...)
+ * stores.  It reads g only and writes nothing but partial_sq[0 .. n_chunks).
+ * Step launch: every workgroup first forms the same total -- lane t adds partial_sq[t], partial_sq[t + 256], ... in that order in
+ * float64, then the same fixed tree -- so all workgroups hold identical bits.  Then, each line ONE rounding, no fused multiply-add:
+ *     norm = sqrt(total)                float64
+ *     n32  = (float) norm
+ *     s    = n32 + 1e-6f                float32
+ *     q    = max_norm / s               float32, IEEE division
+ *     c    = (q > 1.0f) ? 1.0f : q      a NaN q stays NaN (torch.clamp(max=1.0))
+ *     g_c  = g * c                      float32; g itself is never written
+ * and the six lines of "optimizer step" run on g_c (weight decay is added AFTER clipping, as when one clips before torch's step()).
+ * Both translation units compile the same element function (csrc/adam_k.h): for c == 1.0f the results are bit-identical to
+ * bmc_adam_step's.  max_norm = +INF never clips (c = 1 for every finite total).
+ * Non-finite totals.  Squares of float32 values cannot overflow float64: the total is not finite exactly when some gradient
+ * element is Inf or NaN.  skip_nonfinite == 0: the formulas decide -- an Inf total gives c = 0 (finite gradients become 0, Inf
+ * elements NaN), a NaN total gives c = NaN (everything becomes NaN): clip_grad_norm_(error_if_nonfinite=False).  skip_nonfinite == 1
+ * and a non-finite total: no workgroup stores anything to p, m, v or vmax (the branch is uniform over the grid).
+ * info, NULL or a device double[2]: workgroup 0 stores info[0] = norm, info[1] = (double) c, also for a skipped step.  skipped,
+ * NULL or a device int32: when the step is skipped, workgroup 0 does *skipped += 1.  Both are plain stores by one lane.  The host
+ * passes info and skipped to the FIRST step launch of a step only.
+ * The clipped entry points have no partial_sq output of their own: the norm launches' array is the gradient norm's partials.
+ * Capturable form: the step count comes from *step_dev as in bmc_adam_step_capturable, and the advance launch follows the step
+ * launch ALSO for a skipped step: a skipped step counts as a step, on the host and on the device (nothing on the host can know
+ * otherwise without a sync), so the bias corrections of later steps see t one higher than the number of updates applied.
+ * Checked: n_chunks >= 0, tables and partial_sq non-NULL where n_chunks > 0, n_partials >= n_chunks, max_norm > 0 and not NaN,
+ * skip_nonfinite 0 or 1, and the hyper-parameter checks above.  Trusted: the tables.  No flat access, no scratch, no atomics, no
+ * workgroup waits for another. */
+typedef struct bmc_adam_clip {
+    const double* partial_sq;   /* the whole partials array of the step */
+    double* info;               /* NULL or double[2]: {norm, c} */
+    int* skipped;               /* NULL or int32: += 1 when the step is skipped */
+    int n_partials;             /* length of partial_sq */
+    float max_norm;             /* > 0; +INF: never clip */
+    int skip_nonfinite;         /* 0 or 1 */
+} bmc_adam_clip_t;
+int bmc_adam_grad_sq(const bmc_adam_chunk_t* table, int n_chunks, double* partial_sq, bmc_stream_t s);
+int bmc_adam_step_clipped(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, bmc_adam_clip_t clip, bmc_stream_t s);
+int bmc_adam_step_clipped_capturable(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, int* step_dev,
+                                     bmc_adam_clip_t clip, bmc_stream_t s);
+
 #ifdef __cplusplus
 }
 #endif

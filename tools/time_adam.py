@@ -11,7 +11,13 @@ cannot keep up shows here too) and the median.  Floors for comparison: 36 bytes 
 `rocprofv3 --kernel-trace --stats -- python tools/time_adam.py --only NAME --steps N` (N = 2 and N = 7, no timing) and the
 difference of the two traces' kernel counts over 5 steps is printed: set-up kernels cancel.  No counters are collected.
 
-python tools/time_adam.py [--steps 50 --warmup 10 --rounds 3] [--sets bmcnet,plain] [--only hip|foreach|single] [--trace [--trace-dir DIR]]
+--clip: the clipped step (csrc/optim_clip.hip, TWO launches).  Three figures per set: hip_clip, bmc_hip.optim.Adam(max_grad_norm=
+--clip-norm); hip, the unclipped fused step (the difference is the cost of the feature); foreach_clip, what a user has otherwise:
+torch.nn.utils.clip_grad_norm_ with its default foreach followed by torch.optim.Adam with its default.  Floor of the clipped step:
+40 bytes per element (the norm launch reads g once more) and one more launch.
+
+python tools/time_adam.py [--steps 50 --warmup 10 --rounds 3] [--sets bmcnet,plain] [--only NAME] [--clip [--clip-norm 1.0]]
+                          [--trace [--trace-dir DIR]]
 """
 import argparse
 import csv
@@ -27,13 +33,31 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
 
 CFG = dict(lr=1e-4, weight_decay=1e-5, amsgrad=True)
 NAMES = ("foreach", "single", "hip")
+CLIP_NAMES = ("foreach_clip", "hip", "hip_clip")
 
 
-def make(name, params):
+class TorchClipped:
+    """clip_grad_norm_ (default foreach) and torch.optim.Adam (default foreach) as one step()"""
+
+    def __init__(self, params, max_norm):
+        import torch
+        self.params, self.max_norm, self.opt = params, max_norm, torch.optim.Adam(params, **CFG)
+
+    def step(self):
+        import torch
+        torch.nn.utils.clip_grad_norm_(self.params, self.max_norm)
+        self.opt.step()
+
+
+def make(name, params, clip_norm=1.0):
     import torch
     from bmc_hip.optim import Adam
     if name == "hip":
         return Adam(params, **CFG)
+    if name == "hip_clip":
+        return Adam(params, max_grad_norm=clip_norm, **CFG)
+    if name == "foreach_clip":
+        return TorchClipped(params, clip_norm)
     return torch.optim.Adam(params, foreach=None if name == "foreach" else False, **CFG)
 
 
@@ -64,7 +88,7 @@ def timed(opt, steps):
 def run(a):
     import torch
     dev = torch.device("cuda:0")
-    names = [a.only] if a.only else list(NAMES)
+    names = [a.only] if a.only else list(CLIP_NAMES if a.clip else NAMES)
     for kind in a.sets.split(","):
         base = parameter_set(kind, dev)
         n = sum(p.numel() for p in base)
@@ -73,7 +97,7 @@ def run(a):
             params = [torch.nn.Parameter(p.detach().clone()) for p in base]
             for p, q in zip(params, base):
                 p.grad = q.grad.clone()
-            opts[name] = make(name, params)
+            opts[name] = make(name, params, a.clip_norm)
         for _ in range(a.warmup):
             for name in names:
                 opts[name].step()
@@ -88,10 +112,11 @@ def run(a):
         for _ in range(a.rounds):
             for name in names:                  # alternating: what shares the machine hits all three alike
                 rounds[name].append(timed(opts[name], a.steps))
-        print("%s: %d tensors, %d elements, %.1f MB per pass (36 B per element; %.1f us at 6.3 TB/s)" % (
-            kind, len(base), n, 36 * n / 1e6, 36 * n / 6.3e12 * 1e6))
+        per = 40 if a.clip else 36
+        print("%s: %d tensors, %d elements, %.1f MB per pass (%d B per element; %.1f us at 6.3 TB/s)" % (
+            kind, len(base), n, per * n / 1e6, per, per * n / 6.3e12 * 1e6))
         for name in names:
-            print("  %-8s ms per step, %d steps per round: %s   median %.4f" % (
+            print("  %-12s ms per step, %d steps per round: %s   median %.4f" % (
                 name, a.steps, "  ".join("%.4f" % v for v in rounds[name]), statistics.median(rounds[name])))
 
 
@@ -109,12 +134,12 @@ def kernel_count(out_dir):
 def trace(a):
     base = a.trace_dir or tempfile.mkdtemp(prefix="time_adam_trace_")
     for kind in a.sets.split(","):
-        for name in ([a.only] if a.only else NAMES):
+        for name in ([a.only] if a.only else (CLIP_NAMES if a.clip else NAMES)):
             counts = {}
             for steps in (2, 7):
                 out = os.path.join(base, "%s_%s_%d" % (kind, name, steps))
                 cmd = ["rocprofv3", "--kernel-trace", "--stats", "--output-format", "csv", "-d", out, "-o", "t", "--", sys.executable,
-                       os.path.abspath(__file__), "--only", name, "--sets", kind, "--steps", str(steps), "--warmup", "0", "--rounds", "0"]
+                       os.path.abspath(__file__), "--only", name, "--clip-norm", str(a.clip_norm), "--sets", kind, "--steps", str(steps), "--warmup", "0", "--rounds", "0"]
                 r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, timeout=a.child_timeout)
                 if r.returncode != 0:
                     raise SystemExit("traced run failed (rc %d):\n%s" % (r.returncode, r.stdout.decode()[-2000:]))
@@ -129,7 +154,9 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sets", default="bmcnet,plain")
-    ap.add_argument("--only", choices=NAMES, default=None)
+    ap.add_argument("--only", choices=NAMES + CLIP_NAMES[::2], default=None)
+    ap.add_argument("--clip", action="store_true")
+    ap.add_argument("--clip-norm", type=float, default=1.0)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--trace-dir", default=None)
     ap.add_argument("--child-timeout", type=float, default=240.0)

@@ -10,8 +10,12 @@ The index tables are cut here with bmc_hip.encodings.event_window_indices (the r
 
 python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x80] [--steps 10] [--batch 2] [--L 9] [--step-size S]
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
-                             [--optimizer hip|torch] [--wall]
+                             [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
+--clip-norm X: clip the gradients by their global L2 norm.  hip: Adam(max_grad_norm=X), a norm launch and a step launch
+(csrc/optim_clip.hip); torch: torch.nn.utils.clip_grad_norm_ in a pre-step hook, so that the two can be compared.
+--nonfinite skip (hip only): a step whose gradients hold an Inf or a NaN leaves parameters and state untouched.
+With either, the norm and coefficient of the last step and the number of skipped steps are printed once at the end.
 --wall: also print the wall time per step at the end (host clock, device synchronised, the first step left out).
 """
 import argparse
@@ -76,6 +80,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--out", default=None)
     ap.add_argument("--optimizer", choices=("hip", "torch"), default="hip")
+    ap.add_argument("--clip-norm", type=float, default=None)
+    ap.add_argument("--nonfinite", choices=("propagate", "skip"), default="propagate")
     ap.add_argument("--wall", action="store_true")
     a = ap.parse_args()
     if not a.recordings and not a.synthetic:
@@ -98,9 +104,14 @@ def main():
     m = BMCNet(a.scale, a.n_c, a.n_b).to(dev)
     if a.optimizer == "hip":
         from bmc_hip.optim import Adam
-        opt = Adam(m.parameters(), lr=a.lr)
+        opt = Adam(m.parameters(), lr=a.lr, max_grad_norm=a.clip_norm, nonfinite=a.nonfinite)
     else:
+        if a.nonfinite != "propagate":
+            raise SystemExit("--nonfinite skip needs --optimizer hip (torch.optim.Adam cannot skip a step without a host sync)")
         opt = torch.optim.Adam(m.parameters(), lr=a.lr)
+        if a.clip_norm is not None:
+            clipped = list(m.parameters())
+            opt.register_step_pre_hook(lambda *_: (torch.nn.utils.clip_grad_norm_(clipped, a.clip_norm), None)[1])
     g = torch.Generator().manual_seed(a.seed)
     rows, step, epoch, clock = [], 0, 0, None
     while step < a.steps:
@@ -126,6 +137,9 @@ def main():
     if a.wall and step > 1:
         torch.cuda.synchronize()
         print("optimizer %s: %.3f ms wall per step over steps 1..%d" % (a.optimizer, (time.perf_counter() - clock) * 1e3 / (step - 1), step - 1))
+    if a.optimizer == "hip" and (a.clip_norm is not None or a.nonfinite == "skip"):
+        norm, c = opt.last_clip().tolist()                   # once, at the end: the step itself never syncs
+        print("last step: gradient norm %.6g, clip coefficient %.6g; %d of %d steps skipped" % (norm, c, int(opt.skipped_steps()), step))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(rows, f)
