@@ -13,7 +13,7 @@ updates p, exp_avg, exp_avg_sq and max_exp_avg_sq in place, 36 bytes per element
 that every cache keyed on them (weight packs, chains, inference graphs) sees the new values.  There is no fallback: what the
 kernel does not do (CPU, non-fp32 or non-contiguous parameters, sparse gradients, maximize, ...) raises ValueError.
 
-Clipping (csrc/optim_clip.hip; include/bmc_hip.h "optimizer step: clipping").  Adam(..., max_grad_norm=X) clips by the global L2
+Clipping (csrc/optim.hip as well; include/bmc_hip.h "optimizer step: clipping").  Adam(..., max_grad_norm=X) clips by the global L2
 norm of ALL gradients of the step, as torch.nn.utils.clip_grad_norm_(model.parameters(), X) before step() does, and
 nonfinite="skip" leaves parameters and state untouched when any gradient element is Inf or NaN -- both without a host round
 trip: one norm launch per step launch writes float64 partials, and every workgroup of the step launches adds them up in one
@@ -201,36 +201,30 @@ class Adam(torch.optim.Optimizer):
         return launches
 
     def _launch(self, group, dev, count, rows, amsgrad, cap, parts):
-        global STEP_LAUNCHES
-        key = _table_key(rows, amsgrad)
-        other = torch.cuda.current_device() != dev
-        if other:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(dev)
-        try:
-            table, n_chunks, partial = self._table(key, dev)
-            beta1, beta2 = group["betas"]
-            steps = [st["step"] for _, _, st in rows]
-            stream = torch._C._cuda_getCurrentRawStream(dev)
-            part_ptr = partial.data_ptr() if partial is not None else None
-            if cap:
-                h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, None)
-                step_dev = self._cohort(rows, dev)
-                lib.call(lib._adam_step_cap, "bmc_adam_step_capturable", table.data_ptr(), n_chunks, h, step_dev.data_ptr(), part_ptr,
-                         stream)
-                torch._foreach_add_(steps, 1.0)              # torch's own state key, kept true on the device
-            else:
-                h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, count + 1)
-                lib.call(lib._adam_step, "bmc_adam_step", table.data_ptr(), n_chunks, h, part_ptr, stream)
-                torch._foreach_add_(steps, 1.0)              # host tensors: no launch
-        finally:
-            if other:
-                torch.cuda.set_device(prev)
-        STEP_LAUNCHES += 1
-        # the kernel wrote the parameters behind autograd's back: everything keyed on p._version must see a new version
-        torch.autograd.graph.increment_version([p for p, _, _ in rows])
+        with _current(dev):
+            table, n_chunks, partial = self._table(_table_key(rows, amsgrad), dev)
+            self._issue(group, dev, count, rows, amsgrad, cap, table, n_chunks, partial.data_ptr() if partial is not None else None)
         if partial is not None:
             parts.append(partial)
+
+    def _issue(self, group, dev, count, rows, amsgrad, cap, table, n_chunks, last):
+        """One step launch over `table` on the current stream of `dev` (the current device).  last: the partials pointer of an
+        unclipped step (None: no partials) or the AdamClip of a clipped one -- it picks the entry point."""
+        global STEP_LAUNCHES
+        beta1, beta2 = group["betas"]
+        h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, None if cap else count + 1)
+        fn, name = _ENTRY[isinstance(last, lib.AdamClip), cap]
+        stream = torch._C._cuda_getCurrentRawStream(dev)
+        if cap:
+            lib.call(fn, name, table.data_ptr(), n_chunks, h, self._cohort(rows, dev).data_ptr(), last, stream)
+        else:
+            lib.call(fn, name, table.data_ptr(), n_chunks, h, last, stream)
+        # torch's own state key: host tensors (no launch), or with capturable kept true on the device; a skipped step counts too
+        torch._foreach_add_([st["step"] for _, _, st in rows], 1.0)
+        STEP_LAUNCHES += 1
+        # the kernel wrote the parameters behind autograd's back: everything keyed on p._version must see a new version (also
+        # after a skipped step)
+        torch.autograd.graph.increment_version([p for p, _, _ in rows])
 
     def _table(self, key, dev):
         global TABLE_COPIES
@@ -265,7 +259,7 @@ class Adam(torch.optim.Optimizer):
     def _step_clipped(self):
         """k norm launches into ONE partials array, then k step launches that each read all of it (k: the launches of an
         unclipped step).  The norm is global: over every parameter that has a gradient, across groups and cohorts."""
-        global STEP_LAUNCHES, NORM_LAUNCHES
+        global NORM_LAUNCHES
         devs = {p.grad.device for group in self.param_groups for p in group["params"] if p.grad is not None}
         if len(devs) > 1:
             raise ValueError("bmc_hip.optim.Adam: the gradients of a clipped step live on %s; one global norm needs them on one "
@@ -278,11 +272,7 @@ class Adam(torch.optim.Optimizer):
         if not plan:
             return
         dev = plan[0][1]
-        other = torch.cuda.current_device() != dev
-        if other:
-            prev = torch.cuda.current_device()
-            torch.cuda.set_device(dev)
-        try:
+        with _current(dev):
             keys = tuple(_table_key(rows, amsgrad) for _, _, _, rows, amsgrad, _ in plan)
             tables = [self._table(key, dev) for key in keys]
             partials = self._clip_buffers(keys, sum(n for _, n, _ in tables), dev)
@@ -292,29 +282,14 @@ class Adam(torch.optim.Optimizer):
                 lib.call(lib._adam_grad_sq, "bmc_adam_grad_sq", table.data_ptr(), n_chunks, partials.data_ptr() + 8 * at, stream)
                 NORM_LAUNCHES += 1
                 at += n_chunks
-            for j, ((group, _, count, rows, amsgrad, cap), (table, n_chunks, _)) in enumerate(zip(plan, tables)):
+            for j, (launch, (table, n_chunks, _)) in enumerate(zip(plan, tables)):
                 clip = lib.AdamClip()                        # ... then the step launches, each reading the whole array
                 clip.partial_sq, clip.n_partials = partials.data_ptr(), partials.numel()
                 clip.max_norm = float("inf") if self.max_grad_norm is None else self.max_grad_norm
                 clip.skip_nonfinite = int(self.nonfinite == "skip")
                 if j == 0:                                   # the first step launch of the step reports
                     clip.info, clip.skipped = self._clip_info.data_ptr(), self._skipped.data_ptr()
-                beta1, beta2 = group["betas"]
-                steps = [st["step"] for _, _, st in rows]
-                if cap:
-                    h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, None)
-                    step_dev = self._cohort(rows, dev)
-                    lib.call(lib._adam_step_clip_cap, "bmc_adam_step_clipped_capturable", table.data_ptr(), n_chunks, h,
-                             step_dev.data_ptr(), clip, stream)
-                else:
-                    h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, count + 1)
-                    lib.call(lib._adam_step_clip, "bmc_adam_step_clipped", table.data_ptr(), n_chunks, h, clip, stream)
-                torch._foreach_add_(steps, 1.0)              # a skipped step counts as a step
-                STEP_LAUNCHES += 1
-                torch.autograd.graph.increment_version([p for p, _, _ in rows])      # also after a skipped step
-        finally:
-            if other:
-                torch.cuda.set_device(prev)
+                self._issue(*launch, table, n_chunks, clip)
         self._norm_parts = [partials]
         self._clip_stepped = True
 
@@ -389,6 +364,30 @@ class Adam(torch.optim.Optimizer):
         parts = self._norm_parts
         flat = parts[0] if len(parts) == 1 else torch.cat([q.to(parts[0].device) for q in parts])
         return flat.sum().sqrt()
+
+
+# (clipped, capturable) -> the entry point of a step launch
+_ENTRY = {(False, False): (lib._adam_step, "bmc_adam_step"), (False, True): (lib._adam_step_cap, "bmc_adam_step_capturable"),
+          (True, False): (lib._adam_step_clip, "bmc_adam_step_clipped"),
+          (True, True): (lib._adam_step_clip_cap, "bmc_adam_step_clipped_capturable")}
+
+
+class _current:
+    """with _current(dev): device `dev` is the current one inside the block; the one before is restored after it.  A class, not a
+    generator: it sits in every step of a host-bound loop."""
+    __slots__ = ("dev", "prev")
+
+    def __init__(self, dev):
+        self.dev = dev
+
+    def __enter__(self):
+        self.prev = torch.cuda.current_device()
+        if self.prev != self.dev:
+            torch.cuda.set_device(self.dev)
+
+    def __exit__(self, *exc):
+        if self.prev != self.dev:
+            torch.cuda.set_device(self.prev)
 
 
 def _table_key(rows, amsgrad):

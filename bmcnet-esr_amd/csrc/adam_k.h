@@ -1,5 +1,6 @@
-// The element arithmetic of the optimizer step, shared by optim.hip (bmc_adam_step) and optim_clip.hip (the clipped step): both
-// translation units round alike because they compile THIS adam_elem.  Internal; the contract is include/bmc_hip.h "optimizer step".
+// The device pieces of the optimizer step, each written once and compiled by optim.hip alone: the element arithmetic, the view of a
+// chunk, the walk over it (with and without the state tensors) and the set-up of the step's constants.  Every kernel of the family
+// rounds alike because it runs THIS adam_elem over THIS walk.  Internal; the contract is include/bmc_hip.h "optimizer step".
 #pragma once
 #include <math.h>
 #include "bmc_common.h"
@@ -15,7 +16,7 @@ struct AdamK {
     float omb1, beta2, omb2, eps, wd, step_size, bc2s;
 };
 
-// One element.  Both load paths call this, so they round alike.  sqrt and the divisions are the compiler's own operators: in a HIP
+// One element.  Every load path calls this, so they round alike.  sqrt and the divisions are the compiler's own operators: in a HIP
 // compile these are the correctly rounded ones (the __fsqrt_rn / __fdiv_rn spellings are NOT: without OCML's rounded-operations
 // switch __fsqrt_rn is the native, 1-ulp square root).
 template <bool AMS>
@@ -55,24 +56,156 @@ __device__ __forceinline__ double tree_sum(double* red, double acc, int tid) {
     return red[0];
 }
 
-// ---- host: the argument checks every entry point of the family makes before it launches
-bool finite_f(float v) { return isfinite(v); }
+// ---- the coefficient of a clipped step: float32, one rounding per line (torch.nn.utils.clip_grad_norm_: max_norm / (norm + 1e-6),
+// clamped at 1)
+__device__ __forceinline__ float clip_coeff(double norm, float max_norm) {
+#pragma clang fp contract(off)
+    const float n32 = (float)norm;
+    const float s = n32 + 1e-6f;
+    const float q = max_norm / s;
+    return q > 1.0f ? 1.0f : q;                    // a NaN q stays NaN: torch.clamp(max=1.0)
+}
 
-int adam_check(const char* name, const bmc_adam_chunk_t* table, int n_chunks, const bmc_adam_hyper_t& h, bool cap) {
-    BMC_CHECK_ARG(n_chunks >= 0, "%s: n_chunks = %d is negative", name, n_chunks);
-    BMC_CHECK_ARG(table || n_chunks == 0, "%s: no chunk table for %d chunks", name, n_chunks);
-    BMC_CHECK_ARG(finite_f(h.beta1) && finite_f(h.one_minus_beta1) && finite_f(h.beta2) && finite_f(h.one_minus_beta2) &&
-                      finite_f(h.eps) && finite_f(h.weight_decay),
-                  "%s: a hyper-parameter is not finite (beta1 %g, 1 - beta1 %g, beta2 %g, 1 - beta2 %g, eps %g, weight_decay %g)", name,
-                  h.beta1, h.one_minus_beta1, h.beta2, h.one_minus_beta2, h.eps, h.weight_decay);
-    if (cap)
-        BMC_CHECK_ARG(isfinite(h.lr) && isfinite(h.beta1_f64) && isfinite(h.beta2_f64),
-                      "%s: a hyper-parameter is not finite (lr %g, beta1 %g, beta2 %g)", name, h.lr, h.beta1_f64, h.beta2_f64);
-    else
-        BMC_CHECK_ARG(finite_f(h.step_size) && finite_f(h.bias_correction2_sqrt),
-                      "%s: a hyper-parameter is not finite (step_size %g, bias_correction2_sqrt %g)", name, h.step_size,
-                      h.bias_correction2_sqrt);
-    return 0;
+__device__ __forceinline__ float clip_g(float g, float c) {
+#pragma clang fp contract(off)      // g * c is a rounding of its own; it never fuses into the first line of adam_elem
+    return g * c;
+}
+
+// ---- what a step does to every g before adam_elem sees it
+struct GradAsIs {                                  // the plain step
+    __device__ __forceinline__ float operator()(float g) const { return g; }
+};
+struct GradSumSq {                                 // ... that also adds the RAW g to this lane's share of sum(g^2)
+    double& acc;
+    __device__ __forceinline__ float operator()(float g) const { acc += sq(g); return g; }
+};
+struct GradClipped {                               // the clipped step
+    float c;
+    __device__ __forceinline__ float operator()(float g) const { return clip_g(g, c); }
+};
+
+// ---- one workgroup's chunk: the table's pointers made wave-uniform, n clamped to what a workgroup covers
+struct Chunk {
+    float* p;
+    const float* g;
+    float *m, *v, *x;                              // x: vmax, nullptr without amsgrad
+    int n;
+    bool aligned;
+};
+
+template <bool AMS>
+__device__ __forceinline__ Chunk chunk_view(const bmc_adam_chunk_t* ent) {
+    Chunk ck;
+    ck.p = uniform_ptr<float>(&ent->p);
+    ck.g = uniform_ptr<const float>(&ent->g);
+    ck.m = uniform_ptr<float>(&ent->m);
+    ck.v = uniform_ptr<float>(&ent->v);
+    ck.x = AMS ? uniform_ptr<float>(&ent->vmax) : nullptr;
+    const int n = __builtin_amdgcn_readfirstlane(gld<int>(&ent->n));
+    ck.n = n < BMC_ADAM_CHUNK ? n : BMC_ADAM_CHUNK;
+    ck.aligned = __builtin_amdgcn_readfirstlane(gld<int>(&ent->aligned)) != 0;
+    return ck;
+}
+
+// element e on its own: the tail of an aligned chunk and every element of an unaligned one
+template <bool AMS, class Grad>
+__device__ __forceinline__ void step_elem(const Chunk& ck, int e, const AdamK& k, const Grad& grad) {
+    const float ge = grad(gld<float>(ck.g + e));
+    float pe = gld<float>(ck.p + e), me = gld<float>(ck.m + e), ve = gld<float>(ck.v + e), xe = AMS ? gld<float>(ck.x + e) : 0.f;
+    adam_elem<AMS>(pe, ge, me, ve, xe, k);
+    gst<float>(ck.p + e, pe); gst<float>(ck.m + e, me); gst<float>(ck.v + e, ve);
+    if constexpr (AMS) gst<float>(ck.x + e, xe);
+}
+
+// The whole 16-byte vectors of an aligned chunk: vector tid + j * AT is this lane's j-th.  FULL: the chunk has all 4096 elements and
+// nothing is guarded -- straight-line code, the 20 loads of a lane are issued before the first is used.
+template <bool AMS, bool FULL, class Grad>
+__device__ __forceinline__ void vec_pass(const Chunk& ck, int nvec, int tid, const AdamK& k, const Grad& grad) {
+    f32x4 P[VPL], G[VPL], M[VPL], V[VPL], X[VPL];
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int e = 4 * (tid + j * AT);
+        if (FULL || tid + j * AT < nvec) {
+            P[j] = gld<f32x4>(ck.p + e); G[j] = gld<f32x4>(ck.g + e); M[j] = gld<f32x4>(ck.m + e); V[j] = gld<f32x4>(ck.v + e);
+            if constexpr (AMS) X[j] = gld<f32x4>(ck.x + e);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < VPL; ++j) {
+        const int e = 4 * (tid + j * AT);
+        if (FULL || tid + j * AT < nvec) {
+#pragma unroll
+            for (int c = 0; c < 4; ++c) {
+                float pe = P[j][c], me = M[j][c], ve = V[j][c], xe = AMS ? X[j][c] : 0.f;
+                adam_elem<AMS>(pe, grad(G[j][c]), me, ve, xe, k);
+                P[j][c] = pe; M[j][c] = me; V[j][c] = ve;
+                if constexpr (AMS) X[j][c] = xe;
+            }
+            gst<f32x4>(ck.p + e, P[j]); gst<f32x4>(ck.m + e, M[j]); gst<f32x4>(ck.v + e, V[j]);
+            if constexpr (AMS) gst<f32x4>(ck.x + e, X[j]);
+        }
+    }
+}
+
+// ---- THE WALK.  step_chunk and grad_sq_chunk give a lane the same elements in the same order, which is why the partials of the norm
+// launch are the bits a step launch with GradSumSq stores.  Aligned chunk: the lane's vectors tid + j * AT for j = 0 .. VPL - 1 below
+// n / 4, components 0 .. 3 of each, then element 4 * (n / 4) + tid of the last partial vector.  Unaligned chunk: elements tid,
+// tid + AT, ... below n.  Change one of the two functions and the other changes with it.
+template <bool AMS, class Grad>
+__device__ __forceinline__ void step_chunk(const Chunk& ck, int tid, const AdamK& k, const Grad& grad) {
+    if (ck.aligned) {
+        const int nvec = ck.n >> 2;
+        if (ck.n == BMC_ADAM_CHUNK) vec_pass<AMS, true>(ck, nvec, tid, k, grad);      // all loads in flight, then the arithmetic
+        else vec_pass<AMS, false>(ck, nvec, tid, k, grad);
+        const int e = 4 * nvec + tid;
+        if (e < ck.n) step_elem<AMS>(ck, e, k, grad);
+    } else {
+        for (int e = tid; e < ck.n; e += AT) step_elem<AMS>(ck, e, k, grad);
+    }
+}
+
+// the same walk over g alone -> this lane's share of sum(g^2)
+__device__ __forceinline__ double grad_sq_chunk(const Chunk& ck, int tid) {
+    double acc = 0.0;
+    if (ck.aligned) {
+        const int nvec = ck.n >> 2;
+        f32x4 G[VPL];
+#pragma unroll
+        for (int j = 0; j < VPL; ++j)
+            if (tid + j * AT < nvec) G[j] = gld<f32x4>(ck.g + 4 * (tid + j * AT));
+#pragma unroll
+        for (int j = 0; j < VPL; ++j)
+            if (tid + j * AT < nvec) {
+#pragma unroll
+                for (int c = 0; c < 4; ++c) acc += sq(G[j][c]);
+            }
+        const int e = 4 * nvec + tid;
+        if (e < ck.n) acc += sq(gld<float>(ck.g + e));
+    } else {
+        for (int e = tid; e < ck.n; e += AT) acc += sq(gld<float>(ck.g + e));
+    }
+    return acc;
+}
+
+// ---- the constants of a step.  CAP: the step count comes from *step_dev and the two bias corrections are computed here, in float64,
+// once per workgroup, as the host does for the plain entry points (every lane of the workgroup must call this: it holds a barrier).
+template <bool CAP>
+__device__ __forceinline__ AdamK adam_setup(const bmc_adam_hyper_t& h, const int* step_dev, int tid) {
+    AdamK k;
+    k.omb1 = h.one_minus_beta1; k.beta2 = h.beta2; k.omb2 = h.one_minus_beta2; k.eps = h.eps; k.wd = h.weight_decay;
+    if constexpr (CAP) {
+        __shared__ float sh[2];
+        if (tid == 0) {
+            const double t = (double)(gld<int>(step_dev) + 1);
+            sh[0] = (float)(h.lr / (1.0 - pow(h.beta1_f64, t)));
+            sh[1] = (float)sqrt(1.0 - pow(h.beta2_f64, t));
+        }
+        __syncthreads();
+        k.step_size = sh[0]; k.bc2s = sh[1];
+    } else {
+        k.step_size = h.step_size; k.bc2s = h.bias_correction2_sqrt;
+    }
+    return k;
 }
 
 }  // namespace

@@ -1,110 +1,77 @@
 // Optimizer step (bmcnet-esr_amd/bmc_hip/optim.py::Adam): torch.optim.Adam(amsgrad, weight_decay) for every parameter of a group in
-// ONE launch over a device table of chunks.  The contract -- the six roundings per element, the chunk table, the gradient-norm
-// partials, the capturable variant -- is stated once in include/bmc_hip.h "optimizer step".
+// ONE launch over a device table of chunks, and its clipped form (Adam(max_grad_norm=, nonfinite=)): a norm launch, then a step
+// launch that clips by the global gradient norm or skips a non-finite step without a host round trip.  The contract -- the six
+// roundings per element, the chunk table, the gradient-norm partials, the coefficient, the capturable variants -- is stated once in
+// include/bmc_hip.h "optimizer step" and "optimizer step: clipping".
 //
-// An HBM-bound element-wise pass: 36 bytes per element (read p, g, m, v, vmax; write p, m, v, vmax), each touched once.  A
-// workgroup of 256 lanes owns one chunk of at most 4096 elements of one tensor: a lane issues its (up to) 20 16-byte loads, then
-// computes, then stores.  The table's pointers are made wave-uniform (readfirstlane) and every access goes through the
-// address-space(1) accessors of slot_k.h: scalar base + lane offset, global_* instructions, never flat_*.  No workgroup waits for
-// another, no atomics, no scratch memory.
-#include "adam_k.h"                            // AT, VPL, AdamK, adam_elem, uniform_ptr, sq, tree_sum, adam_check
+// An HBM-bound element-wise pass: 36 bytes per element (read p, g, m, v, vmax; write p, m, v, vmax), each touched once; the norm
+// launch reads g alone (4 bytes per element).  A workgroup of 256 lanes owns one chunk of at most 4096 elements of one tensor: a
+// lane issues its (up to) 20 16-byte loads, then computes, then stores.  The table's pointers are made wave-uniform (readfirstlane)
+// and every access goes through the address-space(1) accessors of slot_k.h: scalar base + lane offset, global_* instructions, never
+// flat_*.  No workgroup waits for another, no atomics, no scratch memory.  The kernels below are shells: the walk over a chunk, the
+// element arithmetic and the set-up of the constants are in adam_k.h, once.
+#include "adam_k.h"
 
 namespace {
-
-// The whole 16-byte vectors of an aligned chunk: vector tid + j * AT is this lane's j-th.  FULL: the chunk has all 4096 elements and
-// nothing is guarded -- straight-line code, the 20 loads of a lane are issued before the first is used.
-template <bool AMS, bool NORM, bool FULL>
-__device__ __forceinline__ void vec_pass(float* p, const float* g, float* m, float* v, float* x, int nvec, int tid, const AdamK& k,
-                                         double& acc) {
-    f32x4 P[VPL], G[VPL], M[VPL], V[VPL], X[VPL];
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-        const int e = 4 * (tid + j * AT);
-        if (FULL || tid + j * AT < nvec) {
-            P[j] = gld<f32x4>(p + e); G[j] = gld<f32x4>(g + e); M[j] = gld<f32x4>(m + e); V[j] = gld<f32x4>(v + e);
-            if constexpr (AMS) X[j] = gld<f32x4>(x + e);
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < VPL; ++j) {
-        const int e = 4 * (tid + j * AT);
-        if (FULL || tid + j * AT < nvec) {
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                if constexpr (NORM) acc += sq(G[j][c]);
-                float pe = P[j][c], me = M[j][c], ve = V[j][c], xe = AMS ? X[j][c] : 0.f;
-                adam_elem<AMS>(pe, G[j][c], me, ve, xe, k);
-                P[j][c] = pe; M[j][c] = me; V[j][c] = ve;
-                if constexpr (AMS) X[j][c] = xe;
-            }
-            gst<f32x4>(p + e, P[j]); gst<f32x4>(m + e, M[j]); gst<f32x4>(v + e, V[j]);
-            if constexpr (AMS) gst<f32x4>(x + e, X[j]);
-        }
-    }
-}
 
 // grid: n_chunks workgroups.  AMS: amsgrad; NORM: partial_sq is given; CAP: the step count comes from *step_dev.
 template <bool AMS, bool NORM, bool CAP>
 __global__ __launch_bounds__(AT) void adam_kernel(const bmc_adam_chunk_t* __restrict__ table, const bmc_adam_hyper_t h,
                                                   const int* __restrict__ step_dev, double* __restrict__ partial_sq) {
     const int tid = threadIdx.x;
-    const bmc_adam_chunk_t* const ent = table + blockIdx.x;
-    float* const p = uniform_ptr<float>(&ent->p);
-    const float* const g = uniform_ptr<const float>(&ent->g);
-    float* const m = uniform_ptr<float>(&ent->m);
-    float* const v = uniform_ptr<float>(&ent->v);
-    float* const x = AMS ? uniform_ptr<float>(&ent->vmax) : nullptr;
-    int n = __builtin_amdgcn_readfirstlane(gld<int>(&ent->n));
-    n = n < BMC_ADAM_CHUNK ? n : BMC_ADAM_CHUNK;
-    const bool aligned = __builtin_amdgcn_readfirstlane(gld<int>(&ent->aligned)) != 0;
-
-    AdamK k;
-    k.omb1 = h.one_minus_beta1; k.beta2 = h.beta2; k.omb2 = h.one_minus_beta2; k.eps = h.eps; k.wd = h.weight_decay;
-    if constexpr (CAP) {
-        __shared__ float sh[2];
-        if (tid == 0) {                            // float64, once per workgroup, as the host does for the plain entry point
-            const double t = (double)(gld<int>(step_dev) + 1);
-            sh[0] = (float)(h.lr / (1.0 - pow(h.beta1_f64, t)));
-            sh[1] = (float)sqrt(1.0 - pow(h.beta2_f64, t));
-        }
-        __syncthreads();
-        k.step_size = sh[0]; k.bc2s = sh[1];
-    } else {
-        k.step_size = h.step_size; k.bc2s = h.bias_correction2_sqrt;
-    }
-
-    double acc = 0.0;                              // this lane's share of sum(g^2), added in index order
-    if (aligned) {
-        const int nvec = n >> 2;
-        if (n == BMC_ADAM_CHUNK) vec_pass<AMS, NORM, true>(p, g, m, v, x, nvec, tid, k, acc);     // all loads in flight, then the arithmetic
-        else vec_pass<AMS, NORM, false>(p, g, m, v, x, nvec, tid, k, acc);
-        const int e = 4 * nvec + tid;              // the last partial vector, one element per lane
-        if (e < n) {
-            const float ge = gld<float>(g + e);
-            float pe = gld<float>(p + e), me = gld<float>(m + e), ve = gld<float>(v + e), xe = AMS ? gld<float>(x + e) : 0.f;
-            if constexpr (NORM) acc += sq(ge);
-            adam_elem<AMS>(pe, ge, me, ve, xe, k);
-            gst<float>(p + e, pe); gst<float>(m + e, me); gst<float>(v + e, ve);
-            if constexpr (AMS) gst<float>(x + e, xe);
-        }
-    } else {
-        for (int e = tid; e < n; e += AT) {
-            const float ge = gld<float>(g + e);
-            float pe = gld<float>(p + e), me = gld<float>(m + e), ve = gld<float>(v + e), xe = AMS ? gld<float>(x + e) : 0.f;
-            if constexpr (NORM) acc += sq(ge);
-            adam_elem<AMS>(pe, ge, me, ve, xe, k);
-            gst<float>(p + e, pe); gst<float>(m + e, me); gst<float>(v + e, ve);
-            if constexpr (AMS) gst<float>(x + e, xe);
-        }
-    }
-    if constexpr (NORM) {                          // a fixed tree over the workgroup
+    const Chunk ck = chunk_view<AMS>(table + blockIdx.x);
+    const AdamK k = adam_setup<CAP>(h, step_dev, tid);
+    if constexpr (NORM) {
         __shared__ double red[AT];
+        double acc = 0.0;                          // this lane's share of sum(g^2), added in index order
+        step_chunk<AMS>(ck, tid, k, GradSumSq{acc});
         const double total = tree_sum(red, acc, tid);
         if (tid == 0) gst<double>(partial_sq + blockIdx.x, total);
+    } else {
+        step_chunk<AMS>(ck, tid, k, GradAsIs{});
     }
 }
 
-// the second launch of the capturable entry point: one lane, a plain vector store
+// the norm launch of a clipped step: the partials adam_kernel<.., NORM = true, ..> stores, from g alone
+__global__ __launch_bounds__(AT) void grad_sq_kernel(const bmc_adam_chunk_t* __restrict__ table, double* __restrict__ partial_sq) {
+    __shared__ double red[AT];
+    const int tid = threadIdx.x;
+    const double total = tree_sum(red, grad_sq_chunk(chunk_view<false>(table + blockIdx.x), tid), tid);
+    if (tid == 0) gst<double>(partial_sq + blockIdx.x, total);
+}
+
+// The step launch of a clipped step.  grid: n_chunks workgroups.  AMS: amsgrad; CAP: the step count comes from *step_dev.
+template <bool AMS, bool CAP>
+__global__ __launch_bounds__(AT) void clip_step_kernel(const bmc_adam_chunk_t* __restrict__ table, const bmc_adam_hyper_t h,
+                                                       const int* __restrict__ step_dev, const bmc_adam_clip_t clip) {
+    __shared__ double red[AT];
+    const int tid = threadIdx.x;
+    const Chunk ck = chunk_view<AMS>(table + blockIdx.x);
+
+    // the total of ALL partials of the step, the same bits in every workgroup: lane t adds partial t, t + 256, ... in that order
+    double acc = 0.0;
+    for (int i = tid; i < clip.n_partials; i += AT) acc += gld<double>(clip.partial_sq + i);
+    const double total = tree_sum(red, acc, tid);
+    const double norm = __builtin_sqrt(total);
+    const float c = clip_coeff(norm, clip.max_norm);
+    const bool skip = clip.skip_nonfinite != 0 && !__builtin_isfinite(total);      // uniform over the whole grid
+    if (blockIdx.x == 0 && tid == 0) {             // plain stores by one lane
+        if (clip.info) { gst<double>(clip.info, norm); gst<double>(clip.info + 1, (double)c); }
+        if (skip && clip.skipped) gst<int>(clip.skipped, gld<int>(clip.skipped) + 1);
+    }
+    if (skip) return;                              // nothing of p, m, v, vmax is stored
+
+    // The partials are reduced BEFORE the chunk's loads are issued: step_chunk comes last.  Issuing a full chunk's 20 loads first, so
+    // that the reduction runs under their latency, holds 80 registers across the reduction and its barriers.  On the layout this
+    // kernel had when it was a translation unit of its own (194 VGPRs, occupancy 2) that order was measured and was slower: 248
+    // VGPRs, one wave per SIMD fewer, 24.6 against 17.6 us for the BMCNet(4,128,5) set on an MI355X.  On the shared walk the kernel
+    // stands at 126-128 VGPRs with amsgrad (110-112 without), occupancy 4, and takes 16.0 us for that set; the other order has not
+    // been measured on it.
+    const AdamK k = adam_setup<CAP>(h, step_dev, tid);
+    step_chunk<AMS>(ck, tid, k, GradClipped{c});
+}
+
+// the last launch of the capturable entry points: one lane, a plain vector store (also after a skipped step)
 __global__ void adam_advance_kernel(int* __restrict__ step_dev) {
     if (threadIdx.x == 0) gst<int>(step_dev, gld<int>(step_dev) + 1);
 }
@@ -114,6 +81,42 @@ template <bool CAP>
 adam_fn adam_pick(bool ams, bool norm) {
     if (ams) return norm ? adam_kernel<true, true, CAP> : adam_kernel<true, false, CAP>;
     return norm ? adam_kernel<false, true, CAP> : adam_kernel<false, false, CAP>;
+}
+
+// ---- host: the argument checks the entry points make before they launch
+bool finite_f(float v) { return isfinite(v); }
+
+int adam_check(const char* name, const bmc_adam_chunk_t* table, int n_chunks, const bmc_adam_hyper_t& h, bool cap) {
+    BMC_CHECK_ARG(n_chunks >= 0, "%s: n_chunks = %d is negative", name, n_chunks);
+    BMC_CHECK_ARG(table || n_chunks == 0, "%s: no chunk table for %d chunks", name, n_chunks);
+    BMC_CHECK_ARG(finite_f(h.beta1) && finite_f(h.one_minus_beta1) && finite_f(h.beta2) && finite_f(h.one_minus_beta2) &&
+                      finite_f(h.eps) && finite_f(h.weight_decay),
+                  "%s: a hyper-parameter is not finite (beta1 %g, 1 - beta1 %g, beta2 %g, 1 - beta2 %g, eps %g, weight_decay %g)", name,
+                  h.beta1, h.one_minus_beta1, h.beta2, h.one_minus_beta2, h.eps, h.weight_decay);
+    if (cap)
+        BMC_CHECK_ARG(isfinite(h.lr) && isfinite(h.beta1_f64) && isfinite(h.beta2_f64),
+                      "%s: a hyper-parameter is not finite (lr %g, beta1 %g, beta2 %g)", name, h.lr, h.beta1_f64, h.beta2_f64);
+    else
+        BMC_CHECK_ARG(finite_f(h.step_size) && finite_f(h.bias_correction2_sqrt),
+                      "%s: a hyper-parameter is not finite (step_size %g, bias_correction2_sqrt %g)", name, h.step_size,
+                      h.bias_correction2_sqrt);
+    return 0;
+}
+
+int clip_check(const char* name, int n_chunks, const bmc_adam_clip_t& clip) {
+    BMC_CHECK_ARG(clip.partial_sq || n_chunks == 0, "%s: no partial_sq (the norm launches of the step write it)", name);
+    BMC_CHECK_ARG(clip.n_partials >= n_chunks, "%s: n_partials = %d is less than n_chunks = %d", name, clip.n_partials, n_chunks);
+    BMC_CHECK_ARG(clip.max_norm > 0.f, "%s: max_norm = %g is not a positive number (+INF: never clip)", name, clip.max_norm);
+    BMC_CHECK_ARG(clip.skip_nonfinite == 0 || clip.skip_nonfinite == 1, "%s: skip_nonfinite = %d is neither 0 nor 1", name,
+                  clip.skip_nonfinite);
+    return 0;
+}
+
+// the second launch of every capturable entry point
+int advance(const char* name, int* step_dev, bmc_stream_t s) {
+    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, step_dev);
+    BMC_CHECK_LAUNCH(name);
+    return 0;
 }
 
 }  // namespace
@@ -135,7 +138,38 @@ extern "C" int bmc_adam_step_capturable(const bmc_adam_chunk_t* table, int n_chu
     const adam_fn fn = adam_pick<true>(hyper.amsgrad != 0, partial_sq != nullptr);
     hipLaunchKernelGGL(fn, dim3((unsigned)n_chunks), dim3(AT), 0, (hipStream_t)s, table, hyper, (const int*)step_dev, partial_sq);
     BMC_CHECK_LAUNCH("bmc_adam_step_capturable");
-    hipLaunchKernelGGL(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)s, step_dev);
-    BMC_CHECK_LAUNCH("bmc_adam_step_capturable");
+    return advance("bmc_adam_step_capturable", step_dev, s);
+}
+
+extern "C" int bmc_adam_grad_sq(const bmc_adam_chunk_t* table, int n_chunks, double* partial_sq, bmc_stream_t s) {
+    BMC_CHECK_ARG(n_chunks >= 0, "bmc_adam_grad_sq: n_chunks = %d is negative", n_chunks);
+    BMC_CHECK_ARG(table || n_chunks == 0, "bmc_adam_grad_sq: no chunk table for %d chunks", n_chunks);
+    BMC_CHECK_ARG(partial_sq || n_chunks == 0, "bmc_adam_grad_sq: no partial_sq for %d chunks", n_chunks);
+    if (n_chunks == 0) return 0;
+    hipLaunchKernelGGL(grad_sq_kernel, dim3((unsigned)n_chunks), dim3(AT), 0, (hipStream_t)s, table, partial_sq);
+    BMC_CHECK_LAUNCH("bmc_adam_grad_sq");
     return 0;
+}
+
+extern "C" int bmc_adam_step_clipped(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, bmc_adam_clip_t clip,
+                                     bmc_stream_t s) {
+    if (adam_check("bmc_adam_step_clipped", table, n_chunks, hyper, false)) return -1;
+    if (clip_check("bmc_adam_step_clipped", n_chunks, clip)) return -1;
+    if (n_chunks == 0) return 0;
+    const auto fn = hyper.amsgrad != 0 ? clip_step_kernel<true, false> : clip_step_kernel<false, false>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_chunks), dim3(AT), 0, (hipStream_t)s, table, hyper, (const int*)nullptr, clip);
+    BMC_CHECK_LAUNCH("bmc_adam_step_clipped");
+    return 0;
+}
+
+extern "C" int bmc_adam_step_clipped_capturable(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, int* step_dev,
+                                                bmc_adam_clip_t clip, bmc_stream_t s) {
+    if (adam_check("bmc_adam_step_clipped_capturable", table, n_chunks, hyper, true)) return -1;
+    if (clip_check("bmc_adam_step_clipped_capturable", n_chunks, clip)) return -1;
+    BMC_CHECK_ARG(step_dev || n_chunks == 0, "bmc_adam_step_clipped_capturable: no step counter");
+    if (n_chunks == 0) return 0;
+    const auto fn = hyper.amsgrad != 0 ? clip_step_kernel<true, true> : clip_step_kernel<false, true>;
+    hipLaunchKernelGGL(fn, dim3((unsigned)n_chunks), dim3(AT), 0, (hipStream_t)s, table, hyper, (const int*)step_dev, clip);
+    BMC_CHECK_LAUNCH("bmc_adam_step_clipped_capturable");
+    return advance("bmc_adam_step_clipped_capturable", step_dev, s);
 }

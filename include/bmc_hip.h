@@ -807,7 +807,7 @@ int bmc_adam_step(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t 
 int bmc_adam_step_capturable(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, int* step_dev, double* partial_sq,
                              bmc_stream_t s);
 
-/* ---- optimizer step: clipping (bmcnet-esr_amd/bmc_hip/optim.py::Adam(max_grad_norm=, nonfinite=); csrc/optim_clip.hip) ----------
+/* ---- optimizer step: clipping (bmcnet-esr_amd/bmc_hip/optim.py::Adam(max_grad_norm=, nonfinite=); csrc/optim.hip) ---------------
  * Clipping by the GLOBAL L2 norm of all gradients of a step (torch.nn.utils.clip_grad_norm_ followed by Adam.step()) and the skip
  * of a step whose gradients are not finite, with no host round trip.  A clipped step of one optimizer is k NORM launches followed
  * by k STEP launches over the same k chunk tables, k being the launches of an unclipped step (one per group and step-count cohort,
@@ -826,7 +826,7 @@ int bmc_adam_step_capturable(const bmc_adam_chunk_t* table, int n_chunks, bmc_ad
  *     c    = (q > 1.0f) ? 1.0f : q      a NaN q stays NaN (torch.clamp(max=1.0))
  *     g_c  = g * c                      float32; g itself is never written
  * and the six lines of "optimizer step" run on g_c (weight decay is added AFTER clipping, as when one clips before torch's step()).
- * Both translation units compile the same element function (csrc/adam_k.h): for c == 1.0f the results are bit-identical to
+ * Both step kernels run the same walk and element function (csrc/adam_k.h): for c == 1.0f the results are bit-identical to
  * bmc_adam_step's.  max_norm = +INF never clips (c = 1 for every finite total).
  * Non-finite totals.  Squares of float32 values cannot overflow float64: the total is not finite exactly when some gradient
  * element is Inf or NaN.  skip_nonfinite == 0: the formulas decide -- an Inf total gives c = 0 (finite gradients become 0, Inf

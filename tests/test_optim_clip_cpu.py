@@ -1,22 +1,20 @@
 """The clipped optimizer step without a GPU: the float64 restatement the GPU tests measure against (tests/optim_clip_ref.py) is
 checked against torch.nn.utils.clip_grad_norm_ + torch.optim.Adam in float64; the float32 coefficient function against its
 float64 value; the layout of bmc_adam_clip_t, the exported symbols, the refusals of bmc_hip.optim.Adam(max_grad_norm=, nonfinite=)
-that need no device; and the device assembly of csrc/optim_clip.hip."""
+that need no device; and the device assembly of the clipped kernels of csrc/optim.hip."""
 import ctypes as C
 import os
-import re
 import subprocess
 
 import numpy as np
 import pytest
 import torch
 
+import optim_asm
 import optim_clip_ref as CR
 import optim_ref as R
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-CSRC = os.path.join(ROOT, "bmcnet-esr_amd", "csrc")
-HIPCC = "/opt/rocm/bin/hipcc"
+ROOT = optim_asm.ROOT
 
 
 # ------------------------------------------------------------------ the restatement
@@ -140,38 +138,13 @@ def test_clip_refusals_without_a_device():
 
 
 # ------------------------------------------------------------------ the device assembly
-@pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-def test_device_assembly_of_the_clipped_step(tmp_path):
-    """csrc/optim_clip.hip compiled as tests/test_optim_cpu.py compiles optim.hip; nothing is executed.  Every kernel: no flat_
-    memory instruction, no scratch memory.  The four step kernels keep the 16-byte loads and stores of the aligned path; the norm
-    kernel has 16-byte loads and no 16-byte store."""
-    out = str(tmp_path / "optim_clip.s")
-    r = subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-S", "--cuda-device-only",
-                        "-o", out, os.path.join(CSRC, "optim_clip.hip")], stdout=subprocess.PIPE, stderr=subprocess.STDOUT)
-    assert r.returncode == 0, r.stdout.decode()
-    kernels, cur = {}, None
-    for ln in open(out):
-        m = re.match(r"^(_Z\w+):", ln)
-        if m:
-            cur = kernels[m.group(1)] = {"flat": 0, "ld16": 0, "st16": 0}
-            continue
-        if cur is None:
-            continue
-        code = ln.split(";")[0]
-        cur["flat"] += bool(re.search(r"\bflat_(load|store|atomic)", code))
-        cur["ld16"] += "global_load_dwordx4" in code
-        cur["st16"] += "global_store_dwordx4" in code
-        m = re.match(r"^; (ScratchSize|Occupancy): (\d+)", ln)
-        if m:
-            cur[m.group(1)] = int(m.group(2))
-            if m.group(1) == "Occupancy":
-                cur = None
-    assert not any("adam_kernel" in n for n in kernels)
-    steps = {n: k for n, k in kernels.items() if "clip_step_kernel" in n}
-    norms = {n: k for n, k in kernels.items() if "grad_sq_kernel" in n}
-    assert len(steps) == 4 and len(norms) == 1 and len(kernels) == 6 and any("clip_advance_kernel" in n for n in kernels)
-    for n, k in kernels.items():
-        assert k["flat"] == 0 and k["ScratchSize"] == 0, (n, k)
+@pytest.mark.skipif(not os.path.exists(optim_asm.HIPCC), reason="hipcc not installed")
+def test_device_assembly_of_the_clipped_step():
+    """csrc/optim.hip, the file tests/test_optim_cpu.py reads and with its assertions on every kernel (tests/optim_asm.py); nothing
+    is executed.  The four clipped step kernels keep the 16-byte loads and stores of the aligned path; the norm kernel has 16-byte
+    loads and no 16-byte store."""
+    steps, norms = optim_asm.check_family("clip_step_kernel"), optim_asm.check_family("grad_sq_kernel")
+    assert len(steps) == 4 and len(norms) == 1
     for n, k in steps.items():
         assert k["ld16"] >= 4 and k["st16"] >= 3, (n, k)
     for n, k in norms.items():

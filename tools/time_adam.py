@@ -11,7 +11,7 @@ cannot keep up shows here too) and the median.  Floors for comparison: 36 bytes 
 `rocprofv3 --kernel-trace --stats -- python tools/time_adam.py --only NAME --steps N` (N = 2 and N = 7, no timing) and the
 difference of the two traces' kernel counts over 5 steps is printed: set-up kernels cancel.  No counters are collected.
 
---clip: the clipped step (csrc/optim_clip.hip, TWO launches).  Three figures per set: hip_clip, bmc_hip.optim.Adam(max_grad_norm=
+--clip: the clipped step (csrc/optim.hip as well, TWO launches).  Three figures per set: hip_clip, bmc_hip.optim.Adam(max_grad_norm=
 --clip-norm); hip, the unclipped fused step (the difference is the cost of the feature); foreach_clip, what a user has otherwise:
 torch.nn.utils.clip_grad_norm_ with its default foreach followed by torch.optim.Adam with its default.  Floor of the clipped step:
 40 bytes per element (the norm launch reads g once more) and one more launch.

@@ -13,7 +13,7 @@ python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x8
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
 --clip-norm X: clip the gradients by their global L2 norm.  hip: Adam(max_grad_norm=X), a norm launch and a step launch
-(csrc/optim_clip.hip); torch: torch.nn.utils.clip_grad_norm_ in a pre-step hook, so that the two can be compared.
+(csrc/optim.hip); torch: torch.nn.utils.clip_grad_norm_ in a pre-step hook, so that the two can be compared.
 --nonfinite skip (hip only): a step whose gradients hold an Inf or a NaN leaves parameters and state untouched.
 With either, the norm and coefficient of the last step and the number of skipped steps are printed once at the end.
 --wall: also print the wall time per step at the end (host clock, device synchronised, the first step left out).
