@@ -286,6 +286,47 @@ def render_event_counts(cnt, round=False):
     return out
 
 
+def counts_to_voxel(pred, bins, max_count=255):
+    """The voxel grids of count images: pred [B,2,sH,sW] (fp32, on the GPU) -> float32 [B,bins,sH,sW] on the GPU, grid b what
+    the reference's events_to_voxel_torch (dataloader/encodings.py:100-148, temporal bilinear) returns for the timed event
+    stream of pred[b] -- events_to_voxel_torch(xs, ys, ts, ps, bins, sensor_size=(sH, sW)) of counts_to_events(pred[b:b+1],
+    max_count, times="linear")'s columns as float32 --, bit for bit, without building the stream: per output pixel a closed form
+    of its two counts (bmc_slot_voxel on a temporary slot table: two launches, no sort, no atomics; include/bmc_hip.h "voxel
+    grids" states the contract).  The grid's rows are the sensor's y: vertically flipped against pred's rows, as the emitted ys
+    are.  An image of 3 events or fewer gives zeros.  1 <= bins <= 32, 1 <= max_count <= 255."""
+    import numpy as np
+    from . import slots
+    if not (torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.dtype == torch.float32):
+        raise ValueError("counts_to_voxel: pred must be an fp32 [B,2,sH,sW] tensor")
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not 1 <= bins <= slots.MAX_VOXEL_BINS:
+        raise ValueError("counts_to_voxel: bins must be an integer, 1 <= bins <= %d (got %r)" % (slots.MAX_VOXEL_BINS, bins))
+    if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= slots.MAX_COUNT_TIMED:
+        raise ValueError("counts_to_voxel: max_count must be an integer, 1 <= max_count <= %d (the timed stream's limit; got %r)"
+                         % (slots.MAX_COUNT_TIMED, max_count))
+    B, _, sH, sW = pred.shape
+    if not (1 <= sH <= slots.MAX_COUNT_LIMIT and 1 <= sW <= slots.MAX_COUNT_LIMIT):
+        raise ValueError("counts_to_voxel: images of 1 .. %d pixels a side (got %d x %d)" % (slots.MAX_COUNT_LIMIT, sH, sW))
+    if not pred.is_cuda:
+        raise RuntimeError("counts_to_voxel: pred must live on the MI355X (no CPU fallback in this build)")
+    pred = pred.contiguous()
+    bins = int(bins)
+    out = torch.empty(B, bins, sH, sW, dtype=torch.float32, device=pred.device)
+    nparts = slots.voxel_parts(sH, sW)
+    parts = torch.zeros(2 * min(max(B, 1), slots.MAX_SLOTS) * nparts, dtype=torch.int32, device=pred.device)
+    tables = {}
+    for a in range(0, B, slots.MAX_SLOTS):
+        n = min(slots.MAX_SLOTS, B - a)
+        t = tables[n] = tables.get(n) or slots.SlotTable(n, pred.device, voxel=True)
+        e = t.host()
+        vx = t.voxel_host()
+        for s in range(n):
+            e[s]["frames"], e[s]["flags"] = pred[a + s].data_ptr(), slots.ACTIVE
+            vx[s]["dst"] = out[a + s].data_ptr()
+        t.upload()
+        slots.voxel(t, pred[a:a + n], max_count, bins, nparts, parts)
+    return out
+
+
 def counts_to_events(pred, max_count=255, times=None, spans=None):
     """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
     (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in

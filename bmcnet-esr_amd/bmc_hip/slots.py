@@ -29,7 +29,12 @@ HOT_LAUNCHES), encode_filtered() is encode() storing the LR frames through those
 
 Event-count images (csrc/slot_render.hip; include/bmc_hip.h "event-count images" states the contract): SlotTable(render=K) adds K
 tables of bmc_slot_render_t entries (SLOT_RENDER_DTYPE: a count image and where its picture goes) behind the others, one per kind
-of image; render() draws table k's images for all slots (one call = RENDER_KERNELS launches, counted in RENDER_LAUNCHES)."""
+of image; render() draws table k's images for all slots (one call = RENDER_KERNELS launches, counted in RENDER_LAUNCHES).
+
+Voxel grids (csrc/slot_voxel.hip; include/bmc_hip.h "voxel grids" states the contract): SlotTable(voxel=True) adds a table of
+bmc_slot_voxel_t entries (SLOT_VOXEL_DTYPE: where the slot's grid goes) behind the others; voxel() turns the predictions of every
+slot with a voxel entry into the temporal-bilinear voxel grid of its timed event stream, per pixel (one call = VOXEL_KERNELS
+launches, counted in VOXEL_LAUNCHES)."""
 import numpy as np
 import torch
 
@@ -78,12 +83,18 @@ RENDER_KERNELS = 2                 # launches of one bmc_slot_render call: selec
 MAX_RENDER_PIXELS = 1 << 24        # BMC_SLOT_RENDER_MAX_PIXELS: h * w - 1 is exact in float32
 MAX_RENDER_PARTS = 1024
 MAX_RENDER_TABLES = 8
+SLOT_VOXEL_DTYPE = np.dtype([("dst", "<u8")])                                                                   # bmc_slot_voxel_t
+assert SLOT_VOXEL_DTYPE.itemsize == 8
+VOXEL_LAUNCHES = 0
+VOXEL_KERNELS = 2                  # launches of one bmc_slot_voxel call: reduce, voxel
+MAX_VOXEL_BINS = 32                # BMC_SLOT_VOXEL_MAX_BINS
 
 
-def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0):
+def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False):
     """The sections of a slot table of S slots -> ([(name, dtype, byte offset), ...] in their order in memory, total bytes):
     "slot" (bmc_slot_t) always, then "events", "emit" (bmc_slot_emit_timed_t entries with timed=True), "clock" (needs timed) and
-    "hot" (needs events), each S entries behind the one before, and "render" (render tables of S entries each)."""
+    "hot" (needs events), each S entries behind the one before, "render" (render tables of S entries each) and "voxel"
+    (voxel=True or False: S bmc_slot_voxel_t entries)."""
     if timed and not emit:
         raise ValueError("slots: timed=True needs emit=True")
     if clock and not timed:
@@ -92,11 +103,13 @@ def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=Fals
         raise ValueError("slots: hot=True needs events=True")
     if isinstance(render, bool) or not isinstance(render, int) or not 0 <= render <= MAX_RENDER_TABLES:
         raise ValueError("slots: render must be a number of tables, 0 .. %d (got %r)" % (MAX_RENDER_TABLES, render))
+    if not isinstance(voxel, (bool, np.bool_)):
+        raise ValueError("slots: voxel must be True or False (got %r)" % (voxel,))
     sections, nbytes = [], 0
     for name, dtype, count in (("slot", SLOT_DTYPE, 1), ("events", SLOT_EVENTS_DTYPE, int(bool(events))),
                                ("emit", SLOT_EMIT_TIMED_DTYPE if timed else SLOT_EMIT_DTYPE, int(bool(emit))),
                                ("clock", SLOT_CLOCK_DTYPE, int(bool(clock))), ("hot", SLOT_HOT_DTYPE, int(bool(hot))),
-                               ("render", SLOT_RENDER_DTYPE, render)):
+                               ("render", SLOT_RENDER_DTYPE, render), ("voxel", SLOT_VOXEL_DTYPE, int(voxel))):
         if count:
             sections.append((name, dtype, nbytes))
             nbytes += count * S * dtype.itemsize
@@ -110,17 +123,18 @@ class SlotTable:
     The other sections of table_layout() share the tensor and the copy: `events_host()` / `events_ptr()` (events=True),
     `emit_host()` / `emit_ptr()` (emit=True; timed=True: bmc_slot_emit_timed_t entries), `clock_host()` / `clock_ptr()`
     (clock=True, needs timed), `hot_host()` / `hot_ptr()` (hot=True, needs events), `render_host()` [K,S] / `render_ptr(k)`
-    (render=K tables).  The *_host() views are those of the window being filled, after host(), which cleared them."""
+    (render=K tables), `voxel_host()` / `voxel_ptr()` (voxel=True).  The *_host() views are those of the window being filled, after host(), which cleared them."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False, render=0):
+    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
         self.events, self.emit, self.timed, self.clock, self.hot = bool(events), bool(emit), bool(timed), bool(clock), bool(hot)
         self.render = render
-        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render)
+        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render, voxel)
+        self.voxel = bool(voxel)
         self._at = {name: (dtype, off) for name, dtype, off in sections}
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
@@ -157,6 +171,9 @@ class SlotTable:
         dtype, off = self._at["render"]
         return self._pinned[self._k].numpy()[off:off + self.render * self.S * dtype.itemsize].view(dtype).reshape(self.render, self.S)
 
+    def voxel_host(self):
+        return self._host("voxel")
+
     def upload(self):
         k = self._k
         self.dev.copy_(self._pinned[k], non_blocking=True)
@@ -183,6 +200,10 @@ class SlotTable:
         if not 0 <= k < self.render:
             raise ValueError("slots: the table has %d render tables (got %r)" % (self.render, k))
         return self._ptr("render") + k * self.S * SLOT_RENDER_DTYPE.itemsize
+
+
+    def voxel_ptr(self):
+        return self._ptr("voxel")
 
 
 def _check(cond, what):
@@ -418,6 +439,34 @@ def emit(table, pred, max_count, nparts, parts):
     lib.call(lib._slot_emit, "bmc_slot_emit", table.ptr(), table.emit_ptr(), S, pred.data_ptr(), sH, sW, max_count, nparts,
              parts.data_ptr(), _stream())
     EMIT_LAUNCHES += 1
+
+
+def voxel_parts(sH, sW):
+    """Workgroups per slot of both bmc_slot_voxel launches for a [2,sH,sW] prediction (chunks of about 4 096 elements in the
+    reduce launch and 2 048 pixels in the voxel launch, at most 1 024 parts: 338 at 720x960)."""
+    return max(1, min(MAX_EMIT_PARTS, -(-2 * sH * sW // 4096)))
+
+
+def voxel(table, pred, max_count, bins, nparts, parts):
+    """Every active slot whose voxel entry has a dst: dst (float32 [bins,sH,sW]) <- the temporal-bilinear voxel grid the
+    reference's events_to_voxel_torch gives for the timed event stream of pred[s] ([2,sH,sW]; q = min(rint(v), max_count) for
+    v > 0, else 0), computed per pixel from its two counts -- include/bmc_hip.h "voxel grids" states the contract; the grid's
+    rows are the sensor's y, flipped against the prediction's.  Two launches for all slots (bmc_slot_voxel), no atomics,
+    deterministic; other slots are not touched.  parts: int32 scratch of at least 2 * S * nparts words."""
+    global VOXEL_LAUNCHES
+    _check(table.voxel, "the slot table has no voxel entries (SlotTable(voxel=True))")
+    _check(not isinstance(max_count, bool) and isinstance(max_count, int) and 1 <= max_count <= MAX_COUNT_TIMED,
+           "voxel grids need 1 <= max_count <= %d (got %r)" % (MAX_COUNT_TIMED, max_count))
+    _check(not isinstance(bins, bool) and isinstance(bins, (int, np.integer)) and 1 <= bins <= MAX_VOXEL_BINS,
+           "1 <= bins <= %d (got %r)" % (MAX_VOXEL_BINS, bins))
+    _check(not isinstance(nparts, bool) and isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS,
+           "1 <= nparts <= %d (voxel)" % MAX_EMIT_PARTS)
+    _check(torch.is_tensor(parts) and parts.numel() >= 2 * table.S * nparts,
+           "parts must be a contiguous int32 GPU tensor of at least 2 * S * nparts words")
+    S, sH, sW = _check_emit_args(table, pred, max_count, nparts, parts)
+    lib.call(lib._slot_voxel, "bmc_slot_voxel", table.ptr(), table.voxel_ptr(), S, pred.data_ptr(), sH, sW, max_count, int(bins),
+             nparts, parts.data_ptr(), _stream())
+    VOXEL_LAUNCHES += 1
 
 
 def emit_rank_table_np():

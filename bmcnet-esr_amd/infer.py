@@ -292,15 +292,28 @@ class MultiStreamSR:
     size where that differs (bmc_bicubic_resize_fwd, as the metric does) and rounded half-to-even; bicubic: frame 1 resized to
     the ground truth's size; gt: the window's ground truth.  A recording without ground truth gets lr and esr (at the
     prediction's size) only.  results() then carries images = {kind: uint8 [done,h,w,3]} on the GPU: 3 bytes per pixel and
-    window instead of the 8 of keep_predictions.  None (the default): no image, no launch."""
+    window instead of the 8 of keep_predictions.  None (the default): no image, no launch.
 
+    voxel_bins=B (1 <= B <= 32; needs max_count <= 255): every window's prediction also leaves as the temporal-bilinear VOXEL
+    GRID of its super-resolved events, the input form of reconstruction, flow and recognition networks: what the reference's
+    events_to_voxel_torch (dataloader/encodings.py:100-148) returns for the window's timed event stream (the stream of
+    event_times="linear"), bit for bit, computed per output pixel from the prediction's two counts and one small reduction
+    (bmc_slot_voxel: two more launches per window for all slots, inside the captured graph too; no sort, no atomics, no event
+    storage; include/bmc_hip.h "voxel grids" states the contract).  Independent of emit_events, event_times and render, for
+    frame-backed and event-backed recordings, with or without ground truth.  results() then carries voxels = float32
+    [done,B,sH,sW] on the GPU, at the prediction's own size; its rows are the sensor's y, vertically flipped against the
+    prediction's rows as the emitted ys are.  The grid is window-normalised, so a sensor clock does not change it.  Resident:
+    4 x B x sH x sW bytes per window -- 13.8 MB per window at 720x960 with 5 bins.  None (the default): no grid, no launch, no
+    table section."""
+
+    MAX_VOXEL_BINS = 32          # BMC_SLOT_VOXEL_MAX_BINS
     RENDER_KINDS = ("lr", "bicubic", "esr", "gt")
     MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
     MAX_COUNT_TIMED = 255        # event_times: the sort key is a 16-bit rank of j / (n - 1), n <= 255
     MAX_WINDOW_CAPACITY = 1 << 28
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
-                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None):
+                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None, voxel_bins=None):
         from bmc_hip.slots import check_hot_filter
         self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)
         self.render = self.check_render("MultiStreamSR: ", render)
@@ -317,6 +330,15 @@ class MultiStreamSR:
             raise ValueError("MultiStreamSR: event_times needs emit_events=True")
         if event_times is not None and max_count > self.MAX_COUNT_TIMED:
             raise ValueError("MultiStreamSR: event_times needs max_count <= %d (got %d)" % (self.MAX_COUNT_TIMED, max_count))
+        if voxel_bins is not None:
+            if isinstance(voxel_bins, bool) or not isinstance(voxel_bins, (int, np.integer)) or not 1 <= voxel_bins <= self.MAX_VOXEL_BINS:
+                raise ValueError("MultiStreamSR: voxel_bins must be None or an integer, 1 <= voxel_bins <= %d (got %r)"
+                                 % (self.MAX_VOXEL_BINS, voxel_bins))
+            if max_count > self.MAX_COUNT_TIMED:
+                raise ValueError("MultiStreamSR: voxel_bins needs max_count <= %d (the timed stream's limit; got %d)"
+                                 % (self.MAX_COUNT_TIMED, max_count))
+            voxel_bins = int(voxel_bins)
+        self.voxel_bins = voxel_bins
         self.event_times = event_times
         self._wcap = 0             # events per window the sort scratch holds (the largest window_event_capacity so far)
         self.model = model.eval()
@@ -445,6 +467,7 @@ class MultiStreamSR:
             if self._size is None:                         # once per session: workgroups per slot of the emit launches
                 from bmc_hip import slots
                 self._nparts = slots.emit_parts(self.scale * H, self.scale * W)
+                self._vparts = slots.voxel_parts(self.scale * H, self.scale * W)
             self._size = size
             if len(size) == 4:                             # a running session without ground truth: the metrics launch joins
                 self._grow(self._gt_scratch, self._render_buffers)
@@ -473,6 +496,11 @@ class MultiStreamSR:
                 raise ValueError("MultiStreamSR: images of more than 2^24 pixels cannot be rendered (sizes %s)" % (self._size,))
             rec["images"] = {k: torch.empty((nwin,) + self._render_size(k, has_gt) + (3,), dtype=torch.uint8, device=device)
                              for k in self.render if has_gt or k in ("lr", "esr")}
+        if self.voxel_bins is not None:                    # the recording's voxel grids, at the prediction's size
+            if max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
+                raise ValueError("MultiStreamSR: predictions of %d x %d are too large for voxel grids (at most %d a side)"
+                                 % (self.scale * H, self.scale * W, self.MAX_COUNT_LIMIT))
+            rec["voxels"] = torch.empty(nwin, self.voxel_bins, self.scale * H, self.scale * W, device=device)
         if self.emit_events:                               # the recording's output stream: three columns and the index table
             cap = max(int(event_capacity), 1)
             rec.update(ev_capacity=cap, ev_xs=torch.empty(cap, dtype=torch.int16, device=device),
@@ -596,7 +624,7 @@ class MultiStreamSR:
 
     def resident_bytes(self, handle):
         """Bytes the recording keeps on the GPU: its columns (event-backed) or frames, its result sums, kept predictions and
-        (emit_events) its output columns with their index."""
+        (emit_events) its output columns with their index, (voxel_bins=B) its voxel grids: 4 * B * sH * sW bytes per window."""
         r = self._recs[handle]
         data = r["lr"] + r.get("gt", ()) if "lr" in r else (r["frames"],) + ((r["gts"],) if "gts" in r else ())
         if "ev_xs" in r:
@@ -605,13 +633,16 @@ class MultiStreamSR:
         if "hot_pixels" in r:                              # (hot_filter) the per-window mask counts and the last mask
             data = data + (r["hot_pixels"], r["hot_mask"])
         data = data + tuple(r.get("images", {}).values())  # (render) the pictures
+        if "voxels" in r:
+            data = data + (r["voxels"],)
         return sum(t.numel() * t.element_size() for t in data)
 
     def scratch_bytes(self):
         """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened; with
         hot_filter also the slots' counts, mask rings and workspace: 8 + seqn bytes per pixel) and, with event_times, of the
         sort scratch (0 until a recording has been opened); with render, the percentiles and, once a recording with ground truth
-        has been opened, the resize scratch [S,2,gh,gw] that bicubic and a resized esr share and the frames [S,2,H,W] it reads."""
+        has been opened, the resize scratch [S,2,gh,gw] that bicubic and a resized esr share and the frames [S,2,H,W] it reads;
+        with voxel_bins, the partials of the reduce launch (8 bytes per part and slot)."""
         nbytes = 0
         if self.render and self._size is not None:
             nbytes += 4 * 4 * self.S
@@ -620,6 +651,8 @@ class MultiStreamSR:
         if self._wcap:
             from bmc_hip import slots
             nbytes = slots.emit_timed_scratch_bytes(self.S, self._nparts, self._wcap)
+        if self.voxel_bins is not None and self._size is not None:
+            nbytes += 4 * 2 * self.S * self._vparts
         if not self._has_events:
             return nbytes
         H, W = self._size[:2]
@@ -636,7 +669,8 @@ class MultiStreamSR:
     def results(self, handle):
         """-> dict(esr_mse=[...], bicubic_mse=[...] (a recording with ground truth only), time=[...] per window done so far[,
         hot_pixels=[...] per window, hot_mask=[H,W] uint8 on the GPU (hot_filter, event-backed recordings)][,
-        predictions=[n,2,sH,sW]][, images={kind: uint8 [n,h,w,3] on the GPU} (render)][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
+        predictions=[n,2,sH,sW]][, images={kind: uint8 [n,h,w,3] on the GPU} (render)][, voxels=[n,B,sH,sW] float32 on the GPU
+        (voxel_bins=B)][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
         sr_ts on the GPU, parallel to sr_events (event_times): float32 inside each window, or float64 on the sensor's clock for
         a recording opened with spans / lr_ts]).  Raises RuntimeError when the windows emitted more events than the recording's
         event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity
@@ -657,6 +691,8 @@ class MultiStreamSR:
             out.update(hot_pixels=r["hot_pixels"][:done].tolist(), hot_mask=r["hot_mask"])
         if self.render:
             out["images"] = {k: t[:done] for k, t in r["images"].items()}
+        if self.voxel_bins is not None:
+            out["voxels"] = r["voxels"][:done]
         if self.emit_events:
             index = r["ev_index"][:done + 1].cpu()
             total = int(index[done])
@@ -690,6 +726,8 @@ class MultiStreamSR:
             if self._has_events:
                 self._event_buffers(b, device)
             self._render_buffers(b, device)
+            if self.voxel_bins is not None:
+                b["voxel_parts"] = torch.zeros(2 * S * self._vparts, dtype=torch.int32, device=device)
             if self.state_dtype is None:
                 b["pool"] = b["feat"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device)       # the model reads the pool
             else:
@@ -704,7 +742,8 @@ class MultiStreamSR:
         b["table"] = slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
                                      timed=self.event_times is not None, clock=self._has_clock,
                                      hot=self._has_events and self.hot_filter is not None,
-                                     render=len(self.RENDER_TABLES) if self.render else 0)
+                                     render=len(self.RENDER_TABLES) if self.render else 0,
+                                     voxel=self.voxel_bins is not None)
 
     def _render_resizes(self):
         """Does a session with ground truth resize for its pictures (bicubic always, esr when the sizes differ)?"""
@@ -749,7 +788,8 @@ class MultiStreamSR:
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """[[hot_update ->] encode ->] stage -> model -> commit [-> metrics] [-> emit] [-> render] (what a graph replay runs)."""
+        """[[hot_update ->] encode ->] stage -> model -> commit [-> metrics] [-> emit] [-> render] [-> voxel] (what a graph replay
+        runs)."""
         from bmc_hip import slots
         b = self._bufs
         H, W = self._size[:2]
@@ -772,6 +812,8 @@ class MultiStreamSR:
             slots.emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"])
         if self.render:
             self._render_window(out[-1].contiguous())
+        if self.voxel_bins is not None:
+            slots.voxel(b["table"], out[-1].contiguous(), self.max_count, self.voxel_bins, self._vparts, b["voxel_parts"])
 
     def _render_window(self, pred):
         """The render launches of a window, one pair per table in use: the slots' entries say which of them a slot takes part in.
@@ -887,6 +929,7 @@ class MultiStreamSR:
         em = t.emit_host() if self.emit_events else None
         ck = t.clock_host() if t.clock else None
         ht = t.hot_host() if t.hot else None
+        vx = t.voxel_host() if t.voxel else None
         for s, p in enumerate(plan):
             if p is None:
                 continue
@@ -904,6 +947,8 @@ class MultiStreamSR:
                 self._fill_emit(em[s], ck[s] if "spans" in r else None, r, i)
             if self.render:
                 self._fill_render(t.render_host(), e[s], s, r, i)
+            if vx is not None:
+                vx[s]["dst"] = r["voxels"][i].data_ptr()
             r["steps"].append(len(self._steps))
 
     @torch.no_grad()
@@ -940,7 +985,7 @@ class MultiStreamSR:
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
-                        window_event_capacity=None, hot_filter=None, render=None):
+                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
@@ -957,11 +1002,12 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                                          window in time order (window_event_capacity: per recording, None = the default)]).
       images      = {name: {kind: uint8 [n_windows,h,w,3]}}  with render: the event-count images of every recording]).
     hot_filter: MultiStreamSR's option (the EventRecording items are filtered, frame pairs are not).  render: MultiStreamSR's
-    option (a tuple of kinds from "lr", "bicubic", "esr", "gt")."""
+    option (a tuple of kinds from "lr", "bicubic", "esr", "gt").  voxel_bins=B: MultiStreamSR's option; the result then carries
+    voxels = {name: float32 [n_windows,B,sH,sW]}."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
-                       hot_filter=hot_filter, render=render)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
@@ -976,7 +1022,7 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
     breakdown = {k: {} for k in ("esr_mse", "bicubic_mse", "time", "params")}
-    preds, streams, times, images = {}, {}, {}, {}
+    preds, streams, times, images, voxels = {}, {}, {}, {}, {}
     for name, h in handles:
         r = ms.results(h)
         for k in ("esr_mse", "bicubic_mse", "time"):
@@ -991,6 +1037,8 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
             times[name] = r["sr_ts"]
         if ms.render:
             images[name] = r["images"]
+        if ms.voxel_bins is not None:
+            voxels[name] = r["voxels"]
     out = {"results": breakdown, "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}}
     if keep_predictions:
         out["predictions"] = preds
@@ -1000,4 +1048,6 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
         out["sr_ts"] = times
     if ms.render:
         out["images"] = images
+    if ms.voxel_bins is not None:
+        out["voxels"] = voxels
     return out

@@ -760,6 +760,46 @@ typedef struct bmc_slot_render {
 int bmc_slot_render(const bmc_slot_t* table, const bmc_slot_render_t* render, int S, int h, int w, int round, int nparts,
                     float* scratch, bmc_stream_t s);
 
+/* ---- voxel grids of the slots' predictions (MultiStreamSR(voxel_bins=B)) ---------------------------------------------------
+ * The temporal-bilinear voxel grid of a window's super-resolved events, as the reference's events_to_voxel_torch
+ * (dataloader/encodings.py:100-148, temporal_bilinear=True) computes it -- per output pixel, without building the event stream.
+ * THE CONTRACT.  Input: a slot's prediction P [2][sH][sW] (float32), bins, max_count (1 <= max_count <= 255).  With q as
+ * bmc_slot_emit defines it (q = min(rint(v), max_count) for v > 0, else 0; NaN gives 0), out [bins][sH][sW] (float32) equals, bit
+ * for bit, what events_to_voxel_torch(xs, ys, ts, ps, bins, sensor_size=(sH, sW)) returns for the window's TIMED stream: the
+ * columns of bmc_slot_emit_timed for the same P and max_count as float32 (xs = x, ys = sH-1-row, ps = +1 for channel 0 and -1
+ * for channel 1, ts the times).
+ *   1. Empty.  N = the sum of q.  N <= 3: out is all zeros (the reference's len(ts) <= 3; its ts.sum() == 0 cannot occur, every
+ *      time is at least 0.01).
+ *   2. Window.  Otherwise t_first = float32(0.01) (the stream's first event has j = 0); t_last = float32(1.0) if any q >= 2, else
+ *      float32(0.01) (the stream's last event); dt = (t_last - t_first) + 1e-6f; bm1 = float(bins - 1).
+ *   3. Events of a pixel.  Output pixel (y, x) reads row = sH-1-y of the prediction: its events are those of q0 = q[0][row][x]
+ *      with p = +1 and of q1 = q[1][row][x] with p = -1; event j of n has the timed output's float32 time, (float)(T0 + (T1 - T0)
+ *      * j / (n - 1)) evaluated in float64 and rounded once, (float)T0 for n = 1.
+ *   4. Order.  The two runs are merged by the EXACT rational j / (n - 1) (0 for n = 1), compared by integer cross-multiplication;
+ *      on equal rationals channel 0 comes first -- the order of the timed stream restricted to the pixel.
+ *   5. Accumulation.  For every event in that order and every bin b:  tn = ((t - t_first) / dt) * bm1;  w = fmaxf(0, 1 -
+ *      fabsf(tn - b));  acc_b = acc_b + p * w -- every operation a float32 operation rounded on its own (no fused multiply-add,
+ *      IEEE division), the order of the reference's index_put_(accumulate=True).  out[b][y][x] = acc_b.
+ *   ROWS.  out's rows are the SENSOR'S y: they are vertically flipped against the prediction's rows (out[b][y][x] comes from
+ *   P[c][sH-1-y][x]), exactly as the reference's function gives for the emitted ys.
+ *   The grid is window-normalised: the reference subtracts ts[0] and divides by the span, so a sensor clock does not change it.
+ *   Determinism.  No atomics, no workgroup waits for another, the partials are folded in part order by every workgroup: the
+ *   same bytes run after run, eager or replayed from a graph; a slot's grid does not depend on its neighbours.
+ *   Limits: 1 <= bins <= BMC_SLOT_VOXEL_MAX_BINS = 32; max_count <= 255 (the timed output's limit: the times are defined for
+ *   n <= 255); sH, sW <= 32767; 1 <= nparts <= BMC_SLOT_EMIT_MAX_PARTS and chunk * max_count < 2^32 as for bmc_slot_emit.
+ * A DEVICE table of S entries, parallel to the slot table.  A slot takes part when it is active, has a prediction (frames) and
+ * its entry has a dst; nothing of any other slot is read or written. */
+#define BMC_SLOT_VOXEL_MAX_BINS 32
+typedef struct bmc_slot_voxel {
+    float* dst;                 /* NULL, or the grid [bins][sH][sW] */
+} bmc_slot_voxel_t;
+/* TWO launches for all slots (csrc/slot_voxel.hip), no memset.  reduce, grid (nparts, S): part p sums q and takes the largest q
+ * over elements [p*chunk, (p+1)*chunk) of the slot (chunk as bmc_slot_emit) -> parts[s][0][p], parts[s][1][p].  voxel, grid
+ * (nparts, S): every workgroup folds its slot's partials, then owns output pixels [p*pchunk, (p+1)*pchunk), pchunk =
+ * ceil(sH*sW / nparts): two loads and `bins` stores per pixel, coalesced along x.  parts: 2 * S * nparts words of scratch. */
+int bmc_slot_voxel(const bmc_slot_t* table, const bmc_slot_voxel_t* voxel, int S, const float* pred, int sH, int sW, int max_count,
+                   int bins, int nparts, unsigned* parts, bmc_stream_t s);
+
 /* ---- optimizer step (bmcnet-esr_amd/bmc_hip/optim.py::Adam) ----------------------------------------------------------------
  * torch.optim.Adam(amsgrad, weight_decay) as train.py:653 builds it and train.py:237 steps it, for ALL parameters of a group in
  * ONE launch over a DEVICE table of chunks.  A chunk is at most BMC_ADAM_CHUNK = 4096 consecutive elements of ONE tensor (a tensor

@@ -22,13 +22,17 @@ last table).
 session's last table), and writes the images of the first such session as DIR/<recording>/event_img/<kind dir>/%09d.png with the
 reference's directory names (lr_event_img, hr_bicubic_event_img, hr_esr_event_img, hr_gt_event_img).  A file holds the rendered
 array itself, one pixel per element; the reference's files are the same array resampled by matplotlib at 300 dpi.
+--voxel-bins B adds, per configuration, the frame-backed session with the per-window voxel grids on (voxel_bins=B) and off, --runs
+alternating runs each in this process (windows/s: the median, and every run), the bmc_slot_voxel call alone (both kernels, events
+around 20 calls on the session's last table and prediction) and, for the same predictions, the composition it replaces: the timed
+event stream of every slot (counts_to_events(times="linear")) and events_to_voxel_torch on its columns, slot by slot.
 --resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
                                   [--hot-filter] [--runs 3]
                                   [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
-                                  [--render DIR] [--render-kinds lr,bicubic,esr,gt]"""
+                                  [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]"""
 import argparse
 import json
 import os
@@ -122,6 +126,37 @@ def emit_alone(ms, reps=20):
     return a.elapsed_time(z) / reps
 
 
+def voxel_alone(ms, reps=20):
+    """(ms per bmc_slot_voxel call (reduce + voxel kernel), ms of the composition it replaces) on the session's buffers: the
+    table and prediction of its last window.  The repeated calls rewrite the same grids.  The composition: the timed stream of
+    all slots' predictions (counts_to_events), then events_to_voxel_torch on every slot's columns as float32; timed once, after
+    one untimed pass, with host timers around a device synchronise (it allocates and reads an index back)."""
+    from bmc_hip import encodings, slots
+    b = ms._bufs
+    args = (b["table"], b["pred"], ms.max_count, ms.voxel_bins, ms._vparts, b["voxel_parts"])
+    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    slots.voxel(*args)
+    a.record()
+    for _ in range(reps):
+        slots.voxel(*args)
+    z.record()
+    z.synchronize()
+    sH, sW = b["pred"].shape[2:]
+
+    def composition():
+        xs, ys, ps, ts, index = encodings.counts_to_events(b["pred"], ms.max_count, times="linear")
+        for k in range(len(index) - 1):
+            lo, hi = int(index[k]), int(index[k + 1])
+            encodings.events_to_voxel_torch(xs[lo:hi].float(), ys[lo:hi].float(), ts[lo:hi].contiguous(), ps[lo:hi].float(),
+                                            ms.voxel_bins, sensor_size=(sH, sW))
+        torch.cuda.synchronize()
+
+    composition()
+    t0 = time.perf_counter()
+    composition()
+    return a.elapsed_time(z) / reps, 1e3 * (time.perf_counter() - t0)
+
+
 RENDER_DIRS = {"lr": "lr_event_img", "bicubic": "hr_bicubic_event_img", "esr": "hr_esr_event_img", "gt": "hr_gt_event_img"}
 
 
@@ -172,9 +207,9 @@ def sensor_spans(L, k):
 
 
 def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False,
-                hot_filter=None, render=None, render_dir=None):
+                hot_filter=None, render=None, render_dir=None, voxel_bins=None):
     ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times,
-                       hot_filter=hot_filter, render=render)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
@@ -200,6 +235,8 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
             for k, h in enumerate(hs):
                 write_images(render_dir, "rec%03d" % k, ms.results(h)["images"])
         return lat, S * windows / wall, render_alone(ms), ms.resident_bytes(hs[0])
+    if voxel_bins is not None:
+        return (lat, S * windows / wall) + voxel_alone(ms) + (ms.resident_bytes(hs[0]),)
     if hot_filter is not None:
         return lat, S * windows / wall, hot_update_alone(ms), ms.resident_bytes(hs[0])
     if events:
@@ -216,7 +253,7 @@ def parse_args(argv=None):
     ap.add_argument("--events", action="store_true")
     ap.add_argument("--hot-filter", action="store_true",
                     help="implies --events: the event-backed session with the hot-pixel filter on and off, alternating runs")
-    ap.add_argument("--runs", type=int, default=3, help="with --hot-filter: alternating runs of each")
+    ap.add_argument("--runs", type=int, default=3, help="with --hot-filter / --voxel-bins: alternating runs of each")
     ap.add_argument("--emit-events", action="store_true")
     ap.add_argument("--event-times", action="store_true",
                     help="with --emit-events: the timed, time-ordered stream (MultiStreamSR(event_times='linear'))")
@@ -232,7 +269,11 @@ def parse_args(argv=None):
                          "matplotlib at 300 dpi)")
     ap.add_argument("--render-kinds", default=None,
                     help="with --render: the kinds, a comma-separated choice of lr,bicubic,esr,gt (default: all four)")
+    ap.add_argument("--voxel-bins", type=int, default=None, metavar="B",
+                    help="adds the session with the per-window voxel grids on (voxel_bins=B, 1 .. 32) and off, alternating runs")
     a = ap.parse_args(argv)
+    if a.voxel_bins is not None and not 1 <= a.voxel_bins <= MultiStreamSR.MAX_VOXEL_BINS:
+        ap.error("--voxel-bins: 1 <= B <= %d" % MultiStreamSR.MAX_VOXEL_BINS)
     if a.render_kinds is not None and a.render is None:
         ap.error("--render-kinds needs --render DIR")
     if a.render is not None:
@@ -315,6 +356,20 @@ def main():
                                      ms_per_window=round(lat, 3), windows_per_s=round(wps, 1),
                                      render_ms={k: round(v, 4) for k, v in alone.items()},
                                      render_share=round(sum(alone.values()) / lat, 4), resident_bytes=nbytes))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.voxel_bins is not None:
+                    off, on = [], []
+                    for _ in range(a.runs):
+                        off.append(multistream(m, recs, S, graph, a.warmup, a.windows))
+                        on.append(multistream(m, recs, S, graph, a.warmup, a.windows, voxel_bins=a.voxel_bins))
+                    lat, vox = statistics.median(r[0] for r in on), statistics.median(r[2] for r in on)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(voxel)", slots=S, voxel_bins=a.voxel_bins,
+                                     ms_per_window=round(lat, 3), windows_per_s=round(statistics.median(r[1] for r in on), 1),
+                                     windows_per_s_voxel_off=round(statistics.median(r[1] for r in off), 1),
+                                     windows_per_s_runs=[round(r[1], 1) for r in on],
+                                     windows_per_s_voxel_off_runs=[round(r[1], 1) for r in off],
+                                     voxel_alone_ms=round(vox, 4), voxel_share=round(vox / lat, 4),
+                                     composition_ms=round(statistics.median(r[3] for r in on), 3), resident_bytes=on[-1][4]))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.no_gt:
                     lat, wps, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, no_gt=True)
