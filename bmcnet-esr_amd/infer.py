@@ -8,10 +8,16 @@ reference's evaluation mode 1 on top of it.  A recording is handed over as count
 columns with the index tables of its blocks (open_events, EventRecording), encoded window by window on the GPU.  With
 emit_events the result leaves the same way: the super-resolved event stream of every window, in the dataset's column format."""
 import collections
+import math
 import statistics
 
 import numpy as np
 import torch
+
+from bmc_hip import slots
+from bmc_hip.encodings import event_block_spans
+from bmc_hip.slots import check_hot_filter
+from infer_parts import EventStream, HotFilter, Input, KeptPredictions, Metrics, Pictures, VoxelGrids
 
 EventRecording = collections.namedtuple("EventRecording", "lr gt lr_index gt_index lr_size gt_size", defaults=(None,) * 5)
 EventRecording.__doc__ = """An event-backed recording for MultiStreamSR.open_events / evaluate_recordings: lr, gt = (xs, ys, ps)
@@ -216,106 +222,48 @@ class SlotScheduler:
         return out
 
 
+def _tensors(v):
+    """Every tensor reachable in v through tuples, lists and dict values."""
+    if isinstance(v, dict):
+        v = tuple(v.values())
+    return [v] if torch.is_tensor(v) else [t for x in v for t in _tensors(x)] if isinstance(v, (tuple, list)) else []
+
+
 class MultiStreamSR:
     """Many recordings through one model at once: S slots of one batched forward pass, each carrying its own recording's
     recurrent state; a recording that ends frees its slot for the next queued one (infer_BMCNet.py mode 1, :248-295, runs
     them one after another at batch 1).  Per window: bmc_slot_stage (inputs + state, exact zeros where a recording starts),
     the model under no_grad with init=False (a zero state and a zero previous prediction give what init=True gives), then
-    bmc_slot_commit (state back to the pool) and bmc_slot_metrics (esr_mse / bicubic_mse sums per slot, read only when
-    results() asks) -- one launch each for all slots (bmc_hip/slots.py).
+    bmc_slot_commit (state back to the pool) -- one launch each for all slots (bmc_hip/slots.py) -- and around them the
+    launches of the session's parts.
 
     open(frames [L,2,H,W], gts [L,2,gh,gw]) queues a recording (fp32, on the GPU; windows as oracle.infer_windows: `seqn`
     frames each, the ground truth of window i is frame i+1); step() runs one window for every active slot; run() steps to the
-    end; results(handle) gives per-window esr_mse, bicubic_mse, time (ms, events on the launch stream around the whole
-    window, shared by the slots of that window) and, with keep_predictions, the predictions [n_windows,2,sH,sW].
+    end; results(handle) gives per window the time (ms, events on the launch stream around the whole window, shared by the
+    slots of that window) and what the parts add.
 
-    open_events(lr, gt, lr_index, gt_index, lr_size, gt_size) queues an EVENT-BACKED recording: the raw dataset columns stay
-    on the GPU (12 bytes per event instead of 8 bytes per pixel of every frame) and the frames of a window are encoded on the
-    fly by bmc_slot_encode -- one more launch per window for all slots, into per-slot scratch that the slot's table entry
-    points at; the other kernels do not know the difference, and the results are bit-identical to open() on the frames the
-    raw-column encoder (ops.encode_raw_events, no flips) gives for the same ranges.  The encode launch is issued only once an
-    event-backed recording has been opened; both kinds may share a session.
-
-    graph=True: from the third window on a window is ONE graph replay ([encode,] stage, forward, commit, metrics captured; the
-    slot table is refreshed by one small copy before it); the first open_events after a capture invalidates the graph.  Parameter updates invalidate the graph as in StreamingSR.
+    graph=True: from the third window on a window is ONE graph replay (everything _window() launches is captured; the slot
+    table is refreshed by one small copy before it); a recording that makes a part grow invalidates the graph.  Parameter
+    updates invalidate the graph as in StreamingSR.
     state_dtype=torch.bfloat16: the feature states rest in bf16 between windows, as StreamingSR(state_dtype=bf16).
 
-    emit_events=True: every window's prediction is also turned into an EVENT LIST on the GPU (bmc_slot_emit: two more launches
-    per window for all slots, inside the captured graph too) and appended to the recording's own output columns: per element v
-    of the prediction [2,sH,sW] in flat order, q = min(rint(v), max_count) for v > 0 (else 0; round-half-to-even -- the rounded
-    count image the reference renders, infer_BMCNet.py:94) events xs = x, ys = sH-1-row, ps = +1 (channel 0) / -1 (channel 1),
-    so that encoding a window's events at (sH, sW) gives q back exactly.  results() then carries sr_events = (xs int16, ys int16,
-    ps int8) and sr_index [done+1] (window i owns events [sr_index[i], sr_index[i+1])); without event_times there are no
-    timestamps and a window's events are in pixel order.  The columns hold `event_capacity` events (open / open_events; default 2 x scale^2 x the recording's LR
-    events); the index keeps counting past it, and results() then raises with the capacity that is needed.  About 5 bytes per
-    event instead of 8 x sH x sW bytes per window of keep_predictions; both may be on.
+    Every option is one part (infer_parts.py, where each is described), kept in self.parts in the launch order of a window:
+      hot_filter=dict(...)        HotFilter        the reference's hot-pixel filter for event-backed recordings
+      open / open_events          Input            frames, or raw event columns encoded window by window
+      a ground truth              Metrics          esr_mse / bicubic_mse per window
+      keep_predictions            KeptPredictions  predictions [n_windows,2,sH,sW]
+      emit_events, event_times    EventStream      the super-resolved event stream: plain, timed, or on the sensor's clock
+      render=(kinds...)           Pictures         the reference's event-count images
+      voxel_bins=B                VoxelGrids       the voxel grid of every window's events"""
 
-    event_times="linear" (with emit_events; needs max_count <= 255): the list becomes a STREAM.  Every event also carries a
-    float32 time inside its window and a window's events are stored in time order (bmc_slot_emit_timed: six launches per
-    window instead of the two, inside the captured graph too) -- the reference's linear redistribution of a count image
-    (dataloader/encodings.py:367-414, mode='linear', one time bin): event j of a pixel's n events has t = 0.01 + 0.99 * j /
-    (n - 1) (0.01 for n = 1; float64, rounded once), the window is sorted by the exact j / (n - 1), ties in the pixel order
-    above.  results() then also carries sr_ts (float32, on the GPU), parallel to sr_events.  Times are window-normalised: a
-    count image has no absolute clock.  The sort works in per-slot scratch of `window_event_capacity` events (open /
-    open_events; default 2 x scale^2 x the LR events of the recording's busiest frame, at most 2 x sH x sW x max_count); a
-    window that emits more stores nothing, the index keeps the true count and results() raises with the capacity needed.
-
-    Recordings WITHOUT ground truth (open(frames), open_events(lr, None, lr_index, None, lr_size)): what a deployed sensor
-    delivers.  Their results() carry no esr_mse / bicubic_mse; they only have to match the session's (H, W) and may share it
-    with recordings that have a ground truth.  bmc_slot_metrics is launched only once a recording with ground truth has been
-    opened (the first such open after a capture invalidates the graph, as the first open_events does).
-
-    Events on the SENSOR'S CLOCK (event_times="linear"; open(..., spans=) / open_events(..., lr_ts= or spans=)): spans [L,2]
-    float64 = (t_first, t_last) of every item on the recording's own time base (open_events derives them from the timestamp
-    column lr_ts: bmc_hip.encodings.event_block_spans).  Window i predicts item i+1 (infer_BMCNet.py:52) and uses its span:
-    sr_ts is then FLOAT64, t = t_first + tau * (t_last - t_first) with tau the window time above computed from the reduced
-    fraction of j / (n - 1) (bmc_slot_emit_clocked; include/bmc_hip.h states the contract) -- the inverse of
-    event_formatting's normalisation (dataloader/base_dataset.py:30) without its 1e-6.  Each window is in time order; with
-    sliding_window < window the spans of consecutive windows overlap, so the concatenation of a recording's windows is
-    globally sorted only for non-overlapping spans.  Clocked and unclocked recordings may share a session.
-
-    hot_filter=dict(max_px=, min_obvs=, max_rate=): the reference's hot-pixel filter (dataset.hot_filter; create_hot_mask,
-    dataloader/h5dataset.py:528-548; get_hot_event_mask, dataloader/encodings.py:349-364) on the GPU, for recordings opened with
-    open_events: every LR item is observed once, in item order (a per-slot count of the items in which a pixel fired), its mask
-    follows the reference's rule bit for bit, and the item's count image has both channels zeroed where the mask says so --
-    include/bmc_hip.h states the contract.  bmc_slot_hot_update (one more launch per window for all slots, inside the captured
-    graph too) runs before the encode launch, which becomes bmc_slot_encode_filtered.  Recordings opened with open() in the same
-    session stay UNFILTERED, and so does every ground truth.  results() then carries hot_pixels (per window, the number of
-    pixels masked for the item that window newly observed) and hot_mask ([H,W] uint8 in sensor coordinates, 1 = kept, of the
-    last item observed).  The option needs nothing else switched on.
-
-    render=(kinds...) from ("lr", "bicubic", "esr", "gt"): the four EVENT-COUNT IMAGES the reference's inference writes per
-    window (infer_BMCNet.py:90-97: lr_event_img, hr_bicubic_event_img, hr_esr_event_img, hr_gt_event_img), rendered on the GPU as
-    the uint8 [h,w,3] arrays its plot_event_cnt returns, byte for byte (bmc_slot_render: two launches per kind for all slots,
-    inside the captured graph too; include/bmc_hip.h "event-count images" states the contract).  lr: frame 1 of the window as
-    the model sees it (H x W; after the hot-pixel filter where one applies); esr: the prediction, resized to the ground truth's
-    size where that differs (bmc_bicubic_resize_fwd, as the metric does) and rounded half-to-even; bicubic: frame 1 resized to
-    the ground truth's size; gt: the window's ground truth.  A recording without ground truth gets lr and esr (at the
-    prediction's size) only.  results() then carries images = {kind: uint8 [done,h,w,3]} on the GPU: 3 bytes per pixel and
-    window instead of the 8 of keep_predictions.  None (the default): no image, no launch.
-
-    voxel_bins=B (1 <= B <= 32; needs max_count <= 255): every window's prediction also leaves as the temporal-bilinear VOXEL
-    GRID of its super-resolved events, the input form of reconstruction, flow and recognition networks: what the reference's
-    events_to_voxel_torch (dataloader/encodings.py:100-148) returns for the window's timed event stream (the stream of
-    event_times="linear"), bit for bit, computed per output pixel from the prediction's two counts and one small reduction
-    (bmc_slot_voxel: two more launches per window for all slots, inside the captured graph too; no sort, no atomics, no event
-    storage; include/bmc_hip.h "voxel grids" states the contract).  Independent of emit_events, event_times and render, for
-    frame-backed and event-backed recordings, with or without ground truth.  results() then carries voxels = float32
-    [done,B,sH,sW] on the GPU, at the prediction's own size; its rows are the sensor's y, vertically flipped against the
-    prediction's rows as the emitted ys are.  The grid is window-normalised, so a sensor clock does not change it.  Resident:
-    4 x B x sH x sW bytes per window -- 13.8 MB per window at 720x960 with 5 bins.  None (the default): no grid, no launch, no
-    table section."""
-
-    MAX_VOXEL_BINS = 32          # BMC_SLOT_VOXEL_MAX_BINS
-    RENDER_KINDS = ("lr", "bicubic", "esr", "gt")
-    MAX_COUNT_LIMIT = 32767      # emitted counts and coordinates are int16
-    MAX_COUNT_TIMED = 255        # event_times: the sort key is a 16-bit rank of j / (n - 1), n <= 255
-    MAX_WINDOW_CAPACITY = 1 << 28
+    MAX_VOXEL_BINS, MAX_COUNT_LIMIT, MAX_COUNT_TIMED = slots.MAX_VOXEL_BINS, slots.MAX_COUNT_LIMIT, slots.MAX_COUNT_TIMED
+    MAX_WINDOW_CAPACITY, MAX_ITEMS_FILTERED = slots.MAX_WINDOW_CAPACITY, slots.HOT_MAX_ITEMS
+    MAX_SEQN_EVENTS, MAX_WIDTH_EVENTS = slots.MAX_SEQN, slots.MAX_ENCODE_WIDTH
+    RENDER_KINDS, RENDER_TABLES, check_render = Pictures.KINDS, Pictures.TABLES, staticmethod(Pictures.check)
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
                  seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None, voxel_bins=None):
-        from bmc_hip.slots import check_hot_filter
-        self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)
+        self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)  # (the argument `slots` hides the module here)
         self.render = self.check_render("MultiStreamSR: ", render)
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
@@ -324,103 +272,30 @@ class MultiStreamSR:
         if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= self.MAX_COUNT_LIMIT:
             raise ValueError("MultiStreamSR: max_count must be an integer, 1 <= max_count <= %d (got %r)"
                              % (self.MAX_COUNT_LIMIT, max_count))
-        if event_times not in (None, "linear"):
-            raise ValueError("MultiStreamSR: event_times must be None or 'linear' (got %r)" % (event_times,))
-        if event_times is not None and not emit_events:
-            raise ValueError("MultiStreamSR: event_times needs emit_events=True")
-        if event_times is not None and max_count > self.MAX_COUNT_TIMED:
-            raise ValueError("MultiStreamSR: event_times needs max_count <= %d (got %d)" % (self.MAX_COUNT_TIMED, max_count))
-        if voxel_bins is not None:
-            if isinstance(voxel_bins, bool) or not isinstance(voxel_bins, (int, np.integer)) or not 1 <= voxel_bins <= self.MAX_VOXEL_BINS:
-                raise ValueError("MultiStreamSR: voxel_bins must be None or an integer, 1 <= voxel_bins <= %d (got %r)"
-                                 % (self.MAX_VOXEL_BINS, voxel_bins))
-            if max_count > self.MAX_COUNT_TIMED:
-                raise ValueError("MultiStreamSR: voxel_bins needs max_count <= %d (the timed stream's limit; got %d)"
-                                 % (self.MAX_COUNT_TIMED, max_count))
-            voxel_bins = int(voxel_bins)
-        self.voxel_bins = voxel_bins
-        self.event_times = event_times
+        EventStream.check(emit_events, event_times, max_count)
+        self.voxel_bins, self.event_times = VoxelGrids.check(voxel_bins, max_count), event_times
         self._wcap = 0             # events per window the sort scratch holds (the largest window_event_capacity so far)
         self.model = model.eval()
         self.S, self.n_c, self.scale, self.plain, self.seqn = int(slots), n_c, scale, plain, int(seqn)
-        self.use_graph = graph
+        self.use_graph, self.keep_predictions = graph, keep_predictions
         self.state_dtype = None if state_dtype is torch.float32 else state_dtype
-        self.keep_predictions = keep_predictions
         self.emit_events, self.max_count = bool(emit_events), max_count
         self.sched = SlotScheduler(self.S)
-        self.replays = 0
+        self.replays = self._calls = 0
         self._recs = {}
         self._size = None          # (H, W) of the first recording, (H, W, gh, gw) once one with ground truth has been opened
-        self._bufs = None
         self._steps = []           # (start, end) events per window
-        self._calls = 0
-        self._graph = self._stamp = None
-        self._has_events = False
-        self._has_clock = False
+        self._bufs = self._graph = self._stamp = None
+        self._has_events = self._has_clock = False
+        self._stream = EventStream()
+        on = ((HotFilter(), self.hot_filter is not None), (Input(), True), (Metrics(), True), (KeptPredictions(), keep_predictions),
+              (self._stream, True), (Pictures(), self.render), (VoxelGrids(), self.voxel_bins is not None))
+        self.parts = [p for p, wanted in on if wanted]     # (a part keeps no reference to the session: no cycle)
 
-    @classmethod
-    def check_render(cls, who, render):
-        """render (None, or a tuple / list of distinct kinds from RENDER_KINDS) -> the kinds in RENDER_KINDS' order (() for None);
-        ValueError naming what is wrong."""
-        if render is None:
-            return ()
-        if isinstance(render, str) or not isinstance(render, (tuple, list)) or not render:
-            raise ValueError(who + "render must be None or a non-empty tuple of kinds from %s (got %r)" % (cls.RENDER_KINDS, render))
-        for k in render:
-            if not isinstance(k, str) or k not in cls.RENDER_KINDS:
-                raise ValueError(who + "render has an unknown kind %r (the kinds are %s)" % (k, ", ".join(cls.RENDER_KINDS)))
-        if len(set(render)) != len(render):
-            raise ValueError(who + "render names a kind twice (got %r)" % (render,))
-        return tuple(k for k in cls.RENDER_KINDS if k in render)
-
-    # the render tables of the slot table: "esr" draws from the prediction, "esr_gt" from the prediction resized to the ground truth
-    RENDER_TABLES = ("lr", "esr", "esr_gt", "bicubic", "gt")
-
-    def _render_size(self, kind, has_gt):
-        """(h, w) of a recording's image of `kind`."""
-        H, W = self._size[:2]
-        if kind == "lr":
-            return H, W
-        return tuple(self._size[2:]) if has_gt else (self.scale * H, self.scale * W)
+    def part(self, cls):
+        return next(p for p in self.parts if type(p) is cls)
 
     # ---------------------------------------------------------------- recordings
-    def _check_capacities(self, who, event_capacity, capacity):
-        """The two capacities a caller of open / open_events may give (None: the default)."""
-        if event_capacity is not None:
-            if not self.emit_events:
-                raise ValueError("MultiStreamSR.%s: event_capacity needs a session with emit_events=True" % who)
-            if isinstance(event_capacity, bool) or not isinstance(event_capacity, (int, np.integer)) or event_capacity < 1:
-                raise ValueError("MultiStreamSR.%s: event_capacity must be a positive integer (got %r)" % (who, event_capacity))
-        if capacity is not None:
-            if self.event_times is None:
-                raise ValueError("MultiStreamSR.%s: window_event_capacity needs a session with event_times='linear'" % who)
-            if isinstance(capacity, bool) or not isinstance(capacity, (int, np.integer)) or not 1 <= capacity <= self.MAX_WINDOW_CAPACITY:
-                raise ValueError("MultiStreamSR.%s: window_event_capacity must be a positive integer, at most %d (got %r)"
-                                 % (who, self.MAX_WINDOW_CAPACITY, capacity))
-
-    def _emit_room(self, who, H, W, event_capacity, window_event_capacity, total, busiest):
-        """What an emitting session needs of a recording of H x W frames: coordinates in int16, and the two capacities, by
-        default 2 x scale^2 x the recording's LR events / 2 x scale^2 x the LR events of its busiest item (at most what a window
-        can emit).  total / busiest give those counts and are called only where a default is needed."""
-        if self.emit_events and max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
-            raise ValueError("MultiStreamSR.%s: predictions of %d x %d cannot be emitted (int16 coordinates)"
-                             % (who, self.scale * H, self.scale * W))
-        if self.emit_events and event_capacity is None:
-            event_capacity = 2 * self.scale ** 2 * int(total())
-        if self.event_times is not None and window_event_capacity is None:
-            most = 2 * self.scale ** 2 * H * W * self.max_count
-            window_event_capacity = max(1, min(2 * self.scale ** 2 * int(busiest()), most, self.MAX_WINDOW_CAPACITY))
-        return event_capacity, window_event_capacity
-
-    def _check_spans(self, who, spans, L):
-        """spans (or None) -> a validated [L,2] float64 table on the host (or None)."""
-        if spans is None:
-            return None
-        if self.event_times is None:
-            raise ValueError("MultiStreamSR.%s: spans / lr_ts need a session with event_times='linear'" % who)
-        from bmc_hip.encodings import check_spans
-        return check_spans("MultiStreamSR.%s: " % who, spans, L)
-
     def open(self, frames, gts=None, gt_size=None, event_capacity=None, window_event_capacity=None, spans=None):
         """Queue one recording -> handle.  frames [L,2,H,W], gts [L,2,gh,gw] (fp32, on the GPU); gt_size (the reference's
         gt_sensor_resolution, the bicubic baseline's size) must be the ground truth's size.  gts=None: a recording without
@@ -428,7 +303,7 @@ class MultiStreamSR:
         sum of `frames` (one device reduction here).  window_event_capacity (event_times): events of ONE window the sort
         scratch holds; default 2 x scale^2 x the largest sum of one frame.  spans (event_times) [L,2] float64 on the host:
         (t_first, t_last) of every frame on the sensor's clock -> sr_ts is float64 on that clock."""
-        self._check_capacities("open", event_capacity, window_event_capacity)
+        self._stream.check_capacities(self, "open", event_capacity, window_event_capacity)
         given = (frames,) if gts is None else (frames, gts)
         if frames.dim() != 4 or frames.shape[1] != 2 or any(g.dim() != 4 or tuple(g.shape[:2]) != (frames.shape[0], 2)
                                                             for g in given[1:]):
@@ -436,7 +311,7 @@ class MultiStreamSR:
                              % (" and gts [L,2,gh,gw]" * (gts is not None), ", ".join(str(tuple(g.shape)) for g in given)))
         if gts is None and gt_size is not None:
             raise ValueError("MultiStreamSR.open: gt_size without a ground truth")
-        spans = self._check_spans("open", spans, frames.shape[0])
+        spans = self._stream.check_spans(self, "open", spans, frames.shape[0])
         if not all(g.is_cuda and g.dtype == torch.float32 for g in given):
             raise ValueError("MultiStreamSR.open: %s" % ("frames must be an fp32 GPU tensor" if gts is None else
                                                          "frames and gts must be fp32 GPU tensors"))
@@ -447,8 +322,8 @@ class MultiStreamSR:
         gh, gw = (None, None) if gts is None else (gts.shape[2], gts.shape[3])
         if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
             raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
-        event_capacity, window_event_capacity = self._emit_room(
-            "open", H, W, event_capacity, window_event_capacity, lambda: frames.sum(dtype=torch.float64).item(),
+        event_capacity, window_event_capacity = self._stream.room(
+            self, "open", H, W, event_capacity, window_event_capacity, lambda: frames.sum(dtype=torch.float64).item(),
             lambda: frames.sum(dim=(1, 2, 3), dtype=torch.float64).max().item())
         self._set_size("open", H, W, gh, gw)
         rec = {"frames": frames.contiguous()}
@@ -465,66 +340,36 @@ class MultiStreamSR:
                              "size)" % (who, size, self._size))
         if self._size is None or len(size) > len(self._size):
             if self._size is None:                         # once per session: workgroups per slot of the emit launches
-                from bmc_hip import slots
-                self._nparts = slots.emit_parts(self.scale * H, self.scale * W)
-                self._vparts = slots.voxel_parts(self.scale * H, self.scale * W)
+                self._nparts, self._vparts = (f(self.scale * H, self.scale * W) for f in (slots.emit_parts, slots.voxel_parts))
             self._size = size
             if len(size) == 4:                             # a running session without ground truth: the metrics launch joins
-                self._grow(self._gt_scratch, self._render_buffers)
+                self._grow()
 
-    def _grow(self, *rebuild):
-        """The session gains a part (a first event-backed, clocked or ground-truth recording, a larger window capacity).  One
-        that has run already rebuilds the buffers concerned -- rebuild: methods taking (buffers, device) -- and drops its
-        captured graph, which holds the old addresses and launches."""
-        if self._bufs is not None:
-            for make in rebuild:
-                make(self._bufs, self._bufs["x"].device)
-            self.invalidate()
+    def _grow(self):
+        """The session gains something (a first event-backed, clocked or ground-truth recording, a larger window capacity).  One
+        that has run already rebuilds the buffers whose declared shape changed and no others (the hot-pixel counts live in one),
+        replaces the table when a keyword changed, and drops its captured graph, which holds the old addresses and launches."""
+        b = self._bufs
+        if b is None:
+            return
+        device = b["x"].device
+        for k, d in self._scratch().items():
+            if k not in b or b[k].shape != torch.Size(d[0]):
+                b[k] = self._alloc(d, device)
+        if any(getattr(b["table"], k) != v for k, v in self._table_keywords().items()):
+            b["table"] = slots.SlotTable(self.S, device, **self._table_keywords())
+        self.invalidate()
 
     def _add(self, rec, L, device, event_capacity=None, window_event_capacity=None, spans=None):
         """Queue a recording of L items (frames or event blocks) -> handle."""
-        from bmc_hip import slots
-        H, W = self._size[:2]
-        nwin = L - self.seqn + 1
-        if "gts" in rec or "gt" in rec:                    # the result sums of a recording with ground truth
-            rec["sse"] = torch.zeros(nwin, slots.metric_parts(*self._size[2:]), 2, dtype=torch.float64, device=device)
-        rec.update(n=nwin, steps=[], device=device,
-                   keep=torch.empty(nwin, 2, self.scale * H, self.scale * W, device=device) if self.keep_predictions else None)
-        if self.render:                                    # the recording's pictures: without ground truth, lr and esr only
-            has_gt = "sse" in rec
-            if max(h * w for h, w in (self._render_size(k, has_gt) for k in self.render)) > slots.MAX_RENDER_PIXELS:
-                raise ValueError("MultiStreamSR: images of more than 2^24 pixels cannot be rendered (sizes %s)" % (self._size,))
-            rec["images"] = {k: torch.empty((nwin,) + self._render_size(k, has_gt) + (3,), dtype=torch.uint8, device=device)
-                             for k in self.render if has_gt or k in ("lr", "esr")}
-        if self.voxel_bins is not None:                    # the recording's voxel grids, at the prediction's size
-            if max(self.scale * H, self.scale * W) > self.MAX_COUNT_LIMIT:
-                raise ValueError("MultiStreamSR: predictions of %d x %d are too large for voxel grids (at most %d a side)"
-                                 % (self.scale * H, self.scale * W, self.MAX_COUNT_LIMIT))
-            rec["voxels"] = torch.empty(nwin, self.voxel_bins, self.scale * H, self.scale * W, device=device)
-        if self.emit_events:                               # the recording's output stream: three columns and the index table
-            cap = max(int(event_capacity), 1)
-            rec.update(ev_capacity=cap, ev_xs=torch.empty(cap, dtype=torch.int16, device=device),
-                       ev_ys=torch.empty(cap, dtype=torch.int16, device=device),
-                       ev_ps=torch.empty(cap, dtype=torch.int8, device=device),
-                       ev_index=torch.zeros(nwin + 1, dtype=torch.int64, device=device))
-        if self.event_times is not None:                   # ... a time column, and room for its largest window in the sort
-            rec.update(ev_ts=torch.empty(cap, dtype=torch.float32 if spans is None else torch.float64, device=device),
-                       win_capacity=int(window_event_capacity))
-            if spans is not None:                          # a clocked recording: float64 times on its own clock
-                rec["spans"] = spans
-                if not self._has_clock:
-                    self._has_clock = True
-                    self._grow(self._new_table)            # the table grows a clock part
-            if rec["win_capacity"] > self._wcap:
-                self._wcap = rec["win_capacity"]
-                self._grow(self._sort_buffers)             # the sort scratch grows
-        h = self.sched.add(nwin)
+        rec.update(n=L - self.seqn + 1, steps=[], device=device, keep=None)
+        for p in self.parts:
+            p.open(self, rec, L, event_capacity=event_capacity, window_event_capacity=window_event_capacity, spans=spans)
+        if any([p.grew(self, rec) for p in self.parts]):
+            self._grow()
+        h = self.sched.add(rec["n"])
         self._recs[h] = rec
         return h
-
-    MAX_ITEMS_FILTERED = 1 << 23 # hot_filter: below it distinct counts give distinct float32 rates (include/bmc_hip.h)
-    MAX_SEQN_EVENTS = 8          # bmc_slot_events_t holds the ranges of at most 8 LR frames (BMC_SLOT_MAX_SEQN)
-    MAX_WIDTH_EVENTS = 7680      # bmc_slot_encode: one row of both channels must fit a workgroup's LDS band
 
     def open_events(self, lr, gt=None, lr_index=None, gt_index=None, lr_size=None, gt_size=None, event_capacity=None,
                     window_event_capacity=None, lr_ts=None, spans=None):
@@ -541,7 +386,7 @@ class MultiStreamSR:
         of every item (bmc_hip.encodings.event_block_spans) and float64 sr_ts on the sensor's clock; or spans [L,2] directly
         (not both)."""
         who = "MultiStreamSR.open_events: "
-        self._check_capacities("open_events", event_capacity, window_event_capacity)
+        self._stream.check_capacities(self, "open_events", event_capacity, window_event_capacity)
         if lr_index is None or lr_size is None:
             raise ValueError(who + "lr_index and lr_size are required")
         has_gt = gt is not None
@@ -549,8 +394,7 @@ class MultiStreamSR:
             raise ValueError(who + "gt, gt_index and gt_size are all given or all None")
         if lr_ts is not None and spans is not None:
             raise ValueError(who + "give lr_ts or spans, not both")
-        if (lr_ts is not None or spans is not None) and self.event_times is None:
-            raise ValueError(who + "spans / lr_ts need a session with event_times='linear'")
+        self._stream.check_spans(self, "open_events", lr_ts if spans is None else spans)
         for name, cols in (("lr", lr), ("gt", gt))[:1 + has_gt]:
             if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
                 raise ValueError(who + "%s must be three tensors (xs, ys, ps)" % name)
@@ -577,19 +421,13 @@ class MultiStreamSR:
             raise ValueError(who + "%d items, fewer than one window of seqn = %d" % (L, self.seqn))
         if self.seqn > self.MAX_SEQN_EVENTS:
             raise ValueError(who + "seqn <= %d for event-backed recordings" % self.MAX_SEQN_EVENTS)
-        if self.hot_filter is not None:
-            if L >= self.MAX_ITEMS_FILTERED:
-                raise ValueError(who + "a filtered session takes recordings of fewer than 2^23 items (got %d)" % L)
-            if int((lr_index[:, 1] - lr_index[:, 0]).max()) >= 2 ** 31:
-                raise ValueError(who + "a filtered session takes LR items of fewer than 2^31 events")
         if lr_ts is not None:
             if not ((torch.is_tensor(lr_ts) and lr_ts.dtype == torch.float64 and lr_ts.dim() == 1) or
                     (isinstance(lr_ts, np.ndarray) and lr_ts.dtype == np.float64 and lr_ts.ndim == 1)) \
                     or len(lr_ts) != lr[0].numel() or len(lr_ts) < 1:
                 raise ValueError(who + "lr_ts must be a 1-D float64 column parallel to lr[0]")
-            from bmc_hip.encodings import event_block_spans
             spans = event_block_spans(lr_ts, lr_index)
-        spans = self._check_spans("open_events", spans, L)
+        spans = self._stream.check_spans(self, "open_events", spans, L)
         try:
             (H, W), (gh, gw) = (int(v) for v in lr_size), ((int(v) for v in gt_size) if has_gt else (None, None))
         except (TypeError, ValueError):
@@ -598,8 +436,8 @@ class MultiStreamSR:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)"
                              % (self.MAX_WIDTH_EVENTS, (H, W), (gh, gw)))
         lengths = lr_index[:, 1] - lr_index[:, 0]
-        event_capacity, window_event_capacity = self._emit_room("open_events", H, W, event_capacity, window_event_capacity,
-                                                                lengths.sum, lengths.max)
+        event_capacity, window_event_capacity = self._stream.room(self, "open_events", H, W, event_capacity,
+                                                                  window_event_capacity, lengths.sum, lengths.max)
         cols = tuple(lr) + (tuple(gt) if has_gt else ())
         if not all(t.is_cuda and t.device == cols[0].device for t in cols):
             raise ValueError(who + "the columns must be GPU tensors on one device")
@@ -610,124 +448,54 @@ class MultiStreamSR:
         rec = {"lr": tuple(lr), "lr_index": lr_index}
         if has_gt:
             rec.update(gt=tuple(gt), gt_index=gt_index)
-        if self.hot_filter is not None:                    # written by bmc_slot_hot_update: the slot is reused after the recording
-            from bmc_hip import slots
-            _, min_obvs, max_rate = self.hot_filter
-            rec.update(hot_pixels=torch.zeros(L - self.seqn + 1, dtype=torch.int32, device=cols[0].device),
-                       hot_mask=torch.ones(H, W, dtype=torch.uint8, device=cols[0].device),
-                       hot_cmin=[slots.hot_cmin(j + 1, min_obvs, max_rate) for j in range(L)])
-        h = self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
-        if not self._has_events:
-            self._has_events = True
-            self._grow(self._event_buffers)                # a frames-only session: the table grows an event part
-        return h
+        return self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
 
     def resident_bytes(self, handle):
-        """Bytes the recording keeps on the GPU: its columns (event-backed) or frames, its result sums, kept predictions and
-        (emit_events) its output columns with their index, (voxel_bins=B) its voxel grids: 4 * B * sH * sW bytes per window."""
-        r = self._recs[handle]
-        data = r["lr"] + r.get("gt", ()) if "lr" in r else (r["frames"],) + ((r["gts"],) if "gts" in r else ())
-        if "ev_xs" in r:
-            data = tuple(data) + (r["ev_xs"], r["ev_ys"], r["ev_ps"], r["ev_index"]) + ((r["ev_ts"],) if "ev_ts" in r else ())
-        data = tuple(data) + ((r["sse"],) if "sse" in r else ()) + (() if r["keep"] is None else (r["keep"],))
-        if "hot_pixels" in r:                              # (hot_filter) the per-window mask counts and the last mask
-            data = data + (r["hot_pixels"], r["hot_mask"])
-        data = data + tuple(r.get("images", {}).values())  # (render) the pictures
-        if "voxels" in r:
-            data = data + (r["voxels"],)
-        return sum(t.numel() * t.element_size() for t in data)
+        """Bytes the recording keeps on the GPU: every tensor of its record -- its columns (event-backed) or frames, and what the
+        parts have added to it (result sums, kept predictions, output columns with their index, pictures, voxel grids, ...)."""
+        return sum(t.numel() * t.element_size() for t in _tensors(self._recs[handle]))
 
     def scratch_bytes(self):
-        """Bytes of the per-slot scratch images of event-backed slots (0 until an event-backed recording has been opened; with
-        hot_filter also the slots' counts, mask rings and workspace: 8 + seqn bytes per pixel) and, with event_times, of the
-        sort scratch (0 until a recording has been opened); with render, the percentiles and, once a recording with ground truth
-        has been opened, the resize scratch [S,2,gh,gw] that bicubic and a resized esr share and the frames [S,2,H,W] it reads;
-        with voxel_bins, the partials of the reduce launch (8 bytes per part and slot)."""
-        nbytes = 0
-        if self.render and self._size is not None:
-            nbytes += 4 * 4 * self.S
-            if len(self._size) == 4 and self._render_resizes():
-                nbytes += 4 * self.S * 2 * (self._size[2] * self._size[3] + ("bicubic" in self.render) * self._size[0] * self._size[1])
-        if self._wcap:
-            from bmc_hip import slots
-            nbytes = slots.emit_timed_scratch_bytes(self.S, self._nparts, self._wcap)
-        if self.voxel_bins is not None and self._size is not None:
-            nbytes += 4 * 2 * self.S * self._vparts
-        if not self._has_events:
-            return nbytes
-        H, W = self._size[:2]
-        gh, gw = self._gt_scratch_size()
-        if self.hot_filter is not None:
-            nbytes += self.S * H * W * (4 + 4 + self.seqn)
-        return nbytes + 4 * self.S * (self.seqn * 2 * H * W + 2 * gh * gw)
-
-    def _gt_scratch_size(self):
-        """(gh, gw) of the event-backed slots' ground-truth scratch: a 1 x 1 placeholder (bmc_slot_encode only zero-fills it)
-        while no recording of the session has a ground truth."""
-        return self._size[2:] if len(self._size) == 4 else (1, 1)
+        """Bytes of the session's scratch: the counted entries of the parts' scratch() declarations, which _buffers() allocates
+        from, at the current sizes -- so it answers before the first step(), and a part whose buffers do not exist yet (no event-
+        backed recording, no window capacity) counts 0.  Not counted: x, pred, pool, feat, the table, the stream's emit_parts."""
+        return sum(math.prod(shape) * dtype.itemsize for shape, dtype, _, counted in self._scratch().values() if counted)
 
     def results(self, handle):
-        """-> dict(esr_mse=[...], bicubic_mse=[...] (a recording with ground truth only), time=[...] per window done so far[,
-        hot_pixels=[...] per window, hot_mask=[H,W] uint8 on the GPU (hot_filter, event-backed recordings)][,
-        predictions=[n,2,sH,sW]][, images={kind: uint8 [n,h,w,3] on the GPU} (render)][, voxels=[n,B,sH,sW] float32 on the GPU
-        (voxel_bins=B)][, sr_events=(xs, ys, ps) of those windows on the GPU, sr_index [done+1] int64 on the host][,
-        sr_ts on the GPU, parallel to sr_events (event_times): float32 inside each window, or float64 on the sensor's clock for
-        a recording opened with spans / lr_ts]).  Raises RuntimeError when the windows emitted more events than the recording's
-        event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity
-        needed)."""
+        """-> dict(time=[...] per window done so far, and what the session's parts add: esr_mse, bicubic_mse (a recording with
+        ground truth); hot_pixels, hot_mask (hot_filter, event-backed recordings); predictions; images (render); voxels; sr_events,
+        sr_index, sr_ts (emit_events, event_times)).  Raises RuntimeError when the windows emitted more events than the recording's
+        event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity needed)."""
         r = self._recs[handle]
         done = len(r["steps"])
         if done:
             self._steps[r["steps"][-1]][1].synchronize()
-        from bmc_hip import slots
-        out = {}
-        if "sse" in r:
-            sse = slots.sum_parts(r["sse"][:done]) / (2 * self._size[2] * self._size[3])
-            out.update(esr_mse=sse[:, 0].tolist(), bicubic_mse=sse[:, 1].tolist())
-        out["time"] = [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]
-        if self.keep_predictions:
-            out["predictions"] = r["keep"][:done]
-        if "hot_pixels" in r:
-            out.update(hot_pixels=r["hot_pixels"][:done].tolist(), hot_mask=r["hot_mask"])
-        if self.render:
-            out["images"] = {k: t[:done] for k, t in r["images"].items()}
-        if self.voxel_bins is not None:
-            out["voxels"] = r["voxels"][:done]
-        if self.emit_events:
-            index = r["ev_index"][:done + 1].cpu()
-            total = int(index[done])
-            if total > r["ev_capacity"]:
-                raise RuntimeError("MultiStreamSR.results: recording %d emitted %d events in %d windows, more than its "
-                                   "event_capacity of %d: open it with event_capacity >= %d"
-                                   % (handle, total, done, r["ev_capacity"], total))
-            if self.event_times is not None:
-                most = int((index[1:] - index[:-1]).max()) if done else 0
-                if most > r["win_capacity"]:
-                    raise RuntimeError("MultiStreamSR.results: a window of recording %d emitted %d events, more than its "
-                                       "window_event_capacity of %d: open it with window_event_capacity >= %d"
-                                       % (handle, most, r["win_capacity"], most))
-                out["sr_ts"] = r["ev_ts"][:total]
-            out["sr_events"] = (r["ev_xs"][:total], r["ev_ys"][:total], r["ev_ps"][:total])
-            out["sr_index"] = index
+        out = {"time": [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]}
+        for p in self.parts:
+            p.results(self, out, r, done, handle)
         return out
 
     # ---------------------------------------------------------------- windows
+    def _scratch(self):
+        """{key: (shape, dtype, fill, counted)} of every part's buffers in _bufs at the current sizes ({} before a recording)."""
+        return {} if self._size is None else {k: d for p in self.parts for k, d in p.scratch(self).items()}
+
+    @staticmethod
+    def _alloc(decl, device):
+        shape, dtype, fill, _ = decl
+        return torch.empty(shape, dtype=dtype, device=device) if fill is None else torch.full(shape, fill, dtype=dtype, device=device)
+
+    def _table_keywords(self):
+        return {k: v for p in self.parts for k, v in p.table(self).items()}
+
     def _buffers(self, device):
         if self._bufs is None:
             H, W = self._size[:2]
             S, nfeat = self.S, 1 if self.plain else 3
             b = {"x": torch.zeros(S, 2, self.seqn, H, W, device=device),
-                 "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device)}
-            self._new_table(b, device)
-            if self.emit_events:
-                b["emit_parts"] = torch.zeros(S * self._nparts, dtype=torch.int32, device=device)
-            if self.event_times is not None:
-                self._sort_buffers(b, device)
-            if self._has_events:
-                self._event_buffers(b, device)
-            self._render_buffers(b, device)
-            if self.voxel_bins is not None:
-                b["voxel_parts"] = torch.zeros(2 * S * self._vparts, dtype=torch.int32, device=device)
+                 "pred": torch.zeros(S, 2, self.scale * H, self.scale * W, device=device),
+                 "table": slots.SlotTable(S, device, **self._table_keywords())}
+            b.update({k: self._alloc(d, device) for k, d in self._scratch().items()})
             if self.state_dtype is None:
                 b["pool"] = b["feat"] = torch.zeros(nfeat, S, H, W, self.n_c, device=device)       # the model reads the pool
             else:
@@ -736,113 +504,26 @@ class MultiStreamSR:
             self._bufs = b
         return self._bufs
 
-    def _new_table(self, b, device):
-        """The slot table with the parts the session needs so far."""
-        from bmc_hip import slots
-        b["table"] = slots.SlotTable(self.S, device, events=self._has_events, emit=self.emit_events,
-                                     timed=self.event_times is not None, clock=self._has_clock,
-                                     hot=self._has_events and self.hot_filter is not None,
-                                     render=len(self.RENDER_TABLES) if self.render else 0,
-                                     voxel=self.voxel_bins is not None)
-
-    def _render_resizes(self):
-        """Does a session with ground truth resize for its pictures (bicubic always, esr when the sizes differ)?"""
-        H, W = self._size[:2]
-        return "bicubic" in self.render or ("esr" in self.render and tuple(self._size[2:]) != (self.scale * H, self.scale * W))
-
-    def _render_buffers(self, b, device):
-        if not self.render:
-            return
-        H, W = self._size[:2]
-        b["render_minmax"] = torch.zeros(4 * self.S, device=device)
-        if len(self._size) == 4 and self._render_resizes():
-            b["render_resize"] = torch.zeros(self.S, 2, *self._size[2:], device=device)
-            if "bicubic" in self.render:
-                b["render_mid"] = torch.zeros(self.S, 2, H, W, device=device)
-
-    def _sort_buffers(self, b, device):
-        from bmc_hip import slots
-        slots.emit_rank_table(device)                      # uploaded here, once per device: never inside a graph capture
-        b["emit_scratch"] = torch.empty(slots.emit_timed_scratch_bytes(self.S, self._nparts, self._wcap), dtype=torch.uint8,
-                                        device=device)
-
-    def _gt_scratch(self, b, device):
-        if "lr_scratch" in b:                              # (event-backed slots only)
-            gh, gw = self._gt_scratch_size()
-            b["gt_scratch"] = torch.zeros(self.S, 2, gh, gw, device=device)
-
-    def _event_buffers(self, b, device):
-        H, W = self._size[:2]
-        if not b["table"].events:
-            self._new_table(b, device)
-        b["lr_scratch"] = torch.zeros(self.S, self.seqn, 2, H, W, device=device)
-        self._gt_scratch(b, device)
-        if self.hot_filter is not None:                    # per slot: the running counts, a ring of seqn masks, the workspace
-            b["hot_counts"] = torch.zeros(self.S, H, W, dtype=torch.int32, device=device)
-            b["hot_ring"] = torch.ones(self.S, self.seqn, H, W, dtype=torch.uint8, device=device)
-            b["hot_ws"] = torch.zeros(self.S, H, W, dtype=torch.int32, device=device)
-
     def _forward(self):
         b = self._bufs
         states = [t.permute(0, 3, 1, 2) for t in b["feat"]]             # channels-last [S,n_c,H,W] views, adjacent
         return self.model(b["x"], *states, b["pred"], False)
 
     def _window(self):
-        """[[hot_update ->] encode ->] stage -> model -> commit [-> metrics] [-> emit] [-> render] [-> voxel] (what a graph replay
-        runs)."""
-        from bmc_hip import slots
+        """The input parts ([hot_update ->] [encode ->]) stage -> model -> commit, then the other parts in list order ([-> metrics]
+        [-> emit] [-> render] [-> voxel]): what a graph replay runs."""
         b = self._bufs
-        H, W = self._size[:2]
-        if "hot_ring" in b:
-            slots.hot_update(b["table"], b["hot_counts"], b["hot_ring"], b["hot_ws"], self.hot_filter[0], self.hot_filter[2])
-            slots.encode_filtered(b["table"], b["lr_scratch"], b["gt_scratch"], b["hot_ring"])
-        elif "lr_scratch" in b:
-            slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
+        for p in self.parts:
+            if p.input:
+                p.launch(self, b, None)
         slots.stage(b["table"], b["x"], b["pool"], b["feat"], b["pred"])
         out = self._forward()
         cl = lambda t: t if t.permute(0, 2, 3, 1).is_contiguous() else t.contiguous(memory_format=torch.channels_last)
-        slots.commit(b["table"], [cl(t) for t in out[:-1]], b["pool"], out[-1].contiguous(), b["pred"])
-        if len(self._size) == 4:                           # a recording with ground truth has been opened
-            gh, gw = self._size[2:]
-            slots.metrics(b["table"], out[-1].contiguous(), H, W, gh, gw, slots.metric_parts(gh, gw))
-        if self.event_times is not None:
-            emit = slots.emit_clocked if self._has_clock else slots.emit_timed
-            emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"], b["emit_scratch"], self._wcap)
-        elif self.emit_events:
-            slots.emit(b["table"], out[-1].contiguous(), self.max_count, self._nparts, b["emit_parts"])
-        if self.render:
-            self._render_window(out[-1].contiguous())
-        if self.voxel_bins is not None:
-            slots.voxel(b["table"], out[-1].contiguous(), self.max_count, self.voxel_bins, self._vparts, b["voxel_parts"])
-
-    def _render_window(self, pred):
-        """The render launches of a window, one pair per table in use: the slots' entries say which of them a slot takes part in.
-        The resize scratch serves the resized prediction first and the resized frame 1 after it."""
-        from bmc_hip import lib, slots
-        from bmc_hip.ops import _stream
-        b = self._bufs
-        t, mm, S = b["table"], b["render_minmax"], self.S
-        H, W = self._size[:2]
-        sH, sW = self.scale * H, self.scale * W
-        at = self.RENDER_TABLES.index
-        if "lr" in self.render:
-            slots.render(t, at("lr"), H, W, False, mm)
-        if "esr" in self.render:                           # b["pred"]: the window's predictions, where commit has put them
-            slots.render(t, at("esr"), sH, sW, True, mm)
-        if len(self._size) == 2:
-            return
-        gh, gw = self._size[2:]
-        if "esr" in self.render and (gh, gw) != (sH, sW):
-            lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", pred.data_ptr(), 2 * S, sH, sW, gh, gw,
-                     b["render_resize"].data_ptr(), _stream())
-            slots.render(t, at("esr_gt"), gh, gw, True, mm)
-        if "bicubic" in self.render:
-            b["render_mid"].copy_(b["x"][:, :, 1])         # frame 1 of every slot's window, as stage gathered it: [S,2,H,W]
-            lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", b["render_mid"].data_ptr(), 2 * S, H, W, gh, gw,
-                     b["render_resize"].data_ptr(), _stream())
-            slots.render(t, at("bicubic"), gh, gw, False, mm)
-        if "gt" in self.render:
-            slots.render(t, at("gt"), gh, gw, False, mm)
+        pred = out[-1].contiguous()
+        slots.commit(b["table"], [cl(t) for t in out[:-1]], b["pool"], pred, b["pred"])
+        for p in self.parts:
+            if not p.input:
+                p.launch(self, b, pred)
 
     def _weights_stamp(self):
         return tuple((id(p), p._version) for p in self.model.parameters())
@@ -864,91 +545,21 @@ class MultiStreamSR:
         self._graph = g
         self._stamp = self._weights_stamp()
 
-    def _fill_frames(self, e, r, i):
-        """Slot entry e of window i of a frame-backed recording."""
-        H, W = self._size[:2]
-        e["frames"] = r["frames"].data_ptr() + 4 * i * 2 * H * W
-        if "gts" in r:
-            e["gt"] = r["gts"].data_ptr() + 4 * (i + 1) * 2 * self._size[2] * self._size[3]
-
-    def _fill_events(self, e, ev, ht, s, r, i, reset):
-        """Slot entry e, and entry s of the event (ev) and hot (ht, or None) parts, of window i of an event-backed recording:
-        the slot entry points at the slot's scratch images."""
-        b = self._bufs
-        e["frames"] = b["lr_scratch"][s].data_ptr()
-        for k, t in zip(("lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps"), r["lr"] + r.get("gt", ())):
-            ev[k][s] = t.data_ptr()
-        ev["lr_range"][s, :self.seqn] = r["lr_index"][i:i + self.seqn]
-        if "gt" in r:                                      # (without: NULL columns, range (0, 0): the scratch is only zero-filled)
-            e["gt"] = b["gt_scratch"][s].data_ptr()
-            ev["gt_range"][s] = r["gt_index"][i + 1]
-        if ht is not None:                                 # the first window observes items 0 .. seqn-1, a later one item i+seqn-1
-            ht[s]["active"], ht[s]["first_item"], ht[s]["new_from"] = 1, i, 0 if reset else self.seqn - 1
-            ht[s]["cmin"][:self.seqn] = r["hot_cmin"][i:i + self.seqn]
-            ht[s]["hot_pixels"] = r["hot_pixels"].data_ptr() + 4 * i
-            ht[s]["hot_mask"] = r["hot_mask"].data_ptr()
-
-    @staticmethod
-    def _fill_emit(em, ck, r, i):
-        """Emit entry em and clock entry ck (of a table with a clock part) of window i: it appends at index[i] and leaves
-        index[i+1]."""
-        em["xs"], em["ys"], em["ps"] = r["ev_xs"].data_ptr(), r["ev_ys"].data_ptr(), r["ev_ps"].data_ptr()
-        em["index_in"] = r["ev_index"].data_ptr() + 8 * i
-        em["index_out"] = r["ev_index"].data_ptr() + 8 * (i + 1)
-        em["capacity"] = r["ev_capacity"]
-        if "spans" in r:                                   # window i predicts item i+1: its span, float64 times
-            ck["t_first"], ck["t_last"] = r["spans"][i + 1]
-            ck["ts"] = r["ev_ts"].data_ptr()
-        elif "ev_ts" in r:
-            em["ts"] = r["ev_ts"].data_ptr()
-
-    def _fill_render(self, rn, e, s, r, i):
-        """Entries s of the render tables rn [K,S] for window i of recording r, whose slot entry e has been filled: where each
-        of the recording's pictures reads its count image."""
-        b = self._bufs
-        H, W = self._size[:2]
-        resized = "sse" in r and tuple(self._size[2:]) != (self.scale * H, self.scale * W)
-        for kind, img in r["images"].items():
-            if kind == "lr":                               # frame 1 of the window
-                table, src = "lr", int(e["frames"]) + 4 * 2 * H * W
-            elif kind == "esr":
-                table, src = ("esr_gt", b["render_resize"][s].data_ptr()) if resized else ("esr", b["pred"][s].data_ptr())
-            elif kind == "bicubic":
-                table, src = "bicubic", b["render_resize"][s].data_ptr()
-            else:
-                table, src = "gt", int(e["gt"])
-            k = self.RENDER_TABLES.index(table)
-            rn[k, s]["src"], rn[k, s]["dst"] = src, img[i].data_ptr()
-
     def _fill(self, plan):
         """The table entries of the window `plan`, into the table's host copy."""
-        from bmc_hip import slots
         t = self._bufs["table"]
-        e = t.host()
-        ev = t.events_host() if t.events else None
-        em = t.emit_host() if self.emit_events else None
-        ck = t.clock_host() if t.clock else None
-        ht = t.hot_host() if t.hot else None
-        vx = t.voxel_host() if t.voxel else None
+        v = {"slot": t.host()}                             # host() first: it clears the copy the other views look into
+        for name in ("events", "emit", "clock", "hot", "render", "voxel"):
+            if getattr(t, name):
+                v[name] = getattr(t, name + "_host")()
         for s, p in enumerate(plan):
             if p is None:
                 continue
             h, i, reset = p
             r = self._recs[h]
-            if "lr" in r:
-                self._fill_events(e[s], ev, ht, s, r, i, reset)
-            else:
-                self._fill_frames(e[s], r, i)
-            e[s]["keep"] = r["keep"][i].data_ptr() if r["keep"] is not None else 0
-            if "sse" in r:                                 # (without ground truth: gt = 0, result = 0 -- no metrics for the slot)
-                e[s]["result"] = r["sse"][i].data_ptr()
-            e[s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
-            if em is not None:
-                self._fill_emit(em[s], ck[s] if "spans" in r else None, r, i)
-            if self.render:
-                self._fill_render(t.render_host(), e[s], s, r, i)
-            if vx is not None:
-                vx[s]["dst"] = r["voxels"][i].data_ptr()
+            v["slot"][s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
+            for part in self.parts:
+                part.fill(self, v, s, r, i, reset)
             r["steps"].append(len(self._steps))
 
     @torch.no_grad()
@@ -999,11 +610,10 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                                          recording (MultiStreamSR(emit_events=True); event_capacity: per recording, None =
                                          the default)][,
       sr_ts       = {name: ts float32}           with event_times="linear": the events' times inside their windows, every
-                                         window in time order (window_event_capacity: per recording, None = the default)]).
+                                         window in time order (window_event_capacity: per recording, None = the default)][,
       images      = {name: {kind: uint8 [n_windows,h,w,3]}}  with render: the event-count images of every recording]).
-    hot_filter: MultiStreamSR's option (the EventRecording items are filtered, frame pairs are not).  render: MultiStreamSR's
-    option (a tuple of kinds from "lr", "bicubic", "esr", "gt").  voxel_bins=B: MultiStreamSR's option; the result then carries
-    voxels = {name: float32 [n_windows,B,sH,sW]}."""
+    hot_filter (the EventRecording items are filtered, frame pairs are not), render (a tuple of kinds from "lr", "bicubic", "esr",
+    "gt"), voxel_bins=B (the result then carries voxels = {name: float32 [n_windows,B,sH,sW]}): MultiStreamSR's options."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
@@ -1022,32 +632,17 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     ms.run()
     params = sum(p.numel() for p in model.parameters()) / 1e6
     breakdown = {k: {} for k in ("esr_mse", "bicubic_mse", "time", "params")}
-    preds, streams, times, images, voxels = {}, {}, {}, {}, {}
+    # results() key -> is it on; an output of that name collects it per recording (sr_events with the recording's sr_index)
+    wanted = (("predictions", keep_predictions), ("sr_events", emit_events), ("sr_ts", event_times is not None),
+              ("images", ms.render), ("voxels", ms.voxel_bins is not None))
+    extra = {k: {} for k, on in wanted if on}
     for name, h in handles:
         r = ms.results(h)
         for k in ("esr_mse", "bicubic_mse", "time"):
             if k in r:
                 breakdown[k][name] = float(statistics.mean(r[k]))
         breakdown["params"][name] = params
-        if keep_predictions:
-            preds[name] = r["predictions"]
-        if emit_events:
-            streams[name] = r["sr_events"] + (r["sr_index"],)
-        if event_times is not None:
-            times[name] = r["sr_ts"]
-        if ms.render:
-            images[name] = r["images"]
-        if ms.voxel_bins is not None:
-            voxels[name] = r["voxels"]
-    out = {"results": breakdown, "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}}
-    if keep_predictions:
-        out["predictions"] = preds
-    if emit_events:
-        out["sr_events"] = streams
-    if event_times is not None:
-        out["sr_ts"] = times
-    if ms.render:
-        out["images"] = images
-    if ms.voxel_bins is not None:
-        out["voxels"] = voxels
-    return out
+        for k in extra:
+            extra[k][name] = r[k] + (r["sr_index"],) if k == "sr_events" else r[k]
+    return {"results": breakdown, "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}, **extra}
+

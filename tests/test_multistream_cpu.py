@@ -101,6 +101,18 @@ def test_table_layout_offsets_and_refusals():
         slots.table_layout(3, hot=True)
 
 
+def test_session_limits_are_the_slot_limits():
+    """Every MultiStreamSR.MAX_* is an alias of the limit bmc_hip/slots.py mirrors from include/bmc_hip.h, not a second copy."""
+    from bmc_hip import slots
+    from infer import MultiStreamSR
+    aliases = dict(MAX_COUNT_LIMIT="MAX_COUNT_LIMIT", MAX_COUNT_TIMED="MAX_COUNT_TIMED", MAX_WINDOW_CAPACITY="MAX_WINDOW_CAPACITY",
+                   MAX_VOXEL_BINS="MAX_VOXEL_BINS", MAX_ITEMS_FILTERED="HOT_MAX_ITEMS", MAX_SEQN_EVENTS="MAX_SEQN",
+                   MAX_WIDTH_EVENTS="MAX_ENCODE_WIDTH")
+    assert sorted(k for k in vars(MultiStreamSR) if k.startswith("MAX_")) == sorted(aliases)
+    for name, limit in aliases.items():
+        assert getattr(MultiStreamSR, name) is getattr(slots, limit), name
+
+
 # ------------------------------------------------------------------ ISA of csrc/slots.hip
 HIPCC = "/opt/rocm/bin/hipcc"
 

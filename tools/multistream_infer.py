@@ -45,6 +45,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
 import torch
 
 from infer import MultiStreamSR, StreamingSR
+from infer_parts import EventStream, HotFilter, Input, Pictures, VoxelGrids
 from models.BMCNet import BMCNet
 
 SEQN = 3
@@ -73,120 +74,58 @@ def event_recording(L, H, W, seed):
     return cols[0], cols[1], lr_index, gt_index, (H, W), (4 * H, 4 * W)
 
 
-def encode_alone(ms, reps=20):
-    """ms per bmc_slot_encode launch on the session's buffers (the table of its last window)."""
-    from bmc_hip import slots
-    b = ms._bufs
+def alone(call, reps=20):
+    """ms per call() on the launch stream: events around `reps` calls, after one untimed call."""
     a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
+    call()
     a.record()
     for _ in range(reps):
-        slots.encode(b["table"], b["lr_scratch"], b["gt_scratch"])
+        call()
     z.record()
     z.synchronize()
     return a.elapsed_time(z) / reps
 
 
-def hot_update_alone(ms, reps=20):
-    """ms per bmc_slot_hot_update call on the session's buffers (the table of its last window: every slot observes one more
-    item; the repeated calls keep counting it, which costs what a new item costs)."""
-    from bmc_hip import slots
-    b = ms._bufs
-    args = (b["table"], b["hot_counts"], b["hot_ring"], b["hot_ws"], ms.hot_filter[0], ms.hot_filter[2])
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    slots.hot_update(*args)
-    a.record()
-    for _ in range(reps):
-        slots.hot_update(*args)
-    z.record()
-    z.synchronize()
-    return a.elapsed_time(z) / reps
+def part_alone(ms, part):
+    """ms per call of the launches of the session's part `part` (a class of infer_parts: Input = bmc_slot_encode, HotFilter =
+    bmc_slot_hot_update, EventStream = bmc_slot_emit / _timed / _clocked, VoxelGrids = bmc_slot_voxel) on the session's buffers, with
+    the part's own argument lists.  The calls repeat the last window: they count its item again, append nothing, rewrite its grids."""
+    return alone(lambda: ms.part(part).launch(ms, ms._bufs, ms._bufs["pred"]))
 
 
 HOT_FILTER = dict(max_px=100, min_obvs=5, max_rate=0.8)
 
 
-def emit_alone(ms, reps=20):
-    """ms per bmc_slot_emit call (count + write kernel) on the session's buffers: the table and prediction of its last window.
-    The repeated calls append nothing new: the entries' index words are the last window's."""
-    from bmc_hip import slots
-    b = ms._bufs
-    H, W = ms._size[:2]
-    args = (b["table"], b["pred"], ms.max_count, slots.emit_parts(ms.scale * H, ms.scale * W), b["emit_parts"])
-    call = slots.emit
-    if ms.event_times is not None:                         # bmc_slot_emit_timed / _clocked: the six launches of the sorted stream
-        args, call = args + (b["emit_scratch"], ms._wcap), slots.emit_clocked if ms._has_clock else slots.emit_timed
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    call(*args)
-    a.record()
-    for _ in range(reps):
-        call(*args)
-    z.record()
-    z.synchronize()
-    return a.elapsed_time(z) / reps
-
-
-def voxel_alone(ms, reps=20):
-    """(ms per bmc_slot_voxel call (reduce + voxel kernel), ms of the composition it replaces) on the session's buffers: the
-    table and prediction of its last window.  The repeated calls rewrite the same grids.  The composition: the timed stream of
-    all slots' predictions (counts_to_events), then events_to_voxel_torch on every slot's columns as float32; timed once, after
-    one untimed pass, with host timers around a device synchronise (it allocates and reads an index back)."""
-    from bmc_hip import encodings, slots
-    b = ms._bufs
-    args = (b["table"], b["pred"], ms.max_count, ms.voxel_bins, ms._vparts, b["voxel_parts"])
-    a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    slots.voxel(*args)
-    a.record()
-    for _ in range(reps):
-        slots.voxel(*args)
-    z.record()
-    z.synchronize()
-    sH, sW = b["pred"].shape[2:]
+def voxel_composition(ms):
+    """ms of the composition bmc_slot_voxel replaces, on the session's last predictions: their timed stream (counts_to_events), then
+    events_to_voxel_torch on every slot's columns as float32; timed once, after one untimed pass, by host timers and a synchronise."""
+    from bmc_hip import encodings
+    pred = ms._bufs["pred"]
 
     def composition():
-        xs, ys, ps, ts, index = encodings.counts_to_events(b["pred"], ms.max_count, times="linear")
+        xs, ys, ps, ts, index = encodings.counts_to_events(pred, ms.max_count, times="linear")
         for k in range(len(index) - 1):
             lo, hi = int(index[k]), int(index[k + 1])
             encodings.events_to_voxel_torch(xs[lo:hi].float(), ys[lo:hi].float(), ts[lo:hi].contiguous(), ps[lo:hi].float(),
-                                            ms.voxel_bins, sensor_size=(sH, sW))
+                                            ms.voxel_bins, sensor_size=tuple(pred.shape[2:]))
         torch.cuda.synchronize()
 
     composition()
     t0 = time.perf_counter()
     composition()
-    return a.elapsed_time(z) / reps, 1e3 * (time.perf_counter() - t0)
+    return 1e3 * (time.perf_counter() - t0)
 
 
 RENDER_DIRS = {"lr": "lr_event_img", "bicubic": "hr_bicubic_event_img", "esr": "hr_esr_event_img", "gt": "hr_gt_event_img"}
 
 
-def render_alone(ms, reps=20):
+def render_alone(ms):
     """{table: ms per bmc_slot_render call (select + colour)} on the session's buffers, for every render table the session's
-    last window drew (the table and count images of that window; the repeated calls redraw the same pictures)."""
+    windows draw (Pictures.tables(): the table and count images of the last window; the repeated calls redraw the same pictures)."""
     from bmc_hip import slots
-    b = ms._bufs
-    H, W = ms._size[:2]
-    sizes = {"lr": (H, W), "esr": (ms.scale * H, ms.scale * W)}
-    if len(ms._size) == 4:
-        sizes.update({k: tuple(ms._size[2:]) for k in ("esr_gt", "bicubic", "gt")})
-        if sizes["esr"] != sizes["gt"]:
-            del sizes["esr"]                               # (every recording of the benchmark has a ground truth)
-        else:
-            del sizes["esr_gt"]
-    out = {}
-    for k, name in enumerate(ms.RENDER_TABLES):
-        if name not in sizes or name.split("_")[0] not in ms.render:
-            continue
-        args = (b["table"], k) + sizes[name] + (name.startswith("esr"), b["render_minmax"])
-        a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        slots.render(*args)
-        a.record()
-        for _ in range(reps):
-            slots.render(*args)
-        z.record()
-        z.synchronize()
-        out[name] = a.elapsed_time(z) / reps
-    return out
+    part, b = ms.part(Pictures), ms._bufs
+    return {name: alone(lambda: slots.render(b["table"], part.TABLES.index(name), h, w, rnd, b["render_minmax"]))
+            for name, h, w, rnd in part.tables(ms)}
 
 
 def write_images(root, name, images):
@@ -228,7 +167,7 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
     if emit:
         index = ms.results(hs[0])["sr_index"]
         dense = MultiStreamSR(m, S, n_c=128, scale=4, seqn=SEQN, keep_predictions=True)
-        return (lat, S * windows / wall, emit_alone(ms), int(index[-1] - index[-2]), ms.resident_bytes(hs[0]),
+        return (lat, S * windows / wall, part_alone(ms, EventStream), int(index[-1] - index[-2]), ms.resident_bytes(hs[0]),
                 dense.resident_bytes(dense.open(*recs[0])))
     if render:
         if render_dir:
@@ -236,11 +175,9 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
                 write_images(render_dir, "rec%03d" % k, ms.results(h)["images"])
         return lat, S * windows / wall, render_alone(ms), ms.resident_bytes(hs[0])
     if voxel_bins is not None:
-        return (lat, S * windows / wall) + voxel_alone(ms) + (ms.resident_bytes(hs[0]),)
-    if hot_filter is not None:
-        return lat, S * windows / wall, hot_update_alone(ms), ms.resident_bytes(hs[0])
+        return lat, S * windows / wall, part_alone(ms, VoxelGrids), voxel_composition(ms), ms.resident_bytes(hs[0])
     if events:
-        return lat, S * windows / wall, encode_alone(ms), ms.resident_bytes(hs[0])
+        return lat, S * windows / wall, part_alone(ms, Input if hot_filter is None else HotFilter), ms.resident_bytes(hs[0])
     return lat, S * windows / wall, ms.resident_bytes(hs[0])
 
 
