@@ -571,6 +571,7 @@ extern "C" int bmc_pgemm_reduce_weight(const float* slabs, int nsplit, int G, in
                                        bmc_stream_t stream) {
     BMC_CHECK_ARG(slabs && dw && nsplit >= 1, "bmc_pgemm_reduce_weight: bad args");
     BMC_CHECK_ARG((bias_slabs == nullptr) == (db == nullptr), "bmc_pgemm_reduce_weight: bias_slabs and db go together");
+    BMC_CHECK_ARG(kmap || N <= Cin, "bmc_pgemm_reduce_weight: a NULL kmap needs N <= Cin (got %d, %d)", N, Cin);
     const long long total = (long long)G * taps * M * N;
     const int wblocks = (int)((total + 31) / 32 > 8192 ? 8192 : (total + 31) / 32);
     const int bblocks = bias_slabs ? (int)(((long long)G * M + BIAS_OUT - 1) / BIAS_OUT) : 0;
@@ -594,6 +595,7 @@ extern "C" int bmc_pgemm_reduce_weight_groups(const float* slabs, int nsplit, in
                                               float* const* db, bmc_stream_t stream) {
     BMC_CHECK_ARG(slabs && dw && nsplit >= 1 && G >= 1 && G <= 4, "bmc_pgemm_reduce_weight_groups: bad args (1 <= G <= 4)");
     BMC_CHECK_ARG((bias_slabs == nullptr) == (db == nullptr), "bmc_pgemm_reduce_weight_groups: bias_slabs and db go together");
+    BMC_CHECK_ARG(kmap || N <= Cin, "bmc_pgemm_reduce_weight_groups: a NULL kmap needs N <= Cin (got %d, %d)", N, Cin);
     GroupDst gd = {};
     gd.n = G;
     for (int g = 0; g < G; ++g) {

@@ -423,7 +423,7 @@ __global__ void pack_weight_t_kernel(const float* __restrict__ w, const int* __r
         const int co = chunk * 16 + cc;
         float v = 0.f;
         if (n < nk && co < Cout) {
-            const int ci = kmap ? kmap[k0 + n] : k0 + n;
+            const int ci = kmap ? kmap[k0 + n] : (k0 + n < Cin ? k0 + n : -1);      // implicit map: as pack_weight_kernel
             if (ci >= 0) v = w[(((long long)g * Cout + co) * Cin + ci) * taps + (taps - 1 - tap)];
         }
         out[idx] = v;

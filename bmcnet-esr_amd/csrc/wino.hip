@@ -449,7 +449,8 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
 //   forward  (transposed == 0): rows = output channels co (< Coutpad), K = packed input channels k (kmap[k] -> ci, < 0 = zero);
 //   data gradient w.r.t. packed source channels [k0, k0 + nk) (transposed != 0): rows = n = k - k0 (< rows_pad), K = output
 //   channels co (padded to kpad), taps mirrored: g'[ky][kx] = w[co][kmap[k0 + n]][2 - ky][2 - kx].
-// out[g][K chunk][xi][nu][row][16], the 4 quads of a row XOR-swizzled with (row >> 2) & 3 (the kernel's LDS image).
+// out[g][K chunk][xi][nu][row][16], the 4 quads of a row XOR-swizzled with swz(row) = {0, 2, 3, 1}[(row >> 2) & 3] (the kernel's
+// LDS image).
 __global__ void pack_wino_kernel(const float* __restrict__ w, const int* __restrict__ kmap, int G, int Cout, int Cin, int kpad,
                                  int rows_pad, int transposed, int k0, int nk, float* __restrict__ out) {
     const long long total = (long long)G * (kpad / CK) * rows_pad * CK;
@@ -465,7 +466,7 @@ __global__ void pack_wino_kernel(const float* __restrict__ w, const int* __restr
         for (int i = 0; i < 9; ++i) gt[i / 3][i % 3] = 0.f;
         int co, ci;
         if (!transposed) { co = row; ci = kmap ? kmap[k] : (k < Cin ? k : -1); }
-        else { co = k; ci = row < nk ? (kmap ? kmap[k0 + row] : k0 + row) : -1; }
+        else { co = k; ci = row < nk ? (kmap ? kmap[k0 + row] : (k0 + row < Cin ? k0 + row : -1)) : -1; }
         if (co < Cout && ci >= 0) {
             const float* p = w + (((long long)g * Cout + co) * Cin + ci) * 9;
 #pragma unroll

@@ -750,7 +750,7 @@ __global__ void pack_wino4_kernel(const float* __restrict__ w, const int* __rest
         for (int i = 0; i < 9; ++i) gt[i / 3][i % 3] = 0.0;
         int co, ci;
         if (!transposed) { co = row; ci = kmap ? kmap[k] : (k < Cin ? k : -1); }
-        else { co = k; ci = row < nk ? (kmap ? kmap[k0 + row] : k0 + row) : -1; }
+        else { co = k; ci = row < nk ? (kmap ? kmap[k0 + row] : (k0 + row < Cin ? k0 + row : -1)) : -1; }
         if (co < Cout && ci >= 0) {
             const float* p = w + (((long long)g * Cout + co) * Cin + ci) * 9;
 #pragma unroll

@@ -144,7 +144,9 @@ int bmc_encode_raw_events(const short* xs, const short* ys, const double* ps, co
  * -> MFMA staging layout [G][Kpad/16][taps][Coutpad][16] where packed input
  * channel k holds reference input channel kmap[k] (or zero when kmap[k] < 0).
  * transpose != 0 builds the data-gradient operator instead: output channels =
- * packed k (Kpad rounded up to Coutpad_t), reduction over Cout, taps mirrored. */
+ * packed k (Kpad rounded up to Coutpad_t), reduction over Cout, taps mirrored.
+ * kmap: DEVICE array of Kpad ints (bmc_pack_weight*) or at least k0 + nk ints (the transposed packs), every entry < Cin;
+ * kmap NULL is the implicit map k -> k for k < Cin and -1 (zero) for k >= Cin, in every pack below, forward and transposed. */
 int bmc_pack_weight(const float* w, const int* kmap, int G, int Cout, int Cin, int taps,
                     int Kpad, int Coutpad, float* out, bmc_stream_t s);
 int bmc_pack_weight_t(const float* w, const int* kmap, int G, int Cout, int Cin, int taps,
@@ -162,7 +164,8 @@ int bmc_split_weight(const float* packed, void* out, long long nsteps, int Coutp
 
 /* Conv weights [G][Cout][Cin][3][3] -> the TRANSFORMED weights U = G g G^T of Winograd's F(2x2, 3x3) minimal filtering
  * (16 values per (co, ci) pair instead of 9), in the streaming order of bmc_conv with math = BMC_MATH_FP32_WINO:
- * [G][Kpad/16][4 (xi)][4 (nu)][Coutpad][16], quads of a 16-float row XOR-swizzled with (row >> 2) & 3.
+ * [G][Kpad/16][4 (xi)][4 (nu)][Coutpad][16]; the four 4-float quads of a 16-float row are XOR-swizzled: quad q of row r is stored
+ * at quad q ^ SWZ[(r >> 2) & 3] with SWZ = {0, 2, 3, 1} (csrc/dma_ring.h::swz, the kernels' conflict-free LDS image).
  *   transposed == 0: rows = output channels (Coutpad: multiple of 128), K = packed input channels through kmap (as
  *                    bmc_pack_weight);  w_group_stride of the launch = Kpad * Coutpad * 16 floats;
  *   transposed != 0: the data-gradient operator w.r.t. packed source channels [k0, k0 + nk): rows = those channels (padded
@@ -250,7 +253,9 @@ int bmc_pgemm(const bmc_pgemm_args_t* host_args, bmc_stream_t s);
  * k-steps (pixel pairs) of each pixel tile are cut into.  1: 4 row blocks x 2 column blocks; 2 (taps = 9, N <= 32): 4 row blocks
  * x 2 shares; 4 (taps = 9, M <= 32): 2 column blocks x 4 shares.  The shares are summed in a fixed order inside the workgroup. */
 int bmc_pgemm_wave_map(int taps, int M, int N);
-/* slabs -> dW[Cout][Cin][taps] (nn.Conv2d layout) through kmap; beta 0/1 = overwrite/accumulate */
+/* slabs -> dW[Cout][Cin][taps] (nn.Conv2d layout) through kmap; beta 0/1 = overwrite/accumulate.  kmap: DEVICE array of N ints,
+ * slab column n goes to weight column kmap[n] (< Cin; < 0: the column is dropped); columns no entry names are not written.
+ * kmap NULL: column n goes to weight column n, which REQUIRES N <= Cin (checked). */
 int bmc_pgemm_reduce_weight(const float* slabs, int nsplit, int G, int taps, int M, int N, const int* kmap,
                             int Cin, float* dw, int accumulate, const float* bias_slabs /* or NULL */,
                             float* db /* [G][M] or NULL */, bmc_stream_t s);
