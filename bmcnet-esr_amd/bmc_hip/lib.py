@@ -145,6 +145,9 @@ _head_mse_bwd = _sig("bmc_head_mse_bwd", [_p, _p, _p, _ll, _p, _i, _i, _i, _i, _
 _group_sum = _sig("bmc_group_sum", [_p, _i, _ll, _p, _p])
 _bicubic_fwd = _sig("bmc_bicubic_resize_fwd", [_p, _ll, _i, _i, _i, _i, _p, _p])
 _bicubic_bwd = _sig("bmc_bicubic_resize_bwd", [_p, _ll, _i, _i, _i, _i, _p, _p])
+_head_resize_mse_fwd = _sig("bmc_head_resize_mse_fwd", [_p, _i, _i, _i, _i, _i, _p, _ll, _ll, _ll, _ll, _p, _ll, _i, _i, _p, _p, _p,
+                                                        _p, _p])
+_head_resize_mse_bwd = _sig("bmc_head_resize_mse_bwd", [_p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p])
 _chain_fwd = _sig("bmc_chain_fwd", [C.POINTER(ChainFwdArgs), _p])
 _chain_bwd = _sig("bmc_chain_bwd", [C.POINTER(ChainBwdArgs), _p])
 _chain_affine = _sig("bmc_chain_affine_grads", [_p, _p, _p, _p, _p, _i, _p, _p, _p, _p, _i, _p])
@@ -182,7 +185,8 @@ EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_event
            "bmc_conv_wino_rows", "bmc_slot_stage", "bmc_slot_commit", "bmc_slot_metrics", "bmc_slot_encode", "bmc_slot_emit",
            "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes", "bmc_slot_emit_clocked", "bmc_slot_hot_update",
            "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_slot_voxel", "bmc_seq_encode", "bmc_adam_step",
-           "bmc_adam_step_capturable", "bmc_adam_grad_sq", "bmc_adam_step_clipped", "bmc_adam_step_clipped_capturable"]
+           "bmc_adam_step_capturable", "bmc_adam_grad_sq", "bmc_adam_step_clipped", "bmc_adam_step_clipped_capturable",
+           "bmc_head_resize_mse_fwd", "bmc_head_resize_mse_bwd"]
 
 
 def check(rc, what):

@@ -1856,6 +1856,67 @@ def head_mse(xo, base, gt, r):
     return HeadMseFn.apply(xo, base, gt, r)
 
 
+class HeadResizeMseFn(torch.autograd.Function):
+    """(pred, mse) = head + bicubic resize to the ground truth's size + nn.MSELoss (train.py:227-233) in one pass
+    (bmc_head_resize_mse_fwd): pred is bit for bit ops.head's, the resized prediction is never stored.  Saved for backward:
+    diff = resized - gt only; bmc_head_resize_mse_bwd folds its transposed resize into the pixel-unshuffle of the gradient
+    arriving from the next window.  Where no backward can follow (torch.no_grad()) diff is not allocated either."""
+
+    @staticmethod
+    def forward(ctx, xo, base, gt, r):
+        _need_gpu(xo)
+        xo = xo.contiguous()
+        B, H, W, CC = xo.shape
+        Cc = CC // (r * r)
+        if gt.dim() != 4 or tuple(gt.shape[:2]) != (B, Cc) or not gt.is_cuda or gt.dtype != torch.float32:
+            raise RuntimeError("head_resize_mse: ground truth must be a float32 GPU tensor [B, C, gh, gw] of the prediction's "
+                               "batch and channels")
+        gh, gw = int(gt.shape[2]), int(gt.shape[3])
+        if gt.stride()[1:] != (gh * gw, gw, 1):
+            gt = gt.contiguous()
+        pred = torch.empty((B, Cc, H * r, W * r), device=xo.device, dtype=torch.float32)
+        ws = torch.empty(2048, device=xo.device, dtype=torch.float32)
+        loss = torch.empty((), device=xo.device, dtype=torch.float32)
+        # forward() of a Function runs with grad mode off, so whether a backward can follow is what needs_input_grad says
+        diff = torch.empty((B, Cc, gh, gw), device=xo.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        sb, sc, sy, sx = base.stride()
+        lib.call(lib._head_resize_mse_fwd, "bmc_head_resize_mse_fwd", xo.data_ptr(), B, Cc, H, W, r, base.data_ptr(), sb, sc,
+                 sy, sx, gt.data_ptr(), gt.stride(0), gh, gw, pred.data_ptr(), diff.data_ptr() if diff is not None else None,
+                 ws.data_ptr(), loss.data_ptr(), _stream())
+        ctx.r = r
+        ctx.dims = (B, Cc, H, W, gh, gw)
+        if diff is not None:
+            ctx.save_for_backward(diff)
+        return pred, loss
+
+    @staticmethod
+    def backward(ctx, dpred, dloss):
+        (diff,) = ctx.saved_tensors
+        B, Cc, H, W, gh, gw = ctx.dims
+        r = ctx.r
+        if dpred is not None:
+            dpred = dpred.contiguous()
+        if dloss is not None:
+            dloss = dloss.contiguous()
+        dlr = torch.empty((B, H, W, Cc * r * r), device=diff.device, dtype=torch.float32)
+        lib.call(lib._head_resize_mse_bwd, "bmc_head_resize_mse_bwd", dpred.data_ptr() if dpred is not None else None,
+                 diff.data_ptr(), dloss.data_ptr() if dloss is not None else None, B, Cc, H, W, r, gh, gw, dlr.data_ptr(),
+                 _stream())
+        return dlr, None, None, None
+
+
+def head_resize_mse(xo, base, gt, r):
+    """xo NHWC [B,H,W,C r r], base [B,C,H,W] (any strides), gt [B,C,gh,gw] of any size -> (pred [B,C,rH,rW], mse)."""
+    return HeadResizeMseFn.apply(xo, base, gt, r)
+
+
+def head_loss(xo, base, gt, r):
+    """What the models' forward_loss calls: head_mse for a ground truth of the prediction's size, head_resize_mse otherwise."""
+    if tuple(gt.shape[-2:]) == (xo.shape[1] * r, xo.shape[2] * r):
+        return head_mse(xo, base, gt, r)
+    return head_resize_mse(xo, base, gt, r)
+
+
 def pixel_unshuffle_nhwc(hr, r, split=1):
     return UnshuffleFn.apply(hr, r, split)
 

@@ -20,4 +20,25 @@ __device__ __forceinline__ void cubic_taps(int dst, float scale, int& i0, float 
 }
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
+// The transposed operator as a gather (resize.hip's backward, head_resize.hip's backward):
+// weight with which output index `dst` reads input index `src_i` along one axis (sum over its clamped taps)
+__device__ __forceinline__ float axis_weight(int dst, float scale, int src_i, int n_in) {
+    int i0;
+    float w[4];
+    cubic_taps(dst, scale, i0, w);
+    float s = 0.f;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (clampi(i0 - 1 + k, 0, n_in - 1) == src_i) s += w[k];
+    return s;
+}
+// conservative range of output indices whose taps can touch input index i (the exact test is axis_weight != 0)
+__device__ __forceinline__ void out_range(int i, float scale, int n_out, int& lo, int& hi) {
+    const float inv = 1.f / scale;
+    lo = (int)floorf(((float)i - 2.f + 0.5f) * inv - 0.5f) - 1;
+    hi = (int)ceilf(((float)i + 2.f + 0.5f) * inv - 0.5f) + 1;
+    lo = lo < 0 ? 0 : lo;
+    hi = hi > n_out - 1 ? n_out - 1 : hi;
+}
+
 }  // namespace

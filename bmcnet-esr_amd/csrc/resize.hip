@@ -39,26 +39,7 @@ __global__ void bicubic_fwd_kernel(const float* __restrict__ x, long long planes
     }
 }
 
-// weight with which output index `dst` reads input index `src_i` along one axis (sum over its clamped taps)
-__device__ __forceinline__ float axis_weight(int dst, float scale, int src_i, int n_in) {
-    int i0;
-    float w[4];
-    cubic_taps(dst, scale, i0, w);
-    float s = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-        if (clampi(i0 - 1 + k, 0, n_in - 1) == src_i) s += w[k];
-    return s;
-}
-// conservative range of output indices whose taps can touch input index i (the exact test is axis_weight != 0)
-__device__ __forceinline__ void out_range(int i, float scale, int n_out, int& lo, int& hi) {
-    const float inv = 1.f / scale;
-    lo = (int)floorf(((float)i - 2.f + 0.5f) * inv - 0.5f) - 1;
-    hi = (int)ceilf(((float)i + 2.f + 0.5f) * inv - 0.5f) + 1;
-    lo = lo < 0 ? 0 : lo;
-    hi = hi > n_out - 1 ? n_out - 1 : hi;
-}
-
+// axis_weight / out_range: cubic_taps.h
 __global__ void bicubic_bwd_kernel(const float* __restrict__ gy, long long planes, int H, int W, int Ho, int Wo,
                                    float sy, float sx, float* __restrict__ gx) {
     const long long total = planes * H * W;

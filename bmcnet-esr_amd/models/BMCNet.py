@@ -219,7 +219,9 @@ class BMCNet(nn.Module):
     def forward_loss(self, x, x_h, x_h_p, x_h_n, x_o, init, gt):
         """forward() + nn.MSELoss()(prediction, gt) with the loss computed by the head kernel (one pass over the HR
         tensor forward, the loss gradient folded into the head's backward): -> (x_h, x_h_p, x_h_n, prediction, mse).
-        gt must have the prediction's size (otherwise use forward() + bicubic resize, train.py:227-231)."""
+        gt [B,2,gh,gw] may have any size: the prediction's size takes ops.head_mse; another size is the bicubic branch of
+        train.py:227-231 and takes ops.head_resize_mse (the loss is against the resized prediction, the prediction
+        returned -- the one that recurs -- is the unresized one, the same bits either way)."""
         return self.forward(x, x_h, x_h_p, x_h_n, x_o, init, _gt=gt)
 
     def forward(self, x, x_h, x_h_p, x_h_n, x_o, init, _gt=None):
@@ -239,7 +241,7 @@ class BMCNet(nn.Module):
         h3 = ops.stack_states([x_h, x_h_p, x_h_n])
         n_h, n_hp, n_hn, o = self.neuro.forward_nhwc(xin12, h3, o12, zero_state=bool(init))
         if _gt is not None:
-            pred, mse = ops.head_mse(o, x[:, :, 1], _gt, self.scale)
+            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale)
             return to_nchw(n_h), to_nchw(n_hp), to_nchw(n_hn), pred, mse
         pred = ops.head(o, x[:, :, 1], self.scale)
         return to_nchw(n_h), to_nchw(n_hp), to_nchw(n_hn), pred

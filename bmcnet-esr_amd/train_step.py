@@ -64,8 +64,10 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
     for i in range(L - seqn + 1):
         x = inp_cnt[:, i:i + seqn].transpose(1, 2)          # [B,2(pol),seqn,H,W]   (train.py:211)
         gt = gt_cnt[:, i + 1]                                # (train.py:213)
-        # nn.MSELoss on a prediction of the ground truth's size: head + loss in one kernel pass (models.*.forward_loss)
-        fused = loss_fn is F.mse_loss and hasattr(model, "forward_loss") and tuple(gt.shape[-2:]) == (scale * H, scale * W)
+        # nn.MSELoss: head + loss in one kernel pass (models.*.forward_loss), whatever the ground truth's size -- another size
+        # than the prediction's is the bicubic branch of train.py:227-231, resized inside that pass.  Any other loss_fn object
+        # (a wrapper around F.mse_loss included) selects the unfused chain below.
+        fused = loss_fn is F.mse_loss and hasattr(model, "forward_loss")
         fn = model.forward_loss if fused else model
         extra = (gt,) if fused else ()
         if init:
@@ -87,3 +89,27 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
     loss.backward()
     optimizer.step()
     return loss.detach(), mse.detach()
+
+
+def valid_step(model, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False):
+    """The body of the reference's _valid loop (train.py:479-509) for one batch: model.eval() under torch.no_grad(), the
+    windows as in bptt_step with the state carried, the window losses (nn.MSELoss, against the bicubic-resized prediction
+    where the ground truth has another size, train.py:502-506) summed through forward_loss.  No backward, no optimizer;
+    nothing of the ground truth's size is allocated.  Returns (loss, last mse); the model's training mode is restored."""
+    B, L, _, H, W = inp_cnt.shape
+    dev = inp_cnt.device
+    z = lambda c: torch.zeros(B, c, H, W, device=dev)
+    was_training = model.training
+    model.eval()
+    try:
+        with torch.no_grad():
+            loss = 0
+            state = (z(n_c), z(2 * scale * scale)) if plain else (z(n_c), z(n_c), z(n_c), z(2 * scale * scale))
+            for i in range(L - seqn + 1):
+                x = inp_cnt[:, i:i + seqn].transpose(1, 2)
+                out = model.forward_loss(x, *state, i == 0, gt_cnt[:, i + 1])
+                state, mse = tuple(out[:-1]), out[-1]
+                loss = loss + mse
+    finally:
+        model.train(was_training)
+    return loss, mse

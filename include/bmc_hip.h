@@ -451,6 +451,26 @@ int bmc_small_mm(const bmc_small_mm_args_t* host_args, bmc_stream_t s);
 int bmc_bicubic_resize_fwd(const float* x, long long planes, int H, int W, int Ho, int Wo, float* y, bmc_stream_t s);
 int bmc_bicubic_resize_bwd(const float* gy, long long planes, int H, int W, int Ho, int Wo, float* gx, bmc_stream_t s);
 
+/* Head + loss of one window whose ground truth gt [B][C][gh][gw] (contiguous planes, batch stride gt_batch_stride) is NOT of
+ * the prediction's size -- head, the resize above and nn.MSELoss (train.py:227-233, _valid :502-506) without the resized
+ * prediction or the loss gradient ever reaching memory.  xo [B,H,W,C*r*r], base with strides (sb,sc,sy,sx): as bmc_head_mse_fwd.
+ *   pred [B,C,rH,rW]   = pixel_shuffle(xo, r) + bilinear(base): bit for bit what bmc_shuffle_to_hr writes for the same operands
+ *                        (it recurs into the next window and must not depend on the loss path); one writer per element.
+ *   diff [B,C,gh,gw]   = bicubic(pred -> gh x gw) - gt, taps and summation order of bmc_bicubic_resize_fwd (the four taps of a
+ *                        row, then the rows; clamped taps); what the backward reads.  NULL = forward only: nothing is stored.
+ *   loss[0]            = sum diff^2 / (B*C*gh*gw) from per-block partial sums (partials: >= 2048 floats of workspace) added in
+ *                        a fixed order: deterministic, no atomics.
+ * Any gh, gw >= 1.  Null xo / base / gt / pred / partials / loss or a non-positive size: refused before any launch. */
+int bmc_head_resize_mse_fwd(const float* xo, int B, int C, int H, int W, int r, const float* base, long long sb, long long sc,
+                            long long sy, long long sx, const float* gt, long long gt_batch_stride, int gh, int gw, float* pred,
+                            float* diff, float* partials, float* loss, bmc_stream_t s);
+/* Its backward: dlr [B,H,W,C*r*r] = pixel_unshuffle(dpred + (2 gloss[0] / (B*C*gh*gw)) R^T diff), R^T = the transposed resize
+ * as a gather in bmc_bicubic_resize_bwd's order (deterministic, no atomics).  dpred NULL = no gradient from the next window;
+ * gloss (DEVICE scalar) NULL = no gradient from the loss: a pure permutation of dpred, diff is not read.  At least one of the
+ * two; diff is required with gloss. */
+int bmc_head_resize_mse_bwd(const float* dpred, const float* diff, const float* gloss, int B, int C, int H, int W, int r,
+                            int gh, int gw, float* dlr, bmc_stream_t s);
+
 /* ---- multi-stream inference: recording slots (bmcnet-esr_amd/infer.py::MultiStreamSR) ------------------------------
  * S <= BMC_MAX_SLOTS independent recordings run through one batched forward pass, recording r in slot s of the batch.  The
  * reference runs one recording at a time at batch 1 (infer_BMCNet.py:248-295 around the loop body :44-86).  Each call below is

@@ -1,0 +1,171 @@
+#!/usr/bin/env python3
+"""Time the loss head of a window whose ground truth is not of the prediction's size (train.py:227-231), on the GPU.
+
+Part `isolated`: forward + backward of the head and loss alone, with a gradient arriving from the next window as in a BPTT step,
+  fused    ops.head_resize_mse (bmc_head_resize_mse_fwd / _bwd)
+  unfused  the composition it replaces: ops.head -> ops.bicubic_resize -> F.mse_loss, autograd's backward of the three and its
+           add of the two gradients that reach the prediction
+at LR 31x56 -> 124x222 (EventZoom) and LR 65x87 -> 260x346 (DAVIS346), B = 4, x4.  Each timed repetition is --inner back-to-back
+calls between two device events (the launches are tens of microseconds; one call is below what a pair of events resolves).
+Part `step`: the whole train_step.bptt_step of BMCNet(4,128,5) at BASELINE configs[3]'s shape (31x56, B = 4, L = 9), in fp32 and bf16,
+  fused    ground truth 124x222, the default loss_fn
+  unfused  ground truth 124x222, the unfused chain selected through loss_fn
+  same     ground truth 124x224 (the synthetic size bench.py times)
+The variants alternate inside one process, every variant is warmed before anything is timed, a repetition ends in a device
+synchronise; reported: median and range over --reps (>= 15) repetitions, every repetition in the JSON, and fused / unfused per
+repetition (they run back to back; the launches are host-issue-bound and the host's speed changes under other people's work).
+No GPU is an error: nothing here runs on the CPU.
+
+python tools/time_head_loss.py [--part isolated|step|all] [--variants fused,unfused,same] [--reps 15] [--inner 50] [--warmup 3]
+                               [--math fp32,bf16] [--out FILE]
+For a launch count, trace one variant at a time:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/time_head_loss.py
+--part isolated --variants fused --reps 1 --inner 1 --warmup 0 --allow-few-reps   (then the same with --variants unfused).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
+import torch
+import torch.nn.functional as F
+
+ISOLATED = [("EventZoom", 31, 56, 124, 222), ("DAVIS346", 65, 87, 260, 346)]
+SCALE, B, L, N_C, N_B = 4, 4, 9, 128, 5
+
+
+def timed(fn, inner):
+    t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    t0.record()
+    for _ in range(inner):
+        fn()
+    t1.record()
+    torch.cuda.synchronize()
+    return t0.elapsed_time(t1) / inner
+
+
+def alternate(variants, reps, inner, warmup):
+    """{name: fn} -> {name: [ms per call] * reps}, one repetition of every variant in turn, after `warmup` untimed
+    repetitions of every variant (the same `inner` calls each)."""
+    for _ in range(warmup):
+        for fn in variants.values():
+            timed(fn, inner)
+    out = {k: [] for k in variants}
+    for _ in range(reps):
+        for k, fn in variants.items():
+            out[k].append(timed(fn, inner))
+    return out
+
+
+def summary(ms):
+    return {"median_ms": round(statistics.median(ms), 5), "min_ms": round(min(ms), 5), "max_ms": round(max(ms), 5), "reps": len(ms),
+            "all_ms": [round(v, 5) for v in ms]}
+
+
+def paired(tag, ms, row):
+    """fused / unfused per repetition: the two were timed back to back, so a change of the host's speed between repetitions
+    (these launches are host-issue-bound, and the host is shared) moves both and leaves the ratio."""
+    if "fused" in ms and "unfused" in ms:
+        q = [f / u for f, u in zip(ms["fused"], ms["unfused"])]
+        row["fused_over_unfused"] = {"median": round(statistics.median(q), 4), "min": round(min(q), 4), "max": round(max(q), 4)}
+        print("%s fused / unfused per repetition: %.3f  (%.3f .. %.3f)" % (tag, statistics.median(q), min(q), max(q)), flush=True)
+
+
+def isolated(dev, want, reps, inner, warmup):
+    from bmc_hip import ops
+    rows = {}
+    for name, H, W, gh, gw in ISOLATED:
+        torch.manual_seed(0)
+        xo = torch.randn(B, H, W, 2 * SCALE * SCALE, device=dev, requires_grad=True)
+        base = torch.poisson(torch.full((B, 2, 3, H, W), 0.3)).to(dev)[:, :, 1]       # frame 1 of the window, as the model passes it
+        gt = torch.poisson(torch.full((B, 2, gh, gw), 0.3)).to(dev)
+        dpred = torch.randn(B, 2, SCALE * H, SCALE * W, device=dev)
+        one = torch.ones((), device=dev)
+
+        def fused():
+            pred, mse = ops.head_resize_mse(xo, base, gt, SCALE)
+            return torch.autograd.grad([pred, mse], [xo], [dpred, one])[0]
+
+        def unfused():
+            pred = ops.head(xo, base, SCALE)
+            mse = F.mse_loss(ops.bicubic_resize(pred, (gh, gw)), gt)
+            return torch.autograd.grad([pred, mse], [xo], [dpred, one])[0]
+
+        variants = {k: f for k, f in (("fused", fused), ("unfused", unfused)) if k in want}
+        ms = alternate(variants, reps, inner, warmup)
+        rows[name] = {"shape": "LR %dx%d -> %dx%d, B=%d, x%d" % (H, W, gh, gw, B, SCALE), "inner": inner,
+                      **{k: summary(v) for k, v in ms.items()}}
+        if len(variants) == 2:                                        # the two must be the same function of their operands
+            a, b = fused(), unfused()
+            rows[name]["max_abs_grad_difference"] = float((a - b).abs().max())
+        for k, v in ms.items():
+            s = rows[name][k]
+            print("isolated %-9s %-8s %9.2f us  (%.2f .. %.2f, %d reps x %d calls)" % (name, k, s["median_ms"] * 1e3, s["min_ms"] * 1e3,
+                                                                                 s["max_ms"] * 1e3, s["reps"], inner), flush=True)
+        paired("isolated %-9s" % name, ms, rows[name])
+    return rows
+
+
+def step(dev, want, maths, reps, warmup):
+    from bmc_hip import ops
+    from models.BMCNet import BMCNet
+    from train_step import bptt_step
+    H, W = 31, 56
+    rows = {}
+    for math in maths:
+        ops.set_math(math)
+        torch.manual_seed(3407)
+        m = BMCNet(SCALE, N_C, N_B).to(dev)
+        opt = torch.optim.Adam(m.parameters(), lr=1e-4, weight_decay=1e-5, amsgrad=True)
+        inp = torch.poisson(torch.full((B, L, 2, H, W), 0.57)).to(dev)
+        gt222 = torch.poisson(torch.full((B, L, 2, 124, 222), 0.57)).to(dev)
+        gt224 = torch.poisson(torch.full((B, L, 2, 124, 224), 0.57)).to(dev)
+        wrapped = lambda a, b: F.mse_loss(a, b)
+        all_v = {"fused": lambda: bptt_step(m, opt, inp, gt222, N_C, SCALE),
+                 "unfused": lambda: bptt_step(m, opt, inp, gt222, N_C, SCALE, loss_fn=wrapped),
+                 "same": lambda: bptt_step(m, opt, inp, gt224, N_C, SCALE)}
+        variants = {k: f for k, f in all_v.items() if k in want}
+        ms = alternate(variants, reps, 1, warmup)
+        rows[math] = {"shape": "BMCNet(4,128,5) bptt_step, LR %dx%d, B=%d, L=%d, %s" % (H, W, B, L, math),
+                      **{k: summary(v) for k, v in ms.items()}}
+        for k in ms:
+            s = rows[math][k]
+            print("step %-5s %-8s %9.3f ms  (%.3f .. %.3f, %d reps)" % (math, k, s["median_ms"], s["min_ms"], s["max_ms"], s["reps"]),
+                  flush=True)
+        paired("step %-5s" % math, ms, rows[math])
+    ops.set_math("fp32")
+    return rows
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--part", choices=("isolated", "step", "all"), default="all")
+    ap.add_argument("--variants", default="fused,unfused,same")
+    ap.add_argument("--reps", type=int, default=15)
+    ap.add_argument("--inner", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--math", default="fp32,bf16")
+    ap.add_argument("--allow-few-reps", action="store_true", help="for a kernel trace: fewer than 15 repetitions, no timing claimed")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    if a.reps < 15 and not a.allow_few_reps:
+        ap.error("a timing needs at least 15 repetitions per variant (--allow-few-reps for a kernel trace)")
+    if not torch.cuda.is_available():
+        raise SystemExit("time_head_loss: no GPU -- these are GPU timings, nothing falls back to the CPU")
+    dev = torch.device("cuda:0")
+    want = set(a.variants.split(","))
+    out = {"device": torch.cuda.get_device_name(dev), "reps": a.reps, "warmup": a.warmup}
+    if a.part in ("isolated", "all"):
+        out["isolated"] = isolated(dev, want, a.reps, a.inner, a.warmup)
+    if a.part in ("step", "all"):
+        out["step"] = step(dev, want, a.math.split(","), a.reps, a.warmup)
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            json.dump(out, f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

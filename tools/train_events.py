@@ -6,11 +6,16 @@ EventTrainSet.batch's launch: the table copy and the kernel).
 A recording is an .npz of raw columns, the ones tools/multistream_infer.py --events builds synthetically (event_recording):
 lr_xs / lr_ys (int16), lr_ps (float64), lr_ts (float64, sorted), the same four with gt_, and lr_size = (H, W), gt_size = (gh, gw).
 The index tables are cut here with bmc_hip.encodings.event_window_indices (the reference's blocks: --window / --sliding).
---synthetic K makes K such recordings of --items items at --size instead (and --save DIR writes them out).
+--synthetic K makes K such recordings of --items items at --size instead (and --save DIR writes them out); --gt-size HxW gives
+them a ground truth that is not scale x LR (EventZoom: --size 31x56 --gt-size 124x222), so every window takes the bicubic
+branch of train.py:227-231 -- inside bptt_step's fused head + loss launches.
 
 python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x80] [--steps 10] [--batch 2] [--L 9] [--step-size S]
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
+                             [--gt-size HxW] [--valid-every N]
+--valid-every N: the last recording is held out of training; after every N steps train_step.valid_step (the reference's _valid
+loop: eval mode, no gradients, the same loss) runs over its sequences in order and `valid_loss`, their mean, is printed.
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
 --clip-norm X: clip the gradients by their global L2 norm.  hip: Adam(max_grad_norm=X), a norm launch and a step launch
 (csrc/optim.hip); torch: torch.nn.utils.clip_grad_norm_ in a pre-step hook, so that the two can be compared.
@@ -33,17 +38,19 @@ import torch
 from bmc_hip.encodings import event_window_indices
 from event_dataset import EventTrainSet
 from models.BMCNet import BMCNet
-from train_step import bptt_step
+from train_step import bptt_step, valid_step
 
 KEYS = ("xs", "ys", "ps", "ts")
 
 
-def synthetic_recording(items, H, W, scale, window, sliding, seed):
-    """Raw columns of about `items` items: uniform coordinates, +-1 polarities, sorted uniform timestamps."""
+def synthetic_recording(items, H, W, scale, window, sliding, seed, gt_size=None):
+    """Raw columns of about `items` items: uniform coordinates, +-1 polarities, sorted uniform timestamps.  gt_size: the
+    ground truth's (gh, gw) where it is not (scale H, scale W)."""
     rng = np.random.default_rng(seed)
     n_lr = (window - sliding) * items + 1
-    rec = {"lr_size": np.asarray([H, W]), "gt_size": np.asarray([scale * H, scale * W])}
-    for side, n, h, w in (("lr", n_lr, H, W), ("gt", scale * scale * n_lr, scale * H, scale * W)):
+    gh, gw = gt_size or (scale * H, scale * W)
+    rec = {"lr_size": np.asarray([H, W]), "gt_size": np.asarray([gh, gw])}
+    for side, n, h, w in (("lr", n_lr, H, W), ("gt", scale * scale * n_lr, gh, gw)):
         rec[side + "_xs"] = rng.integers(0, w, n).astype(np.int16)
         rec[side + "_ys"] = rng.integers(0, h, n).astype(np.int16)
         rec[side + "_ps"] = rng.choice([-1.0, 1.0], n)
@@ -83,22 +90,34 @@ def main():
     ap.add_argument("--clip-norm", type=float, default=None)
     ap.add_argument("--nonfinite", choices=("propagate", "skip"), default="propagate")
     ap.add_argument("--wall", action="store_true")
+    ap.add_argument("--gt-size", default=None, help="HxW of the synthetic recordings' ground truth (default: scale x --size)")
+    ap.add_argument("--valid-every", type=int, default=0, help="hold the last recording out and print valid_loss every N steps")
     a = ap.parse_args()
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
     dev = torch.device("cuda:0")
     H, W = (int(v) for v in a.size.split("x"))
     recs = [dict(np.load(p)) for p in a.recordings]
-    recs += [synthetic_recording(a.items, H, W, a.scale, a.window, a.sliding, a.seed + k) for k in range(a.synthetic)]
+    gt_size = tuple(int(v) for v in a.gt_size.split("x")) if a.gt_size else None
+    recs += [synthetic_recording(a.items, H, W, a.scale, a.window, a.sliding, a.seed + k, gt_size) for k in range(a.synthetic)]
     if a.save:
         os.makedirs(a.save, exist_ok=True)
         for k, r in enumerate(recs[len(a.recordings):]):
             np.savez(os.path.join(a.save, "synthetic%d.npz" % k), **r)
     ts = EventTrainSet(L=a.L, step_size=a.step_size, augment=(("Horizontal", "Vertical", "Polarity"), (0.5, 0.5, 0.5)) if a.augment else None,
                        pause=tuple(float(v) for v in a.pause.split(",")) if a.pause else None, add_noise=a.noise, window=a.window)
+    vs = None
+    if a.valid_every > 0:
+        if len(recs) < 2:
+            raise SystemExit("--valid-every holds the last recording out: give at least two")
+        vs = EventTrainSet(L=a.L, step_size=a.step_size, window=a.window)      # as recorded: no augmentation, pause or noise
+        add(vs, recs.pop(), dev, a.window, a.sliding, a.scale)
+        if len(vs) < a.batch:
+            raise SystemExit("the held-out recording gives %d sequences, fewer than one batch of %d" % (len(vs), a.batch))
     for r in recs:
         add(ts, r, dev, a.window, a.sliding, a.scale)
-    print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L))
+    print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) +
+          (", %d held-out sequences" % len(vs) if vs is not None else ""))
     random.seed(a.seed)
     torch.manual_seed(a.seed)
     m = BMCNet(a.scale, a.n_c, a.n_b).to(dev)
@@ -128,6 +147,10 @@ def main():
             rows.append(dict(step=step, epoch=epoch, sequences=idx, loss=loss, encode_ms=round(t0.elapsed_time(t1), 4)))
             print("step %d  loss %.6f  encode %.3f ms  sequences %s" % (step, loss, rows[-1]["encode_ms"], idx))
             step += 1
+            if vs is not None and step % a.valid_every == 0:
+                vl = [float(valid_step(m, *vs.batch(vidx), a.n_c, a.scale)[0]) for vidx in vs.batches(a.batch, shuffle=False)]
+                rows[-1]["valid_loss"] = sum(vl) / len(vl)
+                print("step %d  valid_loss %.6f  (%d batches)" % (step - 1, rows[-1]["valid_loss"], len(vl)))
             if step == 1:
                 torch.cuda.synchronize()
                 clock = time.perf_counter()
