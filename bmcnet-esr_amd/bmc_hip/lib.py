@@ -30,6 +30,11 @@ c_fp = C.c_void_p  # device pointers travel as integers
 class Src(C.Structure):
     _fields_ = [("ptr", C.c_void_p), ("batch_stride", C.c_longlong), ("pix_stride", C.c_int), ("nch", C.c_int),
                 ("batch_shift", C.c_int), ("batch_mod", C.c_int)]
+    # Batch segment of a convolution operand (ops.View with a second tensor): launch images b >= seg_b start seg_delta floats
+    # past where the descriptor puts image b.  Host-side attributes, NOT part of bmc_src_t: the C ABI carries them at launch
+    # level (bmc_conv_args_t::seg_b / *_seg_delta), where ops.conv_raw copies them; every other entry point takes plain operands.
+    seg_b = 0
+    seg_delta = 0
 
 
 class ConvArgs(C.Structure):
@@ -38,7 +43,8 @@ class ConvArgs(C.Structure):
                 ("out", C.c_void_p), ("out_batch_stride", C.c_longlong), ("out_pix_stride", C.c_int),
                 ("B", C.c_int), ("H", C.c_int), ("W", C.c_int), ("Cout", C.c_int), ("Coutpad", C.c_int),
                 ("taps", C.c_int), ("relu", C.c_int), ("residual", Src), ("mask", Src), ("accumulate", C.c_int),
-                ("math", C.c_int)]
+                ("math", C.c_int), ("seg_b", C.c_int), ("src_seg_delta", C.c_longlong * MAX_SRC),
+                ("residual_seg_delta", C.c_longlong), ("mask_seg_delta", C.c_longlong)]
 
 
 class PgemmArgs(C.Structure):

@@ -67,22 +67,46 @@ class View:
     """Channel/batch window of an NHWC tensor used as a convolution operand.
 
     Launch batch b reads batch ((b + shift) % mod) + b0 of `t`, channels
-    [c0, c0 + nch)."""
-    __slots__ = ("t", "c0", "nch", "shift", "mod", "b0")
+    [c0, c0 + nch).
 
-    def __init__(self, t, c0=0, nch=None, shift=0, mod=None, b0=0):
+    Batch segment (t2, seg): launch batches b < seg read batch b of `t`, batches b >= seg read batch b - seg of `t2`, a second
+    tensor of the same H, W and channel count, through the same channel window -- one launch over the images of two tensors
+    without a torch.cat (the Winograd kernels; no shift / mod / b0 with it).  Both tensors must be alive at the launch and are
+    used on the launching stream only."""
+    __slots__ = ("t", "c0", "nch", "shift", "mod", "b0", "t2", "seg")
+
+    def __init__(self, t, c0=0, nch=None, shift=0, mod=None, b0=0, t2=None, seg=None):
         self.t = t
         self.c0 = c0
         self.nch = t.shape[3] - c0 if nch is None else nch
         self.shift = shift
         self.mod = mod
         self.b0 = b0
+        if (t2 is None) != (seg is None):
+            raise ValueError("View: a batch segment needs both the second tensor and the split point")
+        if t2 is not None:
+            if shift or mod is not None or b0:
+                raise ValueError("View: a batch segment cannot be combined with shift / mod / b0")
+            if tuple(t2.shape[1:]) != tuple(t.shape[1:]) or t2.dtype != t.dtype or t2.device != t.device:
+                raise ValueError("View: the two tensors of a batch segment must agree in H, W, channels, dtype and device "
+                                 "(%s / %s)" % (tuple(t.shape), tuple(t2.shape)))
+            if not 1 <= seg <= t.shape[0]:
+                raise ValueError("View: split point %d outside the first tensor's %d images" % (seg, t.shape[0]))
+        self.t2 = t2
+        self.seg = seg
 
     def meta(self):
+        if self.t2 is not None:
+            raise ValueError("View: a batch-segmented view has no single-tensor description")
         return (self.c0, self.nch, self.shift, self.mod, self.b0)
 
+    def src(self, launch_b) -> lib.Src:
+        return _src(self.t, self.c0, self.nch, self.shift, self.mod, self.b0, launch_b, self.t2, self.seg)
 
-def _src(t: torch.Tensor, c0, nch, shift, mod, b0, launch_b) -> lib.Src:
+
+def _src(t: torch.Tensor, c0, nch, shift, mod, b0, launch_b, t2=None, seg=None) -> lib.Src:
+    """Operand descriptor: launch image b starts at ptr + 4 * (((b + batch_shift) % batch_mod) * batch_stride) bytes, plus
+    4 * seg_delta for b >= seg_b > 0 (batch segment: the images of t2; seg_delta is signed, t2 may lie below t)."""
     Bt, H, W, Ct = t.shape
     s = lib.Src()
     s.ptr = t.data_ptr() + 4 * (b0 * H * W * Ct + c0)
@@ -91,7 +115,26 @@ def _src(t: torch.Tensor, c0, nch, shift, mod, b0, launch_b) -> lib.Src:
     s.nch = nch
     s.batch_shift = shift
     s.batch_mod = mod if mod is not None else max(launch_b, 1) + shift
+    if t2 is not None:
+        if shift or mod is not None or b0:
+            raise ValueError("_src: a batch segment cannot be combined with shift / mod / b0")
+        if tuple(t2.shape[1:]) != (H, W, Ct) or not (t.is_contiguous() and t2.is_contiguous()):
+            raise ValueError("_src: the tensors of a batch segment must be contiguous and agree in H, W and channels")
+        if not (1 <= seg < launch_b and seg <= Bt and launch_b - seg <= t2.shape[0]):
+            raise ValueError("_src: split point %d of a launch of %d images over tensors of %d and %d images" %
+                             (seg, launch_b, Bt, t2.shape[0]))
+        d = t2.data_ptr() - (t.data_ptr() + 4 * seg * s.batch_stride)      # (the channel window c0 is in both bases)
+        if d % 16:
+            raise ValueError("_src: the tensors of a batch segment must be 16 bytes apart modulo 16")
+        s.seg_b, s.seg_delta = seg, d // 4
     return s
+
+
+def _plain_srcs(what, *srcs):
+    """Entry points other than bmc_conv know no batch segment (it is not part of bmc_src_t): refuse one here, never ignore it."""
+    for x in srcs:
+        if x is not None and x.seg_b:
+            raise ValueError("%s: a batch-segmented operand is served by convolution launches only" % what)
 
 
 def _null_src() -> lib.Src:
@@ -298,7 +341,7 @@ WINO4_MIN_TILES = int(os.environ.get("BMC_WINO4_MIN_TILES", 300))    # workgroup
 # exact kernels regardless (tests).
 _EXACT_ZERO = threading.local()          # .n: nesting depth of exact_zero_inputs on this thread, .d: of dense_inputs
 DENSE_FLOOR = 1e-5                       # ~10x the largest residue measured on event-count inputs (1.1e-6)
-_DENSE = {}                              # id(bias) -> (weakref, version, min |b|, max b)
+_DENSE = {}                              # id(bias) -> (weakref, version, min |b|, max b, max |b|)
 
 
 class exact_zero_inputs:
@@ -328,17 +371,18 @@ def _dense_cached(b):
 
 
 def prime_bias_dense(biases):
-    """min |b| and max b of every bias whose entry is missing or stale: one stack of device reductions, ONE host read.
+    """min |b|, max b and max |b| of every bias whose entry is missing or stale: one stack of device reductions, ONE host read.
     (Not while a HIP graph is being captured: entries missing then read as "not dense" -- the exact kernels.)"""
     need = [b for b in biases if b is not None and _dense_cached(b) is None]
     if not need or not need[0].is_cuda or torch.cuda.is_current_stream_capturing():
         return
-    vals = torch.stack([torch.stack((b.detach().abs().min(), b.detach().max())) for b in need]).tolist()
+    # (aminmax: min |b| and max |b| in the one reduction that min |b| alone took)
+    vals = torch.stack([torch.stack((*torch.aminmax(b.detach().abs()), b.detach().max())) for b in need]).tolist()
     if len(_DENSE) > 512:
         for k in [k for k, v in _DENSE.items() if v[0]() is None]:
             del _DENSE[k]
-    for b, (mn, mx) in zip(need, vals):
-        _DENSE[id(b)] = (weakref.ref(b), b._version, mn, mx)
+    for b, (mn, amx, mx) in zip(need, vals):
+        _DENSE[id(b)] = (weakref.ref(b), b._version, mn, mx, amx)
 
 
 def _bias_entry(b):
@@ -358,6 +402,17 @@ def bias_dense(b):
         return all(bias_dense(x) for x in b)
     hit = _bias_entry(b)
     return hit is not None and hit[2] >= DENSE_FLOOR
+
+
+def bias_zero(b):
+    """Is every element of this bias (every bias of a tuple) exactly zero -- as initialize_weights leaves it?  Unknown: no."""
+    if isinstance(b, (tuple, list)):
+        prime_bias_dense(b)
+        return all(bias_zero(x) for x in b)
+    if b is None:
+        return False
+    hit = _bias_entry(b)
+    return hit is not None and len(hit) > 4 and hit[4] == 0.0
 
 
 def bias_positive(b):
@@ -498,6 +553,14 @@ def conv_raw(srcs: List[lib.Src], wpacked, w_group_stride, bias, bias_group_stri
     a.nsrc = len(srcs)
     for i, s in enumerate(srcs):
         a.src[i] = s
+        a.src_seg_delta[i] = s.seg_delta
+    # batch segments (View with a second tensor): one split point per launch, a delta per operand
+    segs = {x.seg_b for x in list(srcs) + [residual, mask] if x is not None and x.seg_b}
+    if len(segs) > 1:
+        raise ValueError("conv_raw: the segmented operands of a launch must share one split point (%s)" % sorted(segs))
+    a.seg_b = segs.pop() if segs else 0
+    a.residual_seg_delta = residual.seg_delta if residual is not None else 0
+    a.mask_seg_delta = mask.seg_delta if mask is not None else 0
     a.wpacked = wpacked.data_ptr()
     a.bias = bias.data_ptr() if bias is not None else None
     a.w_group_stride = w_group_stride * MATH // 2 if MATH else w_group_stride   # floats, or dwords of bf16 planes
@@ -544,6 +607,7 @@ TAP_SPLIT_TILES = 8
 def pgemm_raw(a_src: lib.Src, srcs: List[lib.Src], B, H, W, taps, bpg, M, N, device, flops=0.0, want_bias=False):
     """Returns (slabs, nsplit, G), or with want_bias (slabs, nsplit, G, bias_slabs): per-workgroup column sums of the
     A operand (bias-gradient partials) for bmc_pgemm_reduce_weight."""
+    _plain_srcs("pgemm_raw", a_src, *srcs)
     G = B // bpg
     mpad, npad = round_up(M, 32), round_up(N, 32)
     if taps == 9:       # one 8-wave workgroup per CU, 64 columns per workgroup (32 in the bf16x6 mode: pgemm_bf.hip)
@@ -817,6 +881,7 @@ def _wgrad_wino(a_srcs, x_srcs, Bs, H, W, spec, dev, w_param, b_param, w_shape, 
     """One launch + reduction over the (dY, x) pairs of `a_srcs` / `x_srcs` with Bs[i] images each: one pair takes the
     single-use entry points (F(4x4) where wgrad_wino4_ok), several (a merged launch: uses of one sink weight) bmc_wgrad_wino_multi."""
     n, Bt = len(a_srcs), sum(Bs)
+    _plain_srcs("wgrad_wino", *a_srcs, *x_srcs)
     if n == 1 and wgrad_wino4_ok(Bt, H, W):
         f_ns, f_main, f_red, nm, npos, kind = lib._ww4_nsplit, lib._ww4, lib._ww4_red, "bmc_wgrad_wino4", 36, "wgrad_wino4<9>"
     else:
@@ -905,6 +970,7 @@ def wgrad_route(spec, a_src, x_srcs, metas, taps, Cout, G, w_param, b_param=None
 
 def _batch_window(s: lib.Src, b0, nb) -> lib.Src:
     """Launch batches [b0, b0 + nb) of an operand without a batch map, as an operand of its own."""
+    _plain_srcs("_batch_window", s)
     w = lib.Src()
     w.ptr, w.batch_stride, w.pix_stride, w.nch = s.ptr + 4 * b0 * s.batch_stride, s.batch_stride, s.pix_stride, s.nch
     w.batch_shift, w.batch_mod = 0, max(nb, 1)
@@ -951,29 +1017,35 @@ def wgrad(a_src, x_srcs, spec, B, H, W, taps, Cout, dev, w_param, b_param, G=1, 
 # the two convolution launchers: every node's forward-style and data-gradient launches
 # --------------------------------------------------------------------------
 def _launch_stride(srcs, Co, residual, mask):
-    # the widest pixel stride the launch addresses (wino_ok: the Winograd launchers' 32-bit offsets)
+    # the widest pixel stride the launch addresses (wino_ok: the Winograd launchers' 32-bit offsets); both tensors of a
+    # batch-segmented operand have the descriptor's strides (_src checks it), so the descriptor speaks for the two
     return max([x.pix_stride for x in srcs] + [Co] + [x.pix_stride for x in (residual, mask) if x is not None])
 
 
 def conv_launch(srcs, w4, spec, owner, bias, out, B, relu=False, residual=None, mask=None, bpg=None, accumulate=False,
-                out_b0=0, rule=None):
+                out_b0=0, rule=None, wn=None):
     """Forward-style launch: out[out_b0 : out_b0+B] = epi(conv(cat(srcs)) + bias), w4 [G,Cout,Cin,taps] (owner: the parameter
-    it was derived from, the pack-cache key, or None).  The kernel is decided ONCE here (wino_ok) for the pack and the launch."""
+    it was derived from, the pack-cache key, or None).  The kernel is decided ONCE here (wino_ok) for the pack and the launch
+    -- or by the caller (wn: ResPairFn, whose launches take the kernel that each block's own launch would)."""
     G, Cout, Cin, taps = w4.shape
     _, H, W, Co = out.shape
-    wn = wino_ok(B, H, W, Cout, taps, fwd=not accumulate and mask is None, stride=_launch_stride(srcs, Co, residual, mask), rule=rule)
+    if wn is None:
+        wn = wino_ok(B, H, W, Cout, taps, fwd=not accumulate and mask is None, stride=_launch_stride(srcs, Co, residual, mask), rule=rule)
     wp = _packed_weight(w4, spec, owner, wino=wn)
     conv_raw(srcs, wp, spec.kpad * taps * coutpad(Cout), bias, Cout if bias is not None else 0,
              out.data_ptr() + 4 * out_b0 * H * W * Co, H * W * Co, Co, B, H, W, Cout, taps, relu=relu, residual=residual,
              bpg=bpg, accumulate=accumulate, mask=mask, flops=2.0 * B * H * W * Cout * taps * spec.kreal, wino=wn)
 
 
-def dgrad_launch(g_src, w4, spec, src_index, owner, out, B, residual=None, mask=None, bpg=None, accumulate=False, out_b0=0, out_c0=0):
-    """Data gradient w.r.t. source `src_index` of the conv with weights w4: out[out_b0:+B, :, :, out_c0:+nch] (=|+=) conv^T(g)."""
+def dgrad_launch(g_src, w4, spec, src_index, owner, out, B, residual=None, mask=None, bpg=None, accumulate=False, out_b0=0, out_c0=0,
+                 wn=None):
+    """Data gradient w.r.t. source `src_index` of the conv with weights w4: out[out_b0:+B, :, :, out_c0:+nch] (=|+=) conv^T(g).
+    (wn: the kernel, where the caller decided it -- as conv_launch.)"""
     G, Cout, Cin, taps = w4.shape
     _, H, W, Co = out.shape
     nch = spec.nch[src_index]
-    wn = wino_ok(B, H, W, nch, taps, stride=_launch_stride([g_src], Co, residual, mask))
+    if wn is None:
+        wn = wino_ok(B, H, W, nch, taps, stride=_launch_stride([g_src], Co, residual, mask))
     wt = _packed_weight_t(w4, spec, src_index, owner, wino=wn)
     conv_raw([g_src], wt, round_up(Cout, CK) * taps * coutpad(nch), None, 0, out.data_ptr() + 4 * (out_b0 * H * W * Co + out_c0),
              H * W * Co, Co, B, H, W, nch, taps, residual=residual, mask=mask, bpg=bpg, accumulate=accumulate,
@@ -1615,6 +1687,138 @@ class ResBlockFn(torch.autograd.Function):
 
 def res_block(x, w1, b1, w2, b2, spec, out=None):
     return ResBlockFn.apply(x, w1, b1, w2, b2, spec, out)
+
+
+# --------------------------------------------------------------------------
+# Two independent residual blocks of one shape (ParallelBlk.conv1 on x12, conv1_st on xst12; models/BMCNet.py:19-22) as ONE
+# node at large frames: each layer is one launch over the 2 * B2 images of both blocks with two weight groups, the two inputs
+# read in place through a batch-segmented operand (View(t, t2=, seg=)).  A 180x240 image is 169 workgroup tiles of the F(4x4)
+# kernel: 8 images are 5.28 tiles per CU (6 rounds, 12 % of the launch idle), 16 images 10.56 (11 rounds) -- a round saved per
+# pair of launches, and nothing else runs beside a forward pass to fill the tail.  Bit for bit what the two ResBlockFn nodes give:
+# a workgroup tile lies inside one image and is computed by the same kernel from the same packed weights in the same order.
+# --------------------------------------------------------------------------
+PAIR_RES = os.environ.get("BMC_PAIR_RES", "1") != "0"      # 0: the two ResBlockFn nodes (A/B runs)
+PAIR_RES_DGRAD = os.environ.get("BMC_PAIR_RES", "1") != "fwd"      # "fwd": pair the forward launches only (A/B runs)
+# One block's launch must have this many F(4x4) workgroup tiles (16 tiles of 4x4 pixels: four rounds of 256 CUs) for the pair to
+# share launches.  Measured where it is switched on: 8 images of 180x240 (1352 tiles), -52 us per pair.  Smaller launches keep one
+# launch per block: tests/test_gpu_r6.py fixes the forward launch count of a batch-1 window at 180x240 (338 tiles per block: 46
+# launches, at least 40 of them F(4x4)), and what the pair would gain there (3 rounds instead of 2 + 2) is not measured.
+PAIR_RES_MIN_TILES = int(os.environ.get("BMC_PAIR_RES_MIN_TILES", 1024))
+
+
+def pair_res(B2, H, W):
+    return PAIR_RES and B2 * ((((H + 3) // 4) * ((W + 3) // 4) + 15) // 16) >= PAIR_RES_MIN_TILES
+
+
+def _pair_route(B2, H, W, Cn, taps, rules=None, fwd=False):
+    """The kernel (2 / 4) of a launch that serves both blocks, or 0 for one launch each.  Decided with ONE block's batch and each
+    block's own bias, exactly as its own launch would be: pairing never changes which kernel a size takes.  0 where the two
+    blocks would take different kernels, where that kernel is the direct one (it knows no batch segment), and for forward F(2x2)
+    launches with a non-zero bias: that kernel starts a one-group launch's accumulators from the bias and adds a grouped
+    launch's bias at the end -- the same sum in another order; and below pair_res' size."""
+    if not pair_res(B2, H, W):
+        return 0
+    if rules is None:
+        return wino_ok(B2, H, W, Cn, taps, stride=Cn)
+    ra, rb = (wino_ok(B2, H, W, Cn, taps, fwd=fwd, stride=Cn, rule=r) for r in rules)
+    if ra != rb or (ra == 2 and not bias_zero(rules)):
+        return 0
+    return ra
+
+
+class ResPairFn(torch.autograd.Function):
+    """y = [res_block_a(xa); res_block_b(xb)] as one [2 * B2, H, W, C] tensor (the buffer bie.Stack2Fn declared)."""
+
+    @staticmethod
+    def forward(ctx, xa, xb, w1a, b1a, w2a, b2a, w1b, b1b, w2b, b2b, spec):
+        _need_gpu(xa)
+        B2, H, W, Cn = xa.shape
+        taps = w1a.shape[-1] * w1a.shape[-2]
+        xad, xbd = xa.detach(), xb.detach()
+        det = lambda ws: torch.stack([w.detach() for w in ws])
+        t = torch.empty((2 * B2, H, W, Cn), device=xa.device, dtype=xa.dtype)
+        y = torch.empty_like(t)
+        sa, sb = _src(xad, 0, Cn, 0, None, 0, B2), _src(xbd, 0, Cn, 0, None, 0, B2)
+        xseg = None
+        # layer 1: t = relu(conv1(x)), layer 2: y = x + conv2(t)
+        for (wa, ba, wb, bb), dst, relu in (((w1a, b1a, w1b, b1b), t, True), ((w2a, b2a, w2b, b2b), y, False)):
+            wn = _pair_route(B2, H, W, Cn, taps, (ba, bb), fwd=True)
+            src_a = sa if relu else _src(t, 0, Cn, 0, None, 0, B2)
+            src_b = sb if relu else _src(t, 0, Cn, 0, None, B2, B2)
+            if wn:
+                if xseg is None:
+                    xseg = _src(xad, 0, Cn, 0, None, 0, 2 * B2, xbd, B2)
+                wst = stacked((wa, wb), lambda: det((wa, wb)), "stack")
+                bst = stacked((ba, bb), lambda: det((ba, bb)), "stack")
+                conv_launch([xseg if relu else _src(t, 0, Cn, 0, None, 0, 2 * B2)], wst.reshape(2, Cn, Cn, taps), spec, wst, bst, dst,
+                            2 * B2, relu=relu, residual=None if relu else xseg, bpg=B2, wn=wn)
+            else:
+                conv_launch([src_a], wa.detach().reshape(1, Cn, Cn, taps), spec, wa, ba.detach(), dst, B2, relu=relu,
+                            residual=None if relu else sa, rule=ba)
+                conv_launch([src_b], wb.detach().reshape(1, Cn, Cn, taps), spec, wb, bb.detach(), dst, B2, relu=relu,
+                            residual=None if relu else sb, out_b0=B2, rule=bb)
+        ctx.save_for_backward(xa, xb, t, w1a, w2a, w1b, w2b)
+        ctx.spec, ctx.taps = spec, taps
+        ctx.params = ((w1a, b1a, w2a, b2a), (w1b, b1b, w2b, b2b))
+        ctx.gslots = (getattr(xa, "_bmc_gslot", None), getattr(xb, "_bmc_gslot", None))
+        ctx.window = current_window()
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        xa, xb, t, w1a, w2a, w1b, w2b = ctx.saved_tensors
+        spec, taps = ctx.spec, ctx.taps
+        g = g.contiguous()
+        B, H, W, Cn = g.shape
+        B2 = B // 2
+        need = ctx.needs_input_grad
+        half = lambda ten, i: _src(ten, 0, Cn, 0, None, i * B2, B2)
+        # block b first, as autograd runs the two ResBlockFn nodes (the later node's backward comes first)
+        order = (1, 0)
+        for i in order:         # conv2's weight gradients: (g, t), each block's half through a b0 view
+            p_w1, p_b1, p_w2, p_b2 = ctx.params[i]
+            if need[2 + 4 * i + 2] or need[2 + 4 * i + 3]:
+                r = wgrad(half(g, i), [half(t, i)], spec, B2, H, W, taps, Cn, g.device, p_w2, p_b2, keep=(g, t), window=ctx.window,
+                          merge_pgemm=True)
+            else:
+                r = (None, None)
+            if i:
+                dwb2 = r
+            else:
+                dwa2 = r
+        # d(pre-activation of conv1) = ReLU'(t) * conv2^T(g), mask epilogue: one two-group launch over both blocks (g, t and dt are
+        # single buffers: no segment)
+        dt = torch.empty_like(g)
+        wn = _pair_route(B2, H, W, Cn, taps) if PAIR_RES_DGRAD else 0
+        if wn:
+            wst = stacked((w2a, w2b), lambda: torch.stack([w2a.detach(), w2b.detach()]), "stack")
+            dgrad_launch(_src(g, 0, Cn, 0, None, 0, B), wst.reshape(2, Cn, Cn, taps), spec, 0, wst, dt, B, mask=_src(t, 0, Cn, 0, None, 0, B),
+                         bpg=B2, wn=wn)
+        else:
+            for i, w2 in ((1, w2b), (0, w2a)):
+                dgrad_launch(half(g, i), w2.detach().reshape(1, Cn, Cn, taps), spec, 0, w2, dt, B2, mask=half(t, i), out_b0=i * B2)
+        res = {}
+        for i in order:
+            p_w1, p_b1, p_w2, p_b2 = ctx.params[i]
+            x, w1 = (xa, w1a) if i == 0 else (xb, w1b)
+            if need[2 + 4 * i] or need[2 + 4 * i + 1]:
+                dw1 = wgrad(half(dt, i), [_src(x, 0, Cn, 0, None, 0, B2)], spec, B2, H, W, taps, Cn, g.device, p_w1, p_b1, keep=(dt, x),
+                            window=ctx.window, merge_pgemm=True)
+            else:
+                dw1 = (None, None)
+            dx = None
+            if need[i]:       # dx = conv1^T(dt) + g (skip path): residual epilogue, into the block's own gradient slot
+                gi = g[i * B2:(i + 1) * B2]
+                dx = grad_slot(ctx.gslots[i], gi)
+                dgrad_launch(half(dt, i), w1.detach().reshape(1, Cn, Cn, taps), spec, 0, w1, dx, B2, residual=half(g, i))
+            res[i] = (dx, dw1)
+        (dxa, dwa1), (dxb, dwb1) = res[0], res[1]
+        return (dxa, dxb, dwa1[0], dwa1[1], dwa2[0], dwa2[1], dwb1[0], dwb1[1], dwb2[0], dwb2[1], None)
+
+
+def res_pair(xa, xb, blk_a, blk_b, spec):
+    """blk_a / blk_b: (w1, b1, w2, b2) of the two blocks."""
+    return ResPairFn.apply(xa.contiguous(), xb.contiguous(), *blk_a, *blk_b, spec)
 
 
 # --------------------------------------------------------------------------

@@ -431,6 +431,37 @@ extern "C" int bmc_conv(const bmc_conv_args_t* h, bmc_stream_t stream) {
     k.out = h->out; k.out_batch_stride = h->out_batch_stride; k.out_pix_stride = h->out_pix_stride;
     k.B = h->B; k.H = h->H; k.W = h->W; k.Cout = h->Cout; k.Coutpad = h->Coutpad;
     k.relu = h->relu; k.residual = to_dev(h->residual); k.mask = to_dev(h->mask); k.accumulate = h->accumulate;
+    // batch segment: images b >= seg_b of an operand come from a second tensor of the same geometry (same strides: the per-image
+    // 32-bit offset limits the launchers check below hold for both tensors alike)
+    k.seg_b = h->seg_b;
+    for (int i = 0; i < BMC_MAX_SRC; ++i) k.seg_delta[i] = i < h->nsrc ? h->src_seg_delta[i] : 0;
+    k.res_seg_delta = h->residual.ptr ? h->residual_seg_delta : 0;
+    k.mask_seg_delta = h->mask.ptr ? h->mask_seg_delta : 0;
+    {
+        auto seg_ok = [&](const bmc_src_t& s, long long delta, long long given, const char* what) -> bool {
+            if (given != delta) { bmc_set_error("bmc_conv: segment delta on an absent operand (%s)", what); return false; }
+            if (delta == 0) return true;
+            if (h->seg_b < 1 || h->seg_b >= h->B) {
+                bmc_set_error("bmc_conv: %s has a segment delta but seg_b=%d is not in [1, B=%d)", what, h->seg_b, h->B);
+                return false;
+            }
+            if (s.batch_shift != 0 || s.batch_mod < h->B) {
+                bmc_set_error("bmc_conv: %s: a batch shift / modulus (%d / %d) cannot be combined with a batch segment", what,
+                              s.batch_shift, s.batch_mod);
+                return false;
+            }
+            if (delta % 4 != 0) { bmc_set_error("bmc_conv: %s: the segment's second tensor must be 16-byte aligned", what); return false; }
+            return true;
+        };
+        for (int i = 0; i < BMC_MAX_SRC; ++i)
+            if (!seg_ok(h->src[i < h->nsrc ? i : 0], k.seg_delta[i], h->src_seg_delta[i], "a source")) return -1;
+        if (!seg_ok(h->residual, k.res_seg_delta, h->residual_seg_delta, "the residual")) return -1;
+        if (!seg_ok(h->mask, k.mask_seg_delta, h->mask_seg_delta, "the mask")) return -1;
+        BMC_CHECK_ARG(h->seg_b == 0 || (h->seg_b >= 1 && h->seg_b < h->B), "bmc_conv: seg_b=%d is not in [1, B=%d)", h->seg_b, h->B);
+        // (the direct, bf16-plane and 1x1 kernels know no segment: refused here, in front of all of them)
+        BMC_CHECK_ARG(!conv_has_segment(k) || h->math == BMC_MATH_FP32_WINO || h->math == BMC_MATH_FP32_WINO4,
+                      "bmc_conv: batch segments are served by the Winograd kernels only (math %d given)", h->math);
+    }
     // tile shape: 8x16 px x 128 ch when that fills the chip; small problems get 4-row tiles and/or 64-channel tiles so
     // that 2-4x as many workgroups share the work (a workgroup's K loop is serial: its latency is the launch's latency)
     const int cus = bmc_num_cus();

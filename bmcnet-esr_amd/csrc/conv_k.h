@@ -19,7 +19,38 @@ struct ConvK {
     SrcDev mask;
     int accumulate;
     int tiles_x, tiles_y, ntn, nchunks, ntiles;
+    // batch segment (bmc_conv_args_t::seg_b): launch images b >= seg_b of an operand start seg_delta floats past where its
+    // descriptor puts them (the second tensor of the operand); all deltas are 0 in a launch without one, so `b >= seg_b ? delta : 0`
+    // needs no "is there a segment" test.  Launch-level fields, not SrcDev's: the descriptor stays 32 bytes for every other kernel.
+    int seg_b;
+    long long seg_delta[BMC_MAX_SRC];
+    long long res_seg_delta, mask_seg_delta;
 };
+// The kernels read the segment from an LDS table of BMC_SEG_TAB long longs, where they use it (once per image and operand): the
+// sources' deltas by source number, then the residual's, the mask's, and seg_b.  Read from the argument block, the five scalars of
+// the epilogue operands were loaded at the kernel's entry and spilled across the chunk loops (wino4_conv_kernel: 109 -> 122 SGPRs).
+constexpr int BMC_SEG_RES = BMC_MAX_SRC, BMC_SEG_MASK = BMC_MAX_SRC + 1, BMC_SEG_B = BMC_MAX_SRC + 2, BMC_SEG_TAB = BMC_MAX_SRC + 3;
+// Kernel prologue, beside BMC_LOAD_SRC_TABLE (and a macro for the same reason).  Threads 32.. : no lane shared with that copy.
+#define BMC_LOAD_SEG_TABLE(segtab, a, tid)                                       \
+    do {                                                                         \
+        _Pragma("unroll") for (int i_ = 0; i_ < BMC_MAX_SRC; ++i_)               \
+            if ((tid) == 32 + i_) (segtab)[i_] = (a).seg_delta[i_];              \
+        if ((tid) == 32 + BMC_SEG_RES) (segtab)[BMC_SEG_RES] = (a).res_seg_delta;    \
+        if ((tid) == 32 + BMC_SEG_MASK) (segtab)[BMC_SEG_MASK] = (a).mask_seg_delta; \
+        if ((tid) == 32 + BMC_SEG_B) (segtab)[BMC_SEG_B] = (a).seg_b;            \
+    } while (0)
+// floats to add to the base of launch image b of operand `which` (b and the table are wave-uniform: the result is scalar)
+__device__ __forceinline__ long long seg_off(const long long* segtab, int which, int b) {
+    const unsigned long long dv = (unsigned long long)segtab[which];
+    const int seg_b = __builtin_amdgcn_readfirstlane((int)segtab[BMC_SEG_B]);
+    const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)dv), hi = __builtin_amdgcn_readfirstlane((unsigned)(dv >> 32));
+    return b >= seg_b ? (long long)(((unsigned long long)hi << 32) | lo) : 0ll;
+}
+// the same left in vector registers, for a caller that makes the whole address there and takes its first lane afterwards
+__device__ __forceinline__ long long seg_off_v(const long long* segtab, int which, int b) {
+    return b >= (int)segtab[BMC_SEG_B] ? segtab[which] : 0ll;
+}
+static inline bool conv_has_segment(const ConvK& k) { return k.seg_b != 0; }
 
 // Kernel prologue: accumulator start values for the BN channels of a tile -- the bias when it is the same for every tile of
 // the launch (one weight group, one channel tile: the usual case; returns true then), zeros otherwise.  A tile's

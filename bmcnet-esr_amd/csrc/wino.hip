@@ -74,18 +74,20 @@ __device__ __forceinline__ f32x4 sub4w(f32x4 a, f32x4 b) {
 template <int TH>
 __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
     constexpr int HHT = TH + 2, NTB = TH / 4;
-    __shared__ __attribute__((aligned(16))) float lds[2 * XBUFA + NWR * WSTAGE + 2 * VSTAGE + BMC_MAX_SRC * 8 + BN];
+    __shared__ __attribute__((aligned(16))) float lds[2 * XBUFA + NWR * WSTAGE + 2 * VSTAGE + BMC_MAX_SRC * 8 + BN + BMC_SEG_TAB * 2];
     float* const Xb = lds;
     float* const Wb = lds + 2 * XBUFA;
     float* const Vb = lds + 2 * XBUFA + NWR * WSTAGE;
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 2 * XBUFA + NWR * WSTAGE + 2 * VSTAGE);
     float* const init_lds = lds + 2 * XBUFA + NWR * WSTAGE + 2 * VSTAGE + BMC_MAX_SRC * 8;
+    long long* const segtab = reinterpret_cast<long long*>(init_lds + BN);      // the launch's batch segment (conv_k.h)
     const unsigned wb_lds = lds_addr(Wb), xb_lds = lds_addr(Xb);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lj = lane & 15, lk = lane >> 4;
     const bool bias_pre = bias_start_values(init_lds, a, BN, tid);
     BMC_LOAD_SRC_TABLE(tab, a, tid);
+    BMC_LOAD_SEG_TABLE(segtab, a, tid);
     __syncthreads();
 
     const TileWalk tw = tile_walk(a.ntiles);      // persistent workgroups
@@ -116,7 +118,10 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
     int sb_s = -1, sb_b = -1;         // (source, image) sbase belongs to
     auto src_select = [&]() {
         const SrcDev S = tab[s_idx];
-        if (s_idx != sb_s || xl_it.b != sb_b) { sbase = src_batch_ptr(S, xl_it.b); sb_s = s_idx; sb_b = xl_it.b; }
+        if (s_idx != sb_s || xl_it.b != sb_b) {
+            sbase = src_batch_ptr(S, xl_it.b) + seg_off(segtab, s_idx, xl_it.b);
+            sb_s = s_idx; sb_b = xl_it.b;
+        }
         snch = S.nch;
         const int y0 = xl_it.ty * TH, x0 = xl_it.tx * TW;
         xzm = 0;
@@ -325,8 +330,8 @@ __global__ __launch_bounds__(512, 2) void wino2_conv_kernel(const ConvK a) {
         float* const outb = a.out + (long long)it.b * a.out_batch_stride;
         if (it.b != ep_b) {
             ep_b = it.b;
-            ep_res = a.residual.ptr ? src_batch_ptr(a.residual, it.b) : nullptr;
-            ep_mask = a.mask.ptr ? src_batch_ptr(a.mask, it.b) : nullptr;
+            ep_res = a.residual.ptr ? src_batch_ptr(a.residual, it.b) + seg_off(segtab, BMC_SEG_RES, it.b) : nullptr;
+            ep_mask = a.mask.ptr ? src_batch_ptr(a.mask, it.b) + seg_off(segtab, BMC_SEG_MASK, it.b) : nullptr;
         }
         const float* const resb = ep_res;
         const float* const maskb = ep_mask;

@@ -124,7 +124,8 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     float* const Xb = lds;
     float* const Vb = lds + 2 * XBUFA;
     int* const xtab = reinterpret_cast<int*>(lds + 2 * XBUFA + 2 * VBUF);          // [NLW][PPW][64]
-    const SrcDev* const tab = reinterpret_cast<const SrcDev*>(lds + 2 * XBUFA + 2 * VBUF + NLW * PPW * 64);
+    const SrcDev* const tab = reinterpret_cast<const SrcDev*>(lds + 2 * XBUFA + 2 * VBUF + NLW * PPW * 64);      // sources, residual, mask
+    const long long* const segtab = reinterpret_cast<const long long*>(tab + BMC_MAX_SRC + 2);     // the launch's batch segment (conv_k.h)
     const unsigned xb_lds = lds_addr(Xb);
 
     const int lane = threadIdx.x & 63;
@@ -149,10 +150,14 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     auto tiles_x_now = [&]() __attribute__((always_inline)) { return opaque(a.tiles_x); };
     // (the same for the other per-tile divisions by launch constants: weight / bias group of an image, batch maps of the epilogue operands)
     auto group_of = [&](int b) __attribute__((always_inline)) { return a.batch_per_group >= a.B ? 0 : b / opaque(a.batch_per_group); };
-    auto batch_ptr = [&](const SrcDev& sd, int b) __attribute__((always_inline)) {
-        int bs = b + sd.batch_shift;
-        if (sd.batch_mod > 0) bs %= opaque(sd.batch_mod);
-        return sd.ptr + (long long)bs * sd.batch_stride;
+    // Base of image b of an epilogue operand (which = BMC_SEG_RES / BMC_SEG_MASK): descriptor and batch segment from the LDS tables
+    // like the loaders' sources, the address made in vector registers and its first lane taken -- read from the argument block,
+    // the descriptors and the segment's scalars were what the allocator spilled across the chunk loops (109 -> 113 SGPRs; so: 106)
+    auto batch_ptr = [&](int which, int b) __attribute__((always_inline)) {
+        const SrcDev S = tab[which];
+        const unsigned long long pv = reinterpret_cast<unsigned long long>(src_batch_ptr(S, b) + seg_off_v(segtab, which, b));
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pv), hi = __builtin_amdgcn_readfirstlane((unsigned)(pv >> 32));
+        return reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
     };
     const W4Tile stp = decode(t_stride);
     auto advance = [&](W4Tile it) { return tile_advance(it, stp, a.ntn, wpi); };
@@ -210,7 +215,8 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
     };
     auto src_select = [&]() {
         const SrcDev S = tab[s_idx];
-        const unsigned long long pv = reinterpret_cast<unsigned long long>(src_batch_ptr(S, xl_it.b));
+        // (batch segment: images from seg_b on start a delta further on, in a second tensor)
+        const unsigned long long pv = reinterpret_cast<unsigned long long>(src_batch_ptr(S, xl_it.b) + seg_off_v(segtab, s_idx, xl_it.b));
         const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)pv), hi = __builtin_amdgcn_readfirstlane((unsigned)(pv >> 32));
         sbase = reinterpret_cast<const float*>(((unsigned long long)hi << 32) | lo);
         snch = __builtin_amdgcn_readfirstlane(S.nch);
@@ -563,8 +569,8 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
         float* const outb = a.out + (long long)it.b * a.out_batch_stride;
         if (it.b != ep_b) {
             ep_b = it.b;
-            ep_res = a.residual.ptr ? batch_ptr(a.residual, it.b) : nullptr;
-            ep_mask = a.mask.ptr ? batch_ptr(a.mask, it.b) : nullptr;
+            ep_res = a.residual.ptr ? batch_ptr(BMC_SEG_RES, it.b) : nullptr;
+            ep_mask = a.mask.ptr ? batch_ptr(BMC_SEG_MASK, it.b) : nullptr;
         }
         const float* const resb = ep_res;
         const float* const maskb = ep_mask;
@@ -718,10 +724,13 @@ __device__ __forceinline__ void wino4_body(const ConvK& a, float* lds, const int
 }
 
 __global__ __launch_bounds__(512, 2) void wino4_conv_kernel(const ConvK a) {
-    __shared__ __attribute__((aligned(16))) float lds[2 * XBUFA + 2 * VBUF + NLW * PPW * 64 + BMC_MAX_SRC * 8];
+    __shared__ __attribute__((aligned(16))) float lds[2 * XBUFA + 2 * VBUF + NLW * PPW * 64 + (BMC_MAX_SRC + 2) * 8 + BMC_SEG_TAB * 2];
     SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 2 * XBUFA + 2 * VBUF + NLW * PPW * 64);
     const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     BMC_LOAD_SRC_TABLE(tab, a, tid);
+    if (tid == BMC_SEG_RES) tab[BMC_SEG_RES] = a.residual;
+    if (tid == BMC_SEG_MASK) tab[BMC_SEG_MASK] = a.mask;
+    BMC_LOAD_SEG_TABLE(reinterpret_cast<long long*>(tab + BMC_MAX_SRC + 2), a, tid);
     __syncthreads();
 
     const TileWalk tw = tile_walk(a.ntiles);

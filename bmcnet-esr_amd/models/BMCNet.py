@@ -67,10 +67,10 @@ class ParallelBlk(nn.Module):
             t = ops.conv_groups([View(xx)], (c1.conv1.weight, c2.conv1.weight), (c1.conv1.bias, c2.conv1.bias), c1._spec, relu=True)
             return ops.conv_groups([View(t)], (c1.conv2.weight, c2.conv2.weight), (c1.conv2.bias, c2.conv2.bias), c1._spec,
                                    residual=View(xx))
-        slot = ops.OutSlot(torch.empty((2 * B2,) + tuple(x12.shape[1:]), device=x12.device, dtype=x12.dtype), 0)
-        a = self.conv1.forward_nhwc(x12, out=slot)
-        b = self.conv1_st.forward_nhwc(xst12, out=ops.OutSlot(slot.t, B2))
-        return bie.Stack2Fn.apply(a, b, slot)
+        # large frames: one node, each layer ONE two-group launch that reads the two inputs in place (ops.ResPairFn)
+        c1, c2 = self.conv1, self.conv1_st
+        return ops.res_pair(x12, xst12, (c1.conv1.weight, c1.conv1.bias, c1.conv2.weight, c1.conv2.bias),
+                            (c2.conv1.weight, c2.conv1.bias, c2.conv2.weight, c2.conv2.bias), c1._spec)
 
     def forward(self, x_1, x_2, x_s, x_1_st, x_2_st, x_1_s_st, x_2_s_st):
         B = x_1.shape[0]

@@ -221,6 +221,17 @@ typedef struct bmc_conv_args {
                                    BMC_MATH_FP32_WINO (4): taps = 9, Coutpad % 128 == 0, wpacked from bmc_pack_weight_wino: fp32 MFMA
                                    on Winograd-transformed operands, F(2x2, 3x3): 16 instead of 36 multiplies per 2x2 output
                                    tile and channel pair, fp32 throughout (error vs float64 ~1.5x the direct fp32 kernel's) */
+    /* Batch segment: one launch whose images come from TWO tensors of the same H, W, pixel stride and channel window (two
+     * independent, equally shaped convolutions with their own weight groups sharing a launch without a torch.cat of the inputs).
+     * seg_b = 0: none (every delta below must be 0).  1 <= seg_b < B: an operand with a non-zero delta reads launch images
+     * b < seg_b from its descriptor as usual and images b >= seg_b at the address of image b PLUS its delta (floats, signed):
+     * delta = (second tensor's image 0) - (descriptor's image seg_b).  Such an operand has batch_shift 0 and no wrapping
+     * modulus (batch_mod >= B); operands with delta 0 are ordinary ones.  Served by the Winograd kernels (math 4, 5); every
+     * other kernel of bmc_conv refuses a segmented launch. */
+    int seg_b;
+    long long src_seg_delta[BMC_MAX_SRC];
+    long long residual_seg_delta;
+    long long mask_seg_delta;
 } bmc_conv_args_t;
 int bmc_conv(const bmc_conv_args_t* host_args, bmc_stream_t s);
 
