@@ -439,4 +439,37 @@ def encode_sequences(table, B, L, lr_size, gt_size, out=None):
     return out[0], out[1]
 
 
+def encode_sequence_crops(table, crops, B, L, crop, scale, out=None):
+    """encode_sequences for patches: a DEVICE table of B bmc_seq_sample_t entries and, parallel to it, a DEVICE table of B
+    bmc_seq_crop_t entries (uint8 tensors; event_dataset.SEQ_SAMPLE_DTYPE / SEQ_CROP_DTYPE) -> (inp_cnt [B,L,2,h,w], gt_cnt
+    [B,L,2,scale*h,scale*w]) float32, crop = (h, w): ONE bmc_seq_encode_crop launch on the current stream (include/bmc_hip.h
+    "sequence encoder for training").  Every sample is cut out of its own full frames, which may differ in size.  The ranges
+    and the crops are trusted: event_dataset.EventTrainSet checks them.  out: (inp_cnt, gt_cnt) to write into."""
+    B, L, scale = int(B), int(L), int(scale)
+    h, w = (int(v) for v in crop)
+    for name, t in (("table", table), ("crop table", crops)):
+        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.uint8 and t.is_contiguous()):
+            raise RuntimeError("encode_sequence_crops: the %s must be a contiguous uint8 tensor on the MI355X "
+                               "(no CPU fallback in this build)" % name)
+    if B < 1 or table.numel() < B * SEQ_SAMPLE_BYTES or table.data_ptr() % 8:
+        raise ValueError("encode_sequence_crops: the table holds fewer than %d entries of %d bytes (8-byte aligned)"
+                         % (B, SEQ_SAMPLE_BYTES))
+    if crops.numel() < B * SEQ_CROP_BYTES or crops.data_ptr() % 8 or crops.device != table.device:
+        raise ValueError("encode_sequence_crops: the crop table holds fewer than %d entries of %d bytes (8-byte aligned, on the "
+                         "table's device)" % (B, SEQ_CROP_BYTES))
+    shapes = ((B, L, 2, h, w), (B, L, 2, scale * h, scale * w))
+    if out is None:
+        if min(shapes[0] + shapes[1]) < 1:
+            raise ValueError("encode_sequence_crops: B, L, crop and scale must be positive")
+        out = tuple(torch.empty(s, dtype=torch.float32, device=table.device) for s in shapes)
+    for t, s in zip(out, shapes):
+        if not (t.is_cuda and t.device == table.device and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == s):
+            raise ValueError("encode_sequence_crops: out must be contiguous float32 tensors %s and %s on the table's device" % shapes)
+    with torch.cuda.device(table.device):
+        lib.call(lib._seq_encode_crop, "bmc_seq_encode_crop", table.data_ptr(), crops.data_ptr(), B, L, h, w, scale,
+                 out[0].data_ptr(), out[1].data_ptr(), ops._stream())
+    return out[0], out[1]
+
+
 SEQ_SAMPLE_BYTES = 1112          # sizeof(bmc_seq_sample_t)
+SEQ_CROP_BYTES = 24              # sizeof(bmc_seq_crop_t)

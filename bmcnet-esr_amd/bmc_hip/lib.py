@@ -171,6 +171,7 @@ _hot_pixel_mask = _sig("bmc_hot_pixel_mask", [_p, _i, _i, _i, _i, _f, _p, _p, _p
 _slot_render = _sig("bmc_slot_render", [_p, _p, _i, _i, _i, _i, _i, _p, _p])
 _slot_voxel = _sig("bmc_slot_voxel", [_p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p])
 _seq_encode = _sig("bmc_seq_encode", [_p, _i, _i, _i, _i, _i, _i, _p, _p, _p])
+_seq_encode_crop = _sig("bmc_seq_encode_crop", [_p, _p, _i, _i, _i, _i, _i, _p, _p, _p])
 _adam_step = _sig("bmc_adam_step", [_p, _i, AdamHyper, _p, _p])
 _adam_step_cap = _sig("bmc_adam_step_capturable", [_p, _i, AdamHyper, _p, _p, _p])
 _adam_grad_sq = _sig("bmc_adam_grad_sq", [_p, _i, _p, _p])
@@ -190,7 +191,8 @@ EXPORTS = ["bmc_version", "bmc_last_error", "bmc_events_to_channels", "bmc_event
            "bmc_wgrad_wino4_nsplit", "bmc_wgrad_wino4", "bmc_wgrad_wino4_reduce", "bmc_wgrad_wino_multi", "bmc_ptr_table",
            "bmc_conv_wino_rows", "bmc_slot_stage", "bmc_slot_commit", "bmc_slot_metrics", "bmc_slot_encode", "bmc_slot_emit",
            "bmc_slot_emit_timed", "bmc_slot_emit_timed_scratch_bytes", "bmc_slot_emit_clocked", "bmc_slot_hot_update",
-           "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_slot_voxel", "bmc_seq_encode", "bmc_adam_step",
+           "bmc_slot_encode_filtered", "bmc_hot_pixel_mask", "bmc_slot_render", "bmc_slot_voxel", "bmc_seq_encode", "bmc_seq_encode_crop",
+           "bmc_adam_step",
            "bmc_adam_step_capturable", "bmc_adam_grad_sq", "bmc_adam_step_clipped", "bmc_adam_step_clipped_capturable",
            "bmc_head_resize_mse_fwd", "bmc_head_resize_mse_bwd"]
 

@@ -10,35 +10,50 @@
 // for another; counts are integers, so the result does not depend on the order of the atomics.  The differences: a frame per
 // item for the ground truth too, the flips applied to the int16 coordinates and the polarity before the range test, a
 // paused LR item that scans nothing, and the sample's noise events counted (unflipped) on top of every LR item that runs.
+//
+// bmc_seq_encode_crop (EventTrainSet(crop=...)) is the same body writing one patch per sample: the output frame is the patch,
+// the flips and the range test keep the sample's own full frame, and an event counts when its full-frame pixel lies in the band.
 #include "bmc_common.h"
 #include "slot_encode_k.h"
 
 namespace {
 
-// One event of a frame fh x fw whose row test has passed (or whose band holds row fh-1, `last`): the arithmetic of
-// slot_encode_body, on the flipped values.
-__device__ __forceinline__ void seq_count(unsigned* cnt, int x, bool yin, int row, float p, int fh, int fw, int r0, int rows, int n) {
+// One event of a full frame fh x fw whose row test has passed (or whose band holds row fh-1 and column 0, `last`): the arithmetic
+// of slot_encode_body, on the flipped values.  The band starts at full-frame row f0 and, with CROP, at column `left`; it has
+// `rows` rows of pw pixels.
+template <bool CROP>
+__device__ __forceinline__ void seq_count(unsigned* cnt, int x, bool yin, int row, float p, int fh, int fw, int f0, int rows, int n,
+                                          int left, int pw) {
     const bool oob = !yin || x < 0 || x >= fw;
     const bool neg = p < 0.f;
     if (!(neg || (!oob && p > 0.f))) return;                         // an out-of-range positive (or p = 0) counts nowhere
-    const int rr = (oob ? fh - 1 : row) - r0;                        // reset coordinates (0, 0) -> [fh-1][0] of channel 1
+    const int rr = (oob ? fh - 1 : row) - f0;                        // reset coordinates (0, 0) -> [fh-1][0] of channel 1
     if (rr < 0 || rr >= rows) return;
-    atomicAdd(&cnt[(neg ? n : 0) + rr * fw + (oob ? 0 : x)], (unsigned)(p * p));
+    int c = oob ? 0 : x;
+    if constexpr (CROP) {
+        c -= left;
+        if (c < 0 || c >= pw) return;
+    }
+    atomicAdd(&cnt[(neg ? n : 0) + rr * pw + c], (unsigned)(p * p));
 }
 
+// The body of both kernels.  (H, W), (gh, gw): the OUTPUT frames -- the recording's with CROP false, the LR and HR patch with
+// CROP, where the sample's own frame sizes and the patch origin come from crops[s].
 // grid (L * (nb_lr + nb_gt), B): blockIdx.y is the sample, blockIdx.x a (frame, band): first the L * nb_lr LR bands, then the
 // L * nb_gt HR bands
-__global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* __restrict__ table, int L, int H, int W, int gh, int gw,
-                                                        int r_lr, int nb_lr, int r_gt, int nb_gt, float* __restrict__ inp_cnt,
-                                                        float* __restrict__ gt_cnt) {
-    __shared__ unsigned cnt[ENC_LDS];
+template <bool CROP>
+__device__ __forceinline__ void seq_encode_body(unsigned* cnt, const bmc_seq_sample_t* __restrict__ table,
+                                                const bmc_seq_crop_t* __restrict__ crops, int L, int H, int W, int gh, int gw, int scale,
+                                                int r_lr, int nb_lr, int r_gt, int nb_gt, float* __restrict__ inp_cnt,
+                                                float* __restrict__ gt_cnt) {
     const int s = blockIdx.y, tid = threadIdx.x;
     const bmc_seq_sample_t* const ent = table + s;
     const unsigned fl = gld<unsigned>(&ent->flips);
     const short *xs, *ys;
     const double* ps;
     long long e0, e1;
-    int fh, fw, r0, rows, n_noise = 0;
+    int ph, pw, r0, rows, n_noise = 0;                               // the output frame and the band inside it
+    int fh, fw, top = 0, left = 0;                                   // the full frame and where the output frame lies in it
     float* out;
     const int b = blockIdx.x;
     if (b < L * nb_lr) {
@@ -48,8 +63,12 @@ __global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* 
         ps = gld<const double*>(&ent->lr_ps);
         e0 = gld<long long>(&ent->lr_range[t][0]);
         e1 = gld<long long>(&ent->lr_range[t][1]);
-        fh = H; fw = W; r0 = (b - t * nb_lr) * r_lr; rows = r_lr;
+        ph = H; pw = W; r0 = (b - t * nb_lr) * r_lr; rows = r_lr;
         out = inp_cnt + ((long long)s * L + t) * 2 * H * W;
+        if constexpr (CROP) {
+            fh = gld<int>(&crops[s].H); fw = gld<int>(&crops[s].W);
+            top = gld<int>(&crops[s].top); left = gld<int>(&crops[s].left);
+        }
         if ((gld<unsigned>(&ent->paused) >> t) & 1u) e1 = e0;        // a paused item: no events, no noise -> all +0.0
         else n_noise = gld<int>(&ent->n_noise);
     } else {
@@ -59,14 +78,21 @@ __global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* 
         ps = gld<const double*>(&ent->gt_ps);
         e0 = gld<long long>(&ent->gt_range[t][0]);
         e1 = gld<long long>(&ent->gt_range[t][1]);
-        fh = gh; fw = gw; r0 = (b - L * nb_lr - t * nb_gt) * r_gt; rows = r_gt;
+        ph = gh; pw = gw; r0 = (b - L * nb_lr - t * nb_gt) * r_gt; rows = r_gt;
         out = gt_cnt + ((long long)s * L + t) * 2 * gh * gw;
+        if constexpr (CROP) {
+            fh = gld<int>(&crops[s].gh); fw = gld<int>(&crops[s].gw);
+            top = scale * gld<int>(&crops[s].top); left = scale * gld<int>(&crops[s].left);
+        }
     }
-    if (r0 + rows > fh) rows = fh - r0;
-    const int n = rows * fw;                                         // counters per channel: 2 * n <= ENC_LDS
+    if constexpr (!CROP) { fh = ph; fw = pw; }
+    if (r0 + rows > ph) rows = ph - r0;
+    const int n = rows * pw;                                         // counters per channel: 2 * n <= ENC_LDS
     for (int i = tid; i < 2 * n; i += ET) cnt[i] = 0u;
     __syncthreads();
-    const bool last = r0 + rows == fh;                               // row fh-1 is where out-of-range negatives land
+    const int f0 = top + r0;                                         // the band's first row in the full frame
+    // [fh-1][0] is where out-of-range negatives land: only a band that holds it reads xs / ps of every event
+    const bool last = f0 + rows == fh && left == 0;
     const bool fx = fl & 1u, fy = fl & 2u, fp = fl & 4u;
     for (long long e = e0 + tid; e < e1; e += ET) {
         // augment_event's float64 flip and event_formatting's float32 cast are exact on int16 values: integers throughout
@@ -74,12 +100,12 @@ __global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* 
         if (fy) y = fh - 1 - y;
         const bool yin = y >= 0 && y < fh;
         const int row = fh - 1 - (yin ? y : 0);
-        if (!(last || (yin && row >= r0 && row < r0 + rows))) continue;
+        if (!(last || (yin && row >= f0 && row < f0 + rows))) continue;
         int x = (int)gld<short>(xs + e);
         if (fx) x = fw - 1 - x;
         float p = (float)gld<double>(ps + e);
         if (fp) p = -p;
-        seq_count(cnt, x, yin, row, p, fh, fw, r0, rows, n);
+        seq_count<CROP>(cnt, x, yin, row, p, fh, fw, f0, rows, n, left, pw);
     }
     if (n_noise > 0) {                                               // concatenated AFTER augment_event: never flipped
         const short* const nx = gld<const short*>(&ent->noise_xs);
@@ -89,17 +115,33 @@ __global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* 
             const int y = (int)gld<short>(ny + e);
             const bool yin = y >= 0 && y < fh;
             const int row = fh - 1 - (yin ? y : 0);
-            if (!(last || (yin && row >= r0 && row < r0 + rows))) continue;
-            seq_count(cnt, (int)gld<short>(nx + e), yin, row, (float)gld<signed char>(np + e), fh, fw, r0, rows, n);
+            if (!(last || (yin && row >= f0 && row < f0 + rows))) continue;
+            seq_count<CROP>(cnt, (int)gld<short>(nx + e), yin, row, (float)gld<signed char>(np + e), fh, fw, f0, rows, n, left, pw);
         }
     }
     __syncthreads();
-    float* const o0 = out + (long long)r0 * fw;
-    float* const o1 = o0 + (long long)fh * fw;
+    float* const o0 = out + (long long)r0 * pw;
+    float* const o1 = o0 + (long long)ph * pw;
     for (int i = tid; i < n; i += ET) {
         gst<float>(o0 + i, (float)cnt[i]);
         gst<float>(o1 + i, (float)cnt[n + i]);
     }
+}
+
+__global__ __launch_bounds__(ET) void seq_encode_kernel(const bmc_seq_sample_t* __restrict__ table, int L, int H, int W, int gh, int gw,
+                                                        int r_lr, int nb_lr, int r_gt, int nb_gt, float* __restrict__ inp_cnt,
+                                                        float* __restrict__ gt_cnt) {
+    __shared__ unsigned cnt[ENC_LDS];
+    seq_encode_body<false>(cnt, table, nullptr, L, H, W, gh, gw, 1, r_lr, nb_lr, r_gt, nb_gt, inp_cnt, gt_cnt);
+}
+
+// h x w: the LR patch; the HR patch is scale times it
+__global__ __launch_bounds__(ET) void seq_encode_crop_kernel(const bmc_seq_sample_t* __restrict__ table,
+                                                             const bmc_seq_crop_t* __restrict__ crops, int L, int h, int w, int scale,
+                                                             int r_lr, int nb_lr, int r_gt, int nb_gt, float* __restrict__ inp_cnt,
+                                                             float* __restrict__ gt_cnt) {
+    __shared__ unsigned cnt[ENC_LDS];
+    seq_encode_body<true>(cnt, table, crops, L, h, w, scale * h, scale * w, scale, r_lr, nb_lr, r_gt, nb_gt, inp_cnt, gt_cnt);
 }
 
 }  // namespace
@@ -116,5 +158,21 @@ extern "C" int bmc_seq_encode(const bmc_seq_sample_t* table, int B, int L, int H
     hipLaunchKernelGGL(seq_encode_kernel, dim3((unsigned)gx, B), dim3(ET), 0, (hipStream_t)s, table, L, H, W, gh, gw, g.r_lr, g.nb_lr,
                        g.r_gt, g.nb_gt, inp_cnt, gt_cnt);
     BMC_CHECK_LAUNCH("bmc_seq_encode");
+    return 0;
+}
+
+extern "C" int bmc_seq_encode_crop(const bmc_seq_sample_t* table, const bmc_seq_crop_t* crops, int B, int L, int h, int w, int scale,
+                                   float* inp_cnt, float* gt_cnt, bmc_stream_t s) {
+    BMC_CHECK_ARG(table && crops && inp_cnt && gt_cnt && B >= 1 && B <= 65535 && L >= 2 && L <= BMC_SEQ_MAX_ITEMS && h > 0 && w > 0 &&
+                      scale >= 1,
+                  "bmc_seq_encode_crop: bad arguments");
+    BMC_CHECK_ARG(2ll * scale * w <= ENC_LDS, "bmc_seq_encode_crop: HR patches wider than %d pixels are not supported", ENC_LDS / 2);
+    BMC_CHECK_ARG((long long)scale * h < (1ll << 31), "bmc_seq_encode_crop: the HR patch is too tall");
+    const SlotEncodeGrid g = slot_encode_grid(h, w, scale * h, scale * w);
+    const long long gx = (long long)L * (g.nb_lr + g.nb_gt);
+    BMC_CHECK_ARG(gx < (1ll << 31), "bmc_seq_encode_crop: too many bands");
+    hipLaunchKernelGGL(seq_encode_crop_kernel, dim3((unsigned)gx, B), dim3(ET), 0, (hipStream_t)s, table, crops, L, h, w, scale, g.r_lr,
+                       g.nb_lr, g.r_gt, g.nb_gt, inp_cnt, gt_cnt);
+    BMC_CHECK_LAUNCH("bmc_seq_encode_crop");
     return 0;
 }

@@ -7,6 +7,11 @@ launch (csrc/seq_encode.hip, bmc_seq_encode; include/bmc_hip.h "sequence encoder
 collate layout train_step.bptt_step takes.  The host part is the reference's sequence sampling, bit for bit: the step size,
 the seed and the flips one sequence shares, the pause chain, the noise events (sequence_plan, noise_events).
 
+EventTrainSet(crop=(h, w), scale=s) trains on patches: every sample is an h x w LR patch and its s*h x s*w HR patch, cut at one
+origin per sequence (crop_origin, drawn from the sequence's own seed; batch(origins=...) overrides it) out of the recording's own
+frames, so recordings of different sensor sizes share a batch.  The crop happens in the encoder (bmc_seq_encode_crop): still one
+table copy and one launch per batch, which writes only the patches -- bit for bit the slices of the full-frame batch.
+
 Out of scope, as in event_window_indices: HDF5 reading, the reference's 'time' / 'frame' modes, the hot-pixel filter (the
 reference never applies it in training)."""
 import random
@@ -23,7 +28,8 @@ SEQ_SAMPLE_DTYPE = np.dtype({
     "formats": ["<u8"] * 9 + ["<i4", "<u4", "<u4", ("<i8", (MAX_ITEMS, 2)), ("<i8", (MAX_ITEMS, 2))],
     "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 88, 88 + 16 * MAX_ITEMS],
     "itemsize": 88 + 32 * MAX_ITEMS})          # bmc_seq_sample_t
-ENCODE_LAUNCHES = 0      # bmc_seq_encode launches of this process
+SEQ_CROP_DTYPE = np.dtype([(k, "<i4") for k in ("H", "W", "gh", "gw", "top", "left")])          # bmc_seq_crop_t
+ENCODE_LAUNCHES = 0      # bmc_seq_encode and bmc_seq_encode_crop launches of this process
 
 
 def _augment_args(augment):
@@ -123,6 +129,27 @@ def noise_events(window, lr_size, seed, noise_level):
     return xs, ys, ps
 
 
+def _max_origin(lr_size, gt_size, crop, scale):
+    """The largest (top, left) at which the LR patch and its HR patch both lie inside their frames; negative: it does not fit."""
+    (H, W), (gh, gw), (h, w) = lr_size, gt_size, crop
+    return min(H - h, (gh - scale * h) // scale), min(W - w, (gw - scale * w) // scale)
+
+
+def crop_origin(seed, lr_size, gt_size, crop, scale):
+    """The patch origin (top, left), in LR image rows / columns, of a sequence with this seed (sequence_plan's): g =
+    random.Random(seed); top = g.randint(0, max_top); left = g.randint(0, max_left), in that order, with max_top = min(H - h,
+    (gh - scale * h) // scale) and max_left likewise -- the HR patch scale * (top, left) .. scale * (top + h, left + w) must fit
+    a ground truth that may be smaller than scale x LR.  A generator of its own: the caller's rng is not touched, so cropping
+    changes no plan."""
+    lr_size, gt_size, crop = (tuple(int(v) for v in t) for t in (lr_size, gt_size, crop))
+    max_top, max_left = _max_origin(lr_size, gt_size, crop, int(scale))
+    if max_top < 0 or max_left < 0:
+        raise ValueError("crop_origin: a %dx%d patch (scale %d) does not fit frames %s -> %s" % (crop + (int(scale), lr_size, gt_size)))
+    g = random.Random(seed)
+    top = g.randint(0, max_top)
+    return top, g.randint(0, max_left)
+
+
 def _index_table(who, name, idx, n):
     a = np.asarray(idx.cpu() if torch.is_tensor(idx) else idx)
     if a.ndim != 2 or a.shape[1] != 2 or a.dtype.kind not in "iu":
@@ -140,10 +167,12 @@ class EventTrainSet:
 
     L, step_size, augment, pause as sequence_plan; add_noise: None or the reference's noise_level; window: the LR events per
     item the noise count is taken from (config['window']).  Sequence indices run over the recordings in the order they were
-    added, (length - L) // step_size + 1 each, as ConcatDataset over SequenceDataset."""
+    added, (length - L) // step_size + 1 each, as ConcatDataset over SequenceDataset.
+    crop: None (full frames; all recordings share one pair of sizes) or (h, w): batches of h x w LR patches and scale*h x scale*w
+    HR patches, from recordings of any sizes the patch fits."""
     RING = 2
 
-    def __init__(self, L=9, step_size=None, augment=None, pause=None, add_noise=None, window=2048):
+    def __init__(self, L=9, step_size=None, augment=None, pause=None, add_noise=None, window=2048, crop=None, scale=4):
         self.L = int(L)
         if not 2 <= self.L <= MAX_ITEMS:
             raise ValueError("EventTrainSet: 2 <= L <= %d (got %d)" % (MAX_ITEMS, self.L))
@@ -154,6 +183,16 @@ class EventTrainSet:
         self.noise_level = None if add_noise is None else float(add_noise)
         self.window = int(window)
         self.n_noise = 0 if self.noise_level is None else int(self.window * self.noise_level)
+        self.crop, self.scale, self.last_origins = None, int(scale), None
+        if crop is not None:
+            try:
+                h, w = (int(v) for v in crop)
+            except (TypeError, ValueError):
+                raise ValueError("EventTrainSet: crop must be None or (h, w)") from None
+            if min(h, w, self.scale) < 1 or self.scale * w > MAX_WIDTH:
+                raise ValueError("EventTrainSet: crop and scale must be positive and scale * w at most %d (got crop %s, scale %d)"
+                                 % (MAX_WIDTH, (h, w), self.scale))
+            self.crop = (h, w)
         self._recs, self._ends, self._size, self._device = [], [], None, None
         self._pinned, self._events, self._table, self._k = None, [None] * self.RING, None, 0
 
@@ -162,7 +201,7 @@ class EventTrainSet:
         """One recording -> its number.  lr, gt = (xs, ys, ps): 1-D int16, int16, float64 GPU tensors, polarities -1 / 0 / +1;
         lr_index, gt_index [length,2] integer tables on the host (bmc_hip.encodings.event_window_indices gives the reference's);
         every range is checked here against the column lengths: the kernel trusts the table.  All recordings share one pair
-        of sizes."""
+        of sizes; a set with crop takes any sizes the patch fits."""
         who = "EventTrainSet.add_recording: "
         for name, cols in (("lr", lr), ("gt", gt)):
             if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
@@ -181,9 +220,15 @@ class EventTrainSet:
             (H, W), (gh, gw) = (int(v) for v in lr_size), (int(v) for v in gt_size)
         except (TypeError, ValueError):
             raise ValueError(who + "lr_size = (H, W) and gt_size = (gh, gw)") from None
-        if min(H, W, gh, gw) < 1 or max(W, gw) > MAX_WIDTH:
+        if self.crop is not None:
+            if min(H, W, gh, gw) < 1:
+                raise ValueError(who + "sizes must be positive (got %s, %s)" % ((H, W), (gh, gw)))
+            if min(_max_origin((H, W), (gh, gw), self.crop, self.scale)) < 0:
+                raise ValueError(who + "the %dx%d patch (scale %d) does not fit the recording's %s -> %s"
+                                 % (self.crop + (self.scale, (H, W), (gh, gw))))
+        elif min(H, W, gh, gw) < 1 or max(W, gw) > MAX_WIDTH:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)" % (MAX_WIDTH, (H, W), (gh, gw)))
-        if self._size is not None and self._size != (H, W, gh, gw):
+        elif self._size is not None and self._size != (H, W, gh, gw):
             raise ValueError(who + "sizes differ: this set holds %s -> %s, the recording is %s -> %s"
                              % (self._size[:2], self._size[2:], (H, W), (gh, gw)))
         cols = tuple(lr) + tuple(gt)
@@ -193,7 +238,7 @@ class EventTrainSet:
             if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
                 raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
         self._size, self._device = (H, W, gh, gw), cols[0].device
-        self._recs.append(dict(cols=cols, ptrs=[t.data_ptr() for t in cols], lr_index=lr_index, gt_index=gt_index))
+        self._recs.append(dict(cols=cols, ptrs=[t.data_ptr() for t in cols], lr_index=lr_index, gt_index=gt_index, size=(H, W, gh, gw)))
         self._ends.append(len(self) + (len(lr_index) - self.L) // self.step_size + 1)
         return len(self._recs) - 1
 
@@ -216,8 +261,9 @@ class EventTrainSet:
 
     def _buffers(self, B):
         """Pinned host copies (a ring: one is rewritten only after the copy that last read it has completed) and the device
-        buffer of B table entries followed by B noise column sets; grown when a larger batch comes."""
-        nbytes = B * (SEQ_SAMPLE_DTYPE.itemsize + 8 * ((5 * self.n_noise + 7) // 8))
+        buffer of B table entries followed by B crop entries (a set with crop) and B noise column sets; grown when a larger
+        batch comes."""
+        nbytes = B * (SEQ_SAMPLE_DTYPE.itemsize + (SEQ_CROP_DTYPE.itemsize if self.crop else 0) + 8 * ((5 * self.n_noise + 7) // 8))
         if self._table is None or self._table.numel() < nbytes:
             torch.cuda.synchronize(self._device)
             self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
@@ -225,19 +271,36 @@ class EventTrainSet:
             self._table = torch.zeros(nbytes, dtype=torch.uint8, device=self._device)
         return nbytes
 
-    def batch(self, indices, rng=random):
+    def batch(self, indices, rng=random, origins=None):
         """Sequences `indices` of the set -> (inp_cnt [B,L,2,H,W], gt_cnt [B,L,2,gh,gw]) float32 on the GPU, the layout
         train_step.bptt_step takes: one table copy (entries and noise columns in one pinned buffer) and ONE bmc_seq_encode launch
         on the current stream.  The samples' plans draw from `rng` in the order of `indices`, as a loader worker would walk them.
-        The pinned table and its device copy are reused between calls; the two results are new tensors."""
+        The pinned table and its device copy are reused between calls; the two results are new tensors.
+        A set with crop = (h, w) returns the patches [B,L,2,h,w], [B,L,2,scale*h,scale*w] instead, from ONE bmc_seq_encode_crop
+        launch (the crop entries travel in the same table copy, behind the sample entries): the slices of the full-frame batch
+        at self.last_origins ([B,2] int64 numpy, (top, left) per sample), which are crop_origin of each plan's seed, or
+        `origins` (integer [B,2]) where given.  The noise is drawn against each recording's own LR size."""
         global ENCODE_LAUNCHES
-        from bmc_hip.encodings import encode_sequences
+        from bmc_hip.encodings import encode_sequence_crops, encode_sequences
+        who = "EventTrainSet.batch: "
         indices = [int(v) for v in indices]
         B = len(indices)
         if not 1 <= B <= MAX_BATCH:
-            raise ValueError("EventTrainSet.batch: 1 <= B <= %d sequences (got %d)" % (MAX_BATCH, B))
+            raise ValueError(who + "1 <= B <= %d sequences (got %d)" % (MAX_BATCH, B))
+        if origins is not None:
+            if self.crop is None:
+                raise ValueError(who + "origins needs a set with crop")
+            origins = np.asarray(origins.cpu() if torch.is_tensor(origins) else origins)
+            if origins.shape != (B, 2) or origins.dtype.kind not in "iu":
+                raise ValueError(who + "origins must be an integer [%d,2] array (got %s %s)" % (B, origins.dtype, origins.shape))
+            origins = origins.astype(np.int64)
+            for v, (top, left) in zip(indices, origins.tolist()):
+                size = self._recs[self.locate(v)[0]]["size"]
+                max_top, max_left = _max_origin(size[:2], size[2:], self.crop, self.scale)
+                if not (0 <= top <= max_top and 0 <= left <= max_left):
+                    raise ValueError(who + "origin (%d, %d) of sequence %d lies outside (0, 0) .. (%d, %d), where the %dx%d patch "
+                                     "fits its recording's %s -> %s" % ((top, left, v, max_top, max_left) + self.crop + (size[:2], size[2:])))
         plans = [self.plan(v, rng) for v in indices]
-        H, W, gh, gw = self._size
         L, nn = self.L, self.n_noise
         nbytes = self._buffers(B)
         k = self._k
@@ -246,17 +309,26 @@ class EventTrainSet:
         host = self._pinned[k].numpy()
         tab = host[:B * SEQ_SAMPLE_DTYPE.itemsize].view(SEQ_SAMPLE_DTYPE)
         tab[:] = np.zeros((), SEQ_SAMPLE_DTYPE)
+        crop_off = noise_off = B * SEQ_SAMPLE_DTYPE.itemsize
+        if self.crop is not None:
+            noise_off += B * SEQ_CROP_DTYPE.itemsize
+            crops = host[crop_off:noise_off].view(SEQ_CROP_DTYPE)
+            used = np.zeros((B, 2), np.int64)
         stride = 8 * ((5 * nn + 7) // 8)
         for b, (r, seed, items, paused, flips) in enumerate(plans):
             rec = self._recs[r]
+            H, W, gh, gw = rec["size"]
             for name, p in zip(SEQ_SAMPLE_DTYPE.names[:6], rec["ptrs"]):
                 tab[name][b] = p
             tab["lr_range"][b, :L] = rec["lr_index"][items]
             tab["gt_range"][b, :L] = rec["gt_index"][items]
             tab["flips"][b] = flips
             tab["paused"][b] = sum(1 << t for t, p in enumerate(paused) if p)
+            if self.crop is not None:
+                used[b] = origins[b] if origins is not None else crop_origin(seed, (H, W), (gh, gw), self.crop, self.scale)
+                crops[b] = (H, W, gh, gw, used[b, 0], used[b, 1])
             if nn:
-                off = B * SEQ_SAMPLE_DTYPE.itemsize + b * stride
+                off = noise_off + b * stride
                 xs, ys, ps = noise_events(self.window, (H, W), seed, self.noise_level)
                 host[off:off + 2 * nn].view(np.int16)[:] = xs
                 host[off + 2 * nn:off + 4 * nn].view(np.int16)[:] = ys
@@ -268,7 +340,11 @@ class EventTrainSet:
             ev = self._events[k] = self._events[k] or torch.cuda.Event()
             ev.record()
             self._k = (k + 1) % self.RING
-            out = encode_sequences(self._table, B, L, (H, W), (gh, gw))
+            if self.crop is None:
+                out = encode_sequences(self._table, B, L, self._size[:2], self._size[2:])
+            else:
+                out = encode_sequence_crops(self._table, self._table[crop_off:noise_off], B, L, self.crop, self.scale)
+                self.last_origins = used
         ENCODE_LAUNCHES += 1
         return out
 

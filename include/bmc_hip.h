@@ -586,6 +586,26 @@ typedef struct bmc_seq_sample {           /* one sequence of the batch */
 } bmc_seq_sample_t;
 int bmc_seq_encode(const bmc_seq_sample_t* table, int B, int L, int H, int W, int gh, int gw, float* inp_cnt, float* gt_cnt,
                    bmc_stream_t s);
+/* Patch training (event_dataset.EventTrainSet(crop=...)): the same table, and parallel to it a DEVICE table of B crops; ONE
+ * launch writes one patch per sample, inp_cnt [B][L][2][h][w] and gt_cnt [B][L][2][scale*h][scale*w], so that recordings of
+ * different sensor sizes share a batch.  For every sample b the outputs are, bit for bit, the slices
+ *   full_inp[b][:, :, top:top+h, left:left+w]      full_gt[b][:, :, scale*top:scale*(top+h), scale*left:scale*(left+w)]
+ * of what bmc_seq_encode writes for the same table entry at the sample's own (H, W, gh, gw): the flips act on the full frame,
+ * before the range test; an out-of-range negative adds 1 at [fh-1][0] of channel 1 of the FULL frame and is in the patch only
+ * when the patch covers that pixel; noise events are unflipped and ranged against the sample's own (H, W); a paused LR item is
+ * all +0.0; HR items never get noise; zeros are +0.0.  The scheme is bmc_seq_encode's on the patch: a workgroup owns a band of
+ * min(15360 / (2 * patch width), patch height) rows of one patch frame, zeroed in LDS, counted with integer LDS atomics, stored
+ * once -- no global atomics, no memset, order independent and run-to-run identical; a band reads xs / ps of every event only when
+ * it holds the full frame's [fh-1][0] (left == 0 and the band covers row fh-1).  Checked here: 1 <= B <= 65535, 2 <= L <=
+ * BMC_SEQ_MAX_ITEMS, scale >= 1, h, w >= 1, scale * w <= 7680 (the limit is the patch's, not the recording's).  The CALLER
+ * checks and the kernel trusts: every range inside its columns, and the crop inside the frames: top, left >= 0, top + h <= H,
+ * left + w <= W, scale * (top + h) <= gh, scale * (left + w) <= gw. */
+typedef struct bmc_seq_crop {   /* one per sample, parallel to the bmc_seq_sample_t table */
+    int H, W, gh, gw;           /* the sample's OWN full frame sizes (flips and the out-of-range rule use these) */
+    int top, left;              /* patch origin in LR IMAGE rows / columns (row 0 = sensor y = H-1) */
+} bmc_seq_crop_t;
+int bmc_seq_encode_crop(const bmc_seq_sample_t* table, const bmc_seq_crop_t* crops, int B, int L, int h, int w, int scale,
+                        float* inp_cnt, float* gt_cnt, bmc_stream_t s);
 
 /* Event OUTPUT of the slots (MultiStreamSR(emit_events=True)): the window's prediction leaves the session as an event list
  * appended to the recording's own output columns -- the rounded count image the reference renders (infer_BMCNet.py:94:

@@ -13,7 +13,11 @@ branch of train.py:227-231 -- inside bptt_step's fused head + loss launches.
 python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x80] [--steps 10] [--batch 2] [--L 9] [--step-size S]
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
-                             [--gt-size HxW] [--valid-every N]
+                             [--gt-size HxW] [--valid-every N] [--crop HxW]
+--crop HxW: train on HxW LR patches (and scale x that HR patches) cut in the encoder, one random origin per sequence
+(EventTrainSet(crop=...), ONE bmc_seq_encode_crop launch per batch).  --size and --gt-size then take comma-separated lists the
+synthetic recordings cycle through (--size 180x240,260x346), a set of mixed sensors; recordings given as files may differ in size
+too.  Validation stays on full frames.
 --valid-every N: the last recording is held out of training; after every N steps train_step.valid_step (the reference's _valid
 loop: eval mode, no gradients, the same loss) runs over its sequences in order and `valid_loss`, their mean, is printed.
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
@@ -92,20 +96,27 @@ def main():
     ap.add_argument("--wall", action="store_true")
     ap.add_argument("--gt-size", default=None, help="HxW of the synthetic recordings' ground truth (default: scale x --size)")
     ap.add_argument("--valid-every", type=int, default=0, help="hold the last recording out and print valid_loss every N steps")
+    ap.add_argument("--crop", default=None, help="HxW of the LR patches to train on; --size / --gt-size may then be lists")
     a = ap.parse_args()
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
     dev = torch.device("cuda:0")
-    H, W = (int(v) for v in a.size.split("x"))
+    hw = lambda text: tuple(int(v) for v in text.split("x"))
+    sizes = [hw(t) for t in a.size.split(",")]
+    gt_sizes = [hw(t) for t in a.gt_size.split(",")] if a.gt_size else [None]
+    crop = hw(a.crop) if a.crop else None
+    if crop is None and (len(sizes) > 1 or len(gt_sizes) > 1):
+        ap.error("a list of sizes needs --crop: full frames of different sizes cannot share a batch")
     recs = [dict(np.load(p)) for p in a.recordings]
-    gt_size = tuple(int(v) for v in a.gt_size.split("x")) if a.gt_size else None
-    recs += [synthetic_recording(a.items, H, W, a.scale, a.window, a.sliding, a.seed + k, gt_size) for k in range(a.synthetic)]
+    recs += [synthetic_recording(a.items, *sizes[k % len(sizes)], a.scale, a.window, a.sliding, a.seed + k, gt_sizes[k % len(gt_sizes)])
+             for k in range(a.synthetic)]
     if a.save:
         os.makedirs(a.save, exist_ok=True)
         for k, r in enumerate(recs[len(a.recordings):]):
             np.savez(os.path.join(a.save, "synthetic%d.npz" % k), **r)
     ts = EventTrainSet(L=a.L, step_size=a.step_size, augment=(("Horizontal", "Vertical", "Polarity"), (0.5, 0.5, 0.5)) if a.augment else None,
-                       pause=tuple(float(v) for v in a.pause.split(",")) if a.pause else None, add_noise=a.noise, window=a.window)
+                       pause=tuple(float(v) for v in a.pause.split(",")) if a.pause else None, add_noise=a.noise, window=a.window,
+                       crop=crop, scale=a.scale)
     vs = None
     if a.valid_every > 0:
         if len(recs) < 2:
@@ -116,7 +127,7 @@ def main():
             raise SystemExit("the held-out recording gives %d sequences, fewer than one batch of %d" % (len(vs), a.batch))
     for r in recs:
         add(ts, r, dev, a.window, a.sliding, a.scale)
-    print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) +
+    print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) + (", %dx%d patches" % crop if crop else "") +
           (", %d held-out sequences" % len(vs) if vs is not None else ""))
     random.seed(a.seed)
     torch.manual_seed(a.seed)
