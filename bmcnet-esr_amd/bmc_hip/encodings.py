@@ -471,5 +471,5 @@ def encode_sequence_crops(table, crops, B, L, crop, scale, out=None):
     return out[0], out[1]
 
 
-SEQ_SAMPLE_BYTES = 1112          # sizeof(bmc_seq_sample_t)
-SEQ_CROP_BYTES = 24              # sizeof(bmc_seq_crop_t)
+SEQ_SAMPLE_BYTES = lib.STRUCTS["bmc_seq_sample_t"].size
+SEQ_CROP_BYTES = lib.STRUCTS["bmc_seq_crop_t"].size

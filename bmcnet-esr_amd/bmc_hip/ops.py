@@ -18,7 +18,7 @@ import torch
 
 from . import lib
 
-CK = 16
+CK = lib.const("BMC_CK")
 _cur_dev = torch._C._cuda_getDevice      # torch.cuda.current_device() without its Python-level lazy-init wrapper
 
 
@@ -222,7 +222,8 @@ def _prof_end(e0, kind, flops, nbytes=0.0):
 # Arithmetic of the convolution kernels (include/bmc_hip.h BMC_MATH_*): 0 = native fp32 MFMA (default, the headline
 # path), 1 = bf16 operands / fp32 accumulate, 3 = fp32 operands split into three bf16 planes, six plane products
 # (fp32-equivalent).  Set with set_math() or BMC_MATH=fp32|bf16|bf16x6 before the first launch.
-MATH_NAMES = {"fp32": 0, "bf16": 1, "bf16x6": 3}
+MATH_NAMES = {"fp32": lib.const("BMC_MATH_FP32"), "bf16": lib.const("BMC_MATH_BF16"), "bf16x6": lib.const("BMC_MATH_BF16X6")}
+MATH_FP32_WINO, MATH_FP32_WINO4 = lib.const("BMC_MATH_FP32_WINO"), lib.const("BMC_MATH_FP32_WINO4")      # bmc_conv only: F(2x2) / F(4x4)
 MATH = MATH_NAMES[os.environ.get("BMC_MATH", "fp32")]
 
 
@@ -568,7 +569,7 @@ def conv_raw(srcs: List[lib.Src], wpacked, w_group_stride, bias, bias_group_stri
     if wino:
         assert MATH == 0 and taps == 9
         a.w_group_stride = w_group_stride // 9 * (36 if wino == 4 else 16)
-        a.math = 5 if wino == 4 else 4          # BMC_MATH_FP32_WINO4 / BMC_MATH_FP32_WINO
+        a.math = MATH_FP32_WINO4 if wino == 4 else MATH_FP32_WINO
     a.bias_group_stride = bias_group_stride
     a.batch_per_group = bpg if bpg else B
     a.out = out_ptr
@@ -791,7 +792,7 @@ def _table_src(srcs, batches, btot, dev):
             _TABLES[key] = table
     t = lib.Src()
     t.ptr = table.data_ptr()
-    t.batch_stride, t.pix_stride, t.nch, t.batch_shift, t.batch_mod = 0, srcs[0].pix_stride, srcs[0].nch, 0, -1      # BMC_SRC_TABLE
+    t.batch_stride, t.pix_stride, t.nch, t.batch_shift, t.batch_mod = 0, srcs[0].pix_stride, srcs[0].nch, 0, lib.SRC_TABLE
     return t, table
 
 
@@ -824,7 +825,7 @@ def _queue_use(wino, a_src, x_srcs, B, H, W, taps, Cout, spec, dev, w_param, b_p
     if wino:
         if wgrad_wino4_ok(B, H, W):         # (merged launches stay on F(2x2): a use that F(4x4) takes leaves alone)
             return False
-    elif not (B <= PTR_TABLE_MAX and a_src.batch_mod != -1 and all(x.batch_mod != -1 for x in x_srcs)):
+    elif not (B <= PTR_TABLE_MAX and a_src.batch_mod != lib.SRC_TABLE and all(x.batch_mod != lib.SRC_TABLE for x in x_srcs)):
         return False
     key = (id(w_param), k0, taps, len(x_srcs), H, W, want_bias)
     qs = _MERGE.setdefault(task, {})

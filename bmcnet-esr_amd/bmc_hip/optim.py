@@ -36,9 +36,8 @@ import torch
 from . import lib
 from . import ops  # noqa: F401  -- registers the global pre-step hook (ops._join_before_step) wherever this optimizer is used
 
-CHUNK = 4096                      # BMC_ADAM_CHUNK
-CHUNK_DTYPE = np.dtype({"names": ["p", "g", "m", "v", "vmax", "n", "aligned"], "formats": ["<u8"] * 5 + ["<i4", "<i4"],
-                        "offsets": [0, 8, 16, 24, 32, 40, 44], "itemsize": 48})       # bmc_adam_chunk_t
+CHUNK = lib.const("BMC_ADAM_CHUNK")
+CHUNK_DTYPE = lib.dtype("bmc_adam_chunk_t")
 STEP_LAUNCHES = 0                 # calls of bmc_adam_step / bmc_adam_step_capturable of this process
 NORM_LAUNCHES = 0                 # calls of bmc_adam_grad_sq of this process (a clipped step: one per step launch)
 TABLE_COPIES = 0                  # chunk tables copied to the device

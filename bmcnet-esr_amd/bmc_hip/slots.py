@@ -41,53 +41,42 @@ import torch
 from . import lib
 from .ops import _stream
 
-ACTIVE, RESET = 1, 2
-MAX_SLOTS = 256
-MAX_PARTS = 64
-SLOT_DTYPE = np.dtype([("frames", "<u8"), ("gt", "<u8"), ("keep", "<u8"), ("result", "<u8"), ("flags", "<i4"),
-                       ("pad", "<i4")])
-assert SLOT_DTYPE.itemsize == 40
+# the header's limits and table layouts (include/bmc_hip.h), as the library states them
+ACTIVE, RESET = lib.const("BMC_SLOT_ACTIVE"), lib.const("BMC_SLOT_RESET")
+MAX_SLOTS = lib.const("BMC_MAX_SLOTS")
+MAX_PARTS = lib.const("BMC_SLOT_MAX_PARTS")
+SLOT_DTYPE = lib.dtype("bmc_slot_t")
 LAUNCHES = {"stage": 0, "commit": 0, "metrics": 0}
-MAX_SEQN = 8
+MAX_SEQN = lib.const("BMC_SLOT_MAX_SEQN")
 MAX_ENCODE_WIDTH = 7680
-SLOT_EVENTS_DTYPE = np.dtype([("lr_xs", "<u8"), ("lr_ys", "<u8"), ("lr_ps", "<u8"), ("gt_xs", "<u8"), ("gt_ys", "<u8"),
-                              ("gt_ps", "<u8"), ("gt_range", "<i8", (2,)), ("lr_range", "<i8", (MAX_SEQN, 2))])
-assert SLOT_EVENTS_DTYPE.itemsize == 192
+SLOT_EVENTS_DTYPE = lib.dtype("bmc_slot_events_t")
 ENCODE_LAUNCHES = 0
-MAX_EMIT_PARTS = 1024
+MAX_EMIT_PARTS = lib.const("BMC_SLOT_EMIT_MAX_PARTS")
 MAX_COUNT_LIMIT = 32767            # counts and coordinates of emitted events fit int16
-SLOT_EMIT_DTYPE = np.dtype([("xs", "<u8"), ("ys", "<u8"), ("ps", "<u8"), ("index_in", "<u8"), ("index_out", "<u8"),
-                            ("capacity", "<i8")])
-assert SLOT_EMIT_DTYPE.itemsize == 48
+SLOT_EMIT_DTYPE = lib.dtype("bmc_slot_emit_t")
 EMIT_LAUNCHES = 0
-SLOT_EMIT_TIMED_DTYPE = np.dtype(SLOT_EMIT_DTYPE.descr + [("ts", "<u8")])
-assert SLOT_EMIT_TIMED_DTYPE.itemsize == 56
+SLOT_EMIT_TIMED_DTYPE = lib.dtype("bmc_slot_emit_timed_t")
 EMIT_TIMED_LAUNCHES = 0
 EMIT_TIMED_KERNELS = 6             # launches of one bmc_slot_emit_timed call: count, scan, expand, histogram, scan, scatter
-MAX_COUNT_TIMED = 255              # the rank table of the timed mode
-MAX_WINDOW_CAPACITY = 1 << 28
-EVENT_T0, EVENT_T1 = 0.01, 1.0     # BMC_EVENT_T0 / BMC_EVENT_T1: the window's time axis
-SLOT_CLOCK_DTYPE = np.dtype([("t_first", "<f8"), ("t_last", "<f8"), ("ts", "<u8")])      # bmc_slot_clock_t
-assert SLOT_CLOCK_DTYPE.itemsize == 24
+MAX_COUNT_TIMED = lib.const("BMC_SLOT_EMIT_TIMED_MAX_COUNT")       # the rank table of the timed mode
+MAX_WINDOW_CAPACITY = lib.const("BMC_SLOT_EMIT_TIMED_MAX_WINDOW")
+EVENT_T0, EVENT_T1 = lib.const("BMC_EVENT_T0"), lib.const("BMC_EVENT_T1")      # the window's time axis
+SLOT_CLOCK_DTYPE = lib.dtype("bmc_slot_clock_t")
 _RANK_TABLES = {}
-SLOT_HOT_DTYPE = np.dtype([("hot_pixels", "<u8"), ("hot_mask", "<u8"), ("first_item", "<i4"), ("new_from", "<i4"),
-                           ("active", "<i4"), ("pad", "<i4"), ("cmin", "<i4", (MAX_SEQN,))])                # bmc_slot_hot_t
-assert SLOT_HOT_DTYPE.itemsize == 64
+SLOT_HOT_DTYPE = lib.dtype("bmc_slot_hot_t")
 HOT_LAUNCHES = 0
 HOT_KERNELS = 1                    # launches of one bmc_slot_hot_update call
 HOT_MAX_ITEMS = 1 << 23            # below it distinct counts give distinct float32 rates (the contract's rule 3)
-SLOT_RENDER_DTYPE = np.dtype([("src", "<u8"), ("dst", "<u8")])                                                  # bmc_slot_render_t
-assert SLOT_RENDER_DTYPE.itemsize == 16
+SLOT_RENDER_DTYPE = lib.dtype("bmc_slot_render_t")
 RENDER_LAUNCHES = 0
 RENDER_KERNELS = 2                 # launches of one bmc_slot_render call: select, colour
-MAX_RENDER_PIXELS = 1 << 24        # BMC_SLOT_RENDER_MAX_PIXELS: h * w - 1 is exact in float32
-MAX_RENDER_PARTS = 1024
+MAX_RENDER_PIXELS = lib.const("BMC_SLOT_RENDER_MAX_PIXELS")        # h * w - 1 is exact in float32
+MAX_RENDER_PARTS = lib.const("BMC_SLOT_RENDER_MAX_PARTS")
 MAX_RENDER_TABLES = 8
-SLOT_VOXEL_DTYPE = np.dtype([("dst", "<u8")])                                                                   # bmc_slot_voxel_t
-assert SLOT_VOXEL_DTYPE.itemsize == 8
+SLOT_VOXEL_DTYPE = lib.dtype("bmc_slot_voxel_t")
 VOXEL_LAUNCHES = 0
 VOXEL_KERNELS = 2                  # launches of one bmc_slot_voxel call: reduce, voxel
-MAX_VOXEL_BINS = 32                # BMC_SLOT_VOXEL_MAX_BINS
+MAX_VOXEL_BINS = lib.const("BMC_SLOT_VOXEL_MAX_BINS")
 
 
 def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False):

@@ -19,16 +19,13 @@ import random
 import numpy as np
 import torch
 
-MAX_ITEMS = 32           # BMC_SEQ_MAX_ITEMS
+from bmc_hip import lib
+
+MAX_ITEMS = lib.const("BMC_SEQ_MAX_ITEMS")
 MAX_BATCH = 65535
 MAX_WIDTH = 7680         # one row of both channels must fit a workgroup's LDS band
-SEQ_SAMPLE_DTYPE = np.dtype({
-    "names": ["lr_xs", "lr_ys", "lr_ps", "gt_xs", "gt_ys", "gt_ps", "noise_xs", "noise_ys", "noise_ps", "n_noise", "flips", "paused",
-              "lr_range", "gt_range"],
-    "formats": ["<u8"] * 9 + ["<i4", "<u4", "<u4", ("<i8", (MAX_ITEMS, 2)), ("<i8", (MAX_ITEMS, 2))],
-    "offsets": [0, 8, 16, 24, 32, 40, 48, 56, 64, 72, 76, 80, 88, 88 + 16 * MAX_ITEMS],
-    "itemsize": 88 + 32 * MAX_ITEMS})          # bmc_seq_sample_t
-SEQ_CROP_DTYPE = np.dtype([(k, "<i4") for k in ("H", "W", "gh", "gw", "top", "left")])          # bmc_seq_crop_t
+SEQ_SAMPLE_DTYPE = lib.dtype("bmc_seq_sample_t")
+SEQ_CROP_DTYPE = lib.dtype("bmc_seq_crop_t")
 ENCODE_LAUNCHES = 0      # bmc_seq_encode and bmc_seq_encode_crop launches of this process
 
 

@@ -52,6 +52,11 @@ typedef struct bmc_src {
 /* ---- library ---- */
 int bmc_version(void);
 const char* bmc_last_error(void);
+/* The ABI of this build as text, one record per line: every entry point's return and parameter types, every struct's size,
+ * alignment and fields (offset, size, element type, array extents) and every numeric BMC_* constant of this header, as the
+ * compiler that built the library saw them (csrc/abi.hip gives the record formats).  A binding is built from this text, not
+ * from a second copy of this header.  The string lives as long as the library. */
+const char* bmc_abi(void);
 /* A new stream of the device's lowest priority (hipDeviceGetStreamPriorityRange), never destroyed by the library.  The training
  * step issues its weight-gradient kernels there (the reference has no counterpart: autograd runs train.py:233's backward on
  * one stream): they fill the CUs the data-gradient chain leaves idle without delaying it. */

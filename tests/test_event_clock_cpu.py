@@ -3,8 +3,6 @@ csrc/slot_emit_timed.hip, bmc_slot_emit_clocked): the index table of a recording
 and the reference's recorded tables, the spans of the items, the properties of the reduced-fraction time that the float64
 column rests on, the argument checks, and the layout of bmc_slot_clock_t.  Every comparison is exact."""
 import os
-import shutil
-import subprocess
 import types
 from fractions import Fraction
 
@@ -298,23 +296,16 @@ def test_library_exports_slot_emit_clocked():
     assert "bmc_slot_emit_clocked" in lib.EXPORTS and lib.has_symbol("bmc_slot_emit_clocked")
 
 
-def test_slot_clock_struct_layout_matches_header(tmp_path):
+def test_slot_clock_struct_layout_matches_header():
+    import abi_ref
     from bmc_hip import slots
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler"
     fields = ["t_first", "t_last", "ts"]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmc_hip.h"\nint main(){bmc_slot_clock_t c; printf("%zu ' +
-           "%zu " * len(fields) + '%zu %zu %zu %zu\\n", sizeof(bmc_slot_clock_t), ' +
-           ", ".join("offsetof(bmc_slot_clock_t, %s)" % f for f in fields) +
-           ', sizeof(c.t_first), sizeof(c.ts), sizeof(bmc_slot_emit_timed_t), sizeof(bmc_slot_emit_t));return 0;}')
-    c = tmp_path / "t.c"
-    c.write_text(src)
-    exe = tmp_path / "t"
-    subprocess.run([cc, "-I" + os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE).stdout.split()]
+    structs = abi_ref.compiled_header()[0]
+    size, compiled = structs["bmc_slot_clock_t"]
     dt = slots.SLOT_CLOCK_DTYPE
-    assert out == [dt.itemsize] + [dt.fields[f][1] for f in fields] + [8, 8, slots.SLOT_EMIT_TIMED_DTYPE.itemsize,
-                                                                      slots.SLOT_EMIT_DTYPE.itemsize]
+    assert [size] + [compiled[f][0] for f in fields] + [compiled["t_first"][1], compiled["ts"][1], structs["bmc_slot_emit_timed_t"][0],
+                                                        structs["bmc_slot_emit_t"][0]] == \
+        [dt.itemsize] + [dt.fields[f][1] for f in fields] + [8, 8, slots.SLOT_EMIT_TIMED_DTYPE.itemsize, slots.SLOT_EMIT_DTYPE.itemsize]
     assert dt.names == tuple(fields) and dt.itemsize == 24
     assert dt.fields["t_first"][0] == np.dtype("<f8") and dt.fields["t_last"][0] == np.dtype("<f8")
     assert slots.SLOT_EMIT_TIMED_DTYPE.itemsize == 56 and slots.SLOT_EMIT_DTYPE.itemsize == 48        # the existing layouts stay

@@ -4,7 +4,6 @@ predictions, the argument checks of the public entry points, the layout of bmc_s
 of the two emit kernels (no flat memory instructions, no scratch, no atomics on global memory, nothing that waits)."""
 import os
 import re
-import shutil
 import subprocess
 import types
 
@@ -159,23 +158,16 @@ def test_library_exports_slot_emit():
     assert "bmc_slot_emit" in lib.EXPORTS and lib.has_symbol("bmc_slot_emit")
 
 
-def test_slot_emit_struct_layout_matches_header(tmp_path):
+def test_slot_emit_struct_layout_matches_header():
+    import abi_ref
     from bmc_hip import slots
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    if cc is None:
-        pytest.skip("no host C compiler")
     fields = ["xs", "ys", "ps", "index_in", "index_out", "capacity"]
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmc_hip.h"\nint main(){printf("%zu ' + "%zu " * len(fields) +
-           '%d %zu %zu\\n", sizeof(bmc_slot_emit_t), ' + ", ".join("offsetof(bmc_slot_emit_t, %s)" % f for f in fields) +
-           ', BMC_SLOT_EMIT_MAX_PARTS, sizeof(bmc_slot_t), sizeof(bmc_slot_events_t));return 0;}')
-    c = tmp_path / "t.c"
-    c.write_text(src)
-    exe = tmp_path / "t"
-    subprocess.run([cc, "-I" + os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE).stdout.split()]
+    structs, constants = abi_ref.compiled_header()
+    size, compiled = structs["bmc_slot_emit_t"]
     dt = slots.SLOT_EMIT_DTYPE
-    assert out == [dt.itemsize] + [dt.fields[f][1] for f in fields] + [slots.MAX_EMIT_PARTS, slots.SLOT_DTYPE.itemsize,
-                                                                       slots.SLOT_EVENTS_DTYPE.itemsize]
+    assert [size] + [compiled[f][0] for f in fields] == [dt.itemsize] + [dt.fields[f][1] for f in fields]
+    assert [constants["BMC_SLOT_EMIT_MAX_PARTS"], structs["bmc_slot_t"][0], structs["bmc_slot_events_t"][0]] == [
+        slots.MAX_EMIT_PARTS, slots.SLOT_DTYPE.itemsize, slots.SLOT_EVENTS_DTYPE.itemsize]
     assert dt.names == tuple(fields) and dt.itemsize == 48
 
 

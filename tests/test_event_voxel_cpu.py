@@ -3,8 +3,6 @@
 and against the installed torch's restatement of the composition (timed stream -> events_to_voxel_torch), and the argument
 checks of MultiStreamSR(voxel_bins=...), counts_to_voxel and table_layout(voxel=) that need no GPU."""
 import os
-import shutil
-import subprocess
 import sys
 
 import numpy as np
@@ -147,20 +145,15 @@ def test_slot_table_voxel_section():
     assert slots.VOXEL_KERNELS == 2 and slots.MAX_VOXEL_BINS == 32 and slots.VOXEL_LAUNCHES == 0
 
 
-def test_slot_voxel_struct_layout_matches_header(tmp_path):
+def test_slot_voxel_struct_layout_matches_header():
+    import abi_ref
     from bmc_hip import slots
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    assert cc is not None, "no host C compiler"
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmc_hip.h"\nint main(){bmc_slot_voxel_t v; printf("%zu %zu %zu %d %d %zu\\n", '
-           'sizeof(bmc_slot_voxel_t), offsetof(bmc_slot_voxel_t, dst), sizeof(v.dst), BMC_SLOT_VOXEL_MAX_BINS, '
-           'BMC_SLOT_EMIT_TIMED_MAX_COUNT, sizeof(bmc_slot_render_t));return 0;}')
-    c = tmp_path / "t.c"
-    c.write_text(src)
-    exe = tmp_path / "t"
-    subprocess.run([cc, "-I" + os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE).stdout.split()]
+    structs, constants = abi_ref.compiled_header()
+    size, compiled = structs["bmc_slot_voxel_t"]
     dt = slots.SLOT_VOXEL_DTYPE
-    assert out == [dt.itemsize, dt.fields["dst"][1], 8, slots.MAX_VOXEL_BINS, slots.MAX_COUNT_TIMED, slots.SLOT_RENDER_DTYPE.itemsize]
+    assert [size, compiled["dst"][0], compiled["dst"][1], constants["BMC_SLOT_VOXEL_MAX_BINS"], constants["BMC_SLOT_EMIT_TIMED_MAX_COUNT"],
+            structs["bmc_slot_render_t"][0]] == [dt.itemsize, dt.fields["dst"][1], 8, slots.MAX_VOXEL_BINS, slots.MAX_COUNT_TIMED,
+                                                 slots.SLOT_RENDER_DTYPE.itemsize]
     assert dt.names == ("dst",) and dt.itemsize == 8
 
 

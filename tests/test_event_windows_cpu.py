@@ -3,7 +3,6 @@ tables of bmc_hip.encodings.event_window_indices against tables recorded from th
 (tests/golden/event_windows.npz, written by tests/golden/make_golden_event_windows.py), open_events' argument checks, the
 layout of bmc_slot_events_t, and the gfx950 code of the encode kernel (no flat memory instructions, no scratch)."""
 import os
-import shutil
 import subprocess
 
 import numpy as np
@@ -156,23 +155,15 @@ def test_library_exports_slot_encode():
     assert "bmc_slot_encode" in lib.EXPORTS and lib.has_symbol("bmc_slot_encode")
 
 
-def test_slot_events_struct_layout_matches_header(tmp_path):
-    import ctypes as C  # noqa: F401
+def test_slot_events_struct_layout_matches_header():
+    import abi_ref
     from bmc_hip import slots
-    cc = shutil.which("cc") or shutil.which("gcc") or shutil.which("clang")
-    if cc is None:
-        pytest.skip("no host C compiler")
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmc_hip.h"\nint main(){printf("%zu %zu %zu %zu %d %zu\\n", '
-           'sizeof(bmc_slot_events_t), offsetof(bmc_slot_events_t, gt_xs), offsetof(bmc_slot_events_t, gt_range), '
-           'offsetof(bmc_slot_events_t, lr_range), BMC_SLOT_MAX_SEQN, sizeof(bmc_slot_t));return 0;}')
-    c = tmp_path / "t.c"
-    c.write_text(src)
-    exe = tmp_path / "t"
-    subprocess.run([cc, "-I" + os.path.join(ROOT, "include"), str(c), "-o", str(exe)], check=True)
-    out = [int(v) for v in subprocess.run([str(exe)], check=True, stdout=subprocess.PIPE).stdout.split()]
+    structs, constants = abi_ref.compiled_header()
+    size, compiled = structs["bmc_slot_events_t"]
     dt = slots.SLOT_EVENTS_DTYPE
-    assert out == [dt.itemsize, dt.fields["gt_xs"][1], dt.fields["gt_range"][1], dt.fields["lr_range"][1], slots.MAX_SEQN,
-                   slots.SLOT_DTYPE.itemsize]
+    assert [size, compiled["gt_xs"][0], compiled["gt_range"][0], compiled["lr_range"][0], constants["BMC_SLOT_MAX_SEQN"],
+            structs["bmc_slot_t"][0]] == [dt.itemsize, dt.fields["gt_xs"][1], dt.fields["gt_range"][1], dt.fields["lr_range"][1],
+                                          slots.MAX_SEQN, slots.SLOT_DTYPE.itemsize]
     assert dt.fields["lr_range"][0].shape == (slots.MAX_SEQN, 2)
 
 

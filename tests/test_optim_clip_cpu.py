@@ -4,7 +4,6 @@ float64 value; the layout of bmc_adam_clip_t, the exported symbols, the refusals
 that need no device; and the device assembly of the clipped kernels of csrc/optim.hip."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -91,22 +90,18 @@ def test_global_norm_is_exact():
 
 
 # ------------------------------------------------------------------ struct, exports, refusals
-def test_clip_struct_layout_matches_a_c_compile_of_the_header(tmp_path):
+def test_clip_struct_layout_matches_a_c_compile_of_the_header():
+    import abi_ref
     from bmc_hip import lib
     from bmc_hip.optim import CHUNK_DTYPE
     fields = [f[0] for f in lib.AdamClip._fields_]
     assert sorted(fields) == sorted(["partial_sq", "n_partials", "max_norm", "skip_nonfinite", "info", "skipped"])
-    src = ('#include <stdio.h>\n#include <stddef.h>\n#include "bmc_hip.h"\nint main(){bmc_adam_clip_t c;\n'
-           'printf("%zu %zu %zu", sizeof(bmc_adam_chunk_t), sizeof(bmc_adam_hyper_t), sizeof(bmc_adam_clip_t));\n')
-    src += "".join('printf(" %%zu %%zu", offsetof(bmc_adam_clip_t, %s), sizeof(c.%s));\n' % (f, f) for f in fields)
-    src += "return 0;}\n"
-    (tmp_path / "t.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")], check=True)
-    out = [int(v) for v in subprocess.run([str(tmp_path / "t")], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:2] == [48, 64] == [CHUNK_DTYPE.itemsize, C.sizeof(lib.AdamHyper)]          # the two existing structs: unchanged
-    assert out[2] == C.sizeof(lib.AdamClip)
-    assert out[3::2] == [getattr(lib.AdamClip, f).offset for f in fields]
-    assert out[4::2] == [getattr(lib.AdamClip, f).size for f in fields]
+    structs = abi_ref.compiled_header()[0]
+    size, compiled = structs["bmc_adam_clip_t"]
+    assert [structs["bmc_adam_chunk_t"][0], structs["bmc_adam_hyper_t"][0]] == [48, 64] == [CHUNK_DTYPE.itemsize, C.sizeof(lib.AdamHyper)]
+    assert size == C.sizeof(lib.AdamClip) and list(compiled) == fields
+    assert [compiled[f][0] for f in fields] == [getattr(lib.AdamClip, f).offset for f in fields]
+    assert [compiled[f][1] for f in fields] == [getattr(lib.AdamClip, f).size for f in fields]
     kinds = dict(lib.AdamClip._fields_)
     assert kinds["max_norm"] is C.c_float and kinds["n_partials"] is C.c_int and kinds["skip_nonfinite"] is C.c_int
 

@@ -3,7 +3,6 @@ against the golden reference trajectory, the oracle and torch.optim.Adam in floa
 the exported symbols and the refusals of bmc_hip.optim.Adam that need no device; and the device assembly of csrc/optim.hip."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -86,21 +85,17 @@ def test_chunk_table_alignment_flag_and_skipped_parameters():
     assert len(chunk_table([])) == 0 and len(chunk_table([(1, None, 2, 3, 4, 5)])) == 0
 
 
-def test_struct_layouts_match_a_c_compile_of_the_header(tmp_path):
+def test_struct_layouts_match_a_c_compile_of_the_header():
+    import abi_ref
     from bmc_hip import lib
     from bmc_hip.optim import CHUNK, CHUNK_DTYPE
     chunk = ["p", "g", "m", "v", "vmax", "n", "aligned"]
     hyper = [f[0] for f in lib.AdamHyper._fields_]
-    src = '#include <stdio.h>\n#include <stddef.h>\n#include "bmc_hip.h"\nint main(){printf("%zu %zu %d", sizeof(bmc_adam_chunk_t), sizeof(bmc_adam_hyper_t), BMC_ADAM_CHUNK);\n'
-    src += "".join('printf(" %%zu", offsetof(bmc_adam_chunk_t, %s));\n' % f for f in chunk)
-    src += "".join('printf(" %%zu", offsetof(bmc_adam_hyper_t, %s));\n' % f for f in hyper)
-    src += "return 0;}\n"
-    (tmp_path / "t.c").write_text(src)
-    subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), str(tmp_path / "t.c"), "-o", str(tmp_path / "t")], check=True)
-    out = [int(v) for v in subprocess.run([str(tmp_path / "t")], check=True, capture_output=True, text=True).stdout.split()]
-    assert out[:3] == [CHUNK_DTYPE.itemsize, C.sizeof(lib.AdamHyper), CHUNK]
-    assert out[3:3 + len(chunk)] == [CHUNK_DTYPE.fields[f][1] for f in chunk]
-    assert out[3 + len(chunk):] == [getattr(lib.AdamHyper, f).offset for f in hyper]
+    structs, constants = abi_ref.compiled_header()
+    (chunk_size, c_chunk), (hyper_size, c_hyper) = structs["bmc_adam_chunk_t"], structs["bmc_adam_hyper_t"]
+    assert [chunk_size, hyper_size, constants["BMC_ADAM_CHUNK"]] == [CHUNK_DTYPE.itemsize, C.sizeof(lib.AdamHyper), CHUNK]
+    assert [c_chunk[f][0] for f in chunk] == [CHUNK_DTYPE.fields[f][1] for f in chunk]
+    assert list(c_hyper) == hyper and [c_hyper[f][0] for f in hyper] == [getattr(lib.AdamHyper, f).offset for f in hyper]
     assert [CHUNK_DTYPE.fields[f][0].itemsize for f in chunk] == [8] * 5 + [4, 4]
 
 
