@@ -94,7 +94,8 @@ def augment_flags(seed, mechanisms=("Horizontal", "Vertical", "Polarity"), probs
     """Flip decisions of H5Dataset.augment_event (dataloader/h5dataset.py:559-578) for one sample seed, as the bit
     flags bmc_encode_raw_events takes (bit0 horizontal, bit1 vertical, bit2 polarity).  Same seeding as the reference:
     random.seed(seed), seed+1, seed+2 for H / V / P, one random.random() draw each; the caller's `random` state is
-    left as the reference leaves it (re-seeded)."""
+    left as the reference leaves it (re-seeded).  "Transpose" (not the reference's; bit3, which only bmc_seq_encode_crop
+    reads) follows the pattern: random.seed(seed+3), one draw.  Other names are skipped."""
     import random
     flags = 0
     for i, mech in enumerate(mechanisms):
@@ -110,6 +111,10 @@ def augment_flags(seed, mechanisms=("Horizontal", "Vertical", "Polarity"), probs
             random.seed(seed + 2)
             if random.random() < probs[i]:
                 flags |= 4
+        elif mech == "Transpose":
+            random.seed(seed + 3)
+            if random.random() < probs[i]:
+                flags |= 8
     return flags
 
 
@@ -420,7 +425,8 @@ def encode_sequences(table, B, L, lr_size, gt_size, out=None):
     """The training batch of a DEVICE table of B bmc_seq_sample_t entries (uint8 tensor; event_dataset.SEQ_SAMPLE_DTYPE) ->
     (inp_cnt [B,L,2,H,W], gt_cnt [B,L,2,gh,gw]) float32: ONE bmc_seq_encode launch on the current stream (include/bmc_hip.h
     "sequence encoder for training").  The ranges of the table are trusted: event_dataset.EventTrainSet checks them when a
-    recording is added.  out: (inp_cnt, gt_cnt) to write into instead of new tensors."""
+    recording is added.  Bit 3 of an entry's `flips` (transpose) is ignored here: full frames have one size per launch.
+    out: (inp_cnt, gt_cnt) to write into instead of new tensors."""
     B, L = int(B), int(L)
     (H, W), (gh, gw) = (int(v) for v in lr_size), (int(v) for v in gt_size)
     if not (torch.is_tensor(table) and table.is_cuda and table.dtype == torch.uint8 and table.is_contiguous()):
@@ -443,8 +449,11 @@ def encode_sequence_crops(table, crops, B, L, crop, scale, out=None):
     """encode_sequences for patches: a DEVICE table of B bmc_seq_sample_t entries and, parallel to it, a DEVICE table of B
     bmc_seq_crop_t entries (uint8 tensors; event_dataset.SEQ_SAMPLE_DTYPE / SEQ_CROP_DTYPE) -> (inp_cnt [B,L,2,h,w], gt_cnt
     [B,L,2,scale*h,scale*w]) float32, crop = (h, w): ONE bmc_seq_encode_crop launch on the current stream (include/bmc_hip.h
-    "sequence encoder for training").  Every sample is cut out of its own full frames, which may differ in size.  The ranges
-    and the crops are trusted: event_dataset.EventTrainSet checks them.  out: (inp_cnt, gt_cnt) to write into."""
+    "sequence encoder for training").  Every sample is cut out of its own full frames, which may differ in size.  A sample
+    with bit 3 of its entry's `flips` set is cut out of its TRANSPOSED frames -- full.transpose(-1, -2)[..., top:top+h,
+    left:left+w], the origin in the transposed frames' rows / columns -- in the same launch; the crop entry keeps the
+    recording's own (H, W, gh, gw).  The ranges and the crops are trusted: event_dataset.EventTrainSet checks them.
+    out: (inp_cnt, gt_cnt) to write into."""
     B, L, scale = int(B), int(L), int(scale)
     h, w = (int(v) for v in crop)
     for name, t in (("table", table), ("crop table", crops)):

@@ -13,28 +13,79 @@
 //
 // bmc_seq_encode_crop (EventTrainSet(crop=...)) is the same body writing one patch per sample: the output frame is the patch,
 // the flips and the range test keep the sample's own full frame, and an event counts when its full-frame pixel lies in the band.
+// Bit 3 of a sample's flips transposes its frames (with the two flips: all 8 orientations of a patch): the patch is cut out
+// of the TRANSPOSED full frame, so x is the coordinate that picks the row -- tested first -- and fh-1-y the column; the
+// out-of-range negatives land at [0][fh-1].  The choice is the sample's, uniform per workgroup; bmc_seq_encode ignores the bit.
 #include "bmc_common.h"
 #include "slot_encode_k.h"
 
 namespace {
 
-// One event of a full frame fh x fw whose row test has passed (or whose band holds row fh-1 and column 0, `last`): the arithmetic
-// of slot_encode_body, on the flipped values.  The band starts at full-frame row f0 and, with CROP, at column `left`; it has
+// One event whose row test has passed (or whose band holds the landing pixel of the out-of-range negatives): the arithmetic of
+// slot_encode_body, on the flipped values.  (row, col): the event's pixel in the output orientation of the full frame, (qr, qc)
+// the landing pixel there -- [fh-1][0], transposed [0][fh-1].  The band starts at row f0 and, with CROP, at column `left`; it has
 // `rows` rows of pw pixels.
 template <bool CROP>
-__device__ __forceinline__ void seq_count(unsigned* cnt, int x, bool yin, int row, float p, int fh, int fw, int f0, int rows, int n,
+__device__ __forceinline__ void seq_count(unsigned* cnt, bool oob, int row, int col, float p, int qr, int qc, int f0, int rows, int n,
                                           int left, int pw) {
-    const bool oob = !yin || x < 0 || x >= fw;
     const bool neg = p < 0.f;
     if (!(neg || (!oob && p > 0.f))) return;                         // an out-of-range positive (or p = 0) counts nowhere
-    const int rr = (oob ? fh - 1 : row) - f0;                        // reset coordinates (0, 0) -> [fh-1][0] of channel 1
+    const int rr = (oob ? qr : row) - f0;                            // reset coordinates (0, 0) -> [fh-1][0] of channel 1
     if (rr < 0 || rr >= rows) return;
-    int c = oob ? 0 : x;
+    int c = oob ? qc : col;
     if constexpr (CROP) {
         c -= left;
         if (c < 0 || c >= pw) return;
     }
     atomicAdd(&cnt[(neg ? n : 0) + rr * pw + c], (unsigned)(p * p));
+}
+
+// A band's scan of its item's events and of the sample's noise.  TR (CROP only): the sample is transposed, so the coordinate that
+// picks the row -- the one read first, of every event -- is x against fw, and y picks the column; else y against fh picks the row.
+// One instantiation each, so that an untransposed sample runs the code it always ran.
+template <bool CROP, bool TR>
+__device__ __forceinline__ void seq_scan(unsigned* cnt, const bmc_seq_sample_t* ent, const short* xs, const short* ys, const double* ps,
+                                         long long e0, long long e1, int n_noise, unsigned fl, int fh, int fw, int f0, int rows, int n,
+                                         int left, int pw) {
+    static_assert(CROP || !TR, "full frames have one size per launch: bmc_seq_encode ignores bit 3");
+    const int tid = threadIdx.x;
+    const int na = TR ? fw : fh, nb = TR ? fh : fw;
+    const int qr = TR ? 0 : fh - 1, qc = TR ? fh - 1 : 0;            // where out-of-range negatives land: [fh-1][0], transposed
+    // only a band that holds that pixel reads the second coordinate and ps of every event
+    const bool last = qr >= f0 && qr < f0 + rows && qc >= left && qc < left + pw;
+    const bool fx = fl & 1u, fy = fl & 2u, fp = fl & 4u;
+    const bool fa = TR ? fx : fy, fb = TR ? fy : fx;
+    const short* const as = TR ? xs : ys;
+    const short* const bs = TR ? ys : xs;
+    for (long long e = e0 + tid; e < e1; e += ET) {
+        // augment_event's float64 flip and event_formatting's float32 cast are exact on int16 values: integers throughout
+        int a = (int)gld<short>(as + e);
+        if (fa) a = na - 1 - a;
+        const bool ain = a >= 0 && a < na;
+        const int row = TR ? a : fh - 1 - (ain ? a : 0);
+        if (!(last || (ain && row >= f0 && row < f0 + rows))) continue;
+        int c = (int)gld<short>(bs + e);
+        if (fb) c = nb - 1 - c;
+        float p = (float)gld<double>(ps + e);
+        if (fp) p = -p;
+        seq_count<CROP>(cnt, !ain || c < 0 || c >= nb, row, TR ? fh - 1 - c : c, p, qr, qc, f0, rows, n, left, pw);
+    }
+    if (n_noise > 0) {                                               // concatenated AFTER augment_event: never flipped
+        const short* const nx = gld<const short*>(&ent->noise_xs);
+        const short* const ny = gld<const short*>(&ent->noise_ys);
+        const signed char* const np = gld<const signed char*>(&ent->noise_ps);
+        const short* const nas = TR ? nx : ny;
+        const short* const nbs = TR ? ny : nx;
+        for (int e = tid; e < n_noise; e += ET) {
+            const int a = (int)gld<short>(nas + e);
+            const bool ain = a >= 0 && a < na;
+            const int row = TR ? a : fh - 1 - (ain ? a : 0);
+            if (!(last || (ain && row >= f0 && row < f0 + rows))) continue;
+            const int c = (int)gld<short>(nbs + e);
+            seq_count<CROP>(cnt, !ain || c < 0 || c >= nb, row, TR ? fh - 1 - c : c, (float)gld<signed char>(np + e), qr, qc, f0, rows, n,
+                            left, pw);
+        }
+    }
 }
 
 // The body of both kernels.  (H, W), (gh, gw): the OUTPUT frames -- the recording's with CROP false, the LR and HR patch with
@@ -90,34 +141,13 @@ __device__ __forceinline__ void seq_encode_body(unsigned* cnt, const bmc_seq_sam
     const int n = rows * pw;                                         // counters per channel: 2 * n <= ENC_LDS
     for (int i = tid; i < 2 * n; i += ET) cnt[i] = 0u;
     __syncthreads();
-    const int f0 = top + r0;                                         // the band's first row in the full frame
-    // [fh-1][0] is where out-of-range negatives land: only a band that holds it reads xs / ps of every event
-    const bool last = f0 + rows == fh && left == 0;
-    const bool fx = fl & 1u, fy = fl & 2u, fp = fl & 4u;
-    for (long long e = e0 + tid; e < e1; e += ET) {
-        // augment_event's float64 flip and event_formatting's float32 cast are exact on int16 values: integers throughout
-        int y = (int)gld<short>(ys + e);
-        if (fy) y = fh - 1 - y;
-        const bool yin = y >= 0 && y < fh;
-        const int row = fh - 1 - (yin ? y : 0);
-        if (!(last || (yin && row >= f0 && row < f0 + rows))) continue;
-        int x = (int)gld<short>(xs + e);
-        if (fx) x = fw - 1 - x;
-        float p = (float)gld<double>(ps + e);
-        if (fp) p = -p;
-        seq_count<CROP>(cnt, x, yin, row, p, fh, fw, f0, rows, n, left, pw);
-    }
-    if (n_noise > 0) {                                               // concatenated AFTER augment_event: never flipped
-        const short* const nx = gld<const short*>(&ent->noise_xs);
-        const short* const ny = gld<const short*>(&ent->noise_ys);
-        const signed char* const np = gld<const signed char*>(&ent->noise_ps);
-        for (int e = tid; e < n_noise; e += ET) {
-            const int y = (int)gld<short>(ny + e);
-            const bool yin = y >= 0 && y < fh;
-            const int row = fh - 1 - (yin ? y : 0);
-            if (!(last || (yin && row >= f0 && row < f0 + rows))) continue;
-            seq_count<CROP>(cnt, (int)gld<short>(nx + e), yin, row, (float)gld<signed char>(np + e), fh, fw, f0, rows, n, left, pw);
-        }
+    const int f0 = top + r0;                                         // the band's first row in the (transposed) full frame
+    bool tr = false;                                                 // the sample's choice: uniform in the workgroup
+    if constexpr (CROP) tr = fl & 8u;
+    if (tr) {
+        if constexpr (CROP) seq_scan<true, true>(cnt, ent, xs, ys, ps, e0, e1, n_noise, fl, fh, fw, f0, rows, n, left, pw);
+    } else {
+        seq_scan<CROP, false>(cnt, ent, xs, ys, ps, e0, e1, n_noise, fl, fh, fw, f0, rows, n, left, pw);
     }
     __syncthreads();
     float* const o0 = out + (long long)r0 * pw;

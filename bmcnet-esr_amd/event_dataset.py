@@ -11,6 +11,8 @@ EventTrainSet(crop=(h, w), scale=s) trains on patches: every sample is an h x w 
 origin per sequence (crop_origin, drawn from the sequence's own seed; batch(origins=...) overrides it) out of the recording's own
 frames, so recordings of different sensor sizes share a batch.  The crop happens in the encoder (bmc_seq_encode_crop): still one
 table copy and one launch per batch, which writes only the patches -- bit for bit the slices of the full-frame batch.
+With "Transpose" among the augmentation mechanisms (bit 3 of a sample's flags, this project's addition to the reference's three
+flips) a sample's patch comes out of its transposed frames, in the same launch: all 8 orientations of a patch.
 
 Out of scope, as in event_window_indices: HDF5 reading, the reference's 'time' / 'frame' modes, the hot-pixel filter (the
 reference never applies it in training)."""
@@ -54,12 +56,17 @@ def _pause_args(pause):
         raise ValueError("pause must be None or (proba_pause_when_running, proba_pause_when_paused)") from None
 
 
+TRANSPOSE = 8            # bit 3 of the flags: the sample's frames are transposed (patches only; bmc_seq_encode_crop)
+
+
 def _flags_on(rng, seed, mechanisms, probs):
     """bmc_hip.encodings.augment_flags' rule on `rng`: augment_event (dataloader/h5dataset.py:559-578) re-seeds with seed,
-    seed + 1, seed + 2 for Horizontal / Vertical / Polarity and draws once each; other names are skipped, as there."""
+    seed + 1, seed + 2 for Horizontal / Vertical / Polarity and draws once each; other names are skipped, as there.
+    "Transpose" is this project's fourth mechanism in the same pattern: bit 3, rng.seed(seed + 3), one draw; a list that does
+    not name it makes the calls it always made."""
     flags = 0
     for i, mech in enumerate(mechanisms):
-        bit = {"Horizontal": 0, "Vertical": 1, "Polarity": 2}.get(mech)
+        bit = {"Horizontal": 0, "Vertical": 1, "Polarity": 2, "Transpose": 3}.get(mech)
         if bit is None:
             continue
         rng.seed(seed + bit)
@@ -77,7 +84,8 @@ def sequence_plan(i, length, L, step_size=None, augment=None, pause=None, rng=ra
     and is not repeated here); between the items, with pause on, the chain's rng.random(), the item counter not advancing on a
     paused item (which is paired with the last item's ground truth).
     Kept, not fixed: with augmentation on every item re-seeds rng, so all pause draws of a sequence are the same number -- the
-    second draw after rng.seed(seed + 2) when Polarity is the last mechanism.  Item 0 is never paused.
+    second draw after rng.seed(seed + 2) when Polarity is the last mechanism, after rng.seed(seed + 3) when "Transpose" (bit3 of
+    the flags; EventTrainSet with crop only) is.  Item 0 is never paused.
     step_size None: L, as the reference.  augment: None or (mechanisms, probs); pause: None or (proba_pause_when_running,
     proba_pause_when_paused).  L > length raises: the reference shortens that one sequence and its collate then fails."""
     L, length = int(L), int(length)
@@ -132,13 +140,22 @@ def _max_origin(lr_size, gt_size, crop, scale):
     return min(H - h, (gh - scale * h) // scale), min(W - w, (gw - scale * w) // scale)
 
 
-def crop_origin(seed, lr_size, gt_size, crop, scale):
+def _oriented(size, transpose):
+    """(H, W, gh, gw) as the sample's output sees them: swapped to (W, H, gw, gh) for a transposed sample."""
+    H, W, gh, gw = size
+    return (W, H, gw, gh) if transpose else (H, W, gh, gw)
+
+
+def crop_origin(seed, lr_size, gt_size, crop, scale, transpose=False):
     """The patch origin (top, left), in LR image rows / columns, of a sequence with this seed (sequence_plan's): g =
     random.Random(seed); top = g.randint(0, max_top); left = g.randint(0, max_left), in that order, with max_top = min(H - h,
     (gh - scale * h) // scale) and max_left likewise -- the HR patch scale * (top, left) .. scale * (top + h, left + w) must fit
     a ground truth that may be smaller than scale x LR.  A generator of its own: the caller's rng is not touched, so cropping
-    changes no plan."""
+    changes no plan.  transpose: the origin of a transposed sample (bit 3 of its flags), in the transposed frames' rows / columns:
+    crop_origin on the swapped sizes (W, H), (gw, gh) -- the same draws in the same order."""
     lr_size, gt_size, crop = (tuple(int(v) for v in t) for t in (lr_size, gt_size, crop))
+    if transpose:
+        lr_size, gt_size = lr_size[::-1], gt_size[::-1]
     max_top, max_left = _max_origin(lr_size, gt_size, crop, int(scale))
     if max_top < 0 or max_left < 0:
         raise ValueError("crop_origin: a %dx%d patch (scale %d) does not fit frames %s -> %s" % (crop + (int(scale), lr_size, gt_size)))
@@ -166,7 +183,10 @@ class EventTrainSet:
     item the noise count is taken from (config['window']).  Sequence indices run over the recordings in the order they were
     added, (length - L) // step_size + 1 each, as ConcatDataset over SequenceDataset.
     crop: None (full frames; all recordings share one pair of sizes) or (h, w): batches of h x w LR patches and scale*h x scale*w
-    HR patches, from recordings of any sizes the patch fits."""
+    HR patches, from recordings of any sizes the patch fits.
+    augment may name "Transpose" (a set with crop only: full frames of one size cannot hold a transposed sample): with the two
+    flips, all 8 orientations of a patch.  The encoder cuts a transposed sample's patch out of its transposed frames, in the same
+    launch as the others; the patch must fit every recording in both orientations."""
     RING = 2
 
     def __init__(self, L=9, step_size=None, augment=None, pause=None, add_noise=None, window=2048, crop=None, scale=4):
@@ -180,7 +200,10 @@ class EventTrainSet:
         self.noise_level = None if add_noise is None else float(add_noise)
         self.window = int(window)
         self.n_noise = 0 if self.noise_level is None else int(self.window * self.noise_level)
-        self.crop, self.scale, self.last_origins = None, int(scale), None
+        self.crop, self.scale, self.last_origins, self.last_flips = None, int(scale), None, None
+        self.transposes = self.augment is not None and "Transpose" in self.augment[0]
+        if self.transposes and crop is None:
+            raise ValueError('EventTrainSet: "Transpose" needs crop: full frames of one size cannot hold a transposed sample')
         if crop is not None:
             try:
                 h, w = (int(v) for v in crop)
@@ -223,6 +246,9 @@ class EventTrainSet:
             if min(_max_origin((H, W), (gh, gw), self.crop, self.scale)) < 0:
                 raise ValueError(who + "the %dx%d patch (scale %d) does not fit the recording's %s -> %s"
                                  % (self.crop + (self.scale, (H, W), (gh, gw))))
+            if self.transposes and min(_max_origin((W, H), (gw, gh), self.crop, self.scale)) < 0:
+                raise ValueError(who + "the %dx%d patch (scale %d) does not fit the recording's %s -> %s transposed (%s -> %s)"
+                                 % (self.crop + (self.scale, (H, W), (gh, gw), (W, H), (gw, gh))))
         elif min(H, W, gh, gw) < 1 or max(W, gw) > MAX_WIDTH:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)" % (MAX_WIDTH, (H, W), (gh, gw)))
         elif self._size is not None and self._size != (H, W, gh, gw):
@@ -256,6 +282,10 @@ class EventTrainSet:
         r, i = self.locate(index)
         return (r,) + sequence_plan(i, len(self._recs[r]["lr_index"]), self.L, self.step_size, self.augment, self.pause, rng)
 
+    def _orientation(self, transposed):
+        """For messages: which frames of its recording a sample's plan drew; nothing where the set never transposes."""
+        return "" if not self.transposes else ", transposed: its plan drew the transpose" if transposed else ", not transposed"
+
     def _buffers(self, B):
         """Pinned host copies (a ring: one is rewritten only after the copy that last read it has completed) and the device
         buffer of B table entries followed by B crop entries (a set with crop) and B noise column sets; grown when a larger
@@ -276,7 +306,11 @@ class EventTrainSet:
         A set with crop = (h, w) returns the patches [B,L,2,h,w], [B,L,2,scale*h,scale*w] instead, from ONE bmc_seq_encode_crop
         launch (the crop entries travel in the same table copy, behind the sample entries): the slices of the full-frame batch
         at self.last_origins ([B,2] int64 numpy, (top, left) per sample), which are crop_origin of each plan's seed, or
-        `origins` (integer [B,2]) where given.  The noise is drawn against each recording's own LR size."""
+        `origins` (integer [B,2]) where given.  The noise is drawn against each recording's own LR size.
+        self.last_flips ([B] int64 numpy) holds each sample's flags.  A sample whose plan drew bit 3 ("Transpose") is the patch
+        of its TRANSPOSED frames: full_inp[b].transpose(-1, -2)[..., top:top+h, left:left+w], its origin (crop_origin(...,
+        transpose=True), or the one given) and its entry of last_origins in the transposed frames' rows / columns.  origins are
+        checked after the plans are made, each against the orientation its sample drew; a refused batch leaves rng as it was."""
         global ENCODE_LAUNCHES
         from bmc_hip.encodings import encode_sequence_crops, encode_sequences
         who = "EventTrainSet.batch: "
@@ -291,13 +325,18 @@ class EventTrainSet:
             if origins.shape != (B, 2) or origins.dtype.kind not in "iu":
                 raise ValueError(who + "origins must be an integer [%d,2] array (got %s %s)" % (B, origins.dtype, origins.shape))
             origins = origins.astype(np.int64)
-            for v, (top, left) in zip(indices, origins.tolist()):
-                size = self._recs[self.locate(v)[0]]["size"]
+        state = None if origins is None else rng.getstate()
+        plans = [self.plan(v, rng) for v in indices]
+        if origins is not None:                                      # against the orientation each sample's plan drew
+            for v, plan, (top, left) in zip(indices, plans, origins.tolist()):
+                tr = bool(plan[4] & TRANSPOSE)
+                size = _oriented(self._recs[plan[0]]["size"], tr)
                 max_top, max_left = _max_origin(size[:2], size[2:], self.crop, self.scale)
                 if not (0 <= top <= max_top and 0 <= left <= max_left):
+                    rng.setstate(state)                              # a refused batch has drawn nothing
                     raise ValueError(who + "origin (%d, %d) of sequence %d lies outside (0, 0) .. (%d, %d), where the %dx%d patch "
-                                     "fits its recording's %s -> %s" % ((top, left, v, max_top, max_left) + self.crop + (size[:2], size[2:])))
-        plans = [self.plan(v, rng) for v in indices]
+                                     "fits its recording's %s -> %s%s" % ((top, left, v, max_top, max_left) + self.crop +
+                                                                         (size[:2], size[2:], self._orientation(tr))))
         L, nn = self.L, self.n_noise
         nbytes = self._buffers(B)
         k = self._k
@@ -322,8 +361,9 @@ class EventTrainSet:
             tab["flips"][b] = flips
             tab["paused"][b] = sum(1 << t for t, p in enumerate(paused) if p)
             if self.crop is not None:
-                used[b] = origins[b] if origins is not None else crop_origin(seed, (H, W), (gh, gw), self.crop, self.scale)
-                crops[b] = (H, W, gh, gw, used[b, 0], used[b, 1])
+                used[b] = origins[b] if origins is not None else crop_origin(seed, (H, W), (gh, gw), self.crop, self.scale,
+                                                                             bool(flips & TRANSPOSE))
+                crops[b] = (H, W, gh, gw, used[b, 0], used[b, 1])    # the recording's own sizes, never swapped
             if nn:
                 off = noise_off + b * stride
                 xs, ys, ps = noise_events(self.window, (H, W), seed, self.noise_level)
@@ -342,6 +382,7 @@ class EventTrainSet:
             else:
                 out = encode_sequence_crops(self._table, self._table[crop_off:noise_off], B, L, self.crop, self.scale)
                 self.last_origins = used
+        self.last_flips = np.asarray([p[4] for p in plans], np.int64)
         ENCODE_LAUNCHES += 1
         return out
 

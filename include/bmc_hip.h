@@ -571,7 +571,9 @@ int bmc_slot_encode(const bmc_slot_events_t* table, int S, int seqn, int H, int 
  * the result is the float32 sum of the reference.  The scheme is bmc_slot_encode's: a workgroup owns a band of rows of one
  * frame, at most 60 KB of LDS counters, integer LDS atomics, stored once (the store is the zero fill) -- no global atomics, no
  * memset, order independent and run-to-run identical.  Limits the CALLER checks and the kernel trusts: every range inside its
- * columns, first <= end; checked here: 2 <= L <= BMC_SEQ_MAX_ITEMS, W, gw <= 7680, 1 <= B <= 65535. */
+ * columns, first <= end; checked here: 2 <= L <= BMC_SEQ_MAX_ITEMS, W, gw <= 7680, 1 <= B <= 65535.
+ * Bit 3 of `flips` (transpose) means something to bmc_seq_encode_crop only: bmc_seq_encode has one output size per launch, which
+ * a transposed frame does not have, and ignores the bit -- flips | 8 gives the bytes of flips & 7. */
 #define BMC_SEQ_MAX_ITEMS 32
 typedef struct bmc_seq_sample {           /* one sequence of the batch */
     const short* lr_xs;     /* its recording's LR columns */
@@ -584,7 +586,8 @@ typedef struct bmc_seq_sample {           /* one sequence of the batch */
     const short* noise_ys;
     const signed char* noise_ps;
     int n_noise;
-    unsigned flips;         /* bit0 horizontal, bit1 vertical, bit2 polarity (as bmc_encode_raw_events) */
+    unsigned flips;         /* bit0 horizontal, bit1 vertical, bit2 polarity (as bmc_encode_raw_events); bit3 transpose:
+                               bmc_seq_encode_crop only (below), ignored by bmc_seq_encode; higher bits are ignored */
     unsigned paused;        /* bit t: item t is a paused frame */
     long long lr_range[BMC_SEQ_MAX_ITEMS][2];   /* events [first, end) of LR item t; ranges may overlap */
     long long gt_range[BMC_SEQ_MAX_ITEMS][2];
@@ -604,10 +607,24 @@ int bmc_seq_encode(const bmc_seq_sample_t* table, int B, int L, int H, int W, in
  * it holds the full frame's [fh-1][0] (left == 0 and the band covers row fh-1).  Checked here: 1 <= B <= 65535, 2 <= L <=
  * BMC_SEQ_MAX_ITEMS, scale >= 1, h, w >= 1, scale * w <= 7680 (the limit is the patch's, not the recording's).  The CALLER
  * checks and the kernel trusts: every range inside its columns, and the crop inside the frames: top, left >= 0, top + h <= H,
- * left + w <= W, scale * (top + h) <= gh, scale * (left + w) <= gw. */
+ * left + w <= W, scale * (top + h) <= gh, scale * (left + w) <= gw.
+ * Transpose (bit 3 of the sample's `flips`; with the two flips it gives all 8 orientations of a patch -- rot90 is one flip followed
+ * by the transpose).  Let F_lr[b] [L][2][H][W] and F_gt[b] [L][2][gh][gw] be what bmc_seq_encode writes for the same entry with
+ * flips & 7 at the sample's own sizes: flips before the range test, the out-of-range quirk, the unflipped noise and the paused
+ * items included.  Bit 3 clear: the slices above, as ever.  Bit 3 set, s = scale:
+ *   inp_cnt[b] = F_lr[b].transpose(-1,-2)[..., top:top+h, left:left+w]
+ *   gt_cnt[b]  = F_gt[b].transpose(-1,-2)[..., s*top:s*(top+h), s*left:s*(left+w)]
+ * The transpose acts on the finished image and carries the noise and the quirk pixel with it: the full frame's [fh-1][0] of
+ * channel 1 is [0][fh-1] of the transposed frame and is in the patch only when top == 0 and left <= fh-1 < left + w (scaled
+ * likewise for HR).  top and left are rows / columns of the TRANSPOSED frame, and the caller checks top + h <= W, left + w <= H,
+ * s * (top + h) <= gw, s * (left + w) <= gh.  So the transposed h x w patch at (top, left) is the transpose of the untransposed
+ * w x h patch at (left, top).  Samples with and without the bit share the launch (the choice is uniform per workgroup); the scheme
+ * is unchanged: a band of a transposed sample tests the coordinate that becomes its row first -- xs, after its flip against fw --
+ * and reads ys / ps only of events that can land in it, except the band that holds [0][fh-1], which reads everything. */
 typedef struct bmc_seq_crop {   /* one per sample, parallel to the bmc_seq_sample_t table */
-    int H, W, gh, gw;           /* the sample's OWN full frame sizes (flips and the out-of-range rule use these) */
-    int top, left;              /* patch origin in LR IMAGE rows / columns (row 0 = sensor y = H-1) */
+    int H, W, gh, gw;           /* the sample's OWN full frame sizes (flips and the out-of-range rule use these), never swapped */
+    int top, left;              /* patch origin in LR IMAGE rows / columns (row 0 = sensor y = H-1); of a transposed sample: in
+                                   the transposed image (row 0 = sensor x = 0, column 0 = sensor y = H-1) */
 } bmc_seq_crop_t;
 int bmc_seq_encode_crop(const bmc_seq_sample_t* table, const bmc_seq_crop_t* crops, int B, int L, int h, int w, int scale,
                         float* inp_cnt, float* gt_cnt, bmc_stream_t s);

@@ -13,11 +13,14 @@ branch of train.py:227-231 -- inside bptt_step's fused head + loss launches.
 python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x80] [--steps 10] [--batch 2] [--L 9] [--step-size S]
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
-                             [--gt-size HxW] [--valid-every N] [--crop HxW]
+                             [--gt-size HxW] [--valid-every N] [--crop HxW] [--transpose [P]]
 --crop HxW: train on HxW LR patches (and scale x that HR patches) cut in the encoder, one random origin per sequence
 (EventTrainSet(crop=...), ONE bmc_seq_encode_crop launch per batch).  --size and --gt-size then take comma-separated lists the
 synthetic recordings cycle through (--size 180x240,260x346), a set of mixed sensors; recordings given as files may differ in size
 too.  Validation stays on full frames.
+--transpose [P]: with --crop, "Transpose" joins the augmentation at probability P (0.5): a sample that draws it is the patch of
+its transposed frames, cut in the same launch -- with --augment's flips, all 8 orientations of a patch.  It implies no flips;
+the patch must fit every recording both ways.  Validation stays on untransposed full frames.
 --valid-every N: the last recording is held out of training; after every N steps train_step.valid_step (the reference's _valid
 loop: eval mode, no gradients, the same loss) runs over its sequences in order and `valid_loss`, their mean, is printed.
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
@@ -97,9 +100,13 @@ def main():
     ap.add_argument("--gt-size", default=None, help="HxW of the synthetic recordings' ground truth (default: scale x --size)")
     ap.add_argument("--valid-every", type=int, default=0, help="hold the last recording out and print valid_loss every N steps")
     ap.add_argument("--crop", default=None, help="HxW of the LR patches to train on; --size / --gt-size may then be lists")
+    ap.add_argument("--transpose", type=float, nargs="?", const=0.5, default=None, metavar="P",
+                    help="with --crop: transpose a sample's frames with probability P (default 0.5)")
     a = ap.parse_args()
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
+    if a.transpose is not None and not a.crop:
+        ap.error("--transpose needs --crop: full frames of one size cannot hold a transposed sample")
     dev = torch.device("cuda:0")
     hw = lambda text: tuple(int(v) for v in text.split("x"))
     sizes = [hw(t) for t in a.size.split(",")]
@@ -114,7 +121,9 @@ def main():
         os.makedirs(a.save, exist_ok=True)
         for k, r in enumerate(recs[len(a.recordings):]):
             np.savez(os.path.join(a.save, "synthetic%d.npz" % k), **r)
-    ts = EventTrainSet(L=a.L, step_size=a.step_size, augment=(("Horizontal", "Vertical", "Polarity"), (0.5, 0.5, 0.5)) if a.augment else None,
+    mechanisms = (("Horizontal", "Vertical", "Polarity") if a.augment else ()) + (("Transpose",) if a.transpose is not None else ())
+    probs = (0.5,) * (3 if a.augment else 0) + ((a.transpose,) if a.transpose is not None else ())
+    ts = EventTrainSet(L=a.L, step_size=a.step_size, augment=(mechanisms, probs) if mechanisms else None,
                        pause=tuple(float(v) for v in a.pause.split(",")) if a.pause else None, add_noise=a.noise, window=a.window,
                        crop=crop, scale=a.scale)
     vs = None
@@ -128,6 +137,7 @@ def main():
     for r in recs:
         add(ts, r, dev, a.window, a.sliding, a.scale)
     print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) + (", %dx%d patches" % crop if crop else "") +
+          (", transposed with probability %g" % a.transpose if a.transpose is not None else "") +
           (", %d held-out sequences" % len(vs) if vs is not None else ""))
     random.seed(a.seed)
     torch.manual_seed(a.seed)
@@ -156,6 +166,8 @@ def main():
             loss, mse = bptt_step(m, opt, inp, gt, a.n_c, a.scale)
             loss = float(loss)
             rows.append(dict(step=step, epoch=epoch, sequences=idx, loss=loss, encode_ms=round(t0.elapsed_time(t1), 4)))
+            if a.transpose is not None:
+                rows[-1]["transposed"] = int((ts.last_flips & 8 != 0).sum())
             print("step %d  loss %.6f  encode %.3f ms  sequences %s" % (step, loss, rows[-1]["encode_ms"], idx))
             step += 1
             if vs is not None and step % a.valid_every == 0:
