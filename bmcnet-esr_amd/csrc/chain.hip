@@ -65,21 +65,38 @@ __device__ __forceinline__ f32x4 mfma16(float a, float b, f32x4 c) {
     return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
 }
 
-template <int NT, bool BWD>
+// PAIR (forward only): a unit is the pixel tile of batch b TOGETHER with the same tile of batch b + n (n = B / 2) of a
+// launch whose s0 maps both to one image (the twin layout: s0 = xs with mod = n).  W_f[:, :C] s0 + b_f is then the same
+// bits for both, so it is computed once and kept in Rz: 5 NR steps per pair instead of 6 NR for two units, and the shared
+// s0 chunks are fetched once.  Each accumulator's MFMA chain is instruction for instruction that of the unpaired kernel.
+// 16-byte store to global memory (the address went through integers: without the address space it would be a flat store)
+__device__ __forceinline__ void stg16(float* p, f32x4 v) {
+    *(__attribute__((address_space(1))) f32x4*)(unsigned long long)p = v;
+}
+
+template <int NT, bool BWD, bool PAIR = false>
 __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
+    static_assert(!(BWD && PAIR), "the backward always walks pairs");
     constexpr int C = 16 * NT;
     constexpr int NR = NT;                        // steps of one register-operand GEMM (K = C, 16 per step)
-    constexpr int NS = BWD ? 5 * NR : 3 * NR;     // steps per unit
-    constexpr int NXC = 2 * NR;                   // X chunks per unit (two segments of C channels)
+    constexpr int NS = (BWD || PAIR) ? 5 * NR : 3 * NR;     // steps per unit
+    constexpr int NSEG = PAIR ? 3 : 2;            // X segments of C channels per unit
+    constexpr int NXC = NSEG * NR;                // X chunks per unit
     constexpr int DX = 6, NXR = 8, DW = 3, NWR = 5;
     constexpr int XSLOT = NPX * CK, WSLOT = C * CK;          // floats per ring slot
     constexpr int NDX = NPX / 32;                 // DMA instructions (16 rows = 1 KB each) per X wave and chunk
     constexpr int NDW = (C + 31) / 32;            // ... per W wave and slice
-    __shared__ __attribute__((aligned(16))) float lds[NXR * XSLOT + NWR * WSLOT + 2 * 8 + 5 * C];
-    float* const Xb = lds;
-    float* const Wb = lds + NXR * XSLOT;
-    SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + NXR * XSLOT + NWR * WSLOT);
-    float* const img = lds + NXR * XSLOT + NWR * WSLOT + 2 * 8;     // [0] b_f | 0   [1] b_c | 0   [2] gamma   [3] beta   [4] zeros
+    // The per-channel vectors sit at the START of LDS: every read of them is then one lane-dependent base register plus an
+    // immediate offset.  Behind the rings (past 64 KB, beyond the reach of a ds_read's offset field) the compiler kept one
+    // address register per vector and channel tile alive across the whole unit loop, ~30 at C = 128.  The rings follow 16-byte
+    // aligned: shifting every address of a ds_read_b128 or a DMA image by one multiple of 16 B rotates the banks and changes
+    // no conflict.
+    constexpr int HEAD = 5 * C + 2 * 8;                      // floats
+    __shared__ __attribute__((aligned(16))) float lds[HEAD + NXR * XSLOT + NWR * WSLOT];
+    float* const img = lds;                                  // [0] b_f | 0   [1] b_c | 0   [2] gamma   [3] beta   [4] zeros
+    SrcDev* const tab = reinterpret_cast<SrcDev*>(lds + 5 * C);
+    float* const Xb = lds + HEAD;
+    float* const Wb = lds + HEAD + NXR * XSLOT;
     const unsigned xb_lds = lds_addr(Xb), wb_lds = lds_addr(Wb);
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -99,8 +116,9 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     using UnitIt = Tile3;         // (no channel tiles: nt = 0)
     auto decode = [&](int t) { return tile_decode(t, 1, a.tiles_x, a.tiles_y); };
 
-    // ---- X ring loader (waves 0-1): chunks of 16 channels in consumption order; a unit has two segments of C channels
-    //      (fwd: s0 then s1 at batch b; bwd: dcentre at batch b then at batch b + n).  Instruction i of X wave w covers the
+    // ---- X ring loader (waves 0-1): chunks of 16 channels in consumption order; a unit has NSEG segments of C channels
+    //      (fwd: s0 then s1 at batch b; paired fwd: s0 at b, s1 at b, s1 at b + n; bwd: dcentre at batch b then at
+    //      batch b + n).  Instruction i of X wave w covers the
     //      16 tile pixels [(NDX w + i) * 16, +16) = tile row NDX w + i, 4 lanes per pixel row; lane (pixel p, position q')
     //      fetches quad q' ^ swz(p).  Pixels outside the image re-read the clamped edge pixel: their columns of the result
     //      are never stored, and a pixel's column never mixes with another's.
@@ -112,8 +130,8 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     unsigned xvoff[NDX];          // byte offset from the segment's batch pointer (segment-dependent: pixel stride)
     const int xq = ((lane & 3) ^ swz(lane >> 2)) * 4;         // row index within the instruction = lane / 4
     auto seg_select = [&]() {
-        const SrcDev S = tab[BWD ? 0 : xl_seg];
-        sbase = src_batch_ptr(S, BWD ? xl_it.b + xl_seg * a.n : xl_it.b);
+        const SrcDev S = tab[BWD ? 0 : PAIR ? (xl_seg ? 1 : 0) : xl_seg];
+        sbase = src_batch_ptr(S, BWD ? xl_it.b + xl_seg * a.n : (PAIR && xl_seg == 2) ? xl_it.b + a.n : xl_it.b);
 #pragma unroll
         for (int i = 0; i < NDX; ++i) xvoff[i] = (unsigned)(xpixq[i] * S.pix_stride + xq) * 4u;
     };
@@ -138,7 +156,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         c_in += CK;
         if (c_in >= C) {
             c_in = 0;
-            if (++xl_seg == 2) {
+            if (++xl_seg == NSEG) {
                 xl_unit += t_stride;
                 if (xl_unit < t_hi) { xl_it = decode(xl_unit); xl_setup(); }
             } else {
@@ -146,7 +164,9 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
             }
         }
     };
-    // ---- W ring loader (waves 2-3): NS slices per unit, the same for every unit
+    // ---- W ring loader (waves 2-3): NS slices per unit, the same for every unit.  The paired forward's stream is the
+    //      unpaired one (W_f | W_c, 3 NR slices): steps 3 NR .. 5 NR - 1 (the second half's s1 and clustering phases)
+    //      read slices NR .. 3 NR - 1 again.
     int wl_step = 0, wl_cnt = 0;
     unsigned wvoff[NDW];
     bool wact[NDW];
@@ -157,7 +177,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         wvoff[i] = (unsigned)(row * 64 + (((lane & 3) ^ swz(row)) * 16));
     }
     auto issue_w = [&]() {
-        const float* p = a.w + (long long)wl_step * WSLOT;
+        const float* p = a.w + (long long)((PAIR && wl_step >= 3 * NR) ? wl_step - 2 * NR : wl_step) * WSLOT;
         const unsigned dst = wb_lds + (unsigned)(((wl_cnt % NWR) * WSLOT + (wave & 1) * NDW * 256) * 4);
 #pragma unroll
         for (int i = 0; i < NDW; ++i)
@@ -177,7 +197,7 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         for (int t = 0; t < NT; ++t) bf[t] = *reinterpret_cast<const f32x4*>(wb + brow + 16 * t * CK);
     };
 
-    f32x4 Ra[NT], Rt[NT], Rz[BWD ? NT : 1];
+    f32x4 Ra[NT], Rt[NT], Rz[(BWD || PAIR) ? NT : 1];
     auto init_acc = [&](f32x4 (&R)[NT], int which) {
 #pragma unroll
         for (int t = 0; t < NT; ++t) R[t] = *reinterpret_cast<const f32x4*>(img + which * C + 16 * t + 4 * lg);
@@ -260,22 +280,65 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
     int ep_unit = t_first;
     bool pok = false;
     int pix = 0;
+    long long row0 = 0;           // wave-uniform: the first pixel of the wave's tile row
     auto ep_setup = [&]() {
-        const int y = ep_it.ty * TH + wave, x = ep_it.tx * TW + lp;
+        const int y = ep_it.ty * TH + wave, x0 = ep_it.tx * TW, x = x0 + lp;
         pok = y < a.H && x < a.W;
         pix = y * a.W + x;
+        row0 = (long long)y * a.W + x0;
     };
     const long long img_elems = (long long)a.H * a.W;
+    // A store's address = wave-uniform 64-bit part (plane, tile row; pinned to scalar registers, or the compiler folds the
+    // lane offset into the loop-invariant plane pointer instead) + this lane's constant 32-bit offset: one register for the
+    // whole kernel where per-lane 64-bit pointers to each output were kept alive across the unit loop.
+    const unsigned lane_off = (unsigned)(lp * C + 4 * lg);
+    auto uniform = [](float* p) {
+        const unsigned long long v = reinterpret_cast<unsigned long long>(p);
+        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
+        return reinterpret_cast<float*>(((unsigned long long)hi << 32) | lo);
+    };
     auto store_tile = [&](const f32x4 (&R)[NT], float* base) {     // base: batch plane [H][W][C]
         if (!pok) return;
-        float* p = base + (long long)pix * C + 4 * lg;
+        float* p = uniform(base + row0 * C) + lane_off;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) *reinterpret_cast<f32x4*>(p + 16 * t) = R[t];
+        for (int t = 0; t < NT; ++t) stg16(p + 16 * t, R[t]);
     };
     auto wsum = [&](float v) {      // over the four lanes (channel quads) that share a pixel
         v += __shfl_xor(v, 16);
         v += __shfl_xor(v, 32);
         return v;
+    };
+
+    // ---- forward: LayerNorm over the C channels of each pixel of z in Ra (4 NT registers in each of the pixel's four
+    //      lanes); stores yhat and rstd at batch bb and leaves y = yhat*gamma + beta in Ra
+    auto layer_norm = [&](int bb) {
+        float rstd;
+        {
+            float s = 0.f;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) s += (Ra[t][0] + Ra[t][1]) + (Ra[t][2] + Ra[t][3]);
+            const float mu = wsum(s) * (1.f / C);
+            float q = 0.f;
+#pragma unroll
+            for (int t = 0; t < NT; ++t)
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const float d = Ra[t][k] - mu;
+                    Ra[t][k] = d;
+                    q += d * d;
+                }
+            rstd = 1.f / sqrtf(wsum(q) * (1.f / C) + a.eps);
+#pragma unroll
+            for (int t = 0; t < NT; ++t) Ra[t] *= rstd;
+        }
+        store_tile(Ra, a.out0 + (long long)bb * img_elems * C);
+        if (pok && lg == 0) a.out2[(long long)bb * img_elems + pix] = rstd;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const f32x4 gq = *reinterpret_cast<const f32x4*>(img + 2 * C + 16 * t + 4 * lg);
+            const f32x4 bq = *reinterpret_cast<const f32x4*>(img + 3 * C + 16 * t + 4 * lg);
+            Ra[t] = Ra[t] * gq + bq;
+        }
     };
 
     // ---- prologue: fill the rings DX / DW stages deep, publish stage 0
@@ -298,40 +361,33 @@ __global__ __launch_bounds__(256, 2) void chain_kernel(const ChainK a) {
         ep_setup();
         const bool more_units = ep_unit + t_stride < t_hi;
         if constexpr (!BWD) {
-            // ---- z = convf(cat[s0, s1]) + b_f
-            for (int i = 0; i < NXC; i += 2) lds_pair(Ra, i + 2 < NXC);
-            // ---- LayerNorm over the C channels of each pixel: 4 NT registers in each of the pixel's four lanes
-            float rstd;
-            {
-                float s = 0.f;
+            if constexpr (!PAIR) {
+                // ---- z = convf(cat[s0, s1]) + b_f
+                for (int i = 0; i < NXC; i += 2) lds_pair(Ra, i + 2 < NXC);
+                layer_norm(ep_it.b);
+                // ---- centre = clustering(y) + b_c, pixel operand = the registers of y
+                init_acc(Rt, 1);
+                reg_steps(Ra, Rt, more_units);
+                store_tile(Rt, a.out1 + (long long)ep_it.b * img_elems * C);
+            } else {
+                // ---- the shared half of z: b_f + W_f[:, :C] s0, kept in Rz for the second batch
+                for (int i = 0; i < NR; i += 2) lds_pair(Ra, true);
 #pragma unroll
-                for (int t = 0; t < NT; ++t) s += (Ra[t][0] + Ra[t][1]) + (Ra[t][2] + Ra[t][3]);
-                const float mu = wsum(s) * (1.f / C);
-                float q = 0.f;
+                for (int t = 0; t < NT; ++t) Rz[t] = Ra[t];
+                // ---- batch b, then batch b + n: + W_f[:, C:] s1, LayerNorm, clustering
+                for (int half = 0; half < 2; ++half) {
+                    const int bb = ep_it.b + half * a.n;
+                    for (int i = 0; i < NR; i += 2) lds_pair(Ra, i + 2 < NR);
+                    layer_norm(bb);
+                    init_acc(Rt, 1);
+                    reg_steps(Ra, Rt, half == 0 || more_units);
+                    store_tile(Rt, a.out1 + (long long)bb * img_elems * C);
+                    if (half == 0) {
 #pragma unroll
-                for (int t = 0; t < NT; ++t)
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        const float d = Ra[t][k] - mu;
-                        Ra[t][k] = d;
-                        q += d * d;
+                        for (int t = 0; t < NT; ++t) Ra[t] = Rz[t];
                     }
-                rstd = 1.f / sqrtf(wsum(q) * (1.f / C) + a.eps);
-#pragma unroll
-                for (int t = 0; t < NT; ++t) Ra[t] *= rstd;
+                }
             }
-            store_tile(Ra, a.out0 + (long long)ep_it.b * img_elems * C);
-            if (pok && lg == 0) a.out2[(long long)ep_it.b * img_elems + pix] = rstd;
-#pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                const f32x4 gq = *reinterpret_cast<const f32x4*>(img + 2 * C + 16 * t + 4 * lg);
-                const f32x4 bq = *reinterpret_cast<const f32x4*>(img + 3 * C + 16 * t + 4 * lg);
-                Ra[t] = Ra[t] * gq + bq;
-            }
-            // ---- centre = clustering(y) + b_c, pixel operand = the registers of y
-            init_acc(Rt, 1);
-            reg_steps(Ra, Rt, more_units);
-            store_tile(Rt, a.out1 + (long long)ep_it.b * img_elems * C);
             init_acc(Ra, 0);
         } else {
             // dz of BOTH halves stays in registers (Rz: batch b, Ra: batch b + n): the shared stream's gradient needs
@@ -434,13 +490,14 @@ __global__ __launch_bounds__(1024) void affine_grads_kernel(const float* G, cons
     }
 }
 
-int launch(const ChainK& k, int C, bool bwd, hipStream_t st) {
+int launch(const ChainK& k, int C, bool bwd, bool pair, hipStream_t st) {
     const int cus = bmc_num_cus();
     const int max_blocks = 2 * cus;      // resident workgroups per CU (LDS rings: ~75 KB per workgroup at C = 128)
     dim3 grid((unsigned)(k.nunits < max_blocks ? k.nunits : max_blocks)), block(256);
 #define BMC_LAUNCH_CHAIN(NU_)                                                                    \
     do {                                                                                          \
         if (bwd) hipLaunchKernelGGL((chain_kernel<NU_, true>), grid, block, 0, st, k);            \
+        else if (pair) hipLaunchKernelGGL((chain_kernel<NU_, false, true>), grid, block, 0, st, k); \
         else hipLaunchKernelGGL((chain_kernel<NU_, false>), grid, block, 0, st, k);               \
     } while (0)
     if (C == 128) BMC_LAUNCH_CHAIN(8);
@@ -452,6 +509,33 @@ int launch(const ChainK& k, int C, bool bwd, hipStream_t st) {
 
 bool src_ok(const bmc_src_t& s, int C) {
     return s.ptr && s.nch == C && s.pix_stride % 4 == 0 && s.batch_stride % 4 == 0 && ((uintptr_t)s.ptr & 15) == 0;
+}
+
+// Host image of src_batch_ptr: the element offset of launch batch b.
+long long src_batch_off(const bmc_src_t& s, int b) {
+    long long bs = (long long)b + s.batch_shift;
+    if (s.batch_mod > 0) bs %= s.batch_mod;
+    return bs * s.batch_stride;
+}
+
+// The forward launch can walk pairs (b, b + B/2) when s0 gives both batches of every pair the same image.
+// -> nullptr, or the reason why not.
+const char* fwd_unpairable(const bmc_chain_fwd_args_t& h) {
+    if (h.B % 2) return "B is odd";
+    if (h.s0.batch_mod == BMC_SRC_TABLE) return "s0 is a pointer table";
+    const int n = h.B / 2;
+    for (int b = 0; b < n; ++b)
+        if (src_batch_off(h.s0, b) != src_batch_off(h.s0, b + n)) return "s0 maps batches b and b + B/2 to different images";
+    return nullptr;
+}
+
+// Pair when the fullest CU then runs fewer steps.  A pair costs 5 NR steps where a unit costs 3 NR, and the two workgroups
+// resident on a CU share its matrix pipes, so the launch takes as long as the CU with the most steps: 5 ceil(P / CUs)
+// against 3 ceil(2P / CUs) for P pairs.  (Counting rounds of the 2 x CUs workgroups instead mispredicted three of ten
+// measured shapes: NOTEBOOK R11.)  Up to one pair per CU the launch stays unpaired: a single workgroup on a CU cannot hide
+// its own LayerNorm and barrier phases, and two 3 NR units beside each other measured faster than one 5 NR pair.
+bool fwd_pair_rule(long long pairs, int cus) {
+    return pairs > cus && 5 * ((pairs + cus - 1) / cus) < 3 * ((2 * pairs + cus - 1) / cus);
 }
 
 }  // namespace
@@ -471,10 +555,23 @@ extern "C" int bmc_chain_fwd(const bmc_chain_fwd_args_t* h, bmc_stream_t stream)
     k.out0 = h->yhat; k.out1 = h->centre; k.out2 = h->rstd;
     k.nb = h->B; k.n = 0; k.H = h->H; k.W = h->W;
     k.tiles_x = (h->W + TW - 1) / TW; k.tiles_y = (h->H + TH - 1) / TH;
-    const long long nu = (long long)h->B * k.tiles_x * k.tiles_y;
+    long long nu = (long long)h->B * k.tiles_x * k.tiles_y;
     BMC_CHECK_ARG(nu < (1ll << 31), "bmc_chain_fwd: too many tiles");
+    // BMC_CHAIN_PAIR (tests and experiments, read per launch): 0 = never pair, 1 = pair or refuse, unset = the rule
+    const char* const e = getenv("BMC_CHAIN_PAIR");
+    const int mode = e ? atoi(e) : -1;
+    bool pair = false;
+    if (mode != 0) {
+        const char* const why = fwd_unpairable(*h);
+        BMC_CHECK_ARG(mode != 1 || !why, "bmc_chain_fwd: BMC_CHAIN_PAIR=1 but the launch cannot be paired: %s", why);
+        pair = !why && (mode == 1 || fwd_pair_rule(nu / 2, bmc_num_cus()));
+    }
+    if (pair) {
+        nu /= 2;
+        k.nb = h->B / 2; k.n = h->B / 2;
+    }
     k.nunits = (int)nu;
-    launch(k, h->C, false, (hipStream_t)stream);
+    launch(k, h->C, false, pair, (hipStream_t)stream);
     BMC_CHECK_LAUNCH("bmc_chain_fwd");
     return 0;
 }
@@ -499,7 +596,7 @@ extern "C" int bmc_chain_bwd(const bmc_chain_bwd_args_t* h, bmc_stream_t stream)
     const long long nu = (long long)h->n * k.tiles_x * k.tiles_y;
     BMC_CHECK_ARG(nu < (1ll << 31), "bmc_chain_bwd: too many tiles");
     k.nunits = (int)nu;
-    launch(k, h->C, true, (hipStream_t)stream);
+    launch(k, h->C, true, false, (hipStream_t)stream);
     BMC_CHECK_LAUNCH("bmc_chain_bwd");
     return 0;
 }

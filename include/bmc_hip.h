@@ -383,7 +383,13 @@ int bmc_head_mse_bwd(const float* dpred, const float* pred, const float* gt, lon
  * (before the affine) and rstd.  C = channels of s0, s1, yhat, centre: 32, 64 or 128.  All outputs are contiguous
  * [B][H][W][C] (rstd [B][H][W]).
  * wstream: 3C/16 slices of [C][16] floats = bmc_pack_weight(W_f, Kpad = 2C, Coutpad = C) followed by
- * bmc_pack_weight(W_c, Kpad = C, Coutpad = C). */
+ * bmc_pack_weight(W_c, Kpad = C, Coutpad = C).
+ * Paired launches: where B is even and s0 gives launch batches b and b + B/2 the same image for every b < B/2 (the twin
+ * layout: s0 with batch_mod = B/2), the kernel may walk the two batches of a pixel tile together and compute the half of
+ * convf they share once -- same arguments, same weight stream, bit-identical outputs.  The host decides per launch (more
+ * than one pair per CU, and fewer steps on the fullest CU than unpaired).  BMC_CHAIN_PAIR in the environment, read per
+ * launch: 0 = never pair; 1 = pair, or fail the call (outputs untouched, bmc_last_error names the reason) if the launch
+ * cannot be paired. */
 typedef struct bmc_chain_fwd_args {
     bmc_src_t s0, s1;           /* nch = C each; launch batch b reads them through their batch maps */
     const float* wstream;

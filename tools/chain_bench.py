@@ -1,6 +1,10 @@
 #!/usr/bin/env python3
 """Isolated timing of the fused centre chain (csrc/chain.hip) against the three / five launches it replaces, at the C2
-shapes (gBIE: 2n = 8 launch batches, lBIE: 2n = 16).  python tools/chain_bench.py"""
+shapes (gBIE: 2n = 8 launch batches, lBIE: 2n = 16).  python tools/chain_bench.py
+
+python tools/chain_bench.py pair [HxWx2n ...]: the forward alone, unpaired (BMC_CHAIN_PAIR=0) against paired (=1), alternating in this
+process, three readings each (a reading = 20 launches between two events), at the C2 shapes and at two shapes on the other side
+of the host's pairing rule (31x56 2n = 16, 90x120 2n = 4), or at the shapes given."""
 import os
 import sys
 
@@ -32,6 +36,27 @@ def timeit(fn, it=20):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / it
 
+
+def pair_readings(shapes):
+    for h, w, B2 in shapes or ((180, 240, 8), (180, 240, 16), (31, 56, 16), (90, 120, 4)):
+        n = B2 // 2
+        xs = torch.randn(n, h, w, Cn, device=dev)
+        x12 = torch.randn(B2, h, w, Cn, device=dev)
+        s0, s1 = _src(xs, 0, Cn, 0, n, 0, B2), _src(x12, 0, Cn, n, B2, 0, B2)
+        fwd = lambda: bie.chain_fwd(s0, s1, wf, bf, gamma, beta, wc, bc, 1e-6, B2, h, w, Cn, dev)
+        t = {"0": [], "1": []}
+        for _ in range(3):
+            for mode in ("0", "1"):
+                os.environ["BMC_CHAIN_PAIR"] = mode
+                t[mode].append(timeit(fwd))
+        os.environ.pop("BMC_CHAIN_PAIR")
+        print("%dx%d 2n=%2d  fwd unpaired %s ms   paired %s ms" %
+              (h, w, B2, " / ".join("%.4f" % v for v in t["0"]), " / ".join("%.4f" % v for v in t["1"])), flush=True)
+
+
+if sys.argv[1:2] == ["pair"]:
+    pair_readings([tuple(int(v) for v in a.split("x")) for a in sys.argv[2:]])
+    sys.exit(0)
 
 for n in (4, 8):
     B2 = 2 * n
