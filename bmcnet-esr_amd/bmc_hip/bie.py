@@ -187,10 +187,195 @@ def _spec2(c):
     return s
 
 
+# --------------------------------------------------------------------------
+# The launch steps of the block, each written once.  BIETwinFn and BIEFirstFn (below) are compositions of them and differ in
+# DATA only: the batch window a step covers (the first nb of the 2n images) and the number of value-weight groups.  No step is
+# told which node calls it.
+# --------------------------------------------------------------------------
+def _X(t, shift=0, mod=None, b0=0, B=None):
+    """Operand descriptor over all channels of t [*,H,W,C]: B launch images (default: all of t) from image b0 on, read
+    batch-rotated by `shift` modulo `mod`."""
+    return _src(t, 0, t.shape[3], shift, mod, b0, t.shape[0] if B is None else B)
+
+
+def _new(b, like):
+    return torch.empty((b,) + like.shape[1:], device=like.device, dtype=torch.float32)
+
+
+def _value_weights(p_w, ws, p_b=None, bs=None):
+    """The G = len(ws) weight groups of the value convolutions -> (w4 [G,C,C,1], its pack-cache owner, bias [G,C]; None
+    without bs).  One group: the parameter itself, reshaped.  Several: stacked once per parameter version (ops.stacked, keyed by
+    p_w / p_b, the caller's parameter objects -- saved tensors are fresh aliases in every backward); the stack owns its pack."""
+    Cn = ws[0].shape[0]
+    if len(ws) == 1:
+        return ws[0].detach().reshape(1, Cn, Cn, 1), p_w[0], bs[0].detach().reshape(1, Cn) if bs is not None else None
+    w4 = ops.stacked(p_w, lambda: torch.stack([w.detach().reshape(Cn, Cn, 1) for w in ws]), "v1x1")
+    return w4, w4, ops.stacked(p_b, lambda: torch.stack([b.detach() for b in bs]), "stack") if bs is not None else None
+
+
+def _centres_fwd(x12, xs, wf, bf, gamma, beta, wc, bc, eps):
+    """[c1; c2] = clustering(LN(convf(cat[xs, other half]))) in the one fused launch -> (yhat, rstd, c12)."""
+    B2, H, W, Cn = x12.shape
+    n = B2 // 2
+    return chain_fwd(_X(xs, mod=n, B=B2), _X(x12, shift=n, mod=B2), wf, bf.detach(), gamma.detach(), beta.detach(), wc, bc.detach(),
+                     eps, B2, H, W, Cn, x12.device)
+
+
+def _attention_fwd(c_src, x_src, res_src, w4, owner, bias, scale, nb, like, vfree):
+    """o[b] = softmax(scale c_b^T v_b) v_b + residual[b] over nb launch images; v = W_g x + b_g, the value convolution with
+    the weights of group g = b // (nb / G) (_value_weights).  vfree: the form that never builds v (top of this file).
+    -> (o, P, v, G0, s): v is None in the vfree form, G0 and s in the explicit one."""
+    _, H, W, Cn = like.shape
+    dev, s1 = like.device, _dense_spec(Cn)
+    G = w4.shape[0]
+    o = _new(nb, like)
+    if vfree:       # att = scale (G0 W_v^T + s b_v^T), out = (P W_v) x + P b_v
+        G0, sc = _gram_on_x(c_src, x_src, nb, H, W, Cn, dev)
+        wg, v = w4.view(G, Cn, Cn), None
+        att = _times_wt(G0, sc, wg, bias, nb // G, scale, torch.empty_like(G0))
+        p = torch.empty_like(att)
+        lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), nb * Cn, Cn, p.data_ptr(), _stream())
+        pw, pb = torch.empty_like(p), torch.empty_like(sc)                                 # P W_v [b, i, k],  P b_v [b, i]
+        _times_w(p, wg, bias, nb // G, pw, (Cn * Cn, Cn, 1), vec=pb)
+        conv_launch([x_src], pw.view(nb, Cn, Cn, 1), s1, None, pb, o, nb, residual=res_src, bpg=1)
+    else:
+        G0 = sc = None
+        v = _new(nb, like)
+        conv_launch([x_src], w4, s1, owner, bias, v, nb, bpg=nb // G)
+        # channel attention per sample
+        slabs, nsplit, Gs = pgemm_raw(c_src, [_X(v)], nb, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * nb * H * W * Cn * Cn)
+        att = torch.empty((nb, Cn, Cn), device=dev, dtype=torch.float32)
+        lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, Gs, Cn, Cn, scale, att.data_ptr(), _stream())
+        p = torch.empty_like(att)
+        lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), nb * Cn, Cn, p.data_ptr(), _stream())
+        conv_launch([_X(v)], p.view(nb, Cn, Cn, 1), s1, None, None, o, nb, residual=res_src, bpg=1)
+    return o, p, v, G0, sc
+
+
+def _uncluster_fwd(c12, wu, bu, xs):
+    """shared stream: xs_new = unclustering(cat[c1, c2]) + xs."""
+    n, _, _, Cn = xs.shape
+    xs_new = _new(n, xs)
+    conv_launch([_X(c12, b0=0, B=n), _X(c12, b0=n, B=n)], wu.detach().reshape(1, Cn, 2 * Cn, 1), _spec2(Cn), wu, bu.detach(), xs_new, n,
+                residual=_X(xs))
+    return xs_new
+
+
+def _attention_bwd(g_o, g_x, x12, c12, v, p, G0, sc, w4, bias, scale, w_params, b_params, p_wu, p_bu, wu, window):
+    """Backward of _attention_fwd over its nb = len(p) images (the first nb of x12 / c12) and of _uncluster_fwd, up to the
+    centres: dP, the softmax, dc12 [2n] = the attention's Gram term on the first nb images + the unclustering's data gradient on
+    all of them, and the parameter gradients of the unclustering and of the value convolutions (v is None: the vfree form).
+    -> (dc12, dv, w_dx, dwv, dbv, dwu, dbu); what is left for _attention_dx is dv (explicit form) or the matrices w_dx (vfree)."""
+    nb, Cn, _ = p.shape
+    B2, H, W, _ = x12.shape
+    n = B2 // 2
+    dev, s2 = x12.device, _spec2(Cn)
+    G = w4.shape[0]
+    g_src = _X(g_o)
+    # ---- out = P v (+ residual): dP
+    if v is None:       # dM = g_o^T x, t = column sums of g_o;  dP = dM W_v^T + t b_v^T
+        wg = w4.view(G, Cn, Cn)
+        dM, tg = _gram_on_x(g_src, _X(x12, B=nb), nb, H, W, Cn, dev)
+        dp = _times_wt(dM, tg, wg, bias, nb // G, 1.0, torch.empty_like(dM))
+    else:
+        slabs, nsplit, Gs = pgemm_raw(g_src, [_X(v)], nb, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * nb * H * W * Cn * Cn)
+        dp = torch.empty_like(p)
+        lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, Gs, Cn, Cn, 1.0, dp.data_ptr(), _stream())
+    # ---- softmax, Gram (att = scale * center v^T)
+    da = torch.empty_like(p)
+    lib.call(lib._sm_bwd, "bmc_softmax_bwd", p.data_ptr(), dp.data_ptr(), nb * Cn, Cn, scale, da.data_ptr(), _stream())
+    dwv = dbv = dv = w_dx = None
+    if v is None:
+        # value-convolution parameters: dW_v = P^T dM + da^T G0, db_v = P^T t + da^T s (summed over the group's samples)
+        dwv, dbv = _value_param_grads(p, dM, tg, da, G0, sc, w_params, b_params, nb * H * W)
+    # Each of dv and d center has two contributions that are 1x1 products with per-sample / per-half matrices: ONE
+    # two-source launch each (K = 2C, the matrices side by side) instead of a launch + accumulating launches --
+    #   dv[b]      = P_b^T g_o[b] + da_b^T center[b]                                             (b < nb)
+    #   dcenter[b] = (b < nb: da_b v[b]) + W_u[:, half(b)]^T g_x[b mod n]     (unclustering reads cat[c1, c2]; images from nb on
+    #                                                                          have no attention term: a zero matrix)
+    dc12 = _new(B2, x12)
+    # [B2, C (c_i), C (co)], cached per version of the unclustering weight and batch size (it is the same in all 8 windows)
+    w_ut = ops.stacked((p_wu,), lambda: wu.detach().view(Cn, 2, Cn).permute(1, 2, 0).repeat_interleave(n, 0).contiguous(), "wut%d" % n)
+    gx2 = _X(g_x, mod=n, B=B2)
+    if v is None:
+        # without v:  dx12 (+)= (P W_v)^T g_o + (da W_v)^T center  (_attention_dx, once dx12 exists);
+        #             dcenter = (da W_v) x + da b_v + W_u[:, half]^T g_x
+        # the per-sample matrices are written straight into the two-source weight layouts [b][cout][cin of source 0 | 1]
+        alloc = torch.zeros if nb < B2 else torch.empty         # (rows of the images from nb on are never written: they stay zero)
+        w_dx = torch.empty((nb, Cn, 2 * Cn, 1), device=dev, dtype=torch.float32)
+        w_dc = alloc((B2, Cn, 2 * Cn, 1), device=dev, dtype=torch.float32)
+        w_dc.view(B2, Cn, 2 * Cn)[:, :, Cn:] = w_ut
+        ds = alloc((B2, Cn), device=dev, dtype=torch.float32)
+        cc2 = 2 * Cn * Cn
+        _times_w(da, wg, bias, nb // G, w_dc, (cc2, 2 * Cn, 1), vec=ds)                        # [da W_v | .],  da b_v
+        _times_w(da, wg, bias, nb // G, w_dx[:, :, Cn:], (cc2, 1, 2 * Cn))                     # [. | (da W_v)^T]
+        _times_w(p, wg, bias, nb // G, w_dx, (cc2, 1, 2 * Cn))                                 # [(P W_v)^T | .]
+        conv_launch([_X(x12), gx2], w_dc, s2, None, ds, dc12, B2, bpg=1)
+    else:
+        dv = _new(nb, x12)
+        w_dv = torch.cat([p.transpose(1, 2), da.transpose(1, 2)], 2).view(nb, Cn, 2 * Cn, 1)
+        conv_launch([g_src, _X(c12, B=nb)], w_dv, s2, None, None, dv, nb, bpg=1)
+        da2 = da if nb == B2 else torch.cat([da, da.new_zeros((B2 - nb, Cn, Cn))], 0)
+        w_dc = torch.cat([da2, w_ut], 2).view(B2, Cn, 2 * Cn, 1)
+        conv_launch([_X(v, mod=nb, B=B2), gx2], w_dc, s2, None, None, dc12, B2, bpg=1)
+    # ---- unclustering(cat[c1, c2]) + xs: weight gradient
+    dwu, dbu = ops.wgrad(_X(g_x), [_X(c12, b0=0, B=n), _X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12),
+                         window=window, merge_pgemm=True)
+    if v is not None:   # ---- value convs: one weight group per parameter
+        one = G == 1
+        dwv, dbv = ops.wgrad(_X(dv), [_X(x12, B=nb)], _dense_spec(Cn), nb, H, W, 1, Cn, dev, w_params[0] if one else w_params,
+                             b_params[0] if one else b_params, G=G, w_shape=None if one else (G, Cn, Cn, 1, 1), keep=(dv, x12),
+                             window=window, merge_pgemm=True)
+    return dc12, dv, w_dx, dwv, dbv, dwu, dbu
+
+
+def _chain_bwd_tail(dc12, yhat, rstd, gamma, beta, wf, wc, g_x, xs, x12, params, window, ds1=None):
+    """clustering, LayerNorm, convf: ONE data-gradient launch (csrc/chain.hip) and the parameter gradients that follow from it.
+    dx12 = conv_f^T (second half of its inputs; written into ds1 where given), dxs = skip + conv_f^T (first half) summed over
+    both halves.  params: the caller's (convf w, b, norm w, b, clustering w, b).
+    -> (dx12, dxs, dwf, dbf, dgamma, dbeta, dwc, dbc)"""
+    p_wf, p_bf, p_gamma, p_beta, p_wc, p_bc = params
+    B2, H, W, Cn = x12.shape
+    n = B2 // 2
+    dev = x12.device
+    dz12, dx12, dxs = chain_bwd(_X(dc12), yhat, rstd, gamma.detach(), wf, wc, _X(g_x), n, H, W, Cn, dev, ds1=ds1)
+    # G = dc^T yhat and the clustering bias gradient (temporaries: dW_c, dgamma, dbeta follow from them)
+    Gm, dbc_t = ops.wgrad(_X(dc12), [_X(yhat)], _dense_spec(Cn), B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn), merge_pgemm=True)
+    sg = ops.sink_group([p_wc, p_bc, p_gamma, p_beta])
+    if sg is not None:
+        (o_w, o_b, o_g, o_bt), acc = sg
+        dwc = dbc = dgamma = dbeta = None
+    else:
+        o_w, o_b, acc = Gm, None, 0
+        o_g = dgamma = torch.empty(Cn, device=dev, dtype=torch.float32)
+        o_bt = dbeta = torch.empty(Cn, device=dev, dtype=torch.float32)
+        dwc, dbc = Gm.view(wc.shape), dbc_t
+    lib.call(lib._chain_affine, "bmc_chain_affine_grads", Gm.data_ptr(), dbc_t.data_ptr(), wc.detach().data_ptr(),
+             gamma.detach().data_ptr(), beta.detach().data_ptr(), Cn, o_w.data_ptr(),
+             o_b.data_ptr() if o_b is not None else None, o_g.data_ptr(), o_bt.data_ptr(), acc, _stream())
+    dwf, dbf = ops.wgrad(_X(dz12), [_X(xs, mod=n, B=B2), _X(x12, shift=n, mod=B2)], _spec2(Cn), B2, H, W, 1, Cn, dev, p_wf, p_bf,
+                         keep=(dz12, xs, x12), window=window, merge_pgemm=True)
+    return dx12, dxs, dwf, dbf, dgamma, dbeta, dwc, dbc
+
+
+def _attention_dx(g_o, c12, dv, w_dx, w4, owner, dx12, accumulate):
+    """dx12[:nb] (=|+=) what the attention hands back to the value convolutions' input: through the matrices w_dx of the vfree
+    form, or dv through the value convolutions."""
+    Cn = dx12.shape[3]
+    if w_dx is not None:
+        nb = w_dx.shape[0]
+        conv_launch([_X(g_o), _X(c12, B=nb)], w_dx, _spec2(Cn), None, None, dx12, nb, bpg=1, accumulate=accumulate)
+    else:
+        nb = dv.shape[0]
+        dgrad_launch(_X(dv), w4, _dense_spec(Cn), 0, owner, dx12, nb, bpg=nb // w4.shape[0], accumulate=accumulate)
+
+
 class BIETwinFn(torch.autograd.Function):
     """inputs: x12 [2n,H,W,C] = [first; second], xs [n,H,W,C], then the 16 parameter tensors
     (res.conv1 w,b; res.conv2 w,b; convf w,b; norm w,b; clustering w,b; unclustering w,b; v1 w,b; v2 w,b).
-    outputs: o12 = [softmax(att1) v1 + Res(second); softmax(att2) v2 + Res(first)], xs_new."""
+    outputs: o12 = [softmax(att1) v1 + Res(second); softmax(att2) v2 + Res(first)], xs_new.
+    Every step covers all 2n images; v1 / v2 are two weight groups of one launch; the crossed residual is a batch-rotated
+    read.  Keeps the unfused centre chain (FUSE_CHAIN off, the bf16 mode) and writes dx12 into the input's gradient slot."""
 
     @staticmethod
     def forward(ctx, x12, xs, rw1, rb1, rw2, rb2, wf, bf, gamma, beta, wc, bc, wu, bu, wv1, bv1, wv2, bv2, scale, eps):
@@ -200,55 +385,27 @@ class BIETwinFn(torch.autograd.Function):
         n = B2 // 2
         dev = x12.device
         s1, s2 = _dense_spec(Cn), _spec2(Cn)
-        new = lambda b: torch.empty((b, H, W, Cn), device=dev, dtype=torch.float32)
-        X = lambda t, **k: _src(t, 0, Cn, k.get("shift", 0), k.get("mod"), k.get("b0", 0), k.get("B", t.shape[0]))
-        d = lambda t: t.detach()
         # residual block on both halves (shared weights)
-        t12, r12 = new(B2), new(B2)
-        conv_launch([X(x12)], d(rw1).reshape(1, Cn, Cn, 9), s1, rw1, d(rb1), t12, B2, relu=True, rule=rb1)
-        conv_launch([X(t12)], d(rw2).reshape(1, Cn, Cn, 9), s1, rw2, d(rb2), r12, B2, residual=X(x12), rule=rb2)
+        t12, r12 = _new(B2, x12), _new(B2, x12)
+        ops.res_block_fwd(_X(x12), rw1, rb1, rw2, rb2, s1, t12, r12)
         # centres: clustering(LN(convf(cat[xs, other half])))
         fused = chain_supported(Cn)
         if fused:       # one launch; saved for backward: yhat (normalised, before the affine) and rstd
-            z12, stats, c12 = chain_fwd(X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2), wf, d(bf), d(gamma), d(beta), wc, d(bc),
-                                        eps, B2, H, W, Cn, dev)
+            z12, stats, c12 = _centres_fwd(x12, xs, wf, bf, gamma, beta, wc, bc, eps)
             y12 = z12
         else:
-            z12, y12, c12 = new(B2), new(B2), new(B2)
-            conv_launch([X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], d(wf).reshape(1, Cn, 2 * Cn, 1), s2, wf, d(bf), z12, B2)
+            z12, y12, c12 = _new(B2, x12), _new(B2, x12), _new(B2, x12)
+            conv_launch([_X(xs, mod=n, B=B2), _X(x12, shift=n, mod=B2)], wf.detach().reshape(1, Cn, 2 * Cn, 1), s2, wf, bf.detach(), z12, B2)
             stats = torch.empty(B2 * H * W * 2, device=dev, dtype=torch.float32)
             lib.call(lib._ln_fwd, "bmc_layernorm_fwd", z12.data_ptr(), gamma.data_ptr(), beta.data_ptr(), B2 * H * W, Cn, eps,
                      y12.data_ptr(), stats.data_ptr(), _stream())
-            conv_launch([X(y12)], d(wc).reshape(1, Cn, Cn, 1), s1, wc, d(bc), c12, B2)
-        # values: v1 on the first half, v2 on the second (two weight groups)
-        wv = ops.stacked((wv1, wv2), lambda: torch.stack([d(wv1).reshape(Cn, Cn, 1), d(wv2).reshape(Cn, Cn, 1)]), "v1x1")
-        bv = ops.stacked((bv1, bv2), lambda: torch.stack([d(bv1), d(bv2)]), "stack")
+            conv_launch([_X(y12)], wc.detach().reshape(1, Cn, Cn, 1), s1, wc, bc.detach(), c12, B2)
+        # values: v1 on the first half, v2 on the second (two weight groups); attention per sample, residual = the OTHER half's block
+        w4, owner, bias = _value_weights((wv1, wv2), (wv1, wv2), (bv1, bv2), (bv1, bv2))
         vfree = vfree_supported(B2 * H * W)
-        o12 = new(B2)
-        if vfree:       # attention without v (above): att = scale (G0 W_v^T + s b_v^T), out = (P W_v) x + P b_v
-            G0, sc = _gram_on_x(X(c12), X(x12), B2, H, W, Cn, dev)
-            wg, v12 = wv.view(2, Cn, Cn), None
-            att = _times_wt(G0, sc, wg, bv, n, scale, torch.empty_like(G0))
-            p = torch.empty_like(att)
-            lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), B2 * Cn, Cn, p.data_ptr(), _stream())
-            pw, pb = torch.empty_like(p), torch.empty_like(sc)                                 # P W_v [b, i, k],  P b_v [b, i]
-            _times_w(p, wg, bv, n, pw, (Cn * Cn, Cn, 1), vec=pb)
-            conv_launch([X(x12)], pw.view(B2, Cn, Cn, 1), s1, None, pb, o12, B2, residual=X(r12, shift=n, mod=B2), bpg=1)
-        else:
-            G0 = sc = None
-            v12 = new(B2)
-            conv_launch([X(x12)], wv, s1, wv, bv, v12, B2, bpg=n)
-            # channel attention per sample
-            slabs, nsplit, G = pgemm_raw(X(c12), [X(v12)], B2, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * B2 * H * W * Cn * Cn)
-            att = torch.empty((B2, Cn, Cn), device=dev, dtype=torch.float32)
-            lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, G, Cn, Cn, scale, att.data_ptr(), _stream())
-            p = torch.empty_like(att)
-            lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), B2 * Cn, Cn, p.data_ptr(), _stream())
-            conv_launch([X(v12)], p.view(B2, Cn, Cn, 1), s1, None, None, o12, B2, residual=X(r12, shift=n, mod=B2), bpg=1)
-        # shared stream: unclustering(cat[c1, c2]) + xs
-        xs_new = new(n)
-        conv_launch([X(c12, b0=0, B=n), X(c12, b0=n, B=n)], d(wu).reshape(1, Cn, 2 * Cn, 1), s2, wu, d(bu), xs_new, n, residual=X(xs))
-        ctx.save_for_backward(x12, xs, t12, z12, stats, y12, c12, v12 if not vfree else G0, p, rw1, rw2, wf, gamma, wc, wu, wv1, wv2, beta,
+        o12, p, v12, G0, sc = _attention_fwd(_X(c12), _X(x12), _X(r12, shift=n, mod=B2), w4, owner, bias, scale, B2, x12, vfree)
+        xs_new = _uncluster_fwd(c12, wu, bu, xs)
+        ctx.save_for_backward(x12, xs, t12, z12, stats, y12, c12, G0 if vfree else v12, p, rw1, rw2, wf, gamma, wc, wu, wv1, wv2, beta,
                               *((sc, bv1, bv2) if vfree else ()))
         ctx.vfree = vfree
         ctx.owners = (rw1, rw2, wf, wc, wu)
@@ -264,108 +421,35 @@ class BIETwinFn(torch.autograd.Function):
     def backward(ctx, do12, dxs_new):
         saved = ctx.saved_tensors           # (once: a second access breaks torch.utils.checkpoint's unpack bookkeeping)
         x12, xs, t12, z12, stats, y12, c12, v12, p, rw1, rw2, wf, gamma, wc, wu, wv1, wv2, beta = saved[:18]
-        vfree = ctx.vfree
-        if vfree:
-            G0, (sc, bv1, bv2) = v12, saved[18:]
+        G0 = sc = bvs = None
+        if ctx.vfree:
+            G0, v12, sc, bvs = v12, None, saved[18], saved[19:]
         o_rw1, o_rw2, o_wf, o_wc, o_wu = ctx.owners
         p_rw1, p_rb1, p_rw2, p_rb2, p_wf, p_bf, p_gamma, p_beta, p_wc, p_bc, p_wu, p_bu = ctx.params
+        p_wv, p_bv = ctx.vparams[:2], ctx.vparams[2:]
         B2, H, W, Cn = x12.shape
         n = B2 // 2
         dev = x12.device
         s1, s2 = _dense_spec(Cn), _spec2(Cn)
-        new = lambda b: torch.empty((b, H, W, Cn), device=dev, dtype=torch.float32)
-        X = lambda t, **k: _src(t, 0, Cn, k.get("shift", 0), k.get("mod"), k.get("b0", 0), k.get("B", t.shape[0]))
         g_o = do12.contiguous() if do12 is not None else torch.zeros_like(x12)
         g_x = dxs_new.contiguous() if dxs_new is not None else torch.zeros_like(xs)
-        w_r1, w_r2 = rw1.detach().reshape(1, Cn, Cn, 9), rw2.detach().reshape(1, Cn, Cn, 9)
-        w_f, w_c, w_u = (rw.detach().reshape(1, Cn, k, 1) for rw, k in ((wf, 2 * Cn), (wc, Cn), (wu, 2 * Cn)))
-        # (keyed by the caller's parameter objects: the saved tensors are fresh aliases in every backward)
-        w_v = ops.stacked(ctx.vparams[:2], lambda: torch.stack([wv1.detach().reshape(Cn, Cn, 1), wv2.detach().reshape(Cn, Cn, 1)]), "v1x1")
-
-        # ---- out = P v (+ rotated residual): dP, dv
-        if vfree:       # dM = g_o^T x, t = column sums of g_o;  dP = dM W_v^T + t b_v^T
-            wg = w_v.view(2, Cn, Cn)
-            bg = ops.stacked(ctx.vparams[2:], lambda: torch.stack([bv1.detach(), bv2.detach()]), "stack")
-            dM, tg = _gram_on_x(X(g_o), X(x12), B2, H, W, Cn, dev)
-            dp = _times_wt(dM, tg, wg, bg, n, 1.0, torch.empty_like(dM))
+        w4, owner, bias = _value_weights(p_wv, (wv1, wv2), p_bv, bvs)
+        dc12, dv12, w_dx, dwv, dbv, dwu, dbu = _attention_bwd(g_o, g_x, x12, c12, v12, p, G0, sc, w4, bias, ctx.scale, p_wv, p_bv,
+                                                              p_wu, p_bu, wu, ctx.window)
+        if ctx.fused:               # y12 holds yhat, stats rstd
+            dx12, dxs, dwf, dbf, dgamma, dbeta, dwc, dbc = _chain_bwd_tail(
+                dc12, y12, stats, gamma, beta, wf, wc, g_x, xs, x12, (p_wf, p_bf, p_gamma, p_beta, p_wc, p_bc), ctx.window,
+                ds1=ops.grad_slot(ctx.gslot, x12))
+            _attention_dx(g_o, c12, dv12, w_dx, w4, owner, dx12, True)                                         # dx12 += attention
         else:
-            slabs, nsplit, G = pgemm_raw(X(g_o), [X(v12)], B2, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * B2 * H * W * Cn * Cn)
-            dp = torch.empty_like(p)
-            lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, G, Cn, Cn, 1.0, dp.data_ptr(), _stream())
-        # ---- softmax, Gram (att = scale * center v^T)
-        da = torch.empty_like(p)
-        lib.call(lib._sm_bwd, "bmc_softmax_bwd", p.data_ptr(), dp.data_ptr(), B2 * Cn, Cn, ctx.scale, da.data_ptr(), _stream())
-        if vfree:
-            # value-convolution parameters: dW_v = P^T dM + da^T G0, db_v = P^T t + da^T s (summed over the group's samples)
-            dwv, dbv = _value_param_grads(p, dM, tg, da, G0, sc, ctx.vparams[:2], ctx.vparams[2:], B2 * H * W)
-        # Each of dv and d center has two contributions that are 1x1 products with per-sample / per-half matrices: ONE
-        # two-source launch each (K = 2C, the matrices side by side) instead of a launch + accumulating launches --
-        #   dv[b]      = P_b^T g_o[b] + da_b^T center[b]
-        #   dcenter[b] = da_b  v[b]   + W_u[:, half(b)]^T g_x[b mod n]            (unclustering reads cat[c1, c2])
-        dc12 = new(B2)
-        # [B2, C (c_i), C (co)], cached per version of the unclustering weight and batch size (it is the same in all 8 windows)
-        w_ut = ops.stacked((p_wu,), lambda: wu.detach().view(Cn, 2, Cn).permute(1, 2, 0).repeat_interleave(n, 0).contiguous(), "wut%d" % n)
-        if vfree:
-            # without v:  dx12 (+)= (P W_v)^T g_o + (da W_v)^T center  (below, once dx12 exists);
-            #             dcenter = (da W_v) x + da b_v + W_u[:, half]^T g_x
-            # the per-sample matrices are written straight into the two-source weight layouts [b][cout][cin of source 0 | 1]
-            w_dx = torch.empty((B2, Cn, 2 * Cn, 1), device=dev, dtype=torch.float32)
-            w_dc = torch.empty((B2, Cn, 2 * Cn, 1), device=dev, dtype=torch.float32)
-            w_dc.view(B2, Cn, 2 * Cn)[:, :, Cn:] = w_ut
-            ds = torch.empty((B2, Cn), device=dev, dtype=torch.float32)
-            cc2 = 2 * Cn * Cn
-            _times_w(da, wg, bg, n, w_dc, (cc2, 2 * Cn, 1), vec=ds)                            # [da W_v | .],  da b_v
-            _times_w(da, wg, bg, n, w_dx[:, :, Cn:], (cc2, 1, 2 * Cn))                         # [. | (da W_v)^T]
-            _times_w(p, wg, bg, n, w_dx, (cc2, 1, 2 * Cn))                                     # [(P W_v)^T | .]
-            conv_launch([X(x12), X(g_x, mod=n, B=B2)], w_dc, s2, None, ds, dc12, B2, bpg=1)
-        else:
-            dv12 = new(B2)
-            w_dv = torch.cat([p.transpose(1, 2), da.transpose(1, 2)], 2).view(B2, Cn, 2 * Cn, 1)
-            conv_launch([X(g_o), X(c12)], w_dv, s2, None, None, dv12, B2, bpg=1)
-            w_dc = torch.cat([da, w_ut], 2).view(B2, Cn, 2 * Cn, 1)
-            conv_launch([X(v12), X(g_x, mod=n, B=B2)], w_dc, s2, None, None, dc12, B2, bpg=1)
-        # ---- unclustering(cat[c1, c2]) + xs: weight gradient
-        dwu, dbu = ops.wgrad(X(g_x), [X(c12, b0=0, B=n), X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12), window=ctx.window, merge_pgemm=True)
-        # ---- value convs (two weight groups)
-        if not vfree:
-            dwv, dbv = ops.wgrad(X(dv12), [X(x12)], s1, B2, H, W, 1, Cn, dev, ctx.vparams[:2], ctx.vparams[2:], G=2,
-                              w_shape=(2, Cn, Cn, 1, 1), keep=(dv12, x12), window=ctx.window, merge_pgemm=True)
-        if ctx.fused:
-            # ---- clustering, LayerNorm, convf: ONE data-gradient launch (csrc/chain.hip); y12 holds yhat, stats rstd.
-            # dx12 = conv_f^T (second half of its inputs), dxs = skip + conv_f^T (first half) summed over both halves.
-            dz12, dx12, dxs = chain_bwd(X(dc12), y12, stats, gamma.detach(), wf, wc, X(g_x), n, H, W, Cn, dev,
-                                        ds1=ops.grad_slot(ctx.gslot, x12))
-            # G = dc^T yhat and the clustering bias gradient (temporaries: dW_c, dgamma, dbeta follow from them)
-            Gm, dbc_t = ops.wgrad(X(dc12), [X(y12)], s1, B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn), merge_pgemm=True)
-            sg = ops.sink_group([p_wc, p_bc, p_gamma, p_beta])
-            if sg is not None:
-                (o_w, o_b, o_g, o_bt), acc = sg
-                dwc = dbc = dgamma = dbeta = None
-            else:
-                o_w, o_b, acc = Gm, None, 0
-                o_g = dgamma = torch.empty(Cn, device=dev, dtype=torch.float32)
-                o_bt = dbeta = torch.empty(Cn, device=dev, dtype=torch.float32)
-                dwc, dbc = Gm, dbc_t
-            lib.call(lib._chain_affine, "bmc_chain_affine_grads", Gm.data_ptr(), dbc_t.data_ptr(), wc.detach().data_ptr(),
-                     gamma.detach().data_ptr(), beta.detach().data_ptr(), Cn, o_w.data_ptr(),
-                     o_b.data_ptr() if o_b is not None else None, o_g.data_ptr(), o_bt.data_ptr(), acc, _stream())
-            dwf, dbf = ops.wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
-                              keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
-            if vfree:
-                conv_launch([X(g_o), X(c12)], w_dx, s2, None, None, dx12, B2, bpg=1, accumulate=True)         # dx12 += attention
-            else:
-                dgrad_launch(X(dv12), w_v, s1, 0, w_v, dx12, B2, bpg=n, accumulate=True)                      # dx12 += value convs
-        else:
+            w_f, w_c = wf.detach().reshape(1, Cn, 2 * Cn, 1), wc.detach().reshape(1, Cn, Cn, 1)
             dx12 = ops.grad_slot(ctx.gslot, x12)
-            if vfree:
-                conv_launch([X(g_o), X(c12)], w_dx, s2, None, None, dx12, B2, bpg=1)
-            else:
-                dgrad_launch(X(dv12), w_v, s1, 0, w_v, dx12, B2, bpg=n)                                       # dx12  =
+            _attention_dx(g_o, c12, dv12, w_dx, w4, owner, dx12, False)                                        # dx12  =
             # ---- clustering, LayerNorm, convf
-            dwc, dbc = ops.wgrad(X(dc12), [X(y12)], s1, B2, H, W, 1, Cn, dev, p_wc, p_bc, keep=(dc12, y12), window=ctx.window, merge_pgemm=True)
-            dy12 = new(B2)
-            dgrad_launch(X(dc12), w_c, s1, 0, o_wc, dy12, B2)
-            dz12 = new(B2)
+            dwc, dbc = ops.wgrad(_X(dc12), [_X(y12)], s1, B2, H, W, 1, Cn, dev, p_wc, p_bc, keep=(dc12, y12), window=ctx.window, merge_pgemm=True)
+            dy12 = _new(B2, x12)
+            dgrad_launch(_X(dc12), w_c, s1, 0, o_wc, dy12, B2)
+            dz12 = _new(B2, x12)
             ws = torch.empty(2 * 1024 * Cn, device=dev, dtype=torch.float32)
             sg = ops.sink_group([p_gamma, p_beta])
             if sg is not None:
@@ -377,30 +461,26 @@ class BIETwinFn(torch.autograd.Function):
                 ln_acc = 0
             lib.call(lib._ln_bwd, "bmc_layernorm_bwd", dy12.data_ptr(), z12.data_ptr(), stats.data_ptr(), gamma.data_ptr(),
                      B2 * H * W, Cn, dz12.data_ptr(), ws.data_ptr(), o_g.data_ptr(), o_bt.data_ptr(), ln_acc, _stream())
-            dwf, dbf = ops.wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
-                              keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
-            dxs = new(n)
-            dgrad_launch(X(dz12, b0=0, B=n), w_f, s2, 0, o_wf, dxs, n, residual=X(g_x))                        # dxs  = skip + half 0
-            dgrad_launch(X(dz12, b0=n, B=n), w_f, s2, 0, o_wf, dxs, n, accumulate=True)                        # dxs += half 1
-            dgrad_launch(X(dz12, shift=n, mod=B2), w_f, s2, 1, o_wf, dx12, B2, accumulate=True)                # dx12 += (rotated)
-        # ---- residual block, upstream gradient = batch-rotated g_o
-        g_r = X(g_o, shift=n, mod=B2)
-        dw2, db2 = ops.wgrad(g_r, [X(t12)], s1, B2, H, W, 9, Cn, dev, p_rw2, p_rb2, keep=(g_o, t12), window=ctx.window, merge_pgemm=True)
-        dt = new(B2)
-        dgrad_launch(g_r, w_r2, s1, 0, o_rw2, dt, B2, mask=X(t12))
-        dw1, db1 = ops.wgrad(X(dt), [X(x12)], s1, B2, H, W, 9, Cn, dev, p_rw1, p_rb1, keep=(dt, x12), window=ctx.window, merge_pgemm=True)
-        dgrad_launch(X(dt), w_r1, s1, 0, o_rw1, dx12, B2, residual=g_r, accumulate=True)                       # dx12 += conv1^T + skip
-        v = lambda t, ref: None if t is None else t.view(ref.shape)
+            dwf, dbf = ops.wgrad(_X(dz12), [_X(xs, mod=n, B=B2), _X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
+                                 keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
+            dxs = _new(n, x12)
+            dgrad_launch(_X(dz12, b0=0, B=n), w_f, s2, 0, o_wf, dxs, n, residual=_X(g_x))                      # dxs  = skip + half 0
+            dgrad_launch(_X(dz12, b0=n, B=n), w_f, s2, 0, o_wf, dxs, n, accumulate=True)                       # dxs += half 1
+            dgrad_launch(_X(dz12, shift=n, mod=B2), w_f, s2, 1, o_wf, dx12, B2, accumulate=True)               # dx12 += (rotated)
+        # ---- residual block, upstream gradient = batch-rotated g_o: dx12 += conv1^T + skip
+        _, dw1, db1, dw2, db2 = ops.res_block_bwd(_X(g_o, shift=n, mod=B2), g_o, _X(x12), x12, t12, rw1, rw2, (o_rw1, o_rw2),
+                                                  (p_rw1, p_rb1, p_rw2, p_rb2), s1, ctx.window, dx=dx12)
         gv = (None,) * 4 if dwv is None else (dwv[0].reshape(wv1.shape), dbv[0], dwv[1].reshape(wv2.shape), dbv[1])
-        return (dx12, dxs, dw1, db1, dw2, db2, dwf, dbf, dgamma, dbeta, v(dwc, wc), dbc, dwu, dbu, *gv, None, None)
+        return (dx12, dxs, dw1, db1, dw2, db2, dwf, dbf, dgamma, dbeta, dwc, dbc, dwu, dbu, *gv, None, None)
 
 
 class BIEFirstFn(torch.autograd.Function):
     """BIETwinFn without everything that only feeds its SECOND output (the last ParallelBlk of the backbone never reads it,
     models/BMCNet.py:75-82): x12 [2n,H,W,C] = [first; second], xs [n,H,W,C] ->
         o1 = softmax(att1) v1(first) + Res(second)   [n],   xs_new = unclustering(cat[c1, c2]) + xs   [n].
-    The residual block runs on the second half only, values / Gram / softmax / attention on the first half only; both
-    centres are still needed (unclustering) and come from the one fused chain launch.  Needs the fused chain."""
+    The same steps over narrower windows: the residual block on the second half only, values / Gram / softmax / attention on
+    the first half only (one weight group); both centres are still needed (unclustering) and come from the one fused chain
+    launch.  Needs the fused chain; no gradient slot."""
 
     @staticmethod
     def forward(ctx, x12, xs, rw1, rb1, rw2, rb2, wf, bf, gamma, beta, wc, bc, wu, bu, wv1, bv1, scale, eps):
@@ -408,41 +488,14 @@ class BIEFirstFn(torch.autograd.Function):
         x12, xs = x12.contiguous(), xs.contiguous()
         B2, H, W, Cn = x12.shape
         n = B2 // 2
-        dev = x12.device
-        s1, s2 = _dense_spec(Cn), _spec2(Cn)
-        new = lambda b: torch.empty((b, H, W, Cn), device=dev, dtype=torch.float32)
-        X = lambda t, **k: _src(t, 0, Cn, k.get("shift", 0), k.get("mod"), k.get("b0", 0), k.get("B", t.shape[0]))
-        d = lambda t: t.detach()
-        second = X(x12, b0=n, B=n)
-        t2, r2 = new(n), new(n)
-        conv_launch([second], d(rw1).reshape(1, Cn, Cn, 9), s1, rw1, d(rb1), t2, n, relu=True, rule=rb1)
-        conv_launch([X(t2)], d(rw2).reshape(1, Cn, Cn, 9), s1, rw2, d(rb2), r2, n, residual=second, rule=rb2)
-        yhat, rstd, c12 = chain_fwd(X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2), wf, d(bf), d(gamma), d(beta), wc, d(bc), eps,
-                                    B2, H, W, Cn, dev)
+        t2, r2 = _new(n, x12), _new(n, x12)
+        ops.res_block_fwd(_X(x12, b0=n, B=n), rw1, rb1, rw2, rb2, _dense_spec(Cn), t2, r2)
+        yhat, rstd, c12 = _centres_fwd(x12, xs, wf, bf, gamma, beta, wc, bc, eps)
+        w4, owner, bias = _value_weights((wv1,), (wv1,), (bv1,), (bv1,))
         vfree = vfree_supported(B2 * H * W)
-        o1 = new(n)
-        if vfree:       # attention without v (top of this file)
-            G0, sc = _gram_on_x(X(c12, b0=0, B=n), X(x12, b0=0, B=n), n, H, W, Cn, dev)
-            wg, bg, v1 = d(wv1).reshape(1, Cn, Cn), d(bv1).reshape(1, Cn), None
-            att = _times_wt(G0, sc, wg, bg, n, scale, torch.empty_like(G0))
-            p = torch.empty_like(att)
-            lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), n * Cn, Cn, p.data_ptr(), _stream())
-            pw, pb = torch.empty_like(p), torch.empty_like(sc)
-            _times_w(p, wg, bg, n, pw, (Cn * Cn, Cn, 1), vec=pb)
-            conv_launch([X(x12, b0=0, B=n)], pw.view(n, Cn, Cn, 1), s1, None, pb, o1, n, residual=X(r2), bpg=1)
-        else:
-            G0 = sc = None
-            v1 = new(n)
-            conv_launch([X(x12, b0=0, B=n)], d(wv1).reshape(1, Cn, Cn, 1), s1, wv1, d(bv1), v1, n)
-            slabs, nsplit, G = pgemm_raw(X(c12, b0=0, B=n), [X(v1)], n, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * n * H * W * Cn * Cn)
-            att = torch.empty((n, Cn, Cn), device=dev, dtype=torch.float32)
-            lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, G, Cn, Cn, scale, att.data_ptr(), _stream())
-            p = torch.empty_like(att)
-            lib.call(lib._sm_fwd, "bmc_softmax_fwd", att.data_ptr(), n * Cn, Cn, p.data_ptr(), _stream())
-            conv_launch([X(v1)], p.view(n, Cn, Cn, 1), s1, None, None, o1, n, residual=X(r2), bpg=1)
-        xs_new = new(n)
-        conv_launch([X(c12, b0=0, B=n), X(c12, b0=n, B=n)], d(wu).reshape(1, Cn, 2 * Cn, 1), s2, wu, d(bu), xs_new, n, residual=X(xs))
-        ctx.save_for_backward(x12, xs, t2, yhat, rstd, c12, v1 if not vfree else G0, p, rw1, rw2, wf, gamma, wc, wu, wv1, beta,
+        o1, p, v1, G0, sc = _attention_fwd(_X(c12, B=n), _X(x12, B=n), _X(r2), w4, owner, bias, scale, n, x12, vfree)
+        xs_new = _uncluster_fwd(c12, wu, bu, xs)
+        ctx.save_for_backward(x12, xs, t2, yhat, rstd, c12, G0 if vfree else v1, p, rw1, rw2, wf, gamma, wc, wu, wv1, beta,
                               *((sc, bv1) if vfree else ()))
         ctx.vfree = vfree
         ctx.owners = (rw1, rw2, wf, wc, wu, wv1)
@@ -455,89 +508,26 @@ class BIEFirstFn(torch.autograd.Function):
     def backward(ctx, do1, dxs_new):
         saved = ctx.saved_tensors
         x12, xs, t2, yhat, rstd, c12, v1, p, rw1, rw2, wf, gamma, wc, wu, wv1, beta = saved[:16]
-        vfree = ctx.vfree
-        if vfree:
-            G0, (sc, bv1) = v1, saved[16:]
+        G0 = sc = bvs = None
+        if ctx.vfree:
+            G0, v1, sc, bvs = v1, None, saved[16], saved[17:]
         o_rw1, o_rw2, o_wf, o_wc, o_wu, o_wv1 = ctx.owners
         p_rw1, p_rb1, p_rw2, p_rb2, p_wf, p_bf, p_gamma, p_beta, p_wc, p_bc, p_wu, p_bu, p_wv1, p_bv1 = ctx.params
-        B2, H, W, Cn = x12.shape
-        n = B2 // 2
-        dev = x12.device
-        s1, s2 = _dense_spec(Cn), _spec2(Cn)
-        new = lambda b: torch.empty((b, H, W, Cn), device=dev, dtype=torch.float32)
-        X = lambda t, **k: _src(t, 0, Cn, k.get("shift", 0), k.get("mod"), k.get("b0", 0), k.get("B", t.shape[0]))
+        n, Cn = x12.shape[0] // 2, x12.shape[3]
         g_o = do1.contiguous() if do1 is not None else torch.zeros_like(t2)
         g_x = dxs_new.contiguous() if dxs_new is not None else torch.zeros_like(xs)
-        w_r1, w_r2 = rw1.detach().reshape(1, Cn, Cn, 9), rw2.detach().reshape(1, Cn, Cn, 9)
-        w_v1 = wv1.detach().reshape(1, Cn, Cn, 1)
-        # ---- o1 = P v1 + r2: dP, softmax, Gram
-        if vfree:
-            wg, bg = wv1.detach().reshape(1, Cn, Cn), bv1.detach().reshape(1, Cn)
-            dM, tg = _gram_on_x(X(g_o), X(x12, b0=0, B=n), n, H, W, Cn, dev)
-            dp = _times_wt(dM, tg, wg, bg, n, 1.0, torch.empty_like(dM))
-        else:
-            slabs, nsplit, G = pgemm_raw(X(g_o), [X(v1)], n, H, W, 1, 1, Cn, Cn, dev, flops=2.0 * n * H * W * Cn * Cn)
-            dp = torch.empty_like(p)
-            lib.call(lib._red_p, "bmc_pgemm_reduce_plain", slabs.data_ptr(), nsplit, G, Cn, Cn, 1.0, dp.data_ptr(), _stream())
-        da = torch.empty_like(p)
-        lib.call(lib._sm_bwd, "bmc_softmax_bwd", p.data_ptr(), dp.data_ptr(), n * Cn, Cn, ctx.scale, da.data_ptr(), _stream())
-        if vfree:
-            dwv1, dbv1 = _value_param_grads(p, dM, tg, da, G0, sc, (p_wv1,), (p_bv1,), n * H * W)
-            if dwv1 is not None:
-                dwv1, dbv1 = dwv1.view(wv1.shape), dbv1.view(Cn)
-        #   dv1[b]     = P_b^T g_o[b] + da_b^T c1[b]
-        #   dcentre[b] = (b < n: da_b v1[b]) + W_u[:, half(b)]^T g_x[b mod n]     (the second half has no attention term: a zero matrix)
-        dc12 = new(B2)
-        # [B2, C (c_i), C (co)], cached per version of the unclustering weight and batch size (it is the same in all 8 windows)
-        w_ut = ops.stacked((p_wu,), lambda: wu.detach().view(Cn, 2, Cn).permute(1, 2, 0).repeat_interleave(n, 0).contiguous(), "wut%d" % n)
-        if vfree:       # (as in BIETwinFn; the second half has no attention term: zero matrix, zero bias)
-            w_dx = torch.empty((n, Cn, 2 * Cn, 1), device=dev, dtype=torch.float32)
-            w_dc = torch.zeros((B2, Cn, 2 * Cn, 1), device=dev, dtype=torch.float32)
-            w_dc.view(B2, Cn, 2 * Cn)[:, :, Cn:] = w_ut
-            ds = torch.zeros((B2, Cn), device=dev, dtype=torch.float32)
-            cc2 = 2 * Cn * Cn
-            _times_w(da, wg, bg, n, w_dc, (cc2, 2 * Cn, 1), vec=ds)                            # (first n samples; the rest stay zero)
-            _times_w(da, wg, bg, n, w_dx[:, :, Cn:], (cc2, 1, 2 * Cn))
-            _times_w(p, wg, bg, n, w_dx, (cc2, 1, 2 * Cn))
-            conv_launch([X(x12), X(g_x, mod=n, B=B2)], w_dc, s2, None, ds, dc12, B2, bpg=1)
-        else:
-            dv1 = new(n)
-            w_dv = torch.cat([p.transpose(1, 2), da.transpose(1, 2)], 2).view(n, Cn, 2 * Cn, 1)
-            conv_launch([X(g_o), X(c12, b0=0, B=n)], w_dv, s2, None, None, dv1, n, bpg=1)
-            w_dc = torch.cat([torch.cat([da, torch.zeros_like(da)], 0), w_ut], 2).view(B2, Cn, 2 * Cn, 1)
-            conv_launch([X(v1, mod=n, B=B2), X(g_x, mod=n, B=B2)], w_dc, s2, None, None, dc12, B2, bpg=1)
-        dwu, dbu = ops.wgrad(X(g_x), [X(c12, b0=0, B=n), X(c12, b0=n, B=n)], s2, n, H, W, 1, Cn, dev, p_wu, p_bu, keep=(g_x, c12), window=ctx.window, merge_pgemm=True)
-        if not vfree:
-            dwv1, dbv1 = ops.wgrad(X(dv1), [X(x12, b0=0, B=n)], s1, n, H, W, 1, Cn, dev, p_wv1, p_bv1, keep=(dv1, x12), window=ctx.window, merge_pgemm=True)
-        # ---- clustering, LayerNorm, convf (csrc/chain.hip), as in BIETwinFn
-        dz12, dx12, dxs = chain_bwd(X(dc12), yhat, rstd, gamma.detach(), wf, wc, X(g_x), n, H, W, Cn, dev)
-        Gm, dbc_t = ops.wgrad(X(dc12), [X(yhat)], s1, B2, H, W, 1, Cn, dev, None, None, w_shape=(Cn, Cn), merge_pgemm=True)
-        sg = ops.sink_group([p_wc, p_bc, p_gamma, p_beta])
-        if sg is not None:
-            (o_w, o_b, o_g, o_bt), acc = sg
-            dwc = dbc = dgamma = dbeta = None
-        else:
-            o_w, o_b, acc = Gm, None, 0
-            o_g = dgamma = torch.empty(Cn, device=dev, dtype=torch.float32)
-            o_bt = dbeta = torch.empty(Cn, device=dev, dtype=torch.float32)
-            dwc, dbc = Gm, dbc_t
-        lib.call(lib._chain_affine, "bmc_chain_affine_grads", Gm.data_ptr(), dbc_t.data_ptr(), wc.detach().data_ptr(),
-                 gamma.detach().data_ptr(), beta.detach().data_ptr(), Cn, o_w.data_ptr(),
-                 o_b.data_ptr() if o_b is not None else None, o_g.data_ptr(), o_bt.data_ptr(), acc, _stream())
-        dwf, dbf = ops.wgrad(X(dz12), [X(xs, mod=n, B=B2), X(x12, shift=n, mod=B2)], s2, B2, H, W, 1, Cn, dev, p_wf, p_bf,
-                          keep=(dz12, xs, x12), window=ctx.window, merge_pgemm=True)
-        if vfree:
-            conv_launch([X(g_o), X(c12, b0=0, B=n)], w_dx, s2, None, None, dx12, n, bpg=1, accumulate=True)    # dx12[first] += attention
-        else:
-            dgrad_launch(X(dv1), w_v1, s1, 0, o_wv1, dx12, n, accumulate=True)                                 # dx12[first] += value conv
-        # ---- residual block (second half), upstream gradient = g_o
-        dw2, db2 = ops.wgrad(X(g_o), [X(t2)], s1, n, H, W, 9, Cn, dev, p_rw2, p_rb2, keep=(g_o, t2), window=ctx.window, merge_pgemm=True)
-        dt = new(n)
-        dgrad_launch(X(g_o), w_r2, s1, 0, o_rw2, dt, n, mask=X(t2))
-        dw1, db1 = ops.wgrad(X(dt), [X(x12, b0=n, B=n)], s1, n, H, W, 9, Cn, dev, p_rw1, p_rb1, keep=(dt, x12), window=ctx.window, merge_pgemm=True)
-        dgrad_launch(X(dt), w_r1, s1, 0, o_rw1, dx12, n, residual=X(g_o), accumulate=True, out_b0=n)           # dx12[second] += conv1^T + skip
-        v = lambda t, ref: None if t is None else t.view(ref.shape)
-        return (dx12, dxs, dw1, db1, dw2, db2, dwf, dbf, dgamma, dbeta, v(dwc, wc), dbc, dwu, dbu, v(dwv1, wv1), dbv1, None, None)
+        w4, owner, bias = _value_weights((o_wv1,), (wv1,), (p_bv1,), bvs)
+        dc12, dv1, w_dx, dwv1, dbv1, dwu, dbu = _attention_bwd(g_o, g_x, x12, c12, v1, p, G0, sc, w4, bias, ctx.scale, (p_wv1,), (p_bv1,),
+                                                               p_wu, p_bu, wu, ctx.window)
+        if dwv1 is not None:
+            dwv1 = dwv1.view(wv1.shape)                 # ([C,C] from the vfree form's products)
+        dx12, dxs, dwf, dbf, dgamma, dbeta, dwc, dbc = _chain_bwd_tail(
+            dc12, yhat, rstd, gamma, beta, wf, wc, g_x, xs, x12, (p_wf, p_bf, p_gamma, p_beta, p_wc, p_bc), ctx.window)
+        _attention_dx(g_o, c12, dv1, w_dx, w4, owner, dx12, True)                                              # dx12[first] += attention
+        # ---- residual block (second half), upstream gradient = g_o: dx12[second] += conv1^T + skip
+        _, dw1, db1, dw2, db2 = ops.res_block_bwd(_X(g_o), g_o, _X(x12, b0=n, B=n), x12, t2, rw1, rw2, (o_rw1, o_rw2),
+                                                  (p_rw1, p_rb1, p_rw2, p_rb2), _dense_spec(Cn), ctx.window, dx=dx12, out_b0=n)
+        return (dx12, dxs, dw1, db1, dw2, db2, dwf, dbf, dgamma, dbeta, dwc, dbc, dwu, dbu, dwv1, dbv1, None, None)
 
 
 def bie_first(m, x12, xs):

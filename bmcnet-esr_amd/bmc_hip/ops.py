@@ -1598,8 +1598,8 @@ def conv_groups(views: Sequence[View], weights, biases, spec: ConvSpec, *, B=Non
 # convolution epilogues, so the backward is exactly 2 data-gradient + 2 weight-gradient launches (+ bias sums)
 # --------------------------------------------------------------------------
 def _wgrad_plain(g, x, spec, w_param, b_param, taps, window=None):
-    """ops.wgrad on whole tensors, g [B,H,W,Cout] and x [B,H,W,Cin] (ResBlockFn's two uses; the kernel tests and tools/time_wgrad.py
-    call it too): descriptors only, the routing is wgrad's."""
+    """ops.wgrad on whole tensors, g [B,H,W,Cout] and x [B,H,W,Cin] (what res_block_bwd does for ResBlockFn; the kernel tests and
+    tools/time_wgrad.py call this form): descriptors only, the routing is wgrad's."""
     B, H, W, Cout = g.shape
     return wgrad(_src(g, 0, Cout, 0, None, 0, B), [_src(x, 0, x.shape[3], 0, None, 0, B)], spec, B, H, W, taps, Cout, g.device, w_param,
                  b_param, keep=(g, x), window=window, merge_pgemm=True)
@@ -1609,7 +1609,7 @@ class GradPair:
     """Where the consumers of the two halves of an un-stacked tensor (bie.Unstack2Fn) put their input gradients: the halves
     of ONE lazily allocated buffer, so that Unstack2Fn.backward returns it as it is instead of concatenating two tensors
     (41 full-size copies per C2 step).  The forward tags the two output views (`_bmc_gslot = (pair, half)`); a consumer that
-    knows the protocol (ResBlockFn, BIETwinFn) writes into grad_slot(...) -- any other consumer, or a view with several
+    knows the protocol (res_block_bwd for ResBlockFn, BIETwinFn) writes into grad_slot(...) -- any other consumer, or a view with several
     consumers, simply produces an ordinary gradient and the concatenation happens as before."""
     __slots__ = ("n", "shape", "buf", "taken")
 
@@ -1645,19 +1645,52 @@ class OutSlot:
         self.t, self.b0 = t, b0
 
 
+def res_block_fwd(x_src, w1, b1, w2, b2, spec, t, y):
+    """t = relu(conv1(x)), y = x + conv2(t) over the B launch images of x_src; t, y: the [B,H,W,C] destinations (ResBlockFn and
+    the residual block inside the BIE nodes, bie.py, each over its own batch window)."""
+    B, _, _, Cn = t.shape
+    taps = w1.shape[-1] * w1.shape[-2]
+    conv_launch([x_src], w1.detach().reshape(1, Cn, Cn, taps), spec, w1, b1.detach(), t, B, relu=True, rule=b1)
+    conv_launch([_src(t, 0, Cn, 0, None, 0, B)], w2.detach().reshape(1, Cn, Cn, taps), spec, w2, b2.detach(), y, B, residual=x_src, rule=b2)
+
+
+def res_block_bwd(g_src, g, x_src, x, t, w1, w2, owners, params, spec, window, dx=None, out_b0=0, gslot=None, need=(True, True, True)):
+    """Backward of res_block_fwd over the B images of t: upstream gradient g_src and block input x_src (g, x: the tensors behind
+    them), w1 / w2 as saved, owners = the caller's (w1, w2) objects (pack-cache keys), params = its (w1, b1, w2, b2) (gradient
+    sinks).  dx: the tensor whose images [out_b0, out_b0 + B) the input gradient is ADDED to; None: a destination of its own
+    (grad_slot(gslot)), written.  need: (input gradient, conv1's parameter gradients, conv2's) wanted.
+    -> (dx, dw1, db1, dw2, db2)"""
+    B, H, W, Cn = t.shape
+    taps = w1.shape[-1] * w1.shape[-2]
+    p_w1, p_b1, p_w2, p_b2 = params
+    ts = _src(t, 0, Cn, 0, None, 0, B)
+    dw1 = db1 = dw2 = db2 = None
+    if need[2]:
+        dw2, db2 = wgrad(g_src, [ts], spec, B, H, W, taps, Cn, t.device, p_w2, p_b2, keep=(g, t), window=window, merge_pgemm=True)
+    # d(pre-activation of conv1) = ReLU'(t) * conv2^T(g): mask epilogue
+    dt = torch.empty_like(t)
+    dgrad_launch(g_src, w2.detach().reshape(1, Cn, Cn, taps), spec, 0, owners[1], dt, B, mask=ts)
+    dts = _src(dt, 0, Cn, 0, None, 0, B)
+    if need[1]:
+        dw1, db1 = wgrad(dts, [x_src], spec, B, H, W, taps, Cn, t.device, p_w1, p_b1, keep=(dt, x), window=window, merge_pgemm=True)
+    if need[0]:   # dx (+)= conv1^T(dt) + g (skip path): residual epilogue
+        accumulate = dx is not None
+        if not accumulate:
+            dx = grad_slot(gslot, dt)
+        dgrad_launch(dts, w1.detach().reshape(1, Cn, Cn, taps), spec, 0, owners[0], dx, B, residual=g_src, accumulate=accumulate, out_b0=out_b0)
+    return dx, dw1, db1, dw2, db2
+
+
 class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, spec, out=None):
         _need_gpu(x)
         B, H, W, Cn = x.shape
-        taps = w1.shape[-1] * w1.shape[-2]
-        xs = _src(x.detach(), 0, Cn, 0, None, 0, B)
         t = torch.empty_like(x)
-        conv_launch([xs], w1.detach().reshape(1, Cn, Cn, taps), spec, w1, b1.detach(), t, B, relu=True, rule=b1)
         y = torch.empty_like(x) if out is None else out.t[out.b0:out.b0 + B]
-        conv_launch([_src(t, 0, Cn, 0, None, 0, B)], w2.detach().reshape(1, Cn, Cn, taps), spec, w2, b2.detach(), y, B, residual=xs, rule=b2)
+        res_block_fwd(_src(x.detach(), 0, Cn, 0, None, 0, B), w1, b1, w2, b2, spec, t, y)
         ctx.save_for_backward(x, t, w1, w2)
-        ctx.spec, ctx.taps = spec, taps
+        ctx.spec = spec
         ctx.owners = (w1, w2)
         ctx.params = (w1, b1, w2, b2)
         ctx.gslot = getattr(x, "_bmc_gslot", None)
@@ -1667,23 +1700,11 @@ class ResBlockFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g):
         x, t, w1, w2 = ctx.saved_tensors
-        spec, taps = ctx.spec, ctx.taps
         g = g.contiguous()
         B, H, W, Cn = g.shape
         need = ctx.needs_input_grad
-        gs, ts = _src(g, 0, Cn, 0, None, 0, B), _src(t, 0, Cn, 0, None, 0, B)
-        p_w1, p_b1, p_w2, p_b2 = ctx.params
-        dw2, db2 = _wgrad_plain(g, t, spec, p_w2, p_b2, taps, ctx.window) if (need[3] or need[4]) else (None, None)
-        # d(pre-activation of conv1) = ReLU'(t) * conv2^T(g): mask epilogue
-        dt = torch.empty_like(g)
-        dgrad_launch(gs, w2.detach().reshape(1, Cn, Cn, taps), spec, 0, ctx.owners[1], dt, B, mask=ts)
-        dts = _src(dt, 0, Cn, 0, None, 0, B)
-        dw1, db1 = _wgrad_plain(dt, x, spec, p_w1, p_b1, taps, ctx.window) if (need[1] or need[2]) else (None, None)
-        dx = None
-        if need[0]:   # dx = conv1^T(dt) + g (skip path): residual epilogue
-            dx = grad_slot(ctx.gslot, g)
-            dgrad_launch(dts, w1.detach().reshape(1, Cn, Cn, taps), spec, 0, ctx.owners[0], dx, B, residual=gs)
-        return dx, dw1, db1, dw2, db2, None, None
+        return res_block_bwd(_src(g, 0, Cn, 0, None, 0, B), g, _src(x, 0, Cn, 0, None, 0, B), x, t, w1, w2, ctx.owners, ctx.params,
+                             ctx.spec, ctx.window, gslot=ctx.gslot, need=(need[0], need[1] or need[2], need[3] or need[4])) + (None, None)
 
 
 def res_block(x, w1, b1, w2, b2, spec, out=None):
