@@ -6,6 +6,10 @@ A slot table is S bmc_slot_t entries (SLOT_DTYPE) in a device uint8 tensor; the 
 channels-last [S,n_c,H,W] views of state k are `to_nchw(buf[k])`, adjacent in one buffer (ops.stack_states reads them
 without a copy).  LAUNCHES counts the launches of each wrapper (the tests check that a window costs one of each).
 
+Self-ensemble (include/bmc_hip.h "multi-stream inference" states the contract): a group of K adjacent slots carries one recording
+in K orientations -- fill_leader() / fill_member() write the group's entries (ORIENT_* / GROUP_SHIFT name the bits of `flags`);
+stage() then orients each member's frames, commit() merges the K predictions into the leader's row of the model's output.
+
 Event-backed slots (csrc/slot_events.hip): a second table of S bmc_slot_events_t entries (SLOT_EVENTS_DTYPE) behind the slot
 table in the same device tensor and the same pinned upload (SlotTable(events=True)); encode() builds the count images of
 every slot with an event entry in one launch, counted in ENCODE_LAUNCHES.
@@ -47,6 +51,12 @@ MAX_SLOTS = lib.const("BMC_MAX_SLOTS")
 MAX_PARTS = lib.const("BMC_SLOT_MAX_PARTS")
 SLOT_DTYPE = lib.dtype("bmc_slot_t")
 LAUNCHES = {"stage": 0, "commit": 0, "metrics": 0}
+# self-ensemble (include/bmc_hip.h "multi-stream inference"): bits of bmc_slot_t.flags that no #define carries -- the
+# orientation code o (ORIENT_H | ORIENT_V | ORIENT_P, the order of the sequence encoder's `flips` bits 0..2) in bits 2..4, the
+# group size K at a group's leader in bits 8..11; the leader's pad_ holds the prediction's row length sW
+ORIENT_SHIFT, ORIENT_H, ORIENT_V, ORIENT_P = 2, 1, 2, 4
+GROUP_SHIFT = 8
+GROUP_SIZES = (2, 4, 8)
 MAX_SEQN = lib.const("BMC_SLOT_MAX_SEQN")
 MAX_ENCODE_WIDTH = 7680
 SLOT_EVENTS_DTYPE = lib.dtype("bmc_slot_events_t")
@@ -200,6 +210,32 @@ def _check(cond, what):
         raise ValueError("slots: " + what)
 
 
+def check_group_size(who, K, S):
+    """self_ensemble K (None, or 2 / 4 / 8 dividing the S slots) -> None or K; ValueError otherwise."""
+    if K is None:
+        return None
+    if isinstance(K, bool) or not isinstance(K, (int, np.integer)) or K not in GROUP_SIZES:
+        raise ValueError(who + "self_ensemble must be None, 2, 4 or 8 (got %r)" % (K,))
+    if S % K:
+        raise ValueError(who + "slots must be a multiple of self_ensemble (got %d slots for groups of %d)" % (S, K))
+    return int(K)
+
+
+def fill_leader(entries, s, K, sW):
+    """entries (SLOT_DTYPE, a table's host view): the filled entry s becomes the leader of the ensemble group s .. s+K-1, the
+    identity member -- it gains the group size K and pad_ = sW, the prediction's row length."""
+    entries[s]["flags"] = int(entries[s]["flags"]) | (K << GROUP_SHIFT)
+    entries[s]["pad_"] = sW
+
+
+def fill_member(entries, s, j):
+    """Entry s = member j >= 1 of the group led by entry s - j: the leader's frames in orientation j, with the leader's ACTIVE /
+    RESET bits, and nothing else -- no ground truth, keep or result (the kernels after commit skip the slot)."""
+    lead, e = entries[s - j], entries[s]
+    e["frames"], e["gt"], e["keep"], e["result"], e["pad_"] = lead["frames"], 0, 0, 0, 0
+    e["flags"] = (int(lead["flags"]) & (ACTIVE | RESET)) | (j << ORIENT_SHIFT)
+
+
 def _feat_layout(pool):
     """pool [nfeat, S, H, W, n_c] contiguous -> (nfeat, feat_n)."""
     _check(pool.dim() == 5 and pool.is_contiguous() and pool.dtype in (torch.float32, torch.bfloat16),
@@ -209,7 +245,8 @@ def _feat_layout(pool):
 
 def stage(table, x, pool, feat, pred):
     """x [S,2,seqn,H,W] <- the slots' windows; feat [nfeat,S,H,W,n_c] fp32 <- the pool's state (zeros for reset / empty
-    slots; feat may BE an fp32 pool); pred [S,2,sH,sW] (the previous predictions, in place) zeroed for reset / empty slots."""
+    slots; feat may BE an fp32 pool); pred [S,2,sH,sW] (the previous predictions, in place) zeroed for reset / empty slots.
+    A slot whose flags carry an orientation code gets its frames in that orientation."""
     S, two, seqn, H, W = x.shape
     nfeat, feat_n = _feat_layout(pool)
     _check(two == 2 and x.is_contiguous() and x.dtype == torch.float32, "x must be a contiguous fp32 [S,2,seqn,H,W]")
@@ -224,7 +261,8 @@ def stage(table, x, pool, feat, pred):
 
 def commit(table, srcs, pool, pred_src, pred_pool):
     """Active slots: pool[k] <- srcs[k] (the model's new [S,n_c,H,W] channels-last states; bf16 pool: nearest-even),
-    pred_pool <- pred_src, and the prediction to each slot's `keep` address."""
+    pred_pool <- pred_src, and the prediction to each slot's `keep` address.  The leader of an ensemble group (fill_leader):
+    its row of pred_src and its `keep` then receive the group's merged prediction -- pred_src is written in place."""
     nfeat, feat_n = _feat_layout(pool)
     S = pool.shape[1]
     _check(len(srcs) == nfeat, "%d state tensors for a pool of %d" % (len(srcs), nfeat))

@@ -8,6 +8,9 @@
 //                     fixed-order sum of a fixed set of elements, written as partial sums that the host adds in a fixed
 //                     order when it reads them (no atomics: bit-reproducible, and a slot's sums do not depend on its
 //                     neighbours).
+// Self-ensemble (include/bmc_hip.h states the contract) is table data behind the first two: stage gathers the frames of a slot
+// with an orientation code oriented, commit merges the predictions of a group of K slots into its leader's row of the model's
+// output, in place, which the metrics and the later slot kernels then read.
 // The per-slot table (bmc_slot_t) lives in device memory, so a captured graph replays with whatever the host copied into it.
 // Pointers read from the table are generic to the compiler: every access goes through an address-space(1) cast (global_*
 // instructions, never flat_*).
@@ -39,6 +42,13 @@ __device__ __forceinline__ bmc_slot_t load_slot(const bmc_slot_t* table, int s) 
     return e;
 }
 
+// bits 2..4 of the flags: the slot's orientation code (bit 0 horizontal, 1 vertical, 2 polarity)
+__device__ __forceinline__ int orient_of(int flags) { return (flags >> 2) & 7; }
+// where element (c, y, x) of O_o(img) lies in img [2][H][W]: img[c ^ p][v ? H-1-y : y][h ? W-1-x : x]
+__device__ __forceinline__ int oriented(int o, int c, int y, int x, int H, int W) {
+    return ((c ^ (o >> 2)) * H + ((o & 2) ? H - 1 - y : y)) * W + ((o & 1) ? W - 1 - x : x);
+}
+
 struct SlotInfo {
     bool active, zero;
 };
@@ -50,7 +60,7 @@ __device__ __forceinline__ SlotInfo slot_info(const bmc_slot_t& e) {
 }
 
 // grid (nbx, S), 256 threads: blockIdx.y is the slot, the blocks of a slot stride over its elements
-__global__ __launch_bounds__(256) void slot_stage_kernel(const bmc_slot_t* __restrict__ table, int seqn, int HW,
+__global__ __launch_bounds__(256) void slot_stage_kernel(const bmc_slot_t* __restrict__ table, int seqn, int H, int W,
                                                          float* __restrict__ x, const void* pool, int pool_bf16, float* feat,
                                                          int nfeat, long long feat_n, long long feat_stride, float* pred,
                                                          long long pred_n) {
@@ -58,17 +68,27 @@ __global__ __launch_bounds__(256) void slot_stage_kernel(const bmc_slot_t* __res
     const bmc_slot_t e = load_slot(table, s);
     const SlotInfo si = slot_info(e);
     const long long t0 = (long long)blockIdx.x * blockDim.x + threadIdx.x, step = (long long)gridDim.x * blockDim.x;
-    // input window: x[s][c][t][p] = frames[t][c][p] (the recording's frames i .. i+seqn-1, transposed as infer_BMCNet.py:51)
+    // input window: x[s][c][t][p] = frames[t][c][p] (the recording's frames i .. i+seqn-1, transposed as infer_BMCNet.py:51),
+    // every frame in the slot's orientation (uniform over the slot's workgroups; code 0 takes the loop it always took)
+    const int HW = H * W, o = orient_of(e.flags);
     const long long xn = 2ll * seqn * HW;
     float* const xs = x + (long long)s * xn;
-    for (long long i = t0; i < xn; i += step) {
-        float v = 0.f;
-        if (si.active) {
-            const long long p = i % HW, ct = i / HW;
-            const int t = (int)(ct % seqn), c = (int)(ct / seqn);
-            v = gld<float>(e.frames + ((long long)t * 2 + c) * HW + p);
+    if (si.active && o) {
+        for (long long i = t0; i < xn; i += step) {
+            const int p = (int)(i % HW), ct = (int)(i / HW);
+            const int t = ct % seqn, c = ct / seqn;
+            gst<float>(xs + i, gld<float>(e.frames + (long long)t * 2 * HW + oriented(o, c, p / W, p % W, H, W)));
         }
-        gst<float>(xs + i, v);
+    } else {
+        for (long long i = t0; i < xn; i += step) {
+            float v = 0.f;
+            if (si.active) {
+                const long long p = i % HW, ct = i / HW;
+                const int t = (int)(ct % seqn), c = (int)(ct / seqn);
+                v = gld<float>(e.frames + ((long long)t * 2 + c) * HW + p);
+            }
+            gst<float>(xs + i, v);
+        }
     }
     // feature states: zeros, a widened bf16 pool, or a copy from a separate fp32 pool; nothing when the fp32 pool IS the buffer
     if (si.zero || pool_bf16 || (const void*)feat != pool) {
@@ -96,14 +116,56 @@ __global__ __launch_bounds__(256) void slot_stage_kernel(const bmc_slot_t* __res
     }
 }
 
+// Self-ensemble (include/bmc_hip.h): the merge of a group's K predictions into its leader's row of the model's output, by the
+// workgroups of the leader.  Lane i owns the four canonical elements 4i .. 4i+3 of [2][sH][sW]: it reads them from the leader's row
+// (the identity member), hands them to the pool and to nobody else, adds the members' un-oriented values in slot order and only
+// then overwrites them -- no other lane reads or writes these sixteen bytes of the leader's row, and member rows are only read.
+// VEC (sW % 4 == 0): the four elements lie in one image row, a member's four sources are one aligned 16-byte load (reversed
+// for a horizontal flip); otherwise four element loads.  The same additions in the same order either way.
+template <bool VEC>
+__device__ __forceinline__ void merge_group(const bmc_slot_t* table, int s, int K, int sH, int sW, float* pred_src,
+                                            float* pred_pool, long long pred_n, float* keep, long long t0, long long step) {
+    float* const lead = pred_src + (long long)s * pred_n;
+    float* const pd = pred_pool + (long long)s * pred_n;
+    const float scale = 1.0f / (float)K;
+    for (long long i = t0; i < pred_n / 4; i += step) {
+        const f32x4 own = gld<f32x4>(lead + 4 * i);
+        gst<f32x4>(pd + 4 * i, own);
+        f32x4 acc = own;
+        const int e0 = (int)(4 * i);
+        for (int j = 1; j < K; ++j) {
+            const int o = orient_of(gld<int>(&table[s + j].flags));
+            const float* const row = pred_src + (long long)(s + j) * pred_n;
+            f32x4 u;
+            if (VEC) {
+                const int x0 = e0 % sW, r = e0 / sW;
+                const bool h = o & 1;
+                const f32x4 m = gld<f32x4>(row + oriented(o, r / sH, r % sH, h ? x0 + 3 : x0, sH, sW));
+                u = h ? f32x4{m.w, m.z, m.y, m.x} : m;
+            } else {
+                float q[4];
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int el = e0 + k, r = el / sW;
+                    q[k] = gld<float>(row + oriented(o, r / sH, r % sH, el % sW, sH, sW));
+                }
+                u = f32x4{q[0], q[1], q[2], q[3]};
+            }
+            acc = f32x4{acc.x + u.x, acc.y + u.y, acc.z + u.z, acc.w + u.w};
+        }
+        const f32x4 v = {acc.x * scale, acc.y * scale, acc.z * scale, acc.w * scale};
+        gst<f32x4>(lead + 4 * i, v);
+        if (keep) gst<f32x4>(keep + 4 * i, v);
+    }
+}
+
 struct FeatSrc {
     const float* p[3];
 };
 
 __global__ __launch_bounds__(256) void slot_commit_kernel(const bmc_slot_t* __restrict__ table, FeatSrc src, int nfeat,
                                                           long long feat_n, long long feat_stride, void* pool, int pool_bf16,
-                                                          const float* __restrict__ pred_src, float* __restrict__ pred_pool,
-                                                          long long pred_n) {
+                                                          float* pred_src, float* __restrict__ pred_pool, long long pred_n) {
     const int s = blockIdx.y;
     const bmc_slot_t e = load_slot(table, s);
     if (!slot_info(e).active) return;
@@ -120,6 +182,20 @@ __global__ __launch_bounds__(256) void slot_commit_kernel(const bmc_slot_t* __re
                 gst<u16x4>((unsigned short*)pool + o + 4 * i, u16x4{f2bf(v.x), f2bf(v.y), f2bf(v.z), f2bf(v.w)});
             else
                 gst<f32x4>((float*)pool + o + 4 * i, v);
+        }
+    }
+    // the leader of an ensemble group (bits 8..11: K members from this slot on, pad_: the prediction's row length); a K or a
+    // row length that does not fit the launch is no group
+    const int K = (e.flags >> 8) & 15;
+    if (K == 2 || K == 4 || K == 8) {
+        const int sW = gld<int>(&table[s].pad_);
+        if (s + K <= (int)gridDim.y && sW > 0 && pred_n < (1ll << 31) && pred_n % (2ll * sW) == 0) {
+            const int sH = (int)(pred_n / (2ll * sW));
+            if (sW % 4 == 0)
+                merge_group<true>(table, s, K, sH, sW, pred_src, pred_pool, pred_n, e.keep, t0, step);
+            else
+                merge_group<false>(table, s, K, sH, sW, pred_src, pred_pool, pred_n, e.keep, t0, step);
+            return;
         }
     }
     const float* const ps = pred_src + (long long)s * pred_n;
@@ -211,14 +287,14 @@ extern "C" int bmc_slot_stage(const bmc_slot_t* table, int S, int seqn, int H, i
     long long work = feat_n / 4;
     if (2ll * seqn * H * W > work) work = 2ll * seqn * H * W;
     if (pred_n / 4 > work) work = pred_n / 4;
-    hipLaunchKernelGGL(slot_stage_kernel, dim3(slot_blocks(work, S), S), dim3(256), 0, (hipStream_t)s, table, seqn, H * W, x,
+    hipLaunchKernelGGL(slot_stage_kernel, dim3(slot_blocks(work, S), S), dim3(256), 0, (hipStream_t)s, table, seqn, H, W, x,
                        feat_pool, pool_bf16, feat, nfeat, feat_n, (long long)S * feat_n, pred, pred_n);
     BMC_CHECK_LAUNCH("bmc_slot_stage");
     return 0;
 }
 
 extern "C" int bmc_slot_commit(const bmc_slot_t* table, int S, const float* const* feat_src, int nfeat, long long feat_n,
-                               void* feat_pool, int pool_bf16, const float* pred_src, float* pred_pool, long long pred_n,
+                               void* feat_pool, int pool_bf16, float* pred_src, float* pred_pool, long long pred_n,
                                bmc_stream_t s) {
     BMC_CHECK_ARG(table && feat_src && feat_pool && pred_src && pred_pool && S >= 1 && S <= BMC_MAX_SLOTS && nfeat >= 1 &&
                       nfeat <= 3 && feat_n > 0 && feat_n % 4 == 0 && pred_n > 0 && pred_n % 4 == 0,

@@ -16,7 +16,7 @@ import torch
 
 from bmc_hip import slots
 from bmc_hip.encodings import event_block_spans
-from bmc_hip.slots import check_hot_filter
+from bmc_hip.slots import check_group_size, check_hot_filter
 from infer_parts import EventStream, HotFilter, Input, KeptPredictions, Metrics, Pictures, VoxelGrids
 
 EventRecording = collections.namedtuple("EventRecording", "lr gt lr_index gt_index lr_size gt_size", defaults=(None,) * 5)
@@ -221,6 +221,12 @@ class SlotScheduler:
                 s[1] += 1
         return out
 
+    @staticmethod
+    def expand(plan, K):
+        """A plan of GROUPS of K slots each -> per physical slot (handle, window index, reset, member) or None: group g owns
+        slots gK .. gK+K-1, member j of it (slot gK+j) runs the group's window; member 0 is the group's leader."""
+        return [None if p is None else p + (j,) for p in plan for j in range(K)]
+
 
 def _tensors(v):
     """Every tensor reachable in v through tuples, lists and dict values."""
@@ -254,7 +260,19 @@ class MultiStreamSR:
       keep_predictions            KeptPredictions  predictions [n_windows,2,sH,sW]
       emit_events, event_times    EventStream      the super-resolved event stream: plain, timed, or on the sensor's clock
       render=(kinds...)           Pictures         the reference's event-count images
-      voxel_bins=B                VoxelGrids       the voxel grid of every window's events"""
+      voxel_bins=B                VoxelGrids       the voxel grid of every window's events
+
+    self_ensemble=K (2, 4 or 8; `slots` a multiple of K): geometric self-ensemble, the "+" row of super-resolution tables.  A
+    recording takes a GROUP of K adjacent slots: member j sees every frame in orientation j (bit 0 of j: flipped horizontally,
+    bit 1: vertically, bit 2: polarities swapped -- K = 2: identity and h; 4: also v and hv; 8: all eight; the symmetries the
+    network is trained with, EventTrainSet(augment=...)) and keeps its own recurrent state in that orientation; bmc_slot_stage
+    orients the frames as it gathers them, and bmc_slot_commit turns the K predictions back, averages them (a float32 sum in
+    member order, times 1/K) and writes the result over the leader's row of the model's output.  Everything downstream reads
+    that row: predictions, esr_mse, sr_events / sr_ts, the "esr" picture and voxels are those of the merged prediction;
+    bicubic_mse, the other pictures and hot_* are as without the option.  Nothing else changes per window -- the orientation is
+    table data, one stage and one commit launch, the window of an event-backed recording encoded (and filtered) once -- but a
+    window costs K slots of compute: the session runs slots / K recordings at a time.  include/bmc_hip.h "multi-stream
+    inference" states the contract."""
 
     MAX_VOXEL_BINS, MAX_COUNT_LIMIT, MAX_COUNT_TIMED = slots.MAX_VOXEL_BINS, slots.MAX_COUNT_LIMIT, slots.MAX_COUNT_TIMED
     MAX_WINDOW_CAPACITY, MAX_ITEMS_FILTERED = slots.MAX_WINDOW_CAPACITY, slots.HOT_MAX_ITEMS
@@ -262,8 +280,10 @@ class MultiStreamSR:
     RENDER_KINDS, RENDER_TABLES, check_render = Pictures.KINDS, Pictures.TABLES, staticmethod(Pictures.check)
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
-                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None, voxel_bins=None):
+                 seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None, voxel_bins=None,
+                 self_ensemble=None):
         self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)  # (the argument `slots` hides the module here)
+        self.self_ensemble = check_group_size("MultiStreamSR: ", self_ensemble, int(slots))
         self.render = self.check_render("MultiStreamSR: ", render)
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
@@ -280,7 +300,7 @@ class MultiStreamSR:
         self.use_graph, self.keep_predictions = graph, keep_predictions
         self.state_dtype = None if state_dtype is torch.float32 else state_dtype
         self.emit_events, self.max_count = bool(emit_events), max_count
-        self.sched = SlotScheduler(self.S)
+        self.sched = SlotScheduler(self.S // (self.self_ensemble or 1))      # of groups of K slots with self_ensemble=K
         self.replays = self._calls = 0
         self._recs = {}
         self._size = None          # (H, W) of the first recording, (H, W, gh, gw) once one with ground truth has been opened
@@ -552,14 +572,20 @@ class MultiStreamSR:
         for name in ("events", "emit", "clock", "hot", "render", "voxel"):
             if getattr(t, name):
                 v[name] = getattr(t, name + "_host")()
-        for s, p in enumerate(plan):
+        K = self.self_ensemble or 1                        # the plan is of groups of K slots: the parts fill the leader's entries
+        for s, p in enumerate(SlotScheduler.expand(plan, K)):
             if p is None:
                 continue
-            h, i, reset = p
+            h, i, reset, j = p
+            if j:                                          # a member: the leader's frames, oriented; every other entry stays 0
+                slots.fill_member(v["slot"], s, j)
+                continue
             r = self._recs[h]
             v["slot"][s]["flags"] = slots.ACTIVE | (slots.RESET if reset else 0)
             for part in self.parts:
                 part.fill(self, v, s, r, i, reset)
+            if K > 1:
+                slots.fill_leader(v["slot"], s, K, self.scale * self._size[1])
             r["steps"].append(len(self._steps))
 
     @torch.no_grad()
@@ -596,7 +622,7 @@ class MultiStreamSR:
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
-                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None):
+                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None, self_ensemble=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
@@ -613,11 +639,13 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                                          window in time order (window_event_capacity: per recording, None = the default)][,
       images      = {name: {kind: uint8 [n_windows,h,w,3]}}  with render: the event-count images of every recording]).
     hot_filter (the EventRecording items are filtered, frame pairs are not), render (a tuple of kinds from "lr", "bicubic", "esr",
-    "gt"), voxel_bins=B (the result then carries voxels = {name: float32 [n_windows,B,sH,sW]}): MultiStreamSR's options."""
+    "gt"), voxel_bins=B (the result then carries voxels = {name: float32 [n_windows,B,sH,sW]}), self_ensemble=K (2, 4, 8; slots a
+    multiple of K: every recording runs in K orientations and esr_mse, predictions, sr_events, the esr image and voxels are those
+    of the merged prediction): MultiStreamSR's options."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
-                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, self_ensemble=self_ensemble)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):

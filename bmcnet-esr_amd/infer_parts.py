@@ -384,6 +384,8 @@ class Pictures(Part):
             d["render_resize"] = ((ms.S, 2) + tuple(ms._size[2:]), F32, 0, True)
         if "bicubic" in names:
             d["render_mid"] = ((ms.S, 2) + tuple(ms._size[:2]), F32, 0, True)
+        if "esr" in names and ms.self_ensemble:            # the merged predictions, at an address the table can name
+            d["render_pred"] = ((ms.S, 2, ms.scale * ms._size[0], ms.scale * ms._size[1]), F32, 0, True)
         return d
 
     def fill(self, ms, v, s, r, i, reset):
@@ -395,7 +397,8 @@ class Pictures(Part):
             if kind == "lr":                               # frame 1 of the window
                 table, src = "lr", int(e["frames"]) + 4 * 2 * H * W
             elif kind == "esr":
-                table, src = ("esr_gt", b["render_resize"][s].data_ptr()) if resized else ("esr", b["pred"][s].data_ptr())
+                table, src = ("esr_gt", b["render_resize"][s].data_ptr()) if resized else \
+                    ("esr", b["render_pred" if ms.self_ensemble else "pred"][s].data_ptr())
             elif kind == "bicubic":
                 table, src = "bicubic", b["render_resize"][s].data_ptr()
             else:
@@ -404,10 +407,14 @@ class Pictures(Part):
             rn[k, s]["src"], rn[k, s]["dst"] = src, img[i].data_ptr()
 
     def launch(self, ms, b, pred):
-        # "esr" reads b["pred"], where commit has put the predictions; the resize scratch serves the prediction first, then frame 1
+        # "esr" reads b["pred"], where commit has put the predictions; the resize scratch serves the prediction first, then frame 1.
+        # A self-ensemble session: b["pred"] holds every member's OWN prediction (its recurrence), the merged one is in the leader's
+        # row of `pred`, the model's output, which has no lasting address: "esr" reads a copy of it
         S, (H, W) = ms.S, ms._size[:2]
         for name, h, w, rnd in self.tables(ms):
-            if name == "esr_gt":
+            if name == "esr" and ms.self_ensemble:
+                b["render_pred"].copy_(pred)
+            elif name == "esr_gt":
                 lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", pred.data_ptr(), 2 * S, ms.scale * H, ms.scale * W, h, w,
                          b["render_resize"].data_ptr(), _stream())
             elif name == "bicubic":

@@ -499,7 +499,33 @@ int bmc_head_resize_mse_bwd(const float* dpred, const float* diff, const float* 
  * ONE launch for all S slots; `table` is a DEVICE array of S bmc_slot_t that the host refreshes before each window.
  * Feature states: nfeat tensors (h, h_p, h_n for BMCNet; h for BMCNet_plain) of feat_n = n_c*H*W values per slot, NHWC per
  * slot, laid out [nfeat][S][feat_n] (the model's channels-last [S,n_c,H,W] views, adjacent in one buffer).  The pool holds them
- * in fp32 or bf16 (pool_bf16); the previous prediction [S][pred_n] (pred_n = 2*sH*sW) is always fp32. */
+ * in fp32 or bf16 (pool_bf16); the previous prediction [S][pred_n] (pred_n = 2*sH*sW) is always fp32.
+ *
+ * Self-ensemble (MultiStreamSR(self_ensemble=K)): K adjacent slots carry one recording in K orientations and their predictions
+ * are merged into one.  It is table data only -- bits of bmc_slot_t.flags above BMC_SLOT_RESET and the entry's pad_ word; an
+ * entry with those bits clear and pad_ == 0 behaves byte for byte as before.
+ *   flags bits 2..4: the slot's orientation code o; bit 2 horizontal (h), bit 3 vertical (v), bit 4 polarity (p) -- the order
+ *     of bmc_seq_sample_t.flips bits 0..2.  It acts on a finished two-channel image,
+ *         O_o(img)[c][y][x] = img[c ^ p][v ? H-1-y : y][h ? W-1-x : x],
+ *     an involution; whatever the encoder put into an image (its out-of-range pixel included) moves with the image.
+ *   flags bits 8..11: the group size K in {2, 4, 8} at the LEADER of a group, the first of the slots s .. s+K-1 (0, or any
+ *     other value: no group).  The caller guarantees that these slots exist, are active and are reset together, that no group
+ *     overlaps another, and that the leader's own code is 0: its row is merged as it stands (a lane can overwrite only what it
+ *     alone reads).  pad_ at a leader: the prediction's row length sW, with sH = pred_n / (2 sW) (a pad_ <= 0 or one that does
+ *     not divide pred_n / 2, or s + K > S: no group); 0 in every other entry.
+ *   bmc_slot_stage: an active slot's input is x[s][c][t] = O_o(frames[t])[c]; state and previous prediction as without a code:
+ *     every member keeps its own recurrence, in its own orientation.
+ *   bmc_slot_commit, at a leader s, after every slot's state and pred_src[s] -> pred_pool[s] copy (the leader's too: its
+ *     recurrence continues from its OWN prediction): for every element (c, row, x) of [2][sH][sW], in float32, each operation
+ *     rounded on its own and the members taken in slot order,
+ *         acc = pred_src[s][c][row][x];  acc = acc + O_{o_j}(pred_src[s+j])[c][row][x]  (j = 1 .. K-1, o_j from entry s+j);
+ *         merged = acc * (1.0f / K)                                                       (exact: K is a power of two)
+ *     and merged is written to pred_src[s] -- the leader's row of the model's output, IN PLACE -- and to the leader's `keep` if
+ *     set.  The lane that owns an element of the leader's row reads it, stores it to pred_pool and only then overwrites it;
+ *     member rows are only read; no atomics, no workgroup waits for another: deterministic.  Rows with sW % 4 == 0 take 16-byte
+ *     accesses, other rows element loads, with the same bits.  The kernels that run after it (bmc_slot_metrics, bmc_slot_emit*,
+ *     bmc_slot_render, bmc_slot_voxel) read pred[s] and skip a slot whose own entry is NULL: with NULL entries for the
+ *     members, the leader's entries see the merged prediction. */
 #define BMC_MAX_SLOTS 256
 #define BMC_SLOT_ACTIVE 1   /* the slot carries a recording this window */
 #define BMC_SLOT_RESET 2    /* ... whose first window this is: its state is read as exact zeros (infer_BMCNet.py:55-60) */
@@ -508,8 +534,8 @@ typedef struct bmc_slot {
     const float* gt;        /* the window's ground truth [2][gh][gw] (gt of window i = frame i+1, infer_BMCNet.py:49) */
     float* keep;            /* NULL, or where bmc_slot_commit copies the slot's prediction [2][sH][sW] */
     double* result;         /* NULL, or where bmc_slot_metrics writes nparts x {esr_sse, bicubic_sse} partial sums */
-    int flags;              /* BMC_SLOT_ACTIVE | BMC_SLOT_RESET; 0 (or frames NULL): an empty slot */
-    int pad_;
+    int flags;              /* BMC_SLOT_ACTIVE | BMC_SLOT_RESET; 0 (or frames NULL): an empty slot; bits 2..4, 8..11: self-ensemble */
+    int pad_;               /* 0; at the leader of an ensemble group: the prediction's row length sW */
 } bmc_slot_t;
 
 /* Before the forward pass (replaces the per-recording input_stack / init_h / init_o tensors of infer_BMCNet.py:51,55-60):
@@ -520,9 +546,10 @@ int bmc_slot_stage(const bmc_slot_t* table, int S, int seqn, int H, int W, float
                    float* feat, int nfeat, long long feat_n, float* pred, long long pred_n, bmc_stream_t s);
 /* After the forward pass (the carried h, hp, hn, prediction of infer_BMCNet.py:62-63), active slots only: feat_src = HOST
  * array of nfeat device pointers, each [S][feat_n] fp32 (the model's new states) -> the pool (bf16: round to nearest-even,
- * bit-identical to tensor.to(torch.bfloat16)); pred_src [S][pred_n] -> pred_pool and, where the slot's `keep` is set, there. */
+ * bit-identical to tensor.to(torch.bfloat16)); pred_src [S][pred_n] -> pred_pool and, where the slot's `keep` is set, there.
+ * pred_src is written only at the leader of an ensemble group (above): its row becomes the group's merged prediction. */
 int bmc_slot_commit(const bmc_slot_t* table, int S, const float* const* feat_src, int nfeat, long long feat_n, void* feat_pool,
-                    int pool_bf16, const float* pred_src, float* pred_pool, long long pred_n, bmc_stream_t s);
+                    int pool_bf16, float* pred_src, float* pred_pool, long long pred_n, bmc_stream_t s);
 /* The metrics of infer_BMCNet.py:76-85 as sums of squares, per active slot with a `result`, split into nparts
  * (1 .. BMC_SLOT_MAX_PARTS) partial sums over fixed element sets (element i of [2][gh][gw] in part (i / 1024) % nparts):
  * result[2p] = part p of sum (bicubic(pred[s] -> gh x gw) - gt)^2 (no resize when sH x sW == gh x gw), result[2p+1] = part p

@@ -26,13 +26,18 @@ array itself, one pixel per element; the reference's files are the same array re
 alternating runs each in this process (windows/s: the median, and every run), the bmc_slot_voxel call alone (both kernels, events
 around 20 calls on the session's last table and prediction) and, for the same predictions, the composition it replaces: the timed
 event stream of every slot (counts_to_events(times="linear")) and events_to_voxel_torch on its columns, slot by slot.
+--self-ensemble K [--plain-weights NPZ] adds, per configuration whose slot count K divides, the session with self_ensemble=K and the
+one without, --runs alternating runs each, on structured synthetic recordings (drifting bars: the ground truth is the Poisson counts
+of an HR rate field, an LR frame those of its 4 x 4 block means): RECORDING windows/s of both (with the option a recording takes K
+slots) and the mean esr_mse of the recordings both ran.  --plain-weights: BMCNet_plain(4,128,5) with the parameters of the file.
 --resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
                                   [--hot-filter] [--runs 3]
                                   [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
-                                  [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]"""
+                                  [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]
+                                  [--self-ensemble K] [--plain-weights NPZ]"""
 import argparse
 import json
 import os
@@ -181,6 +186,40 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
     return lat, S * windows / wall, ms.resident_bytes(hs[0])
 
 
+def structured_recording(L, H, W, seed, dev):
+    """A synthetic recording with structure a super-resolver can use: the HR event rate is a field of drifting oriented bars
+    (ON where they advance, OFF where they retreat), the ground truth its Poisson counts, an LR frame the Poisson counts of the
+    4 x 4 block means -> (frames [L,2,H,W], gts [L,2,4H,4W]) on `dev`."""
+    g = torch.Generator().manual_seed(seed)
+    yy, xx = torch.meshgrid(torch.arange(4 * H, dtype=torch.float32), torch.arange(4 * W, dtype=torch.float32), indexing="ij")
+    angle, period, speed = (torch.rand(3, generator=g) * torch.tensor([3.1416, 24.0, 3.0]) + torch.tensor([0.0, 12.0, 1.0])).tolist()
+    phase = (xx * torch.cos(torch.tensor(angle)) + yy * torch.sin(torch.tensor(angle))) * (6.2832 / period)
+    t = torch.arange(L, dtype=torch.float32)[:, None, None] * speed * (6.2832 / period)
+    edge = torch.cos(phase[None] - t)                                      # the brightness change as the bars drift
+    rate = torch.stack([edge.clamp(min=0), (-edge).clamp(min=0)], 1) ** 4 * 0.6 + 0.01
+    gts = torch.poisson(rate, generator=g)
+    frames = torch.poisson(torch.nn.functional.avg_pool2d(rate, 4), generator=g)
+    return frames.to(dev), gts.to(dev)
+
+
+def ensemble(m, plain, recs, S, K, graph, warmup, windows):
+    """One session of S slots on the first S / (K or 1) recordings, self_ensemble=K (None: off) -> (ms per window, RECORDING
+    windows per second, per recording the mean esr_mse and the mean bicubic_mse over its timed windows)."""
+    ms = MultiStreamSR(m, S, n_c=128, scale=4, plain=plain, graph=graph, seqn=SEQN, self_ensemble=K)
+    hs = [ms.open(f, g) for f, g in recs[:S // (K or 1)]]
+    for _ in range(warmup):
+        ms.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(windows):
+        ms.step()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    res = [ms.results(h) for h in hs]
+    mean = lambda key: [statistics.mean(r[key][warmup:]) for r in res]
+    return statistics.median(res[0]["time"][warmup:]), len(hs) * windows / wall, mean("esr_mse"), mean("bicubic_mse")
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--sizes", default="31x56,45x80,180x240")
@@ -208,7 +247,15 @@ def parse_args(argv=None):
                     help="with --render: the kinds, a comma-separated choice of lr,bicubic,esr,gt (default: all four)")
     ap.add_argument("--voxel-bins", type=int, default=None, metavar="B",
                     help="adds the session with the per-window voxel grids on (voxel_bins=B, 1 .. 32) and off, alternating runs")
+    ap.add_argument("--self-ensemble", type=int, default=None, metavar="K", choices=(2, 4, 8),
+                    help="adds, per configuration whose slots K divides, the session with self_ensemble=K and the one without on the "
+                         "same structured synthetic recordings: recording windows/s and mean esr_mse of both, --runs alternating runs")
+    ap.add_argument("--plain-weights", metavar="NPZ", default=None,
+                    help="with --self-ensemble: run BMCNet_plain(4,128,5) with the parameters of this file (p/<name> arrays, as "
+                         "tests/golden/plain_pretrained_weights.npz) instead of a randomly initialised BMCNet")
     a = ap.parse_args(argv)
+    if a.plain_weights is not None and a.self_ensemble is None:
+        ap.error("--plain-weights needs --self-ensemble K")
     if a.voxel_bins is not None and not 1 <= a.voxel_bins <= MultiStreamSR.MAX_VOXEL_BINS:
         ap.error("--voxel-bins: 1 <= B <= %d" % MultiStreamSR.MAX_VOXEL_BINS)
     if a.render_kinds is not None and a.render is None:
@@ -233,6 +280,16 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     m = BMCNet(4, 128, 5).to(dev)
+    em, eplain = m, False                                  # the model of the --self-ensemble rows
+    if a.plain_weights is not None:
+        import numpy as np
+        from models.BMCNet_plain import BMCNet_plain
+        em, eplain = BMCNet_plain(4, 128, 5), True
+        z = np.load(a.plain_weights, allow_pickle=False)
+        with torch.no_grad():
+            for name, p in em.named_parameters():
+                p.copy_(torch.from_numpy(z["p/" + name]))
+        em.to(dev)
     rows = []
     L = a.warmup + a.windows + SEQN - 1
     for size in a.sizes.split(","):
@@ -308,6 +365,25 @@ def main():
                                      voxel_alone_ms=round(vox, 4), voxel_share=round(vox / lat, 4),
                                      composition_ms=round(statistics.median(r[3] for r in on), 3), resident_bytes=on[-1][4]))
                     print(json.dumps(rows[-1]), flush=True)
+                if a.self_ensemble is not None and S % a.self_ensemble == 0:
+                    K = a.self_ensemble
+                    srecs = [structured_recording(L, H, W, 7 * H * W + k, dev) for k in range(S)]
+                    off, on = [], []
+                    for _ in range(a.runs):
+                        off.append(ensemble(em, eplain, srecs, S, None, graph, a.warmup, a.windows))
+                        on.append(ensemble(em, eplain, srecs, S, K, graph, a.warmup, a.windows))
+                    n = S // K                             # the recordings both sessions ran
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(self-ensemble)", slots=S, self_ensemble=K,
+                                     model="BMCNet_plain, " + os.path.basename(a.plain_weights) if eplain else "BMCNet, random",
+                                     ms_per_window=round(statistics.median(r[0] for r in on), 3),
+                                     windows_per_s=round(statistics.median(r[1] for r in on), 1),
+                                     windows_per_s_off=round(statistics.median(r[1] for r in off), 1),
+                                     windows_per_s_runs=[round(r[1], 1) for r in on],
+                                     windows_per_s_off_runs=[round(r[1], 1) for r in off],
+                                     esr_mse=statistics.mean(on[-1][2]), esr_mse_off=statistics.mean(off[-1][2][:n]),
+                                     bicubic_mse=statistics.mean(on[-1][3]), recordings=n))
+                    print(json.dumps(rows[-1]), flush=True)
+                    del srecs
                 if a.no_gt:
                     lat, wps, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, no_gt=True)
                     rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(no gt)", slots=S, ms_per_window=round(lat, 3),
