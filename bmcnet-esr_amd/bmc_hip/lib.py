@@ -122,11 +122,11 @@ AdamHyper = _mirror("bmc_adam_hyper_t", "AdamHyper")
 AdamClip = _mirror("bmc_adam_clip_t", "AdamClip")
 
 
-def _sig(name):
-    if name not in FUNCTIONS:
-        raise ImportError(f"{LIB_PATH}: bmc_abi() does not describe {name} (is it in the function list of csrc/abi.hip?)")
+def _sig(name, functions=FUNCTIONS):
+    if name not in functions:
+        raise ImportError(f"{LIB_PATH}: the library's ABI text does not describe {name} (is it in the function list of csrc/abi.hip?)")
     fn = getattr(_lib, name)
-    restype, *params = FUNCTIONS[name]
+    restype, *params = functions[name]
     fn.argtypes = [_ctype(code) for code in params]
     fn.restype = C.c_char_p if restype == "p:char" else _ctype(restype)
     return fn

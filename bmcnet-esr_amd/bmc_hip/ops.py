@@ -16,7 +16,7 @@ from typing import List, Optional, Sequence
 
 import torch
 
-from . import lib
+from . import lib, loss_lib
 
 CK = lib.const("BMC_CK")
 _cur_dev = torch._C._cuda_getDevice      # torch.cuda.current_device() without its Python-level lazy-init wrapper
@@ -2136,11 +2136,80 @@ def head_resize_mse(xo, base, gt, r):
     return HeadResizeMseFn.apply(xo, base, gt, r)
 
 
-def head_loss(xo, base, gt, r):
-    """What the models' forward_loss calls: head_mse for a ground truth of the prediction's size, head_resize_mse otherwise."""
-    if tuple(gt.shape[-2:]) == (xo.shape[1] * r, xo.shape[2] * r):
-        return head_mse(xo, base, gt, r)
-    return head_resize_mse(xo, base, gt, r)
+class HeadLossFn(torch.autograd.Function):
+    """(pred, loss) = head + a robust loss (bmc_hip.losses: L1, Huber, Charbonnier) against a ground truth of either size in
+    one pass (bmc_head_loss_fwd): pred is bit for bit ops.head's.  A ground truth of another size is compared with the bicubic-
+    resized prediction, which is never stored; saved for backward is then d = resized - gt alone (rho' is applied while
+    bmc_head_loss_bwd gathers), and at the prediction's own size pred and gt, nothing new.  Where no backward can follow
+    (torch.no_grad()) nothing of the ground truth's size is allocated."""
+
+    @staticmethod
+    def forward(ctx, xo, base, gt, r, kind, param):
+        _need_gpu(xo)
+        xo = xo.contiguous()
+        B, H, W, CC = xo.shape
+        Cc = CC // (r * r)
+        if gt.dim() != 4 or tuple(gt.shape[:2]) != (B, Cc) or not gt.is_cuda or gt.dtype != torch.float32:
+            raise RuntimeError("head_loss: ground truth must be a float32 GPU tensor [B, C, gh, gw] of the prediction's batch "
+                               "and channels")
+        gh, gw = int(gt.shape[2]), int(gt.shape[3])
+        if gt.stride()[1:] != (gh * gw, gw, 1):
+            gt = gt.contiguous()
+        resize = (gh, gw) != (H * r, W * r)
+        pred = torch.empty((B, Cc, H * r, W * r), device=xo.device, dtype=torch.float32)
+        ws = torch.empty(2048, device=xo.device, dtype=torch.float32)
+        loss = torch.empty((), device=xo.device, dtype=torch.float32)
+        # forward() of a Function runs with grad mode off, so whether a backward can follow is what needs_input_grad says
+        d = torch.empty((B, Cc, gh, gw), device=xo.device, dtype=torch.float32) if resize and ctx.needs_input_grad[0] else None
+        sb, sc, sy, sx = base.stride()
+        lib.call(loss_lib._head_loss_fwd, "bmc_head_loss_fwd", xo.data_ptr(), B, Cc, H, W, r, base.data_ptr(), sb, sc, sy, sx,
+                 gt.data_ptr(), gt.stride(0), gh, gw, pred.data_ptr(), d.data_ptr() if d is not None else None, ws.data_ptr(),
+                 loss.data_ptr(), kind, param, _stream())
+        ctx.r, ctx.kind, ctx.param = r, kind, param
+        ctx.dims = (B, Cc, H, W, gh, gw)
+        ctx.resize = resize
+        if resize:
+            if d is not None:
+                ctx.save_for_backward(d)
+        else:
+            ctx.save_for_backward(pred, gt)
+        return pred, loss
+
+    @staticmethod
+    def backward(ctx, dpred, dloss):
+        B, Cc, H, W, gh, gw = ctx.dims
+        r = ctx.r
+        if ctx.resize:
+            (d,), pred, gt = ctx.saved_tensors, None, None
+        else:
+            d, (pred, gt) = None, ctx.saved_tensors
+        if dpred is not None:
+            dpred = dpred.contiguous()
+        if dloss is not None:
+            dloss = dloss.contiguous()
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        dev = d.device if ctx.resize else pred.device
+        dlr = torch.empty((B, H, W, Cc * r * r), device=dev, dtype=torch.float32)
+        lib.call(loss_lib._head_loss_bwd, "bmc_head_loss_bwd", ptr(dpred), ptr(d), ptr(pred), ptr(gt),
+                 gt.stride(0) if gt is not None else 0, ptr(dloss), B, Cc, H, W, r, gh, gw, ctx.kind, ctx.param, dlr.data_ptr(),
+                 _stream())
+        return dlr, None, None, None, None, None
+
+
+def head_loss(xo, base, gt, r, loss=None):
+    """What the models' forward_loss calls: xo NHWC [B,H,W,C r r], base [B,C,H,W] (any strides), gt [B,C,gh,gw] of any size
+    (a batch stride is allowed) -> (pred [B,C,rH,rW], loss).  loss None is nn.MSELoss: head_mse for a ground truth of the
+    prediction's size, head_resize_mse otherwise.  loss an instance of bmc_hip.losses.L1 / Huber / Charbonnier: the same head
+    with that loss, at either size (HeadLossFn); anything else is refused -- a plain callable belongs to the unfused chain."""
+    if loss is None:
+        if tuple(gt.shape[-2:]) == (xo.shape[1] * r, xo.shape[2] * r):
+            return head_mse(xo, base, gt, r)
+        return head_resize_mse(xo, base, gt, r)
+    from . import losses
+    if not losses.is_fusable(loss):
+        raise TypeError("head_loss: %r is not a bmc_hip.losses object; the fused head evaluates L1, Huber and Charbonnier only"
+                        % (loss,))
+    return HeadLossFn.apply(xo, base, gt, r, int(loss.kind), float(loss.param))
 
 
 def pixel_unshuffle_nhwc(hr, r, split=1):

@@ -14,6 +14,7 @@
 #include <string>
 #include <type_traits>
 #include "bmc_hip.h"
+#include "bmc_hip_losses.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -70,6 +71,11 @@
     X(BMC_SEQ_MAX_ITEMS) X(BMC_SLOT_EMIT_MAX_PARTS) X(BMC_EVENT_T0) X(BMC_EVENT_T1) X(BMC_SLOT_EMIT_TIMED_MAX_COUNT) \
     X(BMC_SLOT_EMIT_TIMED_BLOCK) X(BMC_SLOT_EMIT_TIMED_MAX_WINDOW) X(BMC_SLOT_RENDER_MAX_PIXELS) X(BMC_SLOT_RENDER_MAX_PARTS) \
     X(BMC_SLOT_VOXEL_MAX_BINS) X(BMC_ADAM_CHUNK)
+
+/* include/bmc_hip_losses.h, the companion header of the robust-loss head: its own lists and its own text, bmc_losses_abi()
+ * (bmc_hip/loss_lib.py binds from it; tests/test_head_loss_cpu.py compares the lists with that header's text). */
+#define BMC_LOSSES_ABI_FUNCTIONS(X) X(bmc_head_loss_fwd) X(bmc_head_loss_bwd) X(bmc_losses_abi)
+#define BMC_LOSSES_ABI_CONSTANTS(X) X(BMC_LOSS_L1) X(BMC_LOSS_HUBER) X(BMC_LOSS_CHARBONNIER)
 
 namespace {
 
@@ -145,7 +151,19 @@ std::string abi_text() {
     return out;
 }
 
+std::string losses_abi_text() {
+    std::string out;
+    BMC_LOSSES_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
+    BMC_LOSSES_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
+    return out;
+}
+
 }  // namespace
+
+extern "C" const char* bmc_losses_abi(void) {
+    static const std::string text = losses_abi_text();
+    return text.c_str();
+}
 
 extern "C" const char* bmc_abi(void) {
     static const std::string text = abi_text();

@@ -216,15 +216,17 @@ class BMCNet(nn.Module):
         self.down = PixelUnShuffle(scale)
         self.repeat = repeat
 
-    def forward_loss(self, x, x_h, x_h_p, x_h_n, x_o, init, gt):
+    def forward_loss(self, x, x_h, x_h_p, x_h_n, x_o, init, gt, loss=None):
         """forward() + nn.MSELoss()(prediction, gt) with the loss computed by the head kernel (one pass over the HR
         tensor forward, the loss gradient folded into the head's backward): -> (x_h, x_h_p, x_h_n, prediction, mse).
         gt [B,2,gh,gw] may have any size: the prediction's size takes ops.head_mse; another size is the bicubic branch of
         train.py:227-231 and takes ops.head_resize_mse (the loss is against the resized prediction, the prediction
-        returned -- the one that recurs -- is the unresized one, the same bits either way)."""
-        return self.forward(x, x_h, x_h_p, x_h_n, x_o, init, _gt=gt)
+        returned -- the one that recurs -- is the unresized one, the same bits either way).
+        loss: None = nn.MSELoss as above; a bmc_hip.losses object (L1, Huber, Charbonnier) = that loss in the same pass
+        (ops.head_loss -> bmc_head_loss_fwd / _bwd), at either ground-truth size, the same prediction bits."""
+        return self.forward(x, x_h, x_h_p, x_h_n, x_o, init, _gt=gt, _loss=loss)
 
-    def forward(self, x, x_h, x_h_p, x_h_n, x_o, init, _gt=None):
+    def forward(self, x, x_h, x_h_p, x_h_n, x_o, init, _gt=None, _loss=None):
         """x [B,2,T>=2,H,W]; x_h/x_h_p/x_h_n [B,n_c,H,W]; x_o [B,2*s*s,H,W] if init else the previous HR
         prediction [B,2,sH,sW]; returns (x_h, x_h_p, x_h_n, prediction [B,2,sH,sW])."""
         B = x.shape[0]
@@ -241,7 +243,7 @@ class BMCNet(nn.Module):
         h3 = ops.stack_states([x_h, x_h_p, x_h_n])
         n_h, n_hp, n_hn, o = self.neuro.forward_nhwc(xin12, h3, o12, zero_state=bool(init))
         if _gt is not None:
-            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale)
+            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale, _loss)
             return to_nchw(n_h), to_nchw(n_hp), to_nchw(n_hn), pred, mse
         pred = ops.head(o, x[:, :, 1], self.scale)
         return to_nchw(n_h), to_nchw(n_hp), to_nchw(n_hn), pred

@@ -99,13 +99,14 @@ class BMCNet_plain(nn.Module):
         self.down = PixelUnShuffle(scale)
         self.repeat = repeat
 
-    def forward_loss(self, x, x_h, x_o, init, gt):
+    def forward_loss(self, x, x_h, x_o, init, gt, loss=None):
         """forward() + nn.MSELoss()(prediction, gt) computed by the head kernel -> (x_h, prediction, mse).  gt of the
         prediction's size: ops.head_mse; of another size (train.py:227-231): ops.head_resize_mse, the loss against the
-        bicubic-resized prediction while the unresized one is returned."""
-        return self.forward(x, x_h, x_o, init, _gt=gt)
+        bicubic-resized prediction while the unresized one is returned.  loss: None = nn.MSELoss; a bmc_hip.losses object
+        (L1, Huber, Charbonnier) = that loss in the same pass (ops.head_loss), at either size."""
+        return self.forward(x, x_h, x_o, init, _gt=gt, _loss=loss)
 
-    def forward(self, x, x_h, x_o, init, _gt=None):
+    def forward(self, x, x_h, x_o, init, _gt=None, _loss=None):
         s2 = self.scale ** 2
         xin12 = ops.pack_inputs(x, self.repeat)
         if init:
@@ -116,6 +117,6 @@ class BMCNet_plain(nn.Module):
         o12 = self.neuro.pad_o(o12)
         n_h, o = self.neuro.forward_nhwc(xin12, to_nhwc(x_h), o12, zero_state=bool(init))
         if _gt is not None:
-            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale)
+            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale, _loss)
             return to_nchw(n_h), pred, mse
         return to_nchw(n_h), ops.head(o, x[:, :, 1], self.scale)

@@ -1,12 +1,13 @@
 """One BPTT training step with the semantics of the reference's hot loop (train.py:202-237):
 zero_grad; for each sliding window: forward with the recurrent state carried WITHOUT detach, MSE against the HR
 count image of the window's second frame, losses summed; one backward over all windows; one optimizer step.
+Other losses than the reference's MSE: a bmc_hip.losses object (L1, Huber, Charbonnier) as loss_fn / loss keeps the fused head.
 
 Plus the synthetic NFS-shaped event generator used by bench.py / tests."""
 import torch
 import torch.nn.functional as F
 
-from bmc_hip import ops
+from bmc_hip import losses, ops
 
 
 def synthetic_events(B, seql, H, W, scale, n_lr, device, seed=3407):
@@ -53,7 +54,11 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
     forward inside backward (activation checkpointing per window): peak memory drops from
     windows x (one window's activations) to one window's activations, at the price of one extra forward per
     window.  Needed for long sequences / big batches (BASELINE configs[4]: T=16, 8 sequences per GPU); results
-    are bit-identical (same kernels, same order)."""
+    are bit-identical (same kernels, same order).
+
+    loss_fn: F.mse_loss (the reference's nn.MSELoss) and INSTANCES of bmc_hip.losses.L1 / Huber / Charbonnier are computed by
+    the head kernel (model.forward_loss); every other callable -- F.l1_loss, a lambda around one of those objects -- gets the
+    unfused chain: model(), ops.bicubic_resize where the sizes differ, loss_fn and its autograd."""
     from torch.utils.checkpoint import checkpoint
     B, L, _, H, W = inp_cnt.shape
     dev = inp_cnt.device
@@ -65,19 +70,22 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
         x = inp_cnt[:, i:i + seqn].transpose(1, 2)          # [B,2(pol),seqn,H,W]   (train.py:211)
         gt = gt_cnt[:, i + 1]                                # (train.py:213)
         # nn.MSELoss: head + loss in one kernel pass (models.*.forward_loss), whatever the ground truth's size -- another size
-        # than the prediction's is the bicubic branch of train.py:227-231, resized inside that pass.  Any other loss_fn object
-        # (a wrapper around F.mse_loss included) selects the unfused chain below.
-        fused = loss_fn is F.mse_loss and hasattr(model, "forward_loss")
+        # than the prediction's is the bicubic branch of train.py:227-231, resized inside that pass.  A bmc_hip.losses object:
+        # the same pass with its rho (forward_loss(..., loss=loss_fn)).  Any other loss_fn object (a wrapper around F.mse_loss
+        # or around a losses object included) selects the unfused chain below.
+        robust = losses.is_fusable(loss_fn)
+        fused = (loss_fn is F.mse_loss or robust) and hasattr(model, "forward_loss")
         fn = model.forward_loss if fused else model
         extra = (gt,) if fused else ()
+        kw = {"loss": loss_fn} if fused and robust else {}
         if init:
             state = (z(n_c), z(2 * scale * scale)) if plain else (z(n_c), z(n_c), z(n_c), z(2 * scale * scale))
-            out = fn(x, *state, True, *extra)
+            out = fn(x, *state, True, *extra, **kw)
             init = False
         elif recompute:
-            out = checkpoint(fn, x, *state, False, *extra, use_reentrant=False)
+            out = checkpoint(fn, x, *state, False, *extra, use_reentrant=False, **kw)
         else:
-            out = fn(x, *state, False, *extra)
+            out = fn(x, *state, False, *extra, **kw)
         if fused:
             state, mse = tuple(out[:-1]), out[-1]
         else:
@@ -91,14 +99,19 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
     return loss.detach(), mse.detach()
 
 
-def valid_step(model, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False):
+def valid_step(model, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False, loss=None):
     """The body of the reference's _valid loop (train.py:479-509) for one batch: model.eval() under torch.no_grad(), the
     windows as in bptt_step with the state carried, the window losses (nn.MSELoss, against the bicubic-resized prediction
     where the ground truth has another size, train.py:502-506) summed through forward_loss.  No backward, no optimizer;
-    nothing of the ground truth's size is allocated.  Returns (loss, last mse); the model's training mode is restored."""
+    nothing of the ground truth's size is allocated.  loss: None = nn.MSELoss; a bmc_hip.losses object (L1, Huber, Charbonnier)
+    = that loss through the same fused head; any other callable = the unfused chain (model(), ops.bicubic_resize where the
+    sizes differ, the callable).  Returns (loss, last window's loss); the model's training mode is restored."""
     B, L, _, H, W = inp_cnt.shape
     dev = inp_cnt.device
     z = lambda c: torch.zeros(B, c, H, W, device=dev)
+    loss_fn = None if loss is F.mse_loss else loss
+    fused = loss_fn is None or losses.is_fusable(loss_fn)
+    kw = {} if loss_fn is None else {"loss": loss_fn}
     was_training = model.training
     model.eval()
     try:
@@ -107,8 +120,13 @@ def valid_step(model, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False):
             state = (z(n_c), z(2 * scale * scale)) if plain else (z(n_c), z(n_c), z(n_c), z(2 * scale * scale))
             for i in range(L - seqn + 1):
                 x = inp_cnt[:, i:i + seqn].transpose(1, 2)
-                out = model.forward_loss(x, *state, i == 0, gt_cnt[:, i + 1])
-                state, mse = tuple(out[:-1]), out[-1]
+                gt = gt_cnt[:, i + 1]
+                if fused:
+                    out = model.forward_loss(x, *state, i == 0, gt, **kw)
+                    state, mse = tuple(out[:-1]), out[-1]
+                else:
+                    state = tuple(model(x, *state, i == 0))
+                    mse = loss_fn(ops.bicubic_resize(state[-1], gt.shape[-2:]), gt)
                 loss = loss + mse
     finally:
         model.train(was_training)

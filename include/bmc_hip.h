@@ -493,6 +493,8 @@ int bmc_head_resize_mse_fwd(const float* xo, int B, int C, int H, int W, int r, 
 int bmc_head_resize_mse_bwd(const float* dpred, const float* diff, const float* gloss, int B, int C, int H, int W, int r,
                             int gh, int gw, float* dlr, bmc_stream_t s);
 
+/* The same head with a robust loss (L1, Huber, Charbonnier) in the squared one's place: include/bmc_hip_losses.h. */
+
 /* ---- multi-stream inference: recording slots (bmcnet-esr_amd/infer.py::MultiStreamSR) ------------------------------
  * S <= BMC_MAX_SLOTS independent recordings run through one batched forward pass, recording r in slot s of the batch.  The
  * reference runs one recording at a time at batch 1 (infer_BMCNet.py:248-295 around the loop body :44-86).  Each call below is

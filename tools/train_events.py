@@ -14,6 +14,10 @@ python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x8
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
                              [--gt-size HxW] [--valid-every N] [--crop HxW] [--transpose [P]]
+                             [--loss mse|l1|huber:DELTA|charbonnier:EPS]
+--loss: the training (and validation) loss, default mse (nn.MSELoss, the reference's).  l1, huber:DELTA (default 1) and
+charbonnier:EPS (default 1e-3) are bmc_hip.losses objects: the same fused head + loss launches with another pointwise function,
+at either ground-truth size.
 --crop HxW: train on HxW LR patches (and scale x that HR patches) cut in the encoder, one random origin per sequence
 (EventTrainSet(crop=...), ONE bmc_seq_encode_crop launch per batch).  --size and --gt-size then take comma-separated lists the
 synthetic recordings cycle through (--size 180x240,260x346), a set of mixed sensors; recordings given as files may differ in size
@@ -42,6 +46,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
 import numpy as np
 import torch
 
+from bmc_hip import losses
 from bmc_hip.encodings import event_window_indices
 from event_dataset import EventTrainSet
 from models.BMCNet import BMCNet
@@ -102,7 +107,12 @@ def main():
     ap.add_argument("--crop", default=None, help="HxW of the LR patches to train on; --size / --gt-size may then be lists")
     ap.add_argument("--transpose", type=float, nargs="?", const=0.5, default=None, metavar="P",
                     help="with --crop: transpose a sample's frames with probability P (default 0.5)")
+    ap.add_argument("--loss", default="mse", help="mse | l1 | huber:DELTA | charbonnier:EPS")
     a = ap.parse_args()
+    try:
+        loss_obj = losses.parse(a.loss)                       # None: nn.MSELoss
+    except ValueError as e:
+        ap.error("--loss: %s" % e)
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
     if a.transpose is not None and not a.crop:
@@ -138,7 +148,7 @@ def main():
         add(ts, r, dev, a.window, a.sliding, a.scale)
     print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) + (", %dx%d patches" % crop if crop else "") +
           (", transposed with probability %g" % a.transpose if a.transpose is not None else "") +
-          (", %d held-out sequences" % len(vs) if vs is not None else ""))
+          (", %d held-out sequences" % len(vs) if vs is not None else "") + (", loss %r" % loss_obj if loss_obj is not None else ""))
     random.seed(a.seed)
     torch.manual_seed(a.seed)
     m = BMCNet(a.scale, a.n_c, a.n_b).to(dev)
@@ -163,7 +173,7 @@ def main():
             t0.record()
             inp, gt = ts.batch(idx)
             t1.record()
-            loss, mse = bptt_step(m, opt, inp, gt, a.n_c, a.scale)
+            loss, mse = bptt_step(m, opt, inp, gt, a.n_c, a.scale, **({"loss_fn": loss_obj} if loss_obj is not None else {}))
             loss = float(loss)
             rows.append(dict(step=step, epoch=epoch, sequences=idx, loss=loss, encode_ms=round(t0.elapsed_time(t1), 4)))
             if a.transpose is not None:
@@ -171,7 +181,7 @@ def main():
             print("step %d  loss %.6f  encode %.3f ms  sequences %s" % (step, loss, rows[-1]["encode_ms"], idx))
             step += 1
             if vs is not None and step % a.valid_every == 0:
-                vl = [float(valid_step(m, *vs.batch(vidx), a.n_c, a.scale)[0]) for vidx in vs.batches(a.batch, shuffle=False)]
+                vl = [float(valid_step(m, *vs.batch(vidx), a.n_c, a.scale, loss=loss_obj)[0]) for vidx in vs.batches(a.batch, shuffle=False)]
                 rows[-1]["valid_loss"] = sum(vl) / len(vl)
                 print("step %d  valid_loss %.6f  (%d batches)" % (step - 1, rows[-1]["valid_loss"], len(vl)))
             if step == 1:
