@@ -332,6 +332,49 @@ def counts_to_voxel(pred, bins, max_count=255):
     return out
 
 
+def image_quality(img, ref, data_range="gt", raw=False):
+    """PSNR and SSIM of count images: img, ref [N,2,h,w] (fp32, on the GPU; h, w >= 7) -> dict(psnr=[N], ssim=[N]) numpy float64,
+    image n what the reference's psnr_loss / ssim_loss (loss/restore.py:44-93: scikit-image's peak_signal_noise_ratio and
+    structural_similarity per channel, the mean of the two) give for img[n] against the ground truth ref[n], in float64 on the
+    float32 inputs: SSIM with the uniform 7x7 window, K1 = 0.01, K2 = 0.03 and sample covariance over the (h - 6) x (w - 6)
+    window positions inside the image; data_range "gt": R_c = max(ref[n, c]) - min(ref[n]) (restore.py:85), or a positive
+    constant.  IEEE results stand: psnr +inf for an exact channel, -inf for R_c = 0 with an error; ssim nan for R_c = 0.
+    bmc_slot_quality on a temporary slot table (three launches, no atomics; include/bmc_hip_quality.h states the contract).
+    raw=True: the dict also carries raw = [N, 2 channels, 4] float64, the kernels' records {sse, gt_max, gt_min, ssim_sum}."""
+    from . import slots
+    for name, t in (("img", img), ("ref", ref)):
+        if not (torch.is_tensor(t) and t.dim() == 4 and t.shape[1] == 2 and t.dtype == torch.float32):
+            raise ValueError("image_quality: %s must be an fp32 [N,2,h,w] tensor" % name)
+    if img.shape != ref.shape:
+        raise ValueError("image_quality: img %s and ref %s differ in shape" % (tuple(img.shape), tuple(ref.shape)))
+    rng = slots.check_data_range("image_quality: ", data_range)
+    N, _, h, w = img.shape
+    if min(h, w) < slots.QUALITY_WIN or 2 * h * w >= 2 ** 30:
+        raise ValueError("image_quality: images of at least %d x %d and fewer than 2^29 pixels (got %d x %d)"
+                         % (slots.QUALITY_WIN, slots.QUALITY_WIN, h, w))
+    if not (img.is_cuda and ref.is_cuda and img.device == ref.device):
+        raise RuntimeError("image_quality: img and ref must live on the MI355X (no CPU fallback in this build)")
+    img, ref = img.contiguous(), ref.contiguous()
+    rec = torch.zeros(N, 2, slots.QUALITY_WORDS, dtype=torch.float64, device=img.device)
+    most, nparts = min(max(N, 1), slots.MAX_SLOTS), slots.metric_parts(h, w)
+    stats = torch.zeros(most * nparts * slots.QUALITY_STATS_WORDS, dtype=torch.float64, device=img.device)
+    tiles = torch.zeros(most * 4 * slots.quality_tiles(h, w), dtype=torch.float64, device=img.device)
+    tables = {}
+    for a in range(0, N, slots.MAX_SLOTS):
+        n = min(slots.MAX_SLOTS, N - a)
+        t = tables[n] = tables.get(n) or slots.SlotTable(n, img.device, quality=True)
+        e = t.host()
+        qe = t.quality_host()
+        for s in range(n):
+            e[s]["frames"], e[s]["gt"], e[s]["flags"] = ref[a + s].data_ptr(), ref[a + s].data_ptr(), slots.ACTIVE
+            qe[s]["dst"] = rec[a + s].data_ptr()
+        t.upload()
+        slots.quality(t, img[a:a + n], None, nparts, rng, stats, tiles)
+    rec = rec.cpu().numpy()
+    psnr, ssim = slots.quality_values(rec, data_range, (h, w))
+    return dict(psnr=psnr, ssim=ssim, raw=rec) if raw else dict(psnr=psnr, ssim=ssim)
+
+
 def counts_to_events(pred, max_count=255, times=None, spans=None):
     """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
     (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in

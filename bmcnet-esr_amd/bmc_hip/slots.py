@@ -38,11 +38,16 @@ of image; render() draws table k's images for all slots (one call = RENDER_KERNE
 Voxel grids (csrc/slot_voxel.hip; include/bmc_hip.h "voxel grids" states the contract): SlotTable(voxel=True) adds a table of
 bmc_slot_voxel_t entries (SLOT_VOXEL_DTYPE: where the slot's grid goes) behind the others; voxel() turns the predictions of every
 slot with a voxel entry into the temporal-bilinear voxel grid of its timed event stream, per pixel (one call = VOXEL_KERNELS
-launches, counted in VOXEL_LAUNCHES)."""
+launches, counted in VOXEL_LAUNCHES).
+
+PSNR and SSIM (csrc/slot_quality.hip; include/bmc_hip_quality.h states the contract): SlotTable(quality=True) adds a table of
+bmc_slot_quality_t entries (SLOT_QUALITY_DTYPE: where the slot's raw record goes) behind the others; quality() writes, for every
+slot with a quality entry, the record of the prediction and of the bicubic baseline against the slot's ground truth (one call =
+QUALITY_KERNELS launches, counted in QUALITY_LAUNCHES); quality_values() finishes records into PSNR and SSIM on the host."""
 import numpy as np
 import torch
 
-from . import lib
+from . import lib, quality_lib
 from .ops import _stream
 
 # the header's limits and table layouts (include/bmc_hip.h), as the library states them
@@ -87,13 +92,19 @@ SLOT_VOXEL_DTYPE = lib.dtype("bmc_slot_voxel_t")
 VOXEL_LAUNCHES = 0
 VOXEL_KERNELS = 2                  # launches of one bmc_slot_voxel call: reduce, voxel
 MAX_VOXEL_BINS = lib.const("BMC_SLOT_VOXEL_MAX_BINS")
+SLOT_QUALITY_DTYPE = quality_lib.dtype("bmc_slot_quality_t")
+QUALITY_LAUNCHES = 0
+QUALITY_KERNELS = 3                # launches of one bmc_slot_quality call: stats, ssim, finish
+QUALITY_WIN, QUALITY_WORDS = quality_lib.const("BMC_QUALITY_WIN"), quality_lib.const("BMC_QUALITY_WORDS")
+QUALITY_TILE_H, QUALITY_TILE_W = quality_lib.const("BMC_QUALITY_TILE_H"), quality_lib.const("BMC_QUALITY_TILE_W")
+QUALITY_STATS_WORDS = quality_lib.const("BMC_QUALITY_STATS_WORDS")
 
 
-def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False):
+def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False, quality=False):
     """The sections of a slot table of S slots -> ([(name, dtype, byte offset), ...] in their order in memory, total bytes):
     "slot" (bmc_slot_t) always, then "events", "emit" (bmc_slot_emit_timed_t entries with timed=True), "clock" (needs timed) and
-    "hot" (needs events), each S entries behind the one before, "render" (render tables of S entries each) and "voxel"
-    (voxel=True or False: S bmc_slot_voxel_t entries)."""
+    "hot" (needs events), each S entries behind the one before, "render" (render tables of S entries each), "voxel"
+    (voxel=True or False: S bmc_slot_voxel_t entries) and "quality" (quality=True or False: S bmc_slot_quality_t entries)."""
     if timed and not emit:
         raise ValueError("slots: timed=True needs emit=True")
     if clock and not timed:
@@ -104,11 +115,14 @@ def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=Fals
         raise ValueError("slots: render must be a number of tables, 0 .. %d (got %r)" % (MAX_RENDER_TABLES, render))
     if not isinstance(voxel, (bool, np.bool_)):
         raise ValueError("slots: voxel must be True or False (got %r)" % (voxel,))
+    if not isinstance(quality, (bool, np.bool_)):
+        raise ValueError("slots: quality must be True or False (got %r)" % (quality,))
     sections, nbytes = [], 0
     for name, dtype, count in (("slot", SLOT_DTYPE, 1), ("events", SLOT_EVENTS_DTYPE, int(bool(events))),
                                ("emit", SLOT_EMIT_TIMED_DTYPE if timed else SLOT_EMIT_DTYPE, int(bool(emit))),
                                ("clock", SLOT_CLOCK_DTYPE, int(bool(clock))), ("hot", SLOT_HOT_DTYPE, int(bool(hot))),
-                               ("render", SLOT_RENDER_DTYPE, render), ("voxel", SLOT_VOXEL_DTYPE, int(voxel))):
+                               ("render", SLOT_RENDER_DTYPE, render), ("voxel", SLOT_VOXEL_DTYPE, int(voxel)),
+                               ("quality", SLOT_QUALITY_DTYPE, int(quality))):
         if count:
             sections.append((name, dtype, nbytes))
             nbytes += count * S * dtype.itemsize
@@ -122,18 +136,19 @@ class SlotTable:
     The other sections of table_layout() share the tensor and the copy: `events_host()` / `events_ptr()` (events=True),
     `emit_host()` / `emit_ptr()` (emit=True; timed=True: bmc_slot_emit_timed_t entries), `clock_host()` / `clock_ptr()`
     (clock=True, needs timed), `hot_host()` / `hot_ptr()` (hot=True, needs events), `render_host()` [K,S] / `render_ptr(k)`
-    (render=K tables), `voxel_host()` / `voxel_ptr()` (voxel=True).  The *_host() views are those of the window being filled, after host(), which cleared them."""
+    (render=K tables), `voxel_host()` / `voxel_ptr()` (voxel=True), `quality_host()` / `quality_ptr()` (quality=True).  The *_host() views are those of the window being filled, after host(), which cleared them."""
 
     RING = 4
 
-    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False):
+    def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False,
+                 quality=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
         self.events, self.emit, self.timed, self.clock, self.hot = bool(events), bool(emit), bool(timed), bool(clock), bool(hot)
         self.render = render
-        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render, voxel)
-        self.voxel = bool(voxel)
+        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render, voxel, quality)
+        self.voxel, self.quality = bool(voxel), bool(quality)
         self._at = {name: (dtype, off) for name, dtype, off in sections}
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
@@ -173,6 +188,9 @@ class SlotTable:
     def voxel_host(self):
         return self._host("voxel")
 
+    def quality_host(self):
+        return self._host("quality")
+
     def upload(self):
         k = self._k
         self.dev.copy_(self._pinned[k], non_blocking=True)
@@ -203,6 +221,9 @@ class SlotTable:
 
     def voxel_ptr(self):
         return self._ptr("voxel")
+
+    def quality_ptr(self):
+        return self._ptr("quality")
 
 
 def _check(cond, what):
@@ -494,6 +515,69 @@ def voxel(table, pred, max_count, bins, nparts, parts):
     lib.call(lib._slot_voxel, "bmc_slot_voxel", table.ptr(), table.voxel_ptr(), S, pred.data_ptr(), sH, sW, max_count, int(bins),
              nparts, parts.data_ptr(), _stream())
     VOXEL_LAUNCHES += 1
+
+
+def quality_tiles(gh, gw):
+    """Workgroups per (slot, image, channel) of bmc_slot_quality's ssim launch for a gh x gw ground truth: the tiles of
+    QUALITY_TILE_H x QUALITY_TILE_W window positions that cover its (gh - 6) x (gw - 6) positions."""
+    _check(min(gh, gw) >= QUALITY_WIN, "PSNR / SSIM need images of at least %d x %d (got %d x %d)" % (QUALITY_WIN, QUALITY_WIN, gh, gw))
+    return -(-(gh - QUALITY_WIN + 1) // QUALITY_TILE_H) * -(-(gw - QUALITY_WIN + 1) // QUALITY_TILE_W)
+
+
+def check_data_range(who, data_range):
+    """data_range ("gt", or a finite positive number) -> the constant bmc_slot_quality takes (0.0 for "gt"); ValueError otherwise."""
+    if isinstance(data_range, str) and data_range == "gt":
+        return 0.0
+    if isinstance(data_range, (bool, str)) or not isinstance(data_range, (int, float, np.integer, np.floating)) \
+            or not np.isfinite(data_range) or not data_range > 0:
+        raise ValueError(who + "data_range must be 'gt' or a finite positive number (got %r)" % (data_range,))
+    return float(data_range)
+
+
+def quality(table, esr, bicubic, nparts, data_range, stats, tiles):
+    """Every active slot with a ground truth whose quality entry has a dst: dst (float64 [2,2,QUALITY_WORDS]) <- the raw records
+    {sse, gt_max, gt_min, ssim_sum} per channel of the images esr[s] and bicubic[s] (fp32 [S,2,gh,gw], at the ground truth's
+    size; bicubic None: the first image only) against the slot entry's gt -- include/bmc_hip_quality.h states the contract.
+    data_range: 0.0 (from the ground truth) or the constant.  Three launches for all slots (bmc_slot_quality), no atomics,
+    deterministic; other slots are not touched.  stats / tiles: float64 scratch of at least S * nparts * QUALITY_STATS_WORDS and
+    S * 4 * quality_tiles(gh, gw) values."""
+    global QUALITY_LAUNCHES
+    _check(table.quality, "the slot table has no quality entries (SlotTable(quality=True))")
+    _check(torch.is_tensor(esr) and esr.dim() == 4 and esr.shape[1] == 2 and esr.is_cuda and esr.is_contiguous()
+           and esr.dtype == torch.float32 and esr.shape[0] == table.S, "esr must be a contiguous fp32 GPU tensor [S,2,gh,gw]")
+    S, _, gh, gw = esr.shape
+    _check(bicubic is None or (torch.is_tensor(bicubic) and bicubic.is_cuda and bicubic.is_contiguous()
+                               and bicubic.dtype == torch.float32 and bicubic.shape == esr.shape),
+           "bicubic must be None or a contiguous fp32 GPU tensor of esr's shape")
+    _check(not isinstance(nparts, bool) and isinstance(nparts, int) and 1 <= nparts <= MAX_PARTS, "1 <= nparts <= %d" % MAX_PARTS)
+    _check(2 * gh * gw < 2 ** 30, "images of fewer than 2^29 pixels")
+    ntiles = quality_tiles(gh, gw)
+    for name, t, need in (("stats", stats, S * nparts * QUALITY_STATS_WORDS), ("tiles", tiles, S * 4 * ntiles)):
+        _check(torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float64 and t.is_contiguous() and t.numel() >= need,
+               "%s must be a contiguous float64 GPU tensor of at least %d values" % (name, need))
+    lib.call(quality_lib._slot_quality, "bmc_slot_quality", table.ptr(), table.quality_ptr(), S, esr.data_ptr(),
+             None if bicubic is None else bicubic.data_ptr(), gh, gw, nparts, float(data_range), stats.data_ptr(),
+             tiles.data_ptr(), _stream())
+    QUALITY_LAUNCHES += 1
+
+
+def quality_values(raw, data_range, size):
+    """Raw records [..., 2 channels, QUALITY_WORDS] = {sse, gt_max, gt_min, ssim_sum} of bmc_slot_quality for images of
+    size = (gh, gw) (float64; numpy, or a tensor on any device) -> (psnr [...], ssim [...]) numpy float64, the mean of the two
+    channels' values: psnr_c = 10 log10(R_c^2 / (sse / (gh gw))), ssim_c = ssim_sum / ((gh - 6)(gw - 6)), R_c = gt_max - gt_min
+    for data_range "gt", else the constant.  IEEE results stand (numpy float64, errstate ignore): +inf for an exact channel,
+    -inf for R_c = 0 with an error, nan for 0 / 0; ssim is nan where R_c = 0 (the kernel wrote a nan sum)."""
+    rng = check_data_range("slots.quality_values: ", data_range)
+    gh, gw = (int(v) for v in size)
+    _check(min(gh, gw) >= QUALITY_WIN, "PSNR / SSIM need images of at least %d x %d (got %d x %d)" % (QUALITY_WIN, QUALITY_WIN, gh, gw))
+    raw = np.asarray(raw.cpu() if torch.is_tensor(raw) else raw, dtype=np.float64)
+    _check(raw.ndim >= 2 and raw.shape[-2:] == (2, QUALITY_WORDS), "raw records are [..., 2, %d] (got %s)" % (QUALITY_WORDS, raw.shape))
+    sse, gt_max, gt_min, ssim_sum = (raw[..., k] for k in range(QUALITY_WORDS))
+    R = gt_max - gt_min if rng == 0.0 else np.full_like(sse, rng)
+    with np.errstate(all="ignore"):
+        psnr = 10.0 * np.log10(R * R / (sse / np.float64(gh * gw)))
+        ssim = ssim_sum / np.float64((gh - QUALITY_WIN + 1) * (gw - QUALITY_WIN + 1))
+        return (psnr[..., 0] + psnr[..., 1]) / 2.0, (ssim[..., 0] + ssim[..., 1]) / 2.0
 
 
 def emit_rank_table_np():

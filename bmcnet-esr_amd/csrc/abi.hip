@@ -15,6 +15,7 @@
 #include <type_traits>
 #include "bmc_hip.h"
 #include "bmc_hip_losses.h"
+#include "bmc_hip_quality.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -77,6 +78,13 @@
 #define BMC_LOSSES_ABI_FUNCTIONS(X) X(bmc_head_loss_fwd) X(bmc_head_loss_bwd) X(bmc_losses_abi)
 #define BMC_LOSSES_ABI_CONSTANTS(X) X(BMC_LOSS_L1) X(BMC_LOSS_HUBER) X(BMC_LOSS_CHARBONNIER)
 
+/* include/bmc_hip_quality.h, the companion header of the slots' PSNR / SSIM: likewise, bmc_quality_abi() (bmc_hip/quality_lib.py
+ * binds from it; tests/test_quality_cpu.py compares the lists with that header's text). */
+#define BMC_QUALITY_ABI_FUNCTIONS(X) X(bmc_slot_quality) X(bmc_quality_abi)
+#define BMC_QUALITY_ABI_STRUCTS(X) X(bmc_slot_quality_t, F(dst))
+#define BMC_QUALITY_ABI_CONSTANTS(X) \
+    X(BMC_QUALITY_WIN) X(BMC_QUALITY_WORDS) X(BMC_QUALITY_TILE_H) X(BMC_QUALITY_TILE_W) X(BMC_QUALITY_STATS_WORDS)
+
 namespace {
 
 struct field {
@@ -115,6 +123,7 @@ template <class T> constexpr bool tiles() {
     template <> struct layout<S> { using T = S; static constexpr const char* name = #S; static constexpr field fields[] = {__VA_ARGS__}; }; \
     static_assert(tiles<S>(), #S ": the field list above does not tile the struct (a field is missing or out of order)");
 BMC_ABI_STRUCTS(BMC_ABI_LAYOUT)
+BMC_QUALITY_ABI_STRUCTS(BMC_ABI_LAYOUT)
 
 template <class Fn> struct signature;
 template <class R, class... A> struct signature<R (*)(A...)> {
@@ -158,7 +167,20 @@ std::string losses_abi_text() {
     return out;
 }
 
+std::string quality_abi_text() {
+    std::string out;
+    BMC_QUALITY_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
+    BMC_QUALITY_ABI_STRUCTS(BMC_ABI_PUT_STRUCT)
+    BMC_QUALITY_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
+    return out;
+}
+
 }  // namespace
+
+extern "C" const char* bmc_quality_abi(void) {
+    static const std::string text = quality_abi_text();
+    return text.c_str();
+}
 
 extern "C" const char* bmc_losses_abi(void) {
     static const std::string text = losses_abi_text();

@@ -17,7 +17,7 @@ import torch
 from bmc_hip import slots
 from bmc_hip.encodings import event_block_spans
 from bmc_hip.slots import check_group_size, check_hot_filter
-from infer_parts import EventStream, HotFilter, Input, KeptPredictions, Metrics, Pictures, VoxelGrids
+from infer_parts import EventStream, HotFilter, Input, KeptPredictions, Metrics, Pictures, Quality, VoxelGrids
 
 EventRecording = collections.namedtuple("EventRecording", "lr gt lr_index gt_index lr_size gt_size", defaults=(None,) * 5)
 EventRecording.__doc__ = """An event-backed recording for MultiStreamSR.open_events / evaluate_recordings: lr, gt = (xs, ys, ps)
@@ -257,6 +257,7 @@ class MultiStreamSR:
       hot_filter=dict(...)        HotFilter        the reference's hot-pixel filter for event-backed recordings
       open / open_events          Input            frames, or raw event columns encoded window by window
       a ground truth              Metrics          esr_mse / bicubic_mse per window
+      quality=True | dict(...)    Quality          esr_psnr / esr_ssim / bicubic_psnr / bicubic_ssim per window (needs a ground truth)
       keep_predictions            KeptPredictions  predictions [n_windows,2,sH,sW]
       emit_events, event_times    EventStream      the super-resolved event stream: plain, timed, or on the sensor's clock
       render=(kinds...)           Pictures         the reference's event-count images
@@ -281,10 +282,11 @@ class MultiStreamSR:
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
                  seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None, voxel_bins=None,
-                 self_ensemble=None):
+                 self_ensemble=None, quality=None):
         self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)  # (the argument `slots` hides the module here)
         self.self_ensemble = check_group_size("MultiStreamSR: ", self_ensemble, int(slots))
         self.render = self.check_render("MultiStreamSR: ", render)
+        self.quality = Quality.check("MultiStreamSR: ", quality)          # None, "gt" or the constant data range
         if state_dtype not in (None, torch.float32, torch.bfloat16):
             raise ValueError("MultiStreamSR: state_dtype must be None / torch.float32 / torch.bfloat16 (got %r)" % (state_dtype,))
         if seqn < 2:
@@ -308,7 +310,8 @@ class MultiStreamSR:
         self._bufs = self._graph = self._stamp = None
         self._has_events = self._has_clock = False
         self._stream = EventStream()
-        on = ((HotFilter(), self.hot_filter is not None), (Input(), True), (Metrics(), True), (KeptPredictions(), keep_predictions),
+        on = ((HotFilter(), self.hot_filter is not None), (Input(), True), (Metrics(), True), (Quality(), self.quality is not None),
+              (KeptPredictions(), keep_predictions),
               (self._stream, True), (Pictures(), self.render), (VoxelGrids(), self.voxel_bins is not None))
         self.parts = [p for p, wanted in on if wanted]     # (a part keeps no reference to the session: no cycle)
 
@@ -342,6 +345,8 @@ class MultiStreamSR:
         gh, gw = (None, None) if gts is None else (gts.shape[2], gts.shape[3])
         if gt_size is not None and tuple(int(v) for v in gt_size) != (gh, gw):
             raise ValueError("MultiStreamSR.open: gt_size %s differs from the ground truth's %s" % (tuple(gt_size), (gh, gw)))
+        if self.quality is not None and gts is not None:
+            Quality.check_size("open", gh, gw)
         event_capacity, window_event_capacity = self._stream.room(
             self, "open", H, W, event_capacity, window_event_capacity, lambda: frames.sum(dtype=torch.float64).item(),
             lambda: frames.sum(dim=(1, 2, 3), dtype=torch.float64).max().item())
@@ -455,6 +460,8 @@ class MultiStreamSR:
         if min(H, W, gh or 1, gw or 1) < 1 or max(W, gw or 1) > self.MAX_WIDTH_EVENTS:
             raise ValueError(who + "sizes must be positive and at most %d wide (got %s, %s)"
                              % (self.MAX_WIDTH_EVENTS, (H, W), (gh, gw)))
+        if self.quality is not None and has_gt:
+            Quality.check_size("open_events", gh, gw)
         lengths = lr_index[:, 1] - lr_index[:, 0]
         event_capacity, window_event_capacity = self._stream.room(self, "open_events", H, W, event_capacity,
                                                                   window_event_capacity, lengths.sum, lengths.max)
@@ -483,7 +490,7 @@ class MultiStreamSR:
 
     def results(self, handle):
         """-> dict(time=[...] per window done so far, and what the session's parts add: esr_mse, bicubic_mse (a recording with
-        ground truth); hot_pixels, hot_mask (hot_filter, event-backed recordings); predictions; images (render); voxels; sr_events,
+        ground truth; with quality also esr_psnr, esr_ssim, bicubic_psnr, bicubic_ssim); hot_pixels, hot_mask (hot_filter, event-backed recordings); predictions; images (render); voxels; sr_events,
         sr_index, sr_ts (emit_events, event_times)).  Raises RuntimeError when the windows emitted more events than the recording's
         event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity needed)."""
         r = self._recs[handle]
@@ -531,7 +538,7 @@ class MultiStreamSR:
 
     def _window(self):
         """The input parts ([hot_update ->] [encode ->]) stage -> model -> commit, then the other parts in list order ([-> metrics]
-        [-> emit] [-> render] [-> voxel]): what a graph replay runs."""
+        [-> quality] [-> emit] [-> render] [-> voxel]): what a graph replay runs."""
         b = self._bufs
         for p in self.parts:
             if p.input:
@@ -569,8 +576,8 @@ class MultiStreamSR:
         """The table entries of the window `plan`, into the table's host copy."""
         t = self._bufs["table"]
         v = {"slot": t.host()}                             # host() first: it clears the copy the other views look into
-        for name in ("events", "emit", "clock", "hot", "render", "voxel"):
-            if getattr(t, name):
+        for name in ("events", "emit", "clock", "hot", "render", "voxel", "quality"):
+            if getattr(t, name, False):                    # (a table without the section: no views of it)
                 v[name] = getattr(t, name + "_host")()
         K = self.self_ensemble or 1                        # the plan is of groups of K slots: the parts fill the leader's entries
         for s, p in enumerate(SlotScheduler.expand(plan, K)):
@@ -622,7 +629,7 @@ class MultiStreamSR:
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
-                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None, self_ensemble=None):
+                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None, self_ensemble=None, quality=None):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
@@ -641,11 +648,15 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     hot_filter (the EventRecording items are filtered, frame pairs are not), render (a tuple of kinds from "lr", "bicubic", "esr",
     "gt"), voxel_bins=B (the result then carries voxels = {name: float32 [n_windows,B,sH,sW]}), self_ensemble=K (2, 4, 8; slots a
     multiple of K: every recording runs in K orientations and esr_mse, predictions, sr_events, the esr image and voxels are those
-    of the merged prediction): MultiStreamSR's options."""
+    of the merged prediction), quality=True | dict(data_range=) (results and mean then carry esr_psnr, esr_ssim, bicubic_psnr and
+    bicubic_ssim for the recordings with ground truth: the mean over the windows whose value is FINITE -- an exact window has an
+    infinite PSNR, an empty ground-truth channel no SSIM -- and, under the key + "_nonfinite", how many windows that left out;
+    mean[key] is the mean over the recordings with a finite value, mean[key + "_nonfinite"] the total of the counts):
+    MultiStreamSR's options."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
-                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, self_ensemble=self_ensemble)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, self_ensemble=self_ensemble, quality=quality)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
@@ -664,13 +675,26 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     wanted = (("predictions", keep_predictions), ("sr_events", emit_events), ("sr_ts", event_times is not None),
               ("images", ms.render), ("voxels", ms.voxel_bins is not None))
     extra = {k: {} for k, on in wanted if on}
+    if ms.quality is not None:
+        breakdown.update({k + tail: {} for k in Quality.KEYS for tail in ("", "_nonfinite")})
     for name, h in handles:
         r = ms.results(h)
+        for k in Quality.KEYS:
+            if k in r:                                     # the mean of the finite windows, and how many were not
+                finite = [v for v in r[k] if math.isfinite(v)]
+                breakdown[k][name] = float(statistics.mean(finite)) if finite else float("nan")
+                breakdown[k + "_nonfinite"][name] = len(r[k]) - len(finite)
         for k in ("esr_mse", "bicubic_mse", "time"):
             if k in r:
                 breakdown[k][name] = float(statistics.mean(r[k]))
         breakdown["params"][name] = params
         for k in extra:
             extra[k][name] = r[k] + (r["sr_index"],) if k == "sr_events" else r[k]
-    return {"results": breakdown, "mean": {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}, **extra}
+    mean = {k: float(statistics.mean(v.values())) for k, v in breakdown.items() if v}
+    for k in Quality.KEYS:
+        if breakdown.get(k):                               # recordings without a finite window are left out, the counts add up
+            finite = [v for v in breakdown[k].values() if math.isfinite(v)]
+            mean[k] = float(statistics.mean(finite)) if finite else float("nan")
+            mean[k + "_nonfinite"] = int(sum(breakdown[k + "_nonfinite"].values()))
+    return {"results": breakdown, "mean": mean, **extra}
 

@@ -12,7 +12,7 @@ session keeps its parts in the launch order of a window and loops over them:
   scratch()                  {key: (shape, dtype, fill, counted)}: the part's buffers in ms._bufs at the session's current sizes
                              (fill None: uninitialised); the session allocates from it, scratch_bytes() sums its counted entries
   fill(v, s, r, i, reset)    the part's table entries for slot s running window i of record r; v: the host views of the table's
-                             sections by name ("slot", "events", "emit", "clock", "hot", "render", "voxel")
+                             sections by name ("slot", "events", "emit", "clock", "hot", "render", "voxel", "quality")
   launch(b, pred)            the part's launches of a window on b = ms._bufs; input parts run before bmc_slot_stage (pred None),
                              the others after bmc_slot_commit with the window's prediction
   results(out, r, done, h)   the part's keys of results(h) after `done` windows, and its capacity errors"""
@@ -23,7 +23,7 @@ from bmc_hip import lib, slots
 from bmc_hip.encodings import check_spans
 from bmc_hip.ops import _stream
 
-F32, I32, U8 = torch.float32, torch.int32, torch.uint8
+F32, F64, I32, U8 = torch.float32, torch.float64, torch.int32, torch.uint8
 
 
 class Part:
@@ -158,6 +158,94 @@ class Metrics(Part):
         if "sse" in r:
             sse = slots.sum_parts(r["sse"][:done]) / (2 * ms._size[2] * ms._size[3])
             out.update(esr_mse=sse[:, 0].tolist(), bicubic_mse=sse[:, 1].tolist())
+
+
+class Quality(Part):
+    """quality=True or dict(data_range="gt" | R): esr_psnr, esr_ssim, bicubic_psnr, bicubic_ssim per window of a recording WITH
+    ground truth -- the other two columns of a super-resolution table, the reference's psnr_loss / ssim_loss (loss/restore.py:44-93:
+    scikit-image's peak_signal_noise_ratio and structural_similarity per channel on the CPU, after a .cpu().numpy() of every
+    prediction), computed on the GPU in float64 (bmc_slot_quality: three more launches per window for all slots, inside the captured
+    graph too; no atomics, no host sync; include/bmc_hip_quality.h states the contract).  Per channel c of the two-channel count
+    image, then the mean of the two: PSNR = 10 log10(R_c^2 / mse_c); SSIM with a uniform 7x7 window, K1 = 0.01, K2 = 0.03 and
+    sample covariance, averaged over the (gh - 6) x (gw - 6) window positions inside the image.  R_c = max(gt[c]) - min(gt), the
+    minimum over both channels (restore.py:85), or the constant R.  IEEE results stand: +inf PSNR for an exact channel, -inf for
+    R_c = 0 with an error; SSIM is nan for R_c = 0.  "esr" is the window's prediction (the MERGED one in a self-ensemble session,
+    as esr_mse), "bicubic" frame 1 of the window as the model saw it (after the hot-pixel filter where one applies); both are
+    resized to the ground truth's size with bmc_bicubic_resize_fwd where theirs differs -- the float32 values esr_mse and the
+    pictures use.  The error is subtracted in float64 here and in float32 in esr_mse, so esr_psnr is not a function of esr_mse
+    to the last bit.  A ground truth must be at least 7 x 7 (ValueError at open).  Resident: 128 bytes per window; session
+    scratch once a recording with ground truth has been opened: the bicubic baseline [S,2,gh,gw], the resized prediction (the
+    same again) where sizes differ, frame 1 [S,2,H,W], and the partial sums of the launches.  A recording without ground truth
+    carries none of the keys; bmc_slot_quality is launched only once a recording with ground truth has been opened."""
+    KEYS = ("esr_psnr", "esr_ssim", "bicubic_psnr", "bicubic_ssim")
+
+    @staticmethod
+    def check(who, quality):
+        """quality (None, True, or a dict with exactly the key data_range: "gt" or a finite positive number) -> None or the data
+        range ("gt" or a float); ValueError otherwise."""
+        if quality is None:
+            return None
+        if quality is True:
+            return "gt"
+        if not isinstance(quality, dict):
+            raise ValueError(who + "quality must be None, True or a dict with the key data_range (got %r)" % (quality,))
+        for k in quality:
+            if k != "data_range":
+                raise ValueError(who + "quality has an unknown key %r (the key is data_range)" % (k,))
+        if "data_range" not in quality:
+            raise ValueError(who + "quality lacks the key 'data_range'")
+        rng = slots.check_data_range(who + "quality: ", quality["data_range"])
+        return "gt" if rng == 0.0 else rng
+
+    @staticmethod
+    def check_size(who, gh, gw):
+        """The ground truth of a recording a session with quality takes: at least one window position."""
+        if min(gh, gw) < slots.QUALITY_WIN:
+            raise ValueError("MultiStreamSR.%s: quality needs a ground truth of at least %d x %d (got %d x %d)"
+                             % (who, slots.QUALITY_WIN, slots.QUALITY_WIN, gh, gw))
+
+    def table(self, ms):
+        return {"quality": True}
+
+    def open(self, ms, rec, L, **room):
+        if "sse" in rec:                                   # (Metrics, the part before: the recording has a ground truth)
+            rec["quality"] = torch.zeros(rec["n"], 2, 2, slots.QUALITY_WORDS, dtype=F64, device=rec["device"])
+
+    def scratch(self, ms):
+        if len(ms._size) != 4:
+            return {}
+        S, (H, W, gh, gw) = ms.S, ms._size
+        d = {"quality_stats": ((S, slots.metric_parts(gh, gw), slots.QUALITY_STATS_WORDS), F64, 0, True),
+             "quality_tiles": ((S, 4, slots.quality_tiles(gh, gw)), F64, 0, True),
+             "quality_resize": ((S, 2, gh, gw), F32, 0, True), "quality_mid": ((S, 2, H, W), F32, 0, True)}
+        if (gh, gw) != (ms.scale * H, ms.scale * W):
+            d["quality_resize_esr"] = ((S, 2, gh, gw), F32, 0, True)
+        return d
+
+    def fill(self, ms, v, s, r, i, reset):
+        if "quality" in r:                                 # (without ground truth: dst = 0 -- no record for the slot)
+            v["quality"][s]["dst"] = r["quality"][i].data_ptr()
+
+    def launch(self, ms, b, pred):
+        if len(ms._size) != 4:                             # no recording with ground truth yet
+            return
+        S, (H, W, gh, gw) = ms.S, ms._size
+        esr = pred                                         # (a self-ensemble session: the merged prediction is in the leader's row)
+        if "quality_resize_esr" in b:
+            esr = b["quality_resize_esr"]
+            lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", pred.data_ptr(), 2 * S, ms.scale * H, ms.scale * W, gh, gw,
+                     esr.data_ptr(), _stream())
+        b["quality_mid"].copy_(b["x"][:, :, 1])            # frame 1 of every slot's window, as stage gathered it: [S,2,H,W]
+        lib.call(lib._bicubic_fwd, "bmc_bicubic_resize_fwd", b["quality_mid"].data_ptr(), 2 * S, H, W, gh, gw,
+                 b["quality_resize"].data_ptr(), _stream())
+        slots.quality(b["table"], esr, b["quality_resize"], slots.metric_parts(gh, gw), 0.0 if ms.quality == "gt" else ms.quality,
+                      b["quality_stats"], b["quality_tiles"])
+
+    def results(self, ms, out, r, done, handle):
+        if "quality" in r:
+            psnr, ssim = slots.quality_values(r["quality"][:done], ms.quality, ms._size[2:])       # [done, 2 images] each
+            out.update(esr_psnr=psnr[:, 0].tolist(), esr_ssim=ssim[:, 0].tolist(), bicubic_psnr=psnr[:, 1].tolist(),
+                       bicubic_ssim=ssim[:, 1].tolist())
 
 
 class KeptPredictions(Part):

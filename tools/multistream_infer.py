@@ -30,6 +30,10 @@ event stream of every slot (counts_to_events(times="linear")) and events_to_voxe
 one without, --runs alternating runs each, on structured synthetic recordings (drifting bars: the ground truth is the Poisson counts
 of an HR rate field, an LR frame those of its 4 x 4 block means): RECORDING windows/s of both (with the option a recording takes K
 slots) and the mean esr_mse of the recordings both ran.  --plain-weights: BMCNet_plain(4,128,5) with the parameters of the file.
+--quality [RANGE] adds, per configuration, the frame-backed session with PSNR / SSIM on (quality=True, or dict(data_range=RANGE) with a
+number) and off, --runs alternating runs each in this process (ms per window and windows/s: the median, and every run), the quality
+part's launches alone (the resizes, the frame-1 copy and bmc_slot_quality's three kernels, events around 20 calls on the session's
+last table and prediction) and the means of esr_psnr, esr_ssim, bicubic_psnr and bicubic_ssim over the recordings' finite windows.
 --resident-windows N prints, per size, what an event-backed recording of N windows keeps resident with dense predictions and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
@@ -37,7 +41,7 @@ python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32]
                                   [--hot-filter] [--runs 3]
                                   [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
                                   [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]
-                                  [--self-ensemble K] [--plain-weights NPZ]"""
+                                  [--self-ensemble K] [--plain-weights NPZ] [--quality [RANGE]]"""
 import argparse
 import json
 import os
@@ -50,7 +54,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
 import torch
 
 from infer import MultiStreamSR, StreamingSR
-from infer_parts import EventStream, HotFilter, Input, Pictures, VoxelGrids
+from infer_parts import EventStream, HotFilter, Input, Pictures, Quality, VoxelGrids
 from models.BMCNet import BMCNet
 
 SEQN = 3
@@ -151,9 +155,9 @@ def sensor_spans(L, k):
 
 
 def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False,
-                hot_filter=None, render=None, render_dir=None, voxel_bins=None):
+                hot_filter=None, render=None, render_dir=None, voxel_bins=None, quality=None):
     ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times,
-                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, quality=quality)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
@@ -181,9 +185,27 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
         return lat, S * windows / wall, render_alone(ms), ms.resident_bytes(hs[0])
     if voxel_bins is not None:
         return lat, S * windows / wall, part_alone(ms, VoxelGrids), voxel_composition(ms), ms.resident_bytes(hs[0])
+    if quality is not None:
+        return lat, S * windows / wall, part_alone(ms, Quality), quality_means(ms, hs), ms.resident_bytes(hs[0])
     if events:
         return lat, S * windows / wall, part_alone(ms, Input if hot_filter is None else HotFilter), ms.resident_bytes(hs[0])
     return lat, S * windows / wall, ms.resident_bytes(hs[0])
+
+
+def quality_means(ms, hs):
+    """{key: (mean over the recordings of the mean over a recording's finite windows, windows left out)} of the four quality keys."""
+    import math
+    out = {}
+    for key in Quality.KEYS:
+        per, skipped = [], 0
+        for h in hs:
+            v = ms.results(h)[key]
+            finite = [x for x in v if math.isfinite(x)]
+            skipped += len(v) - len(finite)
+            if finite:
+                per.append(statistics.mean(finite))
+        out[key] = (statistics.mean(per) if per else float("nan"), skipped)
+    return out
 
 
 def structured_recording(L, H, W, seed, dev):
@@ -253,7 +275,15 @@ def parse_args(argv=None):
     ap.add_argument("--plain-weights", metavar="NPZ", default=None,
                     help="with --self-ensemble: run BMCNet_plain(4,128,5) with the parameters of this file (p/<name> arrays, as "
                          "tests/golden/plain_pretrained_weights.npz) instead of a randomly initialised BMCNet")
+    ap.add_argument("--quality", nargs="?", const="gt", default=None, metavar="RANGE",
+                    help="adds the session with PSNR / SSIM on (quality=True; with a number: dict(data_range=RANGE)) and off, "
+                         "alternating runs, and prints the recordings' means")
     a = ap.parse_args(argv)
+    if a.quality is not None:
+        try:
+            a.quality = Quality.check("--quality: ", True if a.quality == "gt" else dict(data_range=float(a.quality)))
+        except ValueError as e:
+            ap.error(str(e))
     if a.plain_weights is not None and a.self_ensemble is None:
         ap.error("--plain-weights needs --self-ensemble K")
     if a.voxel_bins is not None and not 1 <= a.voxel_bins <= MultiStreamSR.MAX_VOXEL_BINS:
@@ -364,6 +394,25 @@ def main():
                                      windows_per_s_voxel_off_runs=[round(r[1], 1) for r in off],
                                      voxel_alone_ms=round(vox, 4), voxel_share=round(vox / lat, 4),
                                      composition_ms=round(statistics.median(r[3] for r in on), 3), resident_bytes=on[-1][4]))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.quality is not None:
+                    off, on = [], []
+                    opt = True if a.quality == "gt" else dict(data_range=a.quality)
+                    for _ in range(a.runs):
+                        off.append(multistream(m, recs, S, graph, a.warmup, a.windows))
+                        on.append(multistream(m, recs, S, graph, a.warmup, a.windows, quality=opt))
+                    lat, qal = statistics.median(r[0] for r in on), statistics.median(r[2] for r in on)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(quality)", slots=S, data_range=a.quality,
+                                     ms_per_window=round(lat, 3), ms_per_window_quality_off=round(statistics.median(r[0] for r in off), 3),
+                                     ms_per_window_runs=[round(r[0], 3) for r in on],
+                                     ms_per_window_quality_off_runs=[round(r[0], 3) for r in off],
+                                     windows_per_s=round(statistics.median(r[1] for r in on), 1),
+                                     windows_per_s_quality_off=round(statistics.median(r[1] for r in off), 1),
+                                     windows_per_s_runs=[round(r[1], 1) for r in on],
+                                     windows_per_s_quality_off_runs=[round(r[1], 1) for r in off],
+                                     quality_alone_ms=round(qal, 4), quality_share=round(qal / lat, 4),
+                                     means={k: v[0] for k, v in on[-1][3].items()},
+                                     nonfinite_windows={k: v[1] for k, v in on[-1][3].items()}, resident_bytes=on[-1][4]))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.self_ensemble is not None and S % a.self_ensemble == 0:
                     K = a.self_ensemble
