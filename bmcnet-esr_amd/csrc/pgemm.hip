@@ -495,6 +495,15 @@ extern "C" int bmc_pgemm(const bmc_pgemm_args_t* h, bmc_stream_t stream) {
     BMC_CHECK_ARG(h->nsplit >= 1 && h->slabs, "bmc_pgemm: nsplit/slabs");
     BMC_CHECK_ARG(h->zeros != nullptr, "bmc_pgemm: the zero buffer is required");
     BMC_CHECK_ARG(h->a.ptr && h->a.nch > 0 && h->a.nch % 4 == 0 && h->a.pix_stride % 4 == 0, "bmc_pgemm: bad A operand");
+    // Every lane of a tile fill moves 16 bytes (LDS-DMA dwordx4 here, a 16-byte global load in pgemm_bf.hip) from
+    // base + 4 * (image * batch_stride + pixel * pix_stride + channel quad): with nch and pix_stride multiples of 4 that address
+    // is a multiple of 16 exactly when the base pointer and the batch stride are.  (A table operand's base is the table itself;
+    // the image pointers it holds live in device memory and are the caller's to keep aligned.)
+    auto aligned16 = [](const bmc_src_t& s) {
+        return s.batch_mod == BMC_SRC_TABLE ? ((uintptr_t)s.ptr & 7) == 0 : ((uintptr_t)s.ptr & 15) == 0 && s.batch_stride % 4 == 0;
+    };
+    BMC_CHECK_ARG(((uintptr_t)h->zeros & 15) == 0, "bmc_pgemm: the zero buffer must be 16-byte aligned");
+    BMC_CHECK_ARG(aligned16(h->a), "bmc_pgemm: A operand: pointer and batch stride must be 16-byte aligned");
     PgemmK k;
     k.a = to_dev(h->a);
     k.nsrc = h->nsrc;
@@ -503,6 +512,7 @@ extern "C" int bmc_pgemm(const bmc_pgemm_args_t* h, bmc_stream_t stream) {
         if (i < h->nsrc) {
             BMC_CHECK_ARG(h->src[i].ptr && h->src[i].nch > 0 && h->src[i].nch % 4 == 0 && h->src[i].pix_stride % 4 == 0,
                           "bmc_pgemm: bad source %d", i);
+            BMC_CHECK_ARG(aligned16(h->src[i]), "bmc_pgemm: source %d: pointer and batch stride must be 16-byte aligned", i);
             k.src[i] = to_dev(h->src[i]);
             N += h->src[i].nch;
         } else k.src[i] = to_dev(h->src[0]);

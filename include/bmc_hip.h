@@ -246,7 +246,12 @@ int bmc_conv(const bmc_conv_args_t* host_args, bmc_stream_t s);
  * torch.bmm(center, v) at models/submodules.py:69-70 (+ its backward).
  * Split over pixels: partial sums go to `slabs`
  * [nsplit][G][taps][Mpad][Npad] (Mpad/Npad = M/N rounded up to 32), which one of
- * the reduce calls below then sums (deterministic order). */
+ * the reduce calls below then sums (deterministic order).
+ * nsplit may exceed the number of pixel tiles (3x3: 4 x 16 pixels, 1x1: 64 flat pixels, per image of a group): a split
+ * without tiles writes a zero slab and zero bias partials.
+ * Alignment (checked): the tile fills move 16 bytes per lane, so every operand's nch and pix_stride are multiples of 4 and
+ * its ptr and batch_stride multiples of 16 bytes (4 floats); `zeros` is 16-byte aligned.  A BMC_SRC_TABLE operand's image
+ * pointers must be 16-byte aligned too; they live in device memory and are NOT checked. */
 typedef struct bmc_pgemm_args {
     bmc_src_t a;                /* nch = M */
     int nsrc;
