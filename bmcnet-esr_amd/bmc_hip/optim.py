@@ -24,16 +24,31 @@ reduced gradients.  A skipped step still counts as a step: `step` advances on th
 can know it was skipped without a sync), later bias corrections see t one higher, and the parameters' version counters advance
 after every step, a skipped one included.  The two options are attributes of the optimizer like track_grad_norm, not part of
 param_groups or state_dict(): state dicts keep interchanging with torch.optim.Adam.
+
+Weight EMA (csrc/optim_ema.hip; include/bmc_hip_ema.h).  Adam(..., ema_decay=D, ema_warmup=False) keeps an exponential moving
+average of every parameter in state[p]["ema"], updated INSIDE the step launch: the kernel holds the new p in registers and takes
+three more float32 roundings, e += w * (p - e) with w = float32(1 - decay_t), 44 bytes per element instead of 36 -- no launch, no
+host work and no sync is added, p and the other state come out bit for bit as without the option, and a step that
+nonfinite="skip" dropped leaves the averages untouched like everything else.  decay_t is D, or with ema_warmup min(D, t / (t + 9))
+for the 1-based step count t of the bias corrections (a skipped step counts).  The average is created as a copy of p when the
+parameter's state is created, or when a loaded state has none (a torch.optim.Adam state dict, a checkpoint of a run without
+EMA); it travels through state_dict() / load_state_dict() and so through checkpoint.save_checkpoint / resume, and
+torch.optim.Adam carries the extra key along untouched.  `with opt.ema_weights():` exchanges parameters and averages in place
+(one bmc_ema_swap launch per device on entry, one on exit) for validation; opt.ema_state_dict(model) is model.state_dict() with the
+averages in place of the parameters, the bare checkpoint of checkpoint.load_model_state.  Both options are attributes of the
+optimizer, not part of param_groups.  Several ranks need nothing more: GradAllReducer gives every rank the same reduced gradients
+and the step is deterministic, so every rank holds the same averages, bit for bit.
 """
 from __future__ import annotations
 
+import contextlib
 import numbers
 from collections import OrderedDict
 
 import numpy as np
 import torch
 
-from . import lib
+from . import ema_lib, lib
 from . import ops  # noqa: F401  -- registers the global pre-step hook (ops._join_before_step) wherever this optimizer is used
 
 CHUNK = lib.const("BMC_ADAM_CHUNK")
@@ -71,6 +86,33 @@ def chunk_table(entries):
     return tab
 
 
+def ema_chunk_table(entries):
+    """The chunk table of a launch with EMA, a pure host function.  entries: per parameter (p, g, m, v, vmax, n, e), chunk_table's
+    six and the address of the average.  -> (CHUNK_DTYPE array, uint64 array): the table, `aligned` cleared where the average is not
+    16-byte aligned, and parallel to it the EMA pointer of every chunk, at the chunk's first element."""
+    rows = [r for r in entries if r[1] is not None]
+    tab = chunk_table([r[:6] for r in rows])
+    if not rows:
+        return tab, np.zeros(0, np.uint64)
+    per = (np.asarray([r[5] for r in rows], dtype=np.int64) + CHUNK - 1) // CHUNK
+    which = np.repeat(np.arange(len(rows)), per)
+    p = np.asarray([r[0] for r in rows], dtype=np.uint64)[which]
+    e = np.asarray([r[6] for r in rows], dtype=np.uint64)[which]
+    tab["aligned"] = tab["aligned"] * ((e & np.uint64(15)) == 0)
+    return tab, e + (tab["p"] - p)
+
+
+def ema_decay_at(decay, warmup, t):
+    """decay_t of the step whose 1-based count is t, in float64: min(decay, t / (t + 9)) with warm-up, else decay."""
+    t = float(t)
+    return min(float(decay), t / (t + 9.0)) if warmup else float(decay)
+
+
+def ema_weight(decay, warmup, t):
+    """w = float32(1 - decay_t): a float64 subtraction rounded once, the value the capturable kernels compute on the device."""
+    return float(np.float32(1.0 - ema_decay_at(decay, warmup, t)))
+
+
 def step_hyper(lr, beta1, beta2, eps, weight_decay, amsgrad, step):
     """bmc_adam_hyper_t of step `step` (1-based): float64 arithmetic exactly as torch's _single_tensor_adam, each value rounded
     to float32 once (by the ctypes field)."""
@@ -87,8 +129,9 @@ def step_hyper(lr, beta1, beta2, eps, weight_decay, amsgrad, step):
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, amsgrad=False, *, capturable=False,
                  track_grad_norm=False, foreach=None, maximize=False, differentiable=False, fused=None, decoupled_weight_decay=False,
-                 max_grad_norm=None, nonfinite="propagate"):
+                 max_grad_norm=None, nonfinite="propagate", ema_decay=None, ema_warmup=False):
         _check_clip(max_grad_norm, nonfinite)                # before the parameters are looked at
+        _check_ema(ema_decay, ema_warmup)
         if isinstance(lr, torch.Tensor):
             raise ValueError("bmc_hip.optim.Adam: a tensor lr is not supported (the step size is computed on the host)")
         if not 0.0 <= lr:
@@ -106,6 +149,10 @@ class Adam(torch.optim.Optimizer):
         self.track_grad_norm = bool(track_grad_norm)
         self.max_grad_norm = max_grad_norm                   # None: never clip
         self.nonfinite = nonfinite                           # "propagate" | "skip"
+        self.ema_decay = ema_decay                           # None: no weight EMA
+        self.ema_warmup = ema_warmup
+        self._in_ema = False                                 # inside ema_weights(): parameters and averages are exchanged
+        self._ema_seen = {}                                  # parameter -> its average, once its shape, dtype and device are checked
         self._clip_memo = OrderedDict()   # the tables' keys of a clipped step -> its float64 partials (one array for all launches)
         self._clip_info = self._skipped = None               # device float64[2] {norm, c}; device int32 count of skipped steps
         self._clip_stepped = False
@@ -127,7 +174,7 @@ class Adam(torch.optim.Optimizer):
     def load_state_dict(self, state_dict):
         super().load_state_dict(state_dict)
         self._cohorts.clear(); self._cohort_of.clear(); self._count.clear()       # the state tensors are other tensors now
-        self._memo.clear(); self._clip_memo.clear()
+        self._memo.clear(); self._clip_memo.clear(); self._ema_seen.clear()
 
     # ------------------------------------------------------------------ one step
     @torch.no_grad()
@@ -137,6 +184,9 @@ class Adam(torch.optim.Optimizer):
             with torch.enable_grad():
                 loss = closure()
         _check_clip(self.max_grad_norm, self.nonfinite)
+        _check_ema(self.ema_decay, self.ema_warmup)
+        if self._in_ema:
+            raise RuntimeError("bmc_hip.optim.Adam: step() inside ema_weights(): the parameters hold the averages; leave the block first")
         if self._clipping:
             self._step_clipped()
             return loss
@@ -183,6 +233,16 @@ class Adam(torch.optim.Optimizer):
             elif amsgrad and "max_exp_avg_sq" not in st:
                 raise ValueError("bmc_hip.optim.Adam: the state of %s has no max_exp_avg_sq (amsgrad switched on after the first step)"
                                  % _name(group, i, gi))
+            if self.ema_decay is not None:
+                e = st.get("ema")
+                if e is None or self._ema_seen.get(p) is not e:          # (a tensor is looked at once, not at every step)
+                    if e is None:                            # a new state, or a loaded one without the key: the weights as they are
+                        e = st["ema"] = p.detach().clone(memory_format=torch.preserve_format)
+                    elif e.dtype != p.dtype or e.device != p.device or e.shape != p.shape or not e.is_contiguous():
+                        raise ValueError("bmc_hip.optim.Adam: the EMA of %s (%s, %s, %s%s) does not match its parameter: a dense "
+                                         "contiguous tensor of the parameter's shape, dtype and device is required" % (
+                                             _name(group, i, gi), tuple(e.shape), e.dtype, e.device, "" if e.is_contiguous() else ", not contiguous"))
+                    self._ema_seen[p] = e
             step_t = st["step"]
             if cap:
                 if not step_t.is_cuda:
@@ -201,7 +261,7 @@ class Adam(torch.optim.Optimizer):
 
     def _launch(self, group, dev, count, rows, amsgrad, cap, parts):
         with _current(dev):
-            table, n_chunks, partial = self._table(_table_key(rows, amsgrad), dev)
+            table, n_chunks, partial = self._table(_table_key(rows, amsgrad, self.ema_decay is not None), dev)
             self._issue(group, dev, count, rows, amsgrad, cap, table, n_chunks, partial.data_ptr() if partial is not None else None)
         if partial is not None:
             parts.append(partial)
@@ -212,12 +272,20 @@ class Adam(torch.optim.Optimizer):
         global STEP_LAUNCHES
         beta1, beta2 = group["betas"]
         h = step_hyper(group["lr"], beta1, beta2, group["eps"], group["weight_decay"], amsgrad, None if cap else count + 1)
-        fn, name = _ENTRY[isinstance(last, lib.AdamClip), cap]
         stream = torch._C._cuda_getCurrentRawStream(dev)
+        if self.ema_decay is None:
+            fn, name = _ENTRY[isinstance(last, lib.AdamClip), cap]
+            args = (table.data_ptr(), n_chunks, h)
+        else:                                                # the same launch with the averages: the EMA pointers follow the table
+            fn, name = _EMA_ENTRY[isinstance(last, lib.AdamClip), cap]
+            ema = ema_lib.AdamEma()
+            ema.e, ema.decay, ema.warmup = table.data_ptr() + n_chunks * CHUNK_DTYPE.itemsize, self.ema_decay, int(self.ema_warmup)
+            ema.w = 0.0 if cap else ema_weight(self.ema_decay, self.ema_warmup, count + 1)
+            args = (table.data_ptr(), n_chunks, h, ema)
         if cap:
-            lib.call(fn, name, table.data_ptr(), n_chunks, h, self._cohort(rows, dev).data_ptr(), last, stream)
+            lib.call(fn, name, *args, self._cohort(rows, dev).data_ptr(), last, stream)
         else:
-            lib.call(fn, name, table.data_ptr(), n_chunks, h, last, stream)
+            lib.call(fn, name, *args, last, stream)
         # torch's own state key: host tensors (no launch), or with capturable kept true on the device; a skipped step counts too
         torch._foreach_add_([st["step"] for _, _, st in rows], 1.0)
         STEP_LAUNCHES += 1
@@ -234,8 +302,13 @@ class Adam(torch.optim.Optimizer):
         if torch.cuda.is_current_stream_capturing():
             raise RuntimeError("bmc_hip.optim.Adam: this set of parameter, gradient and state buffers has no chunk table on the device "
                                "yet and none can be copied during a graph capture; take one step() with the same buffers first")
-        tab = chunk_table([k for k in key])
-        nbytes = tab.nbytes
+        if len(key[0]) == 7:                                 # with EMA: the pointer array travels behind the table, in the same copy
+            tab, eptr = ema_chunk_table(key)
+            host = np.concatenate([tab.view(np.uint8).reshape(-1), eptr.view(np.uint8)])
+        else:
+            tab = chunk_table([k for k in key])
+            host = tab.view(np.uint8).reshape(-1)
+        nbytes = host.nbytes
         if self._pinned is None or self._pinned.numel() < nbytes:
             if self._pinned_event is not None:
                 self._pinned_event.synchronize()
@@ -243,7 +316,7 @@ class Adam(torch.optim.Optimizer):
             self._pinned_event = torch.cuda.Event()
         else:
             self._pinned_event.synchronize()                 # the copy of the previous table has read the buffer
-        self._pinned[:nbytes].copy_(torch.from_numpy(tab.view(np.uint8).reshape(-1)))
+        self._pinned[:nbytes].copy_(torch.from_numpy(host))
         table = torch.empty(nbytes, dtype=torch.uint8, device=torch.device("cuda", dev))
         table.copy_(self._pinned[:nbytes], non_blocking=True)
         self._pinned_event.record()
@@ -272,7 +345,7 @@ class Adam(torch.optim.Optimizer):
             return
         dev = plan[0][1]
         with _current(dev):
-            keys = tuple(_table_key(rows, amsgrad) for _, _, _, rows, amsgrad, _ in plan)
+            keys = tuple(_table_key(rows, amsgrad, self.ema_decay is not None) for _, _, _, rows, amsgrad, _ in plan)
             tables = [self._table(key, dev) for key in keys]
             partials = self._clip_buffers(keys, sum(n for _, n, _ in tables), dev)
             stream = torch._C._cuda_getCurrentRawStream(dev)
@@ -329,6 +402,64 @@ class Adam(torch.optim.Optimizer):
             raise RuntimeError("bmc_hip.optim.Adam: skipped_steps() before the first step() that had gradients")
         return self._skipped
 
+    # ------------------------------------------------------------------ the averages
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """with opt.ema_weights(): the parameters hold their averages inside the block (validation, a "best" checkpoint) and the
+        raw weights come back after it, also when the block raises.  One bmc_ema_swap launch per device on entry and one on exit
+        exchange p and state[p]["ema"] in place, bit for bit; the parameters' version counters advance both times, so weight packs,
+        chains, ops.bias_dense and inference graphs see the other weights.  A parameter without an average yet keeps its value.
+        Not inside itself, not during a graph capture, and step() is refused inside."""
+        if self.ema_decay is None:
+            raise RuntimeError("bmc_hip.optim.Adam: ema_weights() needs ema_decay")
+        if self._in_ema:
+            raise RuntimeError("bmc_hip.optim.Adam: ema_weights() inside ema_weights(): the parameters already hold the averages")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("bmc_hip.optim.Adam: ema_weights() during a graph capture: the exchange is not part of a captured step")
+        self._swap()
+        self._in_ema = True
+        try:
+            yield self
+        finally:
+            self._in_ema = False
+            self._swap()
+
+    @torch.no_grad()
+    def _swap(self):
+        per_dev = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                e = self.state.get(p, {}).get("ema")
+                if e is not None:
+                    per_dev.setdefault(p.device.index, []).append((p, e))
+        for dev, pairs in per_dev.items():
+            key = tuple((p.data_ptr(), 0, 0, 0, 0, p.numel(), e.data_ptr()) for p, e in pairs)      # of a chunk only p, n, aligned are read
+            with _current(dev):
+                table, n_chunks, _ = self._table(key, dev)
+                lib.call(ema_lib._ema_swap, "bmc_ema_swap", table.data_ptr(), table.data_ptr() + n_chunks * CHUNK_DTYPE.itemsize,
+                         n_chunks, torch._C._cuda_getCurrentRawStream(dev))
+            torch.autograd.graph.increment_version([p for p, _ in pairs] + [e for _, e in pairs])
+
+    def ema_state_dict(self, model):
+        """model.state_dict() with every tensor that is one of this optimizer's parameters replaced by its average (a parameter
+        that has none yet keeps its own value); alias keys are kept, nothing else is touched.  The bare checkpoint that
+        checkpoint.load_model_state, MultiStreamSR and the reference's load_model consume.  Inside ema_weights() the parameters ARE
+        the averages and the dict is model.state_dict()."""
+        sd = model.state_dict()
+        if self._in_ema:
+            return sd
+        mine = {}
+        for group in self.param_groups:
+            for p in group["params"]:
+                e = self.state.get(p, {}).get("ema")
+                if e is not None:
+                    mine[(p.data_ptr(), tuple(p.shape), tuple(p.stride()))] = e.detach()
+        for k, v in sd.items():
+            e = mine.get((v.data_ptr(), tuple(v.shape), tuple(v.stride()))) if isinstance(v, torch.Tensor) else None
+            if e is not None:
+                sd[k] = e
+        return sd
+
     def _cohort(self, rows, dev):
         """capturable: the device int32 step counter of the parameters that leave in one launch.  It is made from the first
         parameter's own `step` tensor (the device holds the truth: a replayed graph advances both without the host), and a
@@ -369,6 +500,10 @@ class Adam(torch.optim.Optimizer):
 _ENTRY = {(False, False): (lib._adam_step, "bmc_adam_step"), (False, True): (lib._adam_step_cap, "bmc_adam_step_capturable"),
           (True, False): (lib._adam_step_clip, "bmc_adam_step_clipped"),
           (True, True): (lib._adam_step_clip_cap, "bmc_adam_step_clipped_capturable")}
+_EMA_ENTRY = {(False, False): (ema_lib._adam_ema_step, "bmc_adam_ema_step"),
+              (False, True): (ema_lib._adam_ema_step_cap, "bmc_adam_ema_step_capturable"),
+              (True, False): (ema_lib._adam_ema_step_clip, "bmc_adam_ema_step_clipped"),
+              (True, True): (ema_lib._adam_ema_step_clip_cap, "bmc_adam_ema_step_clipped_capturable")}
 
 
 class _current:
@@ -389,7 +524,10 @@ class _current:
             torch.cuda.set_device(self.prev)
 
 
-def _table_key(rows, amsgrad):
+def _table_key(rows, amsgrad, ema=False):
+    if ema:                                                  # ... and the address of the average
+        return tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                      st["max_exp_avg_sq"].data_ptr() if amsgrad else 0, p.numel(), st["ema"].data_ptr()) for p, g, st in rows)
     return tuple((p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                   st["max_exp_avg_sq"].data_ptr() if amsgrad else 0, p.numel()) for p, g, st in rows)
 
@@ -402,6 +540,18 @@ def _check_clip(max_grad_norm, nonfinite):
             raise ValueError("bmc_hip.optim.Adam: max_grad_norm = %r is not a positive number (in float32)" % (max_grad_norm,))
     if nonfinite not in ("propagate", "skip"):
         raise ValueError("bmc_hip.optim.Adam: nonfinite must be 'propagate' or 'skip', not %r" % (nonfinite,))
+
+
+def _check_ema(ema_decay, ema_warmup):
+    if ema_decay is not None:
+        if isinstance(ema_decay, (bool, torch.Tensor)) or not isinstance(ema_decay, numbers.Real):
+            raise ValueError("bmc_hip.optim.Adam: ema_decay must be None or a Python number in [0, 1), not %r" % (ema_decay,))
+        if not 0.0 <= float(ema_decay) < 1.0:                # NaN fails too
+            raise ValueError("bmc_hip.optim.Adam: ema_decay = %r is not in [0, 1)" % (ema_decay,))
+    if not isinstance(ema_warmup, (bool, np.bool_)):
+        raise ValueError("bmc_hip.optim.Adam: ema_warmup must be True or False, not %r" % (ema_warmup,))
+    if ema_warmup and ema_decay is None:
+        raise ValueError("bmc_hip.optim.Adam: ema_warmup=True needs ema_decay")
 
 
 def _name(group, i, gi):

@@ -16,6 +16,7 @@
 #include "bmc_hip.h"
 #include "bmc_hip_losses.h"
 #include "bmc_hip_quality.h"
+#include "bmc_hip_ema.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -85,6 +86,13 @@
 #define BMC_QUALITY_ABI_CONSTANTS(X) \
     X(BMC_QUALITY_WIN) X(BMC_QUALITY_WORDS) X(BMC_QUALITY_TILE_H) X(BMC_QUALITY_TILE_W) X(BMC_QUALITY_STATS_WORDS)
 
+/* include/bmc_hip_ema.h, the companion header of the weight EMA inside the optimizer step: likewise, bmc_ema_abi()
+ * (bmc_hip/ema_lib.py binds from it; tests/test_optim_ema_cpu.py compares the lists with that header's text). */
+#define BMC_EMA_ABI_FUNCTIONS(X) \
+    X(bmc_adam_ema_step) X(bmc_adam_ema_step_capturable) X(bmc_adam_ema_step_clipped) X(bmc_adam_ema_step_clipped_capturable) \
+    X(bmc_ema_swap) X(bmc_ema_abi)
+#define BMC_EMA_ABI_STRUCTS(X) X(bmc_adam_ema_t, F(e), F(decay), F(w), F(warmup))
+
 namespace {
 
 struct field {
@@ -124,6 +132,7 @@ template <class T> constexpr bool tiles() {
     static_assert(tiles<S>(), #S ": the field list above does not tile the struct (a field is missing or out of order)");
 BMC_ABI_STRUCTS(BMC_ABI_LAYOUT)
 BMC_QUALITY_ABI_STRUCTS(BMC_ABI_LAYOUT)
+BMC_EMA_ABI_STRUCTS(BMC_ABI_LAYOUT)
 
 template <class Fn> struct signature;
 template <class R, class... A> struct signature<R (*)(A...)> {
@@ -175,7 +184,19 @@ std::string quality_abi_text() {
     return out;
 }
 
+std::string ema_abi_text() {
+    std::string out;
+    BMC_EMA_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
+    BMC_EMA_ABI_STRUCTS(BMC_ABI_PUT_STRUCT)
+    return out;
+}
+
 }  // namespace
+
+extern "C" const char* bmc_ema_abi(void) {
+    static const std::string text = ema_abi_text();
+    return text.c_str();
+}
 
 extern "C" const char* bmc_quality_abi(void) {
     static const std::string text = quality_abi_text();

@@ -9,7 +9,8 @@
 // lane issues its (up to) 20 16-byte loads, then computes, then stores.  The table's pointers are made wave-uniform (readfirstlane)
 // and every access goes through the address-space(1) accessors of slot_k.h: scalar base + lane offset, global_* instructions, never
 // flat_*.  No workgroup waits for another, no atomics, no scratch memory.  The kernels below are shells: the walk over a chunk, the
-// element arithmetic and the set-up of the constants are in adam_k.h, once.
+// element arithmetic, the set-up of the constants, the unclipped body and the clipped head are in adam_k.h, once.  These are the
+// EMA = false instantiations; optim_ema.hip holds the EMA = true ones (include/bmc_hip_ema.h).
 #include "adam_k.h"
 
 namespace {
@@ -18,18 +19,7 @@ namespace {
 template <bool AMS, bool NORM, bool CAP>
 __global__ __launch_bounds__(AT) void adam_kernel(const bmc_adam_chunk_t* __restrict__ table, const bmc_adam_hyper_t h,
                                                   const int* __restrict__ step_dev, double* __restrict__ partial_sq) {
-    const int tid = threadIdx.x;
-    const Chunk ck = chunk_view<AMS>(table + blockIdx.x);
-    const AdamK k = adam_setup<CAP>(h, step_dev, tid);
-    if constexpr (NORM) {
-        __shared__ double red[AT];
-        double acc = 0.0;                          // this lane's share of sum(g^2), added in index order
-        step_chunk<AMS>(ck, tid, k, GradSumSq{acc});
-        const double total = tree_sum(red, acc, tid);
-        if (tid == 0) gst<double>(partial_sq + blockIdx.x, total);
-    } else {
-        step_chunk<AMS>(ck, tid, k, GradAsIs{});
-    }
+    adam_body<AMS, NORM, CAP, false>(table, h, step_dev, partial_sq, NoEma{});
 }
 
 // the norm launch of a clipped step: the partials adam_kernel<.., NORM = true, ..> stores, from g alone
@@ -47,19 +37,7 @@ __global__ __launch_bounds__(AT) void clip_step_kernel(const bmc_adam_chunk_t* _
     __shared__ double red[AT];
     const int tid = threadIdx.x;
     const Chunk ck = chunk_view<AMS>(table + blockIdx.x);
-
-    // the total of ALL partials of the step, the same bits in every workgroup: lane t adds partial t, t + 256, ... in that order
-    double acc = 0.0;
-    for (int i = tid; i < clip.n_partials; i += AT) acc += gld<double>(clip.partial_sq + i);
-    const double total = tree_sum(red, acc, tid);
-    const double norm = __builtin_sqrt(total);
-    const float c = clip_coeff(norm, clip.max_norm);
-    const bool skip = clip.skip_nonfinite != 0 && !__builtin_isfinite(total);      // uniform over the whole grid
-    if (blockIdx.x == 0 && tid == 0) {             // plain stores by one lane
-        if (clip.info) { gst<double>(clip.info, norm); gst<double>(clip.info + 1, (double)c); }
-        if (skip && clip.skipped) gst<int>(clip.skipped, gld<int>(clip.skipped) + 1);
-    }
-    if (skip) return;                              // nothing of p, m, v, vmax is stored
+    BMC_CLIP_STEP_HEAD(clip, red, tid);            // nothing of p, m, v, vmax is stored
 
     // The partials are reduced BEFORE the chunk's loads are issued: step_chunk comes last.  Issuing a full chunk's 20 loads first, so
     // that the reduction runs under their latency, holds 80 registers across the reduction and its barriers.  On the layout this
@@ -67,8 +45,8 @@ __global__ __launch_bounds__(AT) void clip_step_kernel(const bmc_adam_chunk_t* _
     // VGPRs, one wave per SIMD fewer, 24.6 against 17.6 us for the BMCNet(4,128,5) set on an MI355X.  On the shared walk the kernel
     // stands at 126-128 VGPRs with amsgrad (110-112 without), occupancy 4, and takes 16.0 us for that set; the other order has not
     // been measured on it.
-    const AdamK k = adam_setup<CAP>(h, step_dev, tid);
-    step_chunk<AMS>(ck, tid, k, GradClipped{c});
+    const AdamK k = adam_setup<CAP, false>(h, step_dev, tid, NoEma{});
+    step_chunk<AMS, false>(ck, tid, k, GradClipped{c});
 }
 
 // the last launch of the capturable entry points: one lane, a plain vector store (also after a skipped step)
@@ -83,8 +61,12 @@ adam_fn adam_pick(bool ams, bool norm) {
     return norm ? adam_kernel<false, true, CAP> : adam_kernel<false, false, CAP>;
 }
 
-// ---- host: the argument checks the entry points make before they launch
 bool finite_f(float v) { return isfinite(v); }
+
+}  // namespace
+
+// ---- host: the argument checks the entry points make before they launch (declared in adam_k.h: optim_ema.hip calls them too)
+namespace bmc_adam_host {
 
 int adam_check(const char* name, const bmc_adam_chunk_t* table, int n_chunks, const bmc_adam_hyper_t& h, bool cap) {
     BMC_CHECK_ARG(n_chunks >= 0, "%s: n_chunks = %d is negative", name, n_chunks);
@@ -119,7 +101,9 @@ int advance(const char* name, int* step_dev, bmc_stream_t s) {
     return 0;
 }
 
-}  // namespace
+}  // namespace bmc_adam_host
+
+using namespace bmc_adam_host;
 
 extern "C" int bmc_adam_step(const bmc_adam_chunk_t* table, int n_chunks, bmc_adam_hyper_t hyper, double* partial_sq, bmc_stream_t s) {
     if (adam_check("bmc_adam_step", table, n_chunks, hyper, false)) return -1;

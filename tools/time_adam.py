@@ -16,8 +16,14 @@ difference of the two traces' kernel counts over 5 steps is printed: set-up kern
 torch.nn.utils.clip_grad_norm_ with its default foreach followed by torch.optim.Adam with its default.  Floor of the clipped step:
 40 bytes per element (the norm launch reads g once more) and one more launch.
 
+--ema DECAY: the weight EMA inside the step (csrc/optim_ema.hip).  Three figures per set, each with the host's wall time per step
+(perf_counter around the loop that issues the steps, before the device is waited for): hip_ema, bmc_hip.optim.Adam(ema_decay=DECAY)
+(with --clip also max_grad_norm); hip, the same optimizer without the option (44 against 36 bytes per element); hip_swa, what a user
+has otherwise: torch.optim.swa_utils.AveragedModel(multi_avg_fn=get_ema_multi_avg_fn(DECAY)).update_parameters() after
+bmc_hip.optim.Adam.step().  Then the exchange launch alone (bmc_ema_swap, 16 bytes per element).
+
 python tools/time_adam.py [--steps 50 --warmup 10 --rounds 3] [--sets bmcnet,plain] [--only NAME] [--clip [--clip-norm 1.0]]
-                          [--trace [--trace-dir DIR]]
+                          [--trace [--trace-dir DIR]] [--ema DECAY]
 """
 import argparse
 import csv
@@ -34,6 +40,7 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "bmcnet-esr_amd")]
 CFG = dict(lr=1e-4, weight_decay=1e-5, amsgrad=True)
 NAMES = ("foreach", "single", "hip")
 CLIP_NAMES = ("foreach_clip", "hip", "hip_clip")
+EMA_NAMES = ("hip_swa", "hip", "hip_ema")
 
 
 class TorchClipped:
@@ -49,9 +56,33 @@ class TorchClipped:
         self.opt.step()
 
 
-def make(name, params, clip_norm=1.0):
+class HipWithAveragedModel:
+    """bmc_hip.optim.Adam.step() followed by torch's AveragedModel update: a second copy of the weights and a foreach pass"""
+
+    def __init__(self, params, decay, **kw):
+        import torch
+        from bmc_hip.optim import Adam
+        from torch.optim.swa_utils import AveragedModel, get_ema_multi_avg_fn
+        self.opt = Adam(params, **CFG, **kw)
+        self.model = torch.nn.Module()
+        self.model.w = torch.nn.ParameterList(params)
+        self.avg = AveragedModel(self.model, multi_avg_fn=get_ema_multi_avg_fn(decay))
+
+    def step(self):
+        self.opt.step()
+        self.avg.update_parameters(self.model)
+
+
+def make(name, params, clip_norm=1.0, ema=None, clip=False):
     import torch
     from bmc_hip.optim import Adam
+    if ema is not None:                          # the three variants of --ema, clipped alike with --clip
+        kw = dict(max_grad_norm=clip_norm) if clip else {}
+        if name == "hip_ema":
+            return Adam(params, ema_decay=ema, **kw, **CFG)
+        if name == "hip_swa":
+            return HipWithAveragedModel(params, ema, **kw)
+        return Adam(params, **kw, **CFG)
     if name == "hip":
         return Adam(params, **CFG)
     if name == "hip_clip":
@@ -74,31 +105,47 @@ def parameter_set(kind, dev):
     return params
 
 
-def timed(opt, steps):
+def timed(opt, steps, wall=None):
+    import time
     import torch
     e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     e0.record()
+    t0 = time.perf_counter()
     for _ in range(steps):
         opt.step()
+    t1 = time.perf_counter()
     e1.record()
     torch.cuda.synchronize()
+    if wall is not None:
+        wall.append((t1 - t0) * 1e3 / steps)     # the host's share: issuing the steps, not waiting for them
     return e0.elapsed_time(e1) / steps
+
+
+class Swapper:
+    """step() is one exchange of parameters and averages (bmc_ema_swap); an even number of them leaves everything as it was"""
+
+    def __init__(self, opt):
+        self.step = opt._swap
 
 
 def run(a):
     import torch
     dev = torch.device("cuda:0")
-    names = [a.only] if a.only else list(CLIP_NAMES if a.clip else NAMES)
+    made = [a.only] if a.only else list(EMA_NAMES if a.ema is not None else CLIP_NAMES if a.clip else NAMES)
     for kind in a.sets.split(","):
         base = parameter_set(kind, dev)
         n = sum(p.numel() for p in base)
         opts = {}
+        names = list(made)
         for name in names:                      # every optimizer on its own copy of the parameters, the same gradients
             params = [torch.nn.Parameter(p.detach().clone()) for p in base]
             for p, q in zip(params, base):
                 p.grad = q.grad.clone()
-            opts[name] = make(name, params, a.clip_norm)
-        for _ in range(a.warmup):
+            opts[name] = make(name, params, a.clip_norm, a.ema, a.clip)
+        if a.ema is not None and "hip_ema" in opts:
+            names = names + ["swap"]
+            opts["swap"] = Swapper(opts["hip_ema"])
+        for _ in range(a.warmup + a.warmup % 2):     # (an even count: the exchange is its own inverse)
             for name in names:
                 opts[name].step()
         torch.cuda.synchronize()
@@ -109,15 +156,17 @@ def run(a):
             torch.cuda.synchronize()
             continue
         rounds = {name: [] for name in names}
+        walls = {name: [] for name in names}
         for _ in range(a.rounds):
             for name in names:                  # alternating: what shares the machine hits all three alike
-                rounds[name].append(timed(opts[name], a.steps))
-        per = 40 if a.clip else 36
+                rounds[name].append(timed(opts[name], a.steps + (a.steps % 2 if name == "swap" else 0), walls[name]))
+        per = (40 if a.clip else 36) + (8 if a.ema is not None else 0)
         print("%s: %d tensors, %d elements, %.1f MB per pass (%d B per element; %.1f us at 6.3 TB/s)" % (
             kind, len(base), n, per * n / 1e6, per, per * n / 6.3e12 * 1e6))
         for name in names:
             print("  %-12s ms per step, %d steps per round: %s   median %.4f" % (
-                name, a.steps, "  ".join("%.4f" % v for v in rounds[name]), statistics.median(rounds[name])))
+                name, a.steps, "  ".join("%.4f" % v for v in rounds[name]), statistics.median(rounds[name])) +
+                ("   host wall %.4f" % statistics.median(walls[name]) if a.ema is not None else ""))
 
 
 def kernel_count(out_dir):
@@ -154,13 +203,18 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--sets", default="bmcnet,plain")
-    ap.add_argument("--only", choices=NAMES + CLIP_NAMES[::2], default=None)
+    ap.add_argument("--only", choices=NAMES + CLIP_NAMES[::2] + EMA_NAMES[::2], default=None)
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY")
     ap.add_argument("--clip", action="store_true")
     ap.add_argument("--clip-norm", type=float, default=1.0)
     ap.add_argument("--trace", action="store_true")
     ap.add_argument("--trace-dir", default=None)
     ap.add_argument("--child-timeout", type=float, default=240.0)
     a = ap.parse_args()
+    if a.ema is None and a.only in ("hip_swa", "hip_ema"):
+        ap.error("--only %s needs --ema DECAY" % a.only)
+    if a.ema is not None and a.trace:
+        ap.error("--ema is timed, not traced: no launch is added to the step")
     if a.trace:
         trace(a)           # this process never opens the GPU: each traced run is a fresh child
     else:

@@ -14,7 +14,12 @@ python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x8
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
                              [--gt-size HxW] [--valid-every N] [--crop HxW] [--transpose [P]]
-                             [--loss mse|l1|huber:DELTA|charbonnier:EPS]
+                             [--loss mse|l1|huber:DELTA|charbonnier:EPS] [--ema DECAY [--ema-warmup] [--save-ema PATH]]
+--ema DECAY (hip only): Adam(ema_decay=DECAY), an exponential moving average of the weights kept inside the step launch
+(csrc/optim_ema.hip); --ema-warmup ramps the decay as min(DECAY, t / (t + 9)).  With --valid-every the held-out sequences are
+also run under opt.ema_weights() and `valid_loss_ema` is printed beside `valid_loss`.  --save-ema PATH writes
+opt.ema_state_dict(model) there at the end, a bare checkpoint for checkpoint.load_model_state (--save is taken: it names the
+directory of the synthetic recordings).
 --loss: the training (and validation) loss, default mse (nn.MSELoss, the reference's).  l1, huber:DELTA (default 1) and
 charbonnier:EPS (default 1e-3) are bmc_hip.losses objects: the same fused head + loss launches with another pointwise function,
 at either ground-truth size.
@@ -108,6 +113,9 @@ def main():
     ap.add_argument("--transpose", type=float, nargs="?", const=0.5, default=None, metavar="P",
                     help="with --crop: transpose a sample's frames with probability P (default 0.5)")
     ap.add_argument("--loss", default="mse", help="mse | l1 | huber:DELTA | charbonnier:EPS")
+    ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep an EMA of the weights inside the step (hip only)")
+    ap.add_argument("--ema-warmup", action="store_true", help="decay_t = min(DECAY, t / (t + 9))")
+    ap.add_argument("--save-ema", default=None, metavar="PATH", help="write the EMA weights there at the end (a bare state_dict)")
     a = ap.parse_args()
     try:
         loss_obj = losses.parse(a.loss)                       # None: nn.MSELoss
@@ -115,6 +123,10 @@ def main():
         ap.error("--loss: %s" % e)
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
+    if a.ema is None and (a.ema_warmup or a.save_ema):
+        ap.error("--ema-warmup and --save-ema need --ema DECAY")
+    if a.ema is not None and a.optimizer != "hip":
+        ap.error("--ema needs --optimizer hip (the average is kept by the fused step)")
     if a.transpose is not None and not a.crop:
         ap.error("--transpose needs --crop: full frames of one size cannot hold a transposed sample")
     dev = torch.device("cuda:0")
@@ -154,7 +166,7 @@ def main():
     m = BMCNet(a.scale, a.n_c, a.n_b).to(dev)
     if a.optimizer == "hip":
         from bmc_hip.optim import Adam
-        opt = Adam(m.parameters(), lr=a.lr, max_grad_norm=a.clip_norm, nonfinite=a.nonfinite)
+        opt = Adam(m.parameters(), lr=a.lr, max_grad_norm=a.clip_norm, nonfinite=a.nonfinite, ema_decay=a.ema, ema_warmup=a.ema_warmup)
     else:
         if a.nonfinite != "propagate":
             raise SystemExit("--nonfinite skip needs --optimizer hip (torch.optim.Adam cannot skip a step without a host sync)")
@@ -181,9 +193,18 @@ def main():
             print("step %d  loss %.6f  encode %.3f ms  sequences %s" % (step, loss, rows[-1]["encode_ms"], idx))
             step += 1
             if vs is not None and step % a.valid_every == 0:
-                vl = [float(valid_step(m, *vs.batch(vidx), a.n_c, a.scale, loss=loss_obj)[0]) for vidx in vs.batches(a.batch, shuffle=False)]
+                validate = lambda: [float(valid_step(m, *vs.batch(vidx), a.n_c, a.scale, loss=loss_obj)[0])
+                                    for vidx in vs.batches(a.batch, shuffle=False)]
+                vl = validate()
                 rows[-1]["valid_loss"] = sum(vl) / len(vl)
-                print("step %d  valid_loss %.6f  (%d batches)" % (step - 1, rows[-1]["valid_loss"], len(vl)))
+                if a.ema is not None:
+                    with opt.ema_weights():                  # the same sequences on the averaged weights
+                        ve = validate()
+                    rows[-1]["valid_loss_ema"] = sum(ve) / len(ve)
+                    print("step %d  valid_loss %.6f  valid_loss_ema %.6f  (%d batches)" % (
+                        step - 1, rows[-1]["valid_loss"], rows[-1]["valid_loss_ema"], len(vl)))
+                else:
+                    print("step %d  valid_loss %.6f  (%d batches)" % (step - 1, rows[-1]["valid_loss"], len(vl)))
             if step == 1:
                 torch.cuda.synchronize()
                 clock = time.perf_counter()
@@ -196,6 +217,9 @@ def main():
     if a.optimizer == "hip" and (a.clip_norm is not None or a.nonfinite == "skip"):
         norm, c = opt.last_clip().tolist()                   # once, at the end: the step itself never syncs
         print("last step: gradient norm %.6g, clip coefficient %.6g; %d of %d steps skipped" % (norm, c, int(opt.skipped_steps()), step))
+    if a.save_ema:
+        torch.save({k: v.detach().cpu() for k, v in opt.ema_state_dict(m).items()}, a.save_ema)
+        print("EMA weights (decay %g%s) written to %s" % (a.ema, ", warm-up" if a.ema_warmup else "", a.save_ema))
     if a.out:
         with open(a.out, "w") as f:
             json.dump(rows, f)
