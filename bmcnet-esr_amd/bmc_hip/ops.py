@@ -2212,6 +2212,98 @@ def head_loss(xo, base, gt, r, loss=None):
     return HeadLossFn.apply(xo, base, gt, r, int(loss.kind), float(loss.param))
 
 
+_ssim_lib = None      # bmc_hip.ssim_lib, imported by the first structural loss: a run without one never loads it
+_SSIM_TILES = {}      # (device, stream, planes, h, w) -> the float64 tile partials of bmc_ssim_loss_fwd
+
+
+def _ssim():
+    global _ssim_lib
+    if _ssim_lib is None:
+        from . import ssim_lib
+        _ssim_lib = ssim_lib
+    return _ssim_lib
+
+
+class SsimLossFn(torch.autograd.Function):
+    """loss = 1 - mean SSIM(pred, gt) (uniform 7x7 window, constant data range, float64 on the float32 inputs: the contract is in
+    include/bmc_hip_ssim.h) as a float32 scalar: bmc_ssim_loss_fwd, two launches.  Saved for backward: pred and gt, nothing else --
+    bmc_ssim_loss_bwd recomputes the per-position coefficients in one launch and takes the upstream gradient as a device scalar.
+    The tile scratch is cached per device, stream and shape, so a call allocates the scalar only (and dx in backward): no host
+    read, capturable in a HIP graph."""
+
+    @staticmethod
+    def forward(ctx, pred, gt, data_range):
+        _need_gpu(pred)
+        sl = _ssim()
+        if pred.dim() != 4 or tuple(gt.shape) != tuple(pred.shape) or not gt.is_cuda or gt.dtype != torch.float32 or \
+                gt.device != pred.device:
+            raise RuntimeError("ssim_loss: pred and gt must be float32 GPU tensors [B, C, h, w] of one shape and device")
+        B, Cc, h, w = pred.shape
+        if min(h, w) < sl.WIN or B * Cc * h * w >= 2 ** 30:
+            raise ValueError("ssim_loss: images of at least %d x %d and fewer than 2^30 elements (got %s)"
+                             % (sl.WIN, sl.WIN, tuple(pred.shape)))
+        pred = pred.contiguous()
+        if gt.stride()[1:] != (h * w, w, 1) or gt.stride(0) < Cc * h * w:
+            gt = gt.contiguous()
+        stream = _stream()
+        key = (pred.device.index, stream, B * Cc, h, w)
+        tiles = _SSIM_TILES.get(key)
+        if tiles is None:
+            tiles = _SSIM_TILES[key] = torch.empty(B * Cc * sl.fwd_tiles(h, w), device=pred.device, dtype=torch.float64)
+        loss = torch.empty((), device=pred.device, dtype=torch.float32)
+        lib.call(sl._ssim_loss_fwd, "bmc_ssim_loss_fwd", pred.data_ptr(), gt.data_ptr(), gt.stride(0), B, Cc, h, w, data_range,
+                 tiles.data_ptr(), loss.data_ptr(), stream)
+        ctx.data_range = data_range
+        ctx.save_for_backward(pred, gt)
+        return loss
+
+    @staticmethod
+    def backward(ctx, dloss):
+        pred, gt = ctx.saved_tensors
+        B, Cc, h, w = pred.shape
+        dloss = dloss.contiguous()
+        dx = torch.empty_like(pred)
+        lib.call(_ssim()._ssim_loss_bwd, "bmc_ssim_loss_bwd", pred.data_ptr(), gt.data_ptr(), gt.stride(0), dloss.data_ptr(), B,
+                 Cc, h, w, ctx.data_range, dx.data_ptr(), _stream())
+        return dx, None, None
+
+
+def ssim_loss(pred, gt, data_range=1.0):
+    """pred [B,C,h,w] fp32 on the GPU, gt of the same shape (a batch stride is allowed: gt_cnt[:, i]), h, w >= 7 -> the float32
+    scalar 1 - mean SSIM with the constant data range (bmc_hip.losses.SSIM.__call__ is the same value in torch ops).  The
+    gradient reaches pred only."""
+    import math
+    data_range = float(data_range)
+    if not (math.isfinite(data_range) and data_range > 0.0):
+        raise ValueError("ssim_loss: data_range must be a finite positive number, got %r" % (data_range,))
+    return SsimLossFn.apply(pred, gt, data_range)
+
+
+def head_structural_loss(xo, base, gt, r, loss):
+    """head_loss for a bmc_hip.losses.SSIM or Mix object -> (pred, loss).  SSIM: pred from ops.head (bit for bit), resized to the
+    ground truth's size where the sizes differ, then ssim_loss.  Mix: the pointwise term through the fused head as head_loss
+    computes it (MSE for None), the structural term added on the prediction that head returns, weighted in torch scalar ops."""
+    from . import losses
+    if isinstance(loss, losses.Mix):
+        pred, point = head_loss(xo, base, gt, r, loss.pointwise)
+        s = ssim_loss(bicubic_resize(pred, gt.shape[-2:]), gt, loss.structural.param)
+        return pred, (1.0 - loss.alpha) * point + loss.alpha * s
+    if not isinstance(loss, losses.SSIM):
+        raise TypeError("head_structural_loss: %r is neither a bmc_hip.losses.SSIM nor a Mix object" % (loss,))
+    pred = head(xo, base, r)
+    return pred, ssim_loss(bicubic_resize(pred, gt.shape[-2:]), gt, loss.param)
+
+
+def loss_head(xo, base, gt, r, loss=None):
+    """What the models' forward_loss calls: head_loss for None (nn.MSELoss) and the pointwise bmc_hip.losses objects, exactly as
+    before; head_structural_loss for SSIM / Mix objects."""
+    if loss is not None:
+        from . import losses
+        if losses.is_structural(loss):
+            return head_structural_loss(xo, base, gt, r, loss)
+    return head_loss(xo, base, gt, r, loss)
+
+
 def pixel_unshuffle_nhwc(hr, r, split=1):
     return UnshuffleFn.apply(hr, r, split)
 

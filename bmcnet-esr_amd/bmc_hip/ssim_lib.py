@@ -1,0 +1,40 @@
+"""ctypes binding of include/bmc_hip_ssim.h, the companion header of the structural training loss (bmc_ssim_loss_fwd / _bwd),
+built like bmc_hip/lib.py's from the library's own description of it: bmc_ssim_abi() (csrc/abi.hip), fn and const records."""
+import ctypes as C
+
+from . import lib
+
+try:
+    lib._lib.bmc_ssim_abi.restype = C.c_char_p
+except AttributeError:
+    raise ImportError(f"{lib.LIB_PATH} does not export bmc_ssim_abi(): this build has no SSIM training loss -- rebuild it") from None
+lib._lib.bmc_ssim_abi.argtypes = []
+
+FUNCTIONS, CONSTANTS = {}, {}       # name -> [return code, parameter code, ...] / int
+for _kind, _name, *_rec in (line.split() for line in lib._lib.bmc_ssim_abi().decode().splitlines()):
+    if _kind == "fn":
+        FUNCTIONS[_name] = _rec
+    elif _kind == "const":
+        CONSTANTS[_name] = (float if _rec[0][0] == "f" else int)(_rec[1])
+    else:
+        raise ImportError(f"{lib.LIB_PATH}: unknown record in bmc_ssim_abi(): {_kind} {_name}")
+
+
+def const(name):
+    """The value of a numeric #define of include/bmc_hip_ssim.h."""
+    return CONSTANTS[name]
+
+
+WIN = const("BMC_SSIM_WIN")
+TILE_H, TILE_W = const("BMC_SSIM_TILE_H"), const("BMC_SSIM_TILE_W")                    # forward: window positions per workgroup
+BWD_TILE_H, BWD_TILE_W = const("BMC_SSIM_BWD_TILE_H"), const("BMC_SSIM_BWD_TILE_W")    # backward: pixels per workgroup
+FWD_LAUNCHES, BWD_LAUNCHES = 2, 1
+
+
+def fwd_tiles(h, w):
+    """Tile partials per plane of an h x w image: the doubles of scratch bmc_ssim_loss_fwd needs are B * C times this."""
+    return -(-(h - WIN + 1) // TILE_H) * -(-(w - WIN + 1) // TILE_W)
+
+
+_ssim_loss_fwd = lib._sig("bmc_ssim_loss_fwd", FUNCTIONS)
+_ssim_loss_bwd = lib._sig("bmc_ssim_loss_bwd", FUNCTIONS)

@@ -17,6 +17,7 @@
 #include "bmc_hip_losses.h"
 #include "bmc_hip_quality.h"
 #include "bmc_hip_ema.h"
+#include "bmc_hip_ssim.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -92,6 +93,12 @@
     X(bmc_adam_ema_step) X(bmc_adam_ema_step_capturable) X(bmc_adam_ema_step_clipped) X(bmc_adam_ema_step_clipped_capturable) \
     X(bmc_ema_swap) X(bmc_ema_abi)
 #define BMC_EMA_ABI_STRUCTS(X) X(bmc_adam_ema_t, F(e), F(decay), F(w), F(warmup))
+
+/* include/bmc_hip_ssim.h, the companion header of the structural training loss: likewise, bmc_ssim_abi() (bmc_hip/ssim_lib.py
+ * binds from it; tests/test_ssim_loss_cpu.py compares the lists with that header's text). */
+#define BMC_SSIM_ABI_FUNCTIONS(X) X(bmc_ssim_loss_fwd) X(bmc_ssim_loss_bwd) X(bmc_ssim_abi)
+#define BMC_SSIM_ABI_CONSTANTS(X) \
+    X(BMC_SSIM_WIN) X(BMC_SSIM_TILE_H) X(BMC_SSIM_TILE_W) X(BMC_SSIM_BWD_TILE_H) X(BMC_SSIM_BWD_TILE_W)
 
 namespace {
 
@@ -191,7 +198,19 @@ std::string ema_abi_text() {
     return out;
 }
 
+std::string ssim_abi_text() {
+    std::string out;
+    BMC_SSIM_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
+    BMC_SSIM_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
+    return out;
+}
+
 }  // namespace
+
+extern "C" const char* bmc_ssim_abi(void) {
+    static const std::string text = ssim_abi_text();
+    return text.c_str();
+}
 
 extern "C" const char* bmc_ema_abi(void) {
     static const std::string text = ema_abi_text();

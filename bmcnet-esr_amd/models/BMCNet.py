@@ -223,7 +223,9 @@ class BMCNet(nn.Module):
         train.py:227-231 and takes ops.head_resize_mse (the loss is against the resized prediction, the prediction
         returned -- the one that recurs -- is the unresized one, the same bits either way).
         loss: None = nn.MSELoss as above; a bmc_hip.losses object (L1, Huber, Charbonnier) = that loss in the same pass
-        (ops.head_loss -> bmc_head_loss_fwd / _bwd), at either ground-truth size, the same prediction bits."""
+        (ops.head_loss -> bmc_head_loss_fwd / _bwd), at either ground-truth size, the same prediction bits; a bmc_hip.losses SSIM
+        or Mix object = ops.head_structural_loss: the structural term through ops.ssim_loss on that prediction (resized to the
+        ground truth's size where the sizes differ), a Mix's pointwise term on the fused head as above."""
         return self.forward(x, x_h, x_h_p, x_h_n, x_o, init, _gt=gt, _loss=loss)
 
     def forward(self, x, x_h, x_h_p, x_h_n, x_o, init, _gt=None, _loss=None):
@@ -243,7 +245,7 @@ class BMCNet(nn.Module):
         h3 = ops.stack_states([x_h, x_h_p, x_h_n])
         n_h, n_hp, n_hn, o = self.neuro.forward_nhwc(xin12, h3, o12, zero_state=bool(init))
         if _gt is not None:
-            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale, _loss)
+            pred, mse = ops.loss_head(o, x[:, :, 1], _gt, self.scale, _loss)
             return to_nchw(n_h), to_nchw(n_hp), to_nchw(n_hn), pred, mse
         pred = ops.head(o, x[:, :, 1], self.scale)
         return to_nchw(n_h), to_nchw(n_hp), to_nchw(n_hn), pred

@@ -103,7 +103,8 @@ class BMCNet_plain(nn.Module):
         """forward() + nn.MSELoss()(prediction, gt) computed by the head kernel -> (x_h, prediction, mse).  gt of the
         prediction's size: ops.head_mse; of another size (train.py:227-231): ops.head_resize_mse, the loss against the
         bicubic-resized prediction while the unresized one is returned.  loss: None = nn.MSELoss; a bmc_hip.losses object
-        (L1, Huber, Charbonnier) = that loss in the same pass (ops.head_loss), at either size."""
+        (L1, Huber, Charbonnier) = that loss in the same pass (ops.head_loss), at either size; an SSIM or Mix object =
+        ops.head_structural_loss (ops.ssim_loss on the prediction, a Mix's pointwise term on the fused head)."""
         return self.forward(x, x_h, x_o, init, _gt=gt, _loss=loss)
 
     def forward(self, x, x_h, x_o, init, _gt=None, _loss=None):
@@ -117,6 +118,6 @@ class BMCNet_plain(nn.Module):
         o12 = self.neuro.pad_o(o12)
         n_h, o = self.neuro.forward_nhwc(xin12, to_nhwc(x_h), o12, zero_state=bool(init))
         if _gt is not None:
-            pred, mse = ops.head_loss(o, x[:, :, 1], _gt, self.scale, _loss)
+            pred, mse = ops.loss_head(o, x[:, :, 1], _gt, self.scale, _loss)
             return to_nchw(n_h), pred, mse
         return to_nchw(n_h), ops.head(o, x[:, :, 1], self.scale)

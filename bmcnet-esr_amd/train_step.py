@@ -1,7 +1,8 @@
 """One BPTT training step with the semantics of the reference's hot loop (train.py:202-237):
 zero_grad; for each sliding window: forward with the recurrent state carried WITHOUT detach, MSE against the HR
 count image of the window's second frame, losses summed; one backward over all windows; one optimizer step.
-Other losses than the reference's MSE: a bmc_hip.losses object (L1, Huber, Charbonnier) as loss_fn / loss keeps the fused head.
+Other losses than the reference's MSE: a bmc_hip.losses object (L1, Huber, Charbonnier) as loss_fn / loss keeps the fused head; an
+SSIM or Mix object adds the structural term on the head's prediction with the library's own kernels (ops.ssim_loss).
 
 Plus the synthetic NFS-shaped event generator used by bench.py / tests."""
 import torch
@@ -57,8 +58,10 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
     are bit-identical (same kernels, same order).
 
     loss_fn: F.mse_loss (the reference's nn.MSELoss) and INSTANCES of bmc_hip.losses.L1 / Huber / Charbonnier are computed by
-    the head kernel (model.forward_loss); every other callable -- F.l1_loss, a lambda around one of those objects -- gets the
-    unfused chain: model(), ops.bicubic_resize where the sizes differ, loss_fn and its autograd."""
+    the head kernel (model.forward_loss); INSTANCES of bmc_hip.losses.SSIM / Mix go through forward_loss too (the head, the
+    resize where the sizes differ, ops.ssim_loss; a Mix keeps its pointwise term on the head kernel); every other callable --
+    F.l1_loss, a lambda around one of those objects -- gets the unfused chain: model(), ops.bicubic_resize where the sizes
+    differ, loss_fn and its autograd."""
     from torch.utils.checkpoint import checkpoint
     B, L, _, H, W = inp_cnt.shape
     dev = inp_cnt.device
@@ -73,7 +76,7 @@ def bptt_step(model, optimizer, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False
         # than the prediction's is the bicubic branch of train.py:227-231, resized inside that pass.  A bmc_hip.losses object:
         # the same pass with its rho (forward_loss(..., loss=loss_fn)).  Any other loss_fn object (a wrapper around F.mse_loss
         # or around a losses object included) selects the unfused chain below.
-        robust = losses.is_fusable(loss_fn)
+        robust = losses.on_device_path(loss_fn)
         fused = (loss_fn is F.mse_loss or robust) and hasattr(model, "forward_loss")
         fn = model.forward_loss if fused else model
         extra = (gt,) if fused else ()
@@ -104,13 +107,14 @@ def valid_step(model, inp_cnt, gt_cnt, n_c, scale, seqn=2, plain=False, loss=Non
     windows as in bptt_step with the state carried, the window losses (nn.MSELoss, against the bicubic-resized prediction
     where the ground truth has another size, train.py:502-506) summed through forward_loss.  No backward, no optimizer;
     nothing of the ground truth's size is allocated.  loss: None = nn.MSELoss; a bmc_hip.losses object (L1, Huber, Charbonnier)
-    = that loss through the same fused head; any other callable = the unfused chain (model(), ops.bicubic_resize where the
-    sizes differ, the callable).  Returns (loss, last window's loss); the model's training mode is restored."""
+    = that loss through the same fused head; an SSIM / Mix object = forward_loss with ops.ssim_loss, forward only (the resized
+    prediction is allocated where the sizes differ); any other callable = the unfused chain (model(), ops.bicubic_resize where
+    the sizes differ, the callable).  Returns (loss, last window's loss); the model's training mode is restored."""
     B, L, _, H, W = inp_cnt.shape
     dev = inp_cnt.device
     z = lambda c: torch.zeros(B, c, H, W, device=dev)
     loss_fn = None if loss is F.mse_loss else loss
-    fused = loss_fn is None or losses.is_fusable(loss_fn)
+    fused = loss_fn is None or losses.on_device_path(loss_fn)
     kw = {} if loss_fn is None else {"loss": loss_fn}
     was_training = model.training
     model.eval()

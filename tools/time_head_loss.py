@@ -2,10 +2,12 @@
 """Time the loss head of a window, fused against the chain it replaces, on the GPU: a ground truth that is not of the prediction's
 size (train.py:227-231) and, for the equal-size path, BASELINE's C2 frame.
 
---loss mse|l1|huber:DELTA|charbonnier:EPS (default mse) picks the loss; fused and unfused evaluate the SAME loss object.
+--loss mse|l1|huber:DELTA|charbonnier:EPS|ssim[:R]|POINT+ssim[:R][@ALPHA] (default mse) picks the loss; fused and unfused
+evaluate the SAME loss object (unfused: the object's plain-torch __call__, for ssim a float64 chain of avg_pool2d and elementwise ops).
 Part `isolated`: forward + backward of the head and loss alone, with a gradient arriving from the next window as in a BPTT step,
-  fused    ops.head_loss: mse -> ops.head_mse / ops.head_resize_mse (bmc_head_mse_* / bmc_head_resize_mse_*), another loss ->
-           bmc_head_loss_fwd / _bwd
+  fused    ops.loss_head: mse -> ops.head_mse / ops.head_resize_mse (bmc_head_mse_* / bmc_head_resize_mse_*), a pointwise loss ->
+           bmc_head_loss_fwd / _bwd, ssim -> ops.head, ops.bicubic_resize, ops.ssim_loss (bmc_ssim_loss_fwd / _bwd), a mix -> the
+           pointwise head plus ops.ssim_loss on its prediction
   unfused  the composition it replaces: ops.head -> ops.bicubic_resize (where the sizes differ) -> the loss in torch ops,
            autograd's backward of the three and its add of the two gradients that reach the prediction
 at LR 31x56 -> 124x222 (EventZoom), LR 65x87 -> 260x346 (DAVIS346) and LR 180x240 -> 720x960 (C2: the prediction's own size, no
@@ -15,12 +17,16 @@ Part `step`: the whole train_step.bptt_step of BMCNet(4,128,5) at BASELINE confi
   fused    ground truth 124x222, loss_fn = F.mse_loss or the bmc_hip.losses object
   unfused  ground truth 124x222, the unfused chain selected through a lambda around the same loss
   same     ground truth 124x224 (the synthetic size bench.py times)
+Part `ssim` (structural losses only): the loss ALONE on a prediction of the ground truth's size -- forward (under no_grad) and
+backward (of a retained graph) timed separately, the device path (the loss object's structural term through ops.ssim_loss, a mix's
+pointwise term in torch ops on both sides) against the object's plain-torch form, with the kernel launches of one forward and one
+backward of each counted by torch.profiler -- at the reference's training shape (180x320, B = 2) and C2 (720x960, B = 4).
 The variants alternate inside one process, every variant is warmed before anything is timed, a repetition ends in a device
 synchronise; reported: median and range over --reps (>= 15) repetitions, every repetition in the JSON, and fused / unfused per
 repetition (they run back to back; the launches are host-issue-bound and the host's speed changes under other people's work).
 No GPU is an error: nothing here runs on the CPU.
 
-python tools/time_head_loss.py [--part isolated|step|all] [--variants fused,unfused,same] [--reps 15] [--inner 50] [--warmup 3]
+python tools/time_head_loss.py [--part isolated|step|ssim|all] [--variants fused,unfused,same] [--reps 15] [--inner 50] [--warmup 3]
                                [--math fp32,bf16] [--loss mse] [--out FILE]
 For a launch count, trace one variant at a time:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/time_head_loss.py
 --part isolated --variants fused --reps 1 --inner 1 --warmup 0 --allow-few-reps   (then the same with --variants unfused).
@@ -90,7 +96,7 @@ def isolated(dev, want, reps, inner, warmup, loss):
         one = torch.ones((), device=dev)
 
         def fused():
-            pred, mse = ops.head_loss(xo, base, gt, SCALE, loss)
+            pred, mse = ops.loss_head(xo, base, gt, SCALE, loss)
             return torch.autograd.grad([pred, mse], [xo], [dpred, one])[0]
 
         def unfused():
@@ -110,6 +116,63 @@ def isolated(dev, want, reps, inner, warmup, loss):
             print("isolated %-9s %-8s %9.2f us  (%.2f .. %.2f, %d reps x %d calls)" % (name, k, s["median_ms"] * 1e3, s["min_ms"] * 1e3,
                                                                                  s["max_ms"] * 1e3, s["reps"], inner), flush=True)
         paired("isolated %-9s" % name, ms, rows[name])
+    return rows
+
+
+SSIM_SHAPES = [("train", 2, 180, 320), ("C2", 4, 720, 960)]
+
+
+def launches(fn):
+    """Kernel launches of one call of fn, counted by torch.profiler (None where the profiler reports no device activity)."""
+    from torch.profiler import ProfilerActivity, profile
+    torch.cuda.synchronize()
+    with profile(activities=[ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    n = sum(1 for e in prof.events() if e.device_type == torch.autograd.DeviceType.CUDA and "memcpy" not in e.name.lower() and
+            "memset" not in e.name.lower())
+    return n or None
+
+
+def ssim_alone(dev, want, reps, inner, warmup, loss):
+    from bmc_hip import losses, ops
+    structural = loss if isinstance(loss, losses.SSIM) else loss.structural
+
+    def device(pred, gt):
+        s = ops.ssim_loss(pred, gt, structural.param)
+        if structural is loss:
+            return s
+        point = F.mse_loss(pred, gt) if loss.pointwise is None else loss.pointwise(pred, gt)
+        return (1.0 - loss.alpha) * point + loss.alpha * s
+
+    rows = {}
+    for name, b, h, w in SSIM_SHAPES:
+        torch.manual_seed(0)
+        gt = torch.poisson(torch.full((b, 2, h, w), 0.3)).to(dev)
+        pred = (gt + 0.5 * torch.randn_like(gt)).requires_grad_()
+        paths = {k: f for k, f in (("fused", device), ("unfused", lambda a, g: loss(a, g))) if k in want}
+        row = rows[name] = {"shape": "%dx%d, B=%d" % (h, w, b), "inner": inner}
+
+        def fwd(f):
+            def run():
+                with torch.no_grad():
+                    f(pred, gt)
+            return run
+
+        held = {k: f(pred, gt) for k, f in paths.items()}
+        bwd = lambda k: (lambda: torch.autograd.grad(held[k], pred, retain_graph=True))
+        for tag, variants in (("forward", {k: fwd(f) for k, f in paths.items()}), ("backward", {k: bwd(k) for k in paths})):
+            ms = alternate(variants, reps, inner, warmup)
+            row[tag] = {k: summary(v) for k, v in ms.items()}
+            for k in ms:
+                s = row[tag][k]
+                row[tag][k]["launches"] = launches(variants[k])
+                print("ssim %-5s %-8s %-8s %9.2f us  (%.2f .. %.2f, %d reps x %d calls)  launches %s" % (
+                    name, tag, k, s["median_ms"] * 1e3, s["min_ms"] * 1e3, s["max_ms"] * 1e3, s["reps"], inner, s["launches"]), flush=True)
+            paired("ssim %-5s %-8s" % (name, tag), ms, row[tag])
+        if len(paths) == 2:
+            row["loss_difference"] = abs(float(held["fused"]) - float(held["unfused"]))
+            row["max_abs_grad_difference"] = float((bwd("fused")()[0] - bwd("unfused")()[0]).abs().max())
     return rows
 
 
@@ -147,14 +210,14 @@ def step(dev, want, maths, reps, warmup, loss):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--part", choices=("isolated", "step", "all"), default="all")
+    ap.add_argument("--part", choices=("isolated", "step", "ssim", "all"), default="all")
     ap.add_argument("--variants", default="fused,unfused,same")
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--inner", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--math", default="fp32,bf16")
     ap.add_argument("--allow-few-reps", action="store_true", help="for a kernel trace: fewer than 15 repetitions, no timing claimed")
-    ap.add_argument("--loss", default="mse", help="mse | l1 | huber:DELTA | charbonnier:EPS")
+    ap.add_argument("--loss", default="mse", help="mse | l1 | huber:DELTA | charbonnier:EPS | ssim[:R] | POINT+ssim[:R][@ALPHA]")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     from bmc_hip import losses
@@ -171,6 +234,10 @@ def main():
     out = {"device": torch.cuda.get_device_name(dev), "reps": a.reps, "warmup": a.warmup, "loss": a.loss}
     if a.part in ("isolated", "all"):
         out["isolated"] = isolated(dev, want, a.reps, a.inner, a.warmup, loss)
+    if a.part in ("ssim", "all") and losses.is_structural(loss):
+        out["ssim"] = ssim_alone(dev, want, a.reps, a.inner, a.warmup, loss)
+    elif a.part == "ssim":
+        ap.error("--part ssim times a structural loss: --loss ssim[:R] or POINT+ssim[:R][@ALPHA]")
     if a.part in ("step", "all"):
         out["step"] = step(dev, want, a.math.split(","), a.reps, a.warmup, loss)
     print(json.dumps(out))

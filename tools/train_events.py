@@ -14,7 +14,7 @@ python tools/train_events.py [rec.npz ...] [--synthetic 2 --items 24 --size 45x8
                              [--augment] [--pause 0.05,0.9] [--noise 0.01] [--n-c 128 --n-b 5] [--seed 0] [--out FILE]
                              [--optimizer hip|torch] [--clip-norm X] [--nonfinite propagate|skip] [--wall]
                              [--gt-size HxW] [--valid-every N] [--crop HxW] [--transpose [P]]
-                             [--loss mse|l1|huber:DELTA|charbonnier:EPS] [--ema DECAY [--ema-warmup] [--save-ema PATH]]
+                             [--loss mse|l1|huber:DELTA|charbonnier:EPS|ssim[:R]|POINT+ssim[:R][@ALPHA]] [--ema DECAY [--ema-warmup] [--save-ema PATH]]
 --ema DECAY (hip only): Adam(ema_decay=DECAY), an exponential moving average of the weights kept inside the step launch
 (csrc/optim_ema.hip); --ema-warmup ramps the decay as min(DECAY, t / (t + 9)).  With --valid-every the held-out sequences are
 also run under opt.ema_weights() and `valid_loss_ema` is printed beside `valid_loss`.  --save-ema PATH writes
@@ -22,7 +22,9 @@ opt.ema_state_dict(model) there at the end, a bare checkpoint for checkpoint.loa
 directory of the synthetic recordings).
 --loss: the training (and validation) loss, default mse (nn.MSELoss, the reference's).  l1, huber:DELTA (default 1) and
 charbonnier:EPS (default 1e-3) are bmc_hip.losses objects: the same fused head + loss launches with another pointwise function,
-at either ground-truth size.
+at either ground-truth size.  ssim[:R] is 1 - mean SSIM with the constant data range R (default 1, one event; bmc_hip.losses.SSIM)
+and POINT+ssim[:R][@ALPHA], POINT one of mse | l1 | huber[:D] | charbonnier[:E], the mix (1 - ALPHA) POINT + ALPHA ssim (default
+0.84; l1+ssim:8@0.84): the pointwise term stays on the fused head, the structural one runs bmc_ssim_loss_fwd / _bwd on its prediction.
 --crop HxW: train on HxW LR patches (and scale x that HR patches) cut in the encoder, one random origin per sequence
 (EventTrainSet(crop=...), ONE bmc_seq_encode_crop launch per batch).  --size and --gt-size then take comma-separated lists the
 synthetic recordings cycle through (--size 180x240,260x346), a set of mixed sensors; recordings given as files may differ in size
@@ -112,7 +114,7 @@ def main():
     ap.add_argument("--crop", default=None, help="HxW of the LR patches to train on; --size / --gt-size may then be lists")
     ap.add_argument("--transpose", type=float, nargs="?", const=0.5, default=None, metavar="P",
                     help="with --crop: transpose a sample's frames with probability P (default 0.5)")
-    ap.add_argument("--loss", default="mse", help="mse | l1 | huber:DELTA | charbonnier:EPS")
+    ap.add_argument("--loss", default="mse", help="mse | l1 | huber:DELTA | charbonnier:EPS | ssim[:R] | POINT+ssim[:R][@ALPHA]")
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep an EMA of the weights inside the step (hip only)")
     ap.add_argument("--ema-warmup", action="store_true", help="decay_t = min(DECAY, t / (t + 9))")
     ap.add_argument("--save-ema", default=None, metavar="PATH", help="write the EMA weights there at the end (a bare state_dict)")
