@@ -28,28 +28,36 @@ _lib = C.CDLL(LIB_PATH)
 c_fp = C.c_void_p  # device pointers travel as integers
 
 # ---- the ABI, as the library states it (csrc/abi.hip): nothing below types a signature, an offset or a size by hand ----
-try:
-    _lib.bmc_abi.restype = C.c_char_p
-except AttributeError:
-    raise ImportError(f"{LIB_PATH} does not export bmc_abi(): the binding is built from the library's own description of its "
-                      "ABI, and this build (an old one, reached through BMC_HIP_LIB?) has none -- rebuild it") from None
-_lib.bmc_abi.argtypes = []
-
-
 Field = namedtuple("Field", "name offset size elem_size code shape")     # code: the element type, i4 / u4 / i8 / f4 / f8, p[:pointee]
 Struct = namedtuple("Struct", "size align fields")                       # (a pointer), s:<struct>; shape: array extents; fields: by name
-FUNCTIONS, STRUCTS, CONSTANTS = {}, {}, {}      # name -> [return code, parameter code, ...] / Struct / int or float
-for _kind, _name, *_rec in (line.split() for line in _lib.bmc_abi().decode().splitlines()):
-    if _kind == "fn":
-        FUNCTIONS[_name] = _rec
-    elif _kind == "struct":
-        STRUCTS[_name] = Struct(int(_rec[0]), int(_rec[1]), {})
-    elif _kind == "field":
-        STRUCTS[_name].fields[_rec[0]] = Field(_rec[0], int(_rec[1]), int(_rec[2]), int(_rec[3]), _rec[4], tuple(map(int, _rec[5:])))
-    elif _kind == "const":
-        CONSTANTS[_name] = (float if _rec[0][0] == "f" else int)(_rec[1])
-    else:
-        raise ImportError(f"{LIB_PATH}: unknown record in bmc_abi(): {_kind} {_name}")
+
+
+def bind(symbol, lacks):
+    """The records of one ABI text of the library, symbol() -- bmc_abi() for include/bmc_hip.h, one per companion header -- as
+    (FUNCTIONS, STRUCTS, CONSTANTS): name -> [return code, parameter code, ...] / Struct / int or float.  lacks: what a build
+    without the symbol is missing, for the ImportError."""
+    try:
+        text = getattr(_lib, symbol)
+    except AttributeError:
+        raise ImportError(f"{LIB_PATH} does not export {symbol}(): {lacks} -- rebuild it") from None
+    text.restype, text.argtypes = C.c_char_p, []
+    functions, structs, constants = {}, {}, {}
+    for kind, name, *rec in (line.split() for line in text().decode().splitlines()):
+        if kind == "fn":
+            functions[name] = rec
+        elif kind == "struct":
+            structs[name] = Struct(int(rec[0]), int(rec[1]), {})
+        elif kind == "field":
+            structs[name].fields[rec[0]] = Field(rec[0], int(rec[1]), int(rec[2]), int(rec[3]), rec[4], tuple(map(int, rec[5:])))
+        elif kind == "const":
+            constants[name] = (float if rec[0][0] == "f" else int)(rec[1])
+        else:
+            raise ImportError(f"{LIB_PATH}: unknown record in {symbol}(): {kind} {name}")
+    return functions, structs, constants
+
+
+FUNCTIONS, STRUCTS, CONSTANTS = bind("bmc_abi", "the binding is built from the library's own description of its ABI, and this "
+                                     "build (an old one, reached through BMC_HIP_LIB?) has none")
 EXPORTS = list(FUNCTIONS) + ["bmc_abi"]
 
 
@@ -58,10 +66,11 @@ def const(name):
     return CONSTANTS[name]
 
 
-def dtype(struct):
-    """The numpy dtype of a table struct of the header (scalar and pointer fields; pointers are <u8)."""
-    fields = STRUCTS[struct].fields.values()
-    return np.dtype({"names": [f.name for f in fields], "offsets": [f.offset for f in fields], "itemsize": STRUCTS[struct].size,
+def dtype(struct, structs=STRUCTS):
+    """The numpy dtype of a table struct of the header (scalar and pointer fields; pointers are <u8).  structs: the table that
+    describes it, a companion header's for one of its structs."""
+    fields = structs[struct].fields.values()
+    return np.dtype({"names": [f.name for f in fields], "offsets": [f.offset for f in fields], "itemsize": structs[struct].size,
                      "formats": [("<u8" if f.code[0] == "p" else "<" + f.code, f.shape) for f in fields]})
 
 
@@ -81,19 +90,19 @@ def _ctype(code):
     return _SCALARS[kind]
 
 
-def _mirror(struct, cls):
-    """The ctypes mirror of a host struct of the header, fields from the table.  cls: the new class's name, or a Structure
-    subclass that still lacks its _fields_ (one with host-side attributes of its own)."""
+def _mirror(struct, cls, structs=STRUCTS):
+    """The ctypes mirror of a host struct of the header, fields from the table `structs`.  cls: the new class's name, or a
+    Structure subclass that still lacks its _fields_ (one with host-side attributes of its own)."""
     if isinstance(cls, str):
         cls = type(cls, (C.Structure,), {})
     fields = []
-    for f in STRUCTS[struct].fields.values():
+    for f in structs[struct].fields.values():
         t = _ctype(f.code)
         for n in reversed(f.shape):
             t = t * n
         fields.append((f.name, t))
     cls._fields_ = fields
-    if C.sizeof(cls) != STRUCTS[struct].size or any(getattr(cls, f.name).offset != f.offset for f in STRUCTS[struct].fields.values()):
+    if C.sizeof(cls) != structs[struct].size or any(getattr(cls, f.name).offset != f.offset for f in structs[struct].fields.values()):
         raise ImportError(f"ctypes lays out {struct} differently from the compiler that built {LIB_PATH}")
     _MIRRORS[struct] = cls
     return cls

@@ -2037,142 +2037,56 @@ class HeadFn(torch.autograd.Function):
         return _unshuffle(dpred.contiguous(), ctx.r), None, None
 
 
-class HeadMseFn(torch.autograd.Function):
-    """(pred, mse) = head + nn.MSELoss in one pass (bmc_head_mse_fwd); the backward folds the loss gradient
-    2 (pred - gt) / numel into the pixel-unshuffle of the gradient arriving from the next window (bmc_head_mse_bwd)."""
+class FusedHeadFn(torch.autograd.Function):
+    """(pred, loss) = head + the loss against the ground truth in one pass; pred is bit for bit ops.head's.  One node behind
+    head_mse, head_resize_mse and head_loss, which differ in the entry points they launch:
+      kind None, resize False   nn.MSELoss at the prediction's size (bmc_head_mse_fwd / _bwd);
+      kind None, resize True    ... against the bicubic-resized prediction (train.py:227-233; bmc_head_resize_mse_fwd / _bwd);
+      kind, param               a robust loss (bmc_hip.losses: L1, Huber, Charbonnier) at either size (bmc_head_loss_fwd / _bwd);
+                                resize None: whether the sizes differ.
+    The resized prediction is never stored.  Saved for backward: with a resize d = resized - gt alone (the backward folds its
+    transposed resize, and rho' for a robust loss, into the pixel-unshuffle of the gradient arriving from the next window),
+    without one pred and gt, nothing new.  Where no backward can follow (torch.no_grad()) nothing of the ground truth's size is
+    allocated."""
 
     @staticmethod
-    def forward(ctx, xo, base, gt, r):
+    def forward(ctx, xo, base, gt, r, kind, param, resize):
         _need_gpu(xo)
         xo = xo.contiguous()
         B, H, W, CC = xo.shape
         Cc = CC // (r * r)
-        if tuple(gt.shape) != (B, Cc, H * r, W * r) or not gt.is_cuda or gt.dtype != torch.float32:
-            raise RuntimeError("head_mse: ground truth must be a float32 GPU tensor of the prediction's shape")
-        if gt.stride()[1:] != (H * r * W * r, W * r, 1):
-            gt = gt.contiguous()
-        pred = torch.empty((B, Cc, H * r, W * r), device=xo.device, dtype=torch.float32)
-        ws = torch.empty(2048, device=xo.device, dtype=torch.float32)
-        loss = torch.empty((), device=xo.device, dtype=torch.float32)
-        sb, sc, sy, sx = base.stride()
-        lib.call(lib._head_mse_fwd, "bmc_head_mse_fwd", xo.data_ptr(), B, Cc, H, W, r, base.data_ptr(), sb, sc, sy, sx,
-                 gt.data_ptr(), gt.stride(0), pred.data_ptr(), ws.data_ptr(), loss.data_ptr(), _stream())
-        ctx.r = r
-        ctx.dims = (B, Cc, H, W)
-        ctx.save_for_backward(pred, gt)
-        return pred, loss
-
-    @staticmethod
-    def backward(ctx, dpred, dloss):
-        pred, gt = ctx.saved_tensors
-        B, Cc, H, W = ctx.dims
-        r = ctx.r
-        if dpred is not None:
-            dpred = dpred.contiguous()
-        if dloss is not None:
-            dloss = dloss.contiguous()
-        dlr = torch.empty((B, H, W, Cc * r * r), device=pred.device, dtype=torch.float32)
-        lib.call(lib._head_mse_bwd, "bmc_head_mse_bwd", dpred.data_ptr() if dpred is not None else None, pred.data_ptr(),
-                 gt.data_ptr(), gt.stride(0), dloss.data_ptr() if dloss is not None else None, B, Cc, H, W, r,
-                 dlr.data_ptr(), _stream())
-        return dlr, None, None, None
-
-
-def head_mse(xo, base, gt, r):
-    return HeadMseFn.apply(xo, base, gt, r)
-
-
-class HeadResizeMseFn(torch.autograd.Function):
-    """(pred, mse) = head + bicubic resize to the ground truth's size + nn.MSELoss (train.py:227-233) in one pass
-    (bmc_head_resize_mse_fwd): pred is bit for bit ops.head's, the resized prediction is never stored.  Saved for backward:
-    diff = resized - gt only; bmc_head_resize_mse_bwd folds its transposed resize into the pixel-unshuffle of the gradient
-    arriving from the next window.  Where no backward can follow (torch.no_grad()) diff is not allocated either."""
-
-    @staticmethod
-    def forward(ctx, xo, base, gt, r):
-        _need_gpu(xo)
-        xo = xo.contiguous()
-        B, H, W, CC = xo.shape
-        Cc = CC // (r * r)
-        if gt.dim() != 4 or tuple(gt.shape[:2]) != (B, Cc) or not gt.is_cuda or gt.dtype != torch.float32:
-            raise RuntimeError("head_resize_mse: ground truth must be a float32 GPU tensor [B, C, gh, gw] of the prediction's "
-                               "batch and channels")
+        f32_gpu = gt.is_cuda and gt.dtype == torch.float32
+        if kind is None and not resize:
+            if not f32_gpu or tuple(gt.shape) != (B, Cc, H * r, W * r):
+                raise RuntimeError("head_mse: ground truth must be a float32 GPU tensor of the prediction's shape")
+        elif not f32_gpu or gt.dim() != 4 or tuple(gt.shape[:2]) != (B, Cc):
+            raise RuntimeError("%s: ground truth must be a float32 GPU tensor [B, C, gh, gw] of the prediction's batch and channels"
+                               % ("head_resize_mse" if kind is None else "head_loss"))
         gh, gw = int(gt.shape[2]), int(gt.shape[3])
         if gt.stride()[1:] != (gh * gw, gw, 1):
             gt = gt.contiguous()
-        pred = torch.empty((B, Cc, H * r, W * r), device=xo.device, dtype=torch.float32)
-        ws = torch.empty(2048, device=xo.device, dtype=torch.float32)
-        loss = torch.empty((), device=xo.device, dtype=torch.float32)
-        # forward() of a Function runs with grad mode off, so whether a backward can follow is what needs_input_grad says
-        diff = torch.empty((B, Cc, gh, gw), device=xo.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
-        sb, sc, sy, sx = base.stride()
-        lib.call(lib._head_resize_mse_fwd, "bmc_head_resize_mse_fwd", xo.data_ptr(), B, Cc, H, W, r, base.data_ptr(), sb, sc,
-                 sy, sx, gt.data_ptr(), gt.stride(0), gh, gw, pred.data_ptr(), diff.data_ptr() if diff is not None else None,
-                 ws.data_ptr(), loss.data_ptr(), _stream())
-        ctx.r = r
-        ctx.dims = (B, Cc, H, W, gh, gw)
-        if diff is not None:
-            ctx.save_for_backward(diff)
-        return pred, loss
-
-    @staticmethod
-    def backward(ctx, dpred, dloss):
-        (diff,) = ctx.saved_tensors
-        B, Cc, H, W, gh, gw = ctx.dims
-        r = ctx.r
-        if dpred is not None:
-            dpred = dpred.contiguous()
-        if dloss is not None:
-            dloss = dloss.contiguous()
-        dlr = torch.empty((B, H, W, Cc * r * r), device=diff.device, dtype=torch.float32)
-        lib.call(lib._head_resize_mse_bwd, "bmc_head_resize_mse_bwd", dpred.data_ptr() if dpred is not None else None,
-                 diff.data_ptr(), dloss.data_ptr() if dloss is not None else None, B, Cc, H, W, r, gh, gw, dlr.data_ptr(),
-                 _stream())
-        return dlr, None, None, None
-
-
-def head_resize_mse(xo, base, gt, r):
-    """xo NHWC [B,H,W,C r r], base [B,C,H,W] (any strides), gt [B,C,gh,gw] of any size -> (pred [B,C,rH,rW], mse)."""
-    return HeadResizeMseFn.apply(xo, base, gt, r)
-
-
-class HeadLossFn(torch.autograd.Function):
-    """(pred, loss) = head + a robust loss (bmc_hip.losses: L1, Huber, Charbonnier) against a ground truth of either size in
-    one pass (bmc_head_loss_fwd): pred is bit for bit ops.head's.  A ground truth of another size is compared with the bicubic-
-    resized prediction, which is never stored; saved for backward is then d = resized - gt alone (rho' is applied while
-    bmc_head_loss_bwd gathers), and at the prediction's own size pred and gt, nothing new.  Where no backward can follow
-    (torch.no_grad()) nothing of the ground truth's size is allocated."""
-
-    @staticmethod
-    def forward(ctx, xo, base, gt, r, kind, param):
-        _need_gpu(xo)
-        xo = xo.contiguous()
-        B, H, W, CC = xo.shape
-        Cc = CC // (r * r)
-        if gt.dim() != 4 or tuple(gt.shape[:2]) != (B, Cc) or not gt.is_cuda or gt.dtype != torch.float32:
-            raise RuntimeError("head_loss: ground truth must be a float32 GPU tensor [B, C, gh, gw] of the prediction's batch "
-                               "and channels")
-        gh, gw = int(gt.shape[2]), int(gt.shape[3])
-        if gt.stride()[1:] != (gh * gw, gw, 1):
-            gt = gt.contiguous()
-        resize = (gh, gw) != (H * r, W * r)
+        if resize is None:
+            resize = (gh, gw) != (H * r, W * r)
         pred = torch.empty((B, Cc, H * r, W * r), device=xo.device, dtype=torch.float32)
         ws = torch.empty(2048, device=xo.device, dtype=torch.float32)
         loss = torch.empty((), device=xo.device, dtype=torch.float32)
         # forward() of a Function runs with grad mode off, so whether a backward can follow is what needs_input_grad says
         d = torch.empty((B, Cc, gh, gw), device=xo.device, dtype=torch.float32) if resize and ctx.needs_input_grad[0] else None
         sb, sc, sy, sx = base.stride()
-        lib.call(loss_lib._head_loss_fwd, "bmc_head_loss_fwd", xo.data_ptr(), B, Cc, H, W, r, base.data_ptr(), sb, sc, sy, sx,
-                 gt.data_ptr(), gt.stride(0), gh, gw, pred.data_ptr(), d.data_ptr() if d is not None else None, ws.data_ptr(),
-                 loss.data_ptr(), kind, param, _stream())
-        ctx.r, ctx.kind, ctx.param = r, kind, param
-        ctx.dims = (B, Cc, H, W, gh, gw)
-        ctx.resize = resize
-        if resize:
-            if d is not None:
-                ctx.save_for_backward(d)
+        ins = (xo.data_ptr(), B, Cc, H, W, r, base.data_ptr(), sb, sc, sy, sx, gt.data_ptr(), gt.stride(0))
+        outs = (pred.data_ptr(), d.data_ptr() if d is not None else None, ws.data_ptr(), loss.data_ptr())
+        if kind is not None:
+            lib.call(loss_lib._head_loss_fwd, "bmc_head_loss_fwd", *ins, gh, gw, *outs, kind, param, _stream())
+        elif resize:
+            lib.call(lib._head_resize_mse_fwd, "bmc_head_resize_mse_fwd", *ins, gh, gw, *outs, _stream())
         else:
+            lib.call(lib._head_mse_fwd, "bmc_head_mse_fwd", *ins, outs[0], *outs[2:], _stream())
+        ctx.r, ctx.kind, ctx.param, ctx.resize = r, kind, param, resize
+        ctx.dims = (B, Cc, H, W, gh, gw)
+        if not resize:
             ctx.save_for_backward(pred, gt)
+        elif d is not None:
+            ctx.save_for_backward(d)
         return pred, loss
 
     @staticmethod
@@ -2188,19 +2102,35 @@ class HeadLossFn(torch.autograd.Function):
         if dloss is not None:
             dloss = dloss.contiguous()
         ptr = lambda t: t.data_ptr() if t is not None else None
-        dev = d.device if ctx.resize else pred.device
-        dlr = torch.empty((B, H, W, Cc * r * r), device=dev, dtype=torch.float32)
-        lib.call(loss_lib._head_loss_bwd, "bmc_head_loss_bwd", ptr(dpred), ptr(d), ptr(pred), ptr(gt),
-                 gt.stride(0) if gt is not None else 0, ptr(dloss), B, Cc, H, W, r, gh, gw, ctx.kind, ctx.param, dlr.data_ptr(),
-                 _stream())
-        return dlr, None, None, None, None, None
+        dlr = torch.empty((B, H, W, Cc * r * r), device=(d if ctx.resize else pred).device, dtype=torch.float32)
+        if ctx.kind is not None:
+            lib.call(loss_lib._head_loss_bwd, "bmc_head_loss_bwd", ptr(dpred), ptr(d), ptr(pred), ptr(gt),
+                     gt.stride(0) if gt is not None else 0, ptr(dloss), B, Cc, H, W, r, gh, gw, ctx.kind, ctx.param, dlr.data_ptr(),
+                     _stream())
+        elif ctx.resize:
+            lib.call(lib._head_resize_mse_bwd, "bmc_head_resize_mse_bwd", ptr(dpred), ptr(d), ptr(dloss), B, Cc, H, W, r, gh, gw,
+                     dlr.data_ptr(), _stream())
+        else:
+            lib.call(lib._head_mse_bwd, "bmc_head_mse_bwd", ptr(dpred), ptr(pred), ptr(gt), gt.stride(0), ptr(dloss), B, Cc, H, W,
+                     r, dlr.data_ptr(), _stream())
+        return dlr, None, None, None, None, None, None
+
+
+def head_mse(xo, base, gt, r):
+    """(pred, mse) for a ground truth of the prediction's shape."""
+    return FusedHeadFn.apply(xo, base, gt, r, None, None, False)
+
+
+def head_resize_mse(xo, base, gt, r):
+    """xo NHWC [B,H,W,C r r], base [B,C,H,W] (any strides), gt [B,C,gh,gw] of any size -> (pred [B,C,rH,rW], mse)."""
+    return FusedHeadFn.apply(xo, base, gt, r, None, None, True)
 
 
 def head_loss(xo, base, gt, r, loss=None):
     """What the models' forward_loss calls: xo NHWC [B,H,W,C r r], base [B,C,H,W] (any strides), gt [B,C,gh,gw] of any size
     (a batch stride is allowed) -> (pred [B,C,rH,rW], loss).  loss None is nn.MSELoss: head_mse for a ground truth of the
     prediction's size, head_resize_mse otherwise.  loss an instance of bmc_hip.losses.L1 / Huber / Charbonnier: the same head
-    with that loss, at either size (HeadLossFn); anything else is refused -- a plain callable belongs to the unfused chain."""
+    with that loss, at either size; anything else is refused -- a plain callable belongs to the unfused chain."""
     if loss is None:
         if tuple(gt.shape[-2:]) == (xo.shape[1] * r, xo.shape[2] * r):
             return head_mse(xo, base, gt, r)
@@ -2209,7 +2139,7 @@ def head_loss(xo, base, gt, r, loss=None):
     if not losses.is_fusable(loss):
         raise TypeError("head_loss: %r is not a bmc_hip.losses object; the fused head evaluates L1, Huber and Charbonnier only"
                         % (loss,))
-    return HeadLossFn.apply(xo, base, gt, r, int(loss.kind), float(loss.param))
+    return FusedHeadFn.apply(xo, base, gt, r, int(loss.kind), float(loss.param), None)
 
 
 _ssim_lib = None      # bmc_hip.ssim_lib, imported by the first structural loss: a run without one never loads it

@@ -165,69 +165,25 @@ template <class V> std::string number(V v) {
     return buf;
 }
 
-std::string abi_text() {
-    std::string out;
+/* <name>(): the text of one header's three lists, made once.  A header without structs or constants passes BMC_ABI_NONE. */
+#define BMC_ABI_NONE(X)
 #define BMC_ABI_PUT_FN(f) out += "fn " #f " " + signature<decltype(&f)>::text() + "\n";
 #define BMC_ABI_PUT_STRUCT(S, ...) put_struct<S>(out);
 #define BMC_ABI_PUT_CONST(c) out += "const " #c " " + code<decltype(c)>() + " " + number(c) + "\n";
-    BMC_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
-    BMC_ABI_STRUCTS(BMC_ABI_PUT_STRUCT)
-    BMC_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
-    return out;
-}
-
-std::string losses_abi_text() {
-    std::string out;
-    BMC_LOSSES_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
-    BMC_LOSSES_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
-    return out;
-}
-
-std::string quality_abi_text() {
-    std::string out;
-    BMC_QUALITY_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
-    BMC_QUALITY_ABI_STRUCTS(BMC_ABI_PUT_STRUCT)
-    BMC_QUALITY_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
-    return out;
-}
-
-std::string ema_abi_text() {
-    std::string out;
-    BMC_EMA_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
-    BMC_EMA_ABI_STRUCTS(BMC_ABI_PUT_STRUCT)
-    return out;
-}
-
-std::string ssim_abi_text() {
-    std::string out;
-    BMC_SSIM_ABI_FUNCTIONS(BMC_ABI_PUT_FN)
-    BMC_SSIM_ABI_CONSTANTS(BMC_ABI_PUT_CONST)
-    return out;
-}
+#define BMC_ABI_TEXT(name, FUNCTIONS, STRUCTS, CONSTANTS)                                   \
+    extern "C" const char* name(void) {                                                     \
+        static const std::string text = [] {                                                \
+            std::string out;                                                                \
+            FUNCTIONS(BMC_ABI_PUT_FN) STRUCTS(BMC_ABI_PUT_STRUCT) CONSTANTS(BMC_ABI_PUT_CONST) \
+            return out;                                                                     \
+        }();                                                                                \
+        return text.c_str();                                                                \
+    }
 
 }  // namespace
 
-extern "C" const char* bmc_ssim_abi(void) {
-    static const std::string text = ssim_abi_text();
-    return text.c_str();
-}
-
-extern "C" const char* bmc_ema_abi(void) {
-    static const std::string text = ema_abi_text();
-    return text.c_str();
-}
-
-extern "C" const char* bmc_quality_abi(void) {
-    static const std::string text = quality_abi_text();
-    return text.c_str();
-}
-
-extern "C" const char* bmc_losses_abi(void) {
-    static const std::string text = losses_abi_text();
-    return text.c_str();
-}
-
-extern "C" const char* bmc_abi(void) {
-    static const std::string text = abi_text();
-    return text.c_str();
-}
+BMC_ABI_TEXT(bmc_abi, BMC_ABI_FUNCTIONS, BMC_ABI_STRUCTS, BMC_ABI_CONSTANTS)
+BMC_ABI_TEXT(bmc_losses_abi, BMC_LOSSES_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_LOSSES_ABI_CONSTANTS)
+BMC_ABI_TEXT(bmc_quality_abi, BMC_QUALITY_ABI_FUNCTIONS, BMC_QUALITY_ABI_STRUCTS, BMC_QUALITY_ABI_CONSTANTS)
+BMC_ABI_TEXT(bmc_ema_abi, BMC_EMA_ABI_FUNCTIONS, BMC_EMA_ABI_STRUCTS, BMC_ABI_NONE)
+BMC_ABI_TEXT(bmc_ssim_abi, BMC_SSIM_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_SSIM_ABI_CONSTANTS)

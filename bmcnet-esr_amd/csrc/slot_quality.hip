@@ -7,28 +7,21 @@
 //   stats   (nparts, S)            part p of slot s: per channel the squared error of each image, the ground truth's maximum and
 //                                  its minimum over its fixed element set -> stats[s][p][8];
 //   ssim    (tiles, images*2, S)   a workgroup owns TH x TW window positions of one channel of one image: R_c from the slot's
-//                                  parts, the tile and its 6-pixel apron staged in LDS as float32, the five 49-term sums formed
-//                                  separably in double -- a lane owns a column of positions, forms the row sums of the staged rows
-//                                  of its wave's strip one after another and keeps the last seven in registers (no row sums in
-//                                  LDS: doubles for a tile would not fit) -- then S per position and a fixed tree over the tile
-//                                  -> tiles[s][image*2+channel][tile];
+//                                  parts, then the tile body of ssim_k.h (shared with ssim_loss.hip): the tile and its 6-pixel
+//                                  apron staged in LDS as float32, the five 49-term sums formed separably in double, S per
+//                                  position and a fixed tree over the tile -> tiles[s][image*2+channel][tile];
 //   finish  (images*2, S)          the parts and the tile partials added in index order -> the slot's dst.
 // LDS of the ssim launch: two float32 images of (TH+6) x 72 = 21.9 KB per workgroup; a lane reads 4-byte words at consecutive
 // addresses (ds_read_b32: conflict-free at any row stride), and no 8-byte LDS access is on the hot path.
-#include "slot_k.h"
+#include "ssim_k.h"
 #include "bmc_hip_quality.h"
 
 namespace {
 
 constexpr int QT = 1024;                                   // stats: workgroups of 16 waves, as slot_metrics_kernel
-constexpr int WIN = BMC_QUALITY_WIN, AP = WIN - 1;
+static_assert(BMC_QUALITY_WIN == WIN, "the header's window is the shared tile body's");
 constexpr int TH = BMC_QUALITY_TILE_H, TW = BMC_QUALITY_TILE_W;
-constexpr int ST = 256, SW = ST / 64;                      // ssim: 4 waves, each a strip of TH / 4 position rows
-constexpr int STRIP = TH / SW;
-constexpr int LH = TH + AP, LW = TW + AP, LS = 72;         // the staged image: LH rows of LW pixels, LS floats apart
 constexpr int FT = 64;                                     // finish: one wave
-static_assert(TW == 64 && TH % SW == 0 && LS >= LW, "a lane per column of positions, whole strips");
-static_assert(2 * LH * LS * sizeof(float) + 64 <= 65536, "static LDS of the ssim launch");
 
 struct QSlot {
     const float* gt;
@@ -106,14 +99,6 @@ __global__ __launch_bounds__(QT) void quality_stats_kernel(const bmc_slot_t* __r
     }
 }
 
-// the five sums of a window position (or of one of its rows)
-struct Sums {
-    double x, y, xx, yy, xy;
-};
-__device__ __forceinline__ Sums plus(const Sums& a, const Sums& b) {
-    return Sums{a.x + b.x, a.y + b.y, a.xx + b.xx, a.yy + b.yy, a.xy + b.xy};
-}
-
 // grid (tiles, images * 2, S); blockIdx.y = image * 2 + channel
 __global__ __launch_bounds__(ST) void quality_ssim_kernel(const bmc_slot_t* __restrict__ table,
                                                           const bmc_slot_quality_t* __restrict__ quality,
@@ -121,13 +106,12 @@ __global__ __launch_bounds__(ST) void quality_ssim_kernel(const bmc_slot_t* __re
                                                           int gw, int nparts, double range, int tiles_x,
                                                           const double* __restrict__ stats, double* __restrict__ tiles) {
 #pragma clang fp contract(off)      // every float64 operation is rounded on its own, as the contract writes them
-    __shared__ float la[LH * LS], lg[LH * LS];
-    __shared__ double wsum[SW], rng[2];
+    __shared__ SsimTile<TH, TW> t;
+    __shared__ double rng[2];
     const int tile = blockIdx.x, ntiles = gridDim.x, ci = blockIdx.y, s = blockIdx.z, tid = threadIdx.x;
     const int c = ci & 1, img = ci >> 1;
     QSlot q;
     if (!quality_slot(table, quality, s, q)) return;
-    const int ph = gh - AP, pw = gw - AP;                  // window positions of the image
     const int y0 = tile / tiles_x * TH, x0 = tile % tiles_x * TW;      // the tile's first position = its first staged pixel
     if (tid < 64) {                                        // the slot's parts -> max(g[c]) and min(g)
         const double* const o = stats + ((long long)s * nparts + tid) * BMC_QUALITY_STATS_WORDS;
@@ -139,15 +123,7 @@ __global__ __launch_bounds__(ST) void quality_ssim_kernel(const bmc_slot_t* __re
         }
     }
     const long long plane = (long long)gh * gw;
-    const float* const A = (img ? bic : esr) + ((long long)s * 2 + c) * plane;
-    const float* const G = q.gt + c * plane;
-    for (int k = tid; k < LH * LW; k += ST) {              // pixels outside the image: zeros, read by positions outside it only
-        const int r = k / LW, col = k - r * LW, y = y0 + r, x = x0 + col;
-        const bool in = y < gh && x < gw;
-        la[r * LS + col] = in ? gld<float>(A + (long long)y * gw + x) : 0.f;
-        lg[r * LS + col] = in ? gld<float>(G + (long long)y * gw + x) : 0.f;
-    }
-    __syncthreads();
+    t.stage((img ? bic : esr) + ((long long)s * 2 + c) * plane, q.gt + c * plane, y0, x0, gh, gw);     // (its barrier: rng too)
     double* const out = tiles + ((long long)s * 4 + ci) * ntiles + tile;
     const double R = range > 0.0 ? range : rng[0] - rng[1];
     if (R == 0.0) {                                        // (uniform) no defined value: the channel's sum becomes NaN
@@ -155,42 +131,8 @@ __global__ __launch_bounds__(ST) void quality_ssim_kernel(const bmc_slot_t* __re
         return;
     }
     const double C1 = (0.01 * R) * (0.01 * R), C2 = (0.03 * R) * (0.03 * R);
-    const double np = (double)(WIN * WIN), nm1 = (double)(WIN * WIN - 1);
-    const int wave = tid >> 6, lane = tid & 63;
-    const bool col_in = x0 + lane < pw;
-    Sums h[WIN];                                           // the row sums of the last seven staged rows (static indices below)
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < STRIP + AP; ++r) {
-        const float* const ra = la + (wave * STRIP + r) * LS + lane;
-        const float* const rg = lg + (wave * STRIP + r) * LS + lane;
-        Sums t;
-        {
-            const double a = (double)ra[0], g = (double)rg[0];
-            t = Sums{a, g, a * a, g * g, a * g};
-        }
-#pragma unroll
-        for (int k = 1; k < WIN; ++k) {                    // left to right
-            const double a = (double)ra[k], g = (double)rg[k];
-            t = plus(t, Sums{a, g, a * a, g * g, a * g});
-        }
-        h[r % WIN] = t;
-        if (r >= AP) {                                     // position row r - 6 of the strip: its seven rows, top to bottom
-            Sums v = h[(r - AP) % WIN];
-#pragma unroll
-            for (int k = 1; k < WIN; ++k) v = plus(v, h[(r - AP + k) % WIN]);
-            const double ux = v.x / np, uy = v.y / np;
-            const double vx = (v.xx - v.x * v.x / np) / nm1, vy = (v.yy - v.y * v.y / np) / nm1;
-            const double vxy = (v.xy - v.x * v.y / np) / nm1;
-            const double S = ((2.0 * ux * uy + C1) * (2.0 * vxy + C2)) / ((ux * ux + uy * uy + C1) * (vx + vy + C2));
-            const bool in = col_in && y0 + wave * STRIP + (r - AP) < ph;
-            acc += in ? S : 0.0;
-        }
-    }
-    acc = wave_fold(acc, Add());
-    if (lane == 0) wsum[wave] = acc;
-    __syncthreads();
-    if (tid == 0) gst<double>(out, ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+    const double part = t.sum(y0, x0, gh - AP, gw - AP, C1, C2);
+    if (tid == 0) gst<double>(out, part);
 }
 
 // grid (images * 2, S), one wave: the record's four words of (slot, image, channel)

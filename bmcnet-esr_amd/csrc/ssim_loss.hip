@@ -1,6 +1,6 @@
 // The structural training loss 1 - mean SSIM and its gradient: the contract, with every summation order, is in
-// include/bmc_hip_ssim.h.  The forward's tile launch follows slot_quality.hip's ssim launch (same staging, same separable sums,
-// same tree) with a constant data range and one partial per (plane, tile); nothing is shared with that file.
+// include/bmc_hip_ssim.h.  The forward's tile launch is slot_quality.hip's ssim launch with a constant data range and one
+// partial per (plane, tile): the staging, the separable sums, S and the tree are ssim_k.h's, one body for both.
 //
 //   bmc_ssim_loss_fwd   tiles   (planes * ntiles)   TH x TW window positions of one plane -> tiles[plane][tile]
 //                       finish  (1)                 the partials in index order -> loss = 1 - sum / count, float32
@@ -10,19 +10,14 @@
 //                                                   adjacent pixels from eight rows of 7-term row sums -> dx
 // No atomics, no workgroup waits for another, no memset: bit-reproducible.
 // LDS: tiles 2 x (TH + 6) x 72 floats = 21.9 KB; grad 2 x 28 x 44 floats + 3 x 22 x 38 doubles = 29.9 KB.
-#include "slot_k.h"
+#include "ssim_k.h"
 #include "bmc_hip_ssim.h"
 
 namespace {
 
-constexpr int WIN = BMC_SSIM_WIN, AP = WIN - 1;
+static_assert(BMC_SSIM_WIN == WIN, "the header's window is the shared tile body's");
 constexpr int TH = BMC_SSIM_TILE_H, TW = BMC_SSIM_TILE_W;
-constexpr int ST = 256, SW = ST / 64;                      // tiles: 4 waves, each a strip of TH / 4 position rows
-constexpr int STRIP = TH / SW;
-constexpr int LH = TH + AP, LW = TW + AP, LS = 72;         // the staged image: LH rows of LW pixels, LS floats apart
 constexpr int FT = 256;                                    // finish
-static_assert(TW == 64 && TH % SW == 0 && LS >= LW, "a lane per column of positions, whole strips");
-static_assert(2 * LH * LS * sizeof(float) + 64 <= 65536, "static LDS of the tiles launch");
 
 constexpr int PH = BMC_SSIM_BWD_TILE_H, PW = BMC_SSIM_BWD_TILE_W;
 constexpr int BT = 256;                                    // grad: a thread per column and pair of pixel rows
@@ -31,88 +26,19 @@ constexpr int GH = CH + AP, GW = CW + AP;                  // the pixels those p
 static_assert(PW == 32 && PH * PW == 2 * BT, "32 columns, two pixel rows per thread");
 static_assert(2 * GH * GW * sizeof(float) + 3 * CH * CW * sizeof(double) <= 65536, "static LDS of the grad launch");
 
-// the five sums of a window position (or of one of its rows)
-struct Sums {
-    double x, y, xx, yy, xy;
-};
-__device__ __forceinline__ Sums plus(const Sums& a, const Sums& b) {
-    return Sums{a.x + b.x, a.y + b.y, a.xx + b.xx, a.yy + b.yy, a.xy + b.xy};
-}
-// the sums of the seven pixels at a[0..6], g[0..6], left to right
-__device__ __forceinline__ Sums row_sums(const float* a, const float* g) {
-#pragma clang fp contract(off)
-    const double a0 = (double)a[0], g0 = (double)g[0];
-    Sums t{a0, g0, a0 * a0, g0 * g0, a0 * g0};
-#pragma unroll
-    for (int k = 1; k < WIN; ++k) {
-        const double ak = (double)a[k], gk = (double)g[k];
-        t = plus(t, Sums{ak, gk, ak * ak, gk * gk, ak * gk});
-    }
-    return t;
-}
-
-struct Terms {
-    double ux, uy, A1, A2, B1, B2, D, S;
-};
-__device__ __forceinline__ Terms terms(const Sums& v, double C1, double C2) {
-#pragma clang fp contract(off)
-    const double np = (double)(WIN * WIN), nm1 = (double)(WIN * WIN - 1);
-    Terms t;
-    t.ux = v.x / np;
-    t.uy = v.y / np;
-    const double vx = (v.xx - v.x * v.x / np) / nm1, vy = (v.yy - v.y * v.y / np) / nm1;
-    const double vxy = (v.xy - v.x * v.y / np) / nm1;
-    t.A1 = 2.0 * t.ux * t.uy + C1;
-    t.A2 = 2.0 * vxy + C2;
-    t.B1 = t.ux * t.ux + t.uy * t.uy + C1;
-    t.B2 = vx + vy + C2;
-    t.D = t.B1 * t.B2;
-    t.S = (t.A1 * t.A2) / t.D;
-    return t;
-}
-
 // grid (planes * ntiles): workgroup = (plane, tile), tile row-major over the plane's positions
 __global__ __launch_bounds__(ST) void ssim_tiles_kernel(const float* __restrict__ x, const float* __restrict__ y,
                                                         long long y_batch_stride, int C, int h, int w, double range,
                                                         int tiles_x, int ntiles, double* __restrict__ tiles) {
 #pragma clang fp contract(off)      // every float64 operation is rounded on its own, as the contract writes them
-    __shared__ float la[LH * LS], lg[LH * LS];
-    __shared__ double wsum[SW];
-    const int tid = threadIdx.x;
+    __shared__ SsimTile<TH, TW> t;
     const int plane = blockIdx.x / ntiles, tile = blockIdx.x - plane * ntiles;
-    const int ph = h - AP, pw = w - AP;                    // window positions of the image
     const int y0 = tile / tiles_x * TH, x0 = tile % tiles_x * TW;      // the tile's first position = its first staged pixel
     const long long hw = (long long)h * w;
-    const float* const A = x + plane * hw;
-    const float* const G = y + (plane / C) * y_batch_stride + (plane % C) * hw;
-    for (int k = tid; k < LH * LW; k += ST) {              // pixels outside the image: zeros, read by positions outside it only
-        const int r = k / LW, col = k - r * LW, yy = y0 + r, xx = x0 + col;
-        const bool in = yy < h && xx < w;
-        la[r * LS + col] = in ? gld<float>(A + (long long)yy * w + xx) : 0.f;
-        lg[r * LS + col] = in ? gld<float>(G + (long long)yy * w + xx) : 0.f;
-    }
-    __syncthreads();
+    t.stage(x + plane * hw, y + (plane / C) * y_batch_stride + (plane % C) * hw, y0, x0, h, w);
     const double C1 = (0.01 * range) * (0.01 * range), C2 = (0.03 * range) * (0.03 * range);
-    const int wave = tid >> 6, lane = tid & 63;
-    const bool col_in = x0 + lane < pw;
-    Sums hs[WIN];                                          // the row sums of the last seven staged rows (static indices below)
-    double acc = 0.0;
-#pragma unroll
-    for (int r = 0; r < STRIP + AP; ++r) {
-        hs[r % WIN] = row_sums(la + (wave * STRIP + r) * LS + lane, lg + (wave * STRIP + r) * LS + lane);
-        if (r >= AP) {                                     // position row r - 6 of the strip: its seven rows, top to bottom
-            Sums v = hs[(r - AP) % WIN];
-#pragma unroll
-            for (int k = 1; k < WIN; ++k) v = plus(v, hs[(r - AP + k) % WIN]);
-            const double S = terms(v, C1, C2).S;
-            const bool in = col_in && y0 + wave * STRIP + (r - AP) < ph;
-            acc += in ? S : 0.0;
-        }
-    }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if (lane == 0) wsum[wave] = acc;
-    __syncthreads();
-    if (tid == 0) gst<double>(tiles + blockIdx.x, ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3]);
+    const double part = t.sum(y0, x0, h - AP, w - AP, C1, C2);
+    if (threadIdx.x == 0) gst<double>(tiles + blockIdx.x, part);
 }
 
 // one workgroup: the partials, FT at a time, in index order
