@@ -4,6 +4,9 @@
 The scatter runs on the MI355X (bmc_events_to_channels, one float atomic per event, bit-exact with the
 reference including its out-of-range quirk and its in-place reset of the caller's xs/ys).  CPU tensors
 are rejected: there is no CPU fallback."""
+import math
+
+import numpy as np
 import torch
 
 from . import lib, ops
@@ -83,6 +86,116 @@ def get_hot_event_mask(event_rate, idx, max_px=100, min_obvs=5, max_rate=0.8):
     lib.call(lib._hot_pixel_mask, "bmc_hot_pixel_mask", event_rate.data_ptr(), H, W, int(idx > min_obvs),
              max(0, min(int(max_px), H * W)), float(max_rate), mask.data_ptr(), ws.data_ptr(), ops._stream())
     return mask
+
+
+def _noise_columns(who, xs, ys, ts, ps):
+    """The column checks of the noise filter that need no device round trip: types, shapes, lengths, one GPU."""
+    cols = [("xs", xs, torch.int16), ("ys", ys, torch.int16), ("ts", ts, torch.float64)] + ([] if ps is None else [("ps", ps, torch.float64)])
+    for name, t, dtype in cols:
+        if not (torch.is_tensor(t) and t.dtype == dtype and t.dim() == 1 and t.is_contiguous()):
+            raise ValueError(who + "%s must be a contiguous 1-D %s tensor" % (name, str(dtype).replace("torch.", "")))
+        if t.numel() != xs.numel():
+            raise ValueError(who + "%s has %d entries, xs %d" % (name, t.numel(), xs.numel()))
+    if not all(t.is_cuda and t.device == xs.device for _, t, _ in cols):
+        raise ValueError(who + "the columns must be GPU tensors on one device (no CPU fallback in this build)")
+    if xs.numel() >= 1 << 31:
+        raise ValueError(who + "streams of 2^31 events or more are not supported")
+
+
+def _noise_size(who, sensor_size):
+    from . import denoise_lib
+    try:
+        H, W = (int(v) for v in sensor_size)
+    except (TypeError, ValueError):
+        raise ValueError(who + "sensor_size = (H, W)") from None
+    if H < 1 or W < 1 or W > denoise_lib.MAX_W:
+        raise ValueError(who + "sensor_size must be positive and at most %d wide (got %s)" % (denoise_lib.MAX_W, (H, W)))
+    return H, W
+
+
+def _noise_numbers(who, dt, support, names=("dt", "support")):
+    from . import denoise_lib
+    if isinstance(dt, bool) or not isinstance(dt, (int, float, np.integer, np.floating)) or not math.isfinite(dt) or dt < 0:
+        raise ValueError(who + "%s must be a finite number >= 0, in the units of ts (got %r)" % (names[0], dt))
+    if isinstance(support, bool) or not isinstance(support, (int, np.integer)) or not 1 <= support <= denoise_lib.MAX_SUPPORT:
+        raise ValueError(who + "%s must be an integer, 1 <= support <= %d (got %r)" % (names[1], denoise_lib.MAX_SUPPORT, support))
+    return float(dt), int(support)
+
+
+NOISE_CALLS = 0     # calls of bmc_event_denoise so far (tests: one per filtered recording at the door, none per window)
+
+
+def _event_noise(xs, ys, ts, H, W, dt, support, ps=None, keep=True, count=False):
+    """bmc_event_denoise on checked columns, on the current stream, no sync -> (keep or None, ps_out or None, kept or None),
+    kept a 1-element int64 GPU tensor."""
+    global NOISE_CALLS
+    from . import denoise_lib
+    NOISE_CALLS += 1
+    n, dev = xs.numel(), xs.device
+    keep = torch.empty(n, dtype=torch.uint8, device=dev) if keep else None
+    ps_out = None if ps is None else torch.empty_like(ps)
+    kept = torch.empty(1, dtype=torch.int64, device=dev) if count else None
+    scratch = torch.empty(denoise_lib.scratch_bytes(H, W) // 8, dtype=torch.int64, device=dev) if count else None
+    ptr = lambda t: None if t is None else t.data_ptr()
+    lib.call(denoise_lib._event_denoise, "bmc_event_denoise", xs.data_ptr(), ys.data_ptr(), ts.data_ptr(), ptr(ps), n, H, W, dt,
+             support, ptr(keep), ptr(ps_out), ptr(kept), ptr(scratch), ops._stream())
+    return keep, ps_out, kept
+
+
+def event_noise_mask(xs, ys, ts, sensor_size, dt, support=1, ps=None):
+    """The background-activity (nearest-neighbour correlation) filter of one raw event stream, on the GPU (the contract:
+    include/bmc_hip_denoise.h): keep[i] = 1 iff event i is inside the sensor and at least `support` of the eight pixels around
+    it saw their latest earlier event no more than dt before it.  support = 1 is jAER's BackgroundActivityFilter, support > 1
+    its SpatioTemporalCorrelationFilter.  xs, ys int16, ts float64 (finite and non-decreasing: NOT checked here -- the check
+    would wait for the device; check_noise_filter does it), in column order, 1-D contiguous GPU tensors.
+    -> keep (uint8) or, with ps (float64), (keep, ps_out): ps with the dropped events' polarities replaced by +0.0, which every
+    encoder of the library counts as nothing.  One call of bmc_event_denoise on the current stream; nothing waits for it."""
+    who = "event_noise_mask: "
+    _noise_columns(who, xs, ys, ts, ps)
+    H, W = _noise_size(who, sensor_size)
+    dt, support = _noise_numbers(who, dt, support)
+    keep, ps_out, _ = _event_noise(xs, ys, ts, H, W, dt, support, ps)
+    return keep if ps is None else (keep, ps_out)
+
+
+def check_noise_filter(who, noise_filter, columns=None, sensor_size=None):
+    """noise_filter (None, or a dict with exactly the keys ts, dt and, optionally, support) -> None or (ts, dt, support), the
+    arguments of event_noise_mask; ValueError names the bad key, as slots.check_hot_filter.  ts: the stream's float64 timestamp
+    column, finite and non-decreasing (one reduction on its device); dt: finite, >= 0; support: an integer 1 .. 8 (default 1).
+    columns = (xs, ys, ps) and sensor_size = (H, W) of the stream the filter is for: their types and lengths, ts parallel to
+    them on the same GPU, and the width within the kernel's limit."""
+    if noise_filter is None:
+        return None
+    keys = ("ts", "dt", "support")
+    if not isinstance(noise_filter, dict):
+        raise ValueError(who + "noise_filter must be None or a dict with the keys %s (got %r)" % (", ".join(keys), noise_filter))
+    for k in noise_filter:
+        if k not in keys:
+            raise ValueError(who + "noise_filter has an unknown key %r (the keys are %s)" % (k, ", ".join(keys)))
+    for k in keys[:2]:
+        if k not in noise_filter:
+            raise ValueError(who + "noise_filter lacks the key %r" % k)
+    ts = noise_filter["ts"]
+    dt, support = _noise_numbers(who, noise_filter["dt"], noise_filter.get("support", 1), ("noise_filter['dt']", "noise_filter['support']"))
+    if not (torch.is_tensor(ts) and ts.dtype == torch.float64 and ts.dim() == 1 and ts.is_contiguous()):
+        raise ValueError(who + "noise_filter['ts'] must be a contiguous 1-D float64 tensor")
+    if columns is not None:
+        xs, ys, ps = columns
+        _noise_columns(who + "noise_filter: ", xs, ys, ts, ps)
+    if sensor_size is not None:
+        _noise_size(who + "noise_filter: ", sensor_size)
+    if ts.numel() and not bool(torch.isfinite(ts).all() & (ts[1:] >= ts[:-1]).all()):
+        raise ValueError(who + "noise_filter['ts'] must be finite and non-decreasing")
+    return ts, dt, support
+
+
+def filter_noise(who, noise_filter, columns, sensor_size):
+    """(xs, ys, ps) of a recording through its noise_filter -> ((xs, ys, ps_out), events dropped); the caller's ps is not
+    modified.  What open_events(noise_filter=...) and EventTrainSet.add_recording(noise_filter=...) do at the door."""
+    ts, dt, support = check_noise_filter(who, noise_filter, columns, sensor_size)
+    xs, ys, ps = columns
+    _, ps_out, kept = _event_noise(xs, ys, ts, int(sensor_size[0]), int(sensor_size[1]), dt, support, ps, keep=False, count=True)
+    return (xs, ys, ps_out), xs.numel() - int(kept.item())
 
 
 def events_to_channels_batch(xs, ys, ps, offsets, sensor_size=(180, 240), mutate=True):

@@ -18,6 +18,7 @@
 #include "bmc_hip_quality.h"
 #include "bmc_hip_ema.h"
 #include "bmc_hip_ssim.h"
+#include "bmc_hip_denoise.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -99,6 +100,12 @@
 #define BMC_SSIM_ABI_FUNCTIONS(X) X(bmc_ssim_loss_fwd) X(bmc_ssim_loss_bwd) X(bmc_ssim_abi)
 #define BMC_SSIM_ABI_CONSTANTS(X) \
     X(BMC_SSIM_WIN) X(BMC_SSIM_TILE_H) X(BMC_SSIM_TILE_W) X(BMC_SSIM_BWD_TILE_H) X(BMC_SSIM_BWD_TILE_W)
+
+/* include/bmc_hip_denoise.h, the companion header of the event noise filter: likewise, bmc_denoise_abi() (bmc_hip/denoise_lib.py
+ * binds from it; tests/test_event_denoise_cpu.py compares the lists with that header's text). */
+#define BMC_DENOISE_ABI_FUNCTIONS(X) \
+    X(bmc_event_denoise_band_rows) X(bmc_event_denoise_scratch_bytes) X(bmc_event_denoise) X(bmc_denoise_abi)
+#define BMC_DENOISE_ABI_CONSTANTS(X) X(BMC_DENOISE_STEP) X(BMC_DENOISE_LDS_WORDS) X(BMC_DENOISE_MAX_W)
 
 namespace {
 
@@ -187,3 +194,4 @@ BMC_ABI_TEXT(bmc_losses_abi, BMC_LOSSES_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_LOSSES_
 BMC_ABI_TEXT(bmc_quality_abi, BMC_QUALITY_ABI_FUNCTIONS, BMC_QUALITY_ABI_STRUCTS, BMC_QUALITY_ABI_CONSTANTS)
 BMC_ABI_TEXT(bmc_ema_abi, BMC_EMA_ABI_FUNCTIONS, BMC_EMA_ABI_STRUCTS, BMC_ABI_NONE)
 BMC_ABI_TEXT(bmc_ssim_abi, BMC_SSIM_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_SSIM_ABI_CONSTANTS)
+BMC_ABI_TEXT(bmc_denoise_abi, BMC_DENOISE_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_DENOISE_ABI_CONSTANTS)

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from bmc_hip import lib
+from bmc_hip.encodings import filter_noise
 
 MAX_ITEMS = lib.const("BMC_SEQ_MAX_ITEMS")
 MAX_BATCH = 65535
@@ -217,11 +218,15 @@ class EventTrainSet:
         self._pinned, self._events, self._table, self._k = None, [None] * self.RING, None, 0
 
     # ------------------------------------------------------------------ recordings
-    def add_recording(self, lr, gt, lr_index, gt_index, lr_size, gt_size):
+    def add_recording(self, lr, gt, lr_index, gt_index, lr_size, gt_size, noise_filter=None):
         """One recording -> its number.  lr, gt = (xs, ys, ps): 1-D int16, int16, float64 GPU tensors, polarities -1 / 0 / +1;
         lr_index, gt_index [length,2] integer tables on the host (bmc_hip.encodings.event_window_indices gives the reference's);
         every range is checked here against the column lengths: the kernel trusts the table.  All recordings share one pair
-        of sizes; a set with crop takes any sizes the patch fits."""
+        of sizes; a set with crop takes any sizes the patch fits.
+        noise_filter=dict(ts=, dt=, support=) (bmc_hip.encodings.check_noise_filter): the background-activity filter of
+        include/bmc_hip_denoise.h runs once, here, over the whole LR stream, and the set holds the LR polarity column with the
+        dropped events given weight +0.0 -- the recording trains as one added with (xs, ys, ps * keep); the caller's tensors
+        are not modified, the ground truth is not filtered, noise_dropped() tells the count."""
         who = "EventTrainSet.add_recording: "
         for name, cols in (("lr", lr), ("gt", gt)):
             if not (isinstance(cols, (tuple, list)) and len(cols) == 3 and all(torch.is_tensor(t) for t in cols)):
@@ -260,10 +265,19 @@ class EventTrainSet:
         for name, ps in (("lr", lr[2]), ("gt", gt[2])):
             if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
                 raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
+        dropped = None
+        if noise_filter is not None:
+            lr, dropped = filter_noise(who, noise_filter, tuple(lr), (H, W))
+            cols = tuple(lr) + tuple(gt)
         self._size, self._device = (H, W, gh, gw), cols[0].device
-        self._recs.append(dict(cols=cols, ptrs=[t.data_ptr() for t in cols], lr_index=lr_index, gt_index=gt_index, size=(H, W, gh, gw)))
+        self._recs.append(dict(cols=cols, ptrs=[t.data_ptr() for t in cols], lr_index=lr_index, gt_index=gt_index, size=(H, W, gh, gw),
+                               noise_dropped=dropped))
         self._ends.append(len(self) + (len(lr_index) - self.L) // self.step_size + 1)
         return len(self._recs) - 1
+
+    def noise_dropped(self, recording):
+        """Events the noise filter dropped from the recording's LR stream; None for one added without noise_filter."""
+        return self._recs[recording]["noise_dropped"]
 
     def __len__(self):
         return self._ends[-1] if self._ends else 0

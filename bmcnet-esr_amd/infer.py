@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from bmc_hip import slots
-from bmc_hip.encodings import event_block_spans
+from bmc_hip.encodings import event_block_spans, filter_noise
 from bmc_hip.slots import check_group_size, check_hot_filter
 from infer_parts import EventStream, HotFilter, Input, KeptPredictions, Metrics, Pictures, Quality, VoxelGrids
 
@@ -397,7 +397,7 @@ class MultiStreamSR:
         return h
 
     def open_events(self, lr, gt=None, lr_index=None, gt_index=None, lr_size=None, gt_size=None, event_capacity=None,
-                    window_event_capacity=None, lr_ts=None, spans=None):
+                    window_event_capacity=None, lr_ts=None, spans=None, noise_filter=None):
         """Queue one event-backed recording -> handle.  lr, gt = (xs, ys, ps): the raw dataset columns of the LR and the
         ground-truth stream (1-D int16, int16, float64 GPU tensors; polarities -1 / 0 / +1); lr_index, gt_index [L,2]
         (integers, on the host): item j is LR events [lr_index[j,0], lr_index[j,1]) and ground-truth events [gt_index[j,0],
@@ -409,7 +409,14 @@ class MultiStreamSR:
         gt = gt_index = gt_size = None (all three or none): a recording without ground truth (no metrics).
         lr_ts (event_times): the recording's float64 timestamp column, parallel to lr[0], on the GPU or the host -> the span
         of every item (bmc_hip.encodings.event_block_spans) and float64 sr_ts on the sensor's clock; or spans [L,2] directly
-        (not both)."""
+        (not both).
+        noise_filter=dict(ts=, dt=, support=) (bmc_hip.encodings.check_noise_filter; a session needs no event_times for it, and
+        lr_ts / spans keep their own rules): the background-activity filter of include/bmc_hip_denoise.h runs ONCE, here, over the
+        whole LR stream -- nothing is added to a window -- and the recording holds the LR polarity column with the dropped events
+        given weight +0.0: by construction it equals open_events on (xs, ys, ps * keep).  The caller's tensors are not modified;
+        lr_index, capacities and spans are untouched; the ground truth is not filtered; results() gains noise_events, the events
+        dropped.  With hot_filter the hot-pixel filter observes the filtered column: a dropped event that is the last of its
+        pixel in an item gives observation 0."""
         who = "MultiStreamSR.open_events: "
         self._stream.check_capacities(self, "open_events", event_capacity, window_event_capacity)
         if lr_index is None or lr_size is None:
@@ -471,8 +478,13 @@ class MultiStreamSR:
         for name, ps in (("lr", lr[2]), ("gt", gt[2] if has_gt else None))[:1 + has_gt]:
             if not bool(((ps == 1) | (ps == -1) | (ps == 0)).all()):
                 raise ValueError(who + "%s polarities must be -1, 0 or +1 (counts are integers)" % name)
+        dropped = None
+        if noise_filter is not None:
+            lr, dropped = filter_noise(who, noise_filter, tuple(lr), (H, W))
         self._set_size("open_events", H, W, gh, gw)
         rec = {"lr": tuple(lr), "lr_index": lr_index}
+        if dropped is not None:
+            rec["noise_events"] = dropped
         if has_gt:
             rec.update(gt=tuple(gt), gt_index=gt_index)
         return self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
@@ -490,7 +502,7 @@ class MultiStreamSR:
 
     def results(self, handle):
         """-> dict(time=[...] per window done so far, and what the session's parts add: esr_mse, bicubic_mse (a recording with
-        ground truth; with quality also esr_psnr, esr_ssim, bicubic_psnr, bicubic_ssim); hot_pixels, hot_mask (hot_filter, event-backed recordings); predictions; images (render); voxels; sr_events,
+        ground truth; with quality also esr_psnr, esr_ssim, bicubic_psnr, bicubic_ssim); hot_pixels, hot_mask (hot_filter, event-backed recordings); noise_events (a recording opened with noise_filter); predictions; images (render); voxels; sr_events,
         sr_index, sr_ts (emit_events, event_times)).  Raises RuntimeError when the windows emitted more events than the recording's
         event_capacity, or (event_times) one window more than its window_event_capacity (the message names the capacity needed)."""
         r = self._recs[handle]
@@ -500,6 +512,8 @@ class MultiStreamSR:
         out = {"time": [self._steps[k][0].elapsed_time(self._steps[k][1]) for k in r["steps"]]}
         for p in self.parts:
             p.results(self, out, r, done, handle)
+        if "noise_events" in r:
+            out["noise_events"] = r["noise_events"]
         return out
 
     # ---------------------------------------------------------------- windows

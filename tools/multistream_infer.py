@@ -17,6 +17,10 @@ stamps (microseconds around 1e9, one frame every 33 333 us): float64 times on th
 (hot_filter=dict(max_px=100, min_obvs=5, max_rate=0.8), the reference's defaults) and off, --runs alternating runs each in this
 process (windows/s: the median, and every run), and the bmc_slot_hot_update call alone (events around 20 calls on the session's
 last table).
+--noise-filter DT[:K] (implies --events) adds, per configuration, the event-backed session on recordings with a known share of
+uniform noise events (a drifting bar, one second long, 20 % noise) opened with noise_filter=dict(ts=, dt=DT, support=K) and without,
+--runs alternating runs each: the share of the LR events the filter dropped next to the share that is noise, the mean esr_mse of
+both, and ms per window and windows/s of both (the filter runs once per recording at open_events: nothing enters a window).
 --render DIR [--render-kinds lr,bicubic,esr,gt] adds, per configuration, the frame-backed session with the event-count images on
 (render=kinds): its latency and windows/s, one bmc_slot_render call alone per kind (both kernels, events around 20 calls on the
 session's last table), and writes the images of the first such session as DIR/<recording>/event_img/<kind dir>/%09d.png with the
@@ -38,7 +42,7 @@ last table and prediction) and the means of esr_psnr, esr_ssim, bicubic_psnr and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
-                                  [--hot-filter] [--runs 3]
+                                  [--hot-filter] [--noise-filter DT[:K]] [--runs 3]
                                   [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
                                   [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]
                                   [--self-ensemble K] [--plain-weights NPZ] [--quality [RANGE]]"""
@@ -81,6 +85,53 @@ def event_recording(L, H, W, seed):
                      torch.from_numpy(rng.choice([-1.0, 1.0], n))))
     lr_index, gt_index = event_window_indices(np.sort(rng.uniform(0, 1, n_lr)), np.sort(rng.uniform(0, 1, n_gt)), 2048, 1024, 4)
     return cols[0], cols[1], lr_index, gt_index, (H, W), (4 * H, 4 * W)
+
+
+NOISE_SHARE = 0.2
+
+
+def noisy_event_recording(L, H, W, seed):
+    """event_recording with a structured LR stream on a clock: a bar two pixels wide crosses the sensor once in one second, and a
+    known share NOISE_SHARE of the events is uniform noise instead -> the arguments of open_events, then the float64 timestamp
+    column and the number of noise events."""
+    import numpy as np
+    from bmc_hip.encodings import event_window_indices
+    rng = np.random.default_rng(seed)
+    n_lr = 1024 * L + 1
+    n_gt = 16 * n_lr
+    ts = np.sort(rng.uniform(0, 1, n_lr))
+    noise = rng.random(n_lr) < NOISE_SHARE
+    bar = np.minimum(np.floor(ts * max(W - 1, 1)).astype(np.int64) + rng.integers(0, 2, n_lr), W - 1)
+    lr = (torch.from_numpy(np.where(noise, rng.integers(0, W, n_lr), bar).astype(np.int16)),
+          torch.from_numpy(rng.integers(0, H, n_lr).astype(np.int16)), torch.from_numpy(rng.choice([-1.0, 1.0], n_lr)))
+    gt = (torch.from_numpy(rng.integers(0, 4 * W, n_gt).astype(np.int16)), torch.from_numpy(rng.integers(0, 4 * H, n_gt).astype(np.int16)),
+          torch.from_numpy(rng.choice([-1.0, 1.0], n_gt)))
+    lr_index, gt_index = event_window_indices(ts, np.sort(rng.uniform(0, 1, n_gt)), 2048, 1024, 4)
+    return lr, gt, lr_index, gt_index, (H, W), (4 * H, 4 * W), torch.from_numpy(ts), int(noise.sum())
+
+
+def noise_session(m, recs, S, graph, warmup, windows, noise_filter):
+    """The event-backed session on noisy_event_recording()s with open_events(noise_filter=dict(ts=, dt=, support=)) (noise_filter =
+    (dt, support)) or without (None) -> median ms per window of the first recording, windows / s, the mean esr_mse of the timed
+    windows, the share of the LR events the filter dropped (None without it)."""
+    dev = next(m.parameters()).device
+    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN)
+    hs = []
+    for r in recs[:S]:
+        nf = None if noise_filter is None else dict(ts=r[6].to(dev), dt=noise_filter[0], support=noise_filter[1])
+        hs.append(ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:6], noise_filter=nf))
+    for _ in range(warmup):
+        ms.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(windows):
+        ms.step()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    res = [ms.results(h) for h in hs]
+    mse = statistics.mean(v for r in res for v in r["esr_mse"][warmup:])
+    dropped = None if noise_filter is None else sum(r["noise_events"] for r in res) / sum(r[0][0].numel() for r in recs[:S])
+    return statistics.median(res[0]["time"][warmup:]), S * windows / wall, mse, dropped
 
 
 def alone(call, reps=20):
@@ -251,7 +302,11 @@ def parse_args(argv=None):
     ap.add_argument("--events", action="store_true")
     ap.add_argument("--hot-filter", action="store_true",
                     help="implies --events: the event-backed session with the hot-pixel filter on and off, alternating runs")
-    ap.add_argument("--runs", type=int, default=3, help="with --hot-filter / --voxel-bins: alternating runs of each")
+    ap.add_argument("--noise-filter", default=None, metavar="DT[:K]",
+                    help="implies --events: the event-backed session on recordings with a known share of uniform noise events, with "
+                         "open_events(noise_filter=dict(ts=, dt=DT, support=K)) (DT in seconds of a one-second recording; K = 1) "
+                         "and without, alternating runs: the share of events dropped and esr_mse of both")
+    ap.add_argument("--runs", type=int, default=3, help="with --hot-filter / --noise-filter / --voxel-bins: alternating runs of each")
     ap.add_argument("--emit-events", action="store_true")
     ap.add_argument("--event-times", action="store_true",
                     help="with --emit-events: the timed, time-ordered stream (MultiStreamSR(event_times='linear'))")
@@ -297,7 +352,14 @@ def parse_args(argv=None):
             ap.error(str(e))
     if a.sensor_clock:
         a.emit_events = a.event_times = True
-    if a.hot_filter:
+    if a.noise_filter is not None:
+        from bmc_hip.encodings import check_noise_filter
+        dt, _, k = a.noise_filter.partition(":")
+        try:
+            a.noise_filter = check_noise_filter("--noise-filter: ", dict(ts=torch.zeros(0, dtype=torch.float64), dt=float(dt), support=int(k or 1)))[1:]
+        except ValueError as e:
+            ap.error(str(e))
+    if a.hot_filter or a.noise_filter is not None:
         a.events = True
     if a.event_times and not a.emit_events:
         ap.error("--event-times needs --emit-events")
@@ -329,6 +391,7 @@ def main():
         recs = [(torch.poisson(torch.full((L, 2, H, W), 0.284), generator=g).to(dev),
                  torch.poisson(torch.full((L, 2, 4 * H, 4 * W), 0.1), generator=g).to(dev)) for _ in range(max(slots))]
         erecs = [event_recording(L, H, W, H * W + k) for k in range(max(slots))] if a.events else None
+        nrecs = [noisy_event_recording(L, H, W, 3 * H * W + k) for k in range(max(slots))] if a.noise_filter is not None else None
         if a.resident_windows:
             r = event_recording(a.resident_windows + SEQN - 1, H, W, 1)
             r = (tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1])) + r[2:]
@@ -371,6 +434,22 @@ def main():
                                      windows_per_s_filter_off_runs=[round(r[1], 1) for r in off],
                                      hot_update_alone_ms=round(upd, 4), hot_update_share=round(upd / lat, 4),
                                      resident_bytes=on[-1][3]))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.noise_filter is not None:
+                    off, on = [], []
+                    for _ in range(a.runs):
+                        off.append(noise_session(m, nrecs, S, graph, a.warmup, a.windows, None))
+                        on.append(noise_session(m, nrecs, S, graph, a.warmup, a.windows, a.noise_filter))
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(events, noise filter)", slots=S, events=True,
+                                     noise_filter=dict(dt=a.noise_filter[0], support=a.noise_filter[1]),
+                                     noise_share=round(sum(r[7] for r in nrecs[:S]) / sum(r[0][0].numel() for r in nrecs[:S]), 4),
+                                     dropped_share=round(on[-1][3], 4), esr_mse=on[-1][2], esr_mse_filter_off=off[-1][2],
+                                     ms_per_window=round(statistics.median(r[0] for r in on), 3),
+                                     ms_per_window_filter_off=round(statistics.median(r[0] for r in off), 3),
+                                     ms_per_window_runs=[round(r[0], 3) for r in on],
+                                     ms_per_window_filter_off_runs=[round(r[0], 3) for r in off],
+                                     windows_per_s=round(statistics.median(r[1] for r in on), 1),
+                                     windows_per_s_filter_off=round(statistics.median(r[1] for r in off), 1)))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.render is not None:
                     lat, wps, alone, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, render=a.render_kinds,

@@ -32,6 +32,10 @@ too.  Validation stays on full frames.
 --transpose [P]: with --crop, "Transpose" joins the augmentation at probability P (0.5): a sample that draws it is the patch of
 its transposed frames, cut in the same launch -- with --augment's flips, all 8 orientations of a patch.  It implies no flips;
 the patch must fit every recording both ways.  Validation stays on untransposed full frames.
+--denoise DT[:K]: every training recording is added with noise_filter=dict(ts=its LR timestamps, dt=DT, support=K) (K = 1): the
+background-activity filter of include/bmc_hip_denoise.h runs once per recording, on the GPU, and the LR events it drops train with
+weight zero; the events dropped are printed.  DT is in the units of the recordings' timestamps.  The held-out recording of
+--valid-every is filtered too; the ground truth never is.
 --valid-every N: the last recording is held out of training; after every N steps train_step.valid_step (the reference's _valid
 loop: eval mode, no gradients, the same loss) runs over its sequences in order and `valid_loss`, their mean, is printed.
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
@@ -54,7 +58,7 @@ import numpy as np
 import torch
 
 from bmc_hip import losses
-from bmc_hip.encodings import event_window_indices
+from bmc_hip.encodings import check_noise_filter, event_window_indices
 from event_dataset import EventTrainSet
 from models.BMCNet import BMCNet
 from train_step import bptt_step, valid_step
@@ -77,10 +81,14 @@ def synthetic_recording(items, H, W, scale, window, sliding, seed, gt_size=None)
     return rec
 
 
-def add(ts, rec, dev, window, sliding, scale):
+def add(ts, rec, dev, window, sliding, scale, denoise=None):
     lr_index, gt_index = event_window_indices(rec["lr_ts"], rec["gt_ts"], window, sliding, scale)
     cols = lambda side: tuple(torch.from_numpy(np.ascontiguousarray(rec["%s_%s" % (side, k)])).to(dev) for k in KEYS[:3])
-    return ts.add_recording(cols("lr"), cols("gt"), lr_index, gt_index, tuple(rec["lr_size"].tolist()), tuple(rec["gt_size"].tolist()))
+    nf = None
+    if denoise is not None:
+        nf = dict(ts=torch.from_numpy(np.ascontiguousarray(rec["lr_ts"], np.float64)).to(dev), dt=denoise[0], support=denoise[1])
+    return ts.add_recording(cols("lr"), cols("gt"), lr_index, gt_index, tuple(rec["lr_size"].tolist()), tuple(rec["gt_size"].tolist()),
+                            noise_filter=nf)
 
 
 def main():
@@ -118,11 +126,20 @@ def main():
     ap.add_argument("--ema", type=float, default=None, metavar="DECAY", help="keep an EMA of the weights inside the step (hip only)")
     ap.add_argument("--ema-warmup", action="store_true", help="decay_t = min(DECAY, t / (t + 9))")
     ap.add_argument("--save-ema", default=None, metavar="PATH", help="write the EMA weights there at the end (a bare state_dict)")
+    ap.add_argument("--denoise", default=None, metavar="DT[:K]",
+                    help="filter the LR streams: drop events with fewer than K (1) neighbour pixels active within DT before them")
     a = ap.parse_args()
     try:
         loss_obj = losses.parse(a.loss)                       # None: nn.MSELoss
     except ValueError as e:
         ap.error("--loss: %s" % e)
+    denoise = None
+    if a.denoise is not None:
+        dt, _, k = a.denoise.partition(":")
+        try:
+            denoise = check_noise_filter("--denoise: ", dict(ts=torch.zeros(0, dtype=torch.float64), dt=float(dt), support=int(k or 1)))[1:]
+        except ValueError as e:
+            ap.error(str(e))
     if not a.recordings and not a.synthetic:
         ap.error("give recordings or --synthetic K")
     if a.ema is None and (a.ema_warmup or a.save_ema):
@@ -155,11 +172,13 @@ def main():
         if len(recs) < 2:
             raise SystemExit("--valid-every holds the last recording out: give at least two")
         vs = EventTrainSet(L=a.L, step_size=a.step_size, window=a.window)      # as recorded: no augmentation, pause or noise
-        add(vs, recs.pop(), dev, a.window, a.sliding, a.scale)
+        add(vs, recs.pop(), dev, a.window, a.sliding, a.scale, denoise)
         if len(vs) < a.batch:
             raise SystemExit("the held-out recording gives %d sequences, fewer than one batch of %d" % (len(vs), a.batch))
     for r in recs:
-        add(ts, r, dev, a.window, a.sliding, a.scale)
+        k = add(ts, r, dev, a.window, a.sliding, a.scale, denoise)
+        if denoise is not None:
+            print("recording %d: noise filter dt %g support %d dropped %d of %d LR events" % ((k,) + denoise + (ts.noise_dropped(k), len(r["lr_xs"]))))
     print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) + (", %dx%d patches" % crop if crop else "") +
           (", transposed with probability %g" % a.transpose if a.transpose is not None else "") +
           (", %d held-out sequences" % len(vs) if vs is not None else "") + (", loss %r" % loss_obj if loss_obj is not None else ""))
