@@ -198,6 +198,118 @@ def filter_noise(who, noise_filter, columns, sensor_size):
     return (xs, ys, ps_out), xs.numel() - int(kept.item())
 
 
+DOWNSAMPLE_CALLS = 0    # streams downsampled so far (tests: one per HR-only recording at the door, none per window or batch)
+DOWNSAMPLE_LAUNCHES = 0  # launches of the library those calls made (downsample_lib.LAUNCHES each; 2 for an empty stream)
+
+
+def downsample_geometry(who, sensor_size, scale, threshold=None):
+    """The number checks of downsample_events -> (H, W, s, T, (h, w)): sensor_size = (H, W) positive; scale an integer 1 .. 16;
+    threshold an integer 1 .. 32767, None = scale^2; (h, w) = the LR sensor, ceil(H / s) x ceil(W / s)."""
+    from . import downsample_lib
+    try:
+        H, W = (int(v) for v in sensor_size)
+    except (TypeError, ValueError):
+        raise ValueError(who + "sensor_size = (H, W)") from None
+    if H < 1 or W < 1:
+        raise ValueError(who + "sensor_size must be positive (got %s)" % ((H, W),))
+    if isinstance(scale, bool) or not isinstance(scale, (int, np.integer)) or not 1 <= scale <= downsample_lib.MAX_SCALE:
+        raise ValueError(who + "scale must be an integer, 1 <= scale <= %d (got %r)" % (downsample_lib.MAX_SCALE, scale))
+    s = int(scale)
+    T = s * s if threshold is None else threshold
+    if isinstance(T, bool) or not isinstance(T, (int, np.integer)) or not 1 <= T <= downsample_lib.MAX_THRESHOLD:
+        raise ValueError(who + "threshold must be an integer, 1 <= threshold <= %d, or None for scale^2 (got %r)"
+                         % (downsample_lib.MAX_THRESHOLD, threshold))
+    h, w = -(-H // s), -(-W // s)
+    if h * w >= (1 << 31) - 1:
+        raise ValueError(who + "%d x %d LR pixels are not below 2^31 - 1" % (h, w))
+    return H, W, s, int(T), (h, w)
+
+
+def check_downsample(who, xs, ys, ts, ps, sensor_size, scale, threshold=None):
+    """The checks of downsample_events, none of which waits for the device -> downsample_geometry's tuple: the numbers, then
+    column types, shapes, lengths, one GPU (as check_noise_filter's columns)."""
+    geometry = downsample_geometry(who, sensor_size, scale, threshold)
+    if ps is None:
+        raise ValueError(who + "ps must be a contiguous 1-D float64 tensor")
+    _noise_columns(who, xs, ys, ts, ps)
+    return geometry
+
+
+def _event_downsample(xs, ys, ts, ps, H, W, s, T):
+    """The four stages of include/bmc_hip_downsample.h on checked columns, on the current stream, no sync -> (xs, ys, ts, ps,
+    count): output columns of capacity n // T and a 1-element int64 GPU tensor."""
+    global DOWNSAMPLE_CALLS, DOWNSAMPLE_LAUNCHES
+    from . import downsample_lib as D
+    DOWNSAMPLE_CALLS += 1
+    n, dev, stream = xs.numel(), xs.device, ops._stream()
+    cap = D.capacity(n, T)
+    out = (torch.empty(cap, dtype=torch.int16, device=dev), torch.empty(cap, dtype=torch.int16, device=dev),
+           torch.empty(cap, dtype=torch.float64, device=dev), torch.empty(cap, dtype=torch.float64, device=dev))
+    count = torch.empty(1, dtype=torch.int64, device=dev)
+    scratch = torch.empty(D.scratch_bytes(n) // 8, dtype=torch.int64, device=dev)
+    fire = torch.empty(n, dtype=torch.int8, device=dev)
+    if n:
+        keys = torch.empty(n, dtype=torch.int32, device=dev)
+        lib.call(D._keys, "bmc_event_downsample_keys", xs.data_ptr(), ys.data_ptr(), ps.data_ptr(), n, H, W, s, keys.data_ptr(),
+                 fire.data_ptr(), stream)
+        keys, perm = torch.sort(keys, stable=True)                   # the grouping: every LR pixel's events, in column order
+        lib.call(D._walk, "bmc_event_downsample_walk", keys.data_ptr(), perm.data_ptr(), ps.data_ptr(), n, H, W, s, T,
+                 fire.data_ptr(), stream)
+        DOWNSAMPLE_LAUNCHES += 2
+    ptr = lambda t: t.data_ptr() if t.numel() else None
+    lib.call(D._gather, "bmc_event_downsample_gather", ptr(xs), ptr(ys), ptr(ts), ptr(fire), n, s, *(ptr(t) for t in out), cap,
+             count.data_ptr(), scratch.data_ptr(), stream)
+    DOWNSAMPLE_LAUNCHES += 2
+    return out + (count,)
+
+
+def downsample_events(xs, ys, ts, ps, sensor_size, scale, threshold=None, trim=True):
+    """The LR event stream of an HR stream by integrate-and-fire over blocks of scale x scale pixels, on the GPU (the contract:
+    include/bmc_hip_downsample.h): an LR pixel adds the +1 / -1 steps of the counted events of its block in column order and
+    fires, and starts again from 0, when the sum reaches +threshold or -threshold (None: scale^2, one LR contrast step of the
+    block's mean).  An event with polarity +-0.0 or NaN, or outside the sensor, touches nothing.
+    xs, ys int16, ts float64 (non-decreasing: the caller's business; the result depends on column order only), ps float64, 1-D
+    contiguous GPU tensors; sensor_size = (H, W) of the HR sensor.  The caller's tensors are not modified.
+    -> (xs, ys, ts, ps, lr_size): int16, int16, float64 (the firing events' own timestamps), float64 (+-1.0) GPU tensors --
+    the column types open_events / add_recording take -- and lr_size = (ceil(H / scale), ceil(W / scale)).
+    trim=True cuts the columns to the number of LR events, which costs ONE host sync, the only one.  trim=False waits for
+    nothing: -> (xs, ys, ts, ps, lr_size, count), the columns at their capacity n // threshold, count a 1-element int64 GPU
+    tensor, entries at count and after unwritten.  One stable torch.sort of n int32 keys plus downsample_lib.LAUNCHES launches."""
+    who = "downsample_events: "
+    H, W, s, T, lr_size = check_downsample(who, xs, ys, ts, ps, sensor_size, scale, threshold)
+    oxs, oys, ots, ops_, count = _event_downsample(xs, ys, ts, ps, H, W, s, T)
+    if not trim:
+        return oxs, oys, ots, ops_, lr_size, count
+    k = int(count.item())
+    return oxs[:k], oys[:k], ots[:k], ops_[:k], lr_size
+
+
+def check_hr_noise_filter(who, noise_filter):
+    """noise_filter of an HR-only recording (None, or a dict with the keys dt and, optionally, support: ts is the synthesized
+    column, which the caller cannot have) -> None or dict(dt=, support=), checked as check_noise_filter checks them."""
+    if noise_filter is None:
+        return None
+    if not isinstance(noise_filter, dict) or "dt" not in noise_filter or set(noise_filter) - {"dt", "support"}:
+        raise ValueError(who + "noise_filter must be None or a dict with the keys dt, support (ts is the synthesized column; got %r)"
+                         % (noise_filter,))
+    dt, support = _noise_numbers(who, noise_filter["dt"], noise_filter.get("support", 1), ("noise_filter['dt']", "noise_filter['support']"))
+    return dict(dt=dt, support=support)
+
+
+def synthesize_lr(who, gt, gt_ts, gt_size, scale, threshold=None):
+    """(xs, ys, ps) and the timestamp column of an HR-only recording -> ((xs, ys, ps), lr_ts, lr_size) of its synthetic LR stream
+    (downsample_events, trimmed: one host sync).  What EventTrainSet.add_hr_recording and MultiStreamSR.open_hr_events do at the
+    door."""
+    if not (isinstance(gt, (tuple, list)) and len(gt) == 3 and all(torch.is_tensor(t) for t in gt)):
+        raise ValueError(who + "gt must be three tensors (xs, ys, ps)")
+    if not torch.is_tensor(gt_ts):
+        raise ValueError(who + "gt_ts must be a contiguous 1-D float64 tensor")
+    H, W, s, T, lr_size = check_downsample(who, gt[0], gt[1], gt_ts, gt[2], gt_size, scale, threshold)
+    xs, ys, ts, ps, count = _event_downsample(gt[0], gt[1], gt_ts, gt[2], H, W, s, T)
+    k = int(count.item())
+    return (xs[:k], ys[:k], ps[:k]), ts[:k], lr_size
+
+
 def events_to_channels_batch(xs, ys, ps, offsets, sensor_size=(180, 240), mutate=True):
     """Many frames in one launch: frame f owns events [offsets[f], offsets[f+1]) -> [nframes,2,H,W]."""
     return ops.events_to_channels_batched(xs, ys, ps, offsets, int(sensor_size[0]), int(sensor_size[1]), mutate=mutate)

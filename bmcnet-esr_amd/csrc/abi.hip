@@ -19,6 +19,7 @@
 #include "bmc_hip_ema.h"
 #include "bmc_hip_ssim.h"
 #include "bmc_hip_denoise.h"
+#include "bmc_hip_downsample.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -106,6 +107,15 @@
 #define BMC_DENOISE_ABI_FUNCTIONS(X) \
     X(bmc_event_denoise_band_rows) X(bmc_event_denoise_scratch_bytes) X(bmc_event_denoise) X(bmc_denoise_abi)
 #define BMC_DENOISE_ABI_CONSTANTS(X) X(BMC_DENOISE_STEP) X(BMC_DENOISE_LDS_WORDS) X(BMC_DENOISE_MAX_W)
+
+/* include/bmc_hip_downsample.h, the companion header of the event downsampler: likewise, bmc_downsample_abi()
+ * (bmc_hip/downsample_lib.py binds from it; tests/test_event_downsample_cpu.py compares the lists with that header's text). */
+#define BMC_DOWNSAMPLE_ABI_FUNCTIONS(X) \
+    X(bmc_event_downsample_capacity) X(bmc_event_downsample_chunk) X(bmc_event_downsample_scratch_bytes) \
+    X(bmc_event_downsample_keys) X(bmc_event_downsample_walk) X(bmc_event_downsample_gather) X(bmc_downsample_abi)
+#define BMC_DOWNSAMPLE_ABI_CONSTANTS(X) \
+    X(BMC_DOWNSAMPLE_MAX_SCALE) X(BMC_DOWNSAMPLE_MAX_THRESHOLD) X(BMC_DOWNSAMPLE_LANES) X(BMC_DOWNSAMPLE_TILE) \
+    X(BMC_DOWNSAMPLE_MAX_PARTS) X(BMC_DOWNSAMPLE_LAUNCHES)
 
 namespace {
 
@@ -195,3 +205,4 @@ BMC_ABI_TEXT(bmc_quality_abi, BMC_QUALITY_ABI_FUNCTIONS, BMC_QUALITY_ABI_STRUCTS
 BMC_ABI_TEXT(bmc_ema_abi, BMC_EMA_ABI_FUNCTIONS, BMC_EMA_ABI_STRUCTS, BMC_ABI_NONE)
 BMC_ABI_TEXT(bmc_ssim_abi, BMC_SSIM_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_SSIM_ABI_CONSTANTS)
 BMC_ABI_TEXT(bmc_denoise_abi, BMC_DENOISE_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_DENOISE_ABI_CONSTANTS)
+BMC_ABI_TEXT(bmc_downsample_abi, BMC_DOWNSAMPLE_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_DOWNSAMPLE_ABI_CONSTANTS)

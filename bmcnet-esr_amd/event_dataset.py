@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from bmc_hip import lib
-from bmc_hip.encodings import filter_noise
+from bmc_hip.encodings import check_hr_noise_filter, event_window_indices, filter_noise, synthesize_lr
 
 MAX_ITEMS = lib.const("BMC_SEQ_MAX_ITEMS")
 MAX_BATCH = 65535
@@ -274,6 +274,35 @@ class EventTrainSet:
                                noise_dropped=dropped))
         self._ends.append(len(self) + (len(lr_index) - self.L) // self.step_size + 1)
         return len(self._recs) - 1
+
+    def add_hr_recording(self, gt, gt_ts, gt_size, window=2048, sliding_window=1024, threshold=None, dataset_length=None,
+                         noise_filter=None):
+        """One HR-ONLY recording -> its number.  gt = (xs, ys, ps) and gt_ts, the float64 timestamp column parallel to them
+        (1-D GPU tensors), of a sensor of gt_size = (gh, gw).  The LR half is synthesized here, once, on the GPU, by integrate-and-
+        fire over blocks of scale x scale pixels with the set's scale (bmc_hip.encodings.downsample_events, the contract:
+        include/bmc_hip_downsample.h; threshold None = scale^2), both index tables are event_window_indices(lr_ts, gt_ts, window,
+        sliding_window, scale, dataset_length) on the synthetic and the given timestamps, and the rest is add_recording: by
+        construction the recording trains bit for bit as one added with the same LR columns made beforehand.
+        noise_filter=dict(dt=, support=) needs no ts: the synthesized column is supplied, so the filter acts on the synthetic LR
+        stream.  One host sync (the LR event count).  synthesized_events() tells the count; the caller's tensors are not
+        modified."""
+        who = "EventTrainSet.add_hr_recording: "
+        noise_filter = check_hr_noise_filter(who, noise_filter)
+        lr, lr_ts, lr_size = synthesize_lr(who, gt, gt_ts, gt_size, self.scale, threshold)
+        try:
+            lr_index, gt_index = event_window_indices(lr_ts.cpu().numpy(), gt_ts.cpu().numpy(), window, sliding_window, self.scale,
+                                                      dataset_length)
+        except ValueError as e:
+            raise ValueError(who + "the %d synthesized LR events: %s" % (lr_ts.numel(), e)) from None
+        if noise_filter is not None:
+            noise_filter = dict(noise_filter, ts=lr_ts)
+        r = self.add_recording(lr, gt, lr_index, gt_index, lr_size, gt_size, noise_filter=noise_filter)
+        self._recs[r]["synthesized"] = lr_ts.numel()
+        return r
+
+    def synthesized_events(self, recording):
+        """LR events synthesized for a recording added with add_hr_recording; None for one added with its own LR stream."""
+        return self._recs[recording].get("synthesized")
 
     def noise_dropped(self, recording):
         """Events the noise filter dropped from the recording's LR stream; None for one added without noise_filter."""

@@ -15,7 +15,7 @@ import numpy as np
 import torch
 
 from bmc_hip import slots
-from bmc_hip.encodings import event_block_spans, filter_noise
+from bmc_hip.encodings import check_hr_noise_filter, event_block_spans, event_window_indices, filter_noise, synthesize_lr
 from bmc_hip.slots import check_group_size, check_hot_filter
 from infer_parts import EventStream, HotFilter, Input, KeptPredictions, Metrics, Pictures, Quality, VoxelGrids
 
@@ -24,6 +24,13 @@ EventRecording.__doc__ = """An event-backed recording for MultiStreamSR.open_eve
 raw dataset columns on the GPU (int16, int16, float64); lr_index, gt_index [L,2] = the event range [first, end) of every
 item's LR / ground-truth frame (bmc_hip.encodings.event_window_indices); lr_size = (H, W), gt_size = (gh, gw).  A recording
 without ground truth: gt = gt_index = gt_size = None."""
+
+HREventRecording = collections.namedtuple("HREventRecording", "gt gt_ts gt_size window sliding_window threshold",
+                                          defaults=(2048, 1024, None))
+HREventRecording.__doc__ = """An HR-only event recording for MultiStreamSR.open_hr_events / evaluate_recordings: gt = (xs, ys, ps)
+and gt_ts, its float64 timestamp column, GPU tensors of a sensor of gt_size = (gh, gw); the LR stream is synthesized at the door
+(bmc_hip.encodings.downsample_events) with the session's scale and `threshold` (None = scale^2), the blocks are those of
+event_window_indices(lr_ts, gt_ts, window, sliding_window, scale)."""
 
 
 class StreamingSR:
@@ -489,6 +496,33 @@ class MultiStreamSR:
             rec.update(gt=tuple(gt), gt_index=gt_index)
         return self._add(rec, L, cols[0].device, event_capacity, window_event_capacity, spans)
 
+    def open_hr_events(self, gt, gt_ts, gt_size, window=2048, sliding_window=1024, threshold=None, dataset_length=None,
+                       event_capacity=None, window_event_capacity=None, spans=None, noise_filter=None):
+        """Queue one HR-ONLY event recording -> handle.  gt = (xs, ys, ps) and gt_ts, the float64 timestamp column parallel to
+        them (1-D GPU tensors), of a sensor of gt_size = (gh, gw).  The LR half is synthesized here, once, on the GPU, by
+        integrate-and-fire over blocks of scale x scale pixels with the session's scale (bmc_hip.encodings.downsample_events, the
+        contract: include/bmc_hip_downsample.h; threshold None = scale^2); both index tables are event_window_indices(lr_ts,
+        gt_ts, window, sliding_window, scale, dataset_length); the rest is open_events, with its remaining keyword arguments:
+        by construction the session is bit-identical to open_events on those LR columns.  An event_times session gets the
+        synthesized lr_ts unless spans are given.  noise_filter=dict(dt=, support=) needs no ts: the synthesized column is
+        supplied.  One host sync (the LR event count), nothing per window; results() gains synthesized_events."""
+        who = "MultiStreamSR.open_hr_events: "
+        noise_filter = check_hr_noise_filter(who, noise_filter)
+        lr, lr_ts, lr_size = synthesize_lr(who, gt, gt_ts, gt_size, self.scale, threshold)
+        try:
+            lr_index, gt_index = event_window_indices(lr_ts.cpu().numpy(), gt_ts.cpu().numpy(), window, sliding_window, self.scale,
+                                                      dataset_length)
+        except ValueError as e:
+            raise ValueError(who + "the %d synthesized LR events: %s" % (lr_ts.numel(), e)) from None
+        if noise_filter is not None:
+            noise_filter = dict(noise_filter, ts=lr_ts)
+        timed = self.event_times is not None and spans is None
+        h = self.open_events(lr, gt, lr_index, gt_index, lr_size, gt_size, event_capacity=event_capacity,
+                             window_event_capacity=window_event_capacity, lr_ts=lr_ts if timed else None, spans=spans,
+                             noise_filter=noise_filter)
+        self._recs[h]["synthesized_events"] = lr_ts.numel()
+        return h
+
     def resident_bytes(self, handle):
         """Bytes the recording keeps on the GPU: every tensor of its record -- its columns (event-backed) or frames, and what the
         parts have added to it (result sums, kept predictions, output columns with their index, pictures, voxel grids, ...)."""
@@ -514,6 +548,8 @@ class MultiStreamSR:
             p.results(self, out, r, done, handle)
         if "noise_events" in r:
             out["noise_events"] = r["noise_events"]
+        if "synthesized_events" in r:
+            out["synthesized_events"] = r["synthesized_events"]
         return out
 
     # ---------------------------------------------------------------- windows
@@ -647,7 +683,8 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
-    (frames, None) or an EventRecording with gt = None.  -> dict(
+    (frames, None) or an EventRecording with gt = None.  An HREventRecording is an HR-only event recording whose LR stream is
+    synthesized at the door (MultiStreamSR.open_hr_events).  -> dict(
       results = {metric: {name: value}}  per recording the mean over its windows of esr_mse, bicubic_mse (recordings with
                                          ground truth only), time (ms), and params (millions) -- infer_body's MetricTracker
                                          result (:34,:70-86),
@@ -679,6 +716,12 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
                                  % (tuple(gt_size), name, tuple(r.gt_size)))
             handles.append((name, ms.open_events(*r, event_capacity=event_capacity,
                                                  window_event_capacity=window_event_capacity)))
+        elif isinstance(r, HREventRecording):
+            if gt_size is not None and tuple(int(v) for v in gt_size) != tuple(int(v) for v in r.gt_size):
+                raise ValueError("evaluate_recordings: gt_size %s differs from recording %s's %s"
+                                 % (tuple(gt_size), name, tuple(r.gt_size)))
+            handles.append((name, ms.open_hr_events(*r, event_capacity=event_capacity,
+                                                    window_event_capacity=window_event_capacity)))
         else:
             handles.append((name, ms.open(r[0], r[1], gt_size if r[1] is not None else None, event_capacity=event_capacity,
                                           window_event_capacity=window_event_capacity)))

@@ -21,6 +21,10 @@ last table).
 uniform noise events (a drifting bar, one second long, 20 % noise) opened with noise_filter=dict(ts=, dt=DT, support=K) and without,
 --runs alternating runs each: the share of the LR events the filter dropped next to the share that is noise, the mean esr_mse of
 both, and ms per window and windows/s of both (the filter runs once per recording at open_events: nothing enters a window).
+--from-hr [T] adds, per configuration, the event-backed session on HR-ONLY recordings (open_hr_events: the LR stream is made at the
+door, on the GPU, by integrate-and-fire over 4 x 4 blocks with threshold T, default 16; include/bmc_hip_downsample.h) with PSNR /
+SSIM on: ms per window, windows/s, the LR events synthesized per HR event, ms of open_hr_events per recording (the synthesis, its
+one host sync and both index tables) and the means of esr_mse, esr_psnr and esr_ssim -- the table from recordings that have no LR half.
 --render DIR [--render-kinds lr,bicubic,esr,gt] adds, per configuration, the frame-backed session with the event-count images on
 (render=kinds): its latency and windows/s, one bmc_slot_render call alone per kind (both kernels, events around 20 calls on the
 session's last table), and writes the images of the first such session as DIR/<recording>/event_img/<kind dir>/%09d.png with the
@@ -42,7 +46,7 @@ last table and prediction) and the means of esr_psnr, esr_ssim, bicubic_psnr and
 with the event output (nothing is run: the buffers are allocated when a recording is opened).
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
-                                  [--hot-filter] [--noise-filter DT[:K]] [--runs 3]
+                                  [--hot-filter] [--noise-filter DT[:K]] [--from-hr [T]] [--runs 3]
                                   [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
                                   [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]
                                   [--self-ensemble K] [--plain-weights NPZ] [--quality [RANGE]]"""
@@ -132,6 +136,49 @@ def noise_session(m, recs, S, graph, warmup, windows, noise_filter):
     mse = statistics.mean(v for r in res for v in r["esr_mse"][warmup:])
     dropped = None if noise_filter is None else sum(r["noise_events"] for r in res) / sum(r[0][0].numel() for r in recs[:S])
     return statistics.median(res[0]["time"][warmup:]), S * windows / wall, mse, dropped
+
+
+def hr_recording(L, H, W, seed):
+    """An HR-only recording on the CPU that gives at least L LR items of 2 048 events advancing by 1 024: uniform positions on the
+    4H x 4W sensor, one second long, the polarity of an event fixed by its LR pixel (a checkerboard), so that every LR pixel fires
+    once per 16 of its events -> (xs, ys, ps), the float64 timestamp column, (4H, 4W)."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    n = 16 * (1024 * L + 1) + 16 * H * W
+    xs, ys = rng.integers(0, 4 * W, n), rng.integers(0, 4 * H, n)
+    ps = np.where((xs // 4 + ys // 4) % 2 == 0, 1.0, -1.0)
+    return ((torch.from_numpy(xs.astype(np.int16)), torch.from_numpy(ys.astype(np.int16)), torch.from_numpy(ps)),
+            torch.from_numpy(np.sort(rng.uniform(0, 1, n))), (4 * H, 4 * W))
+
+
+def hr_session(m, recs, S, graph, warmup, windows, threshold):
+    """The event-backed session on hr_recording()s opened with open_hr_events, quality on -> median ms per window of the first
+    recording, windows / s, LR events per HR event, median ms of open_hr_events, the means of esr_mse, esr_psnr, esr_ssim over the
+    timed windows (finite values)."""
+    import math
+    dev = next(m.parameters()).device
+    ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, quality=True)
+    hs, door = [], []
+    for gt, gt_ts, gt_size in recs[:S]:
+        gt, gt_ts = tuple(t.to(dev) for t in gt), gt_ts.to(dev)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        hs.append(ms.open_hr_events(gt, gt_ts, gt_size, threshold=threshold, dataset_length=warmup + windows + SEQN - 1))
+        torch.cuda.synchronize()
+        door.append(1e3 * (time.perf_counter() - t0))
+    for _ in range(warmup):
+        ms.step()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(windows):
+        ms.step()
+    torch.cuda.synchronize()
+    wall = time.perf_counter() - t0
+    res = [ms.results(h) for h in hs]
+    mean = lambda k: statistics.mean([v for r in res for v in r[k][warmup:] if math.isfinite(v)] or [float("nan")])
+    made = sum(r["synthesized_events"] for r in res) / sum(r[0][0].numel() for r in recs[:S])
+    return (statistics.median(res[0]["time"][warmup:]), S * windows / wall, made, statistics.median(door), mean("esr_mse"),
+            mean("esr_psnr"), mean("esr_ssim"))
 
 
 def alone(call, reps=20):
@@ -306,6 +353,9 @@ def parse_args(argv=None):
                     help="implies --events: the event-backed session on recordings with a known share of uniform noise events, with "
                          "open_events(noise_filter=dict(ts=, dt=DT, support=K)) (DT in seconds of a one-second recording; K = 1) "
                          "and without, alternating runs: the share of events dropped and esr_mse of both")
+    ap.add_argument("--from-hr", type=int, nargs="?", const=0, default=None, metavar="T",
+                    help="adds the event-backed session on HR-only recordings (open_hr_events: the LR stream is synthesized on the "
+                         "GPU by integrate-and-fire with threshold T, default scale^2) with PSNR / SSIM on")
     ap.add_argument("--runs", type=int, default=3, help="with --hot-filter / --noise-filter / --voxel-bins: alternating runs of each")
     ap.add_argument("--emit-events", action="store_true")
     ap.add_argument("--event-times", action="store_true",
@@ -450,6 +500,14 @@ def main():
                                      ms_per_window_filter_off_runs=[round(r[0], 3) for r in off],
                                      windows_per_s=round(statistics.median(r[1] for r in on), 1),
                                      windows_per_s_filter_off=round(statistics.median(r[1] for r in off), 1)))
+                    print(json.dumps(rows[-1]), flush=True)
+                if a.from_hr is not None:
+                    hrecs = [hr_recording(L, H, W, 5 * H * W + k) for k in range(S)]
+                    lat, wps, made, door, mse, psnr, ssim = hr_session(m, hrecs, S, graph, a.warmup, a.windows, a.from_hr or None)
+                    rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(events, from HR)", slots=S, events=True,
+                                     threshold=a.from_hr or 16, ms_per_window=round(lat, 3), windows_per_s=round(wps, 1),
+                                     lr_events_per_hr_event=round(made, 5), open_hr_events_ms=round(door, 3), esr_mse=mse,
+                                     esr_psnr=psnr, esr_ssim=ssim))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.render is not None:
                     lat, wps, alone, nbytes = multistream(m, recs, S, graph, a.warmup, a.windows, render=a.render_kinds,

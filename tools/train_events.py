@@ -36,6 +36,11 @@ the patch must fit every recording both ways.  Validation stays on untransposed 
 background-activity filter of include/bmc_hip_denoise.h runs once per recording, on the GPU, and the LR events it drops train with
 weight zero; the events dropped are printed.  DT is in the units of the recordings' timestamps.  The held-out recording of
 --valid-every is filtered too; the ground truth never is.
+--from-hr [T]: the recordings' LR halves are not read: every recording is added with EventTrainSet.add_hr_recording, which makes
+the LR stream from the HR one on the GPU by integrate-and-fire over scale x scale blocks (include/bmc_hip_downsample.h; threshold T,
+default scale^2) and cuts both index tables from the synthetic timestamps; the LR events made are printed.  With --denoise the
+filter acts on the synthetic LR stream.  Uniform random events fire rarely (a random walk needs about T^2 steps to reach T): give
+the synthetic recordings of this tool a small T, or real recordings.
 --valid-every N: the last recording is held out of training; after every N steps train_step.valid_step (the reference's _valid
 loop: eval mode, no gradients, the same loss) runs over its sequences in order and `valid_loss`, their mean, is printed.
 --optimizer: hip (default) steps with bmc_hip.optim.Adam (csrc/optim.hip, one launch per step), torch with torch.optim.Adam.
@@ -81,9 +86,16 @@ def synthetic_recording(items, H, W, scale, window, sliding, seed, gt_size=None)
     return rec
 
 
-def add(ts, rec, dev, window, sliding, scale, denoise=None):
-    lr_index, gt_index = event_window_indices(rec["lr_ts"], rec["gt_ts"], window, sliding, scale)
+def add(ts, rec, dev, window, sliding, scale, denoise=None, from_hr=None):
     cols = lambda side: tuple(torch.from_numpy(np.ascontiguousarray(rec["%s_%s" % (side, k)])).to(dev) for k in KEYS[:3])
+    if from_hr is not None:
+        nf = None if denoise is None else dict(dt=denoise[0], support=denoise[1])
+        gt_ts = torch.from_numpy(np.ascontiguousarray(rec["gt_ts"], np.float64)).to(dev)
+        k = ts.add_hr_recording(cols("gt"), gt_ts, tuple(rec["gt_size"].tolist()), window, sliding, threshold=from_hr or None,
+                                noise_filter=nf)
+        print("recording %d: %d LR events synthesized from %d HR events" % (k, ts.synthesized_events(k), len(rec["gt_xs"])))
+        return k
+    lr_index, gt_index = event_window_indices(rec["lr_ts"], rec["gt_ts"], window, sliding, scale)
     nf = None
     if denoise is not None:
         nf = dict(ts=torch.from_numpy(np.ascontiguousarray(rec["lr_ts"], np.float64)).to(dev), dt=denoise[0], support=denoise[1])
@@ -128,6 +140,8 @@ def main():
     ap.add_argument("--save-ema", default=None, metavar="PATH", help="write the EMA weights there at the end (a bare state_dict)")
     ap.add_argument("--denoise", default=None, metavar="DT[:K]",
                     help="filter the LR streams: drop events with fewer than K (1) neighbour pixels active within DT before them")
+    ap.add_argument("--from-hr", type=int, nargs="?", const=0, default=None, metavar="T",
+                    help="make every recording's LR stream from its HR stream on the GPU (integrate-and-fire, threshold T = scale^2)")
     a = ap.parse_args()
     try:
         loss_obj = losses.parse(a.loss)                       # None: nn.MSELoss
@@ -172,13 +186,13 @@ def main():
         if len(recs) < 2:
             raise SystemExit("--valid-every holds the last recording out: give at least two")
         vs = EventTrainSet(L=a.L, step_size=a.step_size, window=a.window)      # as recorded: no augmentation, pause or noise
-        add(vs, recs.pop(), dev, a.window, a.sliding, a.scale, denoise)
+        add(vs, recs.pop(), dev, a.window, a.sliding, a.scale, denoise, a.from_hr)
         if len(vs) < a.batch:
             raise SystemExit("the held-out recording gives %d sequences, fewer than one batch of %d" % (len(vs), a.batch))
     for r in recs:
-        k = add(ts, r, dev, a.window, a.sliding, a.scale, denoise)
+        k = add(ts, r, dev, a.window, a.sliding, a.scale, denoise, a.from_hr)
         if denoise is not None:
-            print("recording %d: noise filter dt %g support %d dropped %d of %d LR events" % ((k,) + denoise + (ts.noise_dropped(k), len(r["lr_xs"]))))
+            print("recording %d: noise filter dt %g support %d dropped %d of %d LR events" % ((k,) + denoise + (ts.noise_dropped(k), ts.synthesized_events(k) if a.from_hr is not None else len(r["lr_xs"]))))
     print("%d recordings, %d sequences of L = %d" % (len(recs), len(ts), a.L) + (", %dx%d patches" % crop if crop else "") +
           (", transposed with probability %g" % a.transpose if a.transpose is not None else "") +
           (", %d held-out sequences" % len(vs) if vs is not None else "") + (", loss %r" % loss_obj if loss_obj is not None else ""))
