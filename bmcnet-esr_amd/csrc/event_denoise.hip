@@ -19,13 +19,13 @@
 #include <math.h>
 #include "bmc_common.h"
 #include "bmc_hip_denoise.h"
-#include "slot_k.h"
+#include "wave_k.h"
 
 namespace {
 
 constexpr int STEP = BMC_DENOISE_STEP;
 constexpr int WORDS = BMC_DENOISE_LDS_WORDS;
-static_assert(STEP == 256, "the wave fold of the kept count assumes four waves");
+static_assert(STEP % 64 == 0, "whole waves");
 
 static inline int band_rows(int H, int W) {
     const int r = WORDS / (W + 2) - 2;
@@ -126,10 +126,8 @@ __global__ __launch_bounds__(STEP) void event_denoise_kernel(const short* __rest
         mine += kept ? 1 : 0;
     }
     if (partial == nullptr) return;
-    for (int o = 32; o > 0; o >>= 1) mine += __shfl_xor(mine, o);
-    if ((tid & 63) == 0) wsum[tid >> 6] = mine;
-    __syncthreads();
-    if (tid == 0) gst<long long>(partial + band, (long long)wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    mine = block_fold<STEP / 64>(mine, Sum(), wsum);                 // (a band keeps at most n < 2^31 events: no overflow)
+    if (tid == 0) gst<long long>(partial + band, (long long)mine);
 }
 
 // one workgroup: kept[0] = the sum of the band counts
@@ -139,10 +137,8 @@ __global__ __launch_bounds__(STEP) void event_denoise_finish_kernel(const long l
     const int tid = threadIdx.x;
     long long v = 0;
     for (int b = tid; b < nb; b += STEP) v += gld<long long>(partial + b);
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((tid & 63) == 0) wsum[tid >> 6] = v;
-    __syncthreads();
-    if (tid == 0) gst<long long>(kept, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    v = block_fold<STEP / 64>(v, Sum(), wsum);
+    if (tid == 0) gst<long long>(kept, v);
 }
 
 }  // namespace

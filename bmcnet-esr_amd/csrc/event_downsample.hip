@@ -11,21 +11,21 @@
 //           contract over it in a register; a firing event's sign goes to fire[] at its ORIGINAL index, so the gather sees the
 //           events in column order again without a second sort;
 //   gather  the ordered compaction of slot_emit.hip in its two launches (chunk totals; every chunk adds the totals before it),
-//           with slot_emit_k.h's chunk range and sum of totals.  The tile scan is another one: an event fires once or not at
+//           with wave_k.h's chunk range and sum of totals.  The tile scan is another one: an event fires once or not at
 //           all, so a wave ranks its lanes with one ballot and a popcount instead of a prefix sum of counts, and the firing
 //           events' indices are staged in LDS at their rank so that lane p stores output p.
 // Integers decide everything; no global atomic, no workgroup waits for another, the grids are fixed by (n, h * w): the same bytes
 // run after run.
 #include "bmc_hip_downsample.h"
-#include "slot_emit_k.h"
+#include "wave_k.h"
 
 namespace {
 
 constexpr int LANES = BMC_DOWNSAMPLE_LANES;
+constexpr int NW = LANES / 64;
 constexpr int DTILE = BMC_DOWNSAMPLE_TILE;
 constexpr int ROUNDS = DTILE / LANES;
-static_assert(LANES == EMT && NW == 4, "sum_parts and the wave exchange assume slot_emit_k.h's workgroup of four waves");
-static_assert(ROUNDS * LANES == DTILE, "a tile is whole rounds of one event per lane");
+static_assert(NW * 64 == LANES && ROUNDS * LANES == DTILE, "whole waves; a tile is whole rounds of one event per lane");
 
 // grid ceil(n / LANES): lane l of workgroup g takes event g * LANES + l
 __global__ __launch_bounds__(LANES) void event_downsample_keys_kernel(const short* __restrict__ xs, const short* __restrict__ ys,
@@ -81,10 +81,8 @@ __global__ __launch_bounds__(LANES) void event_downsample_total_kernel(const sig
     const PartRange r = part_range(part, chunk, n);
     unsigned acc = 0u;
     for (int i = r.lo + tid; i < r.hi; i += LANES) acc += gld<signed char>(fire + i) != 0 ? 1u : 0u;
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) gst<unsigned>(parts + part, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    acc = block_fold<NW>(acc, Sum(), wsum);
+    if (tid == 0) gst<unsigned>(parts + part, acc);
 }
 
 // grid (nparts): workgroup c places its chunk's firing events behind those of the chunks before it
@@ -100,7 +98,7 @@ __global__ __launch_bounds__(LANES) void event_downsample_write_kernel(const sho
     __shared__ unsigned long long red[NW];
     const int part = blockIdx.x, nparts = gridDim.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     // events of the chunks before this one; workgroup 0 has none before it and adds ALL chunks instead: the count
-    const unsigned long long before = sum_parts(parts, part == 0 ? nparts : part, red, tid);
+    const unsigned long long before = sum_parts<NW>(parts, part == 0 ? nparts : part, red);
     long long gpos = (long long)before;
     if (part == 0) {
         if (tid == 0) gst<long long>(count, gpos);

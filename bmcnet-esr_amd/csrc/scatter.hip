@@ -2,6 +2,7 @@
 // Integer bin indices, +p*p contributions (exact integers for p = +-1) accumulated with
 // global_atomic_add_f32: the sum is order independent below 2^24, hence bit-exact.
 #include "bmc_common.h"
+#include "wave_k.h"
 
 namespace {
 
@@ -159,23 +160,20 @@ __global__ __launch_bounds__(256) void bin_events_kernel(const EV ev, const long
             if (hist[i]) atomicAdd(table + (long long)f * nbands + i, hist[i]);
     }
 }
-// exclusive prefix sum of table[0 .. n) in place, table[n] = total; one workgroup (n is a few thousand at most)
-__global__ __launch_bounds__(1024) void bin_scan_kernel(int* __restrict__ table, int n) {
-    __shared__ int part[1024];
+// Workgroup b (1 024 threads): the exclusive prefix sum of its table c = cnt + b * stride, c[0 .. n), in place, c[n] = the
+// total; cur (or NULL) + b * stride receives the same n + 1 words (the fill cursors of the voxel paths).  A contiguous chunk per
+// thread, the threads' sums through wave_k.h's block_scan_excl.
+__global__ __launch_bounds__(1024) void table_scan_kernel(int* __restrict__ cnt, int* __restrict__ cur, int n, long long stride) {
+    __shared__ int wtot[16];
+    int* const c = cnt + blockIdx.x * stride;
+    int* const u = cur ? cur + blockIdx.x * stride : nullptr;
     const int per = (n + 1023) / 1024;
     const int lo = threadIdx.x * per < n ? threadIdx.x * per : n, hi = lo + per < n ? lo + per : n;
     int s = 0;
-    for (int i = lo; i < hi; ++i) s += table[i];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < 1024; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        table[n] = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { const int v = table[i]; table[i] = run; run += v; }
+    for (int i = lo; i < hi; ++i) s += c[i];
+    int total, run = block_scan_excl<16>(s, wtot, &total);
+    if (threadIdx.x == 0) { c[n] = total; if (u) u[n] = total; }
+    for (int i = lo; i < hi; ++i) { const int v = c[i]; c[i] = run; if (u) u[i] = run; run += v; }
 }
 __global__ __launch_bounds__(1024) void bin_gather_kernel(const unsigned long long* __restrict__ records, const int* __restrict__ starts,
                                                           int H, int W, int R, int nbands, float* __restrict__ out) {
@@ -220,7 +218,7 @@ int launch_binned(const EV& ev, const long long* offsets, long long nevents, int
     if (per < 1) per = 1;
     const dim3 grid((unsigned)per, (unsigned)nframes);
     hipLaunchKernelGGL((bin_events_kernel<EV, false>), grid, dim3(256), 0, st, ev, offsets, H, W, R, nbands, table, cursors, records);
-    hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(1024), 0, st, table, (int)ntab);
+    hipLaunchKernelGGL(table_scan_kernel, dim3(1), dim3(1024), 0, st, table, (int*)nullptr, (int)ntab, 0ll);
     hipLaunchKernelGGL((bin_events_kernel<EV, true>), grid, dim3(256), 0, st, ev, offsets, H, W, R, nbands, table, cursors, records);
     hipLaunchKernelGGL(bin_gather_kernel, dim3((unsigned)nbands, (unsigned)nframes), dim3(1024), 0, st, records, table, H, W, R, nbands, out);
     return 0;
@@ -251,27 +249,6 @@ __global__ void voxel_count_kernel(const float* __restrict__ xs, const float* __
         bool oob;
         atomicAdd(c + voxel_pixel(xs[e], ys[e], H, W, oob), 1);
     }
-}
-// in-place exclusive scan of cnt[f][0 .. HW] (entry HW receives the total); cur[f][q] = start of segment q (fill cursor)
-__global__ void voxel_scan_kernel(int* __restrict__ cnt, int* __restrict__ cur, int HW) {
-    int* const c = cnt + (long long)blockIdx.x * (HW + 1);
-    int* const u = cur + (long long)blockIdx.x * (HW + 1);
-    const int per = (HW + blockDim.x - 1) / blockDim.x;
-    const int lo = threadIdx.x * per, hi = lo + per < HW ? lo + per : HW;
-    int s = 0;
-    for (int i = lo; i < hi; ++i) s += c[i];
-    __shared__ int part[1024];
-    part[threadIdx.x] = s;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int run = 0;
-        for (int i = 0; i < (int)blockDim.x; ++i) { const int v = part[i]; part[i] = run; run += v; }
-        c[HW] = run;
-        u[HW] = run;
-    }
-    __syncthreads();
-    int run = part[threadIdx.x];
-    for (int i = lo; i < hi; ++i) { const int v = c[i]; c[i] = run; u[i] = run; run += v; }
 }
 __global__ void voxel_fill_kernel(const float* __restrict__ xs, const float* __restrict__ ys,
                                   const long long* __restrict__ offsets, int H, int W, int* __restrict__ cur,
@@ -504,7 +481,7 @@ extern "C" int bmc_events_to_voxel(float* xs, float* ys, const float* ts, const 
     hipError_t e = hipMemsetAsync(seg, 0, (size_t)segn * sizeof(int), st);
     if (e != hipSuccess) { bmc_set_error("bmc_events_to_voxel: memset failed: %s", hipGetErrorString(e)); return -2; }
     hipLaunchKernelGGL(voxel_count_kernel, dim3(64, nframes), dim3(256), 0, st, xs, ys, offsets, H, W, seg);
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3(nframes), dim3(1024), 0, st, seg, cur, H * W);
+    hipLaunchKernelGGL(table_scan_kernel, dim3(nframes), dim3(1024), 0, st, seg, cur, H * W, (long long)H * W + 1);
     hipLaunchKernelGGL(voxel_fill_kernel, dim3(64, nframes), dim3(256), 0, st, xs, ys, offsets, H, W, cur, idx);
     hipLaunchKernelGGL(voxel_sort_long_kernel, dim3(nframes), dim3(1024), 0, st, offsets, H * W, seg, idx);
     hipLaunchKernelGGL(voxel_reduce_kernel, dim3((H * W + 255) / 256, nframes), dim3(256), 0, st, xs, ys, ts, ps, offsets, bins,
@@ -756,7 +733,7 @@ int ordered_cells(float* xs, float* ys, float* ps, long long n, int H, int W, in
     if (e != hipSuccess) { bmc_set_error("events_to_image_torch: memset failed: %s", hipGetErrorString(e)); return -2; }
     hipLaunchKernelGGL(one_frame_offsets_kernel, dim3(1), dim3(1), 0, st, off, n);
     hipLaunchKernelGGL(img_cells_kernel, dim3(256), dim3(256), 0, st, xs, ys, ps, n, H, W, ih, iw, mode, cell, seg, bad, mutate_ps, live);
-    hipLaunchKernelGGL(voxel_scan_kernel, dim3(1), dim3(1024), 0, st, seg, cur, ncell);
+    hipLaunchKernelGGL(table_scan_kernel, dim3(1), dim3(1024), 0, st, seg, cur, ncell, 0ll);
     hipLaunchKernelGGL(cell_fill_kernel, dim3(256), dim3(256), 0, st, cell, n, cur, idx);
     hipLaunchKernelGGL(voxel_sort_long_kernel, dim3(1), dim3(1024), 0, st, off, ncell, seg, idx);
     hipLaunchKernelGGL(cell_sort_kernel, dim3((ncell + 255) / 256), dim3(256), 0, st, seg, ncell, idx);

@@ -9,8 +9,8 @@
 // no flags, no atomics on global memory):
 //   slot_emit_count_kernel   workgroup (part, s) sums q over its fixed contiguous chunk of slot s -> parts[s][part];
 //   slot_emit_write_kernel   workgroup (part, s) adds the totals of the parts before it to *index_in (the recording's running
-//                            event count), scans its chunk tile by tile (wave scan with cross-lane moves, one LDS exchange between
-//                            the waves) and stores the events at their final positions; positions >= capacity are dropped.
+//                            event count), scans its chunk tile by tile (wave_k.h's block_scan_excl: a wave scan, one LDS exchange
+//                            between the waves) and stores the events at their final positions; positions >= capacity are dropped.
 //                            Workgroup 0 of the slot writes *index_out = *index_in + the slot's total: a different word from the
 //                            one every workgroup reads, so there is no ordering requirement inside the launch.
 // A tile's events are expanded position by position: lane p finds the element that owns output position p by a binary search in
@@ -35,12 +35,10 @@ __global__ __launch_bounds__(EMT) void slot_emit_count_kernel(const bmc_slot_t* 
     for (int i = r.lo + 4 * tid; i < r.hi; i += TILE) {
         unsigned q[4];
         load_q4(ps, i, r.hi, vec, mc, q);
-        acc += q[0] + q[1] + q[2] + q[3];
+        acc += sum_q4(q);
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) gst<unsigned>(parts + (long long)s * nparts + part, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    acc = block_fold<NW>(acc, Sum(), wsum);
+    if (tid == 0) gst<unsigned>(parts + (long long)s * nparts + part, acc);
 }
 
 __global__ __launch_bounds__(EMT) void slot_emit_write_kernel(const bmc_slot_t* __restrict__ table,
@@ -60,7 +58,7 @@ __global__ __launch_bounds__(EMT) void slot_emit_write_kernel(const bmc_slot_t* 
     const long long base = gld<long long>(gld<const long long*>(&ent->index_in));
     // events of the parts before this one; workgroup 0 has none before it and adds ALL parts instead: the slot's total
     const unsigned* const pp = parts + (long long)s * nparts;
-    const unsigned long long before = sum_parts(pp, part == 0 ? nparts : part, red, tid);
+    const unsigned long long before = sum_parts<NW>(pp, part == 0 ? nparts : part, red);
     long long gpos = base + (long long)before;
     if (part == 0) {
         if (tid == 0) gst<long long>(gld<long long*>(&ent->index_out), gpos);

@@ -2,7 +2,7 @@
 // _clocked).  A timed stream is "the events of slot_emit.hip, with times", so the quantisation rule, the walk over a slot's
 // prediction and the decoding of an element into an event exist once, here.  slot_emit.hip describes the algorithm.
 #pragma once
-#include "slot_k.h"
+#include "wave_k.h"
 
 namespace {
 
@@ -18,12 +18,21 @@ __device__ __forceinline__ void load_q4(const float* ps, int i, int hi, bool vec
     if (i >= hi) return;
     if (vec) {
         const f32x4 v = gld<f32x4>(ps + i);
-        q[0] = quant(v.x, mc); q[1] = quant(v.y, mc); q[2] = quant(v.z, mc); q[3] = quant(v.w, mc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = quant(v[k], mc);
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             if (i + k < hi) q[k] = quant(gld<float>(ps + i + k), mc);
     }
+}
+
+// the events of a lane's 4 elements
+__device__ __forceinline__ unsigned sum_q4(const unsigned (&q)[4]) {
+    unsigned t = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) t += q[k];
+    return t;
 }
 
 // the slot emits this window: it is active and its emit entry has columns (uniform over the workgroup).  E: bmc_slot_emit_t
@@ -34,53 +43,19 @@ __device__ __forceinline__ bool emits(const bmc_slot_t* table, const E* emit, in
            gld<short*>(&emit[s].xs) != nullptr;
 }
 
-// part p of a grid (nparts, S) owns elements [lo, hi) = [p * chunk, min(n, (p+1) * chunk)) of the slot's n = 2*sH*sW
-struct PartRange {
-    int lo, hi;
-};
-__device__ __forceinline__ PartRange part_range(int part, int chunk, int n) {
-    const long long lo64 = (long long)part * chunk;
-    return PartRange{(int)(lo64 < n ? lo64 : n), (int)(lo64 + chunk < n ? lo64 + chunk : n)};
-}
-
-// pp[0] + .. + pp[cnt - 1] (part totals of a slot) in every thread.  red: NW words of LDS.  Called by all 256 threads.
-__device__ __forceinline__ unsigned long long sum_parts(const unsigned* pp, int cnt, unsigned long long* red, int tid) {
-    unsigned long long acc = 0ull;
-    for (int j = tid; j < cnt; j += EMT) acc += gld<unsigned>(pp + j);
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((tid & 63) == 0) red[tid >> 6] = acc;
-    __syncthreads();
-    return red[0] + red[1] + red[2] + red[3];
-}
-
-// One tile of a part: lane `tid` brings the q of elements tb + 4 * tid .. + 3 (wave scan with cross-lane moves, one LDS
-// exchange between the waves); excl[TILE] <- the exclusive prefix of q inside the tile, -> the tile's events.  wtot: NW words
-// of LDS.  Called by all 256 threads; excl is complete when it returns.
+// One tile of a part: this lane brings the q of elements tb + 4 * tid .. + 3 (block_scan_excl over the lanes' sums);
+// excl[TILE] <- the exclusive prefix of q inside the tile, -> the tile's events.  wtot: NW words of LDS.  Called by all 256
+// threads; excl is complete when it returns.
 __device__ __forceinline__ unsigned tile_scan(const float* ps, int tb, int hi, bool vec, float mc, unsigned* excl, unsigned* wtot,
                                               int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned q[4];
+    unsigned q[4], ttot;
     load_q4(ps, tb + 4 * tid, hi, vec, mc, q);
-    const unsigned t = q[0] + q[1] + q[2] + q[3];
-    unsigned inc = t;                                                 // inclusive scan over the wave
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    unsigned woff = 0u, ttot = 0u;
+    unsigned e = block_scan_excl<NW>(sum_q4(q), wtot, &ttot);
 #pragma unroll
-    for (int w = 0; w < NW; ++w) {
-        const unsigned v = wtot[w];
-        if (w < wave) woff += v;
-        ttot += v;
+    for (int k = 0; k < 4; ++k) {
+        excl[4 * tid + k] = e;
+        e += q[k];
     }
-    const unsigned e0 = woff + inc - t;
-    excl[4 * tid] = e0;
-    excl[4 * tid + 1] = e0 + q[0];
-    excl[4 * tid + 2] = e0 + q[0] + q[1];
-    excl[4 * tid + 3] = e0 + q[0] + q[1] + q[2];
     __syncthreads();
     return ttot;
 }

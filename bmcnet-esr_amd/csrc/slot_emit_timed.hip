@@ -83,15 +83,13 @@ __global__ __launch_bounds__(EMT) void emit_timed_count_kernel(const bmc_slot_t*
     for (int i = r.lo + 4 * tid; i < r.hi; i += TILE) {
         unsigned q[4];
         load_q4(ps, i, r.hi, vec, mc, q);
-        acc += q[0] + q[1] + q[2] + q[3];
+        acc += sum_q4(q);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             for (unsigned j = 0; j < q[k]; ++j) atomicAdd(&lh[gld<unsigned short>(rank + q[k] * 256u + j) & 255u], 1u);
     }
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-    if ((tid & 63) == 0) wsum[tid >> 6] = acc;
-    __syncthreads();
-    if (tid == 0) gst<unsigned>(parts + (long long)s * nparts + part, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
+    acc = block_fold<NW>(acc, Sum(), wsum);                           // (its barrier completes lh too)
+    if (tid == 0) gst<unsigned>(parts + (long long)s * nparts + part, acc);
     gst<unsigned>(hist + ((long long)s * hrows + part) * 256 + tid, lh[tid]);
 }
 
@@ -106,11 +104,11 @@ __global__ __launch_bounds__(EMT) void emit_timed_scan_kernel(const bmc_slot_t* 
                                                               long long wcap) {
     __shared__ unsigned long long red[NW];
     __shared__ unsigned wtot[NW];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x, tid = threadIdx.x;
     if (!emits(table, emit, s)) return;
     unsigned long long total;
     if (first) {
-        total = sum_parts(parts + (long long)s * nparts, nparts, red, tid);
+        total = sum_parts<NW>(parts + (long long)s * nparts, nparts, red);
         if (tid == 0) {
             const bmc_slot_emit_timed_t* const ent = emit + s;
             gst<unsigned long long>(tot + s, total);
@@ -134,18 +132,8 @@ __global__ __launch_bounds__(EMT) void emit_timed_scan_kernel(const bmc_slot_t* 
             running += v[k];
         }
     }
-    unsigned inc = running;                                           // exclusive scan of the digit totals over the workgroup
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = __shfl_up(inc, o);
-        if (lane >= o) inc += v;
-    }
-    if (lane == 63) wtot[wave] = inc;
-    __syncthreads();
-    unsigned woff = 0u;
-#pragma unroll
-    for (int w = 0; w < NW - 1; ++w)
-        if (w < wave) woff += wtot[w];
-    gst<unsigned>(dbase + (long long)s * 256 + tid, woff + inc - running);
+    unsigned all;                                                     // exclusive scan of the digit totals over the workgroup
+    gst<unsigned>(dbase + (long long)s * 256 + tid, block_scan_excl<NW>(running, wtot, &all));
 }
 
 // grid (nparts, S): the events of part p, in flat order, to their positions by low digit in rec[s]

@@ -12,13 +12,14 @@
 //   select   on unsigned integer keys (the counts; a monotone image of the floats for bmc_hot_pixel_mask): the pixels with
 //            key >= kmin are candidates.  At most max_px of them: all are masked (one counting pass -- the common case).  More:
 //            an 8-bit radix select over LDS histograms finds the max_px-th largest key T, every key > T is masked and, of the
-//            keys == T, the first ones in flat order (an ordered prefix count: a contiguous chunk per lane, wave scan with
-//            cross-lane moves, one LDS exchange between the waves, as slot_emit.hip);
+//            keys == T, the first ones in flat order (an ordered prefix count: a contiguous chunk per lane, then wave_k.h's
+//            block_scan_excl over the lanes);
 //   write    the item's mask into the slot's ring and, for the window's last item, into the recording's own outputs.
 // Integers only in every decision, no atomics whose order matters, grid fixed by S: the same bytes run after run, capturable.
 // Pointers read from the tables go through address-space(1) casts (global_* instructions, never flat_*), as in slot_events.hip.
 #include "bmc_common.h"
 #include "slot_encode_k.h"
+#include "wave_k.h"
 
 namespace {
 
@@ -31,21 +32,16 @@ struct Lds {
     unsigned sel[2];
 };
 
-// f(a, b) over the workgroup; every lane gets the result
-template <class F>
-__device__ __forceinline__ unsigned block_reduce(unsigned v, Lds& l, F f) {
-    for (int o = 32; o > 0; o >>= 1) v = f(v, (unsigned)__shfl_xor((int)v, o));
-    __syncthreads();                                                 // (the previous reader of red is done)
-    if ((threadIdx.x & 63) == 0) l.red[threadIdx.x >> 6] = v;
+// op(a, b) over the workgroup; every lane gets the result.  red is used again and again: the leading barrier ends its
+// previous reading
+template <class Op>
+__device__ __forceinline__ unsigned block_reduce(unsigned v, Lds& l, Op op) {
     __syncthreads();
-    unsigned t = l.red[0];
-#pragma unroll
-    for (int w = 1; w < HNW; ++w) t = f(t, l.red[w]);
-    return t;
+    return block_fold_all<HNW>(v, op, l.red);
 }
-__device__ __forceinline__ unsigned block_sum(unsigned v, Lds& l) { return block_reduce(v, l, [](unsigned a, unsigned b) { return a + b; }); }
-__device__ __forceinline__ unsigned block_min(unsigned v, Lds& l) { return block_reduce(v, l, [](unsigned a, unsigned b) { return a < b ? a : b; }); }
-__device__ __forceinline__ unsigned block_max(unsigned v, Lds& l) { return block_reduce(v, l, [](unsigned a, unsigned b) { return a > b ? a : b; }); }
+__device__ __forceinline__ unsigned block_sum(unsigned v, Lds& l) { return block_reduce(v, l, Sum()); }
+__device__ __forceinline__ unsigned block_min(unsigned v, Lds& l) { return block_reduce(v, l, Min()); }
+__device__ __forceinline__ unsigned block_max(unsigned v, Lds& l) { return block_reduce(v, l, Max()); }
 
 // What to mask: every key > T; of the keys == T the first need_eq in flat order; and pixel `extra` (or none: -1).
 struct Decision {
@@ -58,7 +54,7 @@ __device__ __forceinline__ Decision keep_all() { return Decision{0xffffffffu, 0u
 // neg (max_rate < 0): kmin is the key above zero, and the reference's loop, which re-finds the entries it has zeroed, spends
 // what is left of max_px on ONE more pixel: the first in flat order with key >= zero_key, else (every value negative) the
 // first maximum if it reaches ext_kmin.
-__device__ Decision select(const unsigned* keys, int n, unsigned kmin, int max_px, int neg, unsigned zero_key, unsigned ext_kmin,
+__device__ __forceinline__ Decision select(const unsigned* keys, int n, unsigned kmin, int max_px, int neg, unsigned zero_key, unsigned ext_kmin,
                            Lds& l) {
     const int tid = threadIdx.x;
     Decision d = keep_all();
@@ -87,7 +83,8 @@ __device__ Decision select(const unsigned* keys, int n, unsigned kmin, int max_p
         }
         return d;
     }
-    // more candidates than max_px: the max_px-th largest key, digit by digit from the top
+    // more candidates than max_px: the max_px-th largest key, digit by digit from the top.  The largest comes first: digit dg
+    // counts into the mirrored bin 255 - dg, and wave 0 picks the bin of the 0-based rank k - 1 from bin 0 (digit_pick)
     unsigned prefix = 0u, pmask = 0u, k = (unsigned)max_px;
     for (int shift = 24; shift >= 0; shift -= 8) {
         __syncthreads();
@@ -95,16 +92,12 @@ __device__ Decision select(const unsigned* keys, int n, unsigned kmin, int max_p
         __syncthreads();
         for (int p = tid; p < n; p += HT) {
             const unsigned key = gld<unsigned>(keys + p);
-            if ((key & pmask) == prefix) atomicAdd(&l.hist[(key >> shift) & 255u], 1u);
+            if ((key & pmask) == prefix) atomicAdd(&l.hist[(~key >> shift) & 255u], 1u);
         }
         __syncthreads();
-        if (tid == 0) {
-            unsigned cum = 0u;
-            for (int dg = 255; dg >= 0; --dg) {
-                const unsigned h = l.hist[dg];
-                if (cum + h >= k) { l.sel[0] = (unsigned)dg; l.sel[1] = k - cum; break; }
-                cum += h;
-            }
+        if (tid < 64) {
+            const DigitPick dp = digit_pick(l.hist, k - 1u, tid);
+            if (dp.found) { l.sel[0] = 255u - dp.bin; l.sel[1] = dp.rank + 1u; }
         }
         __syncthreads();
         prefix |= l.sel[0] << shift;
@@ -119,7 +112,7 @@ __device__ Decision select(const unsigned* keys, int n, unsigned kmin, int max_p
 // out(p, masked) for every pixel; -> the number of masked pixels (on every lane)
 template <class F>
 __device__ unsigned apply(const unsigned* keys, int n, const Decision& d, Lds& l, F out) {
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x;
     unsigned nm = 0u;
     if (d.need_eq == 0u) {
         for (int p = tid; p < n; p += HT) {
@@ -134,16 +127,8 @@ __device__ unsigned apply(const unsigned* keys, int n, const Decision& d, Lds& l
     const int lo = (int)(lo64 < n ? lo64 : n), hi = (int)(lo64 + chunk < n ? lo64 + chunk : n);
     unsigned eq = 0u;
     for (int p = lo; p < hi; ++p) eq += gld<unsigned>(keys + p) == d.T ? 1u : 0u;
-    unsigned inc = eq;                                               // inclusive scan over the wave
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned v = (unsigned)__shfl_up((int)inc, o);
-        if (lane >= o) inc += v;
-    }
-    __syncthreads();
-    if (lane == 63) l.red[wave] = inc;
-    __syncthreads();
-    unsigned before = inc - eq;
-    for (int w = 0; w < wave; ++w) before += l.red[w];
+    __syncthreads();                                                 // (the previous reader of red is done)
+    unsigned all, before = block_scan_excl<HNW>(eq, l.red, &all);    // the keys == T of the lanes below, in flat order
     for (int p = lo; p < hi; ++p) {
         const unsigned key = gld<unsigned>(keys + p);
         bool m = key > d.T || p == d.extra;

@@ -35,23 +35,6 @@ __device__ __forceinline__ bool quality_slot(const bmc_slot_t* table, const bmc_
            q.dst != nullptr;
 }
 
-struct Add {
-    __device__ __forceinline__ double operator()(double a, double b) const { return a + b; }
-};
-struct Max {
-    __device__ __forceinline__ double operator()(double a, double b) const { return b > a ? b : a; }
-};
-struct Min {
-    __device__ __forceinline__ double operator()(double a, double b) const { return b < a ? b : a; }
-};
-
-// the lanes of a wave folded in a fixed tree (lane 0 holds the result)
-template <class Op>
-__device__ __forceinline__ double wave_fold(double v, Op op) {
-    for (int o = 32; o > 0; o >>= 1) v = op(v, __shfl_down(v, o));
-    return v;
-}
-
 // grid (nparts, S): part p owns elements p * QT + tid + j * nparts * QT of the slot's n = 2*gh*gw, as slot_metrics_kernel
 __global__ __launch_bounds__(QT) void quality_stats_kernel(const bmc_slot_t* __restrict__ table,
                                                            const bmc_slot_quality_t* __restrict__ quality,
@@ -83,18 +66,20 @@ __global__ __launch_bounds__(QT) void quality_stats_kernel(const bmc_slot_t* __r
         else mx0 = g > mx0 ? g : mx0;
         mn = g < mn ? g : mn;
     }
-    const double v[7] = {wave_fold(e0, Add()), wave_fold(e1, Add()), wave_fold(b0, Add()), wave_fold(b1, Add()),
-                         wave_fold(mx0, Max()), wave_fold(mx1, Max()), wave_fold(mn, Min())};
-    if ((tid & 63) == 0)
-#pragma unroll
-        for (int k = 0; k < 7; ++k) sh[k][tid >> 6] = v[k];
+    wave_fold_to(e0, Sum(), sh[0]);
+    wave_fold_to(e1, Sum(), sh[1]);
+    wave_fold_to(b0, Sum(), sh[2]);
+    wave_fold_to(b1, Sum(), sh[3]);
+    wave_fold_to(mx0, Max(), sh[4]);
+    wave_fold_to(mx1, Max(), sh[5]);
+    wave_fold_to(mn, Min(), sh[6]);
     __syncthreads();
     if (tid < BMC_QUALITY_STATS_WORDS) {                   // word `tid` of the part: its waves' values folded in wave order
-        double r = 0.0;
-        if (tid < 7) {
-            r = sh[tid][0];
-            for (int k = 1; k < QT / 64; ++k) r = tid < 4 ? r + sh[tid][k] : tid < 6 ? Max()(r, sh[tid][k]) : Min()(r, sh[tid][k]);
-        }
+        constexpr int QW = QT / 64;
+        const double r = tid < 4   ? lds_fold<QW>(sh[tid], Sum())
+                         : tid < 6 ? lds_fold<QW>(sh[tid], Max())
+                         : tid < 7 ? lds_fold<QW>(sh[tid], Min())
+                                   : 0.0;
         gst<double>(stats + ((long long)s * nparts + part) * BMC_QUALITY_STATS_WORDS + tid, r);
     }
 }

@@ -13,7 +13,7 @@
 // Integer LDS atomics only, no global atomics, no workgroup waits for another, grids fixed by the arguments: the same bytes run
 // after run, capturable.  The float32 arithmetic that decides a byte is written with __f*_rn intrinsics: never contracted into an
 // FMA, the division correctly rounded.  Pointers read from the tables go through address-space(1) casts (slot_k.h).
-#include "slot_k.h"
+#include "wave_k.h"
 
 namespace {
 
@@ -101,22 +101,10 @@ __global__ __launch_bounds__(RT) void slot_render_select_kernel(const bmc_slot_t
         __syncthreads();
         if (wave < NR) {                                             // wave r: the digit of rank r; a lane holds four bins
             const unsigned* const h = hist[pick(rep[0], rep[1], rep[2], rep[3], wave)];
-            const unsigned kk = pick(k[0], k[1], k[2], k[3], wave);
-            const unsigned b0 = h[4 * lane], b1 = h[4 * lane + 1], b2 = h[4 * lane + 2], b3 = h[4 * lane + 3];
-            const unsigned sum = b0 + b1 + b2 + b3;
-            unsigned inc = sum;                                      // inclusive scan over the wave
-            for (int o = 1; o < 64; o <<= 1) {
-                const unsigned v = (unsigned)__shfl_up((int)inc, o);
-                if (lane >= o) inc += v;
-            }
-            const unsigned before = inc - sum;
-            if (before <= kk && kk < inc) {                          // exactly one lane: the bins before it hold `before` keys
-                unsigned d = 0u, cum = before;
-                if (kk >= cum + b0) { cum += b0; d = 1u; }
-                if (d == 1u && kk >= cum + b1) { cum += b1; d = 2u; }
-                if (d == 2u && kk >= cum + b2) { cum += b2; d = 3u; }
-                sel[wave][0] = 4u * lane + d;
-                sel[wave][1] = kk - cum;
+            const DigitPick dp = digit_pick(h, pick(k[0], k[1], k[2], k[3], wave), lane);
+            if (dp.found) {                                          // exactly one lane
+                sel[wave][0] = dp.bin;
+                sel[wave][1] = dp.rank;
             }
         }
         __syncthreads();

@@ -40,25 +40,16 @@ __global__ __launch_bounds__(EMT) void slot_voxel_reduce_kernel(const bmc_slot_t
     for (int i = r.lo + 4 * tid; i < r.hi; i += TILE) {
         unsigned q[4];
         load_q4(ps, i, r.hi, vec, mc, q);
-        acc += q[0] + q[1] + q[2] + q[3];
+        acc += sum_q4(q);
         const unsigned a = q[0] > q[1] ? q[0] : q[1], b = q[2] > q[3] ? q[2] : q[3], m = a > b ? a : b;
         big = big > m ? big : m;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        acc += __shfl_down(acc, o);
-        const unsigned v = __shfl_down(big, o);
-        big = big > v ? big : v;
-    }
-    if ((tid & 63) == 0) {
-        wsum[tid >> 6] = acc;
-        wmax[tid >> 6] = big;
-    }
-    __syncthreads();
+    acc = block_fold<NW>(acc, Sum(), wsum);
+    big = block_fold<NW>(big, Max(), wmax);
     if (tid == 0) {
-        const unsigned a = wmax[0] > wmax[1] ? wmax[0] : wmax[1], b = wmax[2] > wmax[3] ? wmax[2] : wmax[3];
         unsigned* const pp = parts + 2ll * s * nparts + part;
-        gst<unsigned>(pp, wsum[0] + wsum[1] + wsum[2] + wsum[3]);
-        gst<unsigned>(pp + nparts, a > b ? a : b);
+        gst<unsigned>(pp, acc);
+        gst<unsigned>(pp + nparts, big);
     }
 }
 
@@ -86,16 +77,11 @@ __global__ __launch_bounds__(EMT) void slot_voxel_kernel(const bmc_slot_t* __res
         const unsigned v = gld<unsigned>(pp + nparts + j);
         big = big > v ? big : v;
     }
-    for (int o = 32; o > 0; o >>= 1) {
-        const unsigned v = __shfl_down(big, o);
-        big = big > v ? big : v;
-    }
-    if ((tid & 63) == 0) wmax[tid >> 6] = big;
-    const unsigned long long total = sum_parts(pp, nparts, red, tid);                     // (its barrier covers wmax too)
-    const unsigned a = wmax[0] > wmax[1] ? wmax[0] : wmax[1], b = wmax[2] > wmax[3] ? wmax[2] : wmax[3];
+    big = block_fold_all<NW>(big, Max(), wmax);
+    const unsigned long long total = sum_parts<NW>(pp, nparts, red);
     const bool live = total > 3ull;                                   // events_to_voxel_torch :122: len(ts) <= 3 -> zeros
     const float t_first = (float)BMC_EVENT_T0;
-    const float t_last = (a > b ? a : b) >= 2u ? (float)BMC_EVENT_T1 : (float)BMC_EVENT_T0;
+    const float t_last = big >= 2u ? (float)BMC_EVENT_T1 : (float)BMC_EVENT_T0;
     const float dt = (t_last - t_first) + 1e-6f;
     const float bm1 = (float)(bins - 1);
     const float* const p0 = pred + 2ll * s * hw;

@@ -3,7 +3,7 @@
 // include/bmc_hip_ssim.h and include/bmc_hip_quality.h promise is written here once, so the two launches give the same bits
 // for the same pixels and range by construction (tests/test_gpu_ssim_tiles_shared.py).
 #pragma once
-#include "slot_k.h"
+#include "wave_k.h"
 
 namespace {
 
@@ -75,7 +75,8 @@ struct SsimTile {
     }
 
     // S of the tile's positions inside the ph x pw positions of the image (an exact 0.0 for the others), folded over the lanes
-    // in a fixed tree and over the waves as ((w0 + w1) + w2) + w3: the partial, on thread 0.  Holds a barrier.
+    // in a fixed tree and over the waves as ((w0 + w1) + w2) + w3 (wave_k.h's block_fold): the partial, on thread 0.  Holds a
+    // barrier.
     __device__ __forceinline__ double sum(int y0, int x0, int ph, int pw, double C1, double C2) {
 #pragma clang fp contract(off)      // every float64 operation is rounded on its own, as the contracts write them
         const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -94,10 +95,7 @@ struct SsimTile {
                 acc += in ? S : 0.0;
             }
         }
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_down(acc, o);
-        if (lane == 0) wsum[wave] = acc;
-        __syncthreads();
-        return threadIdx.x == 0 ? ((wsum[0] + wsum[1]) + wsum[2]) + wsum[3] : 0.0;
+        return block_fold<SW>(acc, Sum(), wsum);
     }
 };
 

@@ -138,6 +138,32 @@ def test_any_number_of_parts_gives_the_same_stream(nparts):
         _check_slot(got[s], preds[s], True, [0, 11, 0][s], counts[s] + 20, 255)
 
 
+def _with_silent_waves(P, parts):
+    """P with whole waves of a scan tile silenced.  A tile is 1 024 consecutive elements, 256 per wave, and with `parts` parts of
+    2 048 elements the tiles start at multiples of 1 024: wave 1 of tile 0, wave 0 of tile 2 and wave 3 of tile 3 emit nothing,
+    and neither does the whole last part."""
+    flat = P.copy().reshape(-1)
+    assert flat.size == 2048 * parts and parts >= 3
+    for lo in (256, 2048, 3 * 1024 + 768):
+        flat[lo:lo + 256] = -1.0
+    flat[2048 * (parts - 1):] = -1.0
+    return flat.reshape(P.shape)
+
+
+def test_a_wave_and_a_part_without_events():
+    """Zero wave totals in the tile scan and a zero part total in the sum of the parts before a part."""
+    dev = _gpu()
+    rng = np.random.default_rng(64)
+    sH, sW, parts = 32, 96, 3                                          # 6 144 elements: three parts of two tiles
+    P = _synthetic(rng, sH, sW)
+    P = _with_silent_waves(np.where(quantise_np(P) > 0, P, np.float32(1.0)), parts)       # every other element emits
+    q = quantise_np(P).reshape(-1)
+    assert q[256:512].sum() == 0 and q[2048:2304].sum() == 0 and q[4096:].sum() == 0 and (q[:256] > 0).all()
+    n = int(q.sum())
+    (got,) = _emit_once(dev, P[None], [True], [True], [3], [3 + n + 9], 255, nparts=parts)
+    assert _check_slot(got, P, True, 3, 3 + n + 9, 255) == n
+
+
 def test_emit_refuses_bad_arguments():
     dev = _gpu()
     from bmc_hip import slots

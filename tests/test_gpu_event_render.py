@@ -72,6 +72,20 @@ def test_render_event_counts_many_chunks_and_a_batch():
         assert torch.equal(out, again)                                         # the same bytes run after run
 
 
+def test_render_ranks_that_differ_in_the_last_digit_only():
+    """16 x 16 planes whose 256 values are 256 neighbouring float32: the keys of the select agree in their top three digits, so
+    the four ranks of the two percentiles share one histogram for three passes and part in the last."""
+    dev = _gpu()
+    from bmc_hip.encodings import render_event_counts
+    rng = np.random.default_rng(1616)
+    bits = np.stack([0x40000000 + rng.permutation(256), 0x3F800100 + rng.permutation(256)]).astype(np.uint32)
+    cnt = bits.view(np.float32).reshape(2, 16, 16)
+    srt = np.sort(bits[0])
+    assert len({int(v) >> 8 for v in srt}) == 1 and len({int(srt[k]) & 255 for k in (2, 3, 252, 253)}) == 4
+    out = render_event_counts(torch.tensor(cnt)[None].to(dev))
+    assert _np(out[0]).tobytes() == R.render_np(cnt).tobytes()
+
+
 @pytest.mark.parametrize("h,w", [(7, 9), (31, 57), (64, 64)])
 def test_slot_render_touches_only_its_slots(h, w):
     """Slot 0 active with a destination at an odd address (byte stores), slot 1 active at an aligned one (word stores), slot 2

@@ -13,7 +13,7 @@ from event_times_ref import emit_timed_np, times_np
 from test_gpu_r2 import _gpu, _restore_math_mode  # noqa: F401
 from test_gpu_multistream import SCALE, _model
 from test_gpu_event_slots import _dev
-from test_gpu_event_output import SENT16, SENT8, _event_recording, _frames, _synthetic
+from test_gpu_event_output import SENT16, SENT8, _event_recording, _frames, _synthetic, _with_silent_waves
 
 pytestmark = pytest.mark.gpu
 
@@ -147,6 +147,18 @@ def test_any_number_of_parts_gives_the_same_timed_stream(nparts):
     got = _emit_timed_once(dev, preds, [True] * 3, [True] * 3, [0, 11, 0], [c + 20 for c in counts], 255, max(counts), nparts=nparts)
     for s in range(3):
         _check_timed_slot(got[s], preds[s], True, [0, 11, 0][s], counts[s] + 20, 255, max(counts))
+
+
+def test_a_wave_and_a_part_without_timed_events():
+    """Zero wave totals in the tile scan of the expand launch and a zero part total (test_gpu_event_output states the layout)."""
+    dev = _gpu()
+    rng = np.random.default_rng(65)
+    sH, sW, parts = 32, 96, 3
+    P = _synthetic(rng, sH, sW)
+    P = _with_silent_waves(np.where(quantise_np(P) > 0, P, np.float32(1.0)), parts)
+    n = int(quantise_np(P).sum())
+    (got,) = _emit_timed_once(dev, P[None], [True], [True], [3], [3 + n + 9], 255, n, nparts=parts)
+    assert _check_timed_slot(got, P, True, 3, 3 + n + 9, 255, n) == n
 
 
 def test_window_scratch_overflow_stores_nothing_and_counts():

@@ -42,6 +42,46 @@ def test_get_hot_event_mask_equals_the_reference():
         get_hot_event_mask(torch.zeros(2, 2, device=dev, dtype=torch.float64), 9)
 
 
+def _bits(words):
+    return np.asarray(words, np.uint32).view(np.float32)
+
+
+def _tie_cases():
+    """(name, rate [37, 53], max_px): more candidates than max_px on a frame of 1 961 pixels (two per lane of the select's
+    workgroup), so the radix select runs and keys equal to the threshold T must be cut in flat order."""
+    H, W = 37, 53
+    n = H * W
+    yield "uniform", np.full((H, W), 0.9, np.float32), 5                      # every key == T; the cut falls inside a lane's chunk
+    flat = np.full(n, 0.1, np.float32)                                        # T's keys over the waves, at both places of a chunk
+    ties = np.arange(3, n, 97)
+    flat[ties] = 0.9
+    flat[[130, 777, 1500]] = 0.95
+    assert len(ties) == 21 and len(set(ties // 128)) >= 10 and len(set(ties % 2)) == 2
+    yield "spread", flat.reshape(H, W), 3 + 11
+    # T = 0x3F6600FF: the select's third pass picks digit 0 (digit 1 above it), its fourth digit 255 (smaller digits below it)
+    rng = np.random.default_rng(5)
+    flat = np.full(n, 0.1, np.float32)
+    pos = rng.permutation(n)
+    flat[pos[:40]] = _bits(0x3F660100 + rng.integers(0, 256, 40))
+    flat[pos[40:70]] = _bits([0x3F6600FF] * 30)
+    flat[pos[70:270]] = _bits(0x3F660000 + rng.integers(0, 255, 200))
+    assert flat[pos[:270]].min() > np.float32(0.8)
+    yield "digit_ends", flat.reshape(H, W), 40 + 13
+
+
+def test_get_hot_event_mask_cuts_ties_in_flat_order():
+    """Ties at the threshold of the radix select, against the restatement of the reference's loop, byte for byte."""
+    dev = _gpu()
+    from bmc_hip.encodings import get_hot_event_mask
+    for name, rate, max_px in _tie_cases():
+        want_mask, want_after = R.get_hot_event_mask_np(rate, 9, max_px, 5, 0.8)
+        assert (want_mask == 0).sum() == max_px < (rate > np.float32(0.8)).sum(), name
+        t = torch.tensor(rate).to(dev)
+        m = get_hot_event_mask(t, 9, max_px=max_px, min_obvs=5, max_rate=0.8)
+        assert m.cpu().numpy().tobytes() == want_mask.tobytes(), name
+        assert t.cpu().numpy().tobytes() == want_after.tobytes(), name
+
+
 # ------------------------------------------------------------------ (b) bmc_slot_hot_update
 PARAMS = {"ties": (3, 2, 0.6), "max_px_0": (0, 2, 0.6), "negative_rate": (1 << 20, 1, -0.5), "rate_1": (7, 1, 1.0),
           "all_active": (100, 1, 0.5)}

@@ -370,6 +370,66 @@ def test_voxel_long_segments_are_sorted_cooperatively():
     assert dt < 0.5
 
 
+# One scan launch (csrc/scatter.hip::table_scan_kernel, 1 024 threads a table) serves the binned encoder, the voxel frames and the
+# torch-tensor image: tables of one entry, of one entry more or less than its threads, and of several entries per thread.
+@pytest.mark.parametrize("nframes", [1, 1023, 1024, 1025, 3000])
+def test_scan_lengths_binned_encoder(nframes):
+    """3 x 5 frames are one row band each, so the (frame, band) table has nframes entries; some frames are empty."""
+    dev = _gpu()
+    from bmc_hip import ops
+    from oracle import bmc_oracle as O
+    H, W = 3, 5
+    rng = np.random.default_rng(nframes)
+    counts = rng.integers(0, 7, nframes)
+    counts[0] = 6
+    n = int(counts.sum())
+    xs = rng.uniform(-1.0, W + 1.0, n).astype(np.float32)
+    ys = rng.uniform(-1.0, H + 1.0, n).astype(np.float32)
+    ps = rng.choice([-1.0, 1.0], n).astype(np.float32)
+    bounds = np.concatenate([[0], np.cumsum(counts)])
+    off = torch.tensor(bounds, dtype=torch.int64, device=dev)
+    old = ops.BINNED_MIN_PIXELS
+    try:
+        ops.BINNED_MIN_PIXELS = 0                            # force the binned path
+        assert ops._binned_ws(n, nframes, H, W, dev) is not None
+        got = ops.events_to_channels_batched(*(torch.tensor(a, device=dev) for a in (xs, ys, ps)), off, H, W, mutate=False)
+    finally:
+        ops.BINNED_MIN_PIXELS = old
+    got = got.cpu().numpy()
+    for f in range(nframes):
+        a, b = bounds[f], bounds[f + 1]
+        assert np.array_equal(got[f], O.events_to_channels_np(xs[a:b], ys[a:b], ps[a:b], (H, W))[0]), f
+
+
+@pytest.mark.parametrize("H,W", [(1, 1), (33, 31), (32, 32), (25, 41), (45, 80)])
+def test_scan_lengths_voxel_frames_and_torch_image(H, W):
+    """Tables of 1, 1 023, 1 024, 1 025 and 3 600 pixels: three voxel frames (one table each, the middle frame empty) and the
+    single table of events_to_image_torch, against the numpy oracle, bit for bit."""
+    dev = _gpu()
+    from bmc_hip import encodings as E, ops
+    from oracle import bmc_oracle as O
+    rng = np.random.default_rng(H * 100 + W)
+    bins, m = 5, 2 * H * W + 9
+    counts = [m, 0, m + 3]
+    n = sum(counts)
+    xs = np.floor(rng.uniform(-0.2, W + 0.2, n)).astype(np.float32)
+    ys = np.floor(rng.uniform(-0.2, H + 0.2, n)).astype(np.float32)
+    ts = np.concatenate([np.sort(rng.uniform(0, 1, c)) for c in counts]).astype(np.float32)
+    ps = rng.choice([-1.0, 1.0], n).astype(np.float32)        # polarities, as in this file's other voxel cases
+    bounds = np.concatenate([[0], np.cumsum(counts)])
+    d = [torch.tensor(a, device=dev) for a in (xs, ys, ts, ps)]
+    got = ops.events_to_voxel_batched(d[0], d[1], d[2], d[3], torch.tensor(bounds, dtype=torch.int64, device=dev), bins, H, W)
+    for f in range(len(counts)):
+        a, b = bounds[f], bounds[f + 1]
+        ref, xa, ya = O.events_to_voxel_np(xs[a:b], ys[a:b], ts[a:b], ps[a:b], bins, (H, W))
+        assert np.array_equal(got[f].cpu().numpy(), ref), f
+        assert np.array_equal(d[0][a:b].cpu().numpy(), xa) and np.array_equal(d[1][a:b].cpu().numpy(), ya), f
+    pw = rng.standard_normal(n).astype(np.float32)            # the image adds arbitrary weights in event order
+    ref = O.events_to_image_torch_np(xs.copy(), ys.copy(), pw.copy(), (H, W))
+    img = E.events_to_image_torch(*(torch.tensor(a.copy(), device=dev) for a in (xs, ys, pw)), sensor_size=(H, W))
+    assert np.array_equal(img.cpu().numpy(), ref)
+
+
 # ------------------------------------------------------------------ Winograd F(2x2, 3x3) convolution kernel (csrc/wino.hip)
 @pytest.fixture(params=[8, 4], ids=["rows8", "rows4"])
 def force_wino(request, monkeypatch):
