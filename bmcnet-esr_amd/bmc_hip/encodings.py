@@ -600,7 +600,7 @@ def image_quality(img, ref, data_range="gt", raw=False):
     return dict(psnr=psnr, ssim=ssim, raw=rec) if raw else dict(psnr=psnr, ssim=ssim)
 
 
-def counts_to_events(pred, max_count=255, times=None, spans=None):
+def counts_to_events(pred, max_count=255, times=None, spans=None, cuts=None):
     """The event stream of count images: pred [B,2,sH,sW] (fp32, on the GPU; e.g. what StreamingSR.step returns) ->
     (xs int16, ys int16, ps int8, index [B+1] int64 on the host); image b owns events [index[b], index[b+1]).  Per element v in
     the flat order of [2,sH,sW]: q = min(rint(v), max_count) for v > 0, else 0 (round-half-to-even: the rounded count image the
@@ -613,8 +613,12 @@ def counts_to_events(pred, max_count=255, times=None, spans=None):
     bmc_slot_emit_timed (include/bmc_hip.h states the contract).
     spans [B,2] (with times="linear"; float64 on the host): (t_first, t_last) of every image on the sensor's clock -> ts is
     FLOAT64 on that clock, t = t_first + tau * (t_last - t_first) with tau the float64 time above from the reduced fraction
-    (bmc_slot_emit_clocked); events and order are the same."""
-    from . import slots
+    (bmc_slot_emit_clocked); events and order are the same.
+    cuts [B] (with spans; float64 on the host, +inf allowed, no NaN): image b keeps exactly its events with ts < cuts[b] -- a
+    prefix of its sorted events, the same bytes, trimmed before the sort (bmc_slot_emit_trimmed; include/bmc_hip_stream.h states
+    the contract) -> (xs, ys, ps, ts, index, dropped): index counts the kept events, dropped [B] int64 on the host those cut off."""
+    import numpy as np
+    from . import slots, stream_lib
     if times not in (None, "linear"):
         raise ValueError("counts_to_events: times must be None or 'linear' (got %r)" % (times,))
     timed = times is not None
@@ -629,16 +633,26 @@ def counts_to_events(pred, max_count=255, times=None, spans=None):
         raise ValueError("counts_to_events: times='linear' needs max_count <= %d (got %d)" % (slots.MAX_COUNT_TIMED, max_count))
     if spans is not None:
         spans = check_spans("counts_to_events: ", spans, pred.shape[0])
+    if cuts is not None:
+        if spans is None:
+            raise ValueError("counts_to_events: cuts needs spans (the clock the cut is made on)")
+        cuts = np.asarray(cuts.cpu() if torch.is_tensor(cuts) else cuts)
+        if cuts.shape != (pred.shape[0],) or cuts.dtype.kind not in "fiu":
+            raise ValueError("counts_to_events: cuts must hold one number per image (got %s %s)" % (cuts.dtype, cuts.shape))
+        cuts = cuts.astype(np.float64)
+        if np.isnan(cuts).any():
+            raise ValueError("counts_to_events: a cut must not be NaN")
     if not pred.is_cuda:
         raise RuntimeError("counts_to_events: pred must live on the MI355X (no CPU fallback in this build)")
     pred = pred.contiguous()
     B, _, sH, sW = pred.shape
     dev = pred.device
-    clocked = spans is not None
+    clocked, trimmed = spans is not None, cuts is not None
     nparts = slots.emit_parts(sH, sW)
     groups = [(a, min(a + slots.MAX_SLOTS, B)) for a in range(0, B, slots.MAX_SLOTS)]
-    tables = {b - a: slots.SlotTable(b - a, dev, emit=True, timed=timed, clock=clocked) for a, b in groups}
-    parts = torch.zeros(min(B, slots.MAX_SLOTS) * nparts, dtype=torch.int32, device=dev)
+    tables = {b - a: slots.SlotTable(b - a, dev, emit=True, timed=timed, clock=clocked, trim=trimmed) for a, b in groups}
+    parts = torch.zeros((stream_lib.TRIM_PARTS if trimmed else 1) * min(B, slots.MAX_SLOTS) * nparts, dtype=torch.int32, device=dev)
+    dropped = torch.zeros(B, dtype=torch.int64, device=dev) if trimmed else None
     start = torch.zeros(B, dtype=torch.int64, device=dev)
     end = torch.zeros(B, dtype=torch.int64, device=dev)
 
@@ -656,6 +670,9 @@ def counts_to_events(pred, max_count=255, times=None, spans=None):
                 if clocked:
                     ck = t.clock_host()
                     ck[s]["t_first"], ck[s]["t_last"], ck[s]["ts"] = spans[a + s, 0], spans[a + s, 1], ts.data_ptr()
+                if trimmed:
+                    tr = t.trim_host()
+                    tr[s]["t_cut"], tr[s]["dropped"] = cuts[a + s], dropped.data_ptr() + 8 * (a + s)
                 elif timed:
                     em[s]["ts"] = ts.data_ptr()
             t.upload()
@@ -663,7 +680,8 @@ def counts_to_events(pred, max_count=255, times=None, spans=None):
                 if scratch is None:
                     scratch = torch.empty(slots.emit_timed_scratch_bytes(min(B, slots.MAX_SLOTS), nparts, window),
                                           dtype=torch.uint8, device=dev)
-                (slots.emit_clocked if clocked else slots.emit_timed)(t, pred[a:b], max_count, nparts, parts, scratch, window)
+                emit = slots.emit_trimmed if trimmed else slots.emit_clocked if clocked else slots.emit_timed
+                emit(t, pred[a:b], max_count, nparts, parts, scratch, window)
             else:
                 slots.emit(t, pred[a:b], max_count, nparts, parts)
 
@@ -677,14 +695,14 @@ def counts_to_events(pred, max_count=255, times=None, spans=None):
     index[1:] = counts.cumsum(0)
     total = int(index[B])
     if total == 0:
-        return (none[0][:0], none[1][:0], none[2][:0]) + ((no_ts[:0],) if timed else ()) + (index,)
+        return (none[0][:0], none[1][:0], none[2][:0]) + ((no_ts[:0],) if timed else ()) + (index,) + ((dropped.cpu(),) if trimmed else ())
     xs, ys = torch.empty(total, dtype=torch.int16, device=dev), torch.empty(total, dtype=torch.int16, device=dev)
     ps = torch.empty(total, dtype=torch.int8, device=dev)
     start.copy_(index[:B])
     if timed:
         ts = torch.empty(total, dtype=ts_dtype, device=dev)
         run(xs, ys, ps, total, ts, int(counts.max()))
-        return xs, ys, ps, ts, index
+        return (xs, ys, ps, ts, index) + ((dropped.cpu(),) if trimmed else ())
     run(xs, ys, ps, total)
     return xs, ys, ps, index
 

@@ -26,6 +26,11 @@ Clocked event output: SlotTable(emit=True, timed=True, clock=True) adds a fourth
 (SLOT_CLOCK_DTYPE: the window's time span on the recording's clock and a float64 `ts` column); emit_clocked() is emit_timed()
 whose slots with a clock entry store float64 times on that clock instead (the same launches, the same counter).
 
+Continuous event output (csrc/slot_emit_trimmed.hip; include/bmc_hip_stream.h states the contract): SlotTable(emit=True,
+timed=True, clock=True, trim=True) adds a table of bmc_slot_trim_t entries (SLOT_TRIM_DTYPE: the window's cut and where its
+dropped count goes) as the LAST section; emit_trimmed() is emit_clocked() that emits only a window's events before its cut,
+trimmed before the sort (the same launches, the same counter).
+
 Hot-pixel filter (csrc/slot_hot.hip; include/bmc_hip.h "hot-pixel filter" states the contract): SlotTable(events=True, hot=True)
 adds a table of bmc_slot_hot_t entries (SLOT_HOT_DTYPE) behind the others; hot_update() folds the newly observed items of every
 filtered slot into its counts and writes their masks into the slot's ring (one call = HOT_KERNELS launch for all slots, counted in
@@ -47,7 +52,7 @@ QUALITY_KERNELS launches, counted in QUALITY_LAUNCHES); quality_values() finishe
 import numpy as np
 import torch
 
-from . import lib, quality_lib
+from . import lib, quality_lib, stream_lib
 from .ops import _stream
 
 # the header's limits and table layouts (include/bmc_hip.h), as the library states them
@@ -77,6 +82,7 @@ MAX_COUNT_TIMED = lib.const("BMC_SLOT_EMIT_TIMED_MAX_COUNT")       # the rank ta
 MAX_WINDOW_CAPACITY = lib.const("BMC_SLOT_EMIT_TIMED_MAX_WINDOW")
 EVENT_T0, EVENT_T1 = lib.const("BMC_EVENT_T0"), lib.const("BMC_EVENT_T1")      # the window's time axis
 SLOT_CLOCK_DTYPE = lib.dtype("bmc_slot_clock_t")
+SLOT_TRIM_DTYPE = stream_lib.dtype("bmc_slot_trim_t")
 _RANK_TABLES = {}
 SLOT_HOT_DTYPE = lib.dtype("bmc_slot_hot_t")
 HOT_LAUNCHES = 0
@@ -100,17 +106,21 @@ QUALITY_TILE_H, QUALITY_TILE_W = quality_lib.const("BMC_QUALITY_TILE_H"), qualit
 QUALITY_STATS_WORDS = quality_lib.const("BMC_QUALITY_STATS_WORDS")
 
 
-def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False, quality=False):
+def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False, quality=False,
+                 trim=False):
     """The sections of a slot table of S slots -> ([(name, dtype, byte offset), ...] in their order in memory, total bytes):
     "slot" (bmc_slot_t) always, then "events", "emit" (bmc_slot_emit_timed_t entries with timed=True), "clock" (needs timed) and
     "hot" (needs events), each S entries behind the one before, "render" (render tables of S entries each), "voxel"
-    (voxel=True or False: S bmc_slot_voxel_t entries) and "quality" (quality=True or False: S bmc_slot_quality_t entries)."""
+    (voxel=True or False: S bmc_slot_voxel_t entries), "quality" (quality=True or False: S bmc_slot_quality_t entries) and "trim"
+    (needs clock: S bmc_slot_trim_t entries) -- the last section, so every other one lies where it lies without it."""
     if timed and not emit:
         raise ValueError("slots: timed=True needs emit=True")
     if clock and not timed:
         raise ValueError("slots: clock=True needs timed=True")
     if hot and not events:
         raise ValueError("slots: hot=True needs events=True")
+    if trim and not clock:
+        raise ValueError("slots: trim=True needs clock=True")
     if isinstance(render, bool) or not isinstance(render, int) or not 0 <= render <= MAX_RENDER_TABLES:
         raise ValueError("slots: render must be a number of tables, 0 .. %d (got %r)" % (MAX_RENDER_TABLES, render))
     if not isinstance(voxel, (bool, np.bool_)):
@@ -122,7 +132,7 @@ def table_layout(S, events=False, emit=False, timed=False, clock=False, hot=Fals
                                ("emit", SLOT_EMIT_TIMED_DTYPE if timed else SLOT_EMIT_DTYPE, int(bool(emit))),
                                ("clock", SLOT_CLOCK_DTYPE, int(bool(clock))), ("hot", SLOT_HOT_DTYPE, int(bool(hot))),
                                ("render", SLOT_RENDER_DTYPE, render), ("voxel", SLOT_VOXEL_DTYPE, int(voxel)),
-                               ("quality", SLOT_QUALITY_DTYPE, int(quality))):
+                               ("quality", SLOT_QUALITY_DTYPE, int(quality)), ("trim", SLOT_TRIM_DTYPE, int(bool(trim)))):
         if count:
             sections.append((name, dtype, nbytes))
             nbytes += count * S * dtype.itemsize
@@ -136,19 +146,19 @@ class SlotTable:
     The other sections of table_layout() share the tensor and the copy: `events_host()` / `events_ptr()` (events=True),
     `emit_host()` / `emit_ptr()` (emit=True; timed=True: bmc_slot_emit_timed_t entries), `clock_host()` / `clock_ptr()`
     (clock=True, needs timed), `hot_host()` / `hot_ptr()` (hot=True, needs events), `render_host()` [K,S] / `render_ptr(k)`
-    (render=K tables), `voxel_host()` / `voxel_ptr()` (voxel=True), `quality_host()` / `quality_ptr()` (quality=True).  The *_host() views are those of the window being filled, after host(), which cleared them."""
+    (render=K tables), `voxel_host()` / `voxel_ptr()` (voxel=True), `quality_host()` / `quality_ptr()` (quality=True), `trim_host()` / `trim_ptr()` (trim=True, needs clock).  The *_host() views are those of the window being filled, after host(), which cleared them."""
 
     RING = 4
 
     def __init__(self, S, device, events=False, emit=False, timed=False, clock=False, hot=False, render=0, voxel=False,
-                 quality=False):
+                 quality=False, trim=False):
         if not 1 <= S <= MAX_SLOTS:
             raise ValueError("slots: 1 <= S <= %d (got %d)" % (MAX_SLOTS, S))
         self.S = S
         self.events, self.emit, self.timed, self.clock, self.hot = bool(events), bool(emit), bool(timed), bool(clock), bool(hot)
         self.render = render
-        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render, voxel, quality)
-        self.voxel, self.quality = bool(voxel), bool(quality)
+        sections, nbytes = table_layout(S, self.events, self.emit, self.timed, self.clock, self.hot, render, voxel, quality, trim)
+        self.voxel, self.quality, self.trim = bool(voxel), bool(quality), bool(trim)
         self._at = {name: (dtype, off) for name, dtype, off in sections}
         self.dev = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         self._pinned = [torch.zeros(nbytes, dtype=torch.uint8, pin_memory=True) for _ in range(self.RING)]
@@ -191,6 +201,9 @@ class SlotTable:
     def quality_host(self):
         return self._host("quality")
 
+    def trim_host(self):
+        return self._host("trim")
+
     def upload(self):
         k = self._k
         self.dev.copy_(self._pinned[k], non_blocking=True)
@@ -224,6 +237,9 @@ class SlotTable:
 
     def quality_ptr(self):
         return self._ptr("quality")
+
+    def trim_ptr(self):
+        return self._ptr("trim")
 
 
 def _check(cond, what):
@@ -458,15 +474,17 @@ def emit_parts(sH, sW):
     return max(1, min(MAX_EMIT_PARTS, -(-2 * sH * sW // 4096)))
 
 
-def _check_emit_args(table, pred, max_count, nparts, parts):
-    """The prediction and the part totals of emit() / emit_timed() (max_count and nparts are in range) -> (S, sH, sW)."""
+def _check_emit_args(table, pred, max_count, nparts, parts, words=1):
+    """The prediction and the part totals (`words` per slot and part) of emit() / emit_timed() (max_count and nparts are in
+    range) -> (S, sH, sW)."""
     _check(torch.is_tensor(pred) and pred.dim() == 4 and pred.shape[1] == 2 and pred.is_cuda and pred.is_contiguous()
            and pred.dtype == torch.float32 and pred.shape[0] == table.S, "pred must be a contiguous fp32 GPU tensor [S,2,sH,sW]")
     S, _, sH, sW = pred.shape
     _check(max(sH, sW) <= MAX_COUNT_LIMIT, "predictions larger than %d pixels a side cannot be emitted (int16 coordinates)"
            % MAX_COUNT_LIMIT)
     _check(torch.is_tensor(parts) and parts.is_cuda and parts.dtype == torch.int32 and parts.is_contiguous()
-           and parts.numel() >= S * nparts, "parts must be a contiguous int32 GPU tensor of at least S * nparts words")
+           and parts.numel() >= words * S * nparts,
+           "parts must be a contiguous int32 GPU tensor of at least %sS * nparts words" % ("%d * " % words if words > 1 else ""))
     _check((-(-2 * sH * sW // nparts) + 3) // 4 * 4 * max_count < 2 ** 32,
            "a part's event total would overflow 32 bits: use more parts")
     return S, sH, sW
@@ -635,6 +653,18 @@ def emit_clocked(table, pred, max_count, nparts, parts, scratch, window_capacity
     _emit_timed(True, table, pred, max_count, nparts, parts, scratch, window_capacity)
 
 
+def emit_trimmed(table, pred, max_count, nparts, parts, scratch, window_capacity):
+    """emit_clocked() on a table with trim entries (bmc_slot_emit_trimmed; include/bmc_hip_stream.h states the contract): a
+    clocked slot emits exactly the events of emit_clocked() whose float64 time is < its trim entry's t_cut -- a prefix of the
+    sorted window, with the same bytes -- found BEFORE the sort; *index_out <- *index_in + the kept count, both capacity rules
+    apply to the kept events, and the entry's `dropped` address (0: none) receives the number of events cut off.  A slot
+    without a `ts` column in its clock entry is not trimmed.  The arguments and launches of emit_clocked() (counted in
+    EMIT_TIMED_LAUNCHES), but parts: at least stream_lib.TRIM_PARTS * S * nparts words."""
+    _check(table.clock and getattr(table, "trim", False),
+           "the slot table has no trim entries (SlotTable(emit=True, timed=True, clock=True, trim=True))")
+    _emit_timed("trimmed", table, pred, max_count, nparts, parts, scratch, window_capacity)
+
+
 def _emit_timed(clocked, table, pred, max_count, nparts, parts, scratch, window_capacity):
     global EMIT_TIMED_LAUNCHES
     _check(table.emit and table.timed,
@@ -643,14 +673,17 @@ def _emit_timed(clocked, table, pred, max_count, nparts, parts, scratch, window_
            "timed emission needs 1 <= max_count <= %d (got %r)" % (MAX_COUNT_TIMED, max_count))
     _check(isinstance(nparts, int) and 1 <= nparts <= MAX_EMIT_PARTS, "1 <= nparts <= %d (emit)" % MAX_EMIT_PARTS)
     _check_window_capacity(window_capacity)
-    S, sH, sW = _check_emit_args(table, pred, max_count, nparts, parts)
+    S, sH, sW = _check_emit_args(table, pred, max_count, nparts, parts, stream_lib.TRIM_PARTS if clocked == "trimmed" else 1)
     need = emit_timed_scratch_bytes(S, nparts, window_capacity)
     _check(torch.is_tensor(scratch) and scratch.is_cuda and scratch.dtype == torch.uint8 and scratch.is_contiguous()
            and scratch.numel() >= need and scratch.data_ptr() % 8 == 0,
            "scratch must be a contiguous 8-byte aligned uint8 GPU tensor of at least %d bytes" % need)
     tail = (S, pred.data_ptr(), sH, sW, max_count, nparts, parts.data_ptr(), emit_rank_table(pred.device).data_ptr(),
             scratch.data_ptr(), int(window_capacity), _stream())
-    if clocked:
+    if clocked == "trimmed":
+        lib.call(stream_lib._slot_emit_trimmed, "bmc_slot_emit_trimmed", table.ptr(), table.emit_ptr(), table.clock_ptr(),
+                 table.trim_ptr(), *tail)
+    elif clocked:
         lib.call(lib._slot_emit_clocked, "bmc_slot_emit_clocked", table.ptr(), table.emit_ptr(), table.clock_ptr(), *tail)
     else:
         lib.call(lib._slot_emit_timed, "bmc_slot_emit_timed", table.ptr(), table.emit_ptr(), *tail)

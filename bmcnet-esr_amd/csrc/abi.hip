@@ -20,6 +20,7 @@
 #include "bmc_hip_ssim.h"
 #include "bmc_hip_denoise.h"
 #include "bmc_hip_downsample.h"
+#include "bmc_hip_stream.h"
 
 #define BMC_ABI_FUNCTIONS(X) \
     X(bmc_version) X(bmc_last_error) X(bmc_stream_create_low_priority) X(bmc_events_to_channels) X(bmc_events_binned_ws_bytes) \
@@ -117,6 +118,12 @@
     X(BMC_DOWNSAMPLE_MAX_SCALE) X(BMC_DOWNSAMPLE_MAX_THRESHOLD) X(BMC_DOWNSAMPLE_LANES) X(BMC_DOWNSAMPLE_TILE) \
     X(BMC_DOWNSAMPLE_MAX_PARTS) X(BMC_DOWNSAMPLE_LAUNCHES)
 
+/* include/bmc_hip_stream.h, the companion header of the continuous (trimmed) event stream: likewise, bmc_stream_abi()
+ * (bmc_hip/stream_lib.py binds from it; tests/test_event_stream_cpu.py compares the lists with that header's text). */
+#define BMC_STREAM_ABI_FUNCTIONS(X) X(bmc_slot_emit_trimmed) X(bmc_stream_abi)
+#define BMC_STREAM_ABI_STRUCTS(X) X(bmc_slot_trim_t, F(t_cut), F(dropped))
+#define BMC_STREAM_ABI_CONSTANTS(X) X(BMC_SLOT_TRIM_PARTS)
+
 namespace {
 
 struct field {
@@ -157,6 +164,7 @@ template <class T> constexpr bool tiles() {
 BMC_ABI_STRUCTS(BMC_ABI_LAYOUT)
 BMC_QUALITY_ABI_STRUCTS(BMC_ABI_LAYOUT)
 BMC_EMA_ABI_STRUCTS(BMC_ABI_LAYOUT)
+BMC_STREAM_ABI_STRUCTS(BMC_ABI_LAYOUT)
 
 template <class Fn> struct signature;
 template <class R, class... A> struct signature<R (*)(A...)> {
@@ -206,3 +214,4 @@ BMC_ABI_TEXT(bmc_ema_abi, BMC_EMA_ABI_FUNCTIONS, BMC_EMA_ABI_STRUCTS, BMC_ABI_NO
 BMC_ABI_TEXT(bmc_ssim_abi, BMC_SSIM_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_SSIM_ABI_CONSTANTS)
 BMC_ABI_TEXT(bmc_denoise_abi, BMC_DENOISE_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_DENOISE_ABI_CONSTANTS)
 BMC_ABI_TEXT(bmc_downsample_abi, BMC_DOWNSAMPLE_ABI_FUNCTIONS, BMC_ABI_NONE, BMC_DOWNSAMPLE_ABI_CONSTANTS)
+BMC_ABI_TEXT(bmc_stream_abi, BMC_STREAM_ABI_FUNCTIONS, BMC_STREAM_ABI_STRUCTS, BMC_STREAM_ABI_CONSTANTS)

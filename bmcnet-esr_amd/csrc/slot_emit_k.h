@@ -1,5 +1,5 @@
-// What the two event-output files share (internal): slot_emit.hip (bmc_slot_emit) and slot_emit_timed.hip (bmc_slot_emit_timed /
-// _clocked).  A timed stream is "the events of slot_emit.hip, with times", so the quantisation rule, the walk over a slot's
+// What the event-output files share (internal): slot_emit.hip (bmc_slot_emit), slot_emit_timed.hip (bmc_slot_emit_timed /
+// _clocked) and slot_emit_trimmed.hip (bmc_slot_emit_trimmed).  A timed stream is "the events of slot_emit.hip, with times", so the quantisation rule, the walk over a slot's
 // prediction and the decoding of an element into an event exist once, here.  slot_emit.hip describes the algorithm.
 #pragma once
 #include "wave_k.h"
@@ -43,13 +43,21 @@ __device__ __forceinline__ bool emits(const bmc_slot_t* table, const E* emit, in
            gld<short*>(&emit[s].xs) != nullptr;
 }
 
+// every event of an element is emitted: the `pick` of tile_scan that changes nothing
+struct AllEvents {
+    __device__ __forceinline__ void operator()(unsigned (&)[4], int) const {}
+};
+
 // One tile of a part: this lane brings the q of elements tb + 4 * tid .. + 3 (block_scan_excl over the lanes' sums);
 // excl[TILE] <- the exclusive prefix of q inside the tile, -> the tile's events.  wtot: NW words of LDS.  Called by all 256
-// threads; excl is complete when it returns.
+// threads; excl is complete when it returns.  pick(q, e): may lower the q of the tile's elements e .. e+3 before they are
+// scanned (the trimmed output emits the first keep[q] events of an element).
+template <class Pick = AllEvents>
 __device__ __forceinline__ unsigned tile_scan(const float* ps, int tb, int hi, bool vec, float mc, unsigned* excl, unsigned* wtot,
-                                              int tid) {
+                                              int tid, Pick pick = Pick()) {
     unsigned q[4], ttot;
     load_q4(ps, tb + 4 * tid, hi, vec, mc, q);
+    pick(q, 4 * tid);
     unsigned e = block_scan_excl<NW>(sum_q4(q), wtot, &ttot);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -78,6 +86,57 @@ __device__ __forceinline__ void store_event(short* xs, short* ys, signed char* p
     gst<signed char>(pol + pos, (signed char)(c ? -1 : 1));
 }
 
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+
+constexpr int T2 = BMC_SLOT_EMIT_TIMED_BLOCK;   // records per workgroup of the high-digit pass
+
+// One step of the stable split: every lane brings at most one record (digit d; !valid: none), the records of a step are in
+// sequence order by (wave, lane) and the steps of a workgroup follow one another.  run[d] = the position of the next record
+// of digit d (it starts at the workgroup's offset for the digit); stepc[w][d] = 0 between steps.  Called by all 256 threads.
+__device__ __forceinline__ unsigned place(unsigned* run, unsigned (*stepc)[256], bool valid, unsigned d, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+    unsigned long long peers = __ballot(valid);                       // -> the lanes of this wave with the same digit
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const bool bit = (d >> b) & 1u;
+        const unsigned long long m = __ballot(valid && bit);
+        peers &= bit ? m : ~m;
+    }
+    const unsigned below = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
+    if (valid && below == 0u) stepc[wave][d] = (unsigned)__popcll(peers);
+    __syncthreads();
+    unsigned r = 0u;
+    if (valid) {
+        r = run[d] + below;
+#pragma unroll
+        for (int w = 0; w < NW - 1; ++w)
+            if (w < wave) r += stepc[w][d];
+    }
+    __syncthreads();
+    run[tid] += stepc[0][tid] + stepc[1][tid] + stepc[2][tid] + stepc[3][tid];     // thread t owns digit t
+    stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
+    __syncthreads();
+    return r;
+}
+
+// float64 time of event j of n on the clock [t_first, t_first + dt]: tau from the REDUCED fraction (Euclid on 8-bit values: at
+// most 12 steps for j <= n - 1 <= 254), then a multiply and an add that are rounded separately (no fma contraction).
+__device__ __forceinline__ double clock_time(double t_first, double dt, unsigned j, unsigned nq) {
+#pragma clang fp contract(off)
+    double tau = BMC_EVENT_T0;
+    if (nq > 1u) {
+        unsigned a = j, b = nq - 1u;
+        for (int it = 0; it < 16 && b != 0u; ++it) {
+            const unsigned r = a % b;
+            a = b;
+            b = r;
+        }
+        tau = BMC_EVENT_T0 + (BMC_EVENT_T1 - BMC_EVENT_T0) * (double)(j / a) / (double)((nq - 1u) / a);
+    }
+    const double span = tau * dt;
+    return t_first + span;
+}
+
 // elements per slot and per part of a launch, and whether a lane may load its 4 elements as one f32x4
 struct EmitGeom {
     int n, chunk, vec;
@@ -104,3 +163,34 @@ static inline int emit_geometry(const char* who, const void* table, const void* 
 }
 
 }  // namespace
+
+// What slot_emit_trimmed.hip (bmc_slot_emit_trimmed) shares with slot_emit_timed.hip, which defines the three functions: the
+// argument checks and the scratch layout of a timed call, and the launches that are the same kernels in both -- the first scan
+// and the high-digit pass.  Host code, internal to the library.
+struct EmitTimedPlan {
+    const bmc_slot_t* table;
+    const bmc_slot_emit_timed_t* emit;
+    const bmc_slot_clock_t* clock;
+    int S, sH, sW, nparts, blocks, hrows;
+    EmitGeom g;
+    float mc;                           // max_count
+    const float* pred;
+    unsigned* parts;
+    const unsigned short* rank;
+    u32x2* rec;                         // the scratch: records [S][wcap], totals [S], digit bases [S][256], histograms [S][hrows][256]
+    unsigned long long* tot;
+    unsigned* dbase;
+    unsigned* hist;
+    long long wcap;
+    hipStream_t st;
+};
+// -> 0 and the plan, or -1 with the error set (`who` names the entry point)
+__attribute__((visibility("hidden"))) int bmc_emit_timed_plan(const char* who, const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit,
+                                                              const bmc_slot_clock_t* clock, int S, const float* pred, int sH, int sW,
+                                                              int max_count, int nparts, unsigned* parts,
+                                                              const unsigned short* rank_table, void* scratch,
+                                                              long long window_capacity, bmc_stream_t s, EmitTimedPlan* p);
+// scan 1 (after the count launch): the slot's total, *index_out, offsets over (digit, part) -> 0, or -2
+__attribute__((visibility("hidden"))) int bmc_emit_timed_scan_parts(const EmitTimedPlan& p);
+// histogram, scan 2, scatter (after the expand launch) -> 0, or -2
+__attribute__((visibility("hidden"))) int bmc_emit_timed_high_pass(const EmitTimedPlan& p);

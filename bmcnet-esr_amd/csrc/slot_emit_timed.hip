@@ -27,42 +27,13 @@
 // t = t_first + tau * (t_last - t_first), tau = T0 + (T1 - T0) * (j / g) / ((n - 1) / g), g = gcd(j, n - 1) -- the reduced
 // fraction gives equal rationals ONE tau, so the float64 column cannot decrease inside a run of ties.  Only the scatter
 // kernel reads the clock table; a NULL table (bmc_slot_emit_timed) or a NULL `ts` keeps the float32 behaviour.
+//
+// place() and clock_time() live in slot_emit_k.h: slot_emit_trimmed.hip (bmc_slot_emit_trimmed) splits and times its events
+// with them, and launches this file's first scan, histogram, second scan and scatter kernel through bmc_emit_timed_plan /
+// _scan_parts / _high_pass below.
 #include "slot_emit_k.h"
 
 namespace {
-
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-
-constexpr int T2 = BMC_SLOT_EMIT_TIMED_BLOCK;   // records per workgroup of the high-digit pass
-
-// One step of the stable split: every lane brings at most one record (digit d; !valid: none), the records of a step are in
-// sequence order by (wave, lane) and the steps of a workgroup follow one another.  run[d] = the position of the next record
-// of digit d (it starts at the workgroup's offset for the digit); stepc[w][d] = 0 between steps.  Called by all 256 threads.
-__device__ __forceinline__ unsigned place(unsigned* run, unsigned (*stepc)[256], bool valid, unsigned d, int tid) {
-    const int lane = tid & 63, wave = tid >> 6;
-    unsigned long long peers = __ballot(valid);                       // -> the lanes of this wave with the same digit
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const unsigned long long m = __ballot(valid && bit);
-        peers &= bit ? m : ~m;
-    }
-    const unsigned below = (unsigned)__popcll(peers & ((1ull << lane) - 1ull));
-    if (valid && below == 0u) stepc[wave][d] = (unsigned)__popcll(peers);
-    __syncthreads();
-    unsigned r = 0u;
-    if (valid) {
-        r = run[d] + below;
-#pragma unroll
-        for (int w = 0; w < NW - 1; ++w)
-            if (w < wave) r += stepc[w][d];
-    }
-    __syncthreads();
-    run[tid] += stepc[0][tid] + stepc[1][tid] + stepc[2][tid] + stepc[3][tid];     // thread t owns digit t
-    stepc[0][tid] = stepc[1][tid] = stepc[2][tid] = stepc[3][tid] = 0u;
-    __syncthreads();
-    return r;
-}
 
 // grid (nparts, S): part p owns elements [p * chunk, min(n, (p+1) * chunk)) of the slot's n = 2*sH*sW
 __global__ __launch_bounds__(EMT) void emit_timed_count_kernel(const bmc_slot_t* __restrict__ table,
@@ -196,24 +167,6 @@ __global__ __launch_bounds__(EMT) void emit_timed_hist_kernel(const bmc_slot_t* 
     gst<unsigned>(hist + ((long long)s * hrows + b) * 256 + tid, lh[tid]);
 }
 
-// float64 time of event j of n on the clock [t_first, t_first + dt]: tau from the REDUCED fraction (Euclid on 8-bit values: at
-// most 12 steps for j <= n - 1 <= 254), then a multiply and an add that are rounded separately (no fma contraction).
-__device__ __forceinline__ double clock_time(double t_first, double dt, unsigned j, unsigned nq) {
-#pragma clang fp contract(off)
-    double tau = BMC_EVENT_T0;
-    if (nq > 1u) {
-        unsigned a = j, b = nq - 1u;
-        for (int it = 0; it < 16 && b != 0u; ++it) {
-            const unsigned r = a % b;
-            a = b;
-            b = r;
-        }
-        tau = BMC_EVENT_T0 + (BMC_EVENT_T1 - BMC_EVENT_T0) * (double)(j / a) / (double)((nq - 1u) / a);
-    }
-    const double span = tau * dt;
-    return t_first + span;
-}
-
 // grid (blocks, S): records [b * T2, ...) of rec[s], in their order, to the columns at *index_in + position by high digit.
 // clock: NULL, or the table of bmc_slot_emit_clocked; a slot with clock[s].ts stores float64 clock times there, not ts.
 __global__ __launch_bounds__(EMT) void emit_timed_scatter_kernel(const bmc_slot_t* __restrict__ table,
@@ -281,12 +234,10 @@ extern "C" long long bmc_slot_emit_timed_scratch_bytes(int S, int nparts, long l
     return (long long)S * (8 * window_capacity + 8 + 1024 + 1024 * hist_rows(nparts, window_capacity));
 }
 
-namespace {
-
-// the six launches of bmc_slot_emit_timed (clock == NULL) and bmc_slot_emit_clocked; `who` names the entry point in messages
-int emit_timed_launch(const char* who, const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock,
-                      int S, const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
-                      const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s) {
+int bmc_emit_timed_plan(const char* who, const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock,
+                        int S, const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
+                        const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s,
+                        EmitTimedPlan* p) {
     BMC_CHECK_ARG(rank_table && scratch, "%s: bad arguments", who);
     BMC_CHECK_ARG(max_count >= 1 && max_count <= BMC_SLOT_EMIT_TIMED_MAX_COUNT,
                   "%s: 1 <= max_count <= %d (the rank table; got %d)", who, BMC_SLOT_EMIT_TIMED_MAX_COUNT, max_count);
@@ -296,34 +247,58 @@ int emit_timed_launch(const char* who, const bmc_slot_t* table, const bmc_slot_e
     BMC_CHECK_ARG(((unsigned long long)pred & 3ull) == 0 && ((unsigned long long)scratch & 7ull) == 0 &&
                       ((unsigned long long)rank_table & 1ull) == 0,
                   "%s: pred must be 4-byte, scratch 8-byte, rank_table 2-byte aligned", who);
-    EmitGeom g;
-    if (emit_geometry(who, table, emit, pred, parts, S, sH, sW, max_count, nparts, &g)) return -1;
-    const int blocks = (int)((window_capacity + T2 - 1) / T2), hrows = (int)hist_rows(nparts, window_capacity);
-    u32x2* const rec = (u32x2*)scratch;
-    unsigned long long* const tot = (unsigned long long*)(rec + (long long)S * window_capacity);
-    unsigned* const dbase = (unsigned*)(tot + S);
-    unsigned* const hist = dbase + (long long)S * 256;
-    const hipStream_t st = (hipStream_t)s;
-    hipLaunchKernelGGL(emit_timed_count_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, g.n, g.chunk, g.vec,
-                       (float)max_count, rank_table, parts, hist, hrows);
-    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (count)");
-    hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(S), dim3(EMT), 0, st, table, emit, 1, nparts, (const unsigned*)parts, hist,
-                       hrows, dbase, tot, window_capacity);
+    if (emit_geometry(who, table, emit, pred, parts, S, sH, sW, max_count, nparts, &p->g)) return -1;
+    p->table = table, p->emit = emit, p->clock = clock, p->S = S, p->sH = sH, p->sW = sW, p->nparts = nparts;
+    p->blocks = (int)((window_capacity + T2 - 1) / T2), p->hrows = (int)hist_rows(nparts, window_capacity);
+    p->mc = (float)max_count, p->pred = pred, p->parts = parts, p->rank = rank_table, p->wcap = window_capacity;
+    p->rec = (u32x2*)scratch;
+    p->tot = (unsigned long long*)(p->rec + (long long)S * window_capacity);
+    p->dbase = (unsigned*)(p->tot + S);
+    p->hist = p->dbase + (long long)S * 256;
+    p->st = (hipStream_t)s;
+    return 0;
+}
+
+int bmc_emit_timed_scan_parts(const EmitTimedPlan& p) {
+    hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(p.S), dim3(EMT), 0, p.st, p.table, p.emit, 1, p.nparts, (const unsigned*)p.parts,
+                       p.hist, p.hrows, p.dbase, p.tot, p.wcap);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scan 1)");
-    hipLaunchKernelGGL(emit_timed_expand_kernel, dim3(nparts, S), dim3(EMT), 0, st, table, emit, pred, g.n, g.chunk, g.vec,
-                       (float)max_count, rank_table, (const unsigned*)hist, hrows, (const unsigned*)dbase,
-                       (const unsigned long long*)tot, window_capacity, rec);
-    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (expand)");
-    hipLaunchKernelGGL(emit_timed_hist_kernel, dim3(blocks, S), dim3(EMT), 0, st, table, emit, hist, hrows,
-                       (const unsigned long long*)tot, window_capacity, (const u32x2*)rec);
+    return 0;
+}
+
+int bmc_emit_timed_high_pass(const EmitTimedPlan& p) {
+    hipLaunchKernelGGL(emit_timed_hist_kernel, dim3(p.blocks, p.S), dim3(EMT), 0, p.st, p.table, p.emit, p.hist, p.hrows,
+                       (const unsigned long long*)p.tot, p.wcap, (const u32x2*)p.rec);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (histogram)");
-    hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(S), dim3(EMT), 0, st, table, emit, 0, nparts, (const unsigned*)parts, hist,
-                       hrows, dbase, tot, window_capacity);
+    hipLaunchKernelGGL(emit_timed_scan_kernel, dim3(p.S), dim3(EMT), 0, p.st, p.table, p.emit, 0, p.nparts, (const unsigned*)p.parts,
+                       p.hist, p.hrows, p.dbase, p.tot, p.wcap);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scan 2)");
-    hipLaunchKernelGGL(emit_timed_scatter_kernel, dim3(blocks, S), dim3(EMT), 0, st, table, emit, clock, sH, sW, (const unsigned*)hist,
-                       hrows, (const unsigned*)dbase, (const unsigned long long*)tot, window_capacity, (const u32x2*)rec);
+    hipLaunchKernelGGL(emit_timed_scatter_kernel, dim3(p.blocks, p.S), dim3(EMT), 0, p.st, p.table, p.emit, p.clock, p.sH, p.sW,
+                       (const unsigned*)p.hist, p.hrows, (const unsigned*)p.dbase, (const unsigned long long*)p.tot, p.wcap,
+                       (const u32x2*)p.rec);
     BMC_CHECK_LAUNCH("bmc_slot_emit_timed (scatter)");
     return 0;
+}
+
+namespace {
+
+// the six launches of bmc_slot_emit_timed (clock == NULL) and bmc_slot_emit_clocked; `who` names the entry point in messages
+int emit_timed_launch(const char* who, const bmc_slot_t* table, const bmc_slot_emit_timed_t* emit, const bmc_slot_clock_t* clock,
+                      int S, const float* pred, int sH, int sW, int max_count, int nparts, unsigned* parts,
+                      const unsigned short* rank_table, void* scratch, long long window_capacity, bmc_stream_t s) {
+    EmitTimedPlan p;
+    if (bmc_emit_timed_plan(who, table, emit, clock, S, pred, sH, sW, max_count, nparts, parts, rank_table, scratch, window_capacity,
+                            s, &p))
+        return -1;
+    hipLaunchKernelGGL(emit_timed_count_kernel, dim3(nparts, S), dim3(EMT), 0, p.st, table, emit, pred, p.g.n, p.g.chunk, p.g.vec,
+                       p.mc, rank_table, parts, p.hist, p.hrows);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (count)");
+    if (const int rc = bmc_emit_timed_scan_parts(p)) return rc;
+    hipLaunchKernelGGL(emit_timed_expand_kernel, dim3(nparts, S), dim3(EMT), 0, p.st, table, emit, pred, p.g.n, p.g.chunk, p.g.vec,
+                       p.mc, rank_table, (const unsigned*)p.hist, p.hrows, (const unsigned*)p.dbase,
+                       (const unsigned long long*)p.tot, window_capacity, p.rec);
+    BMC_CHECK_LAUNCH("bmc_slot_emit_timed (expand)");
+    return bmc_emit_timed_high_pass(p);
 }
 
 }  // namespace

@@ -267,6 +267,7 @@ class MultiStreamSR:
       quality=True | dict(...)    Quality          esr_psnr / esr_ssim / bicubic_psnr / bicubic_ssim per window (needs a ground truth)
       keep_predictions            KeptPredictions  predictions [n_windows,2,sH,sW]
       emit_events, event_times    EventStream      the super-resolved event stream: plain, timed, or on the sensor's clock
+      continuous=True             EventStream      ... every window trimmed to what no later window covers: one stream in time order
       render=(kinds...)           Pictures         the reference's event-count images
       voxel_bins=B                VoxelGrids       the voxel grid of every window's events
 
@@ -289,7 +290,7 @@ class MultiStreamSR:
 
     def __init__(self, model, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, keep_predictions=False,
                  seqn=3, emit_events=False, max_count=255, event_times=None, hot_filter=None, render=None, voxel_bins=None,
-                 self_ensemble=None, quality=None):
+                 self_ensemble=None, quality=None, continuous=False):
         self.hot_filter = check_hot_filter("MultiStreamSR: ", hot_filter)  # (the argument `slots` hides the module here)
         self.self_ensemble = check_group_size("MultiStreamSR: ", self_ensemble, int(slots))
         self.render = self.check_render("MultiStreamSR: ", render)
@@ -301,7 +302,8 @@ class MultiStreamSR:
         if isinstance(max_count, bool) or not isinstance(max_count, int) or not 1 <= max_count <= self.MAX_COUNT_LIMIT:
             raise ValueError("MultiStreamSR: max_count must be an integer, 1 <= max_count <= %d (got %r)"
                              % (self.MAX_COUNT_LIMIT, max_count))
-        EventStream.check(emit_events, event_times, max_count)
+        EventStream.check(emit_events, event_times, max_count, continuous)
+        self.continuous = bool(continuous)
         self.voxel_bins, self.event_times = VoxelGrids.check(voxel_bins, max_count), event_times
         self._wcap = 0             # events per window the sort scratch holds (the largest window_event_capacity so far)
         self.model = model.eval()
@@ -626,7 +628,7 @@ class MultiStreamSR:
         """The table entries of the window `plan`, into the table's host copy."""
         t = self._bufs["table"]
         v = {"slot": t.host()}                             # host() first: it clears the copy the other views look into
-        for name in ("events", "emit", "clock", "hot", "render", "voxel", "quality"):
+        for name in ("events", "emit", "clock", "hot", "render", "voxel", "quality", "trim"):
             if getattr(t, name, False):                    # (a table without the section: no views of it)
                 v[name] = getattr(t, name + "_host")()
         K = self.self_ensemble or 1                        # the plan is of groups of K slots: the parts fill the leader's entries
@@ -679,7 +681,8 @@ class MultiStreamSR:
 
 def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False, graph=False, state_dtype=None, seqn=3,
                         gt_size=None, keep_predictions=False, emit_events=False, max_count=255, event_capacity=None, event_times=None,
-                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None, self_ensemble=None, quality=None):
+                        window_event_capacity=None, hot_filter=None, render=None, voxel_bins=None, self_ensemble=None, quality=None,
+                        continuous=False):
     """infer_BMCNet.py mode 1 (:248-295) through MultiStreamSR: recordings = {name: (frames [L,2,H,W], gts [L,2,gh,gw])}
     (or a sequence of such pairs, named "0", "1", ...) of one sensor size; an item may also be an EventRecording (raw event
     columns + index tables, encoded window by window: MultiStreamSR.open_events).  A recording WITHOUT ground truth is
@@ -703,11 +706,14 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     bicubic_ssim for the recordings with ground truth: the mean over the windows whose value is FINITE -- an exact window has an
     infinite PSNR, an empty ground-truth channel no SSIM -- and, under the key + "_nonfinite", how many windows that left out;
     mean[key] is the mean over the recordings with a finite value, mean[key + "_nonfinite"] the total of the counts):
-    MultiStreamSR's options."""
+    MultiStreamSR's options.  continuous=True (with event_times="linear"; every recording must bring its clock, which of the items above
+    only an HREventRecording does): one stream in time order per recording (MultiStreamSR(continuous=True)); the result then
+    carries sr_dropped = {name: [events trimmed per window]}."""
     items = list(recordings.items()) if isinstance(recordings, dict) else [(str(i), r) for i, r in enumerate(recordings)]
     ms = MultiStreamSR(model, slots, n_c=n_c, scale=scale, plain=plain, graph=graph, state_dtype=state_dtype,
                        keep_predictions=keep_predictions, seqn=seqn, emit_events=emit_events, max_count=max_count, event_times=event_times,
-                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, self_ensemble=self_ensemble, quality=quality)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, self_ensemble=self_ensemble, quality=quality,
+                       continuous=continuous)
     handles = []
     for name, r in items:
         if isinstance(r, EventRecording):
@@ -730,7 +736,7 @@ def evaluate_recordings(model, recordings, slots, n_c=128, scale=4, plain=False,
     breakdown = {k: {} for k in ("esr_mse", "bicubic_mse", "time", "params")}
     # results() key -> is it on; an output of that name collects it per recording (sr_events with the recording's sr_index)
     wanted = (("predictions", keep_predictions), ("sr_events", emit_events), ("sr_ts", event_times is not None),
-              ("images", ms.render), ("voxels", ms.voxel_bins is not None))
+              ("images", ms.render), ("voxels", ms.voxel_bins is not None), ("sr_dropped", ms.continuous))
     extra = {k: {} for k, on in wanted if on}
     if ms.quality is not None:
         breakdown.update({k + tail: {} for k in Quality.KEYS for tail in ("", "_nonfinite")})

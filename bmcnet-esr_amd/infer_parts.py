@@ -19,7 +19,7 @@ session keeps its parts in the launch order of a window and loops over them:
 import numpy as np
 import torch
 
-from bmc_hip import lib, slots
+from bmc_hip import lib, slots, stream_lib
 from bmc_hip.encodings import check_spans
 from bmc_hip.ops import _stream
 
@@ -288,23 +288,38 @@ class EventStream(Part):
     sr_ts is then FLOAT64, t = t_first + tau * (t_last - t_first) with tau the window time above computed from the reduced
     fraction of j / (n - 1) (bmc_slot_emit_clocked; include/bmc_hip.h states the contract) -- the inverse of
     event_formatting's normalisation (dataloader/base_dataset.py:30) without its 1e-6.  Each window is in time order; with
-    sliding_window < window the spans of consecutive windows overlap, so the concatenation of a recording's windows is
-    globally sorted only for non-overlapping spans.  Clocked and unclocked recordings may share a session; the first clocked
+    sliding_window < window the spans of consecutive windows overlap, so the concatenation of a recording's windows carries
+    every stretch of sensor time as often as items cover it and is not in time order -- unless the session is continuous
+    (below).  Clocked and unclocked recordings may share a session; the first clocked
     one adds the table's clock section, a larger window_event_capacity a larger sort scratch (either invalidates the graph).
+
+    ONE CONTINUOUS STREAM (continuous=True; needs event_times="linear", and every recording spans / lr_ts): window i, which
+    predicts item i+1, emits only its events with t < t_cut = spans[i+2][0], the start of the item the next window predicts
+    (+inf for the recording's last window): bmc_slot_emit_trimmed, include/bmc_hip_stream.h states the contract.  The kept
+    events are a prefix of the window's sorted events with the same bytes, found BEFORE the sort (the same six launches), so
+    sr_events / sr_ts of a recording are globally non-decreasing in time and cover every instant once; with spans that do not
+    overlap nothing is dropped and every byte equals the option off.  sr_index, event_capacity and window_event_capacity
+    count KEPT events; results() also carries sr_dropped, the events every window lost to its cut (written by the kernel: no
+    host sync).  The t_first column of the spans must not decrease over the items the windows predict.
 
     The part is in every session: without emit_events it only refuses the arguments that need it."""
 
     @staticmethod
-    def check(emit_events, event_times, max_count):
+    def check(emit_events, event_times, max_count, continuous=False):
         if event_times not in (None, "linear"):
             raise ValueError("MultiStreamSR: event_times must be None or 'linear' (got %r)" % (event_times,))
         if event_times is not None and not emit_events:
             raise ValueError("MultiStreamSR: event_times needs emit_events=True")
         if event_times is not None and max_count > slots.MAX_COUNT_TIMED:
             raise ValueError("MultiStreamSR: event_times needs max_count <= %d (got %d)" % (slots.MAX_COUNT_TIMED, max_count))
+        if not isinstance(continuous, (bool, np.bool_)):
+            raise ValueError("MultiStreamSR: continuous must be True or False (got %r)" % (continuous,))
+        if continuous and event_times != "linear":
+            raise ValueError("MultiStreamSR: continuous=True needs event_times='linear' (the cut is made on the events' clock)")
 
     def table(self, ms):
-        return {"emit": ms.emit_events, "timed": ms.event_times is not None, "clock": ms._has_clock}
+        return {"emit": ms.emit_events, "timed": ms.event_times is not None, "clock": ms._has_clock,
+                "trim": ms.continuous and ms._has_clock}
 
     # the checks of open / open_events: methods of their own, because they come before those of the recording's tensors
     def check_capacities(self, ms, who, event_capacity, capacity):
@@ -324,10 +339,28 @@ class EventStream(Part):
     def check_spans(self, ms, who, spans, L=None):
         """spans (or None) -> a validated [L,2] float64 table on the host (or None); L None: only that the session takes spans."""
         if spans is None:
+            if ms.continuous:
+                raise ValueError("MultiStreamSR.%s: a continuous session needs spans / lr_ts of every recording (there is no "
+                                 "clock to cut on)" % who)
             return None
         if ms.event_times is None:
             raise ValueError("MultiStreamSR.%s: spans / lr_ts need a session with event_times='linear'" % who)
-        return spans if L is None else check_spans("MultiStreamSR.%s: " % who, spans, L)
+        if L is None:
+            return spans
+        spans = check_spans("MultiStreamSR.%s: " % who, spans, L)
+        if ms.continuous and (np.diff(spans[1:L - ms.seqn + 2, 0]) < 0).any():      # windows 0 .. n-1 predict items 1 .. n
+            raise ValueError("MultiStreamSR.%s: a continuous session needs spans whose t_first does not decrease over the "
+                             "items the windows predict" % who)
+        return spans
+
+    @staticmethod
+    def cuts(spans, n):
+        """[n] float64: the cut of every window of a recording with these spans -- window i predicts item i+1 and is cut at
+        spans[i+2][0], the start of the item the next window predicts; the last window (or i+2 >= L) at +inf."""
+        cuts = np.full(n, np.inf)
+        k = max(min(n - 1, len(spans) - 2), 0)
+        cuts[:k] = spans[2:2 + k, 0]
+        return cuts
 
     def room(self, ms, who, H, W, event_capacity, window_event_capacity, total, busiest):
         """What an emitting session needs of a recording of H x W frames: coordinates in int16, and the two capacities (defaults:
@@ -354,6 +387,8 @@ class EventStream(Part):
             rec.update(ev_ts=column(F32 if spans is None else torch.float64), win_capacity=int(window_event_capacity))
             if spans is not None:                          # a clocked recording: float64 times on its own clock
                 rec["spans"] = spans
+            if ms.continuous:                              # (its spans were demanded at the door) the cuts, the dropped counts
+                rec.update(cuts=self.cuts(spans, rec["n"]), ev_dropped=torch.zeros(rec["n"], dtype=torch.int64, device=device))
 
     def grew(self, ms, rec):
         clock, room = "spans" in rec and not ms._has_clock, rec.get("win_capacity", 0) > ms._wcap
@@ -364,7 +399,8 @@ class EventStream(Part):
     def scratch(self, ms):
         if not ms.emit_events:
             return {}
-        d = {"emit_parts": ((ms.S * ms._nparts,), I32, 0, False)}        # (scratch_bytes() never counted the count launch's totals)
+        words = stream_lib.TRIM_PARTS if ms.continuous else 1             # (a trimmed count launch: kept and dropped totals)
+        d = {"emit_parts": ((words * ms.S * ms._nparts,), I32, 0, False)}  # (scratch_bytes() never counted the count launch's totals)
         if ms._wcap:
             d["emit_scratch"] = ((slots.emit_timed_scratch_bytes(ms.S, ms._nparts, ms._wcap),), U8, None, True)
         return d
@@ -380,12 +416,15 @@ class EventStream(Part):
             ck = v["clock"][s]
             ck["t_first"], ck["t_last"] = r["spans"][i + 1]
             ck["ts"] = r["ev_ts"].data_ptr()
+            if "cuts" in r:                                # a continuous session: the events before the next window's item
+                tr = v["trim"][s]
+                tr["t_cut"], tr["dropped"] = r["cuts"][i], r["ev_dropped"].data_ptr() + 8 * i
         elif "ev_ts" in r:
             em["ts"] = r["ev_ts"].data_ptr()
 
     def launch(self, ms, b, pred):
         if ms.event_times is not None:
-            emit = slots.emit_clocked if ms._has_clock else slots.emit_timed
+            emit = slots.emit_trimmed if ms.continuous else slots.emit_clocked if ms._has_clock else slots.emit_timed
             emit(b["table"], pred, ms.max_count, ms._nparts, b["emit_parts"], b["emit_scratch"], ms._wcap)
         elif ms.emit_events:
             slots.emit(b["table"], pred, ms.max_count, ms._nparts, b["emit_parts"])
@@ -406,6 +445,8 @@ class EventStream(Part):
                                    "window_event_capacity of %d: open it with window_event_capacity >= %d"
                                    % (handle, most, r["win_capacity"], most))
             out["sr_ts"] = r["ev_ts"][:total]
+        if "ev_dropped" in r:
+            out["sr_dropped"] = r["ev_dropped"][:done].tolist()
         out["sr_events"] = (r["ev_xs"][:total], r["ev_ys"][:total], r["ev_ps"][:total])
         out["sr_index"] = index
 

@@ -47,7 +47,7 @@ with the event output (nothing is run: the buffers are allocated when a recordin
 
 python tools/multistream_infer.py [--sizes 31x56,45x80,180x240] [--slots 1,8,32] [--windows 8] [--warmup 4] [--events]
                                   [--hot-filter] [--noise-filter DT[:K]] [--from-hr [T]] [--runs 3]
-                                  [--emit-events] [--event-times] [--sensor-clock] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
+                                  [--emit-events] [--event-times] [--sensor-clock] [--continuous] [--no-gt] [--resident-windows N] [--modes eager,graph] [--out FILE]
                                   [--render DIR] [--render-kinds lr,bicubic,esr,gt] [--voxel-bins B]
                                   [--self-ensemble K] [--plain-weights NPZ] [--quality [RANGE]]"""
 import argparse
@@ -245,22 +245,24 @@ def write_images(root, name, images):
             Image.fromarray(img, "RGB").save(os.path.join(d, "%09d.png" % i))
 
 
-def sensor_spans(L, k):
-    """Synthetic monotone float64 stamps of recording k: microseconds around 1e9, frame j spans [33 333 j, 33 333 j + 33 332]."""
+def sensor_spans(L, k, overlap=False):
+    """Synthetic monotone float64 stamps of recording k: microseconds around 1e9, frame j spans [33 333 j, 33 333 j + 33 332];
+    overlap: [33 333 j, 33 333 (j + 2) - 1] -- consecutive frames overlap by half, as the reference's blocks of 2 048 events
+    that advance by 1 024."""
     import numpy as np
     t0 = 1e9 + 1e7 * k + 33333.0 * np.arange(L, dtype=np.float64)
-    return np.stack([t0, t0 + 33332.0], 1)
+    return np.stack([t0, t0 + (66665.0 if overlap else 33332.0)], 1)
 
 
 def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, event_times=None, no_gt=False, clock=False,
-                hot_filter=None, render=None, render_dir=None, voxel_bins=None, quality=None):
+                hot_filter=None, render=None, render_dir=None, voxel_bins=None, quality=None, overlap=False, continuous=False):
     ms = MultiStreamSR(m, S, n_c=128, scale=4, graph=graph, seqn=SEQN, emit_events=emit, event_times=event_times,
-                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, quality=quality)
+                       hot_filter=hot_filter, render=render, voxel_bins=voxel_bins, quality=quality, continuous=continuous)
     if events:
         dev = next(m.parameters()).device
         hs = [ms.open_events(tuple(t.to(dev) for t in r[0]), tuple(t.to(dev) for t in r[1]), *r[2:]) for r in recs[:S]]
     else:
-        hs = [ms.open(f, None if no_gt else g, spans=sensor_spans(len(f), k) if clock else None)
+        hs = [ms.open(f, None if no_gt else g, spans=sensor_spans(len(f), k, overlap) if clock else None)
               for k, (f, g) in enumerate(recs[:S])]
     for _ in range(warmup):
         ms.step()
@@ -272,10 +274,13 @@ def multistream(m, recs, S, graph, warmup, windows, events=False, emit=False, ev
     wall = time.perf_counter() - t0
     lat = statistics.median(ms.results(hs[0])["time"][warmup:])
     if emit:
-        index = ms.results(hs[0])["sr_index"]
+        res = ms.results(hs[0])
+        index = res["sr_index"]
         dense = MultiStreamSR(m, S, n_c=128, scale=4, seqn=SEQN, keep_predictions=True)
+        stream = dict(events=int(index[-1]), dropped=sum(res.get("sr_dropped", ())), windows=len(index) - 1,      # of recording 0
+                      sr_bytes=int(index[-1]) * sum(t.element_size() for t in res["sr_events"] + ((res["sr_ts"],) if "sr_ts" in res else ())))
         return (lat, S * windows / wall, part_alone(ms, EventStream), int(index[-1] - index[-2]), ms.resident_bytes(hs[0]),
-                dense.resident_bytes(dense.open(*recs[0])))
+                dense.resident_bytes(dense.open(*recs[0])), stream)
     if render:
         if render_dir:
             for k, h in enumerate(hs):
@@ -362,6 +367,10 @@ def parse_args(argv=None):
                     help="with --emit-events: the timed, time-ordered stream (MultiStreamSR(event_times='linear'))")
     ap.add_argument("--sensor-clock", action="store_true",
                     help="implies --emit-events --event-times: float64 times on a synthetic sensor clock (spans= at open)")
+    ap.add_argument("--continuous", action="store_true",
+                    help="implies --sensor-clock: the synthetic spans overlap by half and the emitting session runs twice in this "
+                         "process, with MultiStreamSR(continuous=True) and without -- window time and the six emit launches "
+                         "alone of both, events kept / dropped and bytes of sr_* of a recording")
     ap.add_argument("--no-gt", action="store_true", help="adds the session on recordings without ground truth")
     ap.add_argument("--resident-windows", type=int, default=0)
     ap.add_argument("--modes", default="eager,graph")
@@ -400,6 +409,8 @@ def parse_args(argv=None):
             a.render_kinds = MultiStreamSR.check_render("--render-kinds: ", tuple(("lr,bicubic,esr,gt" if a.render_kinds is None else a.render_kinds).split(",")))
         except ValueError as e:
             ap.error(str(e))
+    if a.continuous:
+        a.sensor_clock = True
     if a.sensor_clock:
         a.emit_events = a.event_times = True
     if a.noise_filter is not None:
@@ -433,7 +444,7 @@ def main():
                 p.copy_(torch.from_numpy(z["p/" + name]))
         em.to(dev)
     rows = []
-    L = a.warmup + a.windows + SEQN - 1
+    L = a.warmup + a.windows + SEQN - 1 + int(a.continuous)   # (--continuous: one window more, so that every timed window has a cut)
     for size in a.sizes.split(","):
         H, W = (int(v) for v in size.split("x"))
         g = torch.Generator().manual_seed(H * W)
@@ -576,13 +587,19 @@ def main():
                                      windows_per_s=round(wps, 1), resident_bytes=nbytes))
                     print(json.dumps(rows[-1]), flush=True)
                 if a.emit_events:
-                    lat, wps, emi, nev, nbytes, dense = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True,
-                                                                    event_times="linear" if a.event_times else None,
-                                                                    clock=a.sensor_clock)
+                    lat, wps, emi, nev, nbytes, dense, stream = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True,
+                                                                            event_times="linear" if a.event_times else None,
+                                                                            clock=a.sensor_clock, overlap=a.continuous)
                     rows.append(dict(size=size, mode=mode, runner="MultiStreamSR(emit, clocked)" if a.sensor_clock else
                                      "MultiStreamSR(emit, timed)" if a.event_times else "MultiStreamSR(emit)", slots=S, ms_per_window=round(lat, 3),
                                      windows_per_s=round(wps, 1), emit_ms=round(emi, 4), emit_share=round(emi / lat, 4),
                                      events_last_window=nev, resident_bytes=nbytes, resident_bytes_dense=dense))
+                    if a.continuous:                       # the same spans with the option on, in this process
+                        on = multistream(m, recs, S, graph, a.warmup, a.windows, emit=True, event_times="linear", clock=True,
+                                         overlap=True, continuous=True)
+                        rows[-1].update(runner="MultiStreamSR(emit, clocked | continuous)", ms_per_window_continuous=round(on[0], 3),
+                                        windows_per_s_continuous=round(on[1], 1), emit_ms_continuous=round(on[2], 4),
+                                        recording0_off=stream, recording0_continuous=on[6])
                     print(json.dumps(rows[-1]), flush=True)
                 torch.cuda.empty_cache()
     if a.out:
