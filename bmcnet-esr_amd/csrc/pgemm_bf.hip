@@ -302,6 +302,8 @@ __global__ __launch_bounds__(512, 1) void pgemm_bf_kernel(const PgemmK a) {
 // One barrier per tile; the producers' VALU / LDS-write / VMEM work runs beside the consumers' MFMAs.
 // LDS: A image [64 px][128 ch] bf16 in 256-byte rows, 64-byte chunks XOR-swizzled by (row & 3) (no padding, so that two
 // images fit); X image [108 halo px][32 ch] in 64-byte rows.
+template <int N>
+__device__ __forceinline__ void staged_wait() { dma_wait<N>(); __builtin_amdgcn_sched_barrier(0); }   // (why: at its first use below)
 template <bool TAB>
 __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
     constexpr int NP = 3, HWD = PT_W + 2, HHT = PT_H + 2, NHALO = HWD * HHT, XCH = 32, XQ = XCH / 4;
@@ -393,8 +395,9 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
         };
         // Loads are inline asm, waited for by hand (the compiler cannot count vmcnt across this loop).  Hazard of the
         // idiom: the compiler believes the register is written AT the asm; were it ever to copy the value elsewhere before
-        // the wait (it does not: the `+v` pin after the wait keeps def and use in one register), the copy would be stale --
-        // the parity tests would show garbage, not a small error.  The common case
+        // the wait, the copy would be stale whenever the load is late.  It did, for the 8 A items: staged_wait below holds
+        // every such copy behind the wait (checked in the assembly: nothing reads a staged register between its load and
+        // its wait).  The common case
         // costs no VALU: uniform base (SGPR pair) + the item's 32-bit byte offset.  (s_nop 4: the scalar base may have been produced
         // by a VALU readfirstlane; 5 wait states are required before VMEM uses it and inline asm is opaque to the hazard pass.)
         auto load_item = [&](const TileP& t, int it) {
@@ -446,6 +449,10 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
                 }
             }
         };
+        // The wait is followed by a scheduling barrier: the copy that the compiler makes of a staged register for the `+v` pin
+        // in store_item has no operand in common with the s_waitcnt, and the machine scheduler did hoist it above the wait
+        // (v_mov_b64 of the load's destination, then s_waitcnt vmcnt(11)): the copy was taken a whole tile after the load was
+        // issued, so it was stale only when a load was that late -- two runs of one launch then differed, once in thousands.
         // Rotating pipeline, one item at a time: wait for the OLDEST outstanding load (item `it` of tile i+1, issued one
         // whole iteration ago), split + store it into image (i+1) & 1, and reissue the same registers for tile i+2: every
         // load has a full iteration to land, with one tile's worth of staging registers.
@@ -453,7 +460,7 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
             const TileP t0 = tile_setup(0);
 #pragma unroll
             for (int it = 0; it < NIT; ++it) load_item(t0, it);
-            dma_wait<0>();
+            staged_wait<0>();
 #pragma unroll
             for (int it = 0; it < NIT; ++it) store_item(it, 0);
             const TileP t1 = tile_setup(1);
@@ -466,7 +473,7 @@ __global__ __launch_bounds__(768, 1) void pgemm_bf9x3_kernel(const PgemmK a) {
                 const TileP t2 = tile_setup(i + 2);
 #pragma unroll
                 for (int it = 0; it < NIT; ++it) {
-                    dma_wait<NIT - 1>();
+                    staged_wait<NIT - 1>();
                     store_item(it, (i + 1) & 1);             // image (i+1)&1 was last read for tile i-1: barrier passed
                     load_item(t2, it);
                 }

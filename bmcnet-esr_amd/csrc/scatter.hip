@@ -234,7 +234,10 @@ int launch_binned(const EV& ev, const long long* offsets, long long nevents, int
 //   scan    : exclusive prefix sum over the pixels of a frame (one workgroup per frame) -> segment offsets;
 //   fill    : every event drops its index into its pixel's segment (arrival order, arbitrary);
 //   reduce  : one thread per pixel sorts its segment by event index (segments are a handful of events) and sums the
-//             bins' weights in that order.
+//             bins' weights in that order, every product rounded where the reference's tensor expressions round it (no
+//             fused multiply-add): the reference's bytes at any bin count and for arbitrary float weights
+//             (tests/test_gpu_voxel_bins.py; t * (bins - 1) is exact only where bins - 1 is a power of two, p * weight
+//             only for p = +-1).
 __device__ __forceinline__ int voxel_pixel(float x, float y, int H, int W, bool& oob) {
     oob = (x >= (float)W) | (x < 0.f) | (y >= (float)H) | (y < 0.f);
     if (oob) { x = 0.f; y = 0.f; }
@@ -308,6 +311,8 @@ __global__ __launch_bounds__(1024) void voxel_sort_long_kernel(const long long* 
 __global__ void voxel_reduce_kernel(float* __restrict__ xs, float* __restrict__ ys, const float* __restrict__ ts,
                                     const float* __restrict__ ps, const long long* __restrict__ offsets, int bins, int H, int W,
                                     const int* __restrict__ seg, int* __restrict__ idx, float* __restrict__ out, int mutate) {
+#pragma clang fp contract(off)      // the reference rounds t * (bins - 1) (:280) and p * weight (:284) before they are subtracted from /
+                                    // added to: fused, the grid differs wherever bins - 1 is no power of two or p is not +-1
     const int f = blockIdx.y, HW = H * W;
     const long long e0 = offsets[f];
     const int* const sg = seg + (long long)f * (HW + 1);

@@ -415,7 +415,7 @@ def test_scan_lengths_voxel_frames_and_torch_image(H, W):
     xs = np.floor(rng.uniform(-0.2, W + 0.2, n)).astype(np.float32)
     ys = np.floor(rng.uniform(-0.2, H + 0.2, n)).astype(np.float32)
     ts = np.concatenate([np.sort(rng.uniform(0, 1, c)) for c in counts]).astype(np.float32)
-    ps = rng.choice([-1.0, 1.0], n).astype(np.float32)        # polarities, as in this file's other voxel cases
+    ps = rng.choice([-1.0, 1.0], n).astype(np.float32)        # polarities; float weights and other bin counts: test_gpu_voxel_bins.py
     bounds = np.concatenate([[0], np.cumsum(counts)])
     d = [torch.tensor(a, device=dev) for a in (xs, ys, ts, ps)]
     got = ops.events_to_voxel_batched(d[0], d[1], d[2], d[3], torch.tensor(bounds, dtype=torch.int64, device=dev), bins, H, W)
